@@ -1,10 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- LM iterations/s of the MI355X normal-equation engine on the BASELINE.json headline scene.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
         N > 1: one rank per GPU.  Either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
         (RANK / LOCAL_RANK / WORLD_SIZE in the environment), or started plainly: bench.py then starts the N ranks itself
         (torch.distributed.run as a child process, before anything touches a GPU) and exits with their status.
+        --full: also the figures beside the headline, each of which takes work of its own (measured MFMA ceiling, final passes,
+        J'WJ dense mode, second engine, strips scene, CPU baseline).  Without it a run sets up, warms up, times the K steps and
+        prints the line.
+        --dump-outputs DIR: after the timed steps, what the last one returned (DIR/dx.npy, the step; DIR/parameters.npy, the
+        parameter vector after its update), float64.  The scene is generated from a fixed seed: same arguments, same inputs.
 
 A "step" is one intermediate Gauss-Newton/LM pass of BundleAdjustment.estimateModel (BundleAdjustment.java:228-355):
 residual + Jacobian rows, N = A'PA / n = A'Pw, datum/damping/preconditioner, factorisation + substitution, parameter
@@ -13,7 +18,7 @@ update -- inputs resident in HBM when the timed region starts.  Workload at N = 
 control-point block, U = 18 014).  For N > 1 the images are sharded contiguously over the ranks (strong scaling), the
 packed normal equations are summed with one all-reduce (RCCL) and every rank solves the identical system.
 
-One JSON line on stdout (rank 0): metric/value (+ roofline of the dominant kernel + cpu_baseline).
+One JSON line on stdout (rank 0): metric/value (+ roofline of the dominant kernel; with --full + cpu_baseline).
 """
 import argparse
 import json
@@ -27,7 +32,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 FP64_MFMA_PEAK_TFLOPS = 78.6   # AMD's public MI355X fp64 matrix (= fp64 vector) peak; the local microarch guide lists
-                               # no fp64 row.  bench also reports the measured issue-rate ceiling (roofline.peak_measured).
+                               # no fp64 row.  bench --full also reports the measured issue-rate ceiling (roofline.peak_measured).
 
 
 def parse():
@@ -36,11 +41,24 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="cfg4")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline (MFMA ceiling, final passes, dense mode, second engine, strips scene, "
+                         "CPU baseline); the options below narrow it down")
     ap.add_argument("--iterations-only", action="store_true",
-                    help="only the timed LM passes (no final passes, no dense-mode measurement, no CPU baseline): profiling runs")
-    ap.add_argument("--no-dense-mode", action="store_true", help="skip the densified J'WJ MFMA measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: only the timed LM passes and the MFMA ceiling (no final passes, no dense-mode measurement, "
+                         "no CPU baseline): profiling runs")
+    ap.add_argument("--no-dense-mode", action="store_true", help="with --full: skip the densified J'WJ MFMA measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     return ap.parse_args()
+
+
+def dump_outputs(path, arrays):
+    """The arrays a caller of the timed path receives, as float64 .npy files (tens of kB at config 4)."""
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def cpu_baseline(fp, eng, sigma2):
@@ -217,7 +235,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        dx = step()
         for k, v in eng.timings().items():
             stage[k] = stage.get(k, 0.0) + v
     sync()
@@ -226,6 +244,9 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if a.dump_outputs and rank == 0:
+        # the last timed step's dx (identical on every rank) and the parameters it was applied to
+        dump_outputs(a.dump_outputs, {"dx": dx, "parameters": eng.get_parameters()})
     ks = eng.kernel_stats()
     eng.set_profiling(False)
     # health of the dataflow factorisation on EVERY rank (a repeated factorisation costs >= 0.25 s: a line measured with one is flagged)
@@ -283,21 +304,22 @@ def main():
                                         "peak": 8000.0, "unit": "GB/s", "frac": abytes / (asm_ms * 1e-3) / 1e9 / 8000.0 if asm_ms > 0 else 0.0,
                                         "algorithmic_bytes_per_pass": abytes, "stage_ms": asm_ms}
         # measured issue ceiling of v_mfma_f64_16x16x4_f64 on this device (back-to-back independent MFMAs in registers):
-        # constant operands / random operands (the chip is power-limited on fp64 MFMA, the two differ)
-        try:
-            import ctypes as C
-            L = engine.load_library()
-            L.jaicov_debug_mfma_peak.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-            meas = []
-            for iters in (20000, -20000):
-                ms_, tf_ = C.c_double(), C.c_double()
-                L.jaicov_debug_mfma_peak(2048, iters, C.byref(ms_), C.byref(tf_))
-                meas.append(tf_.value)
-            out["roofline"]["peak_measured"] = {"constant_operands": meas[0], "random_operands": meas[1], "unit": "TFLOP/s"}
-            if meas[1] > 0:
-                out["roofline"]["frac_of_measured_peak"] = achieved / meas[1]     # against what the chip sustains on random operands (power-limited)
-        except Exception:
-            pass
+        # constant operands / random operands (the chip is power-limited on fp64 MFMA, the two differ); launches of its own: --full
+        if a.full:
+            try:
+                import ctypes as C
+                L = engine.load_library()
+                L.jaicov_debug_mfma_peak.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+                meas = []
+                for iters in (20000, -20000):
+                    ms_, tf_ = C.c_double(), C.c_double()
+                    L.jaicov_debug_mfma_peak(2048, iters, C.byref(ms_), C.byref(tf_))
+                    meas.append(tf_.value)
+                out["roofline"]["peak_measured"] = {"constant_operands": meas[0], "random_operands": meas[1], "unit": "TFLOP/s"}
+                if meas[1] > 0:
+                    out["roofline"]["frac_of_measured_peak"] = achieved / meas[1]     # against what the chip sustains on random operands (power-limited)
+            except Exception:
+                pass
         # registers / spills / scratch of the kernels of the LM pass, from the resource remarks of the build that produced the loaded
         # library (csrc/kernel_resources.json, written by the Makefile)
         try:
@@ -346,7 +368,9 @@ def main():
                                                      "stale_for_this_kernel": stale}
             except Exception:
                 pass
-    if not a.iterations_only:
+    # everything below measures something beside the headline, with runs of its own: only with --full
+    extras = a.full and not a.iterations_only
+    if extras:
         # final pass (BA:252-280): same build, then solve with the full inverse and omega -- reported, not `value`.
         # Run twice: the first call allocates the inverse's buffers (7.8 GB) and builds the tile maps of the full order.
         for rep in range(2):
@@ -394,7 +418,7 @@ def main():
                 out["final_pass_reduced_ms"] = 1e3 * (time.perf_counter() - t2)
                 out["final_pass_reduced_stage_ms"] = eng.timings()
                 out["final_pass_reduced_order"] = eng.cofactor_order()
-    if rank == 0 and world == 1 and not a.no_dense_mode and not a.iterations_only:
+    if rank == 0 and world == 1 and not a.no_dense_mode and extras:
         # BASELINE.json's second figure, "J'WJ MFMA-util%": the jointly dispersed image groups contracted as dense
         # A'(PA) on the fp64 matrix cores (engine option assembly_mode = 1, csrc/densemode.hip).  The default
         # structure-aware assembly computes the same N with ~2 % of the arithmetic; this is the literal form.
@@ -416,7 +440,7 @@ def main():
             "gemm_ms_per_pass": ks2["dense_gemm_ms"], "assembly_ms_per_pass": wall,
             "algorithmic_flops_per_pass": ks2["dense_flops"],
             "structure_aware_assembly_ms_per_pass": out["stage_ms_per_step"].get("assembly")}
-    if rank == 0 and world == 1 and not use_dist and not a.iterations_only:
+    if rank == 0 and world == 1 and not use_dist and extras:
         # engine creation once the process is warm (the first engine above also paid the HIP context, the code objects and the first
         # launch of every kernel): a second engine of the same problem, created and destroyed
         t_c = time.perf_counter()
@@ -424,7 +448,7 @@ def main():
         out["create_ms"]["wall_second_engine"] = 1e3 * (time.perf_counter() - t_c)
         out["create_ms"]["second_engine"] = e2.create_timings()
         e2.close()
-    if rank == 0 and world == 1 and not use_dist and not a.iterations_only and a.config == "cfg4" and not os.environ.get("JAICOV_BENCH_NO_LOCAL_SCENE"):
+    if rank == 0 and world == 1 and not use_dist and extras and a.config == "cfg4" and not os.environ.get("JAICOV_BENCH_NO_LOCAL_SCENE"):
         # The same stage on a scene WITH spatial locality (scene.config("cfg4_local"): config 4's size and stochastic model on a block flown in
         # strips, first-seen numbering -- the shape of real photogrammetric blocks, and of the bundled example): the random-visibility
         # BASELINE scene is the kind case for the point x point gather.  Reported, not `value`.
@@ -448,7 +472,7 @@ def main():
             out["assembly_ms_local_scene"] = None
             out["local_scene"] = {"error": str(ex)}
     if rank == 0:
-        if not a.no_cpu_baseline and not a.iterations_only:
+        if not a.no_cpu_baseline and extras:
             out["cpu_baseline"] = cpu_baseline(fp, eng, s2)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         print(json.dumps(out), flush=True)
