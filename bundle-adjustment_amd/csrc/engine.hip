@@ -18,6 +18,7 @@
 #include "batchinv.h"
 #include "dense.h"
 #include "gemm_f64.h"
+#include "transform.h"
 
 namespace jaicov {
 hipError_t launch_rows(hipStream_t, const DevProblem &, const double *, int, int, double *, double *);
@@ -275,6 +276,7 @@ struct jaicov_engine {
     bool pp_plain_ok = false;   // the point x point gather may store its strips (see PPGather::plain)
     hipEvent_t ev_first = nullptr, ev_all = nullptr;   // solve(): first panel's columns / whole matrix copied into the solver
     hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;       // solve(): device part of a refinement step
+    jaicov::XformState *xform = nullptr;               // result of jaicov_xform_run (transform.hip), kept until the next run / release
 };
 
 #define FAIL(e, code, msg)                 \
@@ -473,6 +475,7 @@ extern "C" void jaicov_neq_destroy(jaicov_engine *e) {
     if (!e) return;
     hipSetDevice(e->device);
     if (e->stream) hipStreamSynchronize(e->stream);
+    jaicov::xform_state_free(e->xform);
     e->solver.release();
     e->solverS.release();
     e->dm.release();
@@ -1855,6 +1858,22 @@ extern "C" int jaicov_neq_get_cofactor(jaicov_engine *e, double *Q_packed, size_
 }
 
 static int cofactor_sub_impl(jaicov_engine *e, const int32_t *idx, int32_t k, double scale, double *out);
+
+// transform.hip reads Qxx, the slot vector and the structure through this view (include/jaicov_transform.h)
+void jaicov::engine_xform_view(jaicov_engine *e, XformView *v) {
+    const DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
+    v->device = e->device;
+    v->stream = e->stream;
+    v->full_q = e->have_Q && !e->q_reduced && e->q_order == e->U;
+    v->Q = qs.Q;
+    v->ld = qs.ld;
+    v->U = e->U;
+    v->d_vals = e->d_vals;
+    v->p = &e->p;
+    v->slot_col = &e->h_slot_col;
+    v->state = &e->xform;
+    v->err = &e->err;
+}
 
 extern "C" int jaicov_neq_get_cofactor_sub(jaicov_engine *e, const int32_t *idx, int32_t k, double *out) {
     return cofactor_sub_impl(e, idx, k, 1.0, out);

@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` (``csrc/libjaicov_neq.so``).
+"""ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` / ``include/jaicov_transform.h``
+(``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
 library has not been built, and every call fails with ``EngineError`` when no gfx950 device is present.
@@ -29,6 +30,13 @@ EXPORTS = [
     "jaicov_neq_set_profiling", "jaicov_neq_kernel_stats", "jaicov_neq_cancel",
     "jaicov_dense_spd_solve_packed", "jaicov_dense_gemm", "jaicov_neq_eo_step_buffer",
     "jaicov_neq_create_timings", "jaicov_neq_get_block_weight", "jaicov_neq_expansion_buffer",
+]
+
+# include/jaicov_transform.h: CoordinateTransformationExteriorOrientation.transform on the device (its own list: EXPORTS is the
+# declarations of jaicov_neq.h + jaicov_dense.h)
+XFORM_EXPORTS = [
+    "jaicov_xform_run", "jaicov_xform_get_coordinates", "jaicov_xform_get_covariance", "jaicov_xform_get_covariance_sub",
+    "jaicov_xform_get_point_blocks", "jaicov_xform_release",
 ]
 
 KROW = 32  # 12 + JAICOV_MAX_DIST_PER_CAMERA
@@ -123,6 +131,12 @@ def load_library():
     L.jaicov_dense_spd_solve_packed.argtypes = [C.c_int32, _pd, _pd, C.c_int32, C.c_int32, _pd]
     L.jaicov_dense_gemm.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, _pd, C.c_int64,
                                     _pd, C.c_int64, C.c_double, _pd, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _pd]
+    L.jaicov_xform_run.argtypes = [vp, _pi, C.c_int32, _pi, _pi, C.c_int32, C.c_double, _pi]
+    L.jaicov_xform_get_coordinates.argtypes = [vp, _pd, _pi, C.c_int32]
+    L.jaicov_xform_get_covariance.argtypes = [vp, _pd, C.c_size_t]
+    L.jaicov_xform_get_covariance_sub.argtypes = [vp, _pi, C.c_int32, _pd]
+    L.jaicov_xform_get_point_blocks.argtypes = [vp, _pd, C.c_int32]
+    L.jaicov_xform_release.argtypes = [vp]
     _LIB = L
     return L
 
@@ -158,6 +172,7 @@ class Engine:
         opts.inverse_refinement = int(inverse_refinement)                   # < 0: no Newton-Schulz step on the inverse of orders <= 8192
         opts.refinement = int(refinement)      # 0 = default (one step of iterative refinement per solve), < 0 = none, k = k steps
         self._h = C.c_void_p()
+        self.xform_count = 0
         rc = self.L.jaicov_neq_create(C.byref(self._desc), C.byref(opts), C.byref(self._h))
         if rc != 0:
             msg = self.L.jaicov_neq_last_error(self._h).decode() if self._h else ""
@@ -280,6 +295,47 @@ class Engine:
         out = np.zeros((idx.size, idx.size))
         self._chk(self.L.jaicov_neq_get_dispersion_sub(self._h, float(sigma2_aposteriori), idx.ctypes.data_as(_pi), idx.size, _p(out)))
         return out
+
+    # coordinate transformation (include/jaicov_transform.h) -----------------------------------------------------------
+    def transform(self, points, pairs, sigma2):
+        """CoordinateTransformationExteriorOrientation.transform on the device: `points` (distinct object point indices, in order),
+        `pairs` ((ref, src) image indices, the reference's Map<Image, List<Image>> flattened in iteration order).  Needs all of Qxx
+        (an inverting solve with INVERT_FULL / INVERT_FULL_EXPANDED).  Returns (xyz (n, 3), ids (n, 3): point, src, ref); the
+        covariance sigma2 J Qxx J' stays on the device (transform_covariance / transform_covariance_sub)."""
+        pts = np.ascontiguousarray(points, np.int32).ravel()
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        ref = np.ascontiguousarray(pr[:, 0]); src = np.ascontiguousarray(pr[:, 1])
+        n = C.c_int32(0)
+        self._chk(self.L.jaicov_xform_run(self._h, pts.ctypes.data_as(_pi), pts.size, ref.ctypes.data_as(_pi), src.ctypes.data_as(_pi),
+                                          ref.size, float(sigma2), C.byref(n)))
+        self.xform_count = n.value
+        xyz = np.zeros((n.value, 3)); ids = np.zeros((n.value, 3), np.int32)
+        self._chk(self.L.jaicov_xform_get_coordinates(self._h, _p(xyz), ids.ctypes.data_as(_pi), n.value))
+        return xyz, ids
+
+    def transform_covariance(self):
+        """The whole covariance of the last transform, packed 'U' of order R = 3 n."""
+        R = 3 * self.xform_count
+        ap = np.zeros(R * (R + 1) // 2)
+        self._chk(self.L.jaicov_xform_get_covariance(self._h, _p(ap), ap.size))
+        return ap
+
+    def transform_covariance_sub(self, rows):
+        """C[rows, rows] of the last transform, gathered on the device (row-major k x k)."""
+        idx = np.ascontiguousarray(rows, np.int32)
+        out = np.zeros((idx.size, idx.size))
+        self._chk(self.L.jaicov_xform_get_covariance_sub(self._h, idx.ctypes.data_as(_pi), idx.size, _p(out)))
+        return out
+
+    def transform_point_blocks(self):
+        """Every 3 x 3 diagonal block of the last transform's covariance in one call: (n, 3, 3)."""
+        out = np.zeros((self.xform_count, 3, 3))
+        self._chk(self.L.jaicov_xform_get_point_blocks(self._h, _p(out), self.xform_count))
+        return out
+
+    def transform_release(self):
+        self._chk(self.L.jaicov_xform_release(self._h))
+        self.xform_count = 0
 
     def get_rows(self, ip_begin, ip_count):
         w = np.zeros((ip_count, 2)); A = np.zeros((ip_count, 2, KROW))

@@ -159,6 +159,7 @@ PYBIND11_MODULE(_jaicov_host, m) {
         .def("getIterations", &BundleAdjustment::getIterations)
         .def("getDatumFlags", [](BundleAdjustment &b) { return b.getRankDefect().flags(); })
         .def("lastError", &BundleAdjustment::lastError)
+        .def("nativeEngineHandle", [](BundleAdjustment &b) { return (uintptr_t)b.nativeEngine(); })
         .def("getObjectCoordinates", [](BundleAdjustment &b) { return b.getObjectCoordinates(); }, py::return_value_policy::reference_internal)
         .def("getCofactorMatrix", [](BundleAdjustment &b) {
             const auto &q = b.getCofactorMatrix();
@@ -197,6 +198,18 @@ PYBIND11_MODULE(_jaicov_host, m) {
         .def(py::init<std::string>())
         .def("toString", &MatlabResultWriter::toString);
     m.def("java_fixed", &java_fixed, "java.util.Formatter %[+].<prec>f");
+
+    py::class_<CoordinateTransformationExteriorOrientation, std::unique_ptr<CoordinateTransformationExteriorOrientation, py::nodelete>>(
+        m, "CoordinateTransformationExteriorOrientation")
+        .def_static("getInstance", &CoordinateTransformationExteriorOrientation::getInstance, py::return_value_policy::reference)
+        .def("transform", &CoordinateTransformationExteriorOrientation::transform, py::arg("objectCoordinatesToTransform"),
+             py::arg("imagesToAlign"), py::arg("sigma2"), py::arg("adjustment"), py::call_guard<py::gil_scoped_release>())
+        .def("getCovarianceMatrix", [](const CoordinateTransformationExteriorOrientation &t) {
+            const auto &v = t.getCovarianceMatrix();
+            return py::array_t<double>((py::ssize_t)v.size(), v.data());
+        })
+        .def("getTransformedCoordinates", &CoordinateTransformationExteriorOrientation::getTransformedCoordinates,
+             py::return_value_policy::reference);
 
     py::class_<AiconProject>(m, "AiconProject")
         .def_property_readonly("camera", [](AiconProject &p) { return p.camera ? p.camera.get() : (p.cameras.empty() ? nullptr : p.cameras[0].get()); },

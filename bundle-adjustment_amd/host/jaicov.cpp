@@ -466,4 +466,59 @@ std::vector<double> BundleAdjustment::cofactorSub(const std::vector<int32_t> &id
     return out;
 }
 
+// CTEO:49-121: rows, coordinates and sigma2 J Qxx J' on the device (jaicov_xform_run), the results copied back
+void CoordinateTransformationExteriorOrientation::transform(const std::vector<ObjectCoordinate *> &objectCoordinatesToTransform,
+                                                            const std::vector<std::pair<Image *, std::vector<Image *>>> &imagesToAlign,
+                                                            double sigma2, BundleAdjustment &adjustment) {
+    jaicov_engine *e = adjustment.nativeEngine();
+    if (!e) throw std::runtime_error("no cofactor matrix: run estimateModel with MatrixInversion.FULL first");
+    auto &ocs = adjustment.getObjectCoordinates();
+    std::vector<int32_t> points, ref, src;
+    std::vector<ObjectCoordinate *> byIndex(ocs.size(), nullptr);
+    for (auto *oc : objectCoordinatesToTransform) {
+        if (!oc || oc->index < 0 || oc->index >= (int)ocs.size() || ocs[oc->index] != oc)
+            throw std::invalid_argument("object coordinate is not part of this adjustment");
+        points.push_back(oc->index);
+        byIndex[oc->index] = oc;
+    }
+    std::vector<Image *> images;
+    for (auto *c : adjustment.getCameras())
+        for (auto &im : c->images()) images.push_back(im.get());
+    auto imageIndex = [&](Image *im) {
+        if (!im || im->index < 0 || im->index >= (int)images.size() || images[im->index] != im)
+            throw std::invalid_argument("image is not part of this adjustment");
+        return im->index;
+    };
+    for (auto &entry : imagesToAlign)
+        for (Image *im : entry.second) { ref.push_back(imageIndex(entry.first)); src.push_back(imageIndex(im)); }
+    int32_t n = 0;
+    int rc = jaicov_xform_run(e, points.data(), (int32_t)points.size(), ref.data(), src.data(), (int32_t)ref.size(), sigma2, &n);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_xform_run: ") + jaicov_neq_last_error(e));
+    std::vector<double> xyz(3 * (size_t)n), vals(jaicov_neq_num_slots(e));
+    std::vector<int32_t> ids(3 * (size_t)n);
+    rc = jaicov_xform_get_coordinates(e, xyz.data(), ids.data(), n);
+    if (rc == JAICOV_OK) rc = jaicov_neq_get_parameters(e, vals.data(), vals.size());
+    const size_t R = 3 * (size_t)n;
+    std::vector<double> cov(R * (R + 1) / 2);
+    if (rc == JAICOV_OK) rc = jaicov_xform_get_covariance(e, cov.data(), cov.size());
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_xform: ") + jaicov_neq_last_error(e));
+    transformed_.clear();
+    for (int32_t t = 0; t < n; t++) {
+        ObjectCoordinate *oc = byIndex[ids[3 * t]];
+        const int32_t p = ids[3 * t];
+        // the engine's values may be centred (BA:115-201); the shift of the point moves the transformed point by the same amount
+        const double sh[3] = {oc->getX().getValue() - vals[3 * (size_t)p], oc->getY().getValue() - vals[3 * (size_t)p + 1],
+                              oc->getZ().getValue() - vals[3 * (size_t)p + 2]};
+        const std::string name = oc->getName() + " " + std::to_string(images[ids[3 * t + 1]]->getId()) + " " +
+                                 std::to_string(images[ids[3 * t + 2]]->getId());
+        const bool same = ids[3 * t + 1] == ids[3 * t + 2];
+        auto tc = std::make_unique<ObjectCoordinate>(name, same ? oc->getX().getValue() : xyz[3 * (size_t)t] + sh[0],
+                                                     same ? oc->getY().getValue() : xyz[3 * (size_t)t + 1] + sh[1],
+                                                     same ? oc->getZ().getValue() : xyz[3 * (size_t)t + 2] + sh[2]);
+        tc->getX().setColumn(3 * t); tc->getY().setColumn(3 * t + 1); tc->getZ().setColumn(3 * t + 2);   // CTEO:154-157, 254-256
+        transformed_.push_back(std::move(tc));
+    }
+    covariance_ = std::move(cov);
+}
+
 }  // namespace jaicov::host

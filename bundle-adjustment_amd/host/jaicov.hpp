@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/jaicov_neq.h"
+#include "../../include/jaicov_transform.h"
 
 namespace jaicov::host {
 
@@ -489,6 +490,7 @@ public:
     // scale * Qxx[idx, idx], row-major k x k, gathered on the device (jaicov_neq_get_dispersion_sub)
     std::vector<double> cofactorSub(const std::vector<int32_t> &idx, double scale = 1.0) const;
     const std::string &lastError() const { return lastError_; }
+    jaicov_engine *nativeEngine() const { return engine_; }     // the engine of the last estimateModel (null before)
 
     // ---- index contract -----------------------------------------------------------------------------------
     void prepareUnknownParameters();          // BA:667-782
@@ -543,6 +545,34 @@ private:
     AdjustmentResultWritable *resultWriter_ = nullptr;
     std::string lastError_;
     jaicov_engine *engine_ = nullptr;
+};
+
+// adjustment/bundle/tranformation/CoordinateTransformationExteriorOrientation.java (CTEO) on the device (include/jaicov_transform.h).
+// transform() takes the BundleAdjustment whose engine holds Qxx in place of the reference's CoVar; it needs MatrixInversion.FULL.
+// imagesToAlign is the reference's Map<Image, ArrayList<Image>> in iteration order.  The coordinates are in the frame of the objects'
+// values (the engine's values plus the centroid shift when estimateModel centred them, BA:115-201: a translation moves X_T by the
+// same shift); the covariance is sigma2 J Qxx J' packed 'U', copied to the host once per transform (a host that needs only blocks
+// uses jaicov_xform_get_covariance_sub on nativeEngine()).  A fixed parameter contributes no column (the reference throws).
+class CoordinateTransformationExteriorOrientation {
+public:
+    static CoordinateTransformationExteriorOrientation &getInstance() {                // CTEO:45-47
+        static CoordinateTransformationExteriorOrientation trans;
+        return trans;
+    }
+    CoordinateTransformationExteriorOrientation(const CoordinateTransformationExteriorOrientation &) = delete;
+    CoordinateTransformationExteriorOrientation &operator=(const CoordinateTransformationExteriorOrientation &) = delete;
+    void transform(const std::vector<ObjectCoordinate *> &objectCoordinatesToTransform,
+                   const std::vector<std::pair<Image *, std::vector<Image *>>> &imagesToAlign, double sigma2, BundleAdjustment &adjustment);
+    const std::vector<double> &getCovarianceMatrix() const { return covariance_; }     // CTEO:123-125 (UpperSymmPackMatrix.getData())
+    std::vector<ObjectCoordinate *> getTransformedCoordinates() const {               // CTEO:127-129, named "<point> <image id> <reference id>"
+        std::vector<ObjectCoordinate *> v;
+        for (auto &c : transformed_) v.push_back(c.get());
+        return v;
+    }
+private:
+    CoordinateTransformationExteriorOrientation() = default;
+    std::vector<std::unique_ptr<ObjectCoordinate>> transformed_;
+    std::vector<double> covariance_;
 };
 
 }  // namespace jaicov::host

@@ -1,5 +1,5 @@
 /*
- * JNI shim between NativeNormalEquationEngine (Java) and the C ABI of include/jaicov_neq.h.
+ * JNI shim between NativeNormalEquationEngine (Java) and the C ABI of include/jaicov_neq.h and include/jaicov_transform.h.
  * The build image has no JDK, so this file is not built by __graft_entry__.build(); on a box with a JDK:
  *   gcc -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -I../../include jaicov_jni.c \
  *       -L../../bundle-adjustment_amd/csrc -ljaicov_neq -o libjaicov_jni.so
@@ -19,6 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "jaicov_neq.h"
+#include "jaicov_transform.h"
 
 #define ENG(h) ((jaicov_engine *)(intptr_t)(h))
 #define NAT(name) Java_org_applied_1geodesy_adjustment_bundle_nativeengine_NativeNormalEquationEngine_##name
@@ -412,3 +413,80 @@ JNIEXPORT jint JNICALL NAT(estimate)(JNIEnv *e, jclass k, jlong h, jint maxItera
 }
 /* BundleAdjustment.interrupt() (BA:1455): callable from another Java thread while estimate() runs */
 JNIEXPORT jint JNICALL NAT(cancel)(JNIEnv *e, jclass k, jlong h) { (void)e; (void)k; return jaicov_neq_cancel(ENG(h)); }
+
+/* --- include/jaicov_transform.h: CoordinateTransformationExteriorOrientation.transform on the device ------------------------- */
+/* the index arrays are small: copies (Get/ReleaseIntArrayElements with JNI_ABORT); count[0] = transformed points */
+JNIEXPORT jint JNICALL NAT(xformRun)(JNIEnv *e, jclass k, jlong h, jintArray points, jintArray pairRef, jintArray pairSrc, jdouble sigma2,
+                                      jlongArray count) {
+    (void)k;
+    const jsize np = (*e)->GetArrayLength(e, points), nr = (*e)->GetArrayLength(e, pairRef);
+    if ((*e)->GetArrayLength(e, pairSrc) != nr || (*e)->GetArrayLength(e, count) < 1) return JAICOV_ERR_BAD_ARGUMENT;
+    jint *pp = (*e)->GetIntArrayElements(e, points, NULL);
+    jint *pr = pp ? (*e)->GetIntArrayElements(e, pairRef, NULL) : NULL;
+    jint *ps = pr ? (*e)->GetIntArrayElements(e, pairSrc, NULL) : NULL;
+    int rc = JAICOV_ERR_OUT_OF_MEMORY;
+    int32_t n = 0;
+    if (ps) rc = jaicov_xform_run(ENG(h), (const int32_t *)pp, (int32_t)np, (const int32_t *)pr, (const int32_t *)ps, (int32_t)nr, sigma2, &n);
+    if (ps) (*e)->ReleaseIntArrayElements(e, pairSrc, ps, JNI_ABORT);
+    if (pr) (*e)->ReleaseIntArrayElements(e, pairRef, pr, JNI_ABORT);
+    if (pp) (*e)->ReleaseIntArrayElements(e, points, pp, JNI_ABORT);
+    const jlong v = (jlong)n;
+    if (rc == JAICOV_OK) (*e)->SetLongArrayRegion(e, count, 0, 1, &v);
+    return rc;
+}
+/* xyz: 3 n doubles, ids: 3 n longs (point, src, ref) -- through malloc'd copies and Set<Type>ArrayRegion (the int ids travel as longs) */
+JNIEXPORT jint JNICALL NAT(xformGetCoordinates)(JNIEnv *e, jclass k, jlong h, jdoubleArray xyz, jlongArray ids) {
+    (void)k;
+    const jsize m = (*e)->GetArrayLength(e, xyz);
+    if (m % 3 != 0 || (*e)->GetArrayLength(e, ids) != m) return JAICOV_ERR_BAD_ARGUMENT;
+    double *px = (double *)malloc(sizeof(double) * (size_t)(m > 0 ? m : 1));
+    int32_t *pi = (int32_t *)malloc(sizeof(int32_t) * (size_t)(m > 0 ? m : 1));
+    jlong *pl = (jlong *)malloc(sizeof(jlong) * (size_t)(m > 0 ? m : 1));
+    int rc = JAICOV_ERR_OUT_OF_MEMORY;
+    if (px && pi && pl) {
+        rc = jaicov_xform_get_coordinates(ENG(h), px, pi, (int32_t)(m / 3));
+        if (rc == JAICOV_OK) {
+            for (jsize i = 0; i < m; i++) pl[i] = (jlong)pi[i];
+            (*e)->SetDoubleArrayRegion(e, xyz, 0, m, px);
+            (*e)->SetLongArrayRegion(e, ids, 0, m, pl);
+        }
+    }
+    free(px); free(pi); free(pl);
+    return rc;
+}
+/* the packed covariance: one device-to-host copy into the pinned array (no device compute while it is held) */
+JNIEXPORT jint JNICALL NAT(xformGetCovariance)(JNIEnv *e, jclass k, jlong h, jdoubleArray packed) {
+    (void)k;
+    const jsize n = (*e)->GetArrayLength(e, packed);
+    double *p = (double *)(*e)->GetPrimitiveArrayCritical(e, packed, NULL);
+    if (!p) return JAICOV_ERR_OUT_OF_MEMORY;
+    int rc = jaicov_xform_get_covariance(ENG(h), p, (size_t)n);
+    (*e)->ReleasePrimitiveArrayCritical(e, packed, p, 0);
+    return rc;
+}
+JNIEXPORT jint JNICALL NAT(xformGetCovarianceSub)(JNIEnv *e, jclass k, jlong h, jintArray rows, jdoubleArray out) {
+    (void)k;
+    const jsize n = (*e)->GetArrayLength(e, rows);
+    if ((*e)->GetArrayLength(e, out) < n * n) return JAICOV_ERR_BAD_ARGUMENT;
+    jint *ip = (*e)->GetIntArrayElements(e, rows, NULL);
+    if (!ip) return JAICOV_ERR_OUT_OF_MEMORY;
+    double *p = (double *)(*e)->GetPrimitiveArrayCritical(e, out, NULL);
+    int rc = JAICOV_ERR_OUT_OF_MEMORY;
+    if (p) {
+        rc = jaicov_xform_get_covariance_sub(ENG(h), (const int32_t *)ip, (int32_t)n, p);
+        (*e)->ReleasePrimitiveArrayCritical(e, out, p, 0);
+    }
+    (*e)->ReleaseIntArrayElements(e, rows, ip, JNI_ABORT);
+    return rc;
+}
+JNIEXPORT jint JNICALL NAT(xformGetPointBlocks)(JNIEnv *e, jclass k, jlong h, jdoubleArray out) {
+    (void)k;
+    const jsize m = (*e)->GetArrayLength(e, out);
+    if (m % 9 != 0) return JAICOV_ERR_BAD_ARGUMENT;
+    double *p = (double *)(*e)->GetPrimitiveArrayCritical(e, out, NULL);
+    if (!p) return JAICOV_ERR_OUT_OF_MEMORY;
+    int rc = jaicov_xform_get_point_blocks(ENG(h), p, (int32_t)(m / 9));
+    (*e)->ReleasePrimitiveArrayCritical(e, out, p, 0);
+    return rc;
+}
+JNIEXPORT jint JNICALL NAT(xformRelease)(JNIEnv *e, jclass k, jlong h) { (void)e; (void)k; return jaicov_xform_release(ENG(h)); }

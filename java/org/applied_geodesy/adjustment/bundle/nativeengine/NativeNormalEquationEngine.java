@@ -172,6 +172,43 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 	/** the weight matrix sigma0^2-free inv(D) of jointly dispersed image block `block`, row-major m x m (DOPG:82-86 getWeightMatrix) */
 	public void getBlockWeight(int block, double[] out) { check(getBlockWeight(handle, block, out)); }
 
+	/**
+	 * CoordinateTransformationExteriorOrientation.transform (tranformation/CoordinateTransformationExteriorOrientation.java:49-121) on
+	 * the device, after an inverting solve that left all of Qxx (JAICOV_INVERT_FULL / _FULL_EXPANDED): points = the engine indices of
+	 * the Set in iteration order, pairRef[k] / pairSrc[k] = the Map<Image, ArrayList<Image>> flattened in iteration order.  Returns the
+	 * number of transformed points n (3 n rows); the covariance sigma2 J Qxx J' stays on the device (include/jaicov_transform.h).
+	 */
+	public int transform(int[] points, int[] pairRef, int[] pairSrc, double sigma2) {
+		if (pairRef.length != pairSrc.length) throw new IllegalArgumentException("pairRef and pairSrc differ in length");
+		long[] n = new long[1];
+		check(xformRun(handle, points, pairRef, pairSrc, sigma2, n));
+		return (int) n[0];
+	}
+	/** X, Y, Z of the n transformed points (xyz: 3 n) and their (point, src image, ref image) indices (ids: 3 n) */
+	public void getTransformedCoordinates(double[] xyz, long[] ids) { check(xformGetCoordinates(handle, xyz, ids)); }
+	/** the whole covariance, packed 'U' (UpperSymmPackMatrix.getData()) of order R = 3 n: refused when R (R + 1) / 2 exceeds a Java array */
+	public double[] getTransformedCovariance(int n) {
+		long R = 3L * n, len = R * (R + 1) / 2;
+		if (len > Integer.MAX_VALUE - 8) throw new IllegalArgumentException("covariance of order " + R + " exceeds a Java array: use getTransformedCovarianceSub");
+		double[] out = new double[(int) len];
+		check(xformGetCovariance(handle, out));
+		return out;
+	}
+	/** C[rows, rows] as a dense row-major k x k block gathered on the device (e.g. the 3 x 3 diagonal block of one point) */
+	public double[] getTransformedCovarianceSub(int[] rows) {
+		double[] out = new double[rows.length * rows.length];
+		check(xformGetCovarianceSub(handle, rows, out));
+		return out;
+	}
+	/** every 3 x 3 diagonal block (the covariance of each transformed point), 9 n doubles, row-major per block */
+	public double[] getTransformedPointBlocks(int n) {
+		double[] out = new double[9 * n];
+		check(xformGetPointBlocks(handle, out));
+		return out;
+	}
+	/** frees the device result of transform() */
+	public void releaseTransformation() { check(xformRelease(handle)); }
+
 	@Override public void close() { if (handle != 0) { destroy(handle); handle = 0; } }
 
 	private void check(int status) {
@@ -216,4 +253,10 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 	private static native int getDispersionSub(long h, double scale, int[] indices, double[] out);
 	private static native int estimate(long h, int maxIterations, int invert, boolean simulation, double lambda0, double sigma2apriori, double[] result);
 	private static native int cancel(long h);
+	private static native int xformRun(long h, int[] points, int[] pairRef, int[] pairSrc, double sigma2, long[] count);
+	private static native int xformGetCoordinates(long h, double[] xyz, long[] ids);
+	private static native int xformGetCovariance(long h, double[] packed);
+	private static native int xformGetCovarianceSub(long h, int[] rows, double[] out);
+	private static native int xformGetPointBlocks(long h, double[] out);
+	private static native int xformRelease(long h);
 }
