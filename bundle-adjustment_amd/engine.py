@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` / ``include/jaicov_transform.h``
-(``csrc/libjaicov_neq.so``).
+"""ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` / ``include/jaicov_transform.h`` /
+``include/jaicov_dlt.h`` (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
 library has not been built, and every call fails with ``EngineError`` when no gfx950 device is present.
@@ -38,6 +38,13 @@ XFORM_EXPORTS = [
     "jaicov_xform_run", "jaicov_xform_get_coordinates", "jaicov_xform_get_covariance", "jaicov_xform_get_covariance_sub",
     "jaicov_xform_get_point_blocks", "jaicov_xform_release",
 ]
+
+# include/jaicov_dlt.h: DirectLinearTransformation.adjust for a batch of images (stand-alone, no engine)
+DLT_EXPORTS = ["jaicov_dlt_adjust"]
+# jaicov_dlt_restriction (DirectLinearTransformation.RestrictionType, DT:51-58 order) and the per-image status values
+DLT_IDENTICAL_PRINCIPLE_DISTANCE, DLT_ROTATION_WITHOUT_SHEAR, DLT_FIXED_PRINCIPLE_DISTANCE_X, DLT_FIXED_PRINCIPLE_DISTANCE_Y, \
+    DLT_FIXED_PRINCIPAL_POINT_X, DLT_FIXED_PRINCIPAL_POINT_Y = range(6)
+DLT_CONVERGED, DLT_NOT_CONVERGED, DLT_TOO_FEW_POINTS, DLT_SINGULAR, DLT_NOT_FINITE = range(5)
 
 KROW = 32  # 12 + JAICOV_MAX_DIST_PER_CAMERA
 INVERT_NONE, INVERT_FULL, INVERT_REDUCED = 0, 1, 2   # MatrixInversion (BundleAdjustment.java:65-70)
@@ -137,6 +144,7 @@ def load_library():
     L.jaicov_xform_get_covariance_sub.argtypes = [vp, _pi, C.c_int32, _pd]
     L.jaicov_xform_get_point_blocks.argtypes = [vp, _pd, C.c_int32]
     L.jaicov_xform_release.argtypes = [vp]
+    L.jaicov_dlt_adjust.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pi, C.c_int32, C.c_int32, _pd, _pi, _pi, _pd]
     _LIB = L
     return L
 
@@ -401,6 +409,32 @@ def dense_spd_solve_packed(ap, b=None, invert=False):
     if rc != 0:
         raise EngineError(rc, "dense SPD solve")
     return b, ap, float(ms[0])
+
+
+def dlt_adjust(obs_begin, xy, xyz, io, io_fixed=None, restrictions=(), max_iterations=5000, with_time=False):
+    """DirectLinearTransformation.adjust for every image at once (include/jaicov_dlt.h).  obs_begin: (n + 1,) CSR offsets of the
+    images' homologous points; xy: (n_obs, 2) image coordinates; xyz: (n_obs, 3) their control coordinates; io: (n, 3) x0, y0, c;
+    io_fixed: (n, 3) bool or None; restrictions: jaicov_dlt_restriction ids in order (duplicates allowed).  Returns
+    (out (n, 20): b11..b33, x0, y0, c, X0, Y0, Z0, omega, phi, kappa; status (n,); solves (n,)), plus the kernel time in ms with
+    with_time."""
+    L = load_library()
+    ob = np.ascontiguousarray(obs_begin, np.int32).ravel()
+    n = ob.size - 1
+    xy = np.ascontiguousarray(xy, np.float64).reshape(-1)
+    xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1)
+    io = np.ascontiguousarray(io, np.float64).reshape(-1)
+    fx = None if io_fixed is None else np.ascontiguousarray(io_fixed, np.uint8).reshape(-1)
+    rs = np.ascontiguousarray(restrictions, np.int32).ravel()
+    out = np.zeros((max(n, 0), 20)); status = np.zeros(max(n, 0), np.int32); solves = np.zeros(max(n, 0), np.int32)
+    ms = np.zeros(1)
+    _pu8 = C.POINTER(C.c_uint8)
+    rc = L.jaicov_dlt_adjust(n, ob.ctypes.data_as(_pi), _p(xy), _p(xyz), _p(io),
+                             fx.ctypes.data_as(_pu8) if fx is not None else C.cast(None, _pu8),
+                             rs.ctypes.data_as(_pi) if rs.size else C.cast(None, _pi), rs.size, int(max_iterations),
+                             _p(out), status.ctypes.data_as(_pi), solves.ctypes.data_as(_pi), _p(ms))
+    if rc != 0:
+        raise EngineError(rc, "dlt adjust")
+    return (out, status, solves, float(ms[0])) if with_time else (out, status, solves)
 
 
 def dense_gemm(alay, blay, A, B, C_in, M, N, K, alpha=1.0, beta=0.0, lower_only=False, kmode=0, repeats=0):

@@ -211,6 +211,34 @@ PYBIND11_MODULE(_jaicov_host, m) {
         .def("getTransformedCoordinates", &CoordinateTransformationExteriorOrientation::getTransformedCoordinates,
              py::return_value_policy::reference);
 
+    py::class_<DLTCoefficients>(m, "DLTCoefficients")
+        .def(py::init<Image *>(), py::keep_alive<1, 2>())
+        .def("get", &DLTCoefficients::get, py::return_value_policy::reference_internal)
+        .def("getReference", &DLTCoefficients::getReference, py::return_value_policy::reference)
+        .def("values", [](DLTCoefficients &c) {
+            std::vector<double> v;
+            for (int k = 0; k < 20; k++) v.push_back(c.at(k)->getValue());
+            return v;
+        })
+        .def_readonly("status", &DLTCoefficients::status)
+        .def_readonly("solves", &DLTCoefficients::solves);
+    py::class_<DirectLinearTransformation> dlt(m, "DirectLinearTransformation");
+    py::enum_<DirectLinearTransformation::RestrictionType>(dlt, "RestrictionType")
+        .value("IDENTICAL_PRINCIPLE_DISTANCE", DirectLinearTransformation::RestrictionType::IDENTICAL_PRINCIPLE_DISTANCE)
+        .value("ROTATION_WITHOUT_SHEAR", DirectLinearTransformation::RestrictionType::ROTATION_WITHOUT_SHEAR)
+        .value("FIXED_PRINCIPLE_DISTANCE_X", DirectLinearTransformation::RestrictionType::FIXED_PRINCIPLE_DISTANCE_X)
+        .value("FIXED_PRINCIPLE_DISTANCE_Y", DirectLinearTransformation::RestrictionType::FIXED_PRINCIPLE_DISTANCE_Y)
+        .value("FIXED_PRINCIPAL_POINT_X", DirectLinearTransformation::RestrictionType::FIXED_PRINCIPAL_POINT_X)
+        .value("FIXED_PRINCIPAL_POINT_Y", DirectLinearTransformation::RestrictionType::FIXED_PRINCIPAL_POINT_Y);
+    dlt.def_static("adjust", [](DLTCoefficients &c, AiconProject &pr, std::vector<DirectLinearTransformation::RestrictionType> rs) {
+           return DirectLinearTransformation::adjust(c, pr.byName, rs);
+       }, py::arg("coefficients"), py::arg("project"), py::arg("restrictions") = std::vector<DirectLinearTransformation::RestrictionType>{})
+        .def_static("adjustAll", [](std::vector<DLTCoefficients *> cs, AiconProject &pr, std::vector<DirectLinearTransformation::RestrictionType> rs) {
+           return DirectLinearTransformation::adjustAll(cs, pr.byName, rs);
+       }, py::arg("coefficients"), py::arg("project"), py::arg("restrictions") = std::vector<DirectLinearTransformation::RestrictionType>{})
+        .def_static("applyExteriorOrientation", &DirectLinearTransformation::applyExteriorOrientation)
+        .def_static("setMaximalNumberOfIterations", &DirectLinearTransformation::setMaximalNumberOfIterations);
+
     py::class_<AiconProject>(m, "AiconProject")
         .def_property_readonly("camera", [](AiconProject &p) { return p.camera ? p.camera.get() : (p.cameras.empty() ? nullptr : p.cameras[0].get()); },
                                py::return_value_policy::reference_internal)

@@ -521,4 +521,86 @@ void CoordinateTransformationExteriorOrientation::transform(const std::vector<Ob
     covariance_ = std::move(cov);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// DirectLinearTransformation (dlt/DirectLinearTransformation.java) on the device
+// ---------------------------------------------------------------------------------------------------------------
+DLTCoefficients::DLTCoefficients(Image *image) : image_(image) {
+    static const ParameterType order[20] = {
+        ParameterType::DIRECT_LINEAR_TRANSFORMATION_B11, ParameterType::DIRECT_LINEAR_TRANSFORMATION_B12,
+        ParameterType::DIRECT_LINEAR_TRANSFORMATION_B13, ParameterType::DIRECT_LINEAR_TRANSFORMATION_B14,
+        ParameterType::DIRECT_LINEAR_TRANSFORMATION_B21, ParameterType::DIRECT_LINEAR_TRANSFORMATION_B22,
+        ParameterType::DIRECT_LINEAR_TRANSFORMATION_B23, ParameterType::DIRECT_LINEAR_TRANSFORMATION_B24,
+        ParameterType::DIRECT_LINEAR_TRANSFORMATION_B31, ParameterType::DIRECT_LINEAR_TRANSFORMATION_B32,
+        ParameterType::DIRECT_LINEAR_TRANSFORMATION_B33, ParameterType::PRINCIPAL_POINT_X, ParameterType::PRINCIPAL_POINT_Y,
+        ParameterType::PRINCIPAL_DISTANCE, ParameterType::CAMERA_COORDINATE_X, ParameterType::CAMERA_COORDINATE_Y,
+        ParameterType::CAMERA_COORDINATE_Z, ParameterType::CAMERA_OMEGA, ParameterType::CAMERA_PHI, ParameterType::CAMERA_KAPPA};
+    for (ParameterType t : order) p_.emplace_back(new UnknownParameter(t, this));
+}
+
+UnknownParameter &DLTCoefficients::get(ParameterType t) {
+    for (auto &q : p_)
+        if (q->getParameterType() == t) return *q;
+    throw std::invalid_argument("not a DLT parameter");
+}
+
+bool DirectLinearTransformation::adjust(DLTCoefficients &coefficients, const std::map<std::string, ObjectCoordinate *> &objectCoordinates,
+                                        const std::vector<RestrictionType> &restrictions) {
+    return adjustAll({&coefficients}, objectCoordinates, restrictions)[0];
+}
+
+std::vector<bool> DirectLinearTransformation::adjustAll(const std::vector<DLTCoefficients *> &coefficients,
+                                                        const std::map<std::string, ObjectCoordinate *> &objectCoordinates,
+                                                        const std::vector<RestrictionType> &restrictions) {
+    const int n = (int)coefficients.size();
+    std::vector<int32_t> begin(1, 0);
+    std::vector<double> xy, xyz, io;
+    std::vector<uint8_t> fixed;
+    for (DLTCoefficients *co : coefficients) {
+        Image *image = co->getReference();
+        for (auto &ic : image->coordinates()) {                           // DT:78-94: the image's order, the map's coordinates
+            auto it = objectCoordinates.find(ic->getObjectCoordinate()->getName());
+            if (it == objectCoordinates.end()) continue;
+            ObjectCoordinate *oc = it->second;
+            xy.push_back(ic->getX().getValue()); xy.push_back(ic->getY().getValue());
+            xyz.push_back(oc->getX().getValue()); xyz.push_back(oc->getY().getValue()); xyz.push_back(oc->getZ().getValue());
+        }
+        begin.push_back((int32_t)(xy.size() / 2));
+        InteriorOrientation &ior = image->getReference()->getInteriorOrientation();   // DT:304-317
+        UnknownParameter *p[3] = {&ior.getPrinciplePointX(), &ior.getPrinciplePointY(), &ior.getPrincipleDistance()};
+        for (UnknownParameter *q : p) {
+            io.push_back(q->getValue());
+            fixed.push_back(q->getColumn() == COLUMN_FIXED ? 1 : 0);
+        }
+    }
+    std::vector<int32_t> rs;
+    for (RestrictionType r : restrictions) rs.push_back((int32_t)r);
+    std::vector<double> out(20 * (size_t)n);
+    std::vector<int32_t> status(n), solves(n);
+    const int rc = jaicov_dlt_adjust(n, begin.data(), xy.data(), xyz.data(), io.data(), fixed.data(), rs.data(), (int32_t)rs.size(),
+                                     maximalNumberOfIterations_, out.data(), status.data(), solves.data(), nullptr);
+    if (rc != JAICOV_OK) throw std::runtime_error("jaicov_dlt_adjust failed with status " + std::to_string(rc));
+    std::vector<bool> ok(n);
+    for (int g = 0; g < n; g++) {
+        DLTCoefficients *co = coefficients[g];
+        for (int k = 0; k < 20; k++) co->at(k)->setValue(out[20 * (size_t)g + k]);
+        for (int k = 0; k < 3; k++) co->at(11 + k)->setColumn(fixed[3 * (size_t)g + k] ? COLUMN_FIXED : COLUMN_NOT_SET);
+        co->status = status[g];
+        co->solves = solves[g];
+        ok[g] = status[g] == JAICOV_DLT_CONVERGED;
+    }
+    return ok;
+}
+
+void DirectLinearTransformation::applyExteriorOrientation(DLTCoefficients &coefficients, ExteriorOrientation &eo) {
+    const ParameterType t[6] = {ParameterType::CAMERA_COORDINATE_X, ParameterType::CAMERA_COORDINATE_Y, ParameterType::CAMERA_COORDINATE_Z,
+                                ParameterType::CAMERA_OMEGA, ParameterType::CAMERA_PHI, ParameterType::CAMERA_KAPPA};
+    for (int i = 0; i < 5; i++) eo.get(t[i]).setValue(coefficients.get(t[i]).getValue());
+    double kappa = coefficients.get(ParameterType::CAMERA_KAPPA).getValue();
+    if (coefficients.getReference()->getReference()->getInteriorOrientation().getPrincipleDistance().getValue() < 0) {
+        kappa += M_PI;                                                    // Q1: (|c|, kappa + pi) -> (c < 0, kappa)
+        if (kappa > M_PI) kappa -= 2.0 * M_PI;
+    }
+    eo.get(ParameterType::CAMERA_KAPPA).setValue(kappa);
+}
+
 }  // namespace jaicov::host

@@ -27,6 +27,7 @@
 
 #include "../../include/jaicov_neq.h"
 #include "../../include/jaicov_transform.h"
+#include "../../include/jaicov_dlt.h"
 
 namespace jaicov::host {
 
@@ -39,7 +40,11 @@ enum class ParameterType : int {
     CAMERA_COORDINATE_X = 251, CAMERA_COORDINATE_Y = 252, CAMERA_COORDINATE_Z = 253,
     CAMERA_OMEGA = 261, CAMERA_PHI = 262, CAMERA_KAPPA = 263,
     OBJECT_COORDINATE_X = 311, OBJECT_COORDINATE_Y = 312, OBJECT_COORDINATE_Z = 313,
-    IMAGE_COORDINATE_X = 411, IMAGE_COORDINATE_Y = 412, SCALE_BAR_LENGTH = 511
+    IMAGE_COORDINATE_X = 411, IMAGE_COORDINATE_Y = 412, SCALE_BAR_LENGTH = 511,
+    DIRECT_LINEAR_TRANSFORMATION_B11 = 611, DIRECT_LINEAR_TRANSFORMATION_B12 = 612, DIRECT_LINEAR_TRANSFORMATION_B13 = 613,
+    DIRECT_LINEAR_TRANSFORMATION_B14 = 614, DIRECT_LINEAR_TRANSFORMATION_B21 = 621, DIRECT_LINEAR_TRANSFORMATION_B22 = 622,
+    DIRECT_LINEAR_TRANSFORMATION_B23 = 623, DIRECT_LINEAR_TRANSFORMATION_B24 = 624, DIRECT_LINEAR_TRANSFORMATION_B31 = 631,
+    DIRECT_LINEAR_TRANSFORMATION_B32 = 632, DIRECT_LINEAR_TRANSFORMATION_B33 = 633
 };
 
 inline const char *parameterTypeName(ParameterType t) {   // ParameterType.name()
@@ -69,6 +74,17 @@ inline const char *parameterTypeName(ParameterType t) {   // ParameterType.name(
     case ParameterType::IMAGE_COORDINATE_X: return "IMAGE_COORDINATE_X";
     case ParameterType::IMAGE_COORDINATE_Y: return "IMAGE_COORDINATE_Y";
     case ParameterType::SCALE_BAR_LENGTH: return "SCALE_BAR_LENGTH";
+    case ParameterType::DIRECT_LINEAR_TRANSFORMATION_B11: return "DIRECT_LINEAR_TRANSFORMATION_B11";
+    case ParameterType::DIRECT_LINEAR_TRANSFORMATION_B12: return "DIRECT_LINEAR_TRANSFORMATION_B12";
+    case ParameterType::DIRECT_LINEAR_TRANSFORMATION_B13: return "DIRECT_LINEAR_TRANSFORMATION_B13";
+    case ParameterType::DIRECT_LINEAR_TRANSFORMATION_B14: return "DIRECT_LINEAR_TRANSFORMATION_B14";
+    case ParameterType::DIRECT_LINEAR_TRANSFORMATION_B21: return "DIRECT_LINEAR_TRANSFORMATION_B21";
+    case ParameterType::DIRECT_LINEAR_TRANSFORMATION_B22: return "DIRECT_LINEAR_TRANSFORMATION_B22";
+    case ParameterType::DIRECT_LINEAR_TRANSFORMATION_B23: return "DIRECT_LINEAR_TRANSFORMATION_B23";
+    case ParameterType::DIRECT_LINEAR_TRANSFORMATION_B24: return "DIRECT_LINEAR_TRANSFORMATION_B24";
+    case ParameterType::DIRECT_LINEAR_TRANSFORMATION_B31: return "DIRECT_LINEAR_TRANSFORMATION_B31";
+    case ParameterType::DIRECT_LINEAR_TRANSFORMATION_B32: return "DIRECT_LINEAR_TRANSFORMATION_B32";
+    case ParameterType::DIRECT_LINEAR_TRANSFORMATION_B33: return "DIRECT_LINEAR_TRANSFORMATION_B33";
     }
     return "?";
 }
@@ -573,6 +589,47 @@ private:
     CoordinateTransformationExteriorOrientation() = default;
     std::vector<std::unique_ptr<ObjectCoordinate>> transformed_;
     std::vector<double> covariance_;
+};
+
+// dlt/DLTCoefficients.java: the 20 parameters of one image's DLT in the reference's iteration order (b11..b33, x0, y0, c,
+// X0, Y0, Z0, omega, phi, kappa).  status / solves: the device's outcome of the last adjust (include/jaicov_dlt.h, not in the reference).
+class DLTCoefficients {
+public:
+    DLTCoefficients(const DLTCoefficients &) = delete;
+    DLTCoefficients &operator=(const DLTCoefficients &) = delete;
+    explicit DLTCoefficients(Image *image);
+    UnknownParameter &get(ParameterType t);
+    UnknownParameter *at(int i) { return p_[i].get(); }
+    Image *getReference() const { return image_; }
+    int status = -1;
+    int solves = 0;
+private:
+    Image *image_;
+    std::vector<std::unique_ptr<UnknownParameter>> p_;
+};
+
+// dlt/DirectLinearTransformation.java (DT) on the device (include/jaicov_dlt.h).  adjust() keeps the reference's signature and bool
+// result; adjustAll() makes one device call for every image.  Homologous points are selected by name, in each image's order (DT:73-94);
+// the map's X, Y, Z are used.  A device error (no GPU, out of memory) throws std::runtime_error.  The values follow the ABI: Q2 (a fixed
+// x0 / y0 / c comes back as the camera's value) and Q3 (NaN after a failure), see DESIGN.md 6b.
+class DirectLinearTransformation {
+public:
+    enum class RestrictionType {                 // DT:51-58
+        IDENTICAL_PRINCIPLE_DISTANCE, ROTATION_WITHOUT_SHEAR, FIXED_PRINCIPLE_DISTANCE_X, FIXED_PRINCIPLE_DISTANCE_Y,
+        FIXED_PRINCIPAL_POINT_X, FIXED_PRINCIPAL_POINT_Y
+    };
+    static bool adjust(DLTCoefficients &coefficients, const std::map<std::string, ObjectCoordinate *> &objectCoordinates,
+                       const std::vector<RestrictionType> &restrictions = {});
+    static std::vector<bool> adjustAll(const std::vector<DLTCoefficients *> &coefficients,
+                                       const std::map<std::string, ObjectCoordinate *> &objectCoordinates,
+                                       const std::vector<RestrictionType> &restrictions = {});
+    // Start values: X0 .. kappa of an adjusted image into an ExteriorOrientation.  Q1: the DLT's c is always positive, so for a camera
+    // with c < 0 (AICON) kappa + pi (wrapped into (-pi, pi]) is written.  Interior orientation is not touched.
+    static void applyExteriorOrientation(DLTCoefficients &coefficients, ExteriorOrientation &eo);
+    static int getMaximalNumberOfIterations() { return maximalNumberOfIterations_; }
+    static void setMaximalNumberOfIterations(int n) { maximalNumberOfIterations_ = n; }
+private:
+    static inline int maximalNumberOfIterations_ = 5000;     // DefaultValue.getMaximalNumberOfIterations()
 };
 
 }  // namespace jaicov::host

@@ -1,5 +1,6 @@
 /*
- * JNI shim between NativeNormalEquationEngine (Java) and the C ABI of include/jaicov_neq.h and include/jaicov_transform.h.
+ * JNI shim between NativeNormalEquationEngine (Java) and the C ABI of include/jaicov_neq.h, include/jaicov_transform.h and
+ * include/jaicov_dlt.h.
  * The build image has no JDK, so this file is not built by __graft_entry__.build(); on a box with a JDK:
  *   gcc -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -I../../include jaicov_jni.c \
  *       -L../../bundle-adjustment_amd/csrc -ljaicov_neq -o libjaicov_jni.so
@@ -20,6 +21,7 @@
 #include <string.h>
 #include "jaicov_neq.h"
 #include "jaicov_transform.h"
+#include "jaicov_dlt.h"
 
 #define ENG(h) ((jaicov_engine *)(intptr_t)(h))
 #define NAT(name) Java_org_applied_1geodesy_adjustment_bundle_nativeengine_NativeNormalEquationEngine_##name
@@ -490,3 +492,56 @@ JNIEXPORT jint JNICALL NAT(xformGetPointBlocks)(JNIEnv *e, jclass k, jlong h, jd
     return rc;
 }
 JNIEXPORT jint JNICALL NAT(xformRelease)(JNIEnv *e, jclass k, jlong h) { (void)e; (void)k; return jaicov_xform_release(ENG(h)); }
+
+/* --- include/jaicov_dlt.h: DirectLinearTransformation.adjust for a batch of images (no engine) ---------------------------------- */
+/* the inputs are read through Get<Type>ArrayElements copies (JNI_ABORT); out comes back through SetDoubleArrayRegion, status and
+ * solves through long[] (the stub jni.h has no SetIntArrayRegion).  ioFixed (int[], nonzero = fixed) may be null (all free). */
+JNIEXPORT jint JNICALL NAT(dltAdjust)(JNIEnv *e, jclass k, jintArray obsBegin, jdoubleArray xy, jdoubleArray xyz, jdoubleArray io,
+                                      jintArray ioFixed, jintArray restrictions, jint maxIterations, jdoubleArray out, jlongArray status,
+                                      jlongArray solves) {
+    (void)k;
+    const jsize nb = (*e)->GetArrayLength(e, obsBegin);
+    if (nb < 1) return JAICOV_ERR_BAD_ARGUMENT;
+    const jsize n = nb - 1, nr = (*e)->GetArrayLength(e, restrictions);
+    if ((*e)->GetArrayLength(e, io) < 3 * n || (ioFixed && (*e)->GetArrayLength(e, ioFixed) < 3 * n) ||
+        (*e)->GetArrayLength(e, out) < 20 * n || (*e)->GetArrayLength(e, status) < n || (*e)->GetArrayLength(e, solves) < n)
+        return JAICOV_ERR_BAD_ARGUMENT;
+    jint *pb = (*e)->GetIntArrayElements(e, obsBegin, NULL);
+    if (!pb) return JAICOV_ERR_OUT_OF_MEMORY;
+    const jint nobs = pb[n];
+    if (nobs < 0 || (*e)->GetArrayLength(e, xy) < 2 * nobs || (*e)->GetArrayLength(e, xyz) < 3 * nobs) {
+        (*e)->ReleaseIntArrayElements(e, obsBegin, pb, JNI_ABORT);
+        return JAICOV_ERR_BAD_ARGUMENT;
+    }
+    jdouble *pxy = (*e)->GetDoubleArrayElements(e, xy, NULL);
+    jdouble *pxyz = pxy ? (*e)->GetDoubleArrayElements(e, xyz, NULL) : NULL;
+    jdouble *pio = pxyz ? (*e)->GetDoubleArrayElements(e, io, NULL) : NULL;
+    jint *pfx = (pio && ioFixed) ? (*e)->GetIntArrayElements(e, ioFixed, NULL) : NULL;
+    jint *prs = pio ? (*e)->GetIntArrayElements(e, restrictions, NULL) : NULL;
+    double *po = (double *)malloc(sizeof(double) * (size_t)(n > 0 ? 20 * n : 1));
+    int32_t *ps = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n > 0 ? 2 * n : 2));
+    jlong *pl = (jlong *)malloc(sizeof(jlong) * (size_t)(n > 0 ? n : 1));
+    uint8_t *pf = (uint8_t *)malloc((size_t)(n > 0 ? 3 * n : 1));
+    int rc = JAICOV_ERR_OUT_OF_MEMORY;
+    if (prs && (pfx || !ioFixed) && po && ps && pl && pf) {
+        if (pfx)
+            for (jsize i = 0; i < 3 * n; i++) pf[i] = pfx[i] != 0;
+        rc = jaicov_dlt_adjust((int32_t)n, (const int32_t *)pb, pxy, pxyz, pio, pfx ? pf : NULL, (const int32_t *)prs, (int32_t)nr,
+                               (int32_t)maxIterations, po, ps, ps + n, NULL);
+        if (rc == JAICOV_OK) {
+            (*e)->SetDoubleArrayRegion(e, out, 0, 20 * n, po);
+            for (jsize i = 0; i < n; i++) pl[i] = (jlong)ps[i];
+            (*e)->SetLongArrayRegion(e, status, 0, n, pl);
+            for (jsize i = 0; i < n; i++) pl[i] = (jlong)ps[n + i];
+            (*e)->SetLongArrayRegion(e, solves, 0, n, pl);
+        }
+    }
+    free(po); free(ps); free(pl); free(pf);
+    if (prs) (*e)->ReleaseIntArrayElements(e, restrictions, prs, JNI_ABORT);
+    if (pfx) (*e)->ReleaseIntArrayElements(e, ioFixed, pfx, JNI_ABORT);
+    if (pio) (*e)->ReleaseDoubleArrayElements(e, io, pio, JNI_ABORT);
+    if (pxyz) (*e)->ReleaseDoubleArrayElements(e, xyz, pxyz, JNI_ABORT);
+    if (pxy) (*e)->ReleaseDoubleArrayElements(e, xy, pxy, JNI_ABORT);
+    (*e)->ReleaseIntArrayElements(e, obsBegin, pb, JNI_ABORT);
+    return rc;
+}

@@ -209,6 +209,29 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 	/** frees the device result of transform() */
 	public void releaseTransformation() { check(xformRelease(handle)); }
 
+	/** jaicov_dlt status values (include/jaicov_dlt.h) */
+	public static final int DLT_CONVERGED = 0, DLT_NOT_CONVERGED = 1, DLT_TOO_FEW_POINTS = 2, DLT_SINGULAR = 3, DLT_NOT_FINITE = 4;
+
+	/**
+	 * DirectLinearTransformation.adjust (dlt/DirectLinearTransformation.java:67-169) for every image at once, on the device, with no
+	 * engine: obsBegin (n + 1 CSR offsets) selects each image's homologous points, in the image's order (DT:73-94); xy = 2 doubles and
+	 * xyz = 3 doubles per point (the control map's X, Y, Z); io = x0, y0, c per image; ioFixed (may be null) = 1 for a FIXED x0 / y0 / c;
+	 * restrictions = RestrictionType ordinals in the caller's order (duplicates are dropped as DT:269-278 drops them).  out receives the
+	 * 20 DLTCoefficients values per image (b11..b33, x0, y0, c, X0, Y0, Z0, omega, phi, kappa); the result is the status per image
+	 * (DLT_CONVERGED is adjust()'s true).  Quirks Q1-Q3 of include/jaicov_dlt.h apply: for a camera with c < 0 the start value of
+	 * kappa is out[19] + pi.
+	 */
+	public static long[] adjustDLT(int[] obsBegin, double[] xy, double[] xyz, double[] io, int[] ioFixed, int[] restrictions,
+	                               int maxIterations, double[] out) {
+		int n = obsBegin.length - 1;
+		long[] status = new long[Math.max(n, 0)], solves = new long[Math.max(n, 0)];
+		int rc = dltAdjust(obsBegin, xy, xyz, io, ioFixed, restrictions, maxIterations, out, status, solves);
+		if (rc == -1) throw new IllegalArgumentException("jaicov_dlt_adjust: bad argument");
+		if (rc == -4) throw new OutOfMemoryError("jaicov_dlt_adjust");
+		if (rc != 0) throw new IllegalStateException("jaicov_dlt_adjust failed with status " + rc);
+		return status;
+	}
+
 	@Override public void close() { if (handle != 0) { destroy(handle); handle = 0; } }
 
 	private void check(int status) {
@@ -259,4 +282,5 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 	private static native int xformGetCovarianceSub(long h, int[] rows, double[] out);
 	private static native int xformGetPointBlocks(long h, double[] out);
 	private static native int xformRelease(long h);
+	private static native int dltAdjust(int[] obsBegin, double[] xy, double[] xyz, double[] io, int[] ioFixed, int[] restrictions, int maxIterations, double[] out, long[] status, long[] solves);
 }
