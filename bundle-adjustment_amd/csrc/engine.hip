@@ -18,6 +18,7 @@
 #include "batchinv.h"
 #include "dense.h"
 #include "gemm_f64.h"
+#include "reliability.h"
 #include "transform.h"
 
 namespace jaicov {
@@ -277,6 +278,10 @@ struct jaicov_engine {
     hipEvent_t ev_first = nullptr, ev_all = nullptr;   // solve(): first panel's columns / whole matrix copied into the solver
     hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;       // solve(): device part of a refinement step
     jaicov::XformState *xform = nullptr;               // result of jaicov_xform_run (transform.hip), kept until the next run / release
+    jaicov::RelState *rel = nullptr;                   // result of jaicov_rel_run (reliability.hip), kept until the next run / release
+    const double *d_ll_diag = nullptr;                 // [2 n_ip + n_dg_rows]: diag(D) of every image coordinate (engine order) and direct row
+    double sigma2_acc = 0.0;                           // sigma0^2 of the last accumulate
+    double q_sigma2 = 0.0, q_lambda = 0.0;             // sigma0^2 and damping of the build whose system the cofactor matrix inverts
 };
 
 #define FAIL(e, code, msg)                 \
@@ -476,6 +481,7 @@ extern "C" void jaicov_neq_destroy(jaicov_engine *e) {
     hipSetDevice(e->device);
     if (e->stream) hipStreamSynchronize(e->stream);
     jaicov::xform_state_free(e->xform);
+    jaicov::rel_state_free(e->rel);
     e->solver.release();
     e->solverS.release();
     e->dm.release();
@@ -942,6 +948,27 @@ static int create_impl(jaicov_engine *e, const jaicov_problem_desc *D_in, const 
                 p.ip_w3 = d_w3;
             }
             if ((rc = invert_dispersions(e, items))) return rc;
+            // diag(D) of every image coordinate in engine order (the variances, or the diagonal of the block's dispersion), then of every
+            // directly observed row (dg_var, or the diagonal of the group's dispersion): Q_ll of jaicov_rel_run
+            std::vector<double> lld(2 * (size_t)D->n_image_points + D->n_direct_rows);
+            for (int ip = 0; ip < D->n_image_points; ip++) { lld[2 * (size_t)ip] = D->ip_var_x[ip]; lld[2 * (size_t)ip + 1] = D->ip_var_y[ip]; }
+            for (int g : blk_list) {
+                if (D->blk_disp_offset[g] < 0) continue;
+                const int b = D->blk_ip_begin[g];
+                const int64_t m = 2 * (int64_t)(D->blk_ip_begin[g + 1] - b);
+                const double *Dg = D->blk_disp + D->blk_disp_offset[g];
+                for (int ip = b; ip < D->blk_ip_begin[g + 1]; ip++) {
+                    const int64_t lp = perm_local.empty() ? ip - b : perm_local[ip];
+                    for (int c = 0; c < 2; c++) lld[2 * (size_t)ip + c] = Dg[(2 * lp + c) * m + 2 * lp + c];
+                }
+            }
+            for (int g = 0; g < D->n_direct_groups; g++) {
+                const int b = D->dg_row_begin[g], m = D->dg_row_begin[g + 1] - b;
+                const bool dense = D->dg_disp_offset && D->dg_disp_offset[g] >= 0;
+                for (int r = 0; r < m; r++)
+                    lld[2 * (size_t)D->n_image_points + b + r] = dense ? D->dg_disp[D->dg_disp_offset[g] + (int64_t)r * m + r] : D->dg_var[b + r];
+            }
+            if ((rc = upload(e, lld.data(), lld.size(), &e->d_ll_diag))) return rc;
         }
     }
 
@@ -1081,6 +1108,7 @@ extern "C" int jaicov_neq_accumulate(jaicov_engine *e, double sigma2) {
     if (!(sigma2 > 0)) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "variance of unit weight must be positive (DOPG:68-69)");
     HIPE(e, hipSetDevice(e->device));
     e->reduced = false;          // a packed buffer of an earlier accumulate must not be unpacked over this one
+    e->sigma2_acc = sigma2;
     const size_t sq = (size_t)e->Upad * e->Upad;
     HIPE(e, hipEventRecord(e->ev[0], e->stream));
     int rc = ensure_rows(e);
@@ -1713,6 +1741,8 @@ extern "C" int jaicov_neq_solve(jaicov_engine *e, int invert, double *dx_out) {
         HIPE(e, hipEventRecord(e->ev[7], e->stream));
         HIPE(e, hipStreamSynchronize(e->stream));
         e->have_Q = true;
+        e->q_sigma2 = e->sigma2_acc;
+        e->q_lambda = e->lambda_used;
         e->q_reduced = schur && !expand;
         e->q_order = expand ? e->U : U;
     } else {
@@ -1873,6 +1903,31 @@ void jaicov::engine_xform_view(jaicov_engine *e, XformView *v) {
     v->slot_col = &e->h_slot_col;
     v->state = &e->xform;
     v->err = &e->err;
+}
+
+// reliability.hip reads Qxx, the rows and the weights through this view (include/jaicov_reliability.h)
+int jaicov::engine_rel_view(jaicov_engine *e, RelView *v, int rows) {
+    const DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
+    v->device = e->device;
+    v->stream = e->stream;
+    v->full_q = e->have_Q && !e->q_reduced && e->q_order == e->U;
+    v->sharded = !e->all_images || !e->opts.apply_shared || e->ip0 != 0 || e->ip_count != e->p.n_ip;
+    v->Q = qs.Q;
+    v->ld = qs.ld;
+    v->U = e->U;
+    v->sigma2 = e->q_sigma2;
+    v->lambda = e->q_lambda;
+    v->p = &e->p;
+    v->rowsA = e->d_rowsA;
+    v->rowsW = e->d_rowsW;
+    v->d_vals = e->d_vals;
+    v->ll_diag = e->d_ll_diag;
+    v->ip_old2new = &e->ip_old2new;
+    v->blk_ip_begin = &e->h_blk_ip_begin;
+    v->blk_w_off = &e->h_blk_w_off;
+    v->state = &e->rel;
+    v->err = &e->err;
+    return rows ? ensure_rows(e) : JAICOV_OK;
 }
 
 extern "C" int jaicov_neq_get_cofactor_sub(jaicov_engine *e, const int32_t *idx, int32_t k, double *out) {

@@ -1,0 +1,674 @@
+// Redundancy numbers and outlier test values of every observation (include/jaicov_reliability.h), formed next to the cofactor
+// matrix.  gfx950 only.
+//
+//   rel_v_kernel        v = A dx - w of every image coordinate (engine order)
+//   rel_points_kernel   image points with 2 x 2 weights: one workgroup per chunk of <= 64 points of one image, Q[shared, shared] in LDS,
+//                       the 2 x 2 H = A_p Q A_p' of each point in registers, then r, P Q_vv P, q_vv and t
+//   rel_prep_kernel     dense image blocks, per row: y = Q[S, P(row)] a_p and u = y + Q[S, S] a_s (S = the image's shared columns)
+//   rel_pp_kernel       dense image blocks: the point x point part of H = A Q A', one workgroup per pair of 16-point chunks
+//   (gemm_f64)          H += [Y | A_s] [A_s | U]' (the shared-column part of A Q A'), then G = H P on the fp64 matrix cores
+//   rel_pad_kernel      P = sigma0^2 inv(D) of a block, zero-padded to the GEMM's size
+//   rel_block_kernel    dense image blocks: r = 1 - G_ii, (P Q_vv P)_ii = P_ii - sum_j P_ji G_ji, q_vv, (P v)_i, t
+//   rel_scalebar_kernel, rel_direct_kernel   the other observation groups
+//   rel_summary_kernel  sum r, max |t| and its row, NaN count, min r in one workgroup
+//
+// H of a dense block.  A row of image point q has its 3 point columns P(q) and the kc <= 29 shared columns S of the image (IO,
+// distortion, EO).  With a_p, a_s the two parts of a row:
+//   H_rs = a_p(r)' Q[P(r), P(s)] a_p(s) + y(r)' a_s(s) + a_s(r)' u(s),   y(r) = Q[S, P(r)] a_p(r),  u(s) = y(s) + Q[S, S] a_s(s).
+// The first term reads the 3 x 3 point blocks of Q once per pair of chunks (rel_pp_kernel); the rest is a GEMM of inner dimension 2 kc.
+// Every output is one fixed-order sum: two runs give the same bits.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/jaicov_reliability.h"
+#include "gemm_f64.h"
+#include "reliability.h"
+
+namespace jaicov {
+
+constexpr int RL_PTS = 64;                // points per workgroup of rel_points_kernel, rows per workgroup of rel_prep_kernel
+constexpr int RL_TP = 16;                 // points per chunk of rel_pp_kernel
+constexpr int RL_PC = 3 * RL_TP;          // point columns of a chunk (48)
+constexpr int RL_RC = 2 * RL_TP;          // rows of a chunk (32)
+constexpr int RL_K = 64;                  // inner dimension of the shared-column GEMM: [Y | A_s], 2 KC_MAX = 58 padded to 16
+constexpr double RL_UNCONTROLLED = 1e-10; // (P Q_vv P)_ii <= this * P_ii: the observation is not controlled, t = NaN
+static_assert(2 * KC_MAX <= RL_K && RL_K % GEMM_BK == 0, "[Y | A_s] must fit the inner dimension of the shared-column GEMM");
+
+struct RelState {
+    long n_rows = 0;
+    double *d_out = nullptr;              // [4][n_rows]: v, qvv, r, t in the caller's row order
+    double summary[6] = {0, 0, 0, 0, 0, 0};  // rel_summary_kernel's five, then the damping of the build Qxx inverts
+};
+
+void rel_state_free(RelState *s) {
+    if (!s) return;
+    hipFree(s->d_out);
+    delete s;
+}
+
+__device__ __forceinline__ double rl_q(const double *__restrict__ Q, long ld, int i, int j) {
+    return i >= j ? Q[(long)i * ld + j] : Q[(long)j * ld + i];
+}
+// shared local column c (0..kc) -> local row of the compact rows, and its global column (assemble.hip's shared_local / shared_col)
+__device__ __forceinline__ int rl_local(int c) { return c < 3 ? 3 + c : (c < 9 ? 6 + (c - 3) : 12 + (c - 9)); }
+__device__ __forceinline__ int rl_col(const DevProblem &p, int img, int cam, int jb, int c) {
+    return c < 3 ? p.io_col[3 * cam + c] : (c < 9 ? p.eo_col[6 * img + (c - 3)] : p.dist_col[jb + (c - 9)]);
+}
+__device__ __forceinline__ long rl_row(const int32_t *__restrict__ new2old, int ip, int c) {
+    return 2 * (long)(new2old ? new2old[ip] : ip) + c;
+}
+__device__ __forceinline__ double rl_t(double pv, double ppp, double pii, double s2t) {
+    return ppp > RL_UNCONTROLLED * pii ? pv / sqrt(s2t * ppp) : (double)NAN;
+}
+__device__ __forceinline__ void rl_store(double *__restrict__ out, long n_rows, long row, double v, double qvv, double r, double t) {
+    out[row] = v;
+    out[n_rows + row] = qvv;
+    out[2 * n_rows + row] = r;
+    out[3 * n_rows + row] = t;
+}
+
+// v = A dx - w of every image coordinate, engine order: v[2 ip + c]
+__global__ __launch_bounds__(256) void rel_v_kernel(DevProblem p, const double *__restrict__ rowsA, const double *__restrict__ rowsW,
+                                                    const double *__restrict__ dx, double *__restrict__ v) {
+    const int ip = blockIdx.x * 256 + threadIdx.x;
+    if (ip >= p.n_ip) return;
+    const long S = p.n_ip;
+    const int img = p.ip_image[ip], cam = p.image_camera[img], pt = p.ip_point[ip];
+    const int jb = p.cam_dist_begin[cam], nd = p.cam_dist_begin[cam + 1] - jb;
+    double v0 = -rowsW[ip], v1 = -rowsW[S + ip];
+    for (int l = 0; l < 12 + nd; l++) {
+        const int col = l < 3 ? p.point_col[3 * pt + l]
+                              : (l < 6 ? p.io_col[3 * cam + l - 3] : (l < 12 ? p.eo_col[6 * img + l - 6] : p.dist_col[jb + l - 12]));
+        if (col < 0) continue;
+        const double d = dx[col];
+        v0 = fma(rowsA[(long)(2 * l) * S + ip], d, v0);
+        v1 = fma(rowsA[(long)(2 * l + 1) * S + ip], d, v1);
+    }
+    v[2 * (long)ip] = v0;
+    v[2 * (long)ip + 1] = v1;
+}
+
+// chunks[i] = (first engine image point, count <= RL_PTS), all of one image, all with 2 x 2 weights
+__global__ __launch_bounds__(RL_PTS) void rel_points_kernel(DevProblem p, const int2 *__restrict__ chunks, const double *__restrict__ Q, long ld,
+                                                            const double *__restrict__ rowsA, const double *__restrict__ v,
+                                                            const double *__restrict__ lld, const int32_t *__restrict__ new2old, double s0,
+                                                            double s2t, long n_rows, double *__restrict__ out) {
+    __shared__ double sQ[KC_MAX * KC_MAX];
+    __shared__ double sA[2 * KC_MAX * RL_PTS];   // the shared part a_s of both rows of every point: [row][column][lane]
+    __shared__ int scol[KC_MAX];
+    const int tid = threadIdx.x;
+    const int2 ch = chunks[blockIdx.x];
+    const int img = p.ip_image[ch.x], cam = p.image_camera[img], jb = p.cam_dist_begin[cam];
+    const int kc = 9 + p.cam_dist_begin[cam + 1] - jb;
+    const long S = p.n_ip;
+    if (tid < kc) scol[tid] = rl_col(p, img, cam, jb, tid);
+    __syncthreads();
+    for (int i = tid; i < kc * kc; i += RL_PTS) {
+        const int a = i / kc, b = i - a * kc;
+        const int qa = scol[a], qb = scol[b];
+        sQ[a * KC_MAX + b] = (qa < 0 || qb < 0) ? 0.0 : rl_q(Q, ld, qa, qb);
+    }
+    __syncthreads();
+    if (tid >= ch.y) return;
+    const int ip = ch.x + tid, pt = p.ip_point[ip];
+    double *my0 = sA + tid, *my1 = sA + KC_MAX * RL_PTS + tid;   // column c of row 0 / 1 at [c * RL_PTS]
+    for (int c = 0; c < kc; c++) {
+        const bool f = scol[c] >= 0;
+        my0[c * RL_PTS] = f ? rowsA[(long)(2 * rl_local(c)) * S + ip] : 0.0;
+        my1[c * RL_PTS] = f ? rowsA[(long)(2 * rl_local(c) + 1) * S + ip] : 0.0;
+    }
+    int pc[3];
+    double ap[2][3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        pc[a] = p.point_col[3 * pt + a];
+        ap[0][a] = pc[a] >= 0 ? rowsA[(long)(2 * a) * S + ip] : 0.0;
+        ap[1][a] = pc[a] >= 0 ? rowsA[(long)(2 * a + 1) * S + ip] : 0.0;
+    }
+    double h00 = 0.0, h01 = 0.0, h11 = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            if (pc[a] < 0 || pc[b] < 0) continue;
+            const double q = rl_q(Q, ld, pc[a], pc[b]);
+            h00 = fma(ap[0][a], q * ap[0][b], h00);
+            h01 = fma(ap[0][a], q * ap[1][b], h01);
+            h11 = fma(ap[1][a], q * ap[1][b], h11);
+        }
+    for (int c = 0; c < kc; c++) {
+        const int qc = scol[c];
+        if (qc < 0) continue;
+        double y0 = 0.0, y1 = 0.0, z0 = 0.0, z1 = 0.0;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            if (pc[a] < 0) continue;
+            const double q = rl_q(Q, ld, qc, pc[a]);
+            y0 = fma(q, ap[0][a], y0);
+            y1 = fma(q, ap[1][a], y1);
+        }
+        for (int b = 0; b < kc; b++) {
+            const double q = sQ[c * KC_MAX + b];
+            z0 = fma(q, my0[b * RL_PTS], z0);
+            z1 = fma(q, my1[b * RL_PTS], z1);
+        }
+        const double a0 = my0[c * RL_PTS], a1 = my1[c * RL_PTS];
+        h00 += a0 * (2.0 * y0 + z0);
+        h11 += a1 * (2.0 * y1 + z1);
+        h01 += y0 * a1 + a0 * (y1 + z1);
+    }
+    // P = sigma0^2 inv(D) of the point (PDF:296-319)
+    double p00, p01, p11;
+    {
+        const double vx = p.ip_var_x[ip], vy = p.ip_var_y[ip], rho = p.ip_rho[ip];
+        if (rho == 0) {
+            p00 = s0 / vx; p11 = s0 / vy; p01 = 0.0;
+        } else {
+            const double invDet = s0 / ((1.0 - rho * rho) * vx * vy);
+            p00 = invDet * vy; p11 = invDet * vx; p01 = -invDet * rho * sqrt(vx * vy);
+        }
+    }
+    const double g00 = h00 * p00 + h01 * p01, g01 = h00 * p01 + h01 * p11;
+    const double g10 = h01 * p00 + h11 * p01, g11 = h01 * p01 + h11 * p11;
+    const double ppp0 = p00 - (p00 * g00 + p01 * g10), ppp1 = p11 - (p01 * g01 + p11 * g11);
+    const double v0 = v[2 * (long)ip], v1 = v[2 * (long)ip + 1];
+    const double pv0 = p00 * v0 + p01 * v1, pv1 = p01 * v0 + p11 * v1;
+    rl_store(out, n_rows, rl_row(new2old, ip, 0), v0, lld[2 * (long)ip] / s0 - h00, 1.0 - g00, rl_t(pv0, ppp0, p00, s2t));
+    rl_store(out, n_rows, rl_row(new2old, ip, 1), v1, lld[2 * (long)ip + 1] / s0 - h11, 1.0 - g11, rl_t(pv1, ppp1, p11, s2t));
+}
+
+// Dense blocks, per row i < m of block bl[blockIdx.y]: L[i] = [y(i) | a_s(i)], R[i] = [a_s(i) | u(i)] (KC_MAX each, zero beyond kc and
+// in the padding rows up to mpad).  L, R: [batch][mpad][RL_K].
+__global__ __launch_bounds__(RL_PTS) void rel_prep_kernel(DevProblem p, const int32_t *__restrict__ bl, int mpad, const double *__restrict__ Q, long ld,
+                                                          const double *__restrict__ rowsA, double *__restrict__ L, double *__restrict__ R) {
+    __shared__ double sQ[KC_MAX * KC_MAX];
+    __shared__ double sA[KC_MAX * RL_PTS];       // a_s of every row of the workgroup: [column][lane]
+    __shared__ int scol[KC_MAX];
+    const int tid = threadIdx.x;
+    const int g = bl[blockIdx.y];
+    const int ipb = p.blk_ip_begin[g], m = 2 * (p.blk_ip_begin[g + 1] - ipb);
+    const int img = p.ip_image[ipb], cam = p.image_camera[img], jb = p.cam_dist_begin[cam];
+    const int kc = 9 + p.cam_dist_begin[cam + 1] - jb;
+    const long S = p.n_ip;
+    if (tid < kc) scol[tid] = rl_col(p, img, cam, jb, tid);
+    __syncthreads();
+    for (int i = tid; i < kc * kc; i += RL_PTS) {
+        const int a = i / kc, b = i - a * kc;
+        const int qa = scol[a], qb = scol[b];
+        sQ[a * KC_MAX + b] = (qa < 0 || qb < 0) ? 0.0 : rl_q(Q, ld, qa, qb);
+    }
+    __syncthreads();
+    const int i = blockIdx.x * RL_PTS + tid;
+    if (i >= mpad) return;
+    double *Lr = L + ((long)blockIdx.y * mpad + i) * RL_K, *Rr = R + ((long)blockIdx.y * mpad + i) * RL_K;
+    if (i >= m) {
+        for (int k = 0; k < RL_K; k++) { Lr[k] = 0.0; Rr[k] = 0.0; }
+        return;
+    }
+    const int ip = ipb + (i >> 1), r = i & 1, pt = p.ip_point[ip];
+    double *my = sA + tid;
+    for (int c = 0; c < kc; c++) my[c * RL_PTS] = scol[c] >= 0 ? rowsA[(long)(2 * rl_local(c) + r) * S + ip] : 0.0;
+    int pc[3];
+    double ap[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        pc[a] = p.point_col[3 * pt + a];
+        ap[a] = pc[a] >= 0 ? rowsA[(long)(2 * a + r) * S + ip] : 0.0;
+    }
+    for (int c = 0; c < KC_MAX; c++) {
+        double y = 0.0, u = 0.0, as = 0.0;
+        if (c < kc && scol[c] >= 0) {
+#pragma unroll
+            for (int a = 0; a < 3; a++)
+                if (pc[a] >= 0) y = fma(rl_q(Q, ld, scol[c], pc[a]), ap[a], y);
+            double z = 0.0;
+            for (int b = 0; b < kc; b++) z = fma(sQ[c * KC_MAX + b], my[b * RL_PTS], z);
+            u = y + z;
+            as = my[c * RL_PTS];
+        }
+        Lr[c] = y; Lr[KC_MAX + c] = as;
+        Rr[c] = as; Rr[KC_MAX + c] = u;
+    }
+    for (int k = 2 * KC_MAX; k < RL_K; k++) { Lr[k] = 0.0; Rr[k] = 0.0; }
+}
+
+// Dense blocks: H[bi][rows of chunk a][rows of chunk b] = a_p Q[P, P] a_p' (and its mirror), one workgroup per chunk pair b <= a.
+// grid (most chunk pairs of a block of the batch, blocks of the batch)
+__global__ __launch_bounds__(256) void rel_pp_kernel(DevProblem p, const int32_t *__restrict__ bl, int mpad, const double *__restrict__ Q, long ld,
+                                                     const double *__restrict__ rowsA, double *__restrict__ H) {
+    __shared__ double sQ[RL_PC * (RL_PC + 1)];
+    __shared__ double sAa[RL_RC * 3], sAb[RL_RC * 3];
+    __shared__ int colA[RL_PC], colB[RL_PC];
+    const int tid = threadIdx.x;
+    const int g = bl[blockIdx.y];
+    const int ipb = p.blk_ip_begin[g], mp = p.blk_ip_begin[g + 1] - ipb;
+    const long nch = (mp + RL_TP - 1) / RL_TP, tiles = nch * (nch + 1) / 2, t = blockIdx.x;
+    if (t >= tiles) return;
+    long a = (long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while (a * (a + 1) / 2 > t) a--;
+    while ((a + 1) * (a + 2) / 2 <= t) a++;
+    const long b = t - a * (a + 1) / 2;
+    const int pa0 = (int)a * RL_TP, pb0 = (int)b * RL_TP;
+    const int na = min(RL_TP, mp - pa0), nb = min(RL_TP, mp - pb0);
+    const long S = p.n_ip;
+    if (tid < RL_PC) {
+        const int k = tid / 3, c = tid - 3 * k;
+        colA[tid] = k < na ? p.point_col[3 * p.ip_point[ipb + pa0 + k] + c] : -1;
+        colB[tid] = k < nb ? p.point_col[3 * p.ip_point[ipb + pb0 + k] + c] : -1;
+    }
+    __syncthreads();
+    if (tid < 2 * RL_RC) {   // a_p of the 32 rows of chunk a (threads 0-31) and of chunk b (32-63)
+        const int side = tid / RL_RC, k = tid - side * RL_RC, q = k >> 1, r = k & 1;
+        const int n = side ? nb : na, p0 = side ? pb0 : pa0;
+        const int *cl = side ? colB : colA;
+        double *dst = (side ? sAb : sAa) + 3 * k;
+        for (int c = 0; c < 3; c++) dst[c] = (q < n && cl[3 * q + c] >= 0) ? rowsA[(long)(2 * c + r) * S + ipb + p0 + q] : 0.0;
+    }
+    // stage Q[cols(a), cols(b)]: lower entries along the column index, mirrored ones along the row index
+    for (int i = tid; i < RL_PC * RL_PC; i += 256) {
+        const int r = i / RL_PC, c = i - r * RL_PC;
+        const int qr = colA[r], qc = colB[c];
+        if (qr < 0 || qc < 0) sQ[r * (RL_PC + 1) + c] = 0.0;
+        else if (qr >= qc) sQ[r * (RL_PC + 1) + c] = Q[(long)qr * ld + qc];
+    }
+    for (int i = tid; i < RL_PC * RL_PC; i += 256) {
+        const int c = i / RL_PC, r = i - c * RL_PC;
+        const int qr = colA[r], qc = colB[c];
+        if (qr >= 0 && qc >= 0 && qr < qc) sQ[r * (RL_PC + 1) + c] = Q[(long)qc * ld + qr];
+    }
+    __syncthreads();
+    double *Hb = H + (long)blockIdx.y * mpad * mpad;
+    const int ra = 2 * pa0, rb = 2 * pb0;
+    for (int i = tid; i < RL_RC * RL_RC; i += 256) {
+        const int x = i / RL_RC, y = i - x * RL_RC;
+        if (x >= 2 * na || y >= 2 * nb) continue;
+        const double *qa = sQ + 3 * (x >> 1) * (RL_PC + 1) + 3 * (y >> 1);
+        const double *ua = sAa + 3 * x, *ub = sAb + 3 * y;
+        double h = 0.0;
+#pragma unroll
+        for (int u = 0; u < 3; u++) {
+            const double z = fma(qa[u * (RL_PC + 1)], ub[0], fma(qa[u * (RL_PC + 1) + 1], ub[1], qa[u * (RL_PC + 1) + 2] * ub[2]));
+            h = fma(ua[u], z, h);
+        }
+        Hb[(long)(ra + x) * mpad + rb + y] = h;
+        if (a != b) Hb[(long)(rb + y) * mpad + ra + x] = h;
+    }
+}
+
+// P = sigma0^2 inv(D) of block bl[blockIdx.z], zero-padded to mpad x mpad; grid (ceil(mpad / 256), mpad, batch)
+__global__ __launch_bounds__(256) void rel_pad_kernel(DevProblem p, const int32_t *__restrict__ bl, int mpad, double s0, double *__restrict__ P) {
+    const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    if (j >= mpad) return;
+    const int g = bl[blockIdx.z];
+    const int m = 2 * (p.blk_ip_begin[g + 1] - p.blk_ip_begin[g]);
+    const double *W = p.blk_w + p.blk_w_offset[g];
+    P[((long)blockIdx.z * mpad + i) * mpad + j] = (i < m && j < m) ? s0 * W[(long)i * m + j] : 0.0;
+}
+
+// grid (ceil(mpad / 256), batch): row i of block bl[blockIdx.y]
+__global__ __launch_bounds__(256) void rel_block_kernel(DevProblem p, const int32_t *__restrict__ bl, int mpad, const double *__restrict__ H,
+                                                        const double *__restrict__ P, const double *__restrict__ G, const double *__restrict__ v,
+                                                        const double *__restrict__ lld, const int32_t *__restrict__ new2old, double s0, double s2t,
+                                                        long n_rows, double *__restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int g = bl[blockIdx.y];
+    const int ipb = p.blk_ip_begin[g], m = 2 * (p.blk_ip_begin[g + 1] - ipb);
+    if (i >= m) return;
+    const long off = (long)blockIdx.y * mpad * mpad;
+    const double *Pb = P + off, *Gb = G + off, *vb = v + 2 * (long)ipb;
+    double php = 0.0, pv = 0.0;
+    for (int j = 0; j < m; j++) {
+        const double pji = Pb[(long)j * mpad + i];
+        php = fma(pji, Gb[(long)j * mpad + i], php);
+        pv = fma(pji, vb[j], pv);
+    }
+    const double pii = Pb[(long)i * mpad + i];
+    const double h = H[off + (long)i * mpad + i], gii = Gb[(long)i * mpad + i];
+    rl_store(out, n_rows, rl_row(new2old, ipb + (i >> 1), i & 1), vb[i], lld[2 * (long)ipb + i] / s0 - h, 1.0 - gii, rl_t(pv, pii - php, pii, s2t));
+}
+
+// scale bars (PDF:210-283): one thread each; row = row0 + s
+__global__ __launch_bounds__(64) void rel_scalebar_kernel(DevProblem p, const double *__restrict__ vals, const double *__restrict__ Q, long ld,
+                                                          const double *__restrict__ dx, double s0, double s2t, long row0, long n_rows,
+                                                          double *__restrict__ out) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= p.n_sb) return;
+    const int pa = p.sb_a[s], pb = p.sb_b[s];
+    const double *a = vals + 3 * pa, *b = vals + 3 * pb;
+    const double dX = b[0] - a[0], dY = b[1] - a[1], dZ = b[2] - a[2];
+    const double len = sqrt(dX * dX + dY * dY + dZ * dZ);
+    const double ev[6] = {-dX / len, -dY / len, -dZ / len, dX / len, dY / len, dZ / len};
+    int col[6];
+    for (int k = 0; k < 6; k++) col[k] = k < 3 ? p.point_col[3 * pa + k] : p.point_col[3 * pb + k - 3];
+    double v = len - p.sb_len[s], h = 0.0;     // v = A dx - w, w = observed - computed
+    for (int k = 0; k < 6; k++) {
+        if (col[k] < 0) continue;
+        v = fma(ev[k], dx[col[k]], v);
+        double z = 0.0;
+        for (int l = 0; l < 6; l++)
+            if (col[l] >= 0) z = fma(rl_q(Q, ld, col[k], col[l]), ev[l], z);
+        h = fma(ev[k], z, h);
+    }
+    const double P = s0 / p.sb_var[s];
+    const double r = 1.0 - h * P;
+    rl_store(out, n_rows, row0 + s, v, p.sb_var[s] / s0 - h, r, rl_t(P * v, P - P * h * P, P, s2t));
+}
+
+// directly observed parameter groups (PDF:447-473): A is a selection matrix, H = Q[cols, cols]; one workgroup per group, a thread per row.
+// lld[r]: diag(D) of direct row r (the dispersion's diagonal for a dense group, dg_var otherwise)
+__global__ __launch_bounds__(256) void rel_direct_kernel(DevProblem p, const double *__restrict__ vals, const double *__restrict__ Q, long ld,
+                                                         const double *__restrict__ dx, const double *__restrict__ lld, double s0, double s2t,
+                                                         long row0, long n_rows, double *__restrict__ out) {
+    const int g = blockIdx.x;
+    const int b = p.dg_row_begin[g], m = p.dg_row_begin[g + 1] - b;
+    const long woff = p.dg_w_offset[g];
+    const double *W = woff >= 0 ? p.dg_w + woff : nullptr;
+    auto col_of = [&](int k) { return p.slot_col[p.dg_slot[b + k]]; };
+    auto v_of = [&](int k) {                   // v = A dx - w, w = observed - value
+        const int c = col_of(k);
+        return vals[p.dg_slot[b + k]] - p.dg_obs[b + k] + (c >= 0 ? dx[c] : 0.0);
+    };
+    auto h_of = [&](int k, int l) {
+        const int ck = col_of(k), cl = col_of(l);
+        return (ck < 0 || cl < 0) ? 0.0 : rl_q(Q, ld, ck, cl);
+    };
+    for (int i = threadIdx.x; i < m; i += 256) {
+        const double hii = h_of(i, i), vi = v_of(i);
+        double pii, gii, php, pv;
+        if (W) {
+            // G = H P: G_ii = sum_j H_ij P_ji;  (P H P)_ii = sum_j P_ij G_ji
+            pii = s0 * W[(long)i * m + i];
+            gii = 0.0; php = 0.0; pv = 0.0;
+            for (int j = 0; j < m; j++) {
+                const double pij = s0 * W[(long)i * m + j];
+                double gji = 0.0;
+                for (int k = 0; k < m; k++) gji = fma(h_of(j, k), s0 * W[(long)k * m + i], gji);
+                gii = fma(h_of(i, j), s0 * W[(long)j * m + i], gii);
+                php = fma(pij, gji, php);
+                pv = fma(pij, v_of(j), pv);
+            }
+        } else {
+            pii = s0 / p.dg_var[b + i];
+            gii = hii * pii;
+            php = pii * gii;
+            pv = pii * vi;
+        }
+        rl_store(out, n_rows, row0 + b + i, vi, lld[b + i] / s0 - hii, 1.0 - gii, rl_t(pv, pii - php, pii, s2t));
+    }
+}
+
+// [0] sum r  [1] max |t|  [2] its row (first of equals)  [3] rows with NaN t  [4] min r; one workgroup, fixed order
+__global__ __launch_bounds__(256) void rel_summary_kernel(const double *__restrict__ out, long n_rows, double *__restrict__ sum) {
+    __shared__ double s_r[256], s_t[256], s_min[256], s_nan[256];
+    __shared__ long s_row[256];
+    const int tid = threadIdx.x;
+    const double *r = out + 2 * n_rows, *t = out + 3 * n_rows;
+    double sr = 0.0, mt = -1.0, mr = INFINITY, nn = 0.0;
+    long row = -1;
+    for (long i = tid; i < n_rows; i += 256) {
+        sr += r[i];
+        mr = fmin(mr, r[i]);
+        const double at = fabs(t[i]);
+        if (isnan(at)) nn += 1.0;
+        else if (at > mt) { mt = at; row = i; }
+    }
+    s_r[tid] = sr; s_t[tid] = mt; s_min[tid] = mr; s_nan[tid] = nn; s_row[tid] = row;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) {
+            s_r[tid] += s_r[tid + h];
+            s_min[tid] = fmin(s_min[tid], s_min[tid + h]);
+            s_nan[tid] += s_nan[tid + h];
+            const double o = s_t[tid + h];
+            const long orow = s_row[tid + h];
+            if (o > s_t[tid] || (o == s_t[tid] && orow >= 0 && (s_row[tid] < 0 || orow < s_row[tid]))) { s_t[tid] = o; s_row[tid] = orow; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        sum[0] = s_r[0];
+        sum[1] = s_row[0] >= 0 ? s_t[0] : (double)NAN;
+        sum[2] = (double)s_row[0];
+        sum[3] = s_nan[0];
+        sum[4] = n_rows > 0 ? s_min[0] : (double)NAN;
+    }
+}
+
+}  // namespace jaicov
+
+using namespace jaicov;
+
+#define RL_FAIL(v, code, msg) \
+    do {                      \
+        *(v).err = (msg);     \
+        return (code);        \
+    } while (0)
+#define RL_HIP(v, x)                                                                           \
+    do {                                                                                       \
+        hipError_t _err = (x);                                                                 \
+        if (_err != hipSuccess) {                                                              \
+            *(v).err = std::string(#x) + ": " + hipGetErrorString(_err);                       \
+            return _err == hipErrorOutOfMemory ? JAICOV_ERR_OUT_OF_MEMORY : JAICOV_ERR_DEVICE; \
+        }                                                                                      \
+    } while (0)
+
+namespace {
+// device buffers of one run, freed on every exit
+struct RelWork {
+    std::vector<void *> ptrs;
+    ~RelWork() {
+        for (void *q : ptrs) hipFree(q);
+    }
+    template <typename T>
+    hipError_t alloc(T **dst, size_t count) {
+        *dst = nullptr;
+        hipError_t he = hipMalloc((void **)dst, std::max<size_t>(count, 1) * sizeof(T));
+        if (he == hipSuccess) ptrs.push_back(*dst);
+        return he;
+    }
+};
+constexpr size_t RL_BATCH_BYTES = (size_t)1 << 30;   // work buffers of the dense blocks per batch
+}  // namespace
+
+
+static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx) {
+    const DevProblem &p = *v.p;
+    const double s0 = v.sigma2;
+    const long n_ip = p.n_ip, n_rows = s->n_rows;
+    const hipStream_t st = v.stream;
+    RelWork w;
+    s->summary[5] = v.lambda;
+    RL_HIP(v, w.alloc(&s->d_out, 4 * (size_t)n_rows));
+    w.ptrs.pop_back();                                  // the result belongs to the state
+    if (n_rows == 0) return JAICOV_OK;
+    double *d_dx = nullptr, *d_v = nullptr, *d_sum = nullptr;
+    RL_HIP(v, w.alloc(&d_dx, (size_t)v.U));
+    RL_HIP(v, w.alloc(&d_v, 2 * (size_t)n_ip));
+    RL_HIP(v, w.alloc(&d_sum, 5));
+    if (dx) RL_HIP(v, hipMemcpyAsync(d_dx, dx, (size_t)v.U * sizeof(double), hipMemcpyHostToDevice, st));
+    else RL_HIP(v, hipMemsetAsync(d_dx, 0, (size_t)v.U * sizeof(double), st));
+    // engine position -> the caller's image point
+    int32_t *d_new2old = nullptr;
+    if (!v.ip_old2new->empty() && n_ip > 0) {
+        std::vector<int32_t> new2old(n_ip);
+        for (long o = 0; o < n_ip; o++) new2old[(*v.ip_old2new)[o]] = (int32_t)o;
+        RL_HIP(v, w.alloc(&d_new2old, (size_t)n_ip));
+        RL_HIP(v, hipMemcpyAsync(d_new2old, new2old.data(), (size_t)n_ip * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        RL_HIP(v, hipStreamSynchronize(st));        // new2old is a host temporary
+    }
+    if (n_ip > 0) {
+        hipLaunchKernelGGL(rel_v_kernel, dim3((unsigned)((n_ip + 255) / 256)), dim3(256), 0, st, p, v.rowsA, v.rowsW, d_dx, d_v);
+        RL_HIP(v, hipGetLastError());
+        // which image points have 2 x 2 weights (ordinary groups, or ordinary images served as blocks with compact weights)
+        const std::vector<int32_t> &bb = *v.blk_ip_begin;
+        const std::vector<int64_t> &bw = *v.blk_w_off;
+        std::vector<uint8_t> dense(n_ip, 0);
+        std::vector<int32_t> dense_blocks;
+        int max_m = 0;
+        for (size_t g = 0; g + 1 < bb.size(); g++) {
+            if (bw[g] < 0 || bb[g + 1] <= bb[g]) continue;
+            dense_blocks.push_back((int32_t)g);
+            max_m = std::max(max_m, 2 * (bb[g + 1] - bb[g]));
+            for (int q = bb[g]; q < bb[g + 1]; q++) dense[q] = 1;
+        }
+        std::vector<int32_t> ip_image(n_ip);
+        RL_HIP(v, hipMemcpyAsync(ip_image.data(), p.ip_image, (size_t)n_ip * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        RL_HIP(v, hipStreamSynchronize(st));
+        std::vector<int2> chunks;
+        for (long q = 0; q < n_ip;) {
+            if (dense[q]) { q++; continue; }
+            long en = q;
+            while (en < n_ip && !dense[en] && ip_image[en] == ip_image[q] && en - q < RL_PTS) en++;
+            chunks.push_back(make_int2((int)q, (int)(en - q)));
+            q = en;
+        }
+        if (!chunks.empty()) {
+            int2 *d_chunks = nullptr;
+            RL_HIP(v, w.alloc(&d_chunks, chunks.size()));
+            RL_HIP(v, hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(rel_points_kernel, dim3((unsigned)chunks.size()), dim3(RL_PTS), 0, st, p, d_chunks, v.Q, v.ld, v.rowsA, d_v,
+                               v.ll_diag, d_new2old, s0, s2t, n_rows, s->d_out);
+            RL_HIP(v, hipGetLastError());
+        }
+        if (!dense_blocks.empty()) {
+            const int nd = (int)dense_blocks.size();
+            const int mpad = (max_m + 127) / 128 * 128;
+            const size_t sq = (size_t)mpad * mpad;
+            const size_t per = (3 * sq + 2 * (size_t)mpad * RL_K) * sizeof(double);
+            size_t cap = RL_BATCH_BYTES / per;
+            if (const char *hook = getenv("JAICOV_REL_BATCH")) cap = std::min<size_t>(cap, (size_t)std::max(1, atoi(hook)));   // test hook
+            const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)nd, cap));
+            int32_t *d_bl = nullptr;
+            double *d_H = nullptr, *d_P = nullptr, *d_G = nullptr, *d_L = nullptr, *d_R = nullptr;
+            RL_HIP(v, w.alloc(&d_bl, (size_t)nd));
+            RL_HIP(v, w.alloc(&d_H, nb * sq));
+            RL_HIP(v, w.alloc(&d_P, nb * sq));
+            RL_HIP(v, w.alloc(&d_G, nb * sq));
+            RL_HIP(v, w.alloc(&d_L, (size_t)nb * mpad * RL_K));
+            RL_HIP(v, w.alloc(&d_R, (size_t)nb * mpad * RL_K));
+            RL_HIP(v, hipMemcpyAsync(d_bl, dense_blocks.data(), (size_t)nd * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            for (int b0 = 0; b0 < nd; b0 += nb) {
+                const int n = std::min(nb, nd - b0);
+                const int32_t *bl = d_bl + b0;
+                long tmax = 0;
+                for (int k = b0; k < b0 + n; k++) {
+                    const long mp = bb[dense_blocks[k] + 1] - bb[dense_blocks[k]], nch = (mp + RL_TP - 1) / RL_TP;
+                    tmax = std::max(tmax, nch * (nch + 1) / 2);
+                }
+                RL_HIP(v, hipMemsetAsync(d_H, 0, n * sq * sizeof(double), st));
+                hipLaunchKernelGGL(rel_prep_kernel, dim3(mpad / RL_PTS, n), dim3(RL_PTS), 0, st, p, bl, mpad, v.Q, v.ld, v.rowsA, d_L, d_R);
+                hipLaunchKernelGGL(rel_pp_kernel, dim3((unsigned)tmax, n), dim3(256), 0, st, p, bl, mpad, v.Q, v.ld, v.rowsA, d_H);
+                hipLaunchKernelGGL(rel_pad_kernel, dim3(mpad / 256 + (mpad % 256 ? 1 : 0), mpad, n), dim3(256), 0, st, p, bl, mpad, s0, d_P);
+                RL_HIP(v, hipGetLastError());
+                GemmArgs g1{};   // H += [Y | A_s] [A_s | U]'
+                g1.A = d_L; g1.lda = RL_K; g1.B = d_R; g1.ldb = RL_K; g1.C = d_H; g1.ldc = mpad;
+                g1.M = mpad; g1.N = mpad; g1.K = RL_K; g1.alpha = 1.0; g1.beta = 1.0; g1.kmode = KMODE_FULL;
+                g1.strideA = (long)mpad * RL_K; g1.strideB = (long)mpad * RL_K; g1.strideC = (long)sq;
+                RL_HIP(v, gemm_f64(st, LAY_KC, LAY_KC, g1, n));
+                GemmArgs g2{};   // G = H P  (P symmetric: P(k, j) = P[j][k])
+                g2.A = d_H; g2.lda = mpad; g2.B = d_P; g2.ldb = mpad; g2.C = d_G; g2.ldc = mpad;
+                g2.M = mpad; g2.N = mpad; g2.K = mpad; g2.alpha = 1.0; g2.beta = 0.0; g2.kmode = KMODE_FULL;
+                g2.strideA = (long)sq; g2.strideB = (long)sq; g2.strideC = (long)sq;
+                RL_HIP(v, gemm_f64(st, LAY_KC, LAY_KC, g2, n));
+                hipLaunchKernelGGL(rel_block_kernel, dim3(mpad / 256 + (mpad % 256 ? 1 : 0), n), dim3(256), 0, st, p, bl, mpad, d_H, d_P, d_G,
+                                   d_v, v.ll_diag, d_new2old, s0, s2t, n_rows, s->d_out);
+                RL_HIP(v, hipGetLastError());
+            }
+        }
+    }
+    if (p.n_sb > 0) {
+        hipLaunchKernelGGL(rel_scalebar_kernel, dim3((p.n_sb + 63) / 64), dim3(64), 0, st, p, v.d_vals, v.Q, v.ld, d_dx, s0, s2t, 2 * n_ip,
+                           n_rows, s->d_out);
+        RL_HIP(v, hipGetLastError());
+    }
+    if (p.n_dg > 0) {
+        hipLaunchKernelGGL(rel_direct_kernel, dim3(p.n_dg), dim3(256), 0, st, p, v.d_vals, v.Q, v.ld, d_dx, v.ll_diag + 2 * n_ip, s0, s2t,
+                           2 * n_ip + p.n_sb, n_rows, s->d_out);
+        RL_HIP(v, hipGetLastError());
+    }
+    hipLaunchKernelGGL(rel_summary_kernel, dim3(1), dim3(256), 0, st, s->d_out, n_rows, d_sum);
+    RL_HIP(v, hipGetLastError());
+    RL_HIP(v, hipMemcpyAsync(s->summary, d_sum, 5 * sizeof(double), hipMemcpyDeviceToHost, st));
+    RL_HIP(v, hipStreamSynchronize(st));
+    return JAICOV_OK;
+}
+
+extern "C" int jaicov_rel_run(jaicov_engine *e, double sigma2_test, const double *dx, int32_t *n_rows) {
+    if (!e) return JAICOV_ERR_BAD_ARGUMENT;
+    RelView v;
+    engine_rel_view(e, &v, 0);
+    if (v.sharded) RL_FAIL(v, JAICOV_ERR_UNSUPPORTED, "reliability needs an engine that holds every observation (not a shard)");
+    if (!(sigma2_test > 0) || !std::isfinite(sigma2_test)) RL_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "sigma2_test must be positive and finite");
+    if (!v.full_q)
+        RL_FAIL(v, JAICOV_ERR_BAD_STATE, "no full cofactor matrix: solve with JAICOV_INVERT_FULL or JAICOV_INVERT_FULL_EXPANDED first");
+    const DevProblem &p0 = *v.p;
+    const long rows = 2 * (long)p0.n_ip + p0.n_sb + p0.n_dg_rows;
+    if (rows > INT32_MAX) RL_FAIL(v, JAICOV_ERR_UNSUPPORTED, "more than 2^31 - 1 observation rows");
+    RL_HIP(v, hipSetDevice(v.device));
+    int rc = engine_rel_view(e, &v, 1);    // the compact rows of the current parameter values
+    if (rc != JAICOV_OK) return rc;
+    // the arguments are accepted: the previous result goes
+    rel_state_free(*v.state);
+    *v.state = nullptr;
+    RelState *s = new RelState();
+    s->n_rows = rows;
+    rc = rel_run_impl(v, s, sigma2_test, dx);
+    if (rc != JAICOV_OK) {
+        hipStreamSynchronize(v.stream);
+        rel_state_free(s);
+        return rc;
+    }
+    *v.state = s;
+    if (n_rows) *n_rows = (int32_t)rows;
+    return JAICOV_OK;
+}
+
+static RelState *rl_result(jaicov_engine *e, RelView &v) {
+    engine_rel_view(e, &v, 0);
+    if (!*v.state) *v.err = "no reliability result: call jaicov_rel_run first";
+    return *v.state;
+}
+
+extern "C" int jaicov_rel_get(jaicov_engine *e, double *vres, double *qvv, double *r, double *t, int32_t n) {
+    if (!e) return JAICOV_ERR_BAD_ARGUMENT;
+    RelView v;
+    RelState *s = rl_result(e, v);
+    if (!s) return JAICOV_ERR_BAD_STATE;
+    if (n != s->n_rows) RL_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "n must equal the number of observation rows of the last run");
+    if (n == 0) return JAICOV_OK;
+    RL_HIP(v, hipSetDevice(v.device));
+    double *dst[4] = {vres, qvv, r, t};
+    for (int k = 0; k < 4; k++)
+        if (dst[k]) RL_HIP(v, hipMemcpyAsync(dst[k], s->d_out + k * (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    RL_HIP(v, hipStreamSynchronize(v.stream));
+    return JAICOV_OK;
+}
+
+extern "C" int jaicov_rel_summary(jaicov_engine *e, double *out, int32_t n) {
+    if (!e) return JAICOV_ERR_BAD_ARGUMENT;
+    RelView v;
+    RelState *s = rl_result(e, v);
+    if (!s) return JAICOV_ERR_BAD_STATE;
+    if ((n != 5 && n != 6) || !out) RL_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "the summary has 5 entries (6 with the damping value)");
+    memcpy(out, s->summary, (size_t)n * sizeof(double));
+    return JAICOV_OK;
+}
+
+extern "C" int jaicov_rel_release(jaicov_engine *e) {
+    if (!e) return JAICOV_ERR_BAD_ARGUMENT;
+    RelView v;
+    engine_rel_view(e, &v, 0);
+    if (*v.state) {
+        hipSetDevice(v.device);
+        hipStreamSynchronize(v.stream);
+        rel_state_free(*v.state);
+        *v.state = nullptr;
+    }
+    return JAICOV_OK;
+}

@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` / ``include/jaicov_transform.h`` /
-``include/jaicov_dlt.h`` (``csrc/libjaicov_neq.so``).
+``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
 library has not been built, and every call fails with ``EngineError`` when no gfx950 device is present.
@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from collections import namedtuple
 
 import numpy as np
 
@@ -41,6 +42,8 @@ XFORM_EXPORTS = [
 
 # include/jaicov_dlt.h: DirectLinearTransformation.adjust for a batch of images (stand-alone, no engine)
 DLT_EXPORTS = ["jaicov_dlt_adjust"]
+# include/jaicov_reliability.h: residuals, redundancy numbers and test values of every observation on the device
+REL_EXPORTS = ["jaicov_rel_run", "jaicov_rel_get", "jaicov_rel_summary", "jaicov_rel_release"]
 # jaicov_dlt_restriction (DirectLinearTransformation.RestrictionType, DT:51-58 order) and the per-image status values
 DLT_IDENTICAL_PRINCIPLE_DISTANCE, DLT_ROTATION_WITHOUT_SHEAR, DLT_FIXED_PRINCIPLE_DISTANCE_X, DLT_FIXED_PRINCIPLE_DISTANCE_Y, \
     DLT_FIXED_PRINCIPAL_POINT_X, DLT_FIXED_PRINCIPAL_POINT_Y = range(6)
@@ -144,9 +147,17 @@ def load_library():
     L.jaicov_xform_get_covariance_sub.argtypes = [vp, _pi, C.c_int32, _pd]
     L.jaicov_xform_get_point_blocks.argtypes = [vp, _pd, C.c_int32]
     L.jaicov_xform_release.argtypes = [vp]
+    L.jaicov_rel_run.argtypes = [vp, C.c_double, _pd, _pi]
+    L.jaicov_rel_get.argtypes = [vp, _pd, _pd, _pd, _pd, C.c_int32]
+    L.jaicov_rel_summary.argtypes = [vp, _pd, C.c_int32]
+    L.jaicov_rel_release.argtypes = [vp]
     L.jaicov_dlt_adjust.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pi, C.c_int32, C.c_int32, _pd, _pi, _pi, _pd]
     _LIB = L
     return L
+
+
+# Engine.reliability: one entry per observation row (include/jaicov_reliability.h)
+Reliability = namedtuple("Reliability", ["v", "qvv", "r", "t"])
 
 
 def _p(a):
@@ -344,6 +355,29 @@ class Engine:
     def transform_release(self):
         self._chk(self.L.jaicov_xform_release(self._h))
         self.xform_count = 0
+
+    # reliability (include/jaicov_reliability.h) ---------------------------------------------------------------------------------
+    def reliability(self, sigma2_test, dx=None):
+        """Residuals v = A dx - w, their cofactors qvv = diag(Q_ll - A Qxx A'), redundancy numbers r = diag(Q_vv P) and test values
+        t = (P v) / sqrt(sigma2_test diag(P Q_vv P)) (NaN: not controlled) of every observation row, in the reference's row order.
+        Needs all of Qxx (an inverting solve with INVERT_FULL / INVERT_FULL_EXPANDED).  dx None = a zero step."""
+        n = C.c_int32(0)
+        d = None if dx is None else np.ascontiguousarray(dx, np.float64)
+        if d is not None and d.size != self.fp.n_unknowns:
+            raise ValueError("dx must have U entries")
+        self._chk(self.L.jaicov_rel_run(self._h, float(sigma2_test), None if d is None else _p(d), C.byref(n)))
+        out = [np.zeros(n.value) for _ in range(4)]
+        self._chk(self.L.jaicov_rel_get(self._h, *[_p(a) for a in out], n.value))
+        return Reliability(*out)
+
+    def reliability_summary(self):
+        """(sum r, max |t|, its row, rows with NaN t, min r, damping of the inverted build) of the last reliability run."""
+        out = np.zeros(6)
+        self._chk(self.L.jaicov_rel_summary(self._h, _p(out), 6))
+        return out
+
+    def reliability_release(self):
+        self._chk(self.L.jaicov_rel_release(self._h))
 
     def get_rows(self, ip_begin, ip_count):
         w = np.zeros((ip_count, 2)); A = np.zeros((ip_count, 2, KROW))

@@ -140,6 +140,11 @@ PYBIND11_MODULE(_jaicov_host, m) {
             std::vector<double> v = b.cofactorSub(idx, scale);
             return py::array_t<double>({idx.size(), idx.size()}, v.data());
         }, py::arg("indices"), py::arg("scale") = 1.0)
+        .def("observationReliability", [](BundleAdjustment &b, double sigma2Test) {
+            auto o = b.observationReliability(sigma2Test);
+            auto arr = [](const std::vector<double> &x) { return py::array_t<double>((py::ssize_t)x.size(), x.data()); };
+            return py::make_tuple(arr(o.v), arr(o.qvv), arr(o.r), arr(o.t));
+        }, py::arg("sigma2Test"), "(v, qvv, r, t) of every observation row (include/jaicov_reliability.h)")
         .def("useCentroidedCoordinates", &BundleAdjustment::useCentroidedCoordinates)
         .def("centroidCoordinates", &BundleAdjustment::centroidCoordinates)
         .def("applyAposterioriVarianceOfUnitWeight", &BundleAdjustment::applyAposterioriVarianceOfUnitWeight)

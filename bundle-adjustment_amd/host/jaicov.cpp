@@ -466,6 +466,19 @@ std::vector<double> BundleAdjustment::cofactorSub(const std::vector<int32_t> &id
     return out;
 }
 
+BundleAdjustment::ObservationReliability BundleAdjustment::observationReliability(double sigma2Test) const {
+    if (!engine_ || inversion_ != MatrixInversion::FULL)
+        throw std::runtime_error("no full cofactor matrix: run estimateModel with MatrixInversion.FULL first");
+    int32_t n = 0;
+    int rc = jaicov_rel_run(engine_, sigma2Test, nullptr, &n);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_rel_run: ") + jaicov_neq_last_error(engine_));
+    ObservationReliability o;
+    o.v.resize(n); o.qvv.resize(n); o.r.resize(n); o.t.resize(n);
+    rc = jaicov_rel_get(engine_, o.v.data(), o.qvv.data(), o.r.data(), o.t.data(), n);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_rel_get: ") + jaicov_neq_last_error(engine_));
+    return o;
+}
+
 // CTEO:49-121: rows, coordinates and sigma2 J Qxx J' on the device (jaicov_xform_run), the results copied back
 void CoordinateTransformationExteriorOrientation::transform(const std::vector<ObjectCoordinate *> &objectCoordinatesToTransform,
                                                             const std::vector<std::pair<Image *, std::vector<Image *>>> &imagesToAlign,

@@ -28,6 +28,7 @@
 #include "../../include/jaicov_neq.h"
 #include "../../include/jaicov_transform.h"
 #include "../../include/jaicov_dlt.h"
+#include "../../include/jaicov_reliability.h"
 
 namespace jaicov::host {
 
@@ -505,6 +506,13 @@ public:
     bool hasCofactorMatrix() const { return inversion_ != MatrixInversion::NONE && (qxxOnDevice_ || !Qxx_.empty()); }
     // scale * Qxx[idx, idx], row-major k x k, gathered on the device (jaicov_neq_get_dispersion_sub)
     std::vector<double> cofactorSub(const std::vector<int32_t> &idx, double scale = 1.0) const;
+    // residuals v, residual cofactors qvv, redundancy numbers r and test values t of every observation row, in row order (BA:670-771),
+    // on the engine of the last estimateModel (jaicov_rel_run with a zero step: v at the adjusted values).  Needs MatrixInversion.FULL.
+    // sigma2Test = getVarianceFactorAposteriori() gives Pope's tau, the a-priori factor Baarda's w-test (include/jaicov_reliability.h).
+    struct ObservationReliability {
+        std::vector<double> v, qvv, r, t;
+    };
+    ObservationReliability observationReliability(double sigma2Test) const;
     const std::string &lastError() const { return lastError_; }
     jaicov_engine *nativeEngine() const { return engine_; }     // the engine of the last estimateModel (null before)
 

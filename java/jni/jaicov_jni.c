@@ -1,6 +1,6 @@
 /*
- * JNI shim between NativeNormalEquationEngine (Java) and the C ABI of include/jaicov_neq.h, include/jaicov_transform.h and
- * include/jaicov_dlt.h.
+ * JNI shim between NativeNormalEquationEngine (Java) and the C ABI of include/jaicov_neq.h, include/jaicov_transform.h,
+ * include/jaicov_dlt.h and include/jaicov_reliability.h.
  * The build image has no JDK, so this file is not built by __graft_entry__.build(); on a box with a JDK:
  *   gcc -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -I../../include jaicov_jni.c \
  *       -L../../bundle-adjustment_amd/csrc -ljaicov_neq -o libjaicov_jni.so
@@ -22,6 +22,7 @@
 #include "jaicov_neq.h"
 #include "jaicov_transform.h"
 #include "jaicov_dlt.h"
+#include "jaicov_reliability.h"
 
 #define ENG(h) ((jaicov_engine *)(intptr_t)(h))
 #define NAT(name) Java_org_applied_1geodesy_adjustment_bundle_nativeengine_NativeNormalEquationEngine_##name
@@ -492,6 +493,57 @@ JNIEXPORT jint JNICALL NAT(xformGetPointBlocks)(JNIEnv *e, jclass k, jlong h, jd
     return rc;
 }
 JNIEXPORT jint JNICALL NAT(xformRelease)(JNIEnv *e, jclass k, jlong h) { (void)e; (void)k; return jaicov_xform_release(ENG(h)); }
+
+/* --- include/jaicov_reliability.h: residuals, redundancy numbers and test values of every observation ------------------------- */
+/* dx (null = a zero step, else exactly U doubles) is copied out of the array before the run; count[0] = observation rows */
+JNIEXPORT jint JNICALL NAT(relRun)(JNIEnv *e, jclass k, jlong h, jdouble sigma2Test, jdoubleArray dx, jlongArray count) {
+    (void)k;
+    if ((*e)->GetArrayLength(e, count) < 1) return JAICOV_ERR_BAD_ARGUMENT;
+    if (dx && !has_u_entries(e, h, dx)) return JAICOV_ERR_BAD_ARGUMENT;      /* the run reads U doubles */
+    double *d = NULL;
+    if (dx) {
+        const jsize n = (*e)->GetArrayLength(e, dx);
+        d = (double *)malloc(sizeof(double) * (size_t)(n > 0 ? n : 1));
+        if (!d) return JAICOV_ERR_OUT_OF_MEMORY;
+        double *p = (double *)(*e)->GetPrimitiveArrayCritical(e, dx, NULL);
+        if (!p) { free(d); return JAICOV_ERR_OUT_OF_MEMORY; }
+        memcpy(d, p, sizeof(double) * (size_t)n);
+        (*e)->ReleasePrimitiveArrayCritical(e, dx, p, JNI_ABORT);
+    }
+    int32_t n = 0;
+    const int rc = jaicov_rel_run(ENG(h), sigma2Test, d, &n);
+    free(d);
+    const jlong v = (jlong)n;
+    if (rc == JAICOV_OK) (*e)->SetLongArrayRegion(e, count, 0, 1, &v);
+    return rc;
+}
+/* v, qvv, r, t (each may be null, else at least n long) through malloc'd copies and SetDoubleArrayRegion */
+JNIEXPORT jint JNICALL NAT(relGet)(JNIEnv *e, jclass k, jlong h, jint n, jdoubleArray v, jdoubleArray qvv, jdoubleArray r, jdoubleArray t) {
+    (void)k;
+    jdoubleArray arr[4] = {v, qvv, r, t};
+    double *buf[4] = {NULL, NULL, NULL, NULL};
+    int rc = n < 0 ? JAICOV_ERR_BAD_ARGUMENT : JAICOV_OK;
+    for (int i = 0; i < 4 && rc == JAICOV_OK; i++) {
+        if (!arr[i]) continue;
+        if ((*e)->GetArrayLength(e, arr[i]) < n) rc = JAICOV_ERR_BAD_ARGUMENT;
+        else if (!(buf[i] = (double *)malloc(sizeof(double) * (size_t)(n > 0 ? n : 1)))) rc = JAICOV_ERR_OUT_OF_MEMORY;
+    }
+    if (rc == JAICOV_OK) rc = jaicov_rel_get(ENG(h), buf[0], buf[1], buf[2], buf[3], (int32_t)n);
+    for (int i = 0; i < 4; i++) {
+        if (rc == JAICOV_OK && buf[i]) (*e)->SetDoubleArrayRegion(e, arr[i], 0, n, buf[i]);
+        free(buf[i]);
+    }
+    return rc;
+}
+JNIEXPORT jint JNICALL NAT(relSummary)(JNIEnv *e, jclass k, jlong h, jdoubleArray out) {
+    (void)k;
+    if ((*e)->GetArrayLength(e, out) < 6) return JAICOV_ERR_BAD_ARGUMENT;
+    double s[6];
+    const int rc = jaicov_rel_summary(ENG(h), s, 6);
+    if (rc == JAICOV_OK) (*e)->SetDoubleArrayRegion(e, out, 0, 6, s);
+    return rc;
+}
+JNIEXPORT jint JNICALL NAT(relRelease)(JNIEnv *e, jclass k, jlong h) { (void)e; (void)k; return jaicov_rel_release(ENG(h)); }
 
 /* --- include/jaicov_dlt.h: DirectLinearTransformation.adjust for a batch of images (no engine) ---------------------------------- */
 /* the inputs are read through Get<Type>ArrayElements copies (JNI_ABORT); out comes back through SetDoubleArrayRegion, status and

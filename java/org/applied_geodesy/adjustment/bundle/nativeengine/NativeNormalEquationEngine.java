@@ -209,6 +209,29 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 	/** frees the device result of transform() */
 	public void releaseTransformation() { check(xformRelease(handle)); }
 
+	/**
+	 * Residuals v = A dx - w, residual cofactors qvv, redundancy numbers r and test values t of every observation row, in the order of
+	 * BundleAdjustment.java:670-771, after an inverting solve that left all of Qxx (JAICOV_INVERT_FULL / _FULL_EXPANDED).  sigma2Test:
+	 * the a-priori variance factor (Baarda's w-test) or the a-posteriori one (Pope's tau); dx: null (a zero step) or the step of the
+	 * inverting solve before update (exactly U doubles).  Returns the number of rows; the result stays on the device
+	 * (include/jaicov_reliability.h).
+	 */
+	public int reliability(double sigma2Test, double[] dx) {
+		long[] n = new long[1];
+		check(relRun(handle, sigma2Test, dx, n));
+		return (int) n[0];
+	}
+	/** the four vectors of the last reliability() (any array may be null, else n long; t is NaN for an uncontrolled row) */
+	public void getReliability(int n, double[] v, double[] qvv, double[] r, double[] t) { check(relGet(handle, n, v, qvv, r, t)); }
+	/** [0] sum of r, [1] max |t|, [2] its row, [3] rows with NaN t, [4] min r, [5] the damping of the inverted build (sum r = f needs 0) */
+	public double[] getReliabilitySummary() {
+		double[] out = new double[6];
+		check(relSummary(handle, out));
+		return out;
+	}
+	/** frees the device result of reliability() */
+	public void releaseReliability() { check(relRelease(handle)); }
+
 	/** jaicov_dlt status values (include/jaicov_dlt.h) */
 	public static final int DLT_CONVERGED = 0, DLT_NOT_CONVERGED = 1, DLT_TOO_FEW_POINTS = 2, DLT_SINGULAR = 3, DLT_NOT_FINITE = 4;
 
@@ -282,5 +305,9 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 	private static native int xformGetCovarianceSub(long h, int[] rows, double[] out);
 	private static native int xformGetPointBlocks(long h, double[] out);
 	private static native int xformRelease(long h);
+	private static native int relRun(long h, double sigma2Test, double[] dx, long[] count);
+	private static native int relGet(long h, int n, double[] v, double[] qvv, double[] r, double[] t);
+	private static native int relSummary(long h, double[] out);
+	private static native int relRelease(long h);
 	private static native int dltAdjust(int[] obsBegin, double[] xy, double[] xyz, double[] io, int[] ioFixed, int[] restrictions, int maxIterations, double[] out, long[] status, long[] solves);
 }
