@@ -36,13 +36,10 @@ hipError_t launch_schur_expand_f(hipStream_t, const DevProblem &, const int32_t 
                                  const double *, double *, long);
 hipError_t launch_omega(hipStream_t, const DevProblem &, const uint8_t *, int, int, const int32_t *, int, int,
                         const double *, const double *, const double *, double, double *, double *);
-}  // namespace jaicov
-
-namespace jaicov {
 struct RefineBorder { double kappa[7]; double rk[7]; };
 hipError_t launch_residual_dd(hipStream_t, const double *, long, int, int, int, const double *, const double *, const double *,
                               const double *, const double *, long, const RefineBorder &, double *, double *);
-}
+}  // namespace jaicov
 using namespace jaicov;
 
 static const double EPS53 = 1.1102230246251565e-16;   // Constant.EPS = 2^-53 (Constant.java:68-75)
@@ -197,15 +194,37 @@ __global__ void store_inv_kernel(const double *__restrict__ Q, long ld, int m, d
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// One owner for a device allocation that only grows: pointer and element count never get out of step, and the memory is
+// freed exactly once, by the destructor.  hipFree waits for the device by itself, so an owner may go out of scope on an
+// error path with work still in flight; on a success path the caller synchronises its stream first.
+template <typename T>
+class DevBuf {
+    T *ptr_ = nullptr;
+    size_t count_ = 0;
+  public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : ptr_(o.ptr_), count_(o.count_) { o.ptr_ = nullptr; o.count_ = 0; }   // move-only: no copies, no assignment
+    ~DevBuf() { if (ptr_) hipFree(ptr_); }
+    // room for `count` elements: the allocation at hand if it is large enough, otherwise a new one (the contents are lost)
+    hipError_t reserve(size_t count) {
+        if (count <= count_) return hipSuccess;
+        if (ptr_) hipFree(ptr_);
+        ptr_ = nullptr; count_ = 0;
+        const hipError_t err = hipMalloc(&ptr_, count * sizeof(T));
+        if (err == hipSuccess) count_ = count; else ptr_ = nullptr;
+        return err;
+    }
+    T *get() const { return ptr_; }
+};
+
 struct jaicov_engine {
     std::string err = "";
     int device = 0;
     int flow_retries = 0;      // dataflow factorisations that were abandoned and repeated (solve)
-    double *ns_work = nullptr; // three squares of the inverse's Newton-Schulz step (orders <= 8192, option inverse_refinement)
-    size_t ns_work_len = 0;
+    DevBuf<double> ns_work;    // three squares of the inverse's Newton-Schulz step (orders <= 8192, option inverse_refinement)
     int refine_steps = 1;      // iterative refinement of the step (refine.hip): engine option `refinement` / JAICOV_REFINE
-    double *d_Braw = nullptr, *d_refP = nullptr, *d_ref = nullptr;   // unscaled datum rows; partial-sum table; rhs | tmp | delta
-    size_t refP_len = 0;
+    double *d_Braw = nullptr, *d_ref = nullptr;   // unscaled datum rows; rhs | tmp | delta
+    DevBuf<double> refP;       // partial-sum table of the refinement's residual
     double last_refine_correction = 0.0;   // max |correction| / max |dx| of the last refinement step (diagnostics)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // assembly: camera-side kernels on a side stream (assemble.hip)
     hipStream_t stream = nullptr;
@@ -232,10 +251,9 @@ struct jaicov_engine {
     double dm_flops_per_pass = 0.0, dm_stat_passes = 0.0, dm_stat_ms = 0.0, dm_stat_flops = 0.0;
     int inverse_mode_next = 0;       // JAICOV_INVERT_* announced for the solve after the next build
     bool all_images = true;          // this engine accumulates every image (not a shard): FULL_EXPANDED needs every image's F band and L_E ...
-    double *d_expF = nullptr;        // ... a shard's caller sums them over the ranks: [F (6 images padded x reduced order padded) | Linv (36 per image)]
-    size_t expF_len = 0;
+    DevBuf<double> expF;             // ... a shard's caller sums them over the ranks: [F (6 images padded x reduced order padded) | Linv (36 per image)]
+    size_t expF_len = 0;             // the length in use (the allocation only grows)
     bool exp_ready = false;          // d_expF belongs to the system accumulated last and has been handed out (jaicov_neq_expansion_buffer)
-    bool solver_has_Q = false;       // solver.Q alone is allocated (target of the expansion)
     int q_order = 0;                 // order of the cofactor matrix on the device (U, or e0 for the reduced one)
     bool q_reduced = false, solverS_has_inverse = false;
     std::vector<int> h_blk_images;   // image of every block handled by this engine
@@ -273,7 +291,7 @@ struct jaicov_engine {
     double timings[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double create_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // jaicov_neq_create: [0] whole call, [1] host time in the dispersion uploads, [2] dispersions -> weights (wall),
                                                       // [3] validation + tables + structure upload, [4] work buffers + full-order solver, [5] EO pre-elimination buffers + reduced solver
-    hipEvent_t ev[10];
+    hipEvent_t ev[10] = {};
     bool pp_plain_ok = false;   // the point x point gather may store its strips (see PPGather::plain)
     hipEvent_t ev_first = nullptr, ev_all = nullptr;   // solve(): first panel's columns / whole matrix copied into the solver
     hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;       // solve(): device part of a refinement step
@@ -297,6 +315,7 @@ struct jaicov_engine {
             return _err == hipErrorOutOfMemory ? JAICOV_ERR_OUT_OF_MEMORY : JAICOV_ERR_DEVICE; \
         }                                                                                 \
     } while (0)
+#define TRY(x) do { const int _rc = (x); if (_rc) return _rc; } while (0)      // a callee's status (JAICOV_*), passed on
 
 template <typename T>
 static int upload(jaicov_engine *e, const T *src, size_t count, const T **dst) {
@@ -488,15 +507,8 @@ extern "C" void jaicov_neq_destroy(jaicov_engine *e) {
     for (void *ptr : e->allocs) hipFree(ptr);
     for (auto &evt : e->ev)
         if (evt) hipEventDestroy(evt);
-    if (e->ev_fork) hipEventDestroy(e->ev_fork);
-    if (e->ev_join) hipEventDestroy(e->ev_join);
-    if (e->ev_first) hipEventDestroy(e->ev_first);
-    if (e->ev_all) hipEventDestroy(e->ev_all);
-    if (e->ev_r0) hipEventDestroy(e->ev_r0);
-    if (e->ev_r1) hipEventDestroy(e->ev_r1);
-    if (e->d_refP) hipFree(e->d_refP);
-    if (e->d_expF) hipFree(e->d_expF);
-    if (e->ns_work) hipFree(e->ns_work);
+    for (hipEvent_t evt : {e->ev_fork, e->ev_join, e->ev_first, e->ev_all, e->ev_r0, e->ev_r1})
+        if (evt) hipEventDestroy(evt);
     jaicov::stream_release(jaicov::STREAM_PLAIN, e->stream);
     delete e;
 }
@@ -1059,7 +1071,6 @@ extern "C" int jaicov_neq_create(const jaicov_problem_desc *desc, const jaicov_e
     int rc = check_device(err);
     if (rc != JAICOV_OK) return rc;
     jaicov_engine *e = new jaicov_engine();
-    for (auto &evt : e->ev) evt = nullptr;
     if (opts) {
         if (opts->struct_size != sizeof(jaicov_engine_options)) { delete e; return JAICOV_ERR_BAD_ARGUMENT; }
         e->opts = *opts;
@@ -1111,8 +1122,7 @@ extern "C" int jaicov_neq_accumulate(jaicov_engine *e, double sigma2) {
     e->sigma2_acc = sigma2;
     const size_t sq = (size_t)e->Upad * e->Upad;
     HIPE(e, hipEventRecord(e->ev[0], e->stream));
-    int rc = ensure_rows(e);
-    if (rc) return rc;
+    TRY(ensure_rows(e));
     HIPE(e, hipEventRecord(e->ev[1], e->stream));
     e->schur_active = e->schur_ok && e->inverse_mode_next != JAICOV_INVERT_FULL;
     // The point x point gather owns every entry of rows cmin..cmax from column cmin on: when it runs before everything
@@ -1214,8 +1224,7 @@ extern "C" int jaicov_neq_finalize(jaicov_engine *e, double sigma2, double lambd
     (void)sigma2;
     if (e->state != jaicov_engine::ST_ACCUMULATED) FAIL(e, JAICOV_ERR_BAD_STATE, "accumulate first");
     HIPE(e, hipSetDevice(e->device));
-    int rc = datum_rows_host(e);
-    if (rc) return rc;
+    TRY(datum_rows_host(e));
     if (e->reduced) {   // the host has summed the packed buffer over ranks: bring it back into the square
         const int Ua = e->schur_active ? e->e0 : e->U;
         const size_t len = (size_t)Ua * (Ua + 1) / 2;
@@ -1238,16 +1247,29 @@ extern "C" int jaicov_neq_finalize(jaicov_engine *e, double sigma2, double lambd
     return JAICOV_OK;
 }
 
-// buffers of the inverse (W = L^-1 and Q, two squares of the solver's order) of the solver that the announced mode will use
-static int ensure_inverse_buffers(jaicov_engine *e, bool reduced_system) {
+// buffers of the inverse (W = L^-1 and Q, two squares of the solver's order) of the solver that factorises; for the effective mode
+// FULL_EXPANDED also the Q of the full-order solver, where the expanded matrix lives
+static int ensure_inverse_buffers(jaicov_engine *e, bool reduced_system, int mode) {
     DenseSolver &slv = reduced_system ? e->solverS : e->solver;
     bool &has_inv = reduced_system ? e->solverS_has_inverse : e->solver_has_inverse;
-    if (has_inv) return JAICOV_OK;
-    const size_t sq = (size_t)slv.n * slv.ld * sizeof(double);
-    HIPE(e, hipMalloc(&slv.W, sq));
-    if (!slv.Q) HIPE(e, hipMalloc(&slv.Q, sq));
-    has_inv = true;
+    if (!has_inv) {
+        const size_t sq = (size_t)slv.n * slv.ld * sizeof(double);
+        HIPE(e, hipMalloc(&slv.W, sq));
+        if (!slv.Q) HIPE(e, hipMalloc(&slv.Q, sq));
+        has_inv = true;
+    }
+    if (mode == JAICOV_INVERT_FULL_EXPANDED && !e->solver.Q)
+        HIPE(e, hipMalloc(&e->solver.Q, (size_t)e->solver.n * e->solver.ld * sizeof(double)));
     return JAICOV_OK;
+}
+
+// the expansion's workspace is the reduced solver's W square: F and T1 ([6 images, padded] x order) and T2 must fit (they do
+// unless the exterior orientations outnumber the other unknowns several times over: then the literal route is taken)
+// *I6p: EO unknowns of all images, padded; *Up: padded order of the reduced system
+static bool expansion_fits(const jaicov_engine *e, size_t *I6p, size_t *Up) {
+    *I6p = ((size_t)6 * e->p.n_images + 127) / 128 * 128;
+    *Up = (size_t)e->solverS.nfact;
+    return *I6p * (2 * *Up + *I6p) <= (size_t)e->solverS.n * e->solverS.ld;
 }
 
 // FULL_EXPANDED is FULL wherever the expansion cannot be done: no EO pre-elimination, or an engine that sees a shard of the images
@@ -1255,11 +1277,8 @@ static int ensure_inverse_buffers(jaicov_engine *e, bool reduced_system) {
 static int effective_invert(const jaicov_engine *e, int invert) {
     if (invert != JAICOV_INVERT_FULL_EXPANDED) return invert;
     if (!(e->schur_ok && (e->all_images || e->opts.expansion_exchange != 0) && e->solverS_ready)) return JAICOV_INVERT_FULL;
-    // the expansion's workspace is the reduced solver's W square: F and T1 ([6 images, padded] x order) and T2 must fit (they do
-    // unless the exterior orientations outnumber the other unknowns several times over: then the literal route is taken)
-    const size_t I6p = ((size_t)6 * e->p.n_images + 127) / 128 * 128, Up = (size_t)e->solverS.nfact;
-    if (I6p * (2 * Up + I6p) > (size_t)e->solverS.n * e->solverS.ld) return JAICOV_INVERT_FULL;
-    return invert;
+    size_t I6p, Up;
+    return expansion_fits(e, &I6p, &Up) ? invert : JAICOV_INVERT_FULL;
 }
 
 extern "C" int jaicov_neq_prepare_inverse(jaicov_engine *e, int inverse_follows) {
@@ -1269,17 +1288,10 @@ extern "C" int jaicov_neq_prepare_inverse(jaicov_engine *e, int inverse_follows)
     e->inverse_mode_next = inverse_follows;
     // the inverse's buffers are allocated HERE, when the final pass is announced (BA:250: known before the build), not inside
     // the solve: hipMalloc of 2 x 1.8 .. 2.6 GB cost the first inverting solve 45 ms at config 4
-    if (inverse_follows != JAICOV_INVERT_NONE) {
-        HIPE(e, hipSetDevice(e->device));
-        const bool reduced = e->schur_ok && (inverse_follows == JAICOV_INVERT_REDUCED || inverse_follows == JAICOV_INVERT_FULL_EXPANDED) && e->solverS_ready;
-        int rc = ensure_inverse_buffers(e, reduced);
-        if (rc) return rc;
-        if (inverse_follows == JAICOV_INVERT_FULL_EXPANDED && !e->solver.Q) {     // the expanded matrix lives in the full-order solver's Q
-            HIPE(e, hipMalloc(&e->solver.Q, (size_t)e->solver.n * e->solver.ld * sizeof(double)));
-            e->solver_has_Q = true;
-        }
-    }
-    return JAICOV_OK;
+    if (inverse_follows == JAICOV_INVERT_NONE) return JAICOV_OK;
+    HIPE(e, hipSetDevice(e->device));
+    const bool reduced = e->schur_ok && (inverse_follows == JAICOV_INVERT_REDUCED || inverse_follows == JAICOV_INVERT_FULL_EXPANDED) && e->solverS_ready;
+    return ensure_inverse_buffers(e, reduced, inverse_follows);
 }
 
 extern "C" int jaicov_neq_cofactor_order(const jaicov_engine *e) {
@@ -1301,8 +1313,7 @@ extern "C" int jaicov_neq_accumulate2(jaicov_engine *e, double sigma2, double la
 extern "C" int jaicov_neq_build(jaicov_engine *e, double sigma2, double lambda, int simulation) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     e->lambda_acc = lambda > 0 ? lambda : 0.0;
-    int rc = jaicov_neq_accumulate(e, sigma2);
-    if (rc) return rc;
+    TRY(jaicov_neq_accumulate(e, sigma2));
     return jaicov_neq_finalize(e, sigma2, lambda, simulation);
 }
 
@@ -1314,10 +1325,7 @@ static int reduce_buffer_impl(jaicov_engine *e, void **device_ptr, size_t *count
     // With the EO pre-elimination only the reduced system (order e0) exists.
     const int Ua = e->schur_active ? e->e0 : e->U;
     const size_t len = (size_t)Ua * (Ua + 1) / 2;
-    if (!e->d_packed) {
-        int rc = dalloc(e, (size_t)e->U * (e->U + 1) / 2 + 2 * (size_t)e->U, &e->d_packed);
-        if (rc) return rc;
-    }
+    if (!e->d_packed) TRY(dalloc(e, (size_t)e->U * (e->U + 1) / 2 + 2 * (size_t)e->U, &e->d_packed));
     hipLaunchKernelGGL(pack_kernel, dim3((Ua + 255) / 256, std::max(Ua, 1)), dim3(256), 0, e->stream, e->d_N, (long)e->Upad, Ua, e->d_packed);
     HIPE(e, hipMemcpyAsync(e->d_packed + len, e->d_n, (size_t)Ua * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
     // with the EO pre-elimination the LM damping needs diag(N) - diag(N_reduced), also a sum over the ranks' images
@@ -1367,227 +1375,107 @@ static bool small_inverse(int d, const double *S, double *Sinv) {
     return true;
 }
 
-extern "C" int jaicov_neq_solve(jaicov_engine *e, int invert, double *dx_out) {
-    if (!e || !dx_out) return JAICOV_ERR_BAD_ARGUMENT;
-    if (e->state != jaicov_engine::ST_BUILT) FAIL(e, JAICOV_ERR_BAD_STATE, "build first");
-    HIPE(e, hipSetDevice(e->device));
-    const bool schur = e->schur_active;
-    if (invert < 0 || invert > JAICOV_INVERT_FULL_EXPANDED) return JAICOV_ERR_BAD_ARGUMENT;
-    invert = effective_invert(e, invert);
-    if (invert == JAICOV_INVERT_FULL_EXPANDED && !schur) invert = JAICOV_INVERT_FULL;     // the system at hand was assembled unreduced
-    const bool expand = invert == JAICOV_INVERT_FULL_EXPANDED;
-    if (schur && invert == JAICOV_INVERT_FULL)
-        FAIL(e, JAICOV_ERR_BAD_STATE, "the normal equations were assembled with the EO blocks pre-eliminated: call "
-                                      "jaicov_neq_prepare_inverse(e, JAICOV_INVERT_FULL) before the build whose solve shall invert");
-    // order of the system that is factorised: the reduced one (points, IO, distortion) or the full one
-    const int U = schur ? e->e0 : e->U, d = e->d, nrhs = d + 1;
-    const int Upad = e->Upad;                      // leading dimension of N, V, B and the rhs/solution vectors
-    if (schur && !e->solverS_ready) {
-        HIPE(e, e->solverS.init(e->stream, ((e->e0 + 127) / 128) * 128, false, true, &e->solver));
-        e->solverS_ready = true;
+// ---- one call of jaicov_neq_solve: what its stages share, then the stages in the order they run ------------------------------
+struct Solve {
+    jaicov_engine *const e;
+    const bool schur;                   // the EO-reduced system is at hand
+    const int U, d, Upad;               // order of the system that is factorised (reduced: points, IO, distortion; or full); rank of the datum border; ld of N, V, B, rhs
+    DenseSolver &slv;
+    const int Up, vs;                   // padded order of the factorised system == stride between the solution vectors (the solver's order)
+    const long ld;
+    int invert = 0;                     // the effective mode
+    bool expand = false;                // ... is FULL_EXPANDED: all of Qxx from the reduced inverse
+    std::vector<double> Bh, X, delta0;  // datum rows R B V [8][Upad]; y~ and G^ [d + 1][vs]; the correction of the device's own refinement step
+    double R[7] = {1, 1, 1, 1, 1, 1, 1}, Sinv[49];
+    bool fast_refined = false;          // d = 0: the first refinement step went out behind the substitution, without the host
+    float refine_ms = 0.f;
+    explicit Solve(jaicov_engine *eng)
+        : e(eng), schur(e->schur_active), U(schur ? e->e0 : e->U), d(e->d), Upad(e->Upad), slv(schur ? e->solverS : e->solver),
+          Up(slv.nfact), vs(Up), ld(slv.ld) {}
+
+    double border_dot(int a, const double *v) const {      // Bh[a] . v over the unknowns
+        double s = 0.0;
+        for (int c = d; c < U; c++) s += Bh[(size_t)a * Upad + c] * v[c];
+        return s;
     }
-    DenseSolver &slv = schur ? e->solverS : e->solver;
-    slv.profile = e->solver.profile;
-    slv.flops_order = (double)(schur ? e->e0 : e->U);
-    const int Up = slv.nfact;                      // padded order of the factorised system
-    const long ld = slv.ld;
-    if (invert) {   // normally done by prepare_inverse(); a host that did not announce the final pass pays the allocation here
-        const int rc_inv = ensure_inverse_buffers(e, schur);
-        if (rc_inv) return rc_inv;
-        if (expand && !e->solver.Q) {
-            HIPE(e, hipMalloc(&e->solver.Q, (size_t)e->solver.n * e->solver.ld * sizeof(double)));
-            e->solver_has_Q = true;
+    void border_multipliers(const double *v, const double *rk, double *k) const {      // k = S^-1 (Bh v - rk)
+        double t[7];
+        for (int a = 0; a < d; a++) t[a] = border_dot(a, v) - rk[a];
+        for (int a = 0; a < d; a++) {
+            double s = 0.0;
+            for (int b = 0; b < d; b++) s += Sinv[a * d + b] * t[b];
+            k[a] = s;
         }
+    }
+
+    int solve_mode(int requested) {
+        invert = effective_invert(e, requested);
+        if (invert == JAICOV_INVERT_FULL_EXPANDED && !schur) invert = JAICOV_INVERT_FULL;     // the system at hand was assembled unreduced
+        expand = invert == JAICOV_INVERT_FULL_EXPANDED;
+        if (schur && invert == JAICOV_INVERT_FULL)
+            FAIL(e, JAICOV_ERR_BAD_STATE, "the normal equations were assembled with the EO blocks pre-eliminated: call "
+                                          "jaicov_neq_prepare_inverse(e, JAICOV_INVERT_FULL) before the build whose solve shall invert");
+        slv.profile = e->solver.profile;
+        slv.flops_order = (double)U;
+        // normally done by prepare_inverse(); a host that did not announce the final pass pays the allocation here
+        return invert ? ensure_inverse_buffers(e, schur, invert) : JAICOV_OK;
     }
     // V to the host, scaled + row-normalised datum rows Bh = R B V (NES:82-91 scaling of the border)
     // This round trip stays even where nothing of it is needed before the factorisation (d = 0): with the host running ahead of
     // the assembly -- enqueuing the factorisation and spinning in its residency handshake while the assembly kernels still run --
     // every pass was 0.6 ms SLOWER (assembly +0.19, factorisation +0.4; measured A/B in round 3).
-    // What d = 0 does save is the round trip between the substitution and the first refinement step (`fast` below).
-    const bool fast = d == 0;
-    int hinfo = 0;   // status of the per-image EO eliminations, fetched in the same round trip
-    {
+    // What d = 0 does save is the round trip between the substitution and the first refinement step (factor_and_substitute).
+    int border_rows() {
+        int hinfo = 0;   // status of the per-image EO eliminations, fetched in the same round trip
         HIPE(e, hipMemcpyAsync(e->h_V.data(), e->d_V, Upad * sizeof(double), hipMemcpyDeviceToHost, e->stream));
         if (schur) HIPE(e, hipMemcpyAsync(&hinfo, e->sb.info, sizeof(int), hipMemcpyDeviceToHost, e->stream));
         HIPE(e, hipStreamSynchronize(e->stream));
         if (hinfo != 0) FAIL(e, JAICOV_ERR_SINGULAR, "exterior orientation block of image " + std::to_string(hinfo - 1000000) + " is not positive definite");
-    }
-    std::vector<double> Bh((size_t)8 * Upad, 0.0);
-    double R[7] = {1, 1, 1, 1, 1, 1, 1};
-    for (int a = 0; a < d; a++) {
-        double s = 0.0;
-        for (int c = d; c < U; c++) {
-            const double v = e->hB[(size_t)a * Upad + c] * e->h_V[c];
-            Bh[(size_t)a * Upad + c] = v;
-            s += v * v;
-        }
-        if (!(s > 0.0)) FAIL(e, JAICOV_ERR_SINGULAR, "empty datum condition row");
-        R[a] = 1.0 / sqrt(s);
-        for (int c = d; c < U; c++) Bh[(size_t)a * Upad + c] *= R[a];
-    }
-    if (d > 0) HIPE(e, hipMemcpyAsync(e->d_B, Bh.data(), (size_t)d * Upad * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    HIPE(e, hipEventRecord(e->ev[4], e->stream));
-    // right-hand sides: row 0 = V n, rows 1..d = Bh.  They are the extra rows below the matrix, so the factorisation
-    // itself carries out the forward substitution (dense.hip).
-    const int vs = Up;   // stride between the solution vectors (the solver's order)
-    const bool fused = slv.flow_ready;
-    const int c1 = std::min(slv.first_panel_cols(), Up);
-    // dataflow factorisation: the tile kernel reads N itself and scales on the fly (no copy of the matrix at all);
-    // stream-scheduled one: the columns of the first panel go first, together with the right-hand sides; the panel then
-    // factors on its stream while the rest of the matrix is still being scaled and copied (0.4 ms at config 4).
-    // (in a loop: a dataflow factorisation that was abandoned -- cholflow.hip, "Visibility": a wait ran into its time limit, seen
-    // about once in 1 000 factorisations at config 4 -- is repeated; N, V and the datum rows are untouched by it)
-    std::vector<double> X, delta0;
-    bool fast_refined = false;
-    int info = 0;
-    for (int attempt = 0;; attempt++) {
-    HIPE(e, slv.begin_refactor());      // the side stream's premultiply of the last pass may still read the old factor: nothing writes L before this
-    if (!fused)
-        hipLaunchKernelGGL(scale_copy_kernel, dim3((c1 + 255) / 256, Up), dim3(256), 0, e->stream, e->d_N, (long)Upad, slv.L, ld, U,
-                           Up, d, e->d_V, e->d_B, Upad, 0, c1);
-    HIPE(e, hipMemsetAsync(slv.rhs_row(0), 0, (size_t)128 * ld * sizeof(double), e->stream));
-    hipLaunchKernelGGL(scale_vec_kernel, dim3((Up + 255) / 256), dim3(256), 0, e->stream, e->d_n, e->d_V, slv.rhs_row(0), U, Up, d);
-    if (d > 0)
-        HIPE(e, hipMemcpy2DAsync(slv.rhs_row(1), (size_t)ld * sizeof(double), e->d_B, (size_t)Upad * sizeof(double),
-                                 (size_t)Up * sizeof(double), (size_t)d, hipMemcpyDeviceToDevice, e->stream));
-    HIPE(e, hipEventRecord(e->ev_first, e->stream));
-    if (!fused && c1 < Up)
-        hipLaunchKernelGGL(scale_copy_kernel, dim3((Up - c1 + 255) / 256, Up), dim3(256), 0, e->stream, e->d_N, (long)Upad, slv.L,
-                           ld, U, Up, d, e->d_V, e->d_B, Upad, c1, Up);
-    HIPE(e, hipEventRecord(e->ev_all, e->stream));
-    if (fused) slv.flow_set_source(e->d_N, (long)Upad, e->d_V, e->d_B, Upad, d, U);
-    HIPE(e, slv.potrf(e->ev_first, e->ev_all));
-    HIPE(e, hipEventRecord(e->ev[5], e->stream));
-    HIPE(e, slv.backsolve_aug(e->d_G, vs, nrhs));           // G <- L^-T (L^-1 Y)   (row 0: y~, rows 1..d: G^)
-    HIPE(e, hipEventRecord(e->ev[6], e->stream));
-    X.assign((size_t)nrhs * vs, 0.0);
-    HIPE(e, hipMemcpyAsync(X.data(), e->d_G, X.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    fast_refined = false;
-    if (fast && e->refine_steps >= 1 && !e->sim_built) {
-        // first refinement step without the host: dx = V y on the device, residual of the unscaled system in two-fold precision,
-        // forward + backward substitution (refine.hip, dense.hip); the correction comes back together with y
-        const int nbk = Up / 128;
-        const size_t need = (size_t)nbk * nbk * 256;
-        if (e->refP_len < need) {
-            if (e->d_refP) hipFree(e->d_refP);
-            e->d_refP = nullptr; e->refP_len = 0;
-            HIPE(e, hipMalloc(&e->d_refP, need * sizeof(double)));
-            e->refP_len = need;
-        }
-        double *d_rhs = e->d_ref, *d_tmp = e->d_ref + Upad, *d_delta = e->d_ref + 2 * (size_t)Upad;
-        HIPE(e, hipEventRecord(e->ev_r0, e->stream));
-        hipLaunchKernelGGL(scale_vec_kernel, dim3((Up + 255) / 256), dim3(256), 0, e->stream, e->d_G, e->d_V, e->d_dx, U, Up, 0);   // dx = V y
-        HIPE(e, launch_residual_dd(e->stream, e->d_N, (long)Upad, U, 0, Up, e->d_dx, e->d_n, e->d_V, e->d_Braw, e->d_B, (long)Upad,
-                                   RefineBorder{}, e->d_refP, d_rhs));
-        HIPE(e, slv.solve_rhs(d_rhs, d_tmp, d_delta));
-        HIPE(e, hipEventRecord(e->ev_r1, e->stream));
-        delta0.assign((size_t)Up, 0.0);
-        HIPE(e, hipMemcpyAsync(delta0.data(), d_delta, delta0.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-        fast_refined = true;
-    }
-    info = slv.fetch_info();
-    if (info == -9 && attempt < 2) {
-        ++e->flow_retries;
-        fprintf(stderr, "jaicov: factorisation abandoned on the device (a wait ran into its time limit); repeating it (%d)\n", attempt + 1);
-        continue;
-    }
-    break;
-    }
-    if (info < 0) FAIL(e, JAICOV_ERR_DEVICE, "factorisation did not complete on the device (code " + std::to_string(info) + ")");
-    if (info != 0) FAIL(e, JAICOV_ERR_SINGULAR, "normal-equation matrix is singular / not positive definite at pivot " + std::to_string(info));
-    // ---- rank-d border algebra on the host ---------------------------------------------------------------------
-    double Sm[49], Sinv[49], kh[7];
-    std::vector<double> y(X.begin(), X.begin() + vs);
-    if (d > 0) {
-        for (int a = 0; a < d; a++)
-            for (int b = 0; b < d; b++) {
-                double s = 0.0;
-                for (int c = d; c < U; c++) s += Bh[(size_t)a * Upad + c] * X[(size_t)(1 + b) * vs + c];
-                Sm[a * d + b] = s;
+        Bh.assign((size_t)8 * Upad, 0.0);
+        for (int a = 0; a < d; a++) {
+            double s = 0.0;
+            for (int c = d; c < U; c++) {
+                const double v = e->hB[(size_t)a * Upad + c] * e->h_V[c];
+                Bh[(size_t)a * Upad + c] = v;
+                s += v * v;
             }
-        if (!small_inverse(d, Sm, Sinv)) FAIL(e, JAICOV_ERR_SINGULAR, "datum conditions are linearly dependent");
-        double by[7];
-        for (int a = 0; a < d; a++) {
-            double s = 0.0;
-            for (int c = d; c < U; c++) s += Bh[(size_t)a * Upad + c] * X[c];
-            by[a] = s;
+            if (!(s > 0.0)) FAIL(e, JAICOV_ERR_SINGULAR, "empty datum condition row");
+            R[a] = 1.0 / sqrt(s);
+            for (int c = d; c < U; c++) Bh[(size_t)a * Upad + c] *= R[a];
         }
-        for (int a = 0; a < d; a++) {
-            double s = 0.0;
-            for (int b = 0; b < d; b++) s += Sinv[a * d + b] * by[b];
-            kh[a] = s;
-        }
-        for (int c = d; c < U; c++) {
-            double s = 0.0;
-            for (int a = 0; a < d; a++) s += X[(size_t)(1 + a) * vs + c] * kh[a];
-            y[c] -= s;
-        }
+        if (d > 0) HIPE(e, hipMemcpyAsync(e->d_B, Bh.data(), (size_t)d * Upad * sizeof(double), hipMemcpyHostToDevice, e->stream));
+        HIPE(e, hipEventRecord(e->ev[4], e->stream));
+        return JAICOV_OK;
     }
-    for (int c = 0; c < U; c++) dx_out[c] = c < d ? R[c] * kh[c] : e->h_V[c] * y[c];
-    for (int c = 0; c < U; c++)
-        if (!std::isfinite(dx_out[c])) FAIL(e, JAICOV_ERR_NOT_FINITE, "non-finite step");
     // ---- iterative refinement (refine.hip): residual of the unscaled bordered system in two-fold precision, one forward and
     // one backward substitution with the factor at hand per step.  The correction of the border follows the same rank-d
-    // algebra as above with r_y = V rho_x, r_k = R rho_kappa:  delta0 = M^-1 (r_y + Bh' r_k),
+    // algebra as the step itself with r_y = V rho_x, r_k = R rho_kappa:  delta0 = M^-1 (r_y + Bh' r_k),
     // dk = S^-1 (Bh delta0 - r_k),  dy = delta0 - G^ dk.
-    float refine_ms = 0.f;
-    e->last_refine_correction = 0.0;
-    if (fast_refined) {      // the step the device took on its own (d = 0: no border algebra): dx += V delta
-        hipEventElapsedTime(&refine_ms, e->ev_r0, e->ev_r1);
-        double cmax = 0.0, xmax = 0.0;
-        for (int c = 0; c < U; c++) {
-            const double corr = e->h_V[c] * delta0[c];
-            if (!std::isfinite(corr)) FAIL(e, JAICOV_ERR_NOT_FINITE, "non-finite refinement step");
-            dx_out[c] += corr;
-            cmax = std::max(cmax, fabs(corr)); xmax = std::max(xmax, fabs(dx_out[c]));
-        }
-        e->last_refine_correction = xmax > 0.0 ? cmax / xmax : 0.0;
-    }
-    for (int step = fast_refined ? 1 : 0; step < e->refine_steps && !e->sim_built; step++) {
+    // The device's part of a step: refine_begin, then whatever gives d_dx its value, then refine_step.
+    int refine_begin() {
         const int nbk = Up / 128;
-        const size_t need = (size_t)nbk * nbk * 256;
-        if (e->refP_len < need) {
-            if (e->d_refP) hipFree(e->d_refP);
-            e->d_refP = nullptr; e->refP_len = 0;
-            HIPE(e, hipMalloc(&e->d_refP, need * sizeof(double)));
-            e->refP_len = need;
-        }
-        RefineBorder bd{};
-        for (int a = 0; a < d; a++) {
-            long double sacc = 0.0L;
-            for (int c = d; c < U; c++) sacc += (long double)e->hB[(size_t)a * Upad + c] * (long double)dx_out[c];
-            bd.kappa[a] = dx_out[a];
-            bd.rk[a] = (double)(-(long double)R[a] * sacc);
-        }
-        double *d_rhs = e->d_ref, *d_tmp = e->d_ref + Upad, *d_delta = e->d_ref + 2 * (size_t)Upad;
+        HIPE(e, e->refP.reserve((size_t)nbk * nbk * 256));      // ahead of the event: an allocation is no part of the step's time
         HIPE(e, hipEventRecord(e->ev_r0, e->stream));
-        if (d > 0 && step == 0)
-            HIPE(e, hipMemcpyAsync(e->d_Braw, e->hB.data(), (size_t)d * Upad * sizeof(double), hipMemcpyHostToDevice, e->stream));
-        HIPE(e, hipMemcpyAsync(e->d_dx, dx_out, (size_t)U * sizeof(double), hipMemcpyHostToDevice, e->stream));
+        return JAICOV_OK;
+    }
+    // residual of d_dx, delta = M^-1 residual, and delta on its way to the host (complete once the stream has been synchronised)
+    int refine_step(const RefineBorder &bd, std::vector<double> &delta) {
+        double *d_rhs = e->d_ref, *d_tmp = e->d_ref + Upad, *d_delta = e->d_ref + 2 * (size_t)Upad;
         HIPE(e, launch_residual_dd(e->stream, e->d_N, (long)Upad, U, d, Up, e->d_dx, e->d_n, e->d_V, e->d_Braw, e->d_B, (long)Upad,
-                                   bd, e->d_refP, d_rhs));
+                                   bd, e->refP.get(), d_rhs));
         HIPE(e, slv.solve_rhs(d_rhs, d_tmp, d_delta));
         HIPE(e, hipEventRecord(e->ev_r1, e->stream));
-        std::vector<double> dl((size_t)Up);
-        HIPE(e, hipMemcpyAsync(dl.data(), d_delta, dl.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-        HIPE(e, hipStreamSynchronize(e->stream));
+        delta.assign((size_t)Up, 0.0);
+        HIPE(e, hipMemcpyAsync(delta.data(), d_delta, delta.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        return JAICOV_OK;
+    }
+    // a completed step: its time, dx += the correction that belongs to delta (d = 0: V delta), max |correction| / max |dx|
+    int apply_correction(const RefineBorder &bd, const std::vector<double> &dl, double *dx_out) {
         float ms1 = 0.f;
         hipEventElapsedTime(&ms1, e->ev_r0, e->ev_r1);
         refine_ms += ms1;
         double dk[7] = {0, 0, 0, 0, 0, 0, 0};
-        if (d > 0) {
-            double tt[7];
-            for (int a = 0; a < d; a++) {
-                double sacc = 0.0;
-                for (int c = d; c < U; c++) sacc += Bh[(size_t)a * Upad + c] * dl[c];
-                tt[a] = sacc - bd.rk[a];
-            }
-            for (int a = 0; a < d; a++) {
-                double sacc = 0.0;
-                for (int b = 0; b < d; b++) sacc += Sinv[a * d + b] * tt[b];
-                dk[a] = sacc;
-            }
-        }
+        border_multipliers(dl.data(), bd.rk, dk);
         double cmax = 0.0, xmax = 0.0;
         for (int c = d; c < U; c++) {
             double dy = dl[c];
@@ -1599,74 +1487,180 @@ extern "C" int jaicov_neq_solve(jaicov_engine *e, int invert, double *dx_out) {
         }
         for (int a = 0; a < d; a++) dx_out[a] += R[a] * dk[a];
         e->last_refine_correction = xmax > 0.0 ? cmax / xmax : 0.0;
+        return JAICOV_OK;
     }
-    if (schur && e->sim_built) {
-        // SIMULATION zeroes the right-hand side of the WHOLE system (BA:830-831 `n.zero()`): the eliminated exterior
-        // orientations get no step either (their back substitution would use the real misclosures)
-        for (int c = U; c < e->U; c++) dx_out[c] = 0.0;
-    } else if (schur && e->opts.reduced_reference_quirk && invert == JAICOV_INVERT_REDUCED) {
-        // what the reference's last pass leaves in the EO entries of dx under MatrixInversion.REDUCED (quirk Q1): V_c^2 n_c
-        std::vector<double> xq((size_t)6 * e->p.n_images);
-        HIPE(e, hipMemcpyAsync(xq.data(), e->sb.xq, xq.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-        HIPE(e, hipStreamSynchronize(e->stream));
-        for (int c = U; c < e->U; c++) dx_out[c] = 0.0;
-        for (int img : e->h_blk_images)
-            for (int k = 0; k < 6; k++) dx_out[e->e0 + 6 * img + k] = xq[(size_t)6 * img + k];
-    } else if (schur) {
-        // EO step of every image of this engine: dx_E = L_E^-T U' (w - A_r dx_R)   (schur.hip)
-        for (int c = U; c < e->U; c++) dx_out[c] = 0.0;
-        HIPE(e, hipMemcpyAsync(e->d_dx, dx_out, (size_t)e->U * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    // right-hand sides: row 0 = V n, rows 1..d = Bh.  They are the extra rows below the matrix, so the factorisation
+    // itself carries out the forward substitution (dense.hip).
+    // dataflow factorisation: the tile kernel reads N itself and scales on the fly (no copy of the matrix at all);
+    // stream-scheduled one: the columns of the first panel go first, together with the right-hand sides; the panel then
+    // factors on its stream while the rest of the matrix is still being scaled and copied (0.4 ms at config 4).
+    // (in a loop: a dataflow factorisation that was abandoned -- cholflow.hip, "Visibility": a wait ran into its time limit, seen
+    // about once in 1 000 factorisations at config 4 -- is repeated; N, V and the datum rows are untouched by it)
+    int factor_and_substitute() {
+        const int nrhs = d + 1;
+        const bool fused = slv.flow_ready;
+        const int c1 = std::min(slv.first_panel_cols(), Up);
+        int info = 0;
+        for (int attempt = 0;; attempt++) {
+            HIPE(e, slv.begin_refactor());      // the side stream's premultiply of the last pass may still read the old factor: nothing writes L before this
+            if (!fused)
+                hipLaunchKernelGGL(scale_copy_kernel, dim3((c1 + 255) / 256, Up), dim3(256), 0, e->stream, e->d_N, (long)Upad, slv.L, ld, U,
+                                   Up, d, e->d_V, e->d_B, Upad, 0, c1);
+            HIPE(e, hipMemsetAsync(slv.rhs_row(0), 0, (size_t)128 * ld * sizeof(double), e->stream));
+            hipLaunchKernelGGL(scale_vec_kernel, dim3((Up + 255) / 256), dim3(256), 0, e->stream, e->d_n, e->d_V, slv.rhs_row(0), U, Up, d);
+            if (d > 0)
+                HIPE(e, hipMemcpy2DAsync(slv.rhs_row(1), (size_t)ld * sizeof(double), e->d_B, (size_t)Upad * sizeof(double),
+                                         (size_t)Up * sizeof(double), (size_t)d, hipMemcpyDeviceToDevice, e->stream));
+            HIPE(e, hipEventRecord(e->ev_first, e->stream));
+            if (!fused && c1 < Up)
+                hipLaunchKernelGGL(scale_copy_kernel, dim3((Up - c1 + 255) / 256, Up), dim3(256), 0, e->stream, e->d_N, (long)Upad, slv.L,
+                                   ld, U, Up, d, e->d_V, e->d_B, Upad, c1, Up);
+            HIPE(e, hipEventRecord(e->ev_all, e->stream));
+            if (fused) slv.flow_set_source(e->d_N, (long)Upad, e->d_V, e->d_B, Upad, d, U);
+            HIPE(e, slv.potrf(e->ev_first, e->ev_all));
+            HIPE(e, hipEventRecord(e->ev[5], e->stream));
+            HIPE(e, slv.backsolve_aug(e->d_G, vs, nrhs));           // G <- L^-T (L^-1 Y)   (row 0: y~, rows 1..d: G^)
+            HIPE(e, hipEventRecord(e->ev[6], e->stream));
+            X.assign((size_t)nrhs * vs, 0.0);
+            HIPE(e, hipMemcpyAsync(X.data(), e->d_G, X.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+            fast_refined = false;
+            if (d == 0 && e->refine_steps >= 1 && !e->sim_built) {
+                // first refinement step without the host: dx = V y on the device, residual of the unscaled system in two-fold precision,
+                // forward + backward substitution (refine.hip, dense.hip); the correction comes back together with y
+                TRY(refine_begin());
+                hipLaunchKernelGGL(scale_vec_kernel, dim3((Up + 255) / 256), dim3(256), 0, e->stream, e->d_G, e->d_V, e->d_dx, U, Up, 0);   // dx = V y
+                TRY(refine_step(RefineBorder{}, delta0));
+                fast_refined = true;
+            }
+            info = slv.fetch_info();
+            if (info == -9 && attempt < 2) {
+                ++e->flow_retries;
+                fprintf(stderr, "jaicov: factorisation abandoned on the device (a wait ran into its time limit); repeating it (%d)\n", attempt + 1);
+                continue;
+            }
+            break;
+        }
+        if (info < 0) FAIL(e, JAICOV_ERR_DEVICE, "factorisation did not complete on the device (code " + std::to_string(info) + ")");
+        if (info != 0) FAIL(e, JAICOV_ERR_SINGULAR, "normal-equation matrix is singular / not positive definite at pivot " + std::to_string(info));
+        return JAICOV_OK;
+    }
+    // ---- rank-d border algebra on the host ---------------------------------------------------------------------
+    int border_step(double *dx_out) {
+        double Sm[49], kh[7];
+        std::vector<double> y(X.begin(), X.begin() + vs);
+        if (d > 0) {
+            for (int a = 0; a < d; a++)
+                for (int b = 0; b < d; b++) Sm[a * d + b] = border_dot(a, &X[(size_t)(1 + b) * vs]);
+            if (!small_inverse(d, Sm, Sinv)) FAIL(e, JAICOV_ERR_SINGULAR, "datum conditions are linearly dependent");
+            const double no_rk[7] = {0, 0, 0, 0, 0, 0, 0};
+            border_multipliers(X.data(), no_rk, kh);
+            for (int c = d; c < U; c++) {
+                double s = 0.0;
+                for (int a = 0; a < d; a++) s += X[(size_t)(1 + a) * vs + c] * kh[a];
+                y[c] -= s;
+            }
+        }
+        for (int c = 0; c < U; c++) dx_out[c] = c < d ? R[c] * kh[c] : e->h_V[c] * y[c];
+        for (int c = 0; c < U; c++)
+            if (!std::isfinite(dx_out[c])) FAIL(e, JAICOV_ERR_NOT_FINITE, "non-finite step");
+        return JAICOV_OK;
+    }
+    // the step the device took on its own (d = 0: no border algebra), then the others with the host in between
+    int refine(double *dx_out) {
+        e->last_refine_correction = 0.0;
+        if (fast_refined) TRY(apply_correction(RefineBorder{}, delta0, dx_out));
+        for (int step = fast_refined ? 1 : 0; step < e->refine_steps && !e->sim_built; step++) {
+            RefineBorder bd{};
+            for (int a = 0; a < d; a++) {
+                long double sacc = 0.0L;
+                for (int c = d; c < U; c++) sacc += (long double)e->hB[(size_t)a * Upad + c] * (long double)dx_out[c];
+                bd.kappa[a] = dx_out[a];
+                bd.rk[a] = (double)(-(long double)R[a] * sacc);
+            }
+            TRY(refine_begin());
+            if (d > 0 && step == 0)
+                HIPE(e, hipMemcpyAsync(e->d_Braw, e->hB.data(), (size_t)d * Upad * sizeof(double), hipMemcpyHostToDevice, e->stream));
+            HIPE(e, hipMemcpyAsync(e->d_dx, dx_out, (size_t)U * sizeof(double), hipMemcpyHostToDevice, e->stream));
+            std::vector<double> dl;
+            TRY(refine_step(bd, dl));
+            HIPE(e, hipStreamSynchronize(e->stream));
+            TRY(apply_correction(bd, dl, dx_out));
+        }
+        return JAICOV_OK;
+    }
+    // EO step of every image of this engine: dx_E = L_E^-T U' (w - A_r dx_R), from d_dx into d_xE   (schur.hip)
+    int eo_backsub() {
         HIPE(e, launch_omega(e->stream, e->p, e->d_in_block, e->ip0, e->ip_count, e->d_blk_list, 0, e->max_m, e->d_rowsA,
                              e->d_rowsW, e->d_dx, 1.0, e->d_vbuf, e->d_omega));
         HIPE(e, launch_schur_backsub(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->sb.U, e->sb.Linv, e->d_vbuf, e->d_xE));
-        std::vector<double> xE((size_t)6 * e->p.n_images);
-        HIPE(e, hipMemcpyAsync(xE.data(), e->d_xE, xE.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-        HIPE(e, hipStreamSynchronize(e->stream));
-        {
-            // Round 5: once in ~10 runs of the GPU test-suite a solve returned an EO step of EXACT zeros for every image (N, n and the reduced
-            // step correct; 1 200 solves of the same scene alone: never).  The back-substitution kernel cannot produce that from finite
-            // operands, so the copy is checked: all zeros -> read again with a blocking copy after a device-wide wait, and say so.
-            bool all_zero = !e->h_blk_images.empty();
-            for (int img : e->h_blk_images)
-                for (int k = 0; k < 6 && all_zero; k++) all_zero = xE[(size_t)6 * img + k] == 0.0;
-            if (all_zero) {
-                HIPE(e, hipDeviceSynchronize());
-                HIPE(e, hipMemcpy(xE.data(), e->d_xE, xE.size() * sizeof(double), hipMemcpyDeviceToHost));
-                bool still = true;
-                for (int img : e->h_blk_images)
-                    for (int k = 0; k < 6 && still; k++) still = xE[(size_t)6 * img + k] == 0.0;
-                if (still) {      // the kernel itself left zeros: run the two kernels once more
-                    HIPE(e, launch_omega(e->stream, e->p, e->d_in_block, e->ip0, e->ip_count, e->d_blk_list, 0, e->max_m, e->d_rowsA,
-                                         e->d_rowsW, e->d_dx, 1.0, e->d_vbuf, e->d_omega));
-                    HIPE(e, launch_schur_backsub(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->sb.U, e->sb.Linv, e->d_vbuf, e->d_xE));
-                    HIPE(e, hipStreamSynchronize(e->stream));
-                    HIPE(e, hipMemcpy(xE.data(), e->d_xE, xE.size() * sizeof(double), hipMemcpyDeviceToHost));
-                }
-                fprintf(stderr, "jaicov: the exterior-orientation step came back as exact zeros; %s\n",
-                        still ? "the back-substitution was run again" : "a second, blocking copy had the values (the first copy returned before the data)");
-            }
-        }
+        return JAICOV_OK;
+    }
+    // Round 5: once in ~10 runs of the GPU test-suite a solve returned an EO step of EXACT zeros for every image (N, n and the reduced
+    // step correct; 1 200 solves of the same scene alone: never).  The back-substitution kernel cannot produce that from finite
+    // operands, so the copy is checked: all zeros -> read again with a blocking copy after a device-wide wait, and say so.
+    int eo_zero_step_guard(std::vector<double> &xE) {
+        bool all_zero = !e->h_blk_images.empty();
         for (int img : e->h_blk_images)
-            for (int k = 0; k < 6; k++) {
-                dx_out[e->e0 + 6 * img + k] = xE[(size_t)6 * img + k];
-                if (!std::isfinite(xE[(size_t)6 * img + k])) FAIL(e, JAICOV_ERR_NOT_FINITE, "non-finite step");
-            }
-    }
-    if (!schur && e->opts.reduced_reference_quirk && invert == JAICOV_INVERT_REDUCED) {
-        // full-order path (no EO pre-elimination possible): the same quirk from the assembled right-hand side, V_c^2 n_c
-        std::vector<double> hn((size_t)e->U);
-        HIPE(e, hipMemcpyAsync(hn.data(), e->d_n, hn.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-        HIPE(e, hipStreamSynchronize(e->stream));
-        const int ns = e->n_slots, s_eo = ns - 6 * e->p.n_images;
-        for (int sl = s_eo; sl < ns; sl++) {
-            const int c = e->h_slot_col[sl];
-            if (c >= 0) dx_out[c] = e->h_V[c] * e->h_V[c] * hn[c];
+            for (int k = 0; k < 6 && all_zero; k++) all_zero = xE[(size_t)6 * img + k] == 0.0;
+        if (!all_zero) return JAICOV_OK;
+        HIPE(e, hipDeviceSynchronize());
+        HIPE(e, hipMemcpy(xE.data(), e->d_xE, xE.size() * sizeof(double), hipMemcpyDeviceToHost));
+        bool still = true;
+        for (int img : e->h_blk_images)
+            for (int k = 0; k < 6 && still; k++) still = xE[(size_t)6 * img + k] == 0.0;
+        if (still) {      // the kernel itself left zeros: run the two kernels once more
+            TRY(eo_backsub());
+            HIPE(e, hipStreamSynchronize(e->stream));
+            HIPE(e, hipMemcpy(xE.data(), e->d_xE, xE.size() * sizeof(double), hipMemcpyDeviceToHost));
         }
+        fprintf(stderr, "jaicov: the exterior-orientation step came back as exact zeros; %s\n",
+                still ? "the back-substitution was run again" : "a second, blocking copy had the values (the first copy returned before the data)");
+        return JAICOV_OK;
     }
-    if (invert) {
-        // FULL: Qxx of all unknowns.  REDUCED on a pre-eliminated system: the inverse of the reduced normal equations,
-        // which IS the block of Qxx that belongs to the datum border, points, interior orientation and distortion
-        // (MatrixInversion.REDUCED / PRE_ELIMINATION, BA:261-267: solve(N, n, numRows, true) on the reduced system).
+    // the EO entries of the step, which the reduced system does not hold
+    int eo_entries(double *dx_out) {
+        const bool quirk = e->opts.reduced_reference_quirk && invert == JAICOV_INVERT_REDUCED;
+        if (schur)
+            for (int c = U; c < e->U; c++) dx_out[c] = 0.0;
+        // SIMULATION zeroes the right-hand side of the WHOLE system (BA:830-831 `n.zero()`): the eliminated exterior
+        // orientations get no step either (their back substitution would use the real misclosures)
+        if (schur && e->sim_built) return JAICOV_OK;
+        if (schur && quirk) {
+            // what the reference's last pass leaves in the EO entries of dx under MatrixInversion.REDUCED (quirk Q1): V_c^2 n_c
+            std::vector<double> xq((size_t)6 * e->p.n_images);
+            HIPE(e, hipMemcpyAsync(xq.data(), e->sb.xq, xq.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+            HIPE(e, hipStreamSynchronize(e->stream));
+            for (int img : e->h_blk_images)
+                for (int k = 0; k < 6; k++) dx_out[e->e0 + 6 * img + k] = xq[(size_t)6 * img + k];
+        } else if (schur) {
+            HIPE(e, hipMemcpyAsync(e->d_dx, dx_out, (size_t)e->U * sizeof(double), hipMemcpyHostToDevice, e->stream));
+            TRY(eo_backsub());
+            std::vector<double> xE((size_t)6 * e->p.n_images);
+            HIPE(e, hipMemcpyAsync(xE.data(), e->d_xE, xE.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+            HIPE(e, hipStreamSynchronize(e->stream));
+            TRY(eo_zero_step_guard(xE));
+            for (int img : e->h_blk_images)
+                for (int k = 0; k < 6; k++) {
+                    dx_out[e->e0 + 6 * img + k] = xE[(size_t)6 * img + k];
+                    if (!std::isfinite(xE[(size_t)6 * img + k])) FAIL(e, JAICOV_ERR_NOT_FINITE, "non-finite step");
+                }
+        } else if (quirk) {
+            // full-order path (no EO pre-elimination possible): the same quirk from the assembled right-hand side, V_c^2 n_c
+            std::vector<double> hn((size_t)e->U);
+            HIPE(e, hipMemcpyAsync(hn.data(), e->d_n, hn.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+            HIPE(e, hipStreamSynchronize(e->stream));
+            const int ns = e->n_slots, s_eo = ns - 6 * e->p.n_images;
+            for (int sl = s_eo; sl < ns; sl++) {
+                const int c = e->h_slot_col[sl];
+                if (c >= 0) dx_out[c] = e->h_V[c] * e->h_V[c] * hn[c];
+            }
+        }
+        return JAICOV_OK;
+    }
+    // FULL: Qxx of all unknowns.  REDUCED on a pre-eliminated system: the inverse of the reduced normal equations,
+    // which IS the block of Qxx that belongs to the datum border, points, interior orientation and distortion
+    // (MatrixInversion.REDUCED / PRE_ELIMINATION, BA:261-267: solve(N, n, numRows, true) on the reduced system).
+    int invert_and_expand() {
         HIPE(e, slv.trtri());
         HIPE(e, slv.lauum());
         if (e->opts.inverse_refinement >= 0 && Up <= 8192) {
@@ -1674,18 +1668,14 @@ extern "C" int jaicov_neq_solve(jaicov_engine *e, int invert, double *dx_out) {
             // (scaled, with the datum border's term; the factor in slv.L is not needed again before the next factorisation), W is free
             // after lauum(), three more squares are kept with the engine.
             const size_t sq = (size_t)Up * ld;
-            if (e->ns_work_len < 3 * sq) {
-                if (e->ns_work) hipFree(e->ns_work);
-                e->ns_work = nullptr; e->ns_work_len = 0;
-                HIPE(e, hipMalloc(&e->ns_work, 3 * sq * sizeof(double)));
-                e->ns_work_len = 3 * sq;
-            }
+            HIPE(e, e->ns_work.reserve(3 * sq));
+            double *ns = e->ns_work.get();
             HIPE(e, slv.begin_refactor());
             HIPE(e, slv.symmetrize(slv.Q));
             hipLaunchKernelGGL(scale_copy_kernel, dim3((Up + 255) / 256, Up), dim3(256), 0, e->stream, e->d_N, (long)Upad, slv.L, ld, U,
                                Up, d, e->d_V, e->d_B, Upad, 0, Up);
             HIPE(e, slv.symmetrize(slv.L));
-            HIPE(e, newton_schulz_exact(e->stream, Up, ld, slv.L, slv.Q, slv.W, e->ns_work, e->ns_work + sq, e->ns_work + 2 * sq));
+            HIPE(e, newton_schulz_exact(e->stream, Up, ld, slv.L, slv.Q, slv.W, ns, ns + sq, ns + 2 * sq));
         }
         // H = Sinv G^ ; F = R (Sinv G^) V ; E = R (I - Sinv) R
         std::vector<double> H((size_t)8 * Upad, 0.0), F((size_t)8 * Upad, 0.0);
@@ -1706,64 +1696,85 @@ extern "C" int jaicov_neq_solve(jaicov_engine *e, int invert, double *dx_out) {
         }
         hipLaunchKernelGGL(qfix_kernel, dim3((Up + 255) / 256, Up), dim3(256), 0, e->stream, slv.Q, ld, U, Upad, d,
                            e->d_V, e->d_G + vs, (long)vs, e->d_H, e->d_F, e->d_E, Up);
-        if (expand) {
-            // ---- the full cofactor matrix from the reduced one (schur.hip, blk_expand_f_kernel): workspace = W of the reduced
-            //      solver, free again after lauum():  F [6I pad][Up] | T1 = -F Q_RR [6I pad][Up] | T2 = -T1 F' [6I pad][6I pad]
-            const int I6 = 6 * e->p.n_images, I6p = ((I6 + 127) / 128) * 128;
-            if ((size_t)I6p * ((size_t)2 * Up + I6p) > (size_t)slv.n * slv.ld)
-                FAIL(e, JAICOV_ERR_UNSUPPORTED, "FULL_EXPANDED: more exterior orientations than the workspace holds; use JAICOV_INVERT_FULL");
-            double *Fm = slv.W, *T1 = Fm + (size_t)I6p * Up, *T2 = T1 + (size_t)I6p * Up;
-            const double *LinvAll = e->sb.Linv;
-            if (e->all_images) {
-                HIPE(e, hipMemsetAsync(Fm, 0, (size_t)I6p * Up * sizeof(double), e->stream));
-                HIPE(e, launch_schur_expand_f(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->d_rowsA, e->sb.U, e->sb.Linv, e->sb.G, Fm, (long)Up));
-            } else {      // a shard: F and L_E^-1 of EVERY image, summed over the ranks by the caller (jaicov_neq_expansion_buffer)
-                if (!e->exp_ready || e->expF_len != (size_t)I6p * Up + (size_t)36 * e->p.n_images)
-                    FAIL(e, JAICOV_ERR_BAD_STATE, "FULL_EXPANDED on a sharded engine: all-reduce jaicov_neq_expansion_buffer() between accumulate and solve");
-                HIPE(e, hipMemcpyAsync(Fm, e->d_expF, (size_t)I6p * Up * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-                // the summed L_E^-1 records are READ from the buffer, never copied over sb.Linv: that array must keep zeros for the
-                // foreign images, or the next pass's expansion buffer would carry their stale records into the sum (ADVICE r4, high:
-                // a second sharded FULL_EXPANDED pass gave R times the EO cofactors)
-                LinvAll = e->d_expF + (size_t)I6p * Up;
-            }
-            HIPE(e, slv.symmetrize(slv.Q));
-            GemmArgs g1{};
-            g1.A = Fm; g1.lda = Up; g1.B = slv.Q; g1.ldb = ld; g1.C = T1; g1.ldc = Up;
-            g1.M = I6p; g1.N = Up; g1.K = Up; g1.alpha = -1.0; g1.beta = 0.0; g1.kmode = KMODE_FULL;
-            HIPE(e, gemm_f64(e->stream, LAY_KC, LAY_KC, g1));             // Q_RR symmetric: F Q_RR = F Q_RR'
-            GemmArgs g2{};
-            g2.A = T1; g2.lda = Up; g2.B = Fm; g2.ldb = Up; g2.C = T2; g2.ldc = I6p;
-            g2.M = I6p; g2.N = I6p; g2.K = Up; g2.alpha = -1.0; g2.beta = 0.0; g2.kmode = KMODE_FULL; g2.lower_only = 1;
-            HIPE(e, gemm_f64(e->stream, LAY_KC, LAY_KC, g2));
-            hipLaunchKernelGGL(expand_cofactor_kernel, dim3((e->U + 255) / 256, e->U), dim3(256), 0, e->stream, e->solver.Q, e->solver.ld,
-                               e->U, e->e0, slv.Q, ld, T1, (long)Up, T2, (long)I6p, LinvAll);
+        return expand ? expand_cofactor() : JAICOV_OK;
+    }
+    // ---- the full cofactor matrix from the reduced one (schur.hip, blk_expand_f_kernel): workspace = W of the reduced
+    //      solver, free again after lauum():  F [6I pad][Up] | T1 = -F Q_RR [6I pad][Up] | T2 = -T1 F' [6I pad][6I pad]
+    int expand_cofactor() {
+        size_t I6, UpS;
+        if (!expansion_fits(e, &I6, &UpS))
+            FAIL(e, JAICOV_ERR_UNSUPPORTED, "FULL_EXPANDED: more exterior orientations than the workspace holds; use JAICOV_INVERT_FULL");
+        const int I6p = (int)I6;
+        double *Fm = slv.W, *T1 = Fm + (size_t)I6p * Up, *T2 = T1 + (size_t)I6p * Up;
+        const double *LinvAll = e->sb.Linv;
+        if (e->all_images) {
+            HIPE(e, hipMemsetAsync(Fm, 0, (size_t)I6p * Up * sizeof(double), e->stream));
+            HIPE(e, launch_schur_expand_f(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->d_rowsA, e->sb.U, e->sb.Linv, e->sb.G, Fm, (long)Up));
+        } else {      // a shard: F and L_E^-1 of EVERY image, summed over the ranks by the caller (jaicov_neq_expansion_buffer)
+            if (!e->exp_ready || e->expF_len != (size_t)I6p * Up + (size_t)36 * e->p.n_images)
+                FAIL(e, JAICOV_ERR_BAD_STATE, "FULL_EXPANDED on a sharded engine: all-reduce jaicov_neq_expansion_buffer() between accumulate and solve");
+            HIPE(e, hipMemcpyAsync(Fm, e->expF.get(), (size_t)I6p * Up * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+            // the summed L_E^-1 records are READ from the buffer, never copied over sb.Linv: that array must keep zeros for the
+            // foreign images, or the next pass's expansion buffer would carry their stale records into the sum (ADVICE r4, high:
+            // a second sharded FULL_EXPANDED pass gave R times the EO cofactors)
+            LinvAll = e->expF.get() + (size_t)I6p * Up;
         }
+        HIPE(e, slv.symmetrize(slv.Q));
+        GemmArgs g1{};
+        g1.A = Fm; g1.lda = Up; g1.B = slv.Q; g1.ldb = ld; g1.C = T1; g1.ldc = Up;
+        g1.M = I6p; g1.N = Up; g1.K = Up; g1.alpha = -1.0; g1.beta = 0.0; g1.kmode = KMODE_FULL;
+        HIPE(e, gemm_f64(e->stream, LAY_KC, LAY_KC, g1));             // Q_RR symmetric: F Q_RR = F Q_RR'
+        GemmArgs g2{};
+        g2.A = T1; g2.lda = Up; g2.B = Fm; g2.ldb = Up; g2.C = T2; g2.ldc = I6p;
+        g2.M = I6p; g2.N = I6p; g2.K = Up; g2.alpha = -1.0; g2.beta = 0.0; g2.kmode = KMODE_FULL; g2.lower_only = 1;
+        HIPE(e, gemm_f64(e->stream, LAY_KC, LAY_KC, g2));
+        hipLaunchKernelGGL(expand_cofactor_kernel, dim3((e->U + 255) / 256, e->U), dim3(256), 0, e->stream, e->solver.Q, e->solver.ld,
+                           e->U, e->e0, slv.Q, ld, T1, (long)Up, T2, (long)I6p, LinvAll);
+        return JAICOV_OK;
+    }
+    // end of the device's work, what the cofactor matrix at hand is, the timings
+    int finish() {
         HIPE(e, hipEventRecord(e->ev[7], e->stream));
         HIPE(e, hipStreamSynchronize(e->stream));
-        e->have_Q = true;
-        e->q_sigma2 = e->sigma2_acc;
-        e->q_lambda = e->lambda_used;
-        e->q_reduced = schur && !expand;
-        e->q_order = expand ? e->U : U;
-    } else {
-        HIPE(e, hipEventRecord(e->ev[7], e->stream));
-        HIPE(e, hipStreamSynchronize(e->stream));
+        if (invert) {
+            e->have_Q = true;
+            e->q_sigma2 = e->sigma2_acc;
+            e->q_lambda = e->lambda_used;
+            e->q_reduced = schur && !expand;
+            e->q_order = expand ? e->U : U;
+        }
+        slv.prof_collect();
+        if (schur) {
+            e->solver.stat_launches += slv.stat_launches; e->solver.stat_ms += slv.stat_ms; e->solver.stat_flops += slv.stat_flops;
+            slv.stat_launches = slv.stat_ms = slv.stat_flops = 0.0;
+        }
+        float ms;
+        hipEventElapsedTime(&ms, e->ev[0], e->ev[1]); e->timings[0] = ms;
+        hipEventElapsedTime(&ms, e->ev[1], e->ev[2]); e->timings[1] = ms;
+        hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); e->timings[2] = ms;
+        hipEventElapsedTime(&ms, e->ev[4], e->ev[5]); e->timings[3] = ms;
+        hipEventElapsedTime(&ms, e->ev[5], e->ev[6]); e->timings[4] = ms + refine_ms;   // substitution + refinement steps
+        hipEventElapsedTime(&ms, e->ev[6], e->ev[7]); e->timings[5] = std::max(0.f, ms - refine_ms);   // the refinement sits between these events: counted under [4]
+        hipEventElapsedTime(&ms, e->ev[0], e->ev[7]); e->timings[7] = ms;
+        e->state = jaicov_engine::ST_SOLVED;
+        return JAICOV_OK;
     }
-    slv.prof_collect();
-    if (schur) {
-        e->solver.stat_launches += slv.stat_launches; e->solver.stat_ms += slv.stat_ms; e->solver.stat_flops += slv.stat_flops;
-        slv.stat_launches = slv.stat_ms = slv.stat_flops = 0.0;
-    }
-    float ms;
-    hipEventElapsedTime(&ms, e->ev[0], e->ev[1]); e->timings[0] = ms;
-    hipEventElapsedTime(&ms, e->ev[1], e->ev[2]); e->timings[1] = ms;
-    hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); e->timings[2] = ms;
-    hipEventElapsedTime(&ms, e->ev[4], e->ev[5]); e->timings[3] = ms;
-    hipEventElapsedTime(&ms, e->ev[5], e->ev[6]); e->timings[4] = ms + refine_ms;   // substitution + refinement steps
-    hipEventElapsedTime(&ms, e->ev[6], e->ev[7]); e->timings[5] = std::max(0.f, ms - refine_ms);   // the refinement sits between these events: counted under [4]
-    hipEventElapsedTime(&ms, e->ev[0], e->ev[7]); e->timings[7] = ms;
-    e->state = jaicov_engine::ST_SOLVED;
-    return JAICOV_OK;
+};
+
+extern "C" int jaicov_neq_solve(jaicov_engine *e, int invert, double *dx_out) {
+    if (!e || !dx_out) return JAICOV_ERR_BAD_ARGUMENT;
+    if (e->state != jaicov_engine::ST_BUILT) FAIL(e, JAICOV_ERR_BAD_STATE, "build first");
+    HIPE(e, hipSetDevice(e->device));
+    if (invert < 0 || invert > JAICOV_INVERT_FULL_EXPANDED) return JAICOV_ERR_BAD_ARGUMENT;
+    Solve s(e);
+    TRY(s.solve_mode(invert));
+    TRY(s.border_rows());
+    TRY(s.factor_and_substitute());
+    TRY(s.border_step(dx_out));
+    TRY(s.refine(dx_out));
+    TRY(s.eo_entries(dx_out));
+    if (s.invert) TRY(s.invert_and_expand());
+    return s.finish();
 }
 
 extern "C" int jaicov_neq_expansion_buffer(jaicov_engine *e, void **device_ptr, size_t *count) {
@@ -1771,23 +1782,20 @@ extern "C" int jaicov_neq_expansion_buffer(jaicov_engine *e, void **device_ptr, 
     if (e->state != jaicov_engine::ST_ACCUMULATED || !e->schur_active || !e->solverS_ready)
         FAIL(e, JAICOV_ERR_BAD_STATE, "expansion buffer: accumulate a pre-eliminated system first (prepare_inverse(JAICOV_INVERT_FULL_EXPANDED))");
     HIPE(e, hipSetDevice(e->device));
-    const size_t I6p = ((size_t)6 * e->p.n_images + 127) / 128 * 128, Up = (size_t)e->solverS.nfact;
+    size_t I6p, Up;
+    expansion_fits(e, &I6p, &Up);
     const size_t len = I6p * Up + (size_t)36 * e->p.n_images;
-    if (!e->d_expF || e->expF_len != len) {
-        if (e->d_expF) hipFree(e->d_expF);
-    if (e->ns_work) hipFree(e->ns_work);
-        e->d_expF = nullptr;
-        HIPE(e, hipMalloc(&e->d_expF, len * sizeof(double)));
-        e->expF_len = len;
-    }
-    { int rr = ensure_rows(e); if (rr) return rr; }
-    HIPE(e, hipMemsetAsync(e->d_expF, 0, I6p * Up * sizeof(double), e->stream));       // foreign images' bands: zero
-    HIPE(e, launch_schur_expand_f(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->d_rowsA, e->sb.U, e->sb.Linv, e->sb.G, e->d_expF, (long)Up));
+    HIPE(e, e->expF.reserve(len));
+    e->expF_len = len;
+    double *d_expF = e->expF.get();
+    TRY(ensure_rows(e));
+    HIPE(e, hipMemsetAsync(d_expF, 0, I6p * Up * sizeof(double), e->stream));       // foreign images' bands: zero
+    HIPE(e, launch_schur_expand_f(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->d_rowsA, e->sb.U, e->sb.Linv, e->sb.G, d_expF, (long)Up));
     // L_E^-1: written for this engine's images only (blk_elim_kernel), zero elsewhere since create
-    HIPE(e, hipMemcpyAsync(e->d_expF + I6p * Up, e->sb.Linv, (size_t)36 * e->p.n_images * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    HIPE(e, hipMemcpyAsync(d_expF + I6p * Up, e->sb.Linv, (size_t)36 * e->p.n_images * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
     HIPE(e, hipStreamSynchronize(e->stream));
     e->exp_ready = true;
-    *device_ptr = e->d_expF;
+    *device_ptr = d_expF;
     *count = len;
     return JAICOV_OK;
 }
@@ -1804,8 +1812,7 @@ extern "C" int jaicov_neq_omega(jaicov_engine *e, double sigma2, const double *d
     if (!e || !dx || !omega) return JAICOV_ERR_BAD_ARGUMENT;
     if (e->state == jaicov_engine::ST_NEW) FAIL(e, JAICOV_ERR_BAD_STATE, "set_parameters first");
     HIPE(e, hipSetDevice(e->device));
-    int rc = ensure_rows(e);
-    if (rc) return rc;
+    TRY(ensure_rows(e));
     hipEvent_t t0 = e->ev[8], t1 = e->ev[9];
     HIPE(e, hipEventRecord(t0, e->stream));
     HIPE(e, hipMemcpyAsync(e->d_dx, dx, (size_t)e->U * sizeof(double), hipMemcpyHostToDevice, e->stream));
@@ -1853,14 +1860,12 @@ extern "C" int jaicov_neq_get_normal(jaicov_engine *e, double *N_packed, size_t 
     // e0 rows / columns, zeros elsewhere.
     const int Ua = e->schur_active ? e->e0 : U;
     const size_t lenA = (size_t)Ua * (Ua + 1) / 2;
-    double *d_ap = nullptr;
-    HIPE(e, hipMalloc(&d_ap, std::max<size_t>(lenA, 1) * sizeof(double)));
-    hipLaunchKernelGGL(pack_kernel, dim3((Ua + 255) / 256, std::max(Ua, 1)), dim3(256), 0, e->stream, e->d_N, (long)e->Upad, Ua, d_ap);
-    hipError_t he = hipMemcpyAsync(N_packed, d_ap, lenA * sizeof(double), hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(n, e->d_n, Ua * sizeof(double), hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    hipFree(d_ap);
-    HIPE(e, he);
+    DevBuf<double> ap;
+    HIPE(e, ap.reserve(std::max<size_t>(lenA, 1)));
+    hipLaunchKernelGGL(pack_kernel, dim3((Ua + 255) / 256, std::max(Ua, 1)), dim3(256), 0, e->stream, e->d_N, (long)e->Upad, Ua, ap.get());
+    HIPE(e, hipMemcpyAsync(N_packed, ap.get(), lenA * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPE(e, hipMemcpyAsync(n, e->d_n, Ua * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPE(e, hipStreamSynchronize(e->stream));
     if (lenA < len) memset(N_packed + lenA, 0, (len - lenA) * sizeof(double));
     for (int c = Ua; c < U; c++) n[c] = 0.0;
     // the datum border lives on the host (rows 0..d-1): K[r][c] = B[r][c]  (BA:548-593), packed index r + c(c+1)/2
@@ -1877,17 +1882,13 @@ extern "C" int jaicov_neq_get_cofactor(jaicov_engine *e, double *Q_packed, size_
     if (len != (size_t)U * (U + 1) / 2) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "cofactor buffer length must be order(order+1)/2 with order = jaicov_neq_cofactor_order()");
     HIPE(e, hipSetDevice(e->device));
     const DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
-    double *d_ap = nullptr;
-    HIPE(e, hipMalloc(&d_ap, std::max<size_t>(len, 1) * sizeof(double)));
-    hipLaunchKernelGGL(pack_kernel, dim3((U + 255) / 256, std::max(U, 1)), dim3(256), 0, e->stream, qs.Q, qs.ld, U, d_ap);
-    hipError_t he = hipMemcpyAsync(Q_packed, d_ap, len * sizeof(double), hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    hipFree(d_ap);
-    HIPE(e, he);
+    DevBuf<double> ap;
+    HIPE(e, ap.reserve(std::max<size_t>(len, 1)));
+    hipLaunchKernelGGL(pack_kernel, dim3((U + 255) / 256, std::max(U, 1)), dim3(256), 0, e->stream, qs.Q, qs.ld, U, ap.get());
+    HIPE(e, hipMemcpyAsync(Q_packed, ap.get(), len * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPE(e, hipStreamSynchronize(e->stream));
     return JAICOV_OK;
 }
-
-static int cofactor_sub_impl(jaicov_engine *e, const int32_t *idx, int32_t k, double scale, double *out);
 
 // transform.hip reads Qxx, the slot vector and the structure through this view (include/jaicov_transform.h)
 void jaicov::engine_xform_view(jaicov_engine *e, XformView *v) {
@@ -1930,6 +1931,24 @@ int jaicov::engine_rel_view(jaicov_engine *e, RelView *v, int rows) {
     return rows ? ensure_rows(e) : JAICOV_OK;
 }
 
+static int cofactor_sub_impl(jaicov_engine *e, const int32_t *idx, int32_t k, double scale, double *out) {
+    if (!e || !idx || !out || k <= 0) return JAICOV_ERR_BAD_ARGUMENT;
+    if (!e->have_Q) FAIL(e, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
+    for (int i = 0; i < k; i++)
+        if (idx[i] < 0 || idx[i] >= e->q_order) return JAICOV_ERR_BAD_ARGUMENT;
+    const DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
+    HIPE(e, hipSetDevice(e->device));
+    DevBuf<int32_t> d_idx;
+    DevBuf<double> d_out;
+    HIPE(e, d_idx.reserve((size_t)k));
+    HIPE(e, d_out.reserve((size_t)k * k));
+    HIPE(e, hipMemcpyAsync(d_idx.get(), idx, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(gather_sub_kernel, dim3(((size_t)k * k + 255) / 256), dim3(256), 0, e->stream, qs.Q, qs.ld, d_idx.get(), k, d_out.get(), scale);
+    HIPE(e, hipMemcpyAsync(out, d_out.get(), (size_t)k * k * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPE(e, hipStreamSynchronize(e->stream));
+    return JAICOV_OK;
+}
+
 extern "C" int jaicov_neq_get_cofactor_sub(jaicov_engine *e, const int32_t *idx, int32_t k, double *out) {
     return cofactor_sub_impl(e, idx, k, 1.0, out);
 }
@@ -1938,34 +1957,11 @@ extern "C" int jaicov_neq_get_dispersion_sub(jaicov_engine *e, double sigma2_apo
     return cofactor_sub_impl(e, idx, k, sigma2_aposteriori, out);
 }
 
-static int cofactor_sub_impl(jaicov_engine *e, const int32_t *idx, int32_t k, double scale, double *out) {
-    if (!e || !idx || !out || k <= 0) return JAICOV_ERR_BAD_ARGUMENT;
-    if (!e->have_Q) FAIL(e, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
-    for (int i = 0; i < k; i++)
-        if (idx[i] < 0 || idx[i] >= e->q_order) return JAICOV_ERR_BAD_ARGUMENT;
-    const DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
-    HIPE(e, hipSetDevice(e->device));
-    int32_t *d_idx = nullptr;
-    double *d_out = nullptr;
-    HIPE(e, hipMalloc(&d_idx, (size_t)k * sizeof(int32_t)));
-    hipError_t he = hipMalloc(&d_out, (size_t)k * k * sizeof(double));
-    if (he == hipSuccess) he = hipMemcpyAsync(d_idx, idx, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(gather_sub_kernel, dim3(((size_t)k * k + 255) / 256), dim3(256), 0, e->stream, qs.Q, qs.ld, d_idx, k, d_out, scale);
-        he = hipMemcpyAsync(out, d_out, (size_t)k * k * sizeof(double), hipMemcpyDeviceToHost, e->stream);
-    }
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    hipFree(d_idx); hipFree(d_out);
-    HIPE(e, he);
-    return JAICOV_OK;
-}
-
 extern "C" int jaicov_neq_get_rows(jaicov_engine *e, int32_t ip_begin, int32_t ip_count, double *w, double *A) {
     if (!e || !w || !A || ip_begin < e->ip0 || ip_count < 0 || ip_begin + ip_count > e->ip0 + e->ip_count) return JAICOV_ERR_BAD_ARGUMENT;
     if (e->state == jaicov_engine::ST_NEW) FAIL(e, JAICOV_ERR_BAD_STATE, "set_parameters first");
     HIPE(e, hipSetDevice(e->device));
-    int rc = ensure_rows(e);
-    if (rc) return rc;
+    TRY(ensure_rows(e));
     const size_t S = (size_t)e->p.n_ip;
     std::vector<double> hA((size_t)2 * KROW * S), hW(2 * S);
     HIPE(e, hipMemcpyAsync(hA.data(), e->d_rowsA, hA.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));

@@ -57,3 +57,11 @@ def test_product_never_imports_oracle():
                 txt = open(os.path.join(dirpath, f)).read()
                 for pat in (r"import\s+oracle", r"from\s+oracle", r"ba_oracle", r"oracle/"):
                     assert not re.search(pat, txt), f"{f} references the oracle ({pat})"
+
+
+def test_engine_frees_none_of_its_members_by_hand():
+    """The engine's growable device buffers have one owner each (DevBuf in csrc/engine.hip) that frees them in its destructor;
+    jaicov_neq_destroy frees the create-time allocations in its loop.  A hand-written free of a member is how the
+    Newton-Schulz workspace came to be freed under a live pointer."""
+    txt = open(os.path.join(ROOT, "bundle-adjustment_amd", "csrc", "engine.hip")).read()
+    assert "hipFree(e->" not in txt

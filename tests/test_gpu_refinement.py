@@ -152,6 +152,39 @@ def test_full_cofactor_expanded_from_the_reduced_inverse(oracle_mod, free_networ
     eng.close()
 
 
+def test_expansion_buffer_between_two_inverting_solves_leaves_their_workspaces_alone():
+    """An inverting solve (which allocates the Newton-Schulz workspace: reduced order far below 8192, `inverse_refinement` at its
+    default), then a FULL_EXPANDED pass whose expansion buffer is fetched between accumulate and finalize -- an engine that sees
+    all images may do that.  The buffers of the engine have one owner each, so fetching one cannot free another: the pass
+    gives the bits of the same pass on a fresh engine (deterministic assembly, bit-reproducible passes: zero tolerance)."""
+    fp = scene.make_scene(8, 60, 40, dist=scene.DIST_FULL, weights="block", n_control=0, scale_bar=True)
+    s2 = fp.sigma2apriori
+    assert fp.rank_defect > 0                                  # datum border
+
+    def expanded_pass(eng):
+        eng.prepare_inverse(engine.INVERT_FULL_EXPANDED)
+        eng.accumulate(s2, 0.0)
+        eng.expansion_buffer()
+        eng.finalize(s2, 0.0)
+        dx = eng.solve(engine.INVERT_FULL_EXPANDED)
+        Q = eng.get_cofactor()
+        eng.close()
+        return dx, Q
+
+    eng = engine.Engine(fp)
+    eng.set_parameters(fp.values)
+    eng.prepare_inverse(engine.INVERT_REDUCED)
+    eng.build(s2, 0.0)
+    eng.solve(engine.INVERT_REDUCED)
+    dx, Q = expanded_pass(eng)
+    fresh = engine.Engine(fp)
+    fresh.set_parameters(fp.values)
+    dx0, Q0 = expanded_pass(fresh)
+    assert Q.size == fp.n_unknowns * (fp.n_unknowns + 1) // 2
+    assert np.array_equal(dx, dx0)
+    assert np.array_equal(Q, Q0)
+
+
 def test_expanded_mode_falls_back_to_full_where_it_cannot_apply(oracle_mod):
     """No EO pre-elimination (here: ordinary image groups kept outside it) -> FULL_EXPANDED is served as FULL (like REDUCED is, jaicov_neq.h)."""
     fp = scene.config("tiny")
