@@ -16,6 +16,7 @@
 #include "../../include/jaicov_neq.h"
 #include "ba_kernels.h"
 #include "batchinv.h"
+#include "datum.h"
 #include "dense.h"
 #include "gemm_f64.h"
 #include "reliability.h"
@@ -300,6 +301,8 @@ struct jaicov_engine {
     const double *d_ll_diag = nullptr;                 // [2 n_ip + n_dg_rows]: diag(D) of every image coordinate (engine order) and direct row
     double sigma2_acc = 0.0;                           // sigma0^2 of the last accumulate
     double q_sigma2 = 0.0, q_lambda = 0.0;             // sigma0^2 and damping of the build whose system the cofactor matrix inverts
+    std::vector<double> q_vals;                        // slot values of that build: the datum rows of jaicov_datum_transform (datum.hip)
+    jaicov::DatumState *datum = nullptr;               // S of the last jaicov_datum_transform and its work buffers
 };
 
 #define FAIL(e, code, msg)                 \
@@ -501,6 +504,7 @@ extern "C" void jaicov_neq_destroy(jaicov_engine *e) {
     if (e->stream) hipStreamSynchronize(e->stream);
     jaicov::xform_state_free(e->xform);
     jaicov::rel_state_free(e->rel);
+    jaicov::datum_state_free(e->datum);
     e->solver.release();
     e->solverS.release();
     e->dm.release();
@@ -1177,17 +1181,17 @@ extern "C" int jaicov_neq_accumulate(jaicov_engine *e, double sigma2) {
     return JAICOV_OK;
 }
 
-// datum rows on the host (BA:493-635) from the host copy of the parameter values
-static int datum_rows_host(jaicov_engine *e) {
-    const int d = e->d, Upad = e->Upad;
-    std::fill(e->hB.begin(), e->hB.end(), 0.0);
+// datum rows (BA:493-635) of the point mask at the slot values `vals`: B [d][stride] (columns >= stride are not stored)
+static int datum_rows(jaicov_engine *e, const uint8_t *mask, const double *vals, std::vector<double> &hB, int stride) {
+    const int d = e->d;
+    std::fill(hB.begin(), hB.end(), 0.0);
     if (d == 0) return JAICOV_OK;
     double x0 = 0, y0 = 0, z0 = 0;
     int count = 0;
     for (int pt = 0; pt < e->n_points; pt++) {
         const int32_t *c = &e->h_point_col[3 * pt];
-        if (!e->h_point_datum[pt] || c[0] < 0 || c[1] < 0 || c[2] < 0) continue;
-        x0 += e->h_vals[3 * pt]; y0 += e->h_vals[3 * pt + 1]; z0 += e->h_vals[3 * pt + 2];
+        if (!mask[pt] || c[0] < 0 || c[1] < 0 || c[2] < 0) continue;
+        x0 += vals[3 * pt]; y0 += vals[3 * pt + 1]; z0 += vals[3 * pt + 2];
         count++;
     }
     if (count < 3) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "not enough object points to realise the frame datum (BA:515-516)");
@@ -1198,11 +1202,12 @@ static int datum_rows_host(jaicov_engine *e) {
     const int rx = (f & JAICOV_DATUM_RX) ? row++ : -1, ry = (f & JAICOV_DATUM_RY) ? row++ : -1, rz = (f & JAICOV_DATUM_RZ) ? row++ : -1;
     const int ms = (f & JAICOV_DATUM_SCALE) ? row++ : -1;
     double norm[7] = {0, 0, 0, 0, 0, 0, 0};
-    auto B = [&](int r, int c) -> double & { return e->hB[(size_t)r * Upad + c]; };
+    double sink = 0.0;
+    auto B = [&](int r, int c) -> double & { return c < stride ? hB[(size_t)r * stride + c] : sink; };
     for (int pt = 0; pt < e->n_points; pt++) {
         const int32_t *c = &e->h_point_col[3 * pt];
-        if (!e->h_point_datum[pt] || c[0] < 0 || c[1] < 0 || c[2] < 0) continue;
-        const double x = e->h_vals[3 * pt] - x0, y = e->h_vals[3 * pt + 1] - y0, z = e->h_vals[3 * pt + 2] - z0;
+        if (!mask[pt] || c[0] < 0 || c[1] < 0 || c[2] < 0) continue;
+        const double x = vals[3 * pt] - x0, y = vals[3 * pt + 1] - y0, z = vals[3 * pt + 2] - z0;
         if (tx >= 0) { B(tx, c[0]) = 1.0; norm[tx] += 1.0; }
         if (ty >= 0) { B(ty, c[1]) = 1.0; norm[ty] += 1.0; }
         if (tz >= 0) { B(tz, c[2]) = 1.0; norm[tz] += 1.0; }
@@ -1211,12 +1216,18 @@ static int datum_rows_host(jaicov_engine *e) {
         if (rz >= 0) { B(rz, c[0]) = y; B(rz, c[1]) = -x; norm[rz] += x * x + y * y; }
         if (ms >= 0) { B(ms, c[0]) = x; B(ms, c[1]) = y; B(ms, c[2]) = z; norm[ms] += x * x + y * y + z * z; }
     }
+    const int cend = std::min(e->U, stride);
     for (int r = 0; r < d; r++) {
         const double s = sqrt(norm[r]);
-        for (int c = 0; c < e->U; c++)
-            if (e->hB[(size_t)r * Upad + c] != 0.0) e->hB[(size_t)r * Upad + c] = e->hB[(size_t)r * Upad + c] / s;
+        for (int c = 0; c < cend; c++)
+            if (hB[(size_t)r * stride + c] != 0.0) hB[(size_t)r * stride + c] = hB[(size_t)r * stride + c] / s;
     }
     return JAICOV_OK;
+}
+
+// datum rows of the build from the host copy of the parameter values
+static int datum_rows_host(jaicov_engine *e) {
+    return datum_rows(e, e->h_point_datum.data(), e->h_vals.data(), e->hB, e->Upad);
 }
 
 extern "C" int jaicov_neq_finalize(jaicov_engine *e, double sigma2, double lambda, int simulation) {
@@ -1740,6 +1751,8 @@ struct Solve {
             e->have_Q = true;
             e->q_sigma2 = e->sigma2_acc;
             e->q_lambda = e->lambda_used;
+            e->q_vals = e->h_vals;
+            jaicov::datum_state_invalidate(e->datum);
             e->q_reduced = schur && !expand;
             e->q_order = expand ? e->U : U;
         }
@@ -1929,6 +1942,28 @@ int jaicov::engine_rel_view(jaicov_engine *e, RelView *v, int rows) {
     v->state = &e->rel;
     v->err = &e->err;
     return rows ? ensure_rows(e) : JAICOV_OK;
+}
+
+// datum.hip transforms the cofactor matrix in place through this view (include/jaicov_datum.h)
+void jaicov::engine_datum_view(jaicov_engine *e, DatumView *v) {
+    DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
+    v->device = e->device;
+    v->stream = e->stream;
+    v->have_q = e->have_Q;
+    v->sharded = !e->all_images || !e->opts.apply_shared || e->ip0 != 0 || e->ip_count != e->p.n_ip;
+    v->Q = qs.Q;
+    v->ld = qs.ld;
+    v->order = e->q_order;
+    v->d = e->d;
+    v->n_points = e->n_points;
+    v->state = &e->datum;
+    v->err = &e->err;
+}
+
+int jaicov::engine_datum_rows(jaicov_engine *e, const uint8_t *mask, std::vector<double> &B, int stride) {
+    if (e->q_vals.size() != (size_t)e->n_slots) FAIL(e, JAICOV_ERR_BAD_STATE, "no inverting solve has recorded its parameter values");
+    B.assign((size_t)e->d * stride, 0.0);
+    return datum_rows(e, mask, e->q_vals.data(), B, stride);
 }
 
 static int cofactor_sub_impl(jaicov_engine *e, const int32_t *idx, int32_t k, double scale, double *out) {

@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` / ``include/jaicov_transform.h`` /
-``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` (``csrc/libjaicov_neq.so``).
+``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_datum.h`` (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
 library has not been built, and every call fails with ``EngineError`` when no gfx950 device is present.
@@ -44,6 +44,8 @@ XFORM_EXPORTS = [
 DLT_EXPORTS = ["jaicov_dlt_adjust"]
 # include/jaicov_reliability.h: residuals, redundancy numbers and test values of every observation on the device
 REL_EXPORTS = ["jaicov_rel_run", "jaicov_rel_get", "jaicov_rel_summary", "jaicov_rel_release"]
+# include/jaicov_datum.h: the cofactor matrix re-expressed in another datum (S-transformation) on the device
+DATUM_EXPORTS = ["jaicov_datum_transform", "jaicov_datum_apply"]
 # jaicov_dlt_restriction (DirectLinearTransformation.RestrictionType, DT:51-58 order) and the per-image status values
 DLT_IDENTICAL_PRINCIPLE_DISTANCE, DLT_ROTATION_WITHOUT_SHEAR, DLT_FIXED_PRINCIPLE_DISTANCE_X, DLT_FIXED_PRINCIPLE_DISTANCE_Y, \
     DLT_FIXED_PRINCIPAL_POINT_X, DLT_FIXED_PRINCIPAL_POINT_Y = range(6)
@@ -151,6 +153,8 @@ def load_library():
     L.jaicov_rel_get.argtypes = [vp, _pd, _pd, _pd, _pd, C.c_int32]
     L.jaicov_rel_summary.argtypes = [vp, _pd, C.c_int32]
     L.jaicov_rel_release.argtypes = [vp]
+    L.jaicov_datum_transform.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int32]
+    L.jaicov_datum_apply.argtypes = [vp, _pd, _pd, C.c_int32]
     L.jaicov_dlt_adjust.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pi, C.c_int32, C.c_int32, _pd, _pi, _pi, _pd]
     _LIB = L
     return L
@@ -378,6 +382,21 @@ class Engine:
 
     def reliability_release(self):
         self._chk(self.L.jaicov_rel_release(self._h))
+
+    # datum transformation (include/jaicov_datum.h) --------------------------------------------------------------------------------
+    def datum_transform(self, mask):
+        """Replaces the cofactor matrix, in place, by the one of the datum whose points the mask flags (one entry per object point,
+        the meaning of FlatProblem.point_datum; the defect flags stay the engine's).  Every consumer of the cofactor matrix sees the
+        new datum until the next inverting solve."""
+        m = np.ascontiguousarray(mask, np.uint8).ravel()
+        self._chk(self.L.jaicov_datum_transform(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8)), m.size))
+
+    def datum_apply(self, v):
+        """S v with the S = I - Z B' of the last datum_transform (v of length cofactor_order(); border entries of the result 0)."""
+        x = np.ascontiguousarray(v, np.float64).ravel()
+        out = np.zeros(x.size)
+        self._chk(self.L.jaicov_datum_apply(self._h, _p(x), _p(out), x.size))
+        return out
 
     def get_rows(self, ip_begin, ip_count):
         w = np.zeros((ip_count, 2)); A = np.zeros((ip_count, 2, KROW))

@@ -145,6 +145,8 @@ PYBIND11_MODULE(_jaicov_host, m) {
             auto arr = [](const std::vector<double> &x) { return py::array_t<double>((py::ssize_t)x.size(), x.data()); };
             return py::make_tuple(arr(o.v), arr(o.qvv), arr(o.r), arr(o.t));
         }, py::arg("sigma2Test"), "(v, qvv, r, t) of every observation row (include/jaicov_reliability.h)")
+        .def("transformDatum", &BundleAdjustment::transformDatum,
+             "re-express the cofactor matrix in the datum of the points flagged now (include/jaicov_datum.h)")
         .def("useCentroidedCoordinates", &BundleAdjustment::useCentroidedCoordinates)
         .def("centroidCoordinates", &BundleAdjustment::centroidCoordinates)
         .def("applyAposterioriVarianceOfUnitWeight", &BundleAdjustment::applyAposterioriVarianceOfUnitWeight)

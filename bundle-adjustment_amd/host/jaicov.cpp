@@ -479,6 +479,17 @@ BundleAdjustment::ObservationReliability BundleAdjustment::observationReliabilit
     return o;
 }
 
+void BundleAdjustment::transformDatum() {
+    if (!engine_ || inversion_ == MatrixInversion::NONE || !hasCofactorMatrix())
+        throw std::runtime_error("no cofactor matrix: run estimateModel with MatrixInversion FULL or REDUCED first");
+    std::vector<uint8_t> mask(objectCoordinates_.size());
+    for (size_t i = 0; i < objectCoordinates_.size(); i++) mask[i] = objectCoordinates_[i]->isDatum() ? 1 : 0;
+    const int rc = jaicov_datum_transform(engine_, mask.data(), (int32_t)mask.size());
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_datum_transform: ") + jaicov_neq_last_error(engine_));
+    Qxx_.clear();
+    qxxOnDevice_ = true;      // a copy fetched before is stale: fetched again on demand
+}
+
 // CTEO:49-121: rows, coordinates and sigma2 J Qxx J' on the device (jaicov_xform_run), the results copied back
 void CoordinateTransformationExteriorOrientation::transform(const std::vector<ObjectCoordinate *> &objectCoordinatesToTransform,
                                                             const std::vector<std::pair<Image *, std::vector<Image *>>> &imagesToAlign,

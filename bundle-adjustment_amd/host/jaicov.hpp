@@ -29,6 +29,7 @@
 #include "../../include/jaicov_transform.h"
 #include "../../include/jaicov_dlt.h"
 #include "../../include/jaicov_reliability.h"
+#include "../../include/jaicov_datum.h"
 
 namespace jaicov::host {
 
@@ -513,6 +514,10 @@ public:
         std::vector<double> v, qvv, r, t;
     };
     ObservationReliability observationReliability(double sigma2Test) const;
+    // The cofactor matrix of the last estimateModel re-expressed, on the device, in the datum of the points whose isDatum() flag is
+    // set NOW (Baarda's S-transformation, include/jaicov_datum.h): re-flag the points, then call.  Needs a free network (d > 0)
+    // and MatrixInversion FULL or REDUCED; cofactorSub, getCofactorMatrix and the writers see the new datum afterwards.
+    void transformDatum();
     const std::string &lastError() const { return lastError_; }
     jaicov_engine *nativeEngine() const { return engine_; }     // the engine of the last estimateModel (null before)
 

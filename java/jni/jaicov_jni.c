@@ -1,6 +1,6 @@
 /*
  * JNI shim between NativeNormalEquationEngine (Java) and the C ABI of include/jaicov_neq.h, include/jaicov_transform.h,
- * include/jaicov_dlt.h and include/jaicov_reliability.h.
+ * include/jaicov_dlt.h, include/jaicov_reliability.h and include/jaicov_datum.h.
  * The build image has no JDK, so this file is not built by __graft_entry__.build(); on a box with a JDK:
  *   gcc -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -I../../include jaicov_jni.c \
  *       -L../../bundle-adjustment_amd/csrc -ljaicov_neq -o libjaicov_jni.so
@@ -23,6 +23,7 @@
 #include "jaicov_transform.h"
 #include "jaicov_dlt.h"
 #include "jaicov_reliability.h"
+#include "jaicov_datum.h"
 
 #define ENG(h) ((jaicov_engine *)(intptr_t)(h))
 #define NAT(name) Java_org_applied_1geodesy_adjustment_bundle_nativeengine_NativeNormalEquationEngine_##name
@@ -544,6 +545,39 @@ JNIEXPORT jint JNICALL NAT(relSummary)(JNIEnv *e, jclass k, jlong h, jdoubleArra
     return rc;
 }
 JNIEXPORT jint JNICALL NAT(relRelease)(JNIEnv *e, jclass k, jlong h) { (void)e; (void)k; return jaicov_rel_release(ENG(h)); }
+
+/* --- include/jaicov_datum.h: the cofactor matrix re-expressed in another datum (S-transformation) ------------------------------ */
+/* pointDatum: one int per object point (nonzero = datum point; the stub jni.h and the binding test know no byte[] natives), read
+ * through a GetIntArrayElements copy (JNI_ABORT) into the byte mask of the C ABI; the engine checks the count against the problem's */
+JNIEXPORT jint JNICALL NAT(datumTransform)(JNIEnv *e, jclass k, jlong h, jintArray pointDatum) {
+    (void)k;
+    if (!pointDatum) return JAICOV_ERR_BAD_ARGUMENT;
+    const jsize n = (*e)->GetArrayLength(e, pointDatum);
+    uint8_t *mask = (uint8_t *)malloc((size_t)(n > 0 ? n : 1));
+    if (!mask) return JAICOV_ERR_OUT_OF_MEMORY;
+    jint *p = (*e)->GetIntArrayElements(e, pointDatum, NULL);
+    if (!p) { free(mask); return JAICOV_ERR_OUT_OF_MEMORY; }
+    for (jsize i = 0; i < n; i++) mask[i] = p[i] != 0;
+    (*e)->ReleaseIntArrayElements(e, pointDatum, p, JNI_ABORT);
+    const int rc = jaicov_datum_transform(ENG(h), mask, (int32_t)n);
+    free(mask);
+    return rc;
+}
+/* out = S v (v and out at least n long, n = cofactorOrder()) through malloc'd copies and SetDoubleArrayRegion */
+JNIEXPORT jint JNICALL NAT(datumApply)(JNIEnv *e, jclass k, jlong h, jdoubleArray v, jdoubleArray out, jint n) {
+    (void)k;
+    if (n < 0 || !v || !out || (*e)->GetArrayLength(e, v) < n || (*e)->GetArrayLength(e, out) < n) return JAICOV_ERR_BAD_ARGUMENT;
+    double *buf = (double *)malloc(sizeof(double) * (size_t)(n > 0 ? n : 1));
+    if (!buf) return JAICOV_ERR_OUT_OF_MEMORY;
+    double *p = (double *)(*e)->GetDoubleArrayElements(e, v, NULL);
+    if (!p) { free(buf); return JAICOV_ERR_OUT_OF_MEMORY; }
+    memcpy(buf, p, sizeof(double) * (size_t)n);
+    (*e)->ReleaseDoubleArrayElements(e, v, p, JNI_ABORT);
+    const int rc = jaicov_datum_apply(ENG(h), buf, buf, (int32_t)n);
+    if (rc == JAICOV_OK) (*e)->SetDoubleArrayRegion(e, out, 0, n, buf);
+    free(buf);
+    return rc;
+}
 
 /* --- include/jaicov_dlt.h: DirectLinearTransformation.adjust for a batch of images (no engine) ---------------------------------- */
 /* the inputs are read through Get<Type>ArrayElements copies (JNI_ABORT); out comes back through SetDoubleArrayRegion, status and

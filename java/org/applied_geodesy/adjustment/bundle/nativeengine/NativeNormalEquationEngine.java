@@ -232,6 +232,21 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 	/** frees the device result of reliability() */
 	public void releaseReliability() { check(relRelease(handle)); }
 
+	/**
+	 * Re-expresses the cofactor matrix of the last inverting solve, in place on the device, in the datum of the object points with
+	 * pointDatum[i] != 0 (one entry per point, the meaning of the problem's point_datum; Baarda's S-transformation,
+	 * include/jaicov_datum.h).  Needs a free network (d > 0); getCofactor, getCofactorSub, getDispersionSub, the writers and
+	 * transform() see the new datum until the next inverting solve.
+	 */
+	public void transformDatum(int[] pointDatum) { check(datumTransform(handle, pointDatum)); }
+	/** S v with the S of the last transformDatum (v.length >= cofactorOrder()): brings a coordinate difference into that datum */
+	public double[] applyDatumTransformation(double[] v) {
+		final int n = cofactorOrder(handle);
+		double[] out = new double[Math.max(n, 0)];
+		check(datumApply(handle, v, out, n));
+		return out;
+	}
+
 	/** jaicov_dlt status values (include/jaicov_dlt.h) */
 	public static final int DLT_CONVERGED = 0, DLT_NOT_CONVERGED = 1, DLT_TOO_FEW_POINTS = 2, DLT_SINGULAR = 3, DLT_NOT_FINITE = 4;
 
@@ -309,5 +324,7 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 	private static native int relGet(long h, int n, double[] v, double[] qvv, double[] r, double[] t);
 	private static native int relSummary(long h, double[] out);
 	private static native int relRelease(long h);
+	private static native int datumTransform(long h, int[] pointDatum);
+	private static native int datumApply(long h, double[] v, double[] out, int n);
 	private static native int dltAdjust(int[] obsBegin, double[] xy, double[] xyz, double[] io, int[] ioFixed, int[] restrictions, int maxIterations, double[] out, long[] status, long[] solves);
 }
