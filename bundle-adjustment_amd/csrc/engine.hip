@@ -16,6 +16,7 @@
 #include "../../include/jaicov_neq.h"
 #include "ba_kernels.h"
 #include "batchinv.h"
+#include "create_plan.h"
 #include "datum.h"
 #include "dense.h"
 #include "gemm_f64.h"
@@ -234,7 +235,7 @@ struct jaicov_engine {
     // host copies
     jaicov_engine_options opts{};
     int U = 0, Upad = 0, d = 0, datum_flags = 0, n_slots = 0;
-    std::vector<int32_t> h_slot_col, h_point_col;
+    std::vector<int32_t> h_slot_col;        // column of every slot [3P | 3C | n_dist | 6I]
     std::vector<uint8_t> h_point_datum;
     std::vector<double> h_vals, h_V;
     int n_points = 0;
@@ -259,11 +260,9 @@ struct jaicov_engine {
     bool q_reduced = false, solverS_has_inverse = false;
     std::vector<int> h_blk_images;   // image of every block handled by this engine
     std::vector<int32_t> h_caller_block; // internal image block -> the caller's block index (-1: an ordinary image served as a block); empty: identity
-    bool synthesized_blocks = false;     // ordinary image groups are served as image blocks with block-diagonal weights (create_impl)
-    bool compact_blocks = false;         // ... and their weights are kept as 2 x 2 blocks (DevProblem::ip_w3), not as m x m matrices
     std::vector<int32_t> h_perm_local;   // per image point of a dense block: engine position -> caller's position inside the block (empty: identity)
     std::vector<int64_t> h_blk_w_off;    // offset of every image block's weight in p.blk_w
-    std::vector<int32_t> h_blk_ip_begin; // copy of blk_ip_begin
+    std::vector<int32_t> h_blk_ip_begin; // blk_ip_begin of the effective description (CreatePlan::D)
     std::vector<uint8_t> h_blk_mine;     // this engine holds the block's weight
     std::vector<int32_t> ip_old2new; // empty, or: engine position of the caller's observation (dense blocks are column-sorted)
     int e0 = 0;                   // first EO column == order of the reduced system
@@ -291,7 +290,7 @@ struct jaicov_engine {
     std::vector<double> hB;      // [d][Upad] datum rows (unscaled), host
     double timings[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double create_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // jaicov_neq_create: [0] whole call, [1] host time in the dispersion uploads, [2] dispersions -> weights (wall),
-                                                      // [3] validation + tables + structure upload, [4] work buffers + full-order solver, [5] EO pre-elimination buffers + reduced solver
+                                                      // [3] validation + tables (the plan, create_plan.h) + structure upload, [4] work buffers + full-order solver, [5] EO pre-elimination buffers + reduced solver
     hipEvent_t ev[10] = {};
     bool pp_plain_ok = false;   // the point x point gather may store its strips (see PPGather::plain)
     hipEvent_t ev_first = nullptr, ev_all = nullptr;   // solve(): first panel's columns / whole matrix copied into the solver
@@ -320,15 +319,15 @@ struct jaicov_engine {
     } while (0)
 #define TRY(x) do { const int _rc = (x); if (_rc) return _rc; } while (0)      // a callee's status (JAICOV_*), passed on
 
-template <typename T>
-static int upload(jaicov_engine *e, const T *src, size_t count, const T **dst) {
+template <typename T, typename P>      // P: T or const T
+static int upload(jaicov_engine *e, const T *src, size_t count, P **dst) {
     *dst = nullptr;
     if (count == 0) return JAICOV_OK;
     void *ptr = nullptr;
     HIPE(e, hipMalloc(&ptr, count * sizeof(T)));
     e->allocs.push_back(ptr);
     HIPE(e, hipMemcpy(ptr, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *dst = (const T *)ptr;
+    *dst = (P *)ptr;
     return JAICOV_OK;
 }
 template <typename T>
@@ -517,18 +516,9 @@ extern "C" void jaicov_neq_destroy(jaicov_engine *e) {
     delete e;
 }
 
-static int create_impl(jaicov_engine *e, const jaicov_problem_desc *D_in, const jaicov_engine_options *opts) {
-    const jaicov_problem_desc *D = D_in;
-    jaicov_problem_desc Dperm;   // the description with the observations of dense image blocks in column order
-    std::vector<int32_t> pv_image, pv_point, perm_local;
-    std::vector<double> pv_x, pv_y, pv_vx, pv_vy, pv_rho;
-    HIPE(e, hipSetDevice(e->device));
-    e->deterministic = e->opts.deterministic >= 0;      // 0 = default = ON since round 4 (costs 0.3 ms per pass at config 4); < 0: arrival-order sums
-    e->refine_steps = e->opts.refinement == 0 ? 1 : (e->opts.refinement < 0 ? 0 : std::min(e->opts.refinement, 4));
-    hipDeviceProp_t prop;
-    HIPE(e, hipGetDeviceProperties(&prop, e->device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        FAIL(e, JAICOV_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+// ---- engine creation, second stage: what happens on the device.  The first stage, every decision and table that needs
+//      no device, is the plan (create_plan.h); each function here takes the engine and the finished plan. ---------------------
+static int acquire_stream_and_events(jaicov_engine *e) {
     e->stream = jaicov::stream_acquire(jaicov::STREAM_PLAIN);
     if (!e->stream) FAIL(e, JAICOV_ERR_DEVICE, "no stream");
     for (auto &evt : e->ev) HIPE(e, hipEventCreate(&evt));
@@ -538,533 +528,258 @@ static int create_impl(jaicov_engine *e, const jaicov_problem_desc *D_in, const 
     HIPE(e, hipEventCreateWithFlags(&e->ev_all, hipEventDisableTiming));
     HIPE(e, hipEventCreate(&e->ev_r0));
     HIPE(e, hipEventCreate(&e->ev_r1));
+    return JAICOV_OK;
+}
 
-    const int U = D->n_unknowns, d = D->rank_defect;
-    e->U = U; e->d = d; e->datum_flags = D->datum_flags;
-    e->Upad = ((U + 127) / 128) * 128;
-    if (e->Upad == 0) e->Upad = 128;
-    e->n_points = D->n_points;
-    e->n_slots = 3 * D->n_points + 3 * D->n_cameras + D->n_dist + 6 * D->n_images;
-    // ---- validate --------------------------------------------------------------------------------------------
-    if (__builtin_popcount((unsigned)D->datum_flags) != d || d < 0 || d > 7) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "datum_flags / rank_defect mismatch");
-    for (int c = 0; c < D->n_cameras; c++) {
-        const int jb = D->cam_dist_begin[c], je = D->cam_dist_begin[c + 1];
-        if (je - jb > JAICOV_MAX_DIST_PER_CAMERA) FAIL(e, JAICOV_ERR_UNSUPPORTED, "too many distortion coefficients for one camera");
-        for (int j = jb + 1; j < je; j++)
-            if (D->dist_kind[j] < D->dist_kind[j - 1]) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "distortion coefficients must be in DistortionModel.Type order");
-        // AffinityShearDistortionModel always owns Cx and Cy, TangentialDistortionModel Bx and By (+ optional Bi): a lone
-        // member would silently drop out of the model (ASF:37-81, TDF:39-134 read both)
-        int cnt[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int j = jb; j < je; j++) {
-            if (D->dist_kind[j] < 0 || D->dist_kind[j] > JAICOV_DIST_ZERNIKE_Z) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "unknown distortion coefficient kind");
-            if (D->dist_kind[j] >= JAICOV_DIST_ZERNIKE_X && (D->dist_order[j] < 1 || D->dist_order[j] > 119))
-                FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "Zernike coefficient order must be 1..119 (ZernikeDistortionModel.java:67-68)");
-            cnt[D->dist_kind[j]]++;
-        }
-        if (cnt[0] != cnt[1] || cnt[0] > 1 || cnt[2] != cnt[3] || cnt[2] > 1 || (cnt[4] > 0 && cnt[2] == 0))
-            FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "affinity (Cx, Cy) and tangential (Bx, By [, Bi]) coefficients come as complete models");
-    }
-    for (int i = 1; i < D->n_image_points; i++)
-        if (D->ip_image[i] < D->ip_image[i - 1]) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "image points must be image-major");
-    e->h_slot_col.resize(e->n_slots);
-    {
-        int s = 0;
-        for (int i = 0; i < 3 * D->n_points; i++) e->h_slot_col[s++] = D->point_col[i];
-        for (int i = 0; i < 3 * D->n_cameras; i++) e->h_slot_col[s++] = D->io_col[i];
-        for (int i = 0; i < D->n_dist; i++) e->h_slot_col[s++] = D->dist_col[i];
-        for (int i = 0; i < 6 * D->n_images; i++) e->h_slot_col[s++] = D->eo_col[i];
-        std::vector<char> seen(U > 0 ? U : 1, 0);
-        for (int c : e->h_slot_col) {
-            if (c == JAICOV_COL_FIXED) continue;
-            if (c < d || c >= U || seen[c]) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "columns must be a permutation of d..U-1");
-            seen[c] = 1;
-        }
-    }
-    e->h_point_col.assign(D->point_col, D->point_col + 3 * D->n_points);
-    e->h_point_datum.assign(D->point_datum, D->point_datum + D->n_points);
-
-    // ---- image range of this engine ----------------------------------------------------------------------------
-    int ib = 0, ie = D->n_images;
-    if (opts && opts->image_begin >= 0 && opts->image_end >= 0) { ib = opts->image_begin; ie = opts->image_end; }
-    if (ib < 0 || ie > D->n_images || ib > ie) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "bad image range");
-    e->all_images = ib == 0 && ie == D->n_images;
-    {
-        const int32_t *b = std::lower_bound(D->ip_image, D->ip_image + D->n_image_points, ib);
-        const int32_t *en = std::lower_bound(D->ip_image, D->ip_image + D->n_image_points, ie);
-        e->ip0 = (int)(b - D->ip_image);
-        e->ip_count = (int)(en - b);
-    }
-    // ---- ordinary image groups as jointly dispersed groups with a block-diagonal weight ----------------------------------
-    // reduceNormalEquationSystem (BA:1197-1342) eliminates the exterior orientation of EVERY image, whatever its stochastic
-    // model; the device path of that elimination (schur.hip) is written for image groups with a joint weight matrix.  An image
-    // whose points are ordinary ImageCoordinate groups (diagonal / 2 x 2 weights, PDF:296-319) is the special case of a
-    // block-diagonal joint weight: when the whole problem qualifies, every such image becomes an internal image block whose
-    // inv(D) is filled from (var_x, var_y, rho) in closed form -- no dispersion is uploaded or inverted -- and the
-    // elimination, the point x point gather and the reduced solve serve it like any other block.  All or nothing, decided on
-    // the WHOLE problem (every rank of a sharded run must assemble a system of the same order).
-    jaicov_problem_desc Dsyn;
-    std::vector<int32_t> syn_begin;
-    std::vector<int64_t> syn_off;
-    e->h_caller_block.clear();
-    {
-        bool ok = e->opts.ordinary_group_elimination >= 0 && e->opts.assembly_mode == 0 && D->n_images > 0;
-        const int e0 = D->n_images > 0 ? D->eo_col[0] : -1;
-        ok = ok && e0 >= d && e0 + 6 * D->n_images == U;
-        for (int i = 0; ok && i < 6 * D->n_images; i++) ok = D->eo_col[i] == e0 + i;
-        const int s_eo = 3 * D->n_points + 3 * D->n_cameras + D->n_dist;
-        for (int r = 0; ok && r < D->n_direct_rows; r++) ok = D->dg_slot[r] < s_eo;
-        std::vector<int32_t> img_b(D->n_images + 1, 0), img_blk(std::max(1, D->n_images), -1);
-        if (ok) {
-            for (int ip = 0; ip < D->n_image_points; ip++) {
-                if (D->ip_image[ip] < 0 || D->ip_image[ip] >= D->n_images) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "image index out of range");
-                img_b[D->ip_image[ip] + 1]++;
-            }
-            for (int i = 0; i < D->n_images; i++) img_b[i + 1] += img_b[i];
-            for (int g = 0; ok && g < D->n_image_blocks; g++) {       // a caller's block must be ALL observations of its image
-                const int b = D->blk_ip_begin[g], en = D->blk_ip_begin[g + 1];
-                if (en <= b || b < 0 || en > D->n_image_points) { ok = false; break; }
-                const int img = D->ip_image[b];
-                ok = img_b[img] == b && img_b[img + 1] == en && img_blk[img] < 0;
-                if (ok) img_blk[img] = g;
-            }
-            int64_t syn_bytes = 0;
-            bool any = false;
-            for (int i = 0; ok && i < D->n_images; i++) {
-                const int64_t cnt = img_b[i + 1] - img_b[i];
-                if (img_blk[i] >= 0) continue;
-                any = true;
-                ok = cnt >= 3 && 2 * cnt <= 4096;
-                syn_bytes += 4 * cnt * cnt * (int64_t)sizeof(double);
-            }
-            // (the dense form of the block-diagonal weights -- the alternative assembly forms only -- needs m^2 doubles per image)
-            ok = ok && any && (assembly_form() == ASSEMBLY_DEFAULT || assembly_form() == ASSEMBLY_NO_FORK || syn_bytes <= ((int64_t)16 << 30));
-            // Size rule (round 5; option 0 = default): serving ordinary images as blocks costs six block-kernel launches where the ordinary assembly
-            // is one (+0.10 ms per pass at BASELINE config 2), and pays through the factorisation's block columns: eliminate when the 6 I exterior-
-            // orientation columns are at least two 128-blocks of it (config 2: order 726 -> 606, six block columns -> five: not worth it, 0.79 vs
-            // 0.86 ms per pass; config 3: 29 -> 24, the bundled example 10 -> 4: yes).  A property of the WHOLE problem, so every rank of a
-            // sharded run decides alike.  > 0 forces the elimination at any size (tests), < 0 switches it off.
-            // (A problem that ALSO has jointly dispersed images runs the block kernels anyway, and only with every image served as a block
-            // can any exterior orientation be eliminated: no size rule there.)
-            if (ok && e->opts.ordinary_group_elimination == 0 && D->n_image_blocks == 0)
-                ok = (U + 127) / 128 - (U - 6 * D->n_images + 127) / 128 >= 2;
-        }
-        if (ok) {
-            syn_begin.push_back(0);
-            for (int i = 0; i < D->n_images; i++) {
-                syn_begin.push_back(img_b[i + 1]);
-                syn_off.push_back(img_blk[i] >= 0 ? D->blk_disp_offset[img_blk[i]] : (int64_t)-1);
-                e->h_caller_block.push_back(img_blk[i]);
-            }
-            Dsyn = *D;
-            Dsyn.n_image_blocks = D->n_images;
-            Dsyn.blk_ip_begin = syn_begin.data();
-            Dsyn.blk_disp_offset = syn_off.data();
-            D = &Dsyn;
-            e->synthesized_blocks = true;
-        }
-    }
-    // ---- blocks / segments -------------------------------------------------------------------------------------
-    std::vector<uint8_t> in_block(D->n_image_points + 1, 0);
-    std::vector<int32_t> blk_list, blk_ip_list, seg_b, seg_e;
-    std::vector<int64_t> blk_w_off(D->n_image_blocks + 1, 0);
-    int64_t w_total = 0, w_total_saved = 0;
-    for (int g = 0; g < D->n_image_blocks; g++) {
-        const int b = D->blk_ip_begin[g], en = D->blk_ip_begin[g + 1];
-        if (en < b || b < 0 || en > D->n_image_points) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "image blocks must be ascending ranges");
-        for (int ip = b; ip < en; ip++) {
-            if (D->ip_image[ip] != D->ip_image[b]) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "an image block must not span images");
-            in_block[ip] = 1;
-        }
-        // an ordinary image served as a block (no dispersion of its own): block-diagonal weights in compact form (DevProblem::ip_w3),
-        // dense only under the alternative assembly forms, whose kernels read m x m weights
-        const bool compact = e->synthesized_blocks && D->blk_disp_offset[g] < 0 && (assembly_form() == ASSEMBLY_DEFAULT || assembly_form() == ASSEMBLY_NO_FORK);
-        blk_w_off[g] = compact ? -1 : w_total;
-        const bool mine = en > b && D->ip_image[b] >= ib && D->ip_image[b] < ie;
-        if (mine) {
-            const int64_t m = 2 * (int64_t)(en - b);
-            if (!compact) w_total += m * m;
-            else e->compact_blocks = true;
-            blk_list.push_back(g);
-            for (int ip = b; ip < en; ip++) blk_ip_list.push_back(ip);
-            e->max_m = std::max(e->max_m, (int)m);
-        }
-    }
-    for (int ip = e->ip0; ip < e->ip0 + e->ip_count;) {
-        if (in_block[ip]) { ip++; continue; }
-        int en = ip;
-        while (en < e->ip0 + e->ip_count && !in_block[en] && D->ip_image[en] == D->ip_image[ip] && en - ip < SEG) en++;
-        seg_b.push_back(ip); seg_e.push_back(en);
-        ip = en;
-    }
-    w_total_saved = w_total;
-    // ---- column-sorted storage inside dense image blocks -------------------------------------------------------
-    // The point x point gather (assemble.hip) streams, for one object point and one range of columns, the weights of
-    // the partner points of an image; with the image's observations stored in the order of their points' columns
-    // those partners are contiguous.  The engine therefore keeps the observations of every dense block (and the
-    // block's dispersion) in column order; e->ip_old2new maps the caller's observation index for get_rows().
-    {
-        const int NOCOL = 1 << 30;
-        auto key = [&](int ip) {
-            int k = NOCOL;
-            for (int a = 0; a < 3; a++) {
-                const int c = D->point_col[3 * D->ip_point[ip] + a];
-                if (c >= 0) k = std::min(k, c);
-            }
-            return k;
-        };
-        std::vector<int32_t> new2old(D->n_image_points);
-        for (int ip = 0; ip < D->n_image_points; ip++) new2old[ip] = ip;
-        bool permuted = false;
-        for (int g : blk_list) {
-            const int b = D->blk_ip_begin[g], en = D->blk_ip_begin[g + 1];
-            std::vector<int> k(en - b);
-            for (int ip = b; ip < en; ip++) k[ip - b] = key(ip);
-            std::stable_sort(new2old.begin() + b, new2old.begin() + en, [&](int x, int y) { return k[x - b] < k[y - b]; });
-            for (int ip = b; ip < en && !permuted; ip++) permuted = new2old[ip] != ip;
-        }
-        if (permuted) {
-            const size_t n = (size_t)D->n_image_points;
-            pv_image.resize(n); pv_point.resize(n); pv_x.resize(n); pv_y.resize(n); pv_vx.resize(n); pv_vy.resize(n); pv_rho.resize(n);
-            perm_local.resize(n);
-            e->ip_old2new.resize(n);
-            for (size_t i = 0; i < n; i++) {
-                const int o = new2old[i];
-                pv_image[i] = D->ip_image[o]; pv_point[i] = D->ip_point[o]; pv_x[i] = D->ip_x[o]; pv_y[i] = D->ip_y[o];
-                pv_vx[i] = D->ip_var_x[o]; pv_vy[i] = D->ip_var_y[o]; pv_rho[i] = D->ip_rho[o];
-                e->ip_old2new[o] = (int32_t)i;
-            }
-            for (int g : blk_list)
-                for (int ip = D->blk_ip_begin[g]; ip < D->blk_ip_begin[g + 1]; ip++) perm_local[ip] = new2old[ip] - D->blk_ip_begin[g];
-            Dperm = *D;
-            Dperm.ip_image = pv_image.data(); Dperm.ip_point = pv_point.data(); Dperm.ip_x = pv_x.data(); Dperm.ip_y = pv_y.data();
-            Dperm.ip_var_x = pv_vx.data(); Dperm.ip_var_y = pv_vy.data(); Dperm.ip_rho = pv_rho.data();
-            D = &Dperm;
-        }
-    }
-    for (int g : blk_list) e->h_blk_images.push_back(D->ip_image[D->blk_ip_begin[g]]);
-    e->n_seg = (int)seg_b.size();
-    e->n_blk_list = (int)blk_list.size();
-    e->n_blk_ip = (int)blk_ip_list.size();
-
-    // ---- upload structure --------------------------------------------------------------------------------------
-    const auto t_phase0 = std::chrono::steady_clock::now();
+// the sizes and decisions of the plan that the engine's other entry points read
+static void adopt_decisions(jaicov_engine *e, const CreatePlan &pl) {
+    const jaicov_problem_desc *D = &pl.D;
+    e->U = pl.U; e->d = pl.d; e->datum_flags = D->datum_flags; e->Upad = pl.Upad;
+    e->n_points = D->n_points; e->n_slots = pl.n_slots;
+    e->all_images = pl.ib == 0 && pl.ie == D->n_images;
+    e->ip0 = pl.ip0; e->ip_count = pl.ip_count;
+    e->max_m = pl.max_m;
+    e->n_seg = (int)pl.seg_b.size();
+    e->n_blk_list = (int)pl.blk_list.size();
+    e->n_blk_ip = (int)pl.blk_ip_list.size();
+    e->pp_plain_ok = pl.plain_ok;
+    e->dm_flops_per_pass = pl.dm_flops_per_pass;
     DevProblem &p = e->p;
-    p.U = U; p.Upad = e->Upad; p.d = d; p.ld = e->Upad;
+    p.U = pl.U; p.Upad = pl.Upad; p.d = pl.d; p.ld = pl.Upad;
     p.n_points = D->n_points; p.n_cameras = D->n_cameras; p.n_images = D->n_images; p.n_dist = D->n_dist;
     p.n_ip = D->n_image_points; p.n_blocks = D->n_image_blocks; p.n_sb = D->n_scale_bars; p.n_dg = D->n_direct_groups;
-    p.n_dg_rows = D->n_direct_rows; p.n_slots = e->n_slots;
-    int rc;
-#define UP(field, src, cnt) if ((rc = upload(e, src, (size_t)(cnt), &p.field)) != JAICOV_OK) return rc
-    UP(point_col, D->point_col, 3 * D->n_points);
-    UP(io_col, D->io_col, 3 * D->n_cameras);
-    UP(cam_dist_begin, D->cam_dist_begin, D->n_cameras + 1);
-    UP(dist_kind, D->dist_kind, D->n_dist);
-    UP(dist_order, D->dist_order, D->n_dist);
-    UP(dist_col, D->dist_col, D->n_dist);
-    UP(image_camera, D->image_camera, D->n_images);
-    UP(eo_col, D->eo_col, 6 * D->n_images);
-    UP(cam_r0, D->cam_r0, D->n_cameras);
-    UP(ip_image, D->ip_image, D->n_image_points);
-    UP(ip_point, D->ip_point, D->n_image_points);
-    UP(ip_x, D->ip_x, D->n_image_points);
-    UP(ip_y, D->ip_y, D->n_image_points);
-    UP(ip_var_x, D->ip_var_x, D->n_image_points);
-    UP(ip_var_y, D->ip_var_y, D->n_image_points);
-    UP(ip_rho, D->ip_rho, D->n_image_points);
-    UP(blk_ip_begin, D->blk_ip_begin, D->n_image_blocks + 1);
-    UP(blk_w_offset, blk_w_off.data(), D->n_image_blocks);
-    UP(sb_a, D->sb_point_a, D->n_scale_bars);
-    UP(sb_b, D->sb_point_b, D->n_scale_bars);
-    UP(sb_len, D->sb_length, D->n_scale_bars);
-    UP(sb_var, D->sb_var, D->n_scale_bars);
-    UP(dg_row_begin, D->dg_row_begin, D->n_direct_groups + 1);
-    UP(dg_slot, D->dg_slot, D->n_direct_rows);
-    UP(dg_obs, D->dg_obs, D->n_direct_rows);
-    UP(dg_var, D->dg_var, D->n_direct_rows);
-    UP(slot_col, e->h_slot_col.data(), e->n_slots);
-#undef UP
-    const int32_t *tmp32; const uint8_t *tmp8;
-    if ((rc = upload(e, seg_b.data(), seg_b.size(), &tmp32))) return rc; e->d_seg_begin = (int32_t *)tmp32;
-    if ((rc = upload(e, seg_e.data(), seg_e.size(), &tmp32))) return rc; e->d_seg_end = (int32_t *)tmp32;
-    if ((rc = upload(e, blk_list.data(), blk_list.size(), &tmp32))) return rc; e->d_blk_list = (int32_t *)tmp32;
-    if ((rc = upload(e, blk_ip_list.data(), blk_ip_list.size(), &tmp32))) return rc; e->d_blk_ip_list = (int32_t *)tmp32;
-    if ((rc = upload(e, in_block.data(), in_block.size(), &tmp8))) return rc; e->d_in_block = (uint8_t *)tmp8;
-    if (!blk_ip_list.empty()) {
-        // point -> block image points (CSR, image order) for the atomics-free point x point gather
-        std::vector<int32_t> cnt(D->n_points + 1, 0), blk_of_ip(D->n_image_points, -1);
-        for (size_t t = 0; t < blk_list.size(); t++)
-            for (int ip = D->blk_ip_begin[blk_list[t]]; ip < D->blk_ip_begin[blk_list[t] + 1]; ip++) blk_of_ip[ip] = blk_list[t];
-        for (int ip : blk_ip_list) cnt[D->ip_point[ip] + 1]++;
-        for (int i = 0; i < D->n_points; i++) cnt[i + 1] += cnt[i];
-        std::vector<int32_t> fill(cnt.begin(), cnt.end() - 1), list(blk_ip_list.size());
-        int cmin = 1 << 30, cmax = -1;
-        for (int ip : blk_ip_list) {
-            const int pt = D->ip_point[ip];
-            list[fill[pt]++] = ip;
-            for (int a = 0; a < 3; a++) {
-                const int c = D->point_col[3 * pt + a];
-                if (c >= 0) { cmin = std::min(cmin, c); cmax = std::max(cmax, c); }
-            }
-        }
-        if (cmax >= cmin) {
-            std::vector<PPRecord> recs(list.size());
-            for (size_t t = 0; t < list.size(); t++) {
-                const int ip = list[t], g = blk_of_ip[ip];
-                PPRecord r{};
-                r.ipb = D->blk_ip_begin[g]; r.mp = D->blk_ip_begin[g + 1] - r.ipb; r.lp = ip - r.ipb; r.poff = blk_w_off[g];
-                recs[t] = r;
-            }
-            std::vector<int32_t> ipcol((size_t)3 * D->n_image_points, -1);
-            for (int ip : blk_ip_list)
-                for (int a = 0; a < 3; a++) ipcol[(size_t)3 * ip + a] = D->point_col[3 * D->ip_point[ip] + a];
-            // per record and column chunk: the range of partner positions (the block is stored in column order)
-            int cw_rt = std::max(64, std::min(PP_CW, 6400)) / 4 * 4;  // 3 * cw doubles of LDS (<= 150 KB), quarters for the DET form
-            // XCD-partitioned block order (assemble.hip): measured no faster (3.24 vs 3.26 ms at 960 columns, slower where the chunks
-            // do not divide evenly over eight XCDs) and FETCH_SIZE fell by 6 % only: the partner records are not what the kernel waits for
-            e->pp.xcd_map = 0;
-            const int NOCOL = 1 << 30;
-            std::vector<int32_t> lo_col(D->n_image_points, NOCOL), hi_col(D->n_image_points, -1);
-            for (int ip : blk_ip_list)
-                for (int a = 0; a < 3; a++) {
-                    const int c = ipcol[(size_t)3 * ip + a];
-                    if (c >= 0) { lo_col[ip] = std::min(lo_col[ip], c); hi_col[ip] = std::max(hi_col[ip], c); }
-                }
-            // The strip width follows the scene: a wave takes the partners of ONE image inside the strip's columns, 64 at a time.  With
-            // random visibility the default width holds 55 +- 7 of an image's 500 points; on a block flown in strips the
-            // points of an image are neighbours in column order and sit in two or three strips, hundreds in each -- eight segments of one
-            // image inside one turn of the deterministic form.  Then the strip is narrowed until an image's partners in a strip are about
-            // one wave again (never below 256 columns: the range table has one entry per image point and strip).
-            {
-                std::vector<int32_t> per_block;                      // columns spanned by the partners of a block, and how many there are
-                double span = 0.0, cnt = 0.0;
-                for (size_t t = 0; t < blk_list.size(); t++) {
-                    const int g = blk_list[t], ipb = D->blk_ip_begin[g], mp = D->blk_ip_begin[g + 1] - ipb;
-                    // distinct default-width strips touched by this block's points
-                    int touched = 0, last = -1;
-                    for (int j = 0; j < mp; j++) {
-                        if (lo_col[ipb + j] == NOCOL) continue;
-                        const int c = (lo_col[ipb + j] - cmin) / cw_rt;
-                        if (c != last) { ++touched; last = c; }
-                    }
-                    if (touched > 0) { span += touched; cnt += mp; }
-                }
-                const double per_strip = span > 0 ? cnt / span : 0.0;   // mean partners of an image per touched strip
-                if (per_strip > 96.0) {
-                    int cw2 = (int)(cw_rt * 56.0 / per_strip) / 64 * 64;
-                    cw_rt = std::max(256, std::min(cw_rt, cw2));
-                }
-            }
-            e->pp.cw = cw_rt;
-            const int n_chunks = (cmax - cmin + cw_rt) / cw_rt;
-            std::vector<int32_t> chunk_lo((size_t)blk_list.size() * n_chunks), chunk_hi((size_t)blk_list.size() * n_chunks);
-            std::vector<int32_t> blk_pos(D->n_image_blocks, -1);
-            for (size_t t = 0; t < blk_list.size(); t++) {
-                const int g = blk_list[t], ipb = D->blk_ip_begin[g], mp = D->blk_ip_begin[g + 1] - ipb;
-                blk_pos[g] = (int)t;
-                for (int j = 1; j < mp; j++)
-                    if (lo_col[ipb + j] < lo_col[ipb + j - 1]) FAIL(e, JAICOV_ERR_DEVICE, "internal: dense block not in column order");
-                for (int c = 0; c < n_chunks; c++) {
-                    const int c0 = cmin + c * cw_rt, c1 = c0 + cw_rt;
-                    int lo = mp, hi = 0;
-                    for (int j = 0; j < mp; j++)
-                        if (hi_col[ipb + j] >= c0 && lo_col[ipb + j] < c1) { lo = std::min(lo, j); hi = j + 1; }
-                    chunk_lo[t * n_chunks + c] = lo; chunk_hi[t * n_chunks + c] = std::max(hi, lo);
-                }
-            }
-            std::vector<int32_t> range((size_t)2 * list.size() * n_chunks);
-            for (size_t o = 0; o < list.size(); o++) {
-                const int ip = list[o], g = blk_of_ip[ip], ipb = D->blk_ip_begin[g], mp = D->blk_ip_begin[g + 1] - ipb;
-                const int t = blk_pos[g];
-                // partners whose first column is <= the largest row column of this point: a prefix of the block
-                const int qend = (int)(std::upper_bound(lo_col.begin() + ipb, lo_col.begin() + ipb + mp, hi_col[ip]) - (lo_col.begin() + ipb));
-                for (int c = 0; c < n_chunks; c++) {
-                    const int lo = chunk_lo[(size_t)t * n_chunks + c], hi = std::min(chunk_hi[(size_t)t * n_chunks + c], qend);
-                    range[2 * (o * n_chunks + c)] = lo;
-                    range[2 * (o * n_chunks + c) + 1] = std::max(hi, lo);
-                }
-            }
-            if ((rc = upload(e, cnt.data(), cnt.size(), &e->pp.pt_ip_begin))) return rc;
-            if ((rc = upload(e, recs.data(), recs.size(), &e->pp.recs))) return rc;
-            {   // the gather reads the columns as three arrays over the image points (coalesced like A_q and U_q)
-                std::vector<int32_t> soa(ipcol.size());
-                const size_t S = (size_t)D->n_image_points;
-                for (size_t ip = 0; ip < S; ip++)
-                    for (int a = 0; a < 3; a++) soa[(size_t)a * S + ip] = ipcol[3 * ip + a];
-                if ((rc = upload(e, soa.data(), soa.size(), &e->pp.ipcol))) return rc;
-            }
-            if ((rc = upload(e, range.data(), range.size(), &e->pp.range))) return rc;
-            e->pp.det = e->deterministic ? 1 : 0;
-            e->pp.cmin = cmin;
-            e->pp.n_chunks = n_chunks;
-            e->pp.cmax = cmax;
-            {   // rows cmin..cmax all point rows?  (points are numbered first and contiguously, BA:667-782)
-                std::vector<char> is_pt(cmax - cmin + 1, 0);
-                for (int i = 0; i < 3 * D->n_points; i++) {
-                    const int c = D->point_col[i];
-                    if (c >= cmin && c <= cmax) is_pt[c - cmin] = 1;
-                }
-                bool all = true;
-                for (char f : is_pt) all = all && f;
-                e->pp_plain_ok = all;
-            }
+    p.n_dg_rows = D->n_direct_rows; p.n_slots = pl.n_slots;
+}
+
+static int upload_structure(jaicov_engine *e, const CreatePlan &pl) {
+    const jaicov_problem_desc *D = &pl.D;
+    DevProblem &p = e->p;
+    TRY(upload(e, D->point_col, (size_t)3 * D->n_points, &p.point_col));
+    TRY(upload(e, D->io_col, (size_t)3 * D->n_cameras, &p.io_col));
+    TRY(upload(e, D->cam_dist_begin, (size_t)D->n_cameras + 1, &p.cam_dist_begin));
+    TRY(upload(e, D->dist_kind, (size_t)D->n_dist, &p.dist_kind));
+    TRY(upload(e, D->dist_order, (size_t)D->n_dist, &p.dist_order));
+    TRY(upload(e, D->dist_col, (size_t)D->n_dist, &p.dist_col));
+    TRY(upload(e, D->image_camera, (size_t)D->n_images, &p.image_camera));
+    TRY(upload(e, D->eo_col, (size_t)6 * D->n_images, &p.eo_col));
+    TRY(upload(e, D->cam_r0, (size_t)D->n_cameras, &p.cam_r0));
+    TRY(upload(e, D->ip_image, (size_t)D->n_image_points, &p.ip_image));
+    TRY(upload(e, D->ip_point, (size_t)D->n_image_points, &p.ip_point));
+    TRY(upload(e, D->ip_x, (size_t)D->n_image_points, &p.ip_x));
+    TRY(upload(e, D->ip_y, (size_t)D->n_image_points, &p.ip_y));
+    TRY(upload(e, D->ip_var_x, (size_t)D->n_image_points, &p.ip_var_x));
+    TRY(upload(e, D->ip_var_y, (size_t)D->n_image_points, &p.ip_var_y));
+    TRY(upload(e, D->ip_rho, (size_t)D->n_image_points, &p.ip_rho));
+    TRY(upload(e, D->blk_ip_begin, (size_t)D->n_image_blocks + 1, &p.blk_ip_begin));
+    TRY(upload(e, pl.blk_w_off.data(), (size_t)D->n_image_blocks, &p.blk_w_offset));
+    TRY(upload(e, D->sb_point_a, (size_t)D->n_scale_bars, &p.sb_a));
+    TRY(upload(e, D->sb_point_b, (size_t)D->n_scale_bars, &p.sb_b));
+    TRY(upload(e, D->sb_length, (size_t)D->n_scale_bars, &p.sb_len));
+    TRY(upload(e, D->sb_var, (size_t)D->n_scale_bars, &p.sb_var));
+    TRY(upload(e, D->dg_row_begin, (size_t)D->n_direct_groups + 1, &p.dg_row_begin));
+    TRY(upload(e, D->dg_slot, (size_t)D->n_direct_rows, &p.dg_slot));
+    TRY(upload(e, D->dg_obs, (size_t)D->n_direct_rows, &p.dg_obs));
+    TRY(upload(e, D->dg_var, (size_t)D->n_direct_rows, &p.dg_var));
+    TRY(upload(e, pl.slot_col.data(), (size_t)pl.n_slots, &p.slot_col));
+    TRY(upload(e, pl.seg_b.data(), pl.seg_b.size(), &e->d_seg_begin));
+    TRY(upload(e, pl.seg_e.data(), pl.seg_e.size(), &e->d_seg_end));
+    TRY(upload(e, pl.blk_list.data(), pl.blk_list.size(), &e->d_blk_list));
+    TRY(upload(e, pl.blk_ip_list.data(), pl.blk_ip_list.size(), &e->d_blk_ip_list));
+    TRY(upload(e, pl.in_block.data(), pl.in_block.size(), &e->d_in_block));
+    if (!pl.gather) return JAICOV_OK;
+    // XCD-partitioned block order (assemble.hip): measured no faster (3.24 vs 3.26 ms at 960 columns, slower where the chunks
+    // do not divide evenly over eight XCDs) and FETCH_SIZE fell by 6 % only: the partner records are not what the kernel waits for
+    e->pp.xcd_map = 0;
+    e->pp.cw = pl.cw;
+    TRY(upload(e, pl.pt_ip_begin.data(), pl.pt_ip_begin.size(), &e->pp.pt_ip_begin));
+    TRY(upload(e, pl.recs.data(), pl.recs.size(), &e->pp.recs));
+    TRY(upload(e, pl.ipcol.data(), pl.ipcol.size(), &e->pp.ipcol));
+    TRY(upload(e, pl.range.data(), pl.range.size(), &e->pp.range));
+    e->pp.det = e->deterministic ? 1 : 0;
+    e->pp.cmin = pl.cmin;
+    e->pp.n_chunks = pl.n_chunks;
+    e->pp.cmax = pl.cmax;
+    return JAICOV_OK;
+}
+
+// diag(D) of every image coordinate in engine order (the variances, or the diagonal of the block's dispersion), then of every
+// directly observed row (dg_var, or the diagonal of the group's dispersion): Q_ll of jaicov_rel_run
+static int upload_ll_diag(jaicov_engine *e, const CreatePlan &pl) {
+    const jaicov_problem_desc *D = &pl.D;
+    std::vector<double> lld(2 * (size_t)D->n_image_points + D->n_direct_rows);
+    for (int ip = 0; ip < D->n_image_points; ip++) { lld[2 * (size_t)ip] = D->ip_var_x[ip]; lld[2 * (size_t)ip + 1] = D->ip_var_y[ip]; }
+    for (int g : pl.blk_list) {
+        if (D->blk_disp_offset[g] < 0) continue;
+        const int b = D->blk_ip_begin[g];
+        const int64_t m = 2 * (int64_t)(D->blk_ip_begin[g + 1] - b);
+        const double *Dg = D->blk_disp + D->blk_disp_offset[g];
+        for (int ip = b; ip < D->blk_ip_begin[g + 1]; ip++) {
+            const int64_t lp = pl.perm_local.empty() ? ip - b : pl.perm_local[ip];
+            for (int c = 0; c < 2; c++) lld[2 * (size_t)ip + c] = Dg[(2 * lp + c) * m + 2 * lp + c];
         }
     }
-
-    e->create_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_phase0).count();
-    // ---- dense dispersions -> D^-1 on the device (DOPG:82-86: dpptrf + dpptri once, cached) -----------------------
-    {
-        double *d_w = nullptr;
-        if ((rc = dalloc(e, (size_t)w_total, &d_w))) return rc;
-        p.blk_w = d_w;
-        std::vector<int64_t> dg_w_off(D->n_direct_groups + 1, -1);
-        int64_t dg_total = 0;
-        int max_dm = 0;
-        if (e->opts.apply_shared)
-            for (int g = 0; g < D->n_direct_groups; g++) {
-                const int m = D->dg_row_begin[g + 1] - D->dg_row_begin[g];
-                if (D->dg_disp_offset && D->dg_disp_offset[g] >= 0 && m > 0) {
-                    dg_w_off[g] = dg_total;
-                    dg_total += (int64_t)m * m;
-                    max_dm = std::max(max_dm, m);
-                }
-            }
-        double *d_dgw = nullptr;
-        if ((rc = dalloc(e, (size_t)dg_total, &d_dgw))) return rc;
-        p.dg_w = d_dgw;
-        if ((rc = upload(e, dg_w_off.data(), (size_t)D->n_direct_groups, &p.dg_w_offset))) return rc;
-        {
-            std::vector<DispItem> items;
-            const int32_t *d_perm_local = nullptr;
-            if (!perm_local.empty() && (rc = upload(e, perm_local.data(), perm_local.size(), &d_perm_local))) return rc;
-            for (int g : blk_list) {
-                const int m = 2 * (D->blk_ip_begin[g + 1] - D->blk_ip_begin[g]);
-                if (D->blk_disp_offset[g] < 0 && blk_w_off[g] < 0) continue;      // compact form: filled below for all image points at once
-                if (D->blk_disp_offset[g] < 0) {      // an ordinary image: inv(D) = diag of 2 x 2 blocks in closed form, engine order (PDF:296-319)
-                    hipLaunchKernelGGL(fill_diag_weight_kernel, dim3(m), dim3(256), 0, e->stream, p.ip_var_x, p.ip_var_y, p.ip_rho,
-                                       D->blk_ip_begin[g], m, d_w + blk_w_off[g]);
-                    continue;
-                }
-                items.push_back(DispItem{D->blk_disp + D->blk_disp_offset[g], d_w + blk_w_off[g], d_perm_local ? d_perm_local + D->blk_ip_begin[g] : nullptr, m});
-            }
-            for (int g = 0; g < D->n_direct_groups; g++) {
-                if (dg_w_off[g] < 0) continue;
-                items.push_back(DispItem{D->dg_disp + D->dg_disp_offset[g], d_dgw + dg_w_off[g], nullptr, D->dg_row_begin[g + 1] - D->dg_row_begin[g]});
-            }
-            (void)max_dm;
-            e->h_perm_local = perm_local;
-            e->h_blk_w_off.assign(blk_w_off.begin(), blk_w_off.end());
-            e->h_blk_ip_begin.assign(D->blk_ip_begin, D->blk_ip_begin + D->n_image_blocks + 1);
-            e->h_blk_mine.assign(D->n_image_blocks, 0);
-            for (int g : blk_list) e->h_blk_mine[g] = 1;
-            if (e->compact_blocks) {
-                double *d_w3 = nullptr;
-                if ((rc = dalloc(e, (size_t)3 * D->n_image_points, &d_w3))) return rc;
-                hipLaunchKernelGGL(fill_ip_w3_kernel, dim3((D->n_image_points + 255) / 256), dim3(256), 0, e->stream, p.ip_var_x, p.ip_var_y, p.ip_rho,
-                                   D->n_image_points, d_w3);
-                p.ip_w3 = d_w3;
-            }
-            if ((rc = invert_dispersions(e, items))) return rc;
-            // diag(D) of every image coordinate in engine order (the variances, or the diagonal of the block's dispersion), then of every
-            // directly observed row (dg_var, or the diagonal of the group's dispersion): Q_ll of jaicov_rel_run
-            std::vector<double> lld(2 * (size_t)D->n_image_points + D->n_direct_rows);
-            for (int ip = 0; ip < D->n_image_points; ip++) { lld[2 * (size_t)ip] = D->ip_var_x[ip]; lld[2 * (size_t)ip + 1] = D->ip_var_y[ip]; }
-            for (int g : blk_list) {
-                if (D->blk_disp_offset[g] < 0) continue;
-                const int b = D->blk_ip_begin[g];
-                const int64_t m = 2 * (int64_t)(D->blk_ip_begin[g + 1] - b);
-                const double *Dg = D->blk_disp + D->blk_disp_offset[g];
-                for (int ip = b; ip < D->blk_ip_begin[g + 1]; ip++) {
-                    const int64_t lp = perm_local.empty() ? ip - b : perm_local[ip];
-                    for (int c = 0; c < 2; c++) lld[2 * (size_t)ip + c] = Dg[(2 * lp + c) * m + 2 * lp + c];
-                }
-            }
-            for (int g = 0; g < D->n_direct_groups; g++) {
-                const int b = D->dg_row_begin[g], m = D->dg_row_begin[g + 1] - b;
-                const bool dense = D->dg_disp_offset && D->dg_disp_offset[g] >= 0;
-                for (int r = 0; r < m; r++)
-                    lld[2 * (size_t)D->n_image_points + b + r] = dense ? D->dg_disp[D->dg_disp_offset[g] + (int64_t)r * m + r] : D->dg_var[b + r];
-            }
-            if ((rc = upload(e, lld.data(), lld.size(), &e->d_ll_diag))) return rc;
-        }
+    for (int g = 0; g < D->n_direct_groups; g++) {
+        const int b = D->dg_row_begin[g], m = D->dg_row_begin[g + 1] - b;
+        const bool dense = D->dg_disp_offset && D->dg_disp_offset[g] >= 0;
+        for (int r = 0; r < m; r++)
+            lld[2 * (size_t)D->n_image_points + b + r] = dense ? D->dg_disp[D->dg_disp_offset[g] + (int64_t)r * m + r] : D->dg_var[b + r];
     }
+    return upload(e, lld.data(), lld.size(), &e->d_ll_diag);
+}
 
-    // ---- work buffers ------------------------------------------------------------------------------------------
-    const auto t_phase1 = std::chrono::steady_clock::now();
-    const size_t sq = (size_t)e->Upad * e->Upad;
-    if ((rc = dalloc(e, (size_t)e->n_slots, &e->d_vals))) return rc;
-    if ((rc = dalloc(e, (size_t)2 * KROW * std::max(1, D->n_image_points), &e->d_rowsA, true))) return rc;
-    if ((rc = dalloc(e, (size_t)2 * std::max(1, D->n_image_points), &e->d_rowsW, true))) return rc;
-    if ((rc = dalloc(e, (size_t)2 * std::max(1, D->n_image_points) * KC_LD, &e->d_T))) return rc;
-    if ((rc = dalloc(e, (size_t)2 * std::max(1, D->n_image_points), &e->d_vbuf))) return rc;
-    if ((rc = dalloc(e, sq + e->Upad, &e->d_N))) return rc;
+// dense dispersions -> D^-1 on the device (DOPG:82-86: dpptrf + dpptri once, cached); closed-form weights of ordinary images
+static int create_weights(jaicov_engine *e, const CreatePlan &pl) {
+    const jaicov_problem_desc *D = &pl.D;
+    DevProblem &p = e->p;
+    double *d_w = nullptr;
+    TRY(dalloc(e, (size_t)pl.w_total, &d_w));
+    p.blk_w = d_w;
+    std::vector<int64_t> dg_w_off(D->n_direct_groups + 1, -1);
+    int64_t dg_total = 0;
+    if (e->opts.apply_shared)
+        for (int g = 0; g < D->n_direct_groups; g++) {
+            const int m = D->dg_row_begin[g + 1] - D->dg_row_begin[g];
+            if (D->dg_disp_offset && D->dg_disp_offset[g] >= 0 && m > 0) {
+                dg_w_off[g] = dg_total;
+                dg_total += (int64_t)m * m;
+            }
+        }
+    double *d_dgw = nullptr;
+    TRY(dalloc(e, (size_t)dg_total, &d_dgw));
+    p.dg_w = d_dgw;
+    TRY(upload(e, dg_w_off.data(), (size_t)D->n_direct_groups, &p.dg_w_offset));
+    std::vector<DispItem> items;
+    const int32_t *d_perm_local = nullptr;
+    TRY(upload(e, pl.perm_local.data(), pl.perm_local.size(), &d_perm_local));
+    for (int g : pl.blk_list) {
+        const int m = 2 * (D->blk_ip_begin[g + 1] - D->blk_ip_begin[g]);
+        if (D->blk_disp_offset[g] < 0 && pl.blk_w_off[g] < 0) continue;      // compact form: filled below for all image points at once
+        if (D->blk_disp_offset[g] < 0) {      // an ordinary image: inv(D) = diag of 2 x 2 blocks in closed form, engine order (PDF:296-319)
+            hipLaunchKernelGGL(fill_diag_weight_kernel, dim3(m), dim3(256), 0, e->stream, p.ip_var_x, p.ip_var_y, p.ip_rho,
+                               D->blk_ip_begin[g], m, d_w + pl.blk_w_off[g]);
+            continue;
+        }
+        items.push_back(DispItem{D->blk_disp + D->blk_disp_offset[g], d_w + pl.blk_w_off[g], d_perm_local ? d_perm_local + D->blk_ip_begin[g] : nullptr, m});
+    }
+    for (int g = 0; g < D->n_direct_groups; g++) {
+        if (dg_w_off[g] < 0) continue;
+        items.push_back(DispItem{D->dg_disp + D->dg_disp_offset[g], d_dgw + dg_w_off[g], nullptr, D->dg_row_begin[g + 1] - D->dg_row_begin[g]});
+    }
+    if (pl.compact_blocks) {
+        double *d_w3 = nullptr;
+        TRY(dalloc(e, (size_t)3 * D->n_image_points, &d_w3));
+        hipLaunchKernelGGL(fill_ip_w3_kernel, dim3((D->n_image_points + 255) / 256), dim3(256), 0, e->stream, p.ip_var_x, p.ip_var_y, p.ip_rho,
+                           D->n_image_points, d_w3);
+        p.ip_w3 = d_w3;
+    }
+    TRY(invert_dispersions(e, items));
+    return upload_ll_diag(e, pl);
+}
+
+static int alloc_work_buffers(jaicov_engine *e, const CreatePlan &pl) {
+    const size_t sq = (size_t)e->Upad * e->Upad, n_ip = (size_t)std::max(1, pl.D.n_image_points);
+    TRY(dalloc(e, (size_t)e->n_slots, &e->d_vals));
+    TRY(dalloc(e, 2 * KROW * n_ip, &e->d_rowsA, true));
+    TRY(dalloc(e, 2 * n_ip, &e->d_rowsW, true));
+    TRY(dalloc(e, 2 * n_ip * KC_LD, &e->d_T));
+    TRY(dalloc(e, 2 * n_ip, &e->d_vbuf));
+    TRY(dalloc(e, sq + e->Upad, &e->d_N));
     e->d_n = e->d_N + sq;
-    if ((rc = dalloc(e, (size_t)e->Upad, &e->d_V))) return rc;
-    if ((rc = dalloc(e, (size_t)8 * e->Upad, &e->d_B, true))) return rc;
-    if ((rc = dalloc(e, (size_t)e->Upad, &e->d_dx, true))) return rc;
-    if ((rc = dalloc(e, (size_t)8 * e->Upad, &e->d_G, true))) return rc;
-    if ((rc = dalloc(e, (size_t)8 * e->Upad, &e->d_Braw, true))) return rc;
-    if ((rc = dalloc(e, (size_t)3 * e->Upad, &e->d_ref, true))) return rc;
-    if ((rc = dalloc(e, (size_t)8 * e->Upad, &e->d_H, true))) return rc;
-    if ((rc = dalloc(e, (size_t)8 * e->Upad, &e->d_F, true))) return rc;
-    if ((rc = dalloc(e, (size_t)64, &e->d_E, true))) return rc;
-    if ((rc = dalloc(e, (size_t)1, &e->d_omega, true))) return rc;
-    if ((rc = dalloc(e, (size_t)std::max(1, e->n_blk_list) * 16 * KC_MAX * (KC_MAX + 1), &e->d_cc_partial))) return rc;
+    TRY(dalloc(e, (size_t)e->Upad, &e->d_V));
+    TRY(dalloc(e, (size_t)8 * e->Upad, &e->d_B, true));
+    TRY(dalloc(e, (size_t)e->Upad, &e->d_dx, true));
+    TRY(dalloc(e, (size_t)8 * e->Upad, &e->d_G, true));
+    TRY(dalloc(e, (size_t)8 * e->Upad, &e->d_Braw, true));
+    TRY(dalloc(e, (size_t)3 * e->Upad, &e->d_ref, true));
+    TRY(dalloc(e, (size_t)8 * e->Upad, &e->d_H, true));
+    TRY(dalloc(e, (size_t)8 * e->Upad, &e->d_F, true));
+    TRY(dalloc(e, (size_t)64, &e->d_E, true));
+    TRY(dalloc(e, (size_t)1, &e->d_omega, true));
+    TRY(dalloc(e, (size_t)std::max(1, e->n_blk_list) * 16 * KC_MAX * (KC_MAX + 1), &e->d_cc_partial));
     HIPE(e, e->solver.init(e->stream, e->Upad, false, true));
-    e->create_ms[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_phase1).count();
-    const auto t_phase2 = std::chrono::steady_clock::now();
-    // ---- EO pre-elimination is possible when every image point sits in an image block, the EO columns are the
-    //      trailing columns e0 + 6*image + k, and no directly observed parameter is an EO parameter ------------------
-    {
-        // Eligibility is a property of the WHOLE problem, not of this engine's image range: every rank of a sharded run must
-        // reach the same decision, or their reduce buffers differ in length (and only some ranks enter the EO exchange).
-        size_t n_in_block = 0;
-        for (int ip = 0; ip < D->n_image_points; ip++) n_in_block += in_block[ip] ? 1 : 0;
-        bool ok = D->n_images > 0 && D->n_image_blocks > 0 && n_in_block == (size_t)D->n_image_points;
-        if ((e->opts.assembly_mode == 1 || e->opts.assembly_mode == 2) && e->n_blk_list > 0) {   // densified MFMA contraction of the image groups (densemode.hip)
-            int max_k1 = 0;
-            for (int g : blk_list) {
-                const int mp = D->blk_ip_begin[g + 1] - D->blk_ip_begin[g], cam = D->image_camera[D->ip_image[D->blk_ip_begin[g]]];
-                const int k1 = 3 * mp + 9 + D->cam_dist_begin[cam + 1] - D->cam_dist_begin[cam] + 1;
-                max_k1 = std::max(max_k1, k1);
-                e->dm_flops_per_pass += 2.0 * (2.0 * mp) * (2.0 * mp) * k1 + (2.0 * mp) * k1 * (k1 + 1.0);
-            }
-            HIPE(e, e->dm.init(e->max_m, max_k1, e->n_blk_list, e->opts.assembly_mode == 2));
-            e->dense_mode = true;
-            ok = false;
-        } else if (e->opts.assembly_mode < 0 || e->opts.assembly_mode > 2)
-            FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "assembly_mode must be 0 (structure-aware), 1 (densified fp64 MFMA contraction) or 2 (the same with fp32 operands and accumulation)");
-        const int e0 = D->n_images > 0 ? D->eo_col[0] : -1;
-        ok = ok && e0 >= d && e0 + 6 * D->n_images == U;
-        for (int i = 0; ok && i < 6 * D->n_images; i++) ok = D->eo_col[i] == e0 + i;
-        const int s_eo = 3 * D->n_points + 3 * D->n_cameras + D->n_dist;
-        for (int r = 0; ok && r < D->n_direct_rows; r++) ok = D->dg_slot[r] < s_eo;
-        for (int g = 0; ok && g < D->n_image_blocks; g++) ok = D->blk_ip_begin[g + 1] - D->blk_ip_begin[g] >= 3;
-        if (ok) {
-            if ((rc = dalloc(e, (size_t)16 * std::max(1, D->n_image_points), &e->sb.U, true))) return rc;
-            if ((rc = dalloc(e, (size_t)12 * std::max(1, D->n_image_points), &e->sb.Ug, true))) return rc;   // U again, in the gather's layout
-            if ((rc = dalloc(e, (size_t)36 * D->n_images, &e->sb.Linv, true))) return rc;
-            if ((rc = dalloc(e, (size_t)6 * SCHUR_GLD * D->n_images, &e->sb.G, true))) return rc;
-            // P' = sigma2 Dinv - U U' is formed inside the point x point gather; a copy in memory (4 GB at config 4) only on request
-            e->sb.materialise = assembly_form() == ASSEMBLY_MATERIALISE ? 1 : 0;     // test hook (JAICOV_ASSEMBLY_FORM, assemble.hip)
-            if (e->sb.materialise && (rc = dalloc(e, (size_t)std::max<int64_t>(w_total_saved, 1), &e->sb.Pp))) return rc;
-            if ((rc = dalloc(e, (size_t)6 * D->n_images, &e->d_xE, true))) return rc;
-            if (e->opts.reduced_reference_quirk && (rc = dalloc(e, (size_t)6 * D->n_images, &e->sb.xq, true))) return rc;
-            if ((rc = dalloc(e, (size_t)1, &e->sb.info, true))) return rc;
-            if ((rc = dalloc(e, (size_t)e->Upad, &e->sb.diagcorr, true))) return rc;
-            e->schur_ok = true;
-            e->e0 = e0;
-            // the solver of the reduced system is created here, with its streams, not at the first solve: stream creation
-            // order matters when the host also runs RCCL (bench.py: communicator after the engine)
-            HIPE(e, e->solverS.init(e->stream, ((e0 + 127) / 128) * 128, false, true, &e->solver));      // never at work beside the full-order solver: shares its side streams
-            e->solverS_ready = true;
-        }
-    }
-    e->create_ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_phase2).count();
+    return JAICOV_OK;
+}
+
+// buffers of the EO pre-elimination (schur.hip) and the solver of the reduced system
+static int init_elimination(jaicov_engine *e, const CreatePlan &pl) {
+    const jaicov_problem_desc *D = &pl.D;
+    const size_t n_ip = (size_t)std::max(1, D->n_image_points);
+    TRY(dalloc(e, 16 * n_ip, &e->sb.U, true));
+    TRY(dalloc(e, 12 * n_ip, &e->sb.Ug, true));   // U again, in the gather's layout
+    TRY(dalloc(e, (size_t)36 * D->n_images, &e->sb.Linv, true));
+    TRY(dalloc(e, (size_t)6 * SCHUR_GLD * D->n_images, &e->sb.G, true));
+    // P' = sigma2 Dinv - U U' is formed inside the point x point gather; a copy in memory (4 GB at config 4) only on request
+    e->sb.materialise = assembly_form() == ASSEMBLY_MATERIALISE ? 1 : 0;     // test hook (JAICOV_ASSEMBLY_FORM, assemble.hip)
+    if (e->sb.materialise) TRY(dalloc(e, (size_t)std::max<int64_t>(pl.w_total, 1), &e->sb.Pp));
+    TRY(dalloc(e, (size_t)6 * D->n_images, &e->d_xE, true));
+    if (e->opts.reduced_reference_quirk) TRY(dalloc(e, (size_t)6 * D->n_images, &e->sb.xq, true));
+    TRY(dalloc(e, (size_t)1, &e->sb.info, true));
+    TRY(dalloc(e, (size_t)e->Upad, &e->sb.diagcorr, true));
+    e->schur_ok = true;
+    e->e0 = pl.e0;
+    // the solver of the reduced system is created here, with its streams, not at the first solve: stream creation
+    // order matters when the host also runs RCCL (bench.py: communicator after the engine)
+    HIPE(e, e->solverS.init(e->stream, ((pl.e0 + 127) / 128) * 128, false, true, &e->solver));      // never at work beside the full-order solver: shares its side streams
+    e->solverS_ready = true;
+    return JAICOV_OK;
+}
+
+// the plan's tables that the engine reads after creation change owner; nothing is copied
+static void keep_host_tables(jaicov_engine *e, CreatePlan &pl) {
+    e->h_slot_col = std::move(pl.slot_col);
+    e->h_point_datum = std::move(pl.point_datum);
+    e->h_caller_block = std::move(pl.caller_block);
+    e->h_blk_images = std::move(pl.blk_images);
+    e->h_perm_local = std::move(pl.perm_local);
+    e->h_blk_w_off = std::move(pl.blk_w_off);
+    e->h_blk_ip_begin = std::move(pl.blk_ip_begin);
+    e->h_blk_mine = std::move(pl.blk_mine);
+    e->ip_old2new = std::move(pl.ip_old2new);
     e->h_vals.assign(e->n_slots, 0.0);
     e->h_V.assign(e->Upad, 1.0);
     e->hB.assign((size_t)8 * e->Upad, 0.0);
+}
+
+static double ms_since(std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+static int create_impl(jaicov_engine *e, const jaicov_problem_desc *desc) {
+    HIPE(e, hipSetDevice(e->device));
+    e->deterministic = e->opts.deterministic >= 0;      // 0 = default = ON since round 4 (costs 0.3 ms per pass at config 4); < 0: arrival-order sums
+    e->refine_steps = e->opts.refinement == 0 ? 1 : (e->opts.refinement < 0 ? 0 : std::min(e->opts.refinement, 4));
+    hipDeviceProp_t prop;
+    HIPE(e, hipGetDeviceProperties(&prop, e->device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        FAIL(e, JAICOV_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    auto t = std::chrono::steady_clock::now();
+    CreatePlan pl;
+    if (!build_create_plan(pl, *desc, e->opts, assembly_form())) FAIL(e, pl.status, pl.err);
+    adopt_decisions(e, pl);
+    TRY(acquire_stream_and_events(e));      // a refused description has created nothing on the device
+    TRY(upload_structure(e, pl));
+    e->create_ms[3] = ms_since(t);
+    TRY(create_weights(e, pl));
+    t = std::chrono::steady_clock::now();
+    TRY(alloc_work_buffers(e, pl));
+    e->create_ms[4] = ms_since(t);
+    t = std::chrono::steady_clock::now();
+    if (pl.dense_mode) {
+        HIPE(e, e->dm.init(pl.max_m, pl.max_k1, e->n_blk_list, e->opts.assembly_mode == 2));
+        e->dense_mode = true;
+    } else if (pl.schur_ok)
+        TRY(init_elimination(e, pl));
+    e->create_ms[5] = ms_since(t);
+    keep_host_tables(e, pl);
     HIPE(e, hipStreamSynchronize(e->stream));
     return JAICOV_OK;
+}
+
+static jaicov_engine_options default_options() {
+    jaicov_engine_options o{};
+    o.image_begin = o.image_end = -1;
+    o.apply_shared = 1;
+    return o;
 }
 
 extern "C" int jaicov_neq_create(const jaicov_problem_desc *desc, const jaicov_engine_options *opts, jaicov_engine **out) {
@@ -1074,19 +789,14 @@ extern "C" int jaicov_neq_create(const jaicov_problem_desc *desc, const jaicov_e
     std::string err;
     int rc = check_device(err);
     if (rc != JAICOV_OK) return rc;
+    if (opts && opts->struct_size != sizeof(jaicov_engine_options)) return JAICOV_ERR_BAD_ARGUMENT;
     jaicov_engine *e = new jaicov_engine();
-    if (opts) {
-        if (opts->struct_size != sizeof(jaicov_engine_options)) { delete e; return JAICOV_ERR_BAD_ARGUMENT; }
-        e->opts = *opts;
-        e->device = opts->device;
-    } else {
-        e->opts.image_begin = e->opts.image_end = -1;
-        e->opts.apply_shared = 1;
-    }
+    e->opts = opts ? *opts : default_options();
+    e->device = e->opts.device;
     *out = e;     // returned even on failure so that the caller can read jaicov_neq_last_error(); destroy() frees it
     const auto t0 = std::chrono::steady_clock::now();
-    rc = create_impl(e, desc, opts);
-    e->create_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    rc = create_impl(e, desc);
+    e->create_ms[0] = ms_since(t0);
     return rc;
 }
 
@@ -1189,7 +899,7 @@ static int datum_rows(jaicov_engine *e, const uint8_t *mask, const double *vals,
     double x0 = 0, y0 = 0, z0 = 0;
     int count = 0;
     for (int pt = 0; pt < e->n_points; pt++) {
-        const int32_t *c = &e->h_point_col[3 * pt];
+        const int32_t *c = &e->h_slot_col[3 * pt];
         if (!mask[pt] || c[0] < 0 || c[1] < 0 || c[2] < 0) continue;
         x0 += vals[3 * pt]; y0 += vals[3 * pt + 1]; z0 += vals[3 * pt + 2];
         count++;
@@ -1205,7 +915,7 @@ static int datum_rows(jaicov_engine *e, const uint8_t *mask, const double *vals,
     double sink = 0.0;
     auto B = [&](int r, int c) -> double & { return c < stride ? hB[(size_t)r * stride + c] : sink; };
     for (int pt = 0; pt < e->n_points; pt++) {
-        const int32_t *c = &e->h_point_col[3 * pt];
+        const int32_t *c = &e->h_slot_col[3 * pt];
         if (!mask[pt] || c[0] < 0 || c[1] < 0 || c[2] < 0) continue;
         const double x = vals[3 * pt] - x0, y = vals[3 * pt + 1] - y0, z = vals[3 * pt + 2] - z0;
         if (tx >= 0) { B(tx, c[0]) = 1.0; norm[tx] += 1.0; }
@@ -2226,6 +1936,38 @@ extern "C" int jaicov_dense_spd_solve_packed(int32_t n, double *ap, double *b, i
 namespace jaicov { hipError_t diag_kernel_bench(int dbg, int iters, float *ms_out); hipError_t mfma_peak_bench(int, int, float *, double *); }
 namespace jaicov { hipError_t cumask_bench(const uint32_t *, int, int, float *, double *); }
 // Per-workgroup timeline of one trailing-update shaped GEMM (C -= A A', K columns): out[8 * tiles]
+// The plan of jaicov_neq_create alone (create_plan.h): no device is looked for and nothing is created on one.  Returns the plan's status,
+// leaves its text in err and its decisions in summary: {blocks of the effective description, synthesized, compact, permuted, n_seg,
+// n_blk_list, n_blk_ip, max_m, w_total (saturated), schur_ok, e0, cw, n_chunks, cmin, cmax, plain_ok}.  tests/test_create_plan.py
+extern "C" int jaicov_debug_create_plan(const jaicov_problem_desc *desc, const jaicov_engine_options *opts, int assembly_form, int32_t *summary,
+                                        int n_summary, char *err, int err_cap) {
+    if (!desc || desc->struct_size != sizeof(jaicov_problem_desc) || (opts && opts->struct_size != sizeof(jaicov_engine_options))) return JAICOV_ERR_BAD_ARGUMENT;
+    CreatePlan pl;
+    build_create_plan(pl, *desc, opts ? *opts : default_options(), assembly_form);
+    if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "%s", pl.err.c_str());
+    const int64_t s[16] = {pl.D.n_image_blocks, pl.synthesized, pl.compact_blocks, !pl.ip_old2new.empty(), (int64_t)pl.seg_b.size(),
+                           (int64_t)pl.blk_list.size(), (int64_t)pl.blk_ip_list.size(), pl.max_m, std::min<int64_t>(pl.w_total, INT32_MAX),
+                           pl.schur_ok, pl.e0, pl.cw, pl.n_chunks, pl.cmin, pl.cmax, pl.plain_ok};
+    for (int i = 0; summary && pl.status == JAICOV_OK && i < n_summary && i < 16; i++) summary[i] = (int32_t)s[i];
+    return pl.status;
+}
+
+// One table of the same plan.  which: 0 ip_old2new, 1 seg_b, 2 seg_e, 3 blk_list, 4 range, 5 the gather's records as (ipb, mp, lp),
+// 6 blk_ip_begin of the effective description.  Returns the number of entries (out == NULL: nothing else), or the plan's status (< 0).
+extern "C" int jaicov_debug_create_plan_table(const jaicov_problem_desc *desc, const jaicov_engine_options *opts, int assembly_form, int which,
+                                              int32_t *out, int cap) {
+    if (!desc || desc->struct_size != sizeof(jaicov_problem_desc) || (opts && opts->struct_size != sizeof(jaicov_engine_options))) return JAICOV_ERR_BAD_ARGUMENT;
+    CreatePlan pl;
+    if (!build_create_plan(pl, *desc, opts ? *opts : default_options(), assembly_form)) return pl.status;
+    std::vector<int32_t> recs;
+    for (const PPRecord &r : pl.recs) recs.insert(recs.end(), {r.ipb, r.mp, r.lp});
+    const std::vector<int32_t> *tables[7] = {&pl.ip_old2new, &pl.seg_b, &pl.seg_e, &pl.blk_list, &pl.range, &recs, &pl.blk_ip_begin};
+    if (which < 0 || which >= 7) return JAICOV_ERR_BAD_ARGUMENT;
+    const std::vector<int32_t> &t = *tables[which];
+    if (out) std::copy(t.begin(), t.begin() + std::min<size_t>(t.size(), (size_t)std::max(cap, 0)), out);
+    return (int)t.size();
+}
+
 extern "C" int jaicov_debug_gemm_trace(int M, int K, int lower_only, long long *out) {
     std::string err;
     if (check_device(err)) return JAICOV_ERR_NO_DEVICE;

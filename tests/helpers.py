@@ -1,9 +1,11 @@
 """Shared test helpers (host side only)."""
+import dataclasses
 import json
 import os
 
 import numpy as np
 
+from bundle_adjustment_amd import scene
 from bundle_adjustment_amd.problem import FlatProblem
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -44,3 +46,49 @@ def problem_from_cases(dist, cases, sigma=5e-4, rho=0.0):
 def rel_err(a, b):
     a = np.asarray(a, float); b = np.asarray(b, float)
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
+
+
+# ---- malformed problems (test_gpu_errors.py through jaicov_neq_create, test_create_plan.py through the plan alone) ----
+def base_scene():
+    return scene.make_scene(6, 40, 24, dist=scene.DIST_FULL, weights="block", n_control=4)
+
+
+def corrupt(fp, what):
+    """One malformed field per case; everything else stays the valid scene."""
+    r = dataclasses.replace
+    if what == "datum_flags":
+        return r(fp, datum_flags=fp.datum_flags | 1), "datum_flags"                      # one flag, rank_defect 0
+    if what == "dist_order_of_kinds":
+        k = fp.dist_kind.copy(); k[[4, 5]] = k[[5, 4]]                                   # ... Bi, Ai -> Ai, Bi
+        return r(fp, dist_kind=k), "Type order"
+    if what == "unknown_kind":
+        k = fp.dist_kind.copy(); k[-1] = 10
+        return r(fp, dist_kind=k), "unknown distortion coefficient kind"
+    if what == "zernike_order_0":
+        k = fp.dist_kind.copy(); o = fp.dist_order.copy(); k[-1] = 9; o[-1] = 0
+        return r(fp, dist_kind=k, dist_order=o), "1..119"
+    if what == "zernike_order_120":
+        k = fp.dist_kind.copy(); o = fp.dist_order.copy(); k[-1] = 7; o[-1] = 120
+        return r(fp, dist_kind=k, dist_order=o), "1..119"
+    if what == "not_image_major":
+        im = fp.ip_image.copy(); im[0], im[-1] = im[-1], im[0]
+        return r(fp, ip_image=im), "image-major"
+    if what == "duplicate_column":
+        pc = fp.point_col.copy(); free = np.argwhere(pc >= 0)
+        pc[tuple(free[0])] = pc[tuple(free[1])]
+        return r(fp, point_col=pc), "permutation"
+    if what == "column_out_of_range":
+        pc = fp.point_col.copy(); free = np.argwhere(pc >= 0)
+        pc[tuple(free[0])] = fp.n_unknowns
+        return r(fp, point_col=pc), "permutation"
+    if what == "block_spans_images":
+        b = fp.blk_ip_begin.copy(); b[1] += 1                                            # block 0 takes the first point of image 1
+        return r(fp, blk_ip_begin=b), "span"
+    if what == "blocks_descending":
+        b = fp.blk_ip_begin.copy(); b[2] = b[1] - 1
+        return r(fp, blk_ip_begin=b), "ascending"
+    if what == "too_many_coefficients":
+        n = 21                                                                           # JAICOV_MAX_DIST_PER_CAMERA = 20
+        return r(fp, cam_dist_begin=np.array([0, n], np.int32), dist_kind=np.full(n, 5, np.int32), dist_order=np.arange(1, n + 1, dtype=np.int32),
+                 dist_col=np.full(n, -1, np.int32)), "too many"
+    raise KeyError(what)

@@ -9,54 +9,10 @@ import dataclasses
 import numpy as np
 import pytest
 
-from bundle_adjustment_amd import engine, scene
+from bundle_adjustment_amd import engine
+from helpers import base_scene, corrupt
 
 pytestmark = pytest.mark.gpu
-
-
-def base_scene():
-    return scene.make_scene(6, 40, 24, dist=scene.DIST_FULL, weights="block", n_control=4)
-
-
-def corrupt(fp, what):
-    """One malformed field per case; everything else stays the valid scene."""
-    r = dataclasses.replace
-    if what == "datum_flags":
-        return r(fp, datum_flags=fp.datum_flags | 1), "datum_flags"                      # one flag, rank_defect 0
-    if what == "dist_order_of_kinds":
-        k = fp.dist_kind.copy(); k[[4, 5]] = k[[5, 4]]                                   # ... Bi, Ai -> Ai, Bi
-        return r(fp, dist_kind=k), "Type order"
-    if what == "unknown_kind":
-        k = fp.dist_kind.copy(); k[-1] = 10
-        return r(fp, dist_kind=k), "unknown distortion coefficient kind"
-    if what == "zernike_order_0":
-        k = fp.dist_kind.copy(); o = fp.dist_order.copy(); k[-1] = 9; o[-1] = 0
-        return r(fp, dist_kind=k, dist_order=o), "1..119"
-    if what == "zernike_order_120":
-        k = fp.dist_kind.copy(); o = fp.dist_order.copy(); k[-1] = 7; o[-1] = 120
-        return r(fp, dist_kind=k, dist_order=o), "1..119"
-    if what == "not_image_major":
-        im = fp.ip_image.copy(); im[0], im[-1] = im[-1], im[0]
-        return r(fp, ip_image=im), "image-major"
-    if what == "duplicate_column":
-        pc = fp.point_col.copy(); free = np.argwhere(pc >= 0)
-        pc[tuple(free[0])] = pc[tuple(free[1])]
-        return r(fp, point_col=pc), "permutation"
-    if what == "column_out_of_range":
-        pc = fp.point_col.copy(); free = np.argwhere(pc >= 0)
-        pc[tuple(free[0])] = fp.n_unknowns
-        return r(fp, point_col=pc), "permutation"
-    if what == "block_spans_images":
-        b = fp.blk_ip_begin.copy(); b[1] += 1                                            # block 0 takes the first point of image 1
-        return r(fp, blk_ip_begin=b), "span"
-    if what == "blocks_descending":
-        b = fp.blk_ip_begin.copy(); b[2] = b[1] - 1
-        return r(fp, blk_ip_begin=b), "ascending"
-    if what == "too_many_coefficients":
-        n = 21                                                                           # JAICOV_MAX_DIST_PER_CAMERA = 20
-        return r(fp, cam_dist_begin=np.array([0, n], np.int32), dist_kind=np.full(n, 5, np.int32), dist_order=np.arange(1, n + 1, dtype=np.int32),
-                 dist_col=np.full(n, -1, np.int32)), "too many"
-    raise KeyError(what)
 
 
 @pytest.mark.parametrize("what", ["datum_flags", "dist_order_of_kinds", "unknown_kind", "zernike_order_0", "zernike_order_120", "not_image_major",
@@ -77,6 +33,21 @@ def test_create_rejects_a_bad_image_range(rng):
     with pytest.raises(engine.EngineError) as ei:
         engine.Engine(fp, image_range=rng)
     assert ei.value.code == -1 and "image range" in str(ei.value)
+
+
+def test_create_rejects_an_image_index_out_of_range_on_every_path():
+    """Checked for every description, not only where ordinary images may be served as blocks."""
+    fp = base_scene()
+    im = fp.ip_image.copy(); im[-1] = fp.n_images
+    with pytest.raises(engine.EngineError) as ei:
+        engine.Engine(dataclasses.replace(fp, ip_image=im), ordinary_group_elimination=-1)
+    assert ei.value.code == -1 and "image index out of range" in str(ei.value)
+
+
+def test_create_rejects_an_unknown_assembly_mode():
+    with pytest.raises(engine.EngineError) as ei:
+        engine.Engine(base_scene(), assembly_mode=3)
+    assert ei.value.code == -1 and "assembly_mode must be" in str(ei.value)
 
 
 def test_call_order_is_enforced():

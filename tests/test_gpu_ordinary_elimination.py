@@ -300,7 +300,7 @@ def test_the_largest_ordinary_image_that_is_served_as_a_block(per_image, elimina
 
 
 def test_default_eliminates_ordinary_images_only_where_it_saves_block_columns():
-    """Round 5's size rule (engine.hip, create): the default serves ordinary images as blocks when the 6 I exterior-orientation columns are
+    """Round 5's size rule (create_plan.h, synthesize_blocks): the default serves ordinary images as blocks when the 6 I exterior-orientation columns are
     at least two 128-column blocks of the factorisation.  BASELINE config 2 (order 726 -> 606: six block columns -> five) stays at full
     order -- its pass is 0.79 ms that way against 0.86 --, config 3 (3 614 -> 3 014: 29 -> 24) is eliminated, as is a block the size of
     the bundled example (115 images: ten block columns -> four)."""
