@@ -1,5 +1,6 @@
 // Dataflow Cholesky: the whole factorisation L L' = M (plus the right-hand-side rows below M) as TWO concurrent launches
-// (from 24 block columns on; dense.hip's stream-scheduled potrf_streams() below that).
+// (from 12 block columns on; dense.hip's stream-scheduled potrf_streams() below that).  The host side -- the choice of the form, the
+// layout of the flag words, the owner of the buffers -- is declared in cholflow.h.
 // Replaces the arithmetic of dpptrf / the factorisation half of dspsv (MathExtension.java:248,348) like dense.hip's
 // stream-scheduled potrf(), with the dependencies carried by flags in memory instead of streams, events and launches.
 //
@@ -15,7 +16,7 @@
 //                       keeps the critical chain potrf(c) -> L[c+1][c] -> diagonal tile (c+1, c+1) -> potrf(c+1) inside one
 //                       CU (LDS + accumulators, no trip through memory and flags between the links); workgroup 1 inverts
 //                       the factors.  The tile kernel hands the two tiles over as partial visits (`applied` flags).
-//   potrf_diag_chain_kernel   the first companion (JAICOV_FLOW_CHAIN=0): ONE workgroup: for c = 0, 1, ...: waits for the
+//   potrf_diag_chain_kernel   the first companion (JAICOV_FACTOR_FORM=two_step): ONE workgroup: for c = 0, 1, ...: waits for the
 //                       updated diagonal tile c, factors and inverts it (potrf_diag.h), publishes L_cc and inv(L_cc).
 //   chol_tile_kernel<.., true>   the one-kernel form for hosts on which two kernels cannot run side by side.
 //
@@ -62,8 +63,6 @@ namespace jaicov {
         if (_e != hipSuccess) return _e;           \
     } while (0)
 
-// control words
-enum { FLOW_TICKET = 0, FLOW_ABORT = 1, FLOW_DIAG_NEXT = 2, FLOW_CHAIN_AT = 3, FLOW_STALE = 4, FLOW_STALE_CONFIRMED = 5, FLOW_RESCUED = 6, FLOW_WG_OFF = 7, FLOW_CTRL_WORDS = 16 };   // RESCUED: hits of the read-modify-write poll after > 1 ms of waiting   // CHAIN_AT: column << 4 | stage of the chain workgroup
 constexpr int FLOW_FIN = 1 << 20;        // task.w = k1 | FLOW_FIN: finish the tile after the updates
 // Split update ranges (the late block columns' tiles: each has ~100 block-column steps to do one after the other, is drawn late -- tickets go
 // out in column order -- and the chip drains while the last of them crawl through their ranges).  task.w | FLOW_PART: a PARTIAL-SUM task: zeros
@@ -90,7 +89,7 @@ struct FlowArgs {
     int *diag_ready;         // [nb] the updated diagonal tile is in memory
     int *factored;           // [nb] chain form: L_cc is in memory (the inverse follows, done[c][c])
     int *info;               // first failing pivot (dense.h)
-    int *alive;              // host-visible words: workgroup b of the diagonal / chain kernel stores `seq` into alive[b] when it starts (potrf_flow's handshake)
+    int *alive;              // host-visible words: workgroup b of the diagonal / chain kernel stores `seq` into alive[b] when it starts (FlowFactor::factor's handshake)
     int seq;
     // optional: the matrix is not in L yet but is M = V N V + Bh' Bh (identity on the d border rows and on the padding) of a
     // source square N (NES.applyPrecondition, NES:82-91, fused into the first load of every tile; engine.hip scale_copy_kernel)
@@ -112,7 +111,7 @@ struct FlowArgs {
     int second_update;       // chain form: workgroup 2 also subtracts its tile from tile (c+2, c+1)
     int inv_wt;              // chain form: the inverses leave write-through (1) or plainly behind a release (0)
     int crit_span;           // ... which are the tiles (i, j) with i <= j + crit_span
-    int *wgstate;            // [grid] where each workgroup is: ticket << 12 | k << 4 | stage (flow_report_stall reads it after a stall)
+    int *wgstate;            // [grid] where each workgroup is: ticket << 12 | k << 4 | stage (FlowFactor::report_stall reads it after a stall)
     long long *ctrace;       // optional [nb][8], chain kernel: potrf start, factor done, operands there, solve done, update done (wall clock)
     long long *trace;        // optional [n_tasks][8]: start, C loaded, updates done, end (wall clock), ticks spent waiting, cycles, block, HW_ID | XCC_ID << 32
 };
@@ -148,11 +147,11 @@ __device__ __forceinline__ void drain_stores() { asm volatile("s_waitcnt vmcnt(0
 #define FLOW_OPAQUE_TID(name) int name = tid; asm volatile("" : "+v"(name))
 
 // The lane whose wait runs out: set the abort word and, if it is the first, copy every workgroup's state word next to it (what the
-// others were doing at THAT moment; flow_report_stall prints it beside what they had reached when the kernel ended).
+// others were doing at THAT moment; FlowFactor::report_stall prints it beside what they had reached when the kernel ended).
 __device__ __forceinline__ void flow_give_up(int *ctrl) {
     if (atomicCAS(ctrl + FLOW_ABORT, 0, 2) == 0) {
         int *wg = ctrl + ctrl[FLOW_WG_OFF];
-        for (int b = 0; b < 1024; b++) wg[1024 + b] = flow_ld(wg + b);
+        for (int b = 0; b < FLOW_MAX_GRID; b++) wg[FLOW_MAX_GRID + b] = flow_ld(wg + b);
     }
 }
 
@@ -903,7 +902,7 @@ __global__ __launch_bounds__(256) void potrf_chain_kernel(FlowArgs g) {
     __shared__ double Wd[8 * 16 * WDP];
     __shared__ int s_ok;
     const int tid = threadIdx.x;
-    if (tid == 0) {      // where this workgroup runs: HW_ID, XCC_ID + 1 (the tile kernel and flow_report_stall read them) ...
+    if (tid == 0) {      // where this workgroup runs: HW_ID, XCC_ID + 1 (the tile kernel and FlowFactor::report_stall read them) ...
         flow_st(g.ctrl + 8 + 2 * blockIdx.x, (int)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)));
         flow_st(g.ctrl + 9 + 2 * blockIdx.x, 1 + (int)(__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) & 0xf));
         drain_stores();
@@ -960,22 +959,90 @@ __global__ __launch_bounds__(256) void potrf_chain_kernel(FlowArgs g) {
     }
 }
 
-// Which tasks get their update range split (flow_schedule).  Round 5.  Tickets go out in column order, so the tiles of the late block columns --
-// each with ~100 block-column steps to do one after the other, 3+ ms -- are drawn last; the chip drained while they crawled through their
-// ranges (mean resident tasks in the last two tenths of the span: 417 and 138 of 496), and the chain waited for exactly those tiles.  Cutting
-// the range in two, the first half as an independent partial-sum task at the head of the column (its operands are final long before: it never
-// waits, 30.2 us per step), halves the serial length of every late task.  Measured (ms per factorisation, without / with, same box):
-// 80 block columns 8.33 / 8.18, 100: 14.4 / 13.8, 118: 22.5 / 21.4, 142: 36.7 / 35.5; 64: 5.20 / 5.40, 40: 2.63 / 2.80 (the partial sums' extra
-// store + load and the later start of the column's own tasks cost more than the shorter tail saves).  At 118 block columns the first split
-// column anywhere in 40 .. 72 gives the same time (21.35-21.45), 88: 21.8; three pieces 22.3, four 23.3 (worse than none: the tile's own task
-// then spends most of its life waiting for operand columns, holding a slot).  JAICOV_FLOW_SPLIT="m:from" is a test hook.
-void flow_split_rule(int nb, int *m, int *from) {
-    *m = 1; *from = 1 << 30;
-    if (nb >= 80) { *m = 2; *from = nb / 2; }
+// The only reader of the environment in the solver (cholflow.h says when each hook takes effect).
+FlowHooks flow_hooks() {
+    FlowHooks h;
+    if (const char *e = getenv("JAICOV_FACTOR_FORM")) {
+        if (!strcmp(e, "streams")) h.form = FACTOR_STREAMS;
+        else if (!strcmp(e, "two_step")) h.form = FACTOR_TWO_STEP;
+        else if (!strcmp(e, "one_kernel")) h.form = FACTOR_ONE_KERNEL;
+        else if (!strcmp(e, "chain2")) h.form = FACTOR_CHAIN2;          // the chain form with two chain workgroups (no third one for the second subdiagonal)
+        else if (!strcmp(e, "chain3")) h.form = FACTOR_CHAIN3;          // ... with three, whatever the order (default: below 80 block columns)
+    }
+    if (const char *e = getenv("JAICOV_FLOW_MIN_BLOCKS")) h.min_blocks = atoi(e);
     if (const char *e = getenv("JAICOV_FLOW_SPLIT")) {
         int a = 1, b = 0;
-        if (sscanf(e, "%d:%d", &a, &b) >= 1) { *m = a < 1 ? 1 : a; *from = b; }
+        if (sscanf(e, "%d:%d", &a, &b) >= 1) { h.split_m = a < 1 ? 1 : a; h.split_from = b; }
     }
+    if (const char *e = getenv("JAICOV_FLOW_TIMEOUT_MS")) h.timeout_ms = atoi(e);
+    h.trace_on = getenv("JAICOV_FLOW_TRACE_ON") != nullptr;
+    if (const char *e = getenv("JAICOV_CHAIN8_MIN_NB")) h.chain8_min_nb = atoi(e);
+    h.chain_trace = getenv("JAICOV_CHAIN_TRACE") != nullptr;
+    h.verbose = getenv("JAICOV_VERBOSE") != nullptr;
+    return h;
+}
+
+// The polling-wave chains pay two batched GEMM launches per factorisation (~0.1 ms) for ~1.2 us per link and chain: from this many
+// block columns on (config 2, 6 block columns: 0.085 -> 0.14 ms per pass with them; config 3, 29: 0.28 -> 0.27)
+int chain8_min_blocks(const FlowHooks &h) { return h.chain8_min_nb != HOOK_UNSET ? h.chain8_min_nb : 24; }
+
+// Which factorisation a solver of nb block columns uses, and in which form.
+FlowDecision flow_decide(int nb, bool kernels_overlap, const FlowHooks &h) {
+    FlowDecision dec{};
+    // Dataflow or stream-scheduled: both are bound by a chain of one link per block column while the order is small (dataflow: the
+    // chain workgroup's potrf -> solve -> update, ~80-95 us; streams: diagonal kernel + two dependent launches, ~80 us), the
+    // dataflow form then pays its start-up (two launches, a host handshake, ~0.15 ms).  Measured on MI355X
+    // (scripts/flow_trace.py, ms per factorisation dataflow / streams): order 1024 0.76 / 0.62, 2048 1.32 / 1.28,
+    // 3072 1.94 / 2.00, 3712 2.37 / 2.50, 5120 3.33 / 3.75, 6144 4.07 / 4.78, 8192 5.95 / 7.92, 15104 22.3 / 26.3
+    // -> from 24 block columns on (rounds 2 and 3).  Round 4 (diagonal block 41 -> 27 us, third chain workgroup below 48 block columns):
+    // order 640 0.43 / 0.39, 1024 0.65 / 0.59, 1152 0.70 / 0.69, 1280 0.75 / 0.77, 1408 0.82 / 0.83, 1536 0.82 / 0.92, 2048 1.10 / 1.25,
+    // 2560 1.32 / 1.59, 3072 1.55 / 1.94 -> from 12 block columns on.
+    dec.use_flow = h.form != FACTOR_STREAMS && nb >= (h.min_blocks != HOOK_UNSET ? h.min_blocks : 12);
+    if (dec.use_flow) {
+        // chain form unless kernels cannot run side by side (one-kernel form, diagonal blocks inline; JAICOV_FACTOR_FORM=one_kernel forces
+        // it) or it is switched off
+        dec.one_kernel = !kernels_overlap || h.form == FACTOR_ONE_KERNEL;
+        dec.chain = !dec.one_kernel && h.form != FACTOR_TWO_STEP;
+        // Third chain workgroup for the second subdiagonal: it finishes tile (c+2, c) by the chain's own forward substitution (from L_cc
+        // itself: no wait for the inverse workgroup) and subtracts it from tile (c+2, c+1), the tile the chain workgroup needs next.
+        // Rounds 2 and 3 measured it flat (22.4 +- 0.3 ms at order 15 104) and round 4's prune removed it -- for a day: once potrf of the
+        // 128-block had fallen from 41 to 27 us (potrf_diag.h) the chain workgroup's own cycle (59 us) was no longer the one that
+        // binds at small orders; the path potrf(c-1) -> inverse -> product with the inverse -> last update of tile (c+1, c) was (the chain
+        // waited 6-9 us per block column for that tile at order 3 072), and that is the path this workgroup shortens: order 3 072
+        // 1.70 -> 1.58 ms.  At order 8 192 it is neutral (5.3 vs 5.4 ms) and at 15 104 it changes nothing (22.7 vs 22.8 ms: the tiles it
+        // needs are late by the same path one diagonal further out, and the row chain of the tile kernel binds).  Crossover measured at the end of
+        // round 4 (ms, two / three chain workgroups): 40 block columns 2.88 / 2.65, 48: 3.60 / 3.39, 56: 4.42 / 4.20, 64: 5.36 / 5.21, 72: 6.65 / 6.53,
+        // 80: 8.25 / 8.21, 118: 22.3 / 22.7 -> used below 80 block columns.  JAICOV_FACTOR_FORM=chain2 / chain3 (test hooks): the chain form with two / three workgroups at any order.
+        dec.second = dec.chain && h.form != FACTOR_CHAIN2 && (nb < 80 || h.form == FACTOR_CHAIN3) ? 2 : 0;
+    }
+    // Which tasks get their update range split (flow_schedule).  Round 5.  Tickets go out in column order, so the tiles of the late block columns --
+    // each with ~100 block-column steps to do one after the other, 3+ ms -- are drawn last; the chip drained while they crawled through their
+    // ranges (mean resident tasks in the last two tenths of the span: 417 and 138 of 496), and the chain waited for exactly those tiles.  Cutting
+    // the range in two, the first half as an independent partial-sum task at the head of the column (its operands are final long before: it never
+    // waits, 30.2 us per step), halves the serial length of every late task.  Measured (ms per factorisation, without / with, same box):
+    // 80 block columns 8.33 / 8.18, 100: 14.4 / 13.8, 118: 22.5 / 21.4, 142: 36.7 / 35.5; 64: 5.20 / 5.40, 40: 2.63 / 2.80 (the partial sums' extra
+    // store + load and the later start of the column's own tasks cost more than the shorter tail saves).  At 118 block columns the first split
+    // column anywhere in 40 .. 72 gives the same time (21.35-21.45), 88: 21.8; three pieces 22.3, four 23.3 (worse than none: the tile's own task
+    // then spends most of its life waiting for operand columns, holding a slot).  JAICOV_FLOW_SPLIT="m:from" is a test hook.
+    dec.split_m = 1; dec.split_from = 1 << 30;
+    if (nb >= 80) { dec.split_m = 2; dec.split_from = nb / 2; }
+    if (h.split_m > 0) { dec.split_m = h.split_m; dec.split_from = h.split_from; }
+    return dec;
+}
+
+// The flag words: control words, done / applied flags, diag_ready, factored, one state word per workgroup and room for their copy at the
+// moment a wait runs out, one flag per partial-sum buffer.
+FlowLayout flow_layout(int nb, int row_blocks, int partials) {
+    FlowLayout l{};
+    l.done = FLOW_CTRL_WORDS;
+    l.applied = l.done + (size_t)row_blocks * nb;
+    l.diag_ready = l.applied + (size_t)row_blocks * nb;
+    l.factored = l.diag_ready + nb;
+    l.wgstate = l.factored + nb;
+    l.wgsnap = l.wgstate + FLOW_MAX_GRID;
+    l.pflag = l.wgsnap + FLOW_MAX_GRID;
+    l.words = l.pflag + (size_t)partials;
+    return l;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1051,7 +1118,23 @@ extern "C" int jaicov_debug_flow_tasks(int nb, int row_blocks, int w, int chain,
     return jaicov_debug_flow_tasks2(nb, row_blocks, w, chain, second, 1, 1 << 30, out, cap);
 }
 // the split the solver uses for nb block columns: *m pieces for the tasks of the block columns >= *from (m = 1: none)
-extern "C" void jaicov_debug_flow_split(int nb, int *m, int *from) { jaicov::flow_split_rule(nb, m, from); }
+extern "C" void jaicov_debug_flow_split(int nb, int *m, int *from) {
+    const jaicov::FlowDecision dec = jaicov::flow_decide(nb, true, jaicov::flow_hooks());
+    *m = dec.split_m; *from = dec.split_from;
+}
+// the decision for nb block columns under the hooks of the environment: {use_flow, one_kernel, chain, second, split_m, split_from}
+extern "C" void jaicov_debug_flow_decision(int nb, int kernels_overlap, int *out6) {
+    const jaicov::FlowDecision dec = jaicov::flow_decide(nb, kernels_overlap != 0, jaicov::flow_hooks());
+    out6[0] = dec.use_flow; out6[1] = dec.one_kernel; out6[2] = dec.chain; out6[3] = dec.second; out6[4] = dec.split_m; out6[5] = dec.split_from;
+}
+// where the flag words lie: {done, applied, diag_ready, factored, state words, their snapshot, partial-sum flags, total}; returns FLOW_MAX_GRID
+extern "C" int jaicov_debug_flow_layout(int nb, int row_blocks, int partials, long long *out8) {
+    if (nb < 1 || row_blocks < nb || partials < 0) return -1;
+    const jaicov::FlowLayout l = jaicov::flow_layout(nb, row_blocks, partials);
+    const size_t w[8] = {l.done, l.applied, l.diag_ready, l.factored, l.wgstate, l.wgsnap, l.pflag, l.words};
+    for (int i = 0; i < 8; i++) out8[i] = (long long)w[i];
+    return jaicov::FLOW_MAX_GRID;
+}
 namespace jaicov {
 
 // Can two kernels of this process run at the same time?  Probed once: a kernel that waits (at most 50 ms) for a word that a
@@ -1068,29 +1151,30 @@ __global__ void flow_probe_wait_kernel(int *word, int *result) {
 }
 __global__ void flow_probe_set_kernel(int *word) { __hip_atomic_store(word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-bool DenseSolver::flow_kernels_overlap() {
+static bool flow_kernels_overlap(hipStream_t dstream) {
     static int cached = -1;
-    if (factor_form() == FACTOR_ONE_KERNEL) return false;                 // JAICOV_FACTOR_FORM=one_kernel: force the one-kernel form
+    static std::mutex cache_mutex;                      // engines may be created from several host threads (as flow_measure_residency)
+    std::lock_guard<std::mutex> lock(cache_mutex);
     if (cached >= 0) return cached != 0;
-    int *d = nullptr, h[2] = {0, 0};
+    DevBuf<int> d;
+    int h[2] = {0, 0};
     hipStream_t s2 = nullptr;
-    bool ok = hipMalloc(&d, 2 * sizeof(int)) == hipSuccess && hipMemset(d, 0, 2 * sizeof(int)) == hipSuccess &&
+    bool ok = d.reserve(2) == hipSuccess && hipMemset(d.get(), 0, 2 * sizeof(int)) == hipSuccess &&
               hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
     if (ok) {
-        hipLaunchKernelGGL(flow_probe_wait_kernel, dim3(1), dim3(1), 0, dstream, d, d + 1);
-        hipLaunchKernelGGL(flow_probe_set_kernel, dim3(1), dim3(1), 0, s2, d);
+        hipLaunchKernelGGL(flow_probe_wait_kernel, dim3(1), dim3(1), 0, dstream, d.get(), d.get() + 1);
+        hipLaunchKernelGGL(flow_probe_set_kernel, dim3(1), dim3(1), 0, s2, d.get());
         ok = hipStreamSynchronize(dstream) == hipSuccess && hipStreamSynchronize(s2) == hipSuccess &&
-             hipMemcpy(h, d, 2 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+             hipMemcpy(h, d.get(), 2 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
     }
     if (s2) hipStreamDestroy(s2);
-    if (d) hipFree(d);
     cached = ok && h[1] == 1 ? 1 : 0;
-    if (!cached && getenv("JAICOV_VERBOSE")) fprintf(stderr, "jaicov: kernels do not overlap on this host: dataflow factorisation runs as one kernel with inline diagonal blocks\n");
+    if (!cached && flow_hooks().verbose) fprintf(stderr, "jaicov: kernels do not overlap on this host: dataflow factorisation runs as one kernel with inline diagonal blocks\n");
     return cached != 0;
 }
 
 // ---- residency of the tile kernel beside the chain workgroups, MEASURED (round 5) -----------------------------------------------------
-// The `keep` rule of potrf_flow (the last workgroups dealt to an XCD that hosts a chain workgroup leave without a ticket, so that the ones
+// The `keep` rule of FlowFactor::factor (the last workgroups dealt to an XCD that hosts a chain workgroup leave without a ticket, so that the ones
 // queued behind its full shader engine get in and leave too) used to assume the MI355X's shape: 8 XCDs x 4 shader engines, 64 blocks dealt
 // per XCD, "the last eight".  It is now derived from what a launch of the tile kernel's footprint actually does next to stand-ins of the
 // chain workgroups: XCDs seen, shader engines per XCD, blocks dealt to an XCD, and how many of them stay QUEUED on an XCD whose reserved CU
@@ -1135,10 +1219,12 @@ static FlowResidency flow_measure_residency(hipStream_t stream, hipStream_t dstr
     for (auto &c : cache)
         if (c.first == std::make_pair(grid, chain_wgs)) return c.second;
     FlowResidency r;
-    int *host = nullptr, *counts = nullptr;
+    HostMapped<int> host_words;
+    DevBuf<int> count_words;
     int h[192] = {0};
-    bool ok = hipHostMalloc((void **)&host, 8 * sizeof(int), hipHostMallocMapped) == hipSuccess && hipMalloc(&counts, 192 * sizeof(int)) == hipSuccess &&
-              hipMemset(counts, 0, 192 * sizeof(int)) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    bool ok = host_words.alloc(8) == hipSuccess && count_words.reserve(192) == hipSuccess &&
+              hipMemset(count_words.get(), 0, 192 * sizeof(int)) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    int *const host = host_words.get(), *const counts = count_words.get();
     if (ok) {
         for (int i = 0; i < 8; i++) host[i] = 0;
         hipLaunchKernelGGL(flow_residency_standin_kernel, dim3(chain_wgs), dim3(256), 0, dstream, host, host + 4);
@@ -1154,8 +1240,6 @@ static FlowResidency flow_measure_residency(hipStream_t stream, hipStream_t dstr
         ok = hipStreamSynchronize(stream) == hipSuccess && hipStreamSynchronize(dstream) == hipSuccess && ok &&
              hipMemcpy(h, counts, 192 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
     }
-    if (host) hipHostFree(host);
-    if (counts) hipFree(counts);
     if (ok) {
         int full = 0;
         for (int x = 0; x < 16; x++)
@@ -1180,7 +1264,7 @@ static FlowResidency flow_measure_residency(hipStream_t stream, hipStream_t dstr
         r.valid = true;
     }
     (void)hipGetLastError();
-    if (getenv("JAICOV_VERBOSE"))
+    if (flow_hooks().verbose)
         fprintf(stderr, "jaicov: residency of the tile kernel beside %d chain workgroups (grid %d): %s; %d XCDs, %d shader engines each, %d blocks dealt per XCD, "
                 "at least %d resident at once (%d on the fullest-booked shader engine), at most %d queued -> blocks >= %d of a chain workgroup's XCD leave without a ticket\n",
                 chain_wgs, grid, r.valid ? "measured" : "NOT measured", r.n_xcd, r.n_se, r.dealt, r.resident_min, r.se_cap, r.queued_max, r.keep);
@@ -1189,159 +1273,121 @@ static FlowResidency flow_measure_residency(hipStream_t stream, hipStream_t dstr
     if (r.valid && r.queued_max <= 3 * std::max(1, r.n_se)) cache.push_back({{grid, chain_wgs}, r});
     return r;
 }
+// two workgroups per CU; the CU of the diagonal kernel takes none, the surplus stays queued (harmless)
+static int flow_grid_size() {
+    const int cus = device_cu_count();
+    return std::max(1, std::min(FLOW_MAX_GRID, 2 * (cus > 0 ? cus : 256)));
+}
 extern "C" int jaicov_debug_flow_residency(int *out8) {       // tests / DESIGN.md: {valid, XCDs, shader engines, dealt, resident min, queued max, keep, 0}
-    hipStream_t s = nullptr, d = stream_acquire(STREAM_DIAGONAL_CUS);
-    if (!d || hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return -1;
-    int cus = 256;
-    hipDeviceProp_t prop;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    const FlowResidency r = flow_measure_residency(s, d, std::min(1024, 2 * cus), 2);
+    hipStream_t s = nullptr;
+    StreamLease d(STREAM_DIAGONAL_CUS);
+    if (!d.get() || hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return -1;
+    const FlowResidency r = flow_measure_residency(s, d.get(), flow_grid_size(), 2);
     hipStreamDestroy(s);
-    stream_release(STREAM_DIAGONAL_CUS, d);
     out8[0] = r.valid; out8[1] = r.n_xcd; out8[2] = r.n_se; out8[3] = r.dealt; out8[4] = r.resident_min; out8[5] = r.queued_max; out8[6] = r.keep; out8[7] = r.se_cap;
     return 0;
 }
 
-hipError_t DenseSolver::flow_init() {
-    const int nb = nfact / 128, row_blocks = n / 128;
-    if (!dstream) return hipErrorNotSupported;
-    // chain form unless kernels cannot run side by side (one-kernel form, diagonal blocks inline) or it is switched off
-    flow_one_kernel = !flow_kernels_overlap();
-    flow_chain = !flow_one_kernel && factor_form() != FACTOR_TWO_STEP;
-    // Third chain workgroup for the second subdiagonal: it finishes tile (c+2, c) by the chain's own forward substitution (from L_cc
-    // itself: no wait for the inverse workgroup) and subtracts it from tile (c+2, c+1), the tile the chain workgroup needs next.
-    // Rounds 2 and 3 measured it flat (22.4 +- 0.3 ms at order 15 104) and round 4's prune removed it -- for a day: once potrf of the
-    // 128-block had fallen from 41 to 27 us (potrf_diag.h) the chain workgroup's own cycle (59 us) was no longer the one that
-    // binds at small orders; the path potrf(c-1) -> inverse -> product with the inverse -> last update of tile (c+1, c) was (the chain
-    // waited 6-9 us per block column for that tile at order 3 072), and that is the path this workgroup shortens: order 3 072
-    // 1.70 -> 1.58 ms.  At order 8 192 it is neutral (5.3 vs 5.4 ms) and at 15 104 it changes nothing (22.7 vs 22.8 ms: the tiles it
-    // needs are late by the same path one diagonal further out, and the row chain of the tile kernel binds).  Crossover measured at the end of
-    // round 4 (ms, two / three chain workgroups): 40 block columns 2.88 / 2.65, 48: 3.60 / 3.39, 56: 4.42 / 4.20, 64: 5.36 / 5.21, 72: 6.65 / 6.53,
-    // 80: 8.25 / 8.21, 118: 22.3 / 22.7 -> used below 80 block columns.  JAICOV_FACTOR_FORM=chain2 / chain3 (test hooks): the chain form with two / three workgroups at any order.
-    flow_second = flow_chain && factor_form() != FACTOR_CHAIN2 && (nb < 80 || factor_form() == FACTOR_CHAIN3) ? 2 : 0;
-    int split_m = 1, split_from = 1 << 30;
-    flow_split_rule(nb, &split_m, &split_from);
-    flow_partials = 0;
-    const std::vector<int4> tasks = flow_schedule(nb, row_blocks, 1, flow_chain, flow_second, split_m, split_from, &flow_partials);
-    flow_tasks = (int)tasks.size();
-    flow_task_host = tasks;
-    HIPCHK(hipMalloc(&flow_task_list, tasks.size() * sizeof(int4)));
-    HIPCHK(hipMemcpy(flow_task_list, tasks.data(), tasks.size() * sizeof(int4), hipMemcpyHostToDevice));
-    flow_fs = nb;
-    flow_words = (size_t)FLOW_CTRL_WORDS + 2 * (size_t)row_blocks * nb + 2 * nb + 2048 + (size_t)flow_partials;   // ... + one state word per workgroup, and room for their copy at the moment a wait runs out
+hipError_t FlowFactor::init(const FlowView &view, const FlowHooks &hooks) {
+    const int nb = view.nfact / 128, row_blocks = view.n / 128;
+    if (!view.dstream) return hipErrorNotSupported;
+    FlowFactor f;        // built aside and moved in at the end: a failure on the way leaves nothing behind
+    f.v_ = view;
+    // (the one_kernel hook decides by itself: no probe, and nothing is cached)
+    const bool overlap = hooks.form != FACTOR_ONE_KERNEL && flow_kernels_overlap(view.dstream);
+    const FlowDecision dec = flow_decide(nb, overlap, hooks);
+    f.one_kernel_ = dec.one_kernel; f.chain_ = dec.chain; f.second_ = dec.second;
+    f.tasks_host_ = flow_schedule(nb, row_blocks, 1, f.chain_, f.second_, dec.split_m, dec.split_from, &f.partials_);
+    HIPCHK(f.tasks_.reserve(f.tasks_host_.size()));
+    HIPCHK(hipMemcpy(f.tasks_.get(), f.tasks_host_.data(), f.tasks_host_.size() * sizeof(int4), hipMemcpyHostToDevice));
+    f.lay_ = flow_layout(nb, row_blocks, f.partials_);
+    f.wg_off_ = (int)f.lay_.wgstate;
     // The flags live in FINE-GRAINED device memory (coherent across the XCDs while a kernel runs): in ordinary (coarse-grained)
     // memory polls of every flavour -- sc1, system scope, read-modify-write, with an acquire in between -- were seen to miss
     // flags that memory held as set, about once in 1 000-2 400 factorisations ("Visibility").
-    flow_flags = nullptr;
-    if (hipExtMallocWithFlags((void **)&flow_flags, flow_words * sizeof(int), hipDeviceMallocFinegrained) != hipSuccess) {
-        flow_flags = nullptr;
+    if (f.flags_.reserve_finegrained(f.lay_.words) != hipSuccess) {
         (void)hipGetLastError();
-    }
-    if (!flow_flags) {
         // (seen to matter: in ordinary memory a flag store can stay invisible to the other XCDs' polls for as long as the kernel runs)
-        fprintf(stderr, "jaicov: no fine-grained device memory for the flags of the dataflow factorisation (%zu words): ordinary memory, rare stalls possible\n", flow_words);
-        HIPCHK(hipMalloc(&flow_flags, flow_words * sizeof(int)));
+        fprintf(stderr, "jaicov: no fine-grained device memory for the flags of the dataflow factorisation (%zu words): ordinary memory, rare stalls possible\n", f.lay_.words);
+        HIPCHK(f.flags_.reserve(f.lay_.words));
     }
-    HIPCHK(hipMemset(flow_flags, 0, flow_words * sizeof(int)));
-    int cus = 256;
-    hipDeviceProp_t prop;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    flow_grid = 2 * cus;             // two workgroups per CU; the CU of the diagonal kernel takes none, the surplus stays queued (harmless)
-    if (flow_grid < 1) flow_grid = 1;
-    if (flow_grid > 1024) flow_grid = 1024;
-    HIPCHK(hipMalloc(&flow_scratch, ((size_t)flow_grid * 16384 + 64) * sizeof(double)));
-    HIPCHK(hipMemset(flow_scratch + (size_t)flow_grid * 16384, 0, 64 * sizeof(double)));
-    if (flow_partials > 0) HIPCHK(hipMalloc(&flow_partial, (size_t)flow_partials * 16384 * sizeof(double)));
-    HIPCHK(hipHostMalloc((void **)&flow_alive, 4 * sizeof(int), hipHostMallocMapped));
-    flow_alive[0] = flow_alive[1] = flow_alive[2] = flow_alive[3] = 0;
-    HIPCHK(hipEventCreateWithFlags(&flow_e0, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&flow_e1, hipEventDisableTiming));
-    HIPCHK(hipEventCreate(&flow_t0));
-    HIPCHK(hipEventCreate(&flow_t1));
-    flow_keep = flow_chain ? flow_measure_residency(stream, dstream, flow_grid, flow_second ? 3 : 2).keep : 0;
-    flow_ready = true;
-    if (getenv("JAICOV_FLOW_TRACE_ON")) HIPCHK(flow_enable_trace(true));     // per-task timestamps, read by flow_report_stall
+    HIPCHK(hipMemset(f.flags_.get(), 0, f.lay_.words * sizeof(int)));
+    f.grid_ = flow_grid_size();
+    HIPCHK(f.scratch_.reserve((size_t)f.grid_ * 16384 + 64));
+    HIPCHK(hipMemset(f.scratch_.get() + (size_t)f.grid_ * 16384, 0, 64 * sizeof(double)));
+    if (f.partials_ > 0) HIPCHK(f.partial_.reserve((size_t)f.partials_ * 16384));
+    HIPCHK(f.alive_.alloc(4));
+    for (int b = 0; b < 4; b++) f.alive_.get()[b] = 0;
+    HIPCHK(f.e0_.create(hipEventDisableTiming));
+    HIPCHK(f.e1_.create(hipEventDisableTiming));
+    HIPCHK(f.t0_.create());
+    HIPCHK(f.t1_.create());
+    f.keep_ = f.chain_ ? flow_measure_residency(view.stream, view.dstream, f.grid_, f.second_ ? 3 : 2).keep : 0;
+    f.ready_ = true;
+    if (hooks.trace_on) HIPCHK(f.enable_trace(true));
+    *this = std::move(f);
     return hipSuccess;
 }
 
-void DenseSolver::flow_release() {
-    if (flow_task_list) hipFree(flow_task_list);
-    if (flow_flags) hipFree(flow_flags);
-    if (flow_scratch) hipFree(flow_scratch);
-    if (flow_partial) hipFree(flow_partial);
-    flow_partial = nullptr;
-    if (flow_trace) hipFree(flow_trace);
-    if (flow_diag_scratch) hipFree(flow_diag_scratch);
-    flow_diag_scratch = nullptr;
-    if (flow_alive) hipHostFree(flow_alive);
-    flow_alive = nullptr;
-    for (hipEvent_t e : {flow_e0, flow_e1, flow_t0, flow_t1})
-        if (e) hipEventDestroy(e);
-    flow_task_list = nullptr; flow_flags = nullptr; flow_scratch = nullptr; flow_trace = nullptr;
-    flow_e0 = flow_e1 = flow_t0 = flow_t1 = nullptr;
-    flow_ready = false;
-}
-
-hipError_t DenseSolver::potrf_flow(hipEvent_t all_ready) {
-    const int nb = nfact / 128, row_blocks = n / 128;
+hipError_t FlowFactor::factor(hipEvent_t all_ready, bool profile) {
+    const hipStream_t stream = v_.stream, dstream = v_.dstream;
+    int *const flags = flags_.get();
     FlowArgs g{};
-    g.L = L; g.ld = ld; g.invd = invd;
-    g.tasks = flow_task_list; g.n_tasks = flow_tasks; g.nb = nb; g.fs = flow_fs;
-    g.ctrl = flow_flags;
-    g.done = flow_flags + FLOW_CTRL_WORDS;
-    g.applied = g.done + (size_t)row_blocks * nb;
-    g.diag_ready = g.applied + (size_t)row_blocks * nb;
-    g.factored = g.diag_ready + nb;
-    g.wgstate = g.factored + nb;
-    g.pflag = g.wgstate + 2048;
-    g.partial = flow_partial;
-    g.info = d_info;
-    g.scratch = flow_scratch;
-    g.zeros = flow_scratch + (size_t)flow_grid * 16384;
+    g.L = v_.L; g.ld = v_.ld; g.invd = v_.invd;
+    g.tasks = tasks_.get(); g.n_tasks = n_tasks(); g.nb = v_.nfact / 128; g.fs = g.nb;
+    g.ctrl = flags;
+    g.done = flags + lay_.done;
+    g.applied = flags + lay_.applied;
+    g.diag_ready = flags + lay_.diag_ready;
+    g.factored = flags + lay_.factored;
+    g.wgstate = flags + lay_.wgstate;
+    g.pflag = flags + lay_.pflag;
+    g.partial = partial_.get();
+    g.info = v_.d_info;
+    g.scratch = scratch_.get();
+    g.zeros = scratch_.get() + (size_t)grid_ * 16384;
     // time limit of a single wait, 100 MHz ticks: 0.25 s + 10 x the time the whole factorisation should take at 20 TFLOP/s
     // (order 15 104: 0.25 + 0.57 s... the longest ordinary wait there is ~2 ms)
-    const double expect_ms = (double)nfact * nfact * nfact / 3.0 / 20e9;
-    g.timeout = 100000LL * (getenv("JAICOV_FLOW_TIMEOUT_MS") ? atoi(getenv("JAICOV_FLOW_TIMEOUT_MS")) : (int)(250 + 10 * expect_ms));   // (the tests set 0)
-    g.src = flow_src; g.src_ld = flow_src_ld; g.V = flow_V; g.Bh = flow_Bh; g.d = flow_d; g.U = flow_U; g.bstride = flow_bstride;
-    flow_src = nullptr;      // one factorisation only
-    g.trace = flow_trace;
-    g.ctrace = flow_trace ? flow_trace + 8 * (size_t)flow_tasks : nullptr;
+    const double expect_ms = (double)v_.nfact * v_.nfact * v_.nfact / 3.0 / 20e9;
+    const FlowHooks now = flow_hooks();      // the time limit is a hook of the single factorisation
+    g.timeout = 100000LL * (now.timeout_ms != HOOK_UNSET ? now.timeout_ms : (int)(250 + 10 * expect_ms));   // (the tests set 0)
+    g.src = src_; g.src_ld = src_ld_; g.V = V_; g.Bh = Bh_; g.d = d_; g.U = U_; g.bstride = bstride_;
+    src_ = nullptr;      // one factorisation only
+    g.trace = trace_.get();
+    g.ctrace = trace_.get() ? trace_.get() + 8 * (size_t)n_tasks() : nullptr;
     g.fake_a = 0;
     g.crit_prio = 1;
-    g.second_update = flow_second >= 2 ? 1 : 0;
-    g.second_wg = flow_second ? 1 : 0;
+    g.second_update = second_ >= 2 ? 1 : 0;
+    g.second_wg = second_ ? 1 : 0;
     // which of the last workgroups of a chain workgroup's XCD take no ticket: from the residency measured beside stand-ins of the chain
     // workgroups (flow_measure_residency; 448 of 512 on the MI355X), 0 = none (nothing stays queued on this device, or not measurable)
-    g.keep = flow_chain ? flow_keep : 0;
+    g.keep = chain_ ? keep_ : 0;
     g.inv_wt = 1;
-    g.crit_span = flow_chain ? 2 : 1;
-    g.alive = flow_alive;
-    g.seq = ++flow_seq;
-    HIPCHK(hipMemsetAsync(flow_flags, 0, flow_words * sizeof(int), stream));
-    flow_wg_off = (int)(g.wgstate - g.ctrl);
-    HIPCHK(hipMemcpyAsync(flow_flags + FLOW_WG_OFF, &flow_wg_off, sizeof(int), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemsetAsync(d_info, 0, sizeof(int), stream));
-    if (flow_one_kernel) {
+    g.crit_span = chain_ ? 2 : 1;
+    g.alive = alive_.get();
+    g.seq = ++seq_;
+    HIPCHK(hipMemsetAsync(flags, 0, lay_.words * sizeof(int), stream));
+    HIPCHK(hipMemcpyAsync(flags + FLOW_WG_OFF, &wg_off_, sizeof(int), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(v_.d_info, 0, sizeof(int), stream));
+    if (one_kernel_) {
         // Kernels cannot run side by side here (every dispatch serialised: counter collection, a debugging environment): the
         // diagonal kernel and the tile kernel would wait for each other until the time limit.  ONE kernel, diagonal blocks inline.
-        if (!flow_diag_scratch) HIPCHK(hipMalloc(&flow_diag_scratch, (size_t)flow_grid * (128 * DP + 8 * 16 * WDP) * sizeof(double)));
-        g.diag_scratch = flow_diag_scratch;
+        HIPCHK(diag_scratch_.reserve((size_t)grid_ * (128 * DP + 8 * 16 * WDP)));
+        g.diag_scratch = diag_scratch_.get();
         g.alive = nullptr;
         if (all_ready) HIPCHK(hipStreamWaitEvent(stream, all_ready, 0));
-        if (profile) HIPCHK(hipEventRecord(flow_t0, stream));
-        hipLaunchKernelGGL((chol_tile_kernel<1, true>), dim3(flow_grid), dim3(256), 0, stream, g);
+        if (profile) HIPCHK(hipEventRecord(t0_.get(), stream));
+        hipLaunchKernelGGL((chol_tile_kernel<1, true>), dim3(grid_), dim3(256), 0, stream, g);
         if (profile) {
-            HIPCHK(hipEventRecord(flow_t1, stream));
-            flow_timed = true;
+            HIPCHK(hipEventRecord(t1_.get(), stream));
+            timed_ = true;
         }
         return hipGetLastError();
     }
-    HIPCHK(hipEventRecord(flow_e0, stream));
-    HIPCHK(hipStreamWaitEvent(dstream, flow_e0, 0));
+    HIPCHK(hipEventRecord(e0_.get(), stream));
+    HIPCHK(hipStreamWaitEvent(dstream, e0_.get(), 0));
     if (all_ready) HIPCHK(hipStreamWaitEvent(dstream, all_ready, 0));
-    if (flow_chain) hipLaunchKernelGGL(potrf_chain_kernel, dim3(flow_second ? 3 : 2), dim3(256), 0, dstream, g);
+    if (chain_) hipLaunchKernelGGL(potrf_chain_kernel, dim3(second_ ? 3 : 2), dim3(256), 0, dstream, g);
     else hipLaunchKernelGGL(potrf_diag_chain_kernel, dim3(1), dim3(256), 0, dstream, g);
     HIPCHK(hipGetLastError());
     // Residency.  The diagonal kernel needs a whole CU's LDS and runs on the stream whose CU mask holds one CU of every XCD.
@@ -1353,48 +1399,48 @@ hipError_t DenseSolver::potrf_flow(hipEvent_t all_ready) {
     {
         const auto t0 = std::chrono::steady_clock::now();
         int spins = 0;
-        while (__atomic_load_n(flow_alive, __ATOMIC_ACQUIRE) != g.seq ||
-               (flow_chain && (__atomic_load_n(flow_alive + 1, __ATOMIC_ACQUIRE) != g.seq ||
-                               (flow_second && __atomic_load_n(flow_alive + 2, __ATOMIC_ACQUIRE) != g.seq)))) {
+        while (__atomic_load_n(alive_.get(), __ATOMIC_ACQUIRE) != g.seq ||
+               (chain_ && (__atomic_load_n(alive_.get() + 1, __ATOMIC_ACQUIRE) != g.seq ||
+                           (second_ && __atomic_load_n(alive_.get() + 2, __ATOMIC_ACQUIRE) != g.seq)))) {
             if ((++spins & 1023) == 0) {
                 const double waited_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                 if (waited_s > 30.0) {
                     // the companion never became resident: tell it to leave (its waits watch the abort word), wait for it, and join
                     // the streams again, so that a later factorisation cannot clear the flags under a kernel that still runs
                     const int two = 2;
-                    (void)hipMemcpyAsync(flow_flags + FLOW_ABORT, &two, sizeof(int), hipMemcpyHostToDevice, pstream ? pstream : stream);
-                    (void)hipStreamSynchronize(pstream ? pstream : stream);
+                    const hipStream_t side = v_.pstream ? v_.pstream : stream;
+                    (void)hipMemcpyAsync(flags + FLOW_ABORT, &two, sizeof(int), hipMemcpyHostToDevice, side);
+                    (void)hipStreamSynchronize(side);
                     (void)hipStreamSynchronize(dstream);
-                    (void)hipEventRecord(flow_e1, dstream);
-                    (void)hipStreamWaitEvent(stream, flow_e1, 0);
+                    (void)hipEventRecord(e1_.get(), dstream);
+                    (void)hipStreamWaitEvent(stream, e1_.get(), 0);
                     return hipErrorLaunchTimeOut;
                 }
                 if (waited_s > 2e-4) std::this_thread::yield();      // the companion waits for earlier work on `stream`: do not burn the core meanwhile
             }
         }
     }
-    if (profile) HIPCHK(hipEventRecord(flow_t0, stream));
+    if (profile) HIPCHK(hipEventRecord(t0_.get(), stream));
     // operand loads TWO k-steps ahead (chol_tile_kernel<2, false>, 256 VGPRs, no scratch).  Measured equal to one step of lead in round 2, when
     // the backlog of the late columns hid everything; with the split update ranges the latency of the short runs at the dependency front shows:
     // 21.6 -> 21.35 ms at 118 block columns, 5.30 -> 5.19 at 64, equal at 24 (round 5)
-    hipLaunchKernelGGL((chol_tile_kernel<2, false>), dim3(flow_grid), dim3(256), 0, stream, g);
+    hipLaunchKernelGGL((chol_tile_kernel<2, false>), dim3(grid_), dim3(256), 0, stream, g);
     if (profile) {
-        HIPCHK(hipEventRecord(flow_t1, stream));
-        flow_timed = true;
+        HIPCHK(hipEventRecord(t1_.get(), stream));
+        timed_ = true;
     }
-    HIPCHK(hipEventRecord(flow_e1, dstream));
-    HIPCHK(hipStreamWaitEvent(stream, flow_e1, 0));
+    HIPCHK(hipEventRecord(e1_.get(), dstream));
+    HIPCHK(hipStreamWaitEvent(stream, e1_.get(), 0));
     return hipGetLastError();
 }
 
 // Error path (fetch_info found the abort word set): where did the factorisation stop?
-void DenseSolver::flow_report_stall() {
-    if (!flow_flags) return;
-    const int nb = nfact / 128, row_blocks = n / 128;
-    std::vector<int> f(flow_words);
-    if (hipMemcpy(f.data(), flow_flags, flow_words * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return;
-    const int *done = f.data() + FLOW_CTRL_WORDS, *applied = done + (size_t)row_blocks * nb;
-    const int *diag_ready = applied + (size_t)row_blocks * nb, *factored = diag_ready + nb;
+void FlowFactor::report_stall() const {
+    if (!flags_.get()) return;
+    const int nb = v_.nfact / 128, row_blocks = v_.n / 128;
+    std::vector<int> f(lay_.words);
+    if (hipMemcpy(f.data(), flags_.get(), lay_.words * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return;
+    const int *done = f.data() + lay_.done, *applied = f.data() + lay_.applied, *factored = f.data() + lay_.factored;
     int c_inv = 0, c_fac = 0, c_sub = 0;
     while (c_inv < nb && done[(size_t)c_inv * nb + c_inv]) ++c_inv;
     while (c_fac < nb && factored[c_fac]) ++c_fac;
@@ -1406,8 +1452,8 @@ void DenseSolver::flow_report_stall() {
     fprintf(stderr,
             "jaicov: dataflow factorisation abandoned (abort %d): ticket %d of %d, chain form %d, blocks %d; inverses published %d, "
             "factors published %d, subdiagonal tiles published %d, first unfinished tile (%d, %d), chain workgroup at column %d stage %d",
-            f[FLOW_ABORT], f[FLOW_TICKET], flow_tasks, (int)flow_chain, nb, c_inv, c_fac, c_sub, open_row, first_open, f[FLOW_CHAIN_AT] >> 4, f[FLOW_CHAIN_AT] & 15);
-    if (flow_chain && c_fac < nb) {
+            f[FLOW_ABORT], f[FLOW_TICKET], n_tasks(), (int)chain_, nb, c_inv, c_fac, c_sub, open_row, first_open, f[FLOW_CHAIN_AT] >> 4, f[FLOW_CHAIN_AT] & 15);
+    if (chain_ && c_fac < nb) {
         const int c = c_fac > 0 ? c_fac - 1 : 0;      // the column the chain workgroup was (probably) working on
         if (c + 1 < nb)
             fprintf(stderr, "; column %d: tile below stored with %d updates, next diagonal tile with %d (wanted %d)", c,
@@ -1416,26 +1462,26 @@ void DenseSolver::flow_report_stall() {
     fprintf(stderr, "\n");
     for (int b = 0; b < 3; b++) {
         const unsigned hw = (unsigned)f[8 + 2 * b];
-        if (flow_chain && (b < 2 || flow_second))
+        if (chain_ && (b < 2 || second_))
             fprintf(stderr, "jaicov:   chain workgroup %d runs on [xcc %d se %u sh %u cu %u]\n", b, f[9 + 2 * b] - 1, (hw >> 13) & 7, (hw >> 12) & 1, (hw >> 8) & 0xf);
     }
     // the oldest tickets still in flight, and what their workgroups were doing (1 drawn, 2 waiting for an earlier visit / the
     // inverse, 3 polling operand flags at block column k, 4 products, 5 / 6 storing after phase 0 / 1, 7 finished, 8 gave up)
-    const int *wg = factored + nb;
+    const int *wg = f.data() + lay_.wgstate, *snap = f.data() + lay_.wgsnap;
     std::vector<std::pair<int, int>> open;
-    for (int b = 0; b < std::min(flow_grid, 1024); b++)
+    for (int b = 0; b < grid_; b++)
         if (wg[b] != 0 && (wg[b] & 15) != 7) open.push_back({wg[b] >> 12, b});
     std::sort(open.begin(), open.end());
     std::vector<long long> tr;
-    if (flow_trace) {
-        tr.resize((size_t)flow_tasks * 8);
-        if (hipMemcpy(tr.data(), flow_trace, tr.size() * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) tr.clear();
+    if (trace_.get()) {
+        tr.resize((size_t)n_tasks() * 8);
+        if (hipMemcpy(tr.data(), trace_.get(), tr.size() * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) tr.clear();
     }
     long long t_last = 0;
     for (size_t q = 0; q + 7 < tr.size(); q += 8) t_last = std::max(t_last, tr[q + 3]);
     auto ticket_of = [&](int i, int j) {
-        for (int t = 0; t < flow_tasks; t++)
-            if (flow_task_host[t].x == i && flow_task_host[t].y == j) return t;
+        for (int t = 0; t < n_tasks(); t++)
+            if (tasks_host_[t].x == i && tasks_host_[t].y == j) return t;
         return -1;
     };
     // What every workgroup was doing at the MOMENT the first wait ran out (flow_give_up's copy of the state words): the ones that were not
@@ -1443,8 +1489,8 @@ void DenseSolver::flow_report_stall() {
     {
         int by_stage[16] = {0};
         std::vector<std::pair<int, int>> busy;
-        for (int b = 0; b < std::min(flow_grid, 1024); b++) {
-            const int w = wg[1024 + b];
+        for (int b = 0; b < grid_; b++) {
+            const int w = snap[b];
             if (w == 0) continue;
             by_stage[w & 15]++;
             if ((w & 15) == 4 || (w & 15) == 5 || (w & 15) == 6 || (w & 15) == 1) busy.push_back({w >> 12, b});
@@ -1453,15 +1499,15 @@ void DenseSolver::flow_report_stall() {
         fprintf(stderr, "jaicov:   when the first wait ran out: workgroups by stage [1 drawn %d, 2 waits for a visit / the inverse %d, 3 polls operands %d, 4 products %d, 5 / 6 stores %d / %d, 7 between tasks %d, 9 waits for partial sums %d]\n",
                 by_stage[1], by_stage[2], by_stage[3], by_stage[4], by_stage[5], by_stage[6], by_stage[7], by_stage[9]);
         for (size_t q = 0; q < busy.size() && q < 8; q++) {
-            const int w = wg[1024 + busy[q].second], t = w >> 12;
-            const int4 tk = (t >= 0 && t < (int)flow_task_host.size()) ? flow_task_host[t] : make_int4(-1, -1, 0, 0);
+            const int w = snap[busy[q].second], t = w >> 12;
+            const int4 tk = (t >= 0 && t < (int)tasks_host_.size()) ? tasks_host_[t] : make_int4(-1, -1, 0, 0);
             fprintf(stderr, "jaicov:     not waiting then: workgroup %d, ticket %d = tile (%d, %d)%s, stage %d at block column %d; now: stage %d at block column %d\n", busy[q].second, t, tk.x, tk.y,
                     (tk.w & FLOW_PART) ? " partial sum" : "", w & 15, (w >> 4) & 255, wg[busy[q].second] & 15, (wg[busy[q].second] >> 4) & 255);
         }
     }
     for (size_t q = 0; q < open.size() && q < 6; q++) {
         const int w = wg[open[q].second], t = w >> 12;
-        const int4 tk = flow_task_host.empty() ? make_int4(-1, -1, 0, 0) : flow_task_host[t];
+        const int4 tk = tasks_host_.empty() ? make_int4(-1, -1, 0, 0) : tasks_host_[t];
         fprintf(stderr, "jaicov:   workgroup %d: ticket %d = tile (%d, %d) to block column %d%s, stage %d at block column %d\n", open[q].second, t, tk.x,
                 tk.y, tk.w & (FLOW_FIN - 1), (tk.w & FLOW_FIN) ? " + finish" : "", w & 15, (w >> 4) & 255);
         // with JAICOV_FLOW_TRACE_ON: when were the two operand tiles it was waiting for finished (ms before the last recorded event)?
@@ -1472,7 +1518,7 @@ void DenseSolver::flow_report_stall() {
                 if (ot < 0) continue;
                 const long long *r = &tr[(size_t)ot * 8];
                 const unsigned hw = (unsigned)(r[7] & 0xffffffff);
-                const int ws = wg[1024 + (int)(r[6] & 0xffff)];
+                const int ws = snap[(int)(r[6] & 0xffff)];
                 fprintf(stderr, "jaicov:     (when the first wait ran out that workgroup was at: ticket %d, block column %d, stage %d)\n", ws >> 12, (ws >> 4) & 255, ws & 15);
                 fprintf(stderr, "jaicov:     operand tile (%d, %d) = ticket %d on workgroup %d [xcc %d se %u sh %u cu %u simd %u wave %u]: started %.3f ms, tile loaded %.3f ms, updates done %.3f ms, finished %.3f ms before the end; it waited %.3f ms\n",
                         oi, kk, ot, (int)(r[6] & 0xffff), (int)((r[7] >> 32) & 0xf), (hw >> 13) & 7, (hw >> 12) & 1, (hw >> 8) & 0xf, (hw >> 4) & 3, hw & 0xf,
@@ -1482,16 +1528,32 @@ void DenseSolver::flow_report_stall() {
 }
 
 // debug: per-task timeline of the next factorisations (scripts/flow_trace.py)
-hipError_t DenseSolver::flow_enable_trace(bool on) {
-    if (on && !flow_trace) {
-        const size_t words = ((size_t)flow_tasks + nfact / 128) * 8;      // per task, then per block column (chain kernel)
-        HIPCHK(hipMalloc(&flow_trace, words * sizeof(long long)));
-        HIPCHK(hipMemset(flow_trace, 0, words * sizeof(long long)));
-    } else if (!on && flow_trace) {
-        hipFree(flow_trace);
-        flow_trace = nullptr;
+hipError_t FlowFactor::enable_trace(bool on) {
+    if (on && !trace_.get()) {
+        HIPCHK(trace_.reserve(trace_words()));      // per task, then per block column (chain kernel)
+        HIPCHK(hipMemset(trace_.get(), 0, trace_words() * sizeof(long long)));
+    } else if (!on) {
+        trace_.reset();
     }
     return hipSuccess;
+}
+
+hipError_t FlowFactor::read_ctrl(int (&cw)[8]) const { return hipMemcpyAsync(cw, flags_.get(), sizeof(cw), hipMemcpyDeviceToHost, v_.stream); }
+
+// cw: [FLOW_ABORT] a wait ran into its time limit, [FLOW_STALE] / [FLOW_STALE_CONFIRMED] / [FLOW_RESCUED] flags that the plain poll missed
+bool FlowFactor::collect(const int (&cw)[8]) {
+    counters_.stale_events += cw[FLOW_STALE];
+    counters_.stale_confirmed += cw[FLOW_STALE_CONFIRMED];
+    counters_.rescued += cw[FLOW_RESCUED];
+    if (cw[FLOW_STALE] && flow_hooks().verbose)
+        fprintf(stderr, "jaicov: dataflow factorisation: %d flag(s) found by the read-modify-write poll, %d of them still invisible to the plain poll, %d after more than 1 ms of waiting\n", cw[FLOW_STALE], cw[FLOW_STALE_CONFIRMED], cw[FLOW_RESCUED]);
+    return cw[FLOW_ABORT] != 0;
+}
+
+bool FlowFactor::elapsed_ms(float *ms) {
+    if (!timed_) return false;
+    timed_ = false;
+    return hipEventElapsedTime(ms, t0_.get(), t1_.get()) == hipSuccess;
 }
 
 }  // namespace jaicov

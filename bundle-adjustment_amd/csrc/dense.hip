@@ -825,9 +825,6 @@ __global__ __launch_bounds__(256) void symmetrize_kernel(double *M, long ld, int
     }
 }
 
-// JAICOV_FACTOR_FORM = streams | two_step | one_kernel | chain2 | chain3: the forms of the factorisation other than the default (dataflow, chain
-// form), each named by a case of tests/test_gpu_parity.py (test_factor_tile_by_tile, test_config3_step_against_oracle).  Read at
-// every call: the tests switch it between engines of one process.
 namespace {
 std::mutex g_stream_mutex;
 std::map<std::pair<int, int>, std::vector<hipStream_t>> g_stream_pool;      // (device, kind) -> idle streams
@@ -930,15 +927,11 @@ extern "C" void jaicov_debug_stream_census(int *out8) {
         if (kv.first.second >= 0 && kv.first.second < 4) out8[4 + kv.first.second] += (int)kv.second.size();
 }
 
-int factor_form() {
-    const char *e = getenv("JAICOV_FACTOR_FORM");
-    if (!e) return FACTOR_DEFAULT;
-    if (!strcmp(e, "streams")) return FACTOR_STREAMS;
-    if (!strcmp(e, "two_step")) return FACTOR_TWO_STEP;
-    if (!strcmp(e, "one_kernel")) return FACTOR_ONE_KERNEL;
-    if (!strcmp(e, "chain2")) return FACTOR_CHAIN2;          // the chain form with two chain workgroups (no third one for the second subdiagonal)
-    if (!strcmp(e, "chain3")) return FACTOR_CHAIN3;          // ... with three, whatever the order (default: below 80 block columns)
-    return FACTOR_DEFAULT;
+int device_cu_count() {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) return cus;
+    (void)hipGetLastError();
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -948,62 +941,59 @@ hipError_t DenseSolver::init(hipStream_t s, int n_padded, bool with_inverse, boo
     nfact = n_padded;
     n = n_padded + (aug ? 128 : 0);
     ld = n;
-    owns = true;
-    const size_t sq = (size_t)n * ld * sizeof(double);
-    HIPCHK(hipMalloc(&L, sq));
-    HIPCHK(hipMalloc(&invd, (size_t)(nfact / 128) * 16384 * sizeof(double)));
-    HIPCHK(hipMemset(invd, 0, (size_t)(nfact / 128) * 16384 * sizeof(double)));
-    HIPCHK(hipMalloc(&xch, (size_t)nfact * sizeof(double)));
-    HIPCHK(hipEventCreateWithFlags(&pm_e0, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&pm_done, hipEventDisableTiming));
-    HIPCHK(hipMalloc(&pm, (size_t)(nfact / 128) * 2 * CH_PM * 16384 * sizeof(double)));
-    HIPCHK(hipMemset(pm, 0, (size_t)(nfact / 128) * 2 * CH_PM * 16384 * sizeof(double)));
-    pm_ready = false;
-    HIPCHK(hipMalloc(&d_info, sizeof(int)));
+    const hipError_t err = acquire(with_inverse, share);
+    if (err != hipSuccess) release();
+    return err;
+}
 
-    // Which factorisation: both are bound by a chain of one link per block column while the order is small (dataflow: the
-    // chain workgroup's potrf -> solve -> update, ~80-95 us; streams: diagonal kernel + two dependent launches, ~80 us), the
-    // dataflow form then pays its start-up (two launches, a host handshake, ~0.15 ms).  Measured on MI355X
-    // (scripts/flow_trace.py, ms per factorisation dataflow / streams): order 1024 0.76 / 0.62, 2048 1.32 / 1.28,
-    // 3072 1.94 / 2.00, 3712 2.37 / 2.50, 5120 3.33 / 3.75, 6144 4.07 / 4.78, 8192 5.95 / 7.92, 15104 22.3 / 26.3
-    // -> from 24 block columns on (rounds 2 and 3).  Round 4 (diagonal block 41 -> 27 us, third chain workgroup below 48 block columns):
-    // order 640 0.43 / 0.39, 1024 0.65 / 0.59, 1152 0.70 / 0.69, 1280 0.75 / 0.77, 1408 0.82 / 0.83, 1536 0.82 / 0.92, 2048 1.10 / 1.25,
-    // 2560 1.32 / 1.59, 3072 1.55 / 1.94 -> from 12 block columns on.
-    const int flow_from = getenv("JAICOV_FLOW_MIN_BLOCKS") ? atoi(getenv("JAICOV_FLOW_MIN_BLOCKS")) : 12;      // (the tests lower it)
-    const bool flow_wanted = factor_form() != FACTOR_STREAMS && nfact / 128 >= flow_from;
-    borrowed_streams = share != nullptr && share->owns && !share->borrowed_streams && share->pstream != nullptr;
-    own_ustream = own_dstream = false;
-    if (borrowed_streams) {
+hipError_t DenseSolver::acquire(bool with_inverse, const DenseSolver *share) {
+    const size_t sq = (size_t)n * ld, nbq = (size_t)(nfact / 128) * 16384;
+    HIPCHK(store.L.reserve(sq));
+    HIPCHK(store.invd.reserve(nbq));
+    HIPCHK(hipMemset(store.invd.get(), 0, nbq * sizeof(double)));
+    HIPCHK(store.xch.reserve((size_t)nfact));
+    HIPCHK(pm_e0.create(hipEventDisableTiming));
+    HIPCHK(pm_done.create(hipEventDisableTiming));
+    HIPCHK(store.pm.reserve(nbq * 2 * CH_PM));
+    HIPCHK(hipMemset(store.pm.get(), 0, nbq * 2 * CH_PM * sizeof(double)));
+    pm_ready = false;
+    HIPCHK(store.info.reserve(1));
+    L = store.L.get(); invd = store.invd.get(); xch = store.xch.get(); pm = store.pm.get(); d_info = store.info.get();
+
+    cus = device_cu_count();
+    hooks = flow_hooks();
+    const bool flow_wanted = flow_decide(nfact / 128, true, hooks).use_flow;      // (whether kernels overlap is asked once the streams are there: it does not bear on this)
+    // the side streams of `share` where it holds them itself, streams of this solver's own otherwise
+    const bool borrowed = share != nullptr && share->pstream_lease.get() != nullptr;
+    if (borrowed) {
         pstream = share->pstream;
     } else {
-        pstream = stream_acquire(STREAM_HIGH_PRIORITY);
+        pstream_lease = StreamLease(STREAM_HIGH_PRIORITY);
+        pstream = pstream_lease.get();
         if (!pstream) return hipErrorUnknown;
     }
-    {
-        // reserved CUs: CU 31 of every XCD for the diagonal blocks, the other 31 for the trailing updates (stream_acquire).  The masked
-        // stream of the trailing updates is only held by a solver that factorises by the stream-scheduled form: the dataflow form
-        // (flow_wanted) launches its tile kernel on the ordinary stream, and every CU-masked stream is a hardware queue (dense.h).
-        // A masked stream the other solver of the engine holds is used (only where this solver needs one); what it does not hold is
-        // acquired here and is then this solver's own to release.
-        if (nfact >= 2048 || flow_wanted) {
-            reserved_cus = 8;
-            dstream = borrowed_streams ? share->dstream : nullptr;
-            if (!dstream) { dstream = stream_acquire(STREAM_DIAGONAL_CUS); own_dstream = dstream != nullptr; }
-            if (!flow_wanted) {
-                ustream = borrowed_streams ? share->ustream : nullptr;
-                if (!ustream) { ustream = stream_acquire(STREAM_UPDATE_CUS); own_ustream = ustream != nullptr; }
-            }
-            if (!dstream || (!flow_wanted && !ustream)) {
-                if (own_ustream) stream_release(STREAM_UPDATE_CUS, ustream);
-                if (own_dstream) stream_release(STREAM_DIAGONAL_CUS, dstream);
-                ustream = dstream = nullptr;
-                own_ustream = own_dstream = false;
-            }
+    // reserved CUs: CU 31 of every XCD for the diagonal blocks, the other 31 for the trailing updates (stream_acquire).  The masked
+    // stream of the trailing updates is only held by a solver that factorises by the stream-scheduled form: the dataflow form
+    // (flow_wanted) launches its tile kernel on the ordinary stream, and every CU-masked stream is a hardware queue (dense.h).
+    // A masked stream the other solver of the engine holds is used (only where this solver needs one); what it does not hold is
+    // acquired here and is then this solver's own to release.
+    auto masked = [&](hipStream_t theirs, StreamLease &own, int kind) {
+        if (theirs) return theirs;
+        own = StreamLease(kind);
+        return own.get();
+    };
+    if (nfact >= 2048 || flow_wanted) {
+        dstream = masked(borrowed ? share->dstream : nullptr, dstream_lease, STREAM_DIAGONAL_CUS);
+        if (!flow_wanted) ustream = masked(borrowed ? share->ustream : nullptr, ustream_lease, STREAM_UPDATE_CUS);
+        if (!dstream || (!flow_wanted && !ustream)) {
+            ustream_lease = StreamLease();
+            dstream_lease = StreamLease();
+            ustream = dstream = nullptr;
         }
     }
     // XCD-aware tile orders of every trailing-update size this solver can launch (one allocation, built here so that the
     // first factorisation does not stop for host work)
-    if (xcd_maps && n / 128 >= 24) {
+    if (n / 128 >= 24) {
         std::vector<int2> all;
         std::vector<std::pair<int, std::pair<size_t, int>>> where;
         for (int T = 24; T <= n / 128; T++) {
@@ -1011,65 +1001,55 @@ hipError_t DenseSolver::init(hipStream_t s, int n_padded, bool with_inverse, boo
             where.push_back({T, {all.size(), (int)m.size()}});
             all.insert(all.end(), m.begin(), m.end());
         }
-        HIPCHK(hipMalloc(&tile_map_store, all.size() * sizeof(int2)));
-        HIPCHK(hipMemcpy(tile_map_store, all.data(), all.size() * sizeof(int2), hipMemcpyHostToDevice));
-        for (auto &w : where) tile_maps.emplace(w.first, std::make_pair(tile_map_store + w.second.first, w.second.second));
+        HIPCHK(tile_map_store.reserve(all.size()));
+        HIPCHK(hipMemcpy(tile_map_store.get(), all.data(), all.size() * sizeof(int2), hipMemcpyHostToDevice));
+        for (auto &w : where) tile_maps.emplace(w.first, std::make_pair(tile_map_store.get() + w.second.first, w.second.second));
     }
     if (with_inverse) {
-        HIPCHK(hipMalloc(&W, sq));
-        HIPCHK(hipMalloc(&Q, sq));
+        HIPCHK(store.W.reserve(sq));
+        HIPCHK(store.Q.reserve(sq));
+        W = store.W.get(); Q = store.Q.get();
     }
-    if (flow_wanted && dstream) {
-        hipError_t fe = flow_init();
-        if (fe != hipSuccess) {      // the stream-scheduled factorisation remains: it wants the masked stream of the trailing updates after all
-            flow_release(); (void)hipGetLastError();
-            if (!ustream) { ustream = stream_acquire(STREAM_UPDATE_CUS); own_ustream = ustream != nullptr; }
-        }
+    if (flow_wanted && dstream && flow.init(FlowView{L, ld, invd, d_info, nfact, n, stream, pstream, dstream}, hooks) != hipSuccess) {
+        // the stream-scheduled factorisation remains: it wants the masked stream of the trailing updates after all
+        (void)hipGetLastError();
+        ustream = masked(ustream, ustream_lease, STREAM_UPDATE_CUS);
     }
     return hipSuccess;
 }
 
 void DenseSolver::release() {
-    if (!owns) return;
-    flow_release();
-    hipFree(L); hipFree(invd); hipFree(d_info); hipFree(W); hipFree(Q); hipFree(pm); hipFree(xch);
-    hipFree(tile_map_store);
-    tile_map_store = nullptr;
-    for (auto &kv : trtri_maps) hipFree(kv.second);
+    flow = FlowFactor();
+    store = Store();
+    tile_map_store.reset();
     trtri_maps.clear();
     tile_maps.clear();
-    for (auto ev : prof_ev) hipEventDestroy(ev);
     prof_ev.clear();
-    for (auto ev : sync_ev) hipEventDestroy(ev);
     sync_ev.clear();
-    if (!borrowed_streams) stream_release(STREAM_HIGH_PRIORITY, pstream);
-    if (own_ustream) stream_release(STREAM_UPDATE_CUS, ustream);
-    if (own_dstream) stream_release(STREAM_DIAGONAL_CUS, dstream);
+    pstream_lease = StreamLease();
+    ustream_lease = StreamLease();
+    dstream_lease = StreamLease();
     pstream = ustream = dstream = nullptr;
-    borrowed_streams = own_ustream = own_dstream = false;
-    L = invd = W = Q = nullptr;
-    if (pm_e0) hipEventDestroy(pm_e0);
-    if (pm_done) hipEventDestroy(pm_done);
-    pm_e0 = pm_done = nullptr; pm_wait = false;
-    pm = nullptr; pm_ready = false; xch = nullptr;
+    L = invd = W = Q = pm = xch = nullptr;
     d_info = nullptr;
-    owns = false;
+    pm_e0.reset(); pm_done.reset();
+    pm_wait = pm_ready = false;
 }
 
-// Two-level right-looking Cholesky with one-panel lookahead.
-// Outer panels of `nbo` columns (trailing update with K = nbo: enough flops per byte of C to be MFMA-bound); inside a
+// Two-level right-looking Cholesky with one-panel look-ahead.
+// Outer panels of DENSE_PANEL columns (trailing update with K = DENSE_PANEL: enough flops per byte of C to be MFMA-bound); inside a
 // panel a left-looking sweep over 128-column blocks:
-//   block column kk -= L[kk:n, k0:kk] L[kk:kk+128, k0:kk]'     (fp64 MFMA GEMM, K grows to nbo-128)
+//   block column kk -= L[kk:n, k0:kk] L[kk:kk+128, k0:kk]'     (fp64 MFMA GEMM, K grows to DENSE_PANEL-128)
 //   diagonal block factor + inverse (one workgroup, LDS)        L21 = A21 inv(L11)'  (GEMM with the inverse)
-// Lookahead: the trailing update of panel s is split into (a) the columns of panel s+1 and (b) the rest; panel s+1 is
+// Look-ahead: the trailing update of panel s is split into (a) the columns of panel s+1 and (b) the rest; panel s+1 is
 // factored on a second, high-priority stream as soon as (a) is done, while (b) keeps the chip busy.
 hipEvent_t DenseSolver::next_event() {
     if (ev_used >= sync_ev.size()) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
-        sync_ev.push_back(e);
+        DevEvent e;
+        if (e.create(hipEventDisableTiming) != hipSuccess) return nullptr;
+        sync_ev.push_back(std::move(e));
     }
-    return sync_ev[ev_used++];
+    return sync_ev[ev_used++].get();
 }
 
 // Panel factorisation of block columns [K0,K1).  GEMMs go to `st`; when a reserved-CU stream exists the diagonal-block
@@ -1084,9 +1064,8 @@ hipError_t DenseSolver::panel(hipStream_t st, int K0, int K1) {
         const int rows_k = n - k * 128;
         // ... except for the first block of a panel: it becomes ready at the moment the trailing update is launched, and a
         // workgroup that wants a whole CU's LDS then waits for the update's first tiles to retire (130 us instead of 49)
-        constexpr bool first_split = true;
         // (only while the update still has more workgroups than the chip has slots: 31 tile rows = 496 tiles)
-        const bool split = dstream != nullptr && st == pstream && (rows_k > tail_rows || (first_split && k == K0 && rows_k > 4096));
+        const bool split = dstream != nullptr && st == pstream && (rows_k > tail_rows || (k == K0 && rows_k > 4096));
         // While the trailing update still hides the panel (many rows left) the panel GEMMs take the 128-tile: it costs
         // the update fewer CU slots per flop than the 64-tile latency variant, which is for the critical-path regime.
         constexpr int bulk_rows = 9216;
@@ -1128,15 +1107,15 @@ hipError_t DenseSolver::panel(hipStream_t st, int K0, int K1) {
 hipError_t DenseSolver::timed_gemm(hipStream_t st, const GemmArgs &u, double flops, int small) {
     if (profile) {
         if (prof_used + 2 > prof_ev.size()) {
-            hipEvent_t a, b;
-            HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-            prof_ev.push_back(a); prof_ev.push_back(b);
+            DevEvent a, b;
+            HIPCHK(a.create()); HIPCHK(b.create());
+            prof_ev.push_back(std::move(a)); prof_ev.push_back(std::move(b));
         }
-        HIPCHK(hipEventRecord(prof_ev[prof_used], st));
+        HIPCHK(hipEventRecord(prof_ev[prof_used].get(), st));
     }
     HIPCHK(gemm_f64(st, LAY_KC, LAY_KC, u, 1, small, 1));   // own kernel symbol: gemm_f64_kernel<0, 0, 128, 128, 1> (64, 64 in the tail)
     if (profile) {
-        HIPCHK(hipEventRecord(prof_ev[prof_used + 1], st));
+        HIPCHK(hipEventRecord(prof_ev[prof_used + 1].get(), st));
         prof_flops.push_back(flops);
         prof_used += 2;
     }
@@ -1145,22 +1124,21 @@ hipError_t DenseSolver::timed_gemm(hipStream_t st, const GemmArgs &u, double flo
 
 int DenseSolver::first_panel_cols() const {
     const int nb = nfact / 128;
-    const int k = nbo / 128 > 0 ? nbo / 128 : 1;
-    return 128 * (k < nb ? k : nb);
+    return 128 * std::min(DENSE_PANEL / 128, nb);
 }
 
 // Call before the first WRITE into L for a new factorisation (the engine's scaled copy, a dispersion load): the Ft half of the last
 // premultiply() may still be reading the old factor on pstream.  potrf() does the same for callers that fill L through potrf's own
-// first tile load (flow_set_source), where nothing writes L earlier.
+// first tile load (FlowFactor::set_source), where nothing writes L earlier.
 hipError_t DenseSolver::begin_refactor() {
     pm_ready = false;
-    if (pm_wait) { HIPCHK(hipStreamWaitEvent(stream, pm_done, 0)); pm_wait = false; }
+    if (pm_wait) { HIPCHK(hipStreamWaitEvent(stream, pm_done.get(), 0)); pm_wait = false; }
     return hipSuccess;
 }
 
 hipError_t DenseSolver::potrf(hipEvent_t first_ready, hipEvent_t all_ready) {
     HIPCHK(begin_refactor());
-    if (flow_ready) return potrf_flow(all_ready);
+    if (flow.ready()) return flow.factor(all_ready, profile);
     return potrf_streams(first_ready, all_ready);
 }
 
@@ -1168,9 +1146,8 @@ hipError_t DenseSolver::potrf_streams(hipEvent_t first_ready, hipEvent_t all_rea
     const int nb = nfact / 128;   // diagonal blocks; rows run to n (the right-hand-side rows below the matrix included)
     // Panel width: one width for the whole factorisation (wide panels while many rows remain, narrow ones in the tail: measured
     // flat +- 0.3 ms at config 4, DESIGN_HISTORY.md)
-    const int bo = nbo / 128 > 0 ? nbo / 128 : 1;
-    auto width = [&](int) { return bo; };
-    const bool la = lookahead && pstream != nullptr && nb > bo;
+    constexpr int bo = DENSE_PANEL / 128;
+    const bool la = pstream != nullptr && nb > bo;            // look-ahead: panel s+1 on pstream beside the rest of trailing update s
     ev_used = 0;
     hipStream_t sp = la ? pstream : stream;                 // panel GEMMs
     hipStream_t su = la && ustream ? ustream : stream;      // trailing updates (all CUs but the reserved ones)
@@ -1186,12 +1163,12 @@ hipError_t DenseSolver::potrf_streams(hipEvent_t first_ready, hipEvent_t all_rea
         }
     }
     HIPCHK(hipMemsetAsync(d_info, 0, sizeof(int), sp));    // before the first diagonal kernel, which runs on sp or behind it
-    int K0 = 0, K1 = width(0) < nb ? width(0) : nb;
+    int K0 = 0, K1 = std::min(bo, nb);
     HIPCHK(panel(sp, 0, K1));
     hipEvent_t e_panel = next_event();
     if (la) HIPCHK(hipEventRecord(e_panel, sp));
     while (K1 < nb) {
-        const int K2 = (K1 + width(K1) < nb) ? K1 + width(K1) : nb;     // end of the next panel
+        const int K2 = std::min(K1 + bo, nb);     // end of the next panel
         if (la) HIPCHK(hipStreamWaitEvent(su, e_panel, 0));
         const int Kw = (K1 - K0) * 128;
         // (a) columns of the next panel: rows >= K1, cols [K1,K2)
@@ -1217,7 +1194,7 @@ hipError_t DenseSolver::potrf_streams(hipEvent_t first_ready, hipEvent_t all_rea
             u.A = L + (long)(K2 * 128) * ld + K0 * 128; u.lda = ld; u.B = u.A; u.ldb = ld;
             u.C = L + (long)(K2 * 128) * ld + K2 * 128; u.ldc = ld;
             u.M = rows; u.N = rows; u.K = Kw; u.alpha = -1.0; u.beta = 1.0; u.lower_only = 1; u.kmode = KMODE_FULL;
-            if (xcd_maps && rows / 128 >= 24) {
+            if (rows / 128 >= 24) {
                 const int T = rows / 128;
                 auto it = tile_maps.find(T);
                 if (it != tile_maps.end()) {
@@ -1242,23 +1219,9 @@ hipError_t DenseSolver::potrf_streams(hipEvent_t first_ready, hipEvent_t all_rea
     return hipGetLastError();
 }
 
-// The polling-wave chains pay two batched GEMM launches per factorisation (~0.1 ms) for ~1.2 us per link and chain: from this many
-// block columns on (config 2, 6 block columns: 0.085 -> 0.14 ms per pass with them; config 3, 29: 0.28 -> 0.27)
-static int chain8_min_nb() {         // (read at every call: the tests lower it)
-    const char *e = getenv("JAICOV_CHAIN8_MIN_NB");
-    return e ? atoi(e) : 24;
-}
-
 // the backward chain for one right-hand side: two workgroups per block column when the whole grid is resident at once
 bool DenseSolver::chain8_split() const {
     const int nb = nfact / 128;
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount;
-        if (cus <= 0) cus = 1;
-    }
     return xch && nb >= 8 && 2 * nb <= cus;
 }
 
@@ -1296,12 +1259,11 @@ hipError_t DenseSolver::premultiply() {
         f.batch_sum_limit = nb - 1;
         // the Ft blocks are needed by the forward chain of the refinement only: on the side stream, beside the first backward chain
         // and the residual (solve_rhs waits for pm_done)
-        constexpr bool side = true;
-        if (side && pstream && pm_e0 && pm_done) {
-            HIPCHK(hipEventRecord(pm_e0, stream));
-            HIPCHK(hipStreamWaitEvent(pstream, pm_e0, 0));
+        if (pstream && pm_e0.get() && pm_done.get()) {
+            HIPCHK(hipEventRecord(pm_e0.get(), stream));
+            HIPCHK(hipStreamWaitEvent(pstream, pm_e0.get(), 0));
             HIPCHK(gemm_f64(pstream, LAY_XC, LAY_KC, f, nb - 1, 0, 0, std::min(CH_PM, nb - 1)));
-            HIPCHK(hipEventRecord(pm_done, pstream));
+            HIPCHK(hipEventRecord(pm_done.get(), pstream));
             pm_wait = true;
         } else {
             HIPCHK(gemm_f64(stream, LAY_XC, LAY_KC, f, nb - 1, 0, 0, std::min(CH_PM, nb - 1)));
@@ -1315,8 +1277,8 @@ hipError_t DenseSolver::backsolve_aug(double *X, long xs, int nrhs) {
     if (!aug || nrhs < 1 || nrhs > DENSE_MAX_RHS) return hipErrorInvalidValue;
     const int nb = nfact / 128;
     HIPCHK(hipMemsetAsync(X, 0xFF, (size_t)nrhs * xs * sizeof(double), stream));   // "not yet published"
-    const int *ab = flow_ready ? flow_flags + 1 : nullptr;      // cholflow.hip FLOW_ABORT
-    if (nrhs <= 1 && pm && nb >= chain8_min_nb()) {
+    const int *ab = flow.abort_word();
+    if (nrhs <= 1 && pm && nb >= chain8_min_blocks(flow_hooks())) {      // (asked at every call: the tests lower it)
         HIPCHK(premultiply());
         HIPCHK(launch_chain8(rhs_row(0), X, ab, nullptr));
     } else if (nrhs <= 1) hipLaunchKernelGGL(backsolve_chain_kernel<1>, dim3(nb), dim3(256), 0, stream, L, ld, invd, rhs_row(0), ld, X, xs, nb, nrhs, ab);
@@ -1332,24 +1294,24 @@ hipError_t DenseSolver::solve_rhs(const double *b, double *tmp, double *X) {
     const int nb = nfact / 128;
     HIPCHK(hipMemsetAsync(tmp, 0xFF, (size_t)nfact * sizeof(double), stream));
     HIPCHK(hipMemsetAsync(X, 0xFF, (size_t)nfact * sizeof(double), stream));
-    if (pm && nb >= chain8_min_nb()) {
+    if (pm && nb >= chain8_min_blocks(flow_hooks())) {
         HIPCHK(premultiply());
-        static const bool tracing = getenv("JAICOV_CHAIN_TRACE") != nullptr;     // development: link times of the backward chain on stderr
-        long long *tr = nullptr;
-        if (tracing) { HIPCHK(hipMalloc(&tr, (size_t)9 * nb * sizeof(long long))); HIPCHK(hipMemsetAsync(tr, 0, (size_t)9 * nb * sizeof(long long), stream)); }
-        if (pm_wait) { HIPCHK(hipStreamWaitEvent(stream, pm_done, 0)); pm_wait = false; }
+        const bool tracing = hooks.chain_trace;     // development: link times of the backward chain on stderr
+        DevBuf<long long> trbuf;
+        if (tracing) { HIPCHK(trbuf.reserve((size_t)9 * nb)); HIPCHK(hipMemsetAsync(trbuf.get(), 0, (size_t)9 * nb * sizeof(long long), stream)); }
+        long long *tr = trbuf.get();
+        if (pm_wait) { HIPCHK(hipStreamWaitEvent(stream, pm_done.get(), 0)); pm_wait = false; }
         if (chain8_split()) {
             HIPCHK(hipMemsetAsync(xch, 0xFF, (size_t)nfact * sizeof(double), stream));
             hipLaunchKernelGGL(forwardsolve_chain8_kernel, dim3(2 * nb), dim3(CHAIN8_THREADS), 0, stream, L, ld, invd, pm + (size_t)CH_PM * nb * 16384, b, tmp, xch, nb);
         } else {
             hipLaunchKernelGGL(forwardsolve_chain_kernel, dim3(nb), dim3(256), 0, stream, L, ld, invd, b, tmp, nb);
         }
-        HIPCHK(launch_chain8(tmp, X, flow_ready ? flow_flags + 1 : nullptr, tr));   // behind an abandoned factorisation: leave at once (as backsolve_aug)
+        HIPCHK(launch_chain8(tmp, X, flow.abort_word(), tr));   // behind an abandoned factorisation: leave at once (as backsolve_aug)
         if (tracing) {
             std::vector<long long> h((size_t)9 * nb);
             HIPCHK(hipMemcpyAsync(h.data(), tr, h.size() * sizeof(long long), hipMemcpyDeviceToHost, stream));
             HIPCHK(hipStreamSynchronize(stream));
-            hipFree(tr);
             fprintf(stderr, "[jaicov chain trace] backward, nb %d, link times in 10 ns:", nb);
             for (int q = 1; q < nb; q++) fprintf(stderr, " %lld", h[q] - h[q - 1]);
             fprintf(stderr, "\n[jaicov chain trace] per position: start, stream done (wave 1), barrier 1, barrier 2, u ready, tails done, polling wave done, stream done (wave 7), relative to the predecessor's publication (10 ns)\n");
@@ -1362,7 +1324,7 @@ hipError_t DenseSolver::solve_rhs(const double *b, double *tmp, double *X) {
         return hipGetLastError();
     }
     hipLaunchKernelGGL(forwardsolve_chain_kernel, dim3(nb), dim3(256), 0, stream, L, ld, invd, b, tmp, nb);
-    hipLaunchKernelGGL(backsolve_chain_kernel<1>, dim3(nb), dim3(256), 0, stream, L, ld, invd, tmp, (long)nfact, X, (long)nfact, nb, 1, flow_ready ? flow_flags + 1 : (const int *)nullptr);
+    hipLaunchKernelGGL(backsolve_chain_kernel<1>, dim3(nb), dim3(256), 0, stream, L, ld, invd, tmp, (long)nfact, X, (long)nfact, nb, 1, flow.abort_word());
     return hipGetLastError();
 }
 
@@ -1377,7 +1339,7 @@ hipError_t DenseSolver::solve_rhs(const double *b, double *tmp, double *X) {
 const int2 *DenseSolver::trtri_tile_order(int tm, int tn, int kind) {
     const long key = ((long)kind << 40) | ((long)tm << 20) | tn;
     auto it = trtri_maps.find(key);
-    if (it != trtri_maps.end()) return it->second;
+    if (it != trtri_maps.end()) return it->second.get();
     std::vector<int2> m;
     m.reserve((size_t)tm * tn);
     if (kind == 0) {            // KMODE_GE_COL: column 0 has the longest k-range
@@ -1387,17 +1349,16 @@ const int2 *DenseSolver::trtri_tile_order(int tm, int tn, int kind) {
         for (int i = tm - 1; i >= 0; i--)
             for (int j = 0; j < tn; j++) m.push_back(make_int2(i, j));
     }
-    int2 *d = nullptr;
-    if (hipMalloc(&d, m.size() * sizeof(int2)) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, m.data(), m.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return nullptr; }
-    trtri_maps.emplace(key, d);
-    return d;
+    DevBuf<int2> d;
+    if (d.reserve(m.size()) != hipSuccess) return nullptr;
+    if (hipMemcpy(d.get(), m.data(), m.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return trtri_maps.emplace(key, std::move(d)).first->second.get();
 }
 
 hipError_t DenseSolver::trtri() {
     const int nb = nfact / 128;
     if (!Q) return hipErrorInvalidValue;
-    constexpr bool lpt = true;      // longest k-range first (row-major order: 24.7 instead of 18.5 ms at config 4)
+    // tiles of the products longest k-range first (row-major order: 24.7 instead of 18.5 ms at config 4)
     HIPCHK(hipMemsetAsync(W, 0, (size_t)n * ld * sizeof(double), stream));
     hipLaunchKernelGGL(copy_diag_blocks_kernel, dim3(nb), dim3(256), 0, stream, invd, W, ld);
     for (int h = 1; h < nb; h *= 2) {
@@ -1411,7 +1372,7 @@ hipError_t DenseSolver::trtri() {
             t.C = Q + (long)(mid * 128) * ld + lo * 128; t.ldc = ld;
             t.M = M; t.N = N; t.K = N; t.alpha = 1.0; t.beta = 0.0; t.kmode = KMODE_GE_COL;
             t.strideA = t.strideB = t.strideC = pair_stride;
-            if (lpt && (M / 128) * (N / 128) >= 64) { t.tile_map = trtri_tile_order(M / 128, N / 128, 0); t.n_map = t.tile_map ? (M / 128) * (N / 128) : 0; }
+            if ((M / 128) * (N / 128) >= 64) { t.tile_map = trtri_tile_order(M / 128, N / 128, 0); t.n_map = t.tile_map ? (M / 128) * (N / 128) : 0; }
             HIPCHK(gemm_f64(stream, LAY_KC, LAY_XC, t, batch));
             GemmArgs w{};
             w.A = W + (long)(mid * 128) * ld + mid * 128; w.lda = ld;         // W22 (KC), lower-triangular
@@ -1419,7 +1380,7 @@ hipError_t DenseSolver::trtri() {
             w.C = W + (long)(mid * 128) * ld + lo * 128; w.ldc = ld;
             w.M = M; w.N = N; w.K = M; w.alpha = -1.0; w.beta = 0.0; w.kmode = KMODE_LE_ROW;
             w.strideA = w.strideB = w.strideC = pair_stride;
-            if (lpt && (M / 128) * (N / 128) >= 64) { w.tile_map = trtri_tile_order(M / 128, N / 128, 1); w.n_map = w.tile_map ? (M / 128) * (N / 128) : 0; }
+            if ((M / 128) * (N / 128) >= 64) { w.tile_map = trtri_tile_order(M / 128, N / 128, 1); w.n_map = w.tile_map ? (M / 128) * (N / 128) : 0; }
             return gemm_f64(stream, LAY_KC, LAY_XC, w, batch);
         };
         if (full > 0) HIPCHK(merge(0, h, 2 * h, full));
@@ -1445,7 +1406,7 @@ hipError_t DenseSolver::symmetrize(double *M) {
 void DenseSolver::prof_collect() {
     for (size_t i = 0; i + 1 < prof_used; i += 2) {
         float ms = 0;
-        if (hipEventElapsedTime(&ms, prof_ev[i], prof_ev[i + 1]) == hipSuccess) {
+        if (hipEventElapsedTime(&ms, prof_ev[i].get(), prof_ev[i + 1].get()) == hipSuccess) {
             stat_launches += 1.0;
             stat_ms += ms;
             stat_flops += prof_flops[i / 2];
@@ -1453,32 +1414,23 @@ void DenseSolver::prof_collect() {
     }
     prof_used = 0;
     prof_flops.clear();
-    if (flow_timed) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, flow_t0, flow_t1) == hipSuccess) {
-            const double o = flops_order > 0 ? flops_order : (double)nfact;
-            stat_launches += 1.0;
-            stat_ms += ms;
-            stat_flops += o * o * o / 3.0;
-        }
-        flow_timed = false;
+    float ms = 0;
+    if (flow.elapsed_ms(&ms)) {
+        const double o = flops_order > 0 ? flops_order : (double)nfact;
+        stat_launches += 1.0;
+        stat_ms += ms;
+        stat_flops += o * o * o / 3.0;
     }
 }
 
 int DenseSolver::fetch_info() {
     int h = -1;
     if (hipMemcpyAsync(&h, d_info, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess) return -1;
-    int cw[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // cholflow.hip's control words: [1] abort, [4] / [5] flags that the plain poll missed
-    if (flow_ready && hipMemcpyAsync(cw, flow_flags, sizeof(cw), hipMemcpyDeviceToHost, stream) != hipSuccess) return -1;
+    int cw[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // cholflow.hip's control words
+    if (flow.ready() && flow.read_ctrl(cw) != hipSuccess) return -1;
     if (hipStreamSynchronize(stream) != hipSuccess) return -1;
-    const int ab = cw[1];
-    flow_stale_events += cw[4];
-    flow_stale_confirmed += cw[5];
-    flow_rescued += cw[6];
-    if (cw[4] && getenv("JAICOV_VERBOSE"))
-        fprintf(stderr, "jaicov: dataflow factorisation: %d flag(s) found by the read-modify-write poll, %d of them still invisible to the plain poll, %d after more than 1 ms of waiting\n", cw[4], cw[5], cw[6]);
-    if (ab != 0) {            // a wait of the dataflow factorisation ran into its time limit
-        flow_report_stall();
+    if (flow.collect(cw)) {            // a wait of the dataflow factorisation ran into its time limit
+        flow.report_stall();
         return -9;
     }
     return h;

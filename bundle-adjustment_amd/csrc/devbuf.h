@@ -1,0 +1,79 @@
+// Move-only owners of what the HIP runtime hands out: a device allocation, an event, a host-mapped allocation.  Each frees its
+// resource exactly once, in its destructor, so a function may leave through an error return with any of them half acquired.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include <utility>
+
+namespace jaicov {
+
+// One owner for a device allocation that only grows: pointer and element count never get out of step, and the memory is
+// freed exactly once, by the destructor.  hipFree waits for the device by itself, so an owner may go out of scope on an
+// error path with work still in flight; on a success path the caller synchronises its stream first.
+template <typename T>
+class DevBuf {
+    T *ptr_ = nullptr;
+    size_t count_ = 0;
+  public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : ptr_(o.ptr_), count_(o.count_) { o.ptr_ = nullptr; o.count_ = 0; }   // move-only: no copies
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(ptr_, o.ptr_); std::swap(count_, o.count_); return *this; }
+    ~DevBuf() { if (ptr_) hipFree(ptr_); }
+    // room for `count` elements: the allocation at hand if it is large enough, otherwise a new one (the contents are lost)
+    hipError_t reserve(size_t count) {
+        if (count <= count_) return hipSuccess;
+        reset();
+        const hipError_t err = hipMalloc(&ptr_, count * sizeof(T));
+        if (err == hipSuccess) count_ = count; else ptr_ = nullptr;
+        return err;
+    }
+    // the same in FINE-GRAINED device memory (hipExtMallocWithFlags: freed by hipFree like any other); no fallback here
+    hipError_t reserve_finegrained(size_t count) {
+        reset();
+        const hipError_t err = hipExtMallocWithFlags((void **)&ptr_, count * sizeof(T), hipDeviceMallocFinegrained);
+        if (err == hipSuccess) count_ = count; else ptr_ = nullptr;
+        return err;
+    }
+    void reset() { if (ptr_) hipFree(ptr_); ptr_ = nullptr; count_ = 0; }
+    T *get() const { return ptr_; }
+    size_t count() const { return count_; }
+};
+
+class DevEvent {
+    hipEvent_t ev_ = nullptr;
+  public:
+    DevEvent() = default;
+    DevEvent(DevEvent &&o) noexcept : ev_(o.ev_) { o.ev_ = nullptr; }
+    DevEvent &operator=(DevEvent &&o) noexcept { std::swap(ev_, o.ev_); return *this; }
+    ~DevEvent() { reset(); }
+    hipError_t create(unsigned flags = hipEventDefault) {
+        reset();
+        const hipError_t err = hipEventCreateWithFlags(&ev_, flags);
+        if (err != hipSuccess) ev_ = nullptr;
+        return err;
+    }
+    void reset() { if (ev_) hipEventDestroy(ev_); ev_ = nullptr; }
+    hipEvent_t get() const { return ev_; }
+};
+
+// host memory that the device can address (hipHostMallocMapped): words a kernel and the host pass to each other while the kernel runs
+template <typename T>
+class HostMapped {
+    T *ptr_ = nullptr;
+  public:
+    HostMapped() = default;
+    HostMapped(HostMapped &&o) noexcept : ptr_(o.ptr_) { o.ptr_ = nullptr; }
+    HostMapped &operator=(HostMapped &&o) noexcept { std::swap(ptr_, o.ptr_); return *this; }
+    ~HostMapped() { reset(); }
+    hipError_t alloc(size_t count) {
+        reset();
+        const hipError_t err = hipHostMalloc((void **)&ptr_, count * sizeof(T), hipHostMallocMapped);
+        if (err != hipSuccess) ptr_ = nullptr;
+        return err;
+    }
+    void reset() { if (ptr_) hipHostFree(ptr_); ptr_ = nullptr; }
+    T *get() const { return ptr_; }
+};
+
+}  // namespace jaicov

@@ -19,6 +19,7 @@
 #include "create_plan.h"
 #include "datum.h"
 #include "dense.h"
+#include "devbuf.h"
 #include "gemm_f64.h"
 #include "reliability.h"
 #include "transform.h"
@@ -195,30 +196,6 @@ __global__ void store_inv_kernel(const double *__restrict__ Q, long ld, int m, d
     out[(long)i * m + j] = i >= j ? Q[(long)i * ld + j] : Q[(long)j * ld + i];
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// One owner for a device allocation that only grows: pointer and element count never get out of step, and the memory is
-// freed exactly once, by the destructor.  hipFree waits for the device by itself, so an owner may go out of scope on an
-// error path with work still in flight; on a success path the caller synchronises its stream first.
-template <typename T>
-class DevBuf {
-    T *ptr_ = nullptr;
-    size_t count_ = 0;
-  public:
-    DevBuf() = default;
-    DevBuf(DevBuf &&o) noexcept : ptr_(o.ptr_), count_(o.count_) { o.ptr_ = nullptr; o.count_ = 0; }   // move-only: no copies, no assignment
-    ~DevBuf() { if (ptr_) hipFree(ptr_); }
-    // room for `count` elements: the allocation at hand if it is large enough, otherwise a new one (the contents are lost)
-    hipError_t reserve(size_t count) {
-        if (count <= count_) return hipSuccess;
-        if (ptr_) hipFree(ptr_);
-        ptr_ = nullptr; count_ = 0;
-        const hipError_t err = hipMalloc(&ptr_, count * sizeof(T));
-        if (err == hipSuccess) count_ = count; else ptr_ = nullptr;
-        return err;
-    }
-    T *get() const { return ptr_; }
-};
-
 struct jaicov_engine {
     std::string err = "";
     int device = 0;
@@ -229,7 +206,8 @@ struct jaicov_engine {
     DevBuf<double> refP;       // partial-sum table of the refinement's residual
     double last_refine_correction = 0.0;   // max |correction| / max |dx| of the last refinement step (diagnostics)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // assembly: camera-side kernels on a side stream (assemble.hip)
-    hipStream_t stream = nullptr;
+    StreamLease stream_lease;   // the engine's stream ...
+    hipStream_t stream = nullptr;   // ... as every launch names it
     DevProblem p{};
     std::vector<void *> allocs;
     // host copies
@@ -421,14 +399,14 @@ static int invert_dispersions(jaicov_engine *e, std::vector<DispItem> &items) {
     const auto t_all = std::chrono::steady_clock::now();
     double up_ms = 0.0;
     std::stable_sort(items.begin(), items.end(), [](const DispItem &a, const DispItem &b) { return (a.m + 127) / 128 < (b.m + 127) / 128; });
-    hipStream_t cstream = nullptr;
-    cstream = jaicov::stream_acquire(jaicov::STREAM_PLAIN);
+    StreamLease copy_lease(jaicov::STREAM_PLAIN);      // (goes back to the pool, synchronised, on every way out; so do the events)
+    const hipStream_t cstream = copy_lease.get();
     if (!cstream) FAIL(e, JAICOV_ERR_DEVICE, "no stream for the dispersion uploads");
-    hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
+    DevEvent ev_up[2], ev_free[2];
     int status = JAICOV_OK;
     std::string msg;
-    for (int b = 0; b < 2 && status == JAICOV_OK; b++)      // (no early return from here on: the stream goes back to the pool and the events are destroyed below)
-        if (hipEventCreateWithFlags(&ev_up[b], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ev_free[b], hipEventDisableTiming) != hipSuccess) {
+    for (int b = 0; b < 2 && status == JAICOV_OK; b++)
+        if (ev_up[b].create(hipEventDisableTiming) != hipSuccess || ev_free[b].create(hipEventDisableTiming) != hipSuccess) {
             status = JAICOV_ERR_DEVICE; msg = "inversion of the dispersion matrices: no events";
         }
     for (size_t g0 = 0; g0 < items.size() && status == JAICOV_OK;) {
@@ -459,18 +437,18 @@ static int invert_dispersions(jaicov_engine *e, std::vector<DispItem> &items) {
         }
         for (int c = 0; he == hipSuccess && c * cap < count; c++) {
             const int b = c & 1, first = c * cap, cnt = std::min(cap, count - first);
-            if (c >= 2) he = hipStreamWaitEvent(cstream, ev_free[b], 0);      // the load kernel of chunk c - 2 has consumed this buffer
+            if (c >= 2) he = hipStreamWaitEvent(cstream, ev_free[b].get(), 0);      // the load kernel of chunk c - 2 has consumed this buffer
             const auto t_up = std::chrono::steady_clock::now();
             for (int t = 0; t < cnt && he == hipSuccess; t++) {
                 const DispItem &it = items[g0 + first + t];
                 he = hipMemcpyAsync(d_stage[b] + (size_t)t * mm, it.host, (size_t)it.m * it.m * sizeof(double), hipMemcpyHostToDevice, cstream);
             }
             up_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_up).count();
-            if (he == hipSuccess) he = hipEventRecord(ev_up[b], cstream);
-            if (he == hipSuccess) he = hipStreamWaitEvent(e->stream, ev_up[b], 0);
+            if (he == hipSuccess) he = hipEventRecord(ev_up[b].get(), cstream);
+            if (he == hipSuccess) he = hipStreamWaitEvent(e->stream, ev_up[b].get(), 0);
             if (he != hipSuccess) break;
             hipLaunchKernelGGL(load_disp_batched_kernel, dim3((mp + 255) / 256, mp, cnt), dim3(256), 0, e->stream, d_desc + first, bi.Lb, bi.refine ? bi.Db : (double *)nullptr, bi.ld, bi.msz, mp);
-            he = hipEventRecord(ev_free[b], e->stream);
+            he = hipEventRecord(ev_free[b].get(), e->stream);
             if (he == hipSuccess) he = bi.run(cnt);
             if (he != hipSuccess) break;
             hipLaunchKernelGGL(store_inv_batched_kernel, dim3((mmax + 255) / 256, mmax, cnt), dim3(256), 0, e->stream, d_desc + first, bi.Qb, bi.ld, bi.msz);
@@ -485,8 +463,6 @@ static int invert_dispersions(jaicov_engine *e, std::vector<DispItem> &items) {
         else if (info != 0) { status = JAICOV_ERR_SINGULAR; msg = "dispersion matrix is not positive definite (MatrixNotSPDException, DOPG:85-86)"; }
         g0 = g1;
     }
-    for (int b = 0; b < 2; b++) { if (ev_up[b]) hipEventDestroy(ev_up[b]); if (ev_free[b]) hipEventDestroy(ev_free[b]); }
-    jaicov::stream_release(jaicov::STREAM_PLAIN, cstream);
     e->create_ms[1] = up_ms;
     e->create_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_all).count();
     if (status != JAICOV_OK) FAIL(e, status, msg);
@@ -512,14 +488,15 @@ extern "C" void jaicov_neq_destroy(jaicov_engine *e) {
         if (evt) hipEventDestroy(evt);
     for (hipEvent_t evt : {e->ev_fork, e->ev_join, e->ev_first, e->ev_all, e->ev_r0, e->ev_r1})
         if (evt) hipEventDestroy(evt);
-    jaicov::stream_release(jaicov::STREAM_PLAIN, e->stream);
+    e->stream_lease = StreamLease();
     delete e;
 }
 
 // ---- engine creation, second stage: what happens on the device.  The first stage, every decision and table that needs
 //      no device, is the plan (create_plan.h); each function here takes the engine and the finished plan. ---------------------
 static int acquire_stream_and_events(jaicov_engine *e) {
-    e->stream = jaicov::stream_acquire(jaicov::STREAM_PLAIN);
+    e->stream_lease = StreamLease(jaicov::STREAM_PLAIN);
+    e->stream = e->stream_lease.get();
     if (!e->stream) FAIL(e, JAICOV_ERR_DEVICE, "no stream");
     for (auto &evt : e->ev) HIPE(e, hipEventCreate(&evt));
     HIPE(e, hipEventCreateWithFlags(&e->ev_first, hipEventDisableTiming));
@@ -1219,7 +1196,7 @@ struct Solve {
     // about once in 1 000 factorisations at config 4 -- is repeated; N, V and the datum rows are untouched by it)
     int factor_and_substitute() {
         const int nrhs = d + 1;
-        const bool fused = slv.flow_ready;
+        const bool fused = slv.flow.ready();
         const int c1 = std::min(slv.first_panel_cols(), Up);
         int info = 0;
         for (int attempt = 0;; attempt++) {
@@ -1237,7 +1214,7 @@ struct Solve {
                 hipLaunchKernelGGL(scale_copy_kernel, dim3((Up - c1 + 255) / 256, Up), dim3(256), 0, e->stream, e->d_N, (long)Upad, slv.L,
                                    ld, U, Up, d, e->d_V, e->d_B, Upad, c1, Up);
             HIPE(e, hipEventRecord(e->ev_all, e->stream));
-            if (fused) slv.flow_set_source(e->d_N, (long)Upad, e->d_V, e->d_B, Upad, d, U);
+            if (fused) slv.flow.set_source(e->d_N, (long)Upad, e->d_V, e->d_B, Upad, d, U);
             HIPE(e, slv.potrf(e->ev_first, e->ev_all));
             HIPE(e, hipEventRecord(e->ev[5], e->stream));
             HIPE(e, slv.backsolve_aug(e->d_G, vs, nrhs));           // G <- L^-T (L^-1 Y)   (row 0: y~, rows 1..d: G^)
@@ -1733,9 +1710,10 @@ extern "C" int jaicov_neq_kernel_stats(jaicov_engine *e, double *stats, int32_t 
     if (n >= 6) { stats[3] = e->dm_stat_passes; stats[4] = e->dm_stat_ms; stats[5] = e->dm_stat_flops; }
     if (n >= 10) {   // health of the dataflow factorisation since create (never reset): see jaicov_neq.h
         stats[6] = (double)e->flow_retries;
-        stats[7] = (double)(e->solver.flow_stale_events + e->solverS.flow_stale_events);
-        stats[8] = (double)(e->solver.flow_stale_confirmed + e->solverS.flow_stale_confirmed);
-        stats[9] = (double)(e->solver.flow_rescued + e->solverS.flow_rescued);
+        const FlowCounters &c = e->solver.flow.counters(), &cS = e->solverS.flow.counters();
+        stats[7] = (double)(c.stale_events + cS.stale_events);
+        stats[8] = (double)(c.stale_confirmed + cS.stale_confirmed);
+        stats[9] = (double)(c.rescued + cS.rescued);
     }
     if (n >= 11) stats[10] = e->last_refine_correction;
     if (n >= 12) stats[11] = (double)e->refine_steps;      // refinement steps per solve the engine actually runs (option `refinement`, clamped)
@@ -2039,7 +2017,7 @@ extern "C" int jaicov_debug_potrf_bench(int n, int reps, double *ms_out, long lo
     hipEventCreate(&e0); hipEventCreate(&e1);
     do {
         if (ds.init(s, n, false, true) != hipSuccess) { status = JAICOV_ERR_OUT_OF_MEMORY; break; }
-        if (trace_out && ds.flow_ready) ds.flow_enable_trace(true);
+        if (trace_out && ds.flow.ready()) ds.flow.enable_trace(true);
         for (int r = 0; r < reps; r++) {
             hipLaunchKernelGGL(fill_spd_kernel, dim3((ds.n + 255) / 256, ds.n), dim3(256), 0, s, ds.L, ds.ld, ds.n, n);
             hipEventRecord(e0, s);
@@ -2047,18 +2025,18 @@ extern "C" int jaicov_debug_potrf_bench(int n, int reps, double *ms_out, long lo
             if (pe != hipSuccess) { fprintf(stderr, "potrf: %s\n", hipGetErrorString(pe)); status = JAICOV_ERR_DEVICE; break; }
             hipEventRecord(e1, s);
             const int info = ds.fetch_info();
-            if (info < 0) fprintf(stderr, "potrf: info %d (flow_ready %d)\n", info, (int)ds.flow_ready);
+            if (info < 0) fprintf(stderr, "potrf: info %d (flow_ready %d)\n", info, (int)ds.flow.ready());
             float ms = 0;
             hipEventElapsedTime(&ms, e0, e1);
             ms_out[r] = ms;
             if (info < 0) { status = JAICOV_ERR_DEVICE; break; }
             if (info != 0) { status = JAICOV_ERR_SINGULAR; break; }
         }
-        if (status == JAICOV_OK && trace_out && ds.flow_trace) {
-            const long long cnt = std::min<long long>(trace_cap, ((long long)ds.flow_tasks + n / 128) * 8);   // per task, then per block column (chain kernel)
-            hipMemcpy(trace_out, ds.flow_trace, (size_t)cnt * sizeof(long long), hipMemcpyDeviceToHost);
+        if (status == JAICOV_OK && trace_out && ds.flow.trace()) {
+            const long long cnt = std::min<long long>(trace_cap, (long long)ds.flow.trace_words());   // per task, then per block column (chain kernel)
+            hipMemcpy(trace_out, ds.flow.trace(), (size_t)cnt * sizeof(long long), hipMemcpyDeviceToHost);
         }
-        if (tasks_out) *tasks_out = ds.flow_ready ? ds.flow_tasks : 0;
+        if (tasks_out) *tasks_out = ds.flow.ready() ? ds.flow.n_tasks() : 0;
     } while (0);
     hipStreamSynchronize(s);
     ds.release();

@@ -166,3 +166,103 @@ def test_split_update_ranges_keep_the_list_complete_and_deadlock_free(nb, form, 
     assert r.done[low].all()
     want = np.tile(np.arange(nb), (rows, 1))
     assert (r.updates[low] == want[low]).all()
+
+
+def layout(nb, rows, partials):
+    lib = engine.load_library()
+    lib.jaicov_debug_flow_layout.argtypes = [C.c_int] * 3 + [C.c_void_p]
+    out = np.zeros(8, np.int64)
+    max_grid = lib.jaicov_debug_flow_layout(nb, rows, partials, out.ctypes.data)
+    assert max_grid > 0
+    return [int(x) for x in out], max_grid
+
+
+def default_split_partials(nb, rows):
+    lib = engine.load_library()
+    m, frm = C.c_int(0), C.c_int(0)
+    lib.jaicov_debug_flow_split(nb, C.byref(m), C.byref(frm))
+    t = tasks(nb, rows, 1, 1, 0, m.value, frm.value)
+    return int(((t[:, 3] & PART) != 0).sum())        # two pieces: one partial-sum buffer per split task
+
+
+def test_flag_layout_is_one_disjoint_cover_and_matches_the_kernels_arithmetic(monkeypatch):
+    """The flag words of the dataflow factorisation (cholflow.h, FlowLayout): the host fills the kernel's pointers, sizes and clears the
+    allocation and reads the stall report from ONE layout.  Its offsets are those the factorisation has always used (written out here)."""
+    monkeypatch.delenv("JAICOV_FLOW_SPLIT", raising=False)
+    p118 = default_split_partials(118, 119)
+    assert p118 > 0
+    CTRL = 16
+    for nb, rows, p in [(1, 2, 0), (24, 25, 0), (118, 119, p118)]:
+        (done, applied, diag_ready, factored, wgstate, wgsnap, pflag, total), max_grid = layout(nb, rows, p)
+        sizes = [rows * nb, rows * nb, nb, nb, max_grid, max_grid, p]
+        starts = [done, applied, diag_ready, factored, wgstate, wgsnap, pflag]
+        # the regions follow the control words, in order, without gap or overlap, and end at the total
+        assert done == CTRL
+        for q in range(7):
+            assert starts[q] + sizes[q] == (starts[q + 1] if q < 6 else total), (nb, q)
+        # the offsets the factorisation used before there was a layout
+        assert done == 16
+        assert applied == 16 + rows * nb
+        assert diag_ready == 16 + 2 * rows * nb
+        assert factored == 16 + 2 * rows * nb + nb
+        assert wgstate == 16 + 2 * rows * nb + 2 * nb
+        assert pflag == 16 + 2 * rows * nb + 2 * nb + 2048
+        assert total == 16 + 2 * rows * nb + 2 * nb + 2048 + p
+        # the snapshot of the state words (flow_give_up) lies FLOW_MAX_GRID words after them
+        assert wgsnap == wgstate + max_grid and max_grid == 1024
+
+
+HOOKS = ["JAICOV_FACTOR_FORM", "JAICOV_FLOW_MIN_BLOCKS", "JAICOV_FLOW_SPLIT", "JAICOV_FLOW_TIMEOUT_MS", "JAICOV_FLOW_TRACE_ON",
+         "JAICOV_CHAIN8_MIN_NB", "JAICOV_CHAIN_TRACE", "JAICOV_VERBOSE"]
+NO_SPLIT = (1, 1 << 30)
+# (form hook, block columns, kernels overlap) -> (dataflow, one kernel, chain form, third chain workgroup, split pieces, first split column)
+DECISIONS = [
+    (None, 6, True, (0, 0, 0, 0) + NO_SPLIT),            # below 12 block columns: the stream-scheduled factorisation
+    (None, 11, True, (0, 0, 0, 0) + NO_SPLIT),
+    (None, 12, True, (1, 0, 1, 2) + NO_SPLIT),           # chain form, third chain workgroup below 80 block columns
+    (None, 29, True, (1, 0, 1, 2) + NO_SPLIT),
+    (None, 79, True, (1, 0, 1, 2) + NO_SPLIT),
+    (None, 80, True, (1, 0, 1, 0, 2, 40)),               # from 80 on: two chain workgroups, update ranges split from the middle column on
+    (None, 118, True, (1, 0, 1, 0, 2, 59)),
+    ("streams", 29, True, (0, 0, 0, 0) + NO_SPLIT),
+    ("streams", 118, True, (0, 0, 0, 0, 2, 59)),
+    ("two_step", 29, True, (1, 0, 0, 0) + NO_SPLIT),
+    ("two_step", 118, True, (1, 0, 0, 0, 2, 59)),
+    ("one_kernel", 29, True, (1, 1, 0, 0) + NO_SPLIT),
+    ("chain2", 29, True, (1, 0, 1, 0) + NO_SPLIT),
+    ("chain3", 29, True, (1, 0, 1, 2) + NO_SPLIT),
+    ("chain3", 118, True, (1, 0, 1, 2, 2, 59)),
+    (None, 29, False, (1, 1, 0, 0) + NO_SPLIT),          # kernels cannot run side by side: one kernel, whatever the form
+    (None, 118, False, (1, 1, 0, 0, 2, 59)),
+    ("chain3", 29, False, (1, 1, 0, 0) + NO_SPLIT),
+    (None, 6, False, (0, 0, 0, 0) + NO_SPLIT),
+]
+
+
+@pytest.mark.parametrize("form,nb,overlap,want", DECISIONS)
+def test_the_form_of_the_factorisation_is_decided_in_one_place(monkeypatch, form, nb, overlap, want):
+    """Which factorisation a solver uses (cholflow.h, flow_decide): the first four columns are what the solver did when the rule was spread
+    over DenseSolver::init and flow_init (zeros where it never got as far as asking, the stream-scheduled form); the last two are the split
+    rule, which was a function of the block columns and its hook alone (flow_split_rule behind jaicov_debug_flow_split), whatever the form."""
+    for h in HOOKS:
+        monkeypatch.delenv(h, raising=False)
+    if form is not None:
+        monkeypatch.setenv("JAICOV_FACTOR_FORM", form)
+    lib = engine.load_library()
+    out = (C.c_int * 6)()
+    lib.jaicov_debug_flow_decision(nb, int(overlap), out)
+    assert tuple(out) == want
+
+
+def test_the_hooks_reach_the_decision(monkeypatch):
+    for h in HOOKS:
+        monkeypatch.delenv(h, raising=False)
+    lib = engine.load_library()
+    out = (C.c_int * 6)()
+    monkeypatch.setenv("JAICOV_FLOW_MIN_BLOCKS", "1")
+    monkeypatch.setenv("JAICOV_FLOW_SPLIT", "3:30")
+    lib.jaicov_debug_flow_decision(6, 1, out)
+    assert tuple(out) == (1, 0, 1, 2, 3, 30)
+    monkeypatch.setenv("JAICOV_FLOW_SPLIT", "0")         # fewer than one piece: one
+    lib.jaicov_debug_flow_decision(6, 1, out)
+    assert tuple(out) == (1, 0, 1, 2, 1, 0)
