@@ -1,5 +1,6 @@
 """ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` / ``include/jaicov_transform.h`` /
-``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_datum.h`` (``csrc/libjaicov_neq.so``).
+``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_datum.h`` / ``include/jaicov_intersect.h``
+(``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
 library has not been built, and every call fails with ``EngineError`` when no gfx950 device is present.
@@ -50,6 +51,9 @@ DATUM_EXPORTS = ["jaicov_datum_transform", "jaicov_datum_apply"]
 DLT_IDENTICAL_PRINCIPLE_DISTANCE, DLT_ROTATION_WITHOUT_SHEAR, DLT_FIXED_PRINCIPLE_DISTANCE_X, DLT_FIXED_PRINCIPLE_DISTANCE_Y, \
     DLT_FIXED_PRINCIPAL_POINT_X, DLT_FIXED_PRINCIPAL_POINT_Y = range(6)
 DLT_CONVERGED, DLT_NOT_CONVERGED, DLT_TOO_FEW_POINTS, DLT_SINGULAR, DLT_NOT_FINITE = range(5)
+# include/jaicov_intersect.h: forward intersection of a batch of object points from oriented images (stand-alone, no engine)
+ISECT_EXPORTS = ["jaicov_isect_points"]
+ISECT_OK, ISECT_NOT_CONVERGED, ISECT_TOO_FEW_RAYS, ISECT_SINGULAR, ISECT_NOT_FINITE = range(5)
 
 KROW = 32  # 12 + JAICOV_MAX_DIST_PER_CAMERA
 INVERT_NONE, INVERT_FULL, INVERT_REDUCED = 0, 1, 2   # MatrixInversion (BundleAdjustment.java:65-70)
@@ -156,6 +160,8 @@ def load_library():
     L.jaicov_datum_transform.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int32]
     L.jaicov_datum_apply.argtypes = [vp, _pd, _pd, C.c_int32]
     L.jaicov_dlt_adjust.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pi, C.c_int32, C.c_int32, _pd, _pi, _pi, _pd]
+    L.jaicov_isect_points.argtypes = [C.c_int32, _pi, _pi, _pd, _pd, C.c_int32, _pd, _pd, C.c_double, C.c_int32, C.c_double, C.c_int32,
+                                      _pd, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
     _LIB = L
     return L
 
@@ -488,6 +494,55 @@ def dlt_adjust(obs_begin, xy, xyz, io, io_fixed=None, restrictions=(), max_itera
     if rc != 0:
         raise EngineError(rc, "dlt adjust")
     return (out, status, solves, float(ms[0])) if with_time else (out, status, solves)
+
+
+def intersect_points(ray_begin, ray_image, xy, var, image_io, image_eo, sigma2apriori=1.0, max_iterations=50, reject_threshold=0.0,
+                     min_rays=3, with_time=False):
+    """Forward intersection of every point of a batch from its image rays (include/jaicov_intersect.h).  ray_begin: (n + 1,) CSR
+    offsets of the points' rays; ray_image: (n_rays,) image of each ray; xy: (n_rays, 2); var: (n_rays, 3) var_x, var_y, rho or None
+    (unit weights); image_io: (n_images, 3) x0, y0, c of each image's camera; image_eo: (n_images, 6).  Returns (out (n, 11): X, Y, Z,
+    qXX, qXY, qXZ, qYY, qYZ, qZZ, Omega, largest angle; status (n,); iterations (n,); ray_used (n_rays,); ray_q (n_rays,)), plus the
+    kernel time in ms with with_time."""
+    L = load_library()
+    rb = np.ascontiguousarray(ray_begin, np.int32).ravel()
+    n = rb.size - 1
+    ri = np.ascontiguousarray(ray_image, np.int32).ravel()
+    xy = np.ascontiguousarray(xy, np.float64).reshape(-1)
+    var = None if var is None else np.ascontiguousarray(var, np.float64).reshape(-1)
+    io = np.ascontiguousarray(image_io, np.float64).reshape(-1)
+    eo = np.ascontiguousarray(image_eo, np.float64).reshape(-1)
+    if io.size % 3 or eo.size != 2 * io.size or 2 * ri.size != xy.size or (var is not None and 3 * ri.size != var.size) or \
+            (n >= 0 and rb.size and rb[-1] != ri.size):
+        raise EngineError(-1, "intersect points: array sizes do not agree")
+    out = np.zeros((max(n, 0), 11)); status = np.zeros(max(n, 0), np.int32); iterations = np.zeros(max(n, 0), np.int32)
+    used = np.zeros(ri.size, np.uint8); q = np.zeros(ri.size)
+    ms = np.zeros(1)
+    rc = L.jaicov_isect_points(n, rb.ctypes.data_as(_pi), ri.ctypes.data_as(_pi), _p(xy), _p(var) if var is not None else C.cast(None, _pd),
+                               io.size // 3, _p(io), _p(eo), float(sigma2apriori), int(max_iterations), float(reject_threshold),
+                               int(min_rays), _p(out), status.ctypes.data_as(_pi), iterations.ctypes.data_as(_pi),
+                               used.ctypes.data_as(C.POINTER(C.c_uint8)), _p(q), _p(ms))
+    if rc != 0:
+        raise EngineError(rc, "intersect points")
+    return (out, status, iterations, used, q) + ((float(ms[0]),) if with_time else ())
+
+
+def intersect_problem(fp: FlatProblem, values=None, with_status=False, **kw):
+    """Start values of a FlatProblem's object points by forward intersection: the rays of every point are its image points in the
+    problem's order (a stable sort of ip_point) with their ip_var_x, ip_var_y, ip_rho; interior and exterior orientation come from
+    the slot vector `values` (default fp.values).  Returns the slot vector with every intersected point replaced (a point whose status
+    is TOO_FEW_RAYS, SINGULAR or NOT_FINITE keeps its value); with_status also (out, status).  kw: as intersect_points
+    (sigma2apriori defaults to the problem's)."""
+    v = np.array(fp.values if values is None else values, np.float64)
+    order = np.argsort(fp.ip_point, kind="stable")
+    begin = np.concatenate([[0], np.cumsum(np.bincount(fp.ip_point, minlength=fp.n_points))]).astype(np.int32)
+    io = v[3 * fp.n_points:3 * fp.n_points + 3 * fp.n_cameras].reshape(-1, 3)[fp.image_camera]
+    eo = v[fp.slot_eo(0):].reshape(-1, 6)
+    var = np.stack([fp.ip_var_x, fp.ip_var_y, fp.ip_rho], 1)[order]
+    kw.setdefault("sigma2apriori", fp.sigma2apriori)
+    out, status, _, _, _ = intersect_points(begin, fp.ip_image[order], np.stack([fp.ip_x, fp.ip_y], 1)[order], var, io, eo, **kw)
+    ok = status <= ISECT_NOT_CONVERGED
+    v[:3 * fp.n_points].reshape(-1, 3)[ok] = out[ok, :3]
+    return (v, out, status) if with_status else v
 
 
 def dense_gemm(alay, blay, A, B, C_in, M, N, K, alpha=1.0, beta=0.0, lower_only=False, kmode=0, repeats=0):

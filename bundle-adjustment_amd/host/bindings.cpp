@@ -246,6 +246,18 @@ PYBIND11_MODULE(_jaicov_host, m) {
         .def_static("applyExteriorOrientation", &DirectLinearTransformation::applyExteriorOrientation)
         .def_static("setMaximalNumberOfIterations", &DirectLinearTransformation::setMaximalNumberOfIterations);
 
+    py::class_<ForwardIntersection> isect(m, "ForwardIntersection");
+    py::class_<ForwardIntersection::Result>(isect, "Result")
+        .def_property_readonly("point", [](ForwardIntersection::Result &r) { return r.point; }, py::return_value_policy::reference)
+        .def_readonly("status", &ForwardIntersection::Result::status)
+        .def_readonly("iterations", &ForwardIntersection::Result::iterations)
+        .def_readonly("rays", &ForwardIntersection::Result::rays)
+        .def_readonly("raysUsed", &ForwardIntersection::Result::raysUsed)
+        .def("values", [](ForwardIntersection::Result &r) { return std::vector<double>(r.values, r.values + JAICOV_ISECT_OUT_PER_POINT); });
+    isect.def_static("intersectAll", &ForwardIntersection::intersectAll, py::arg("cameras"), py::arg("sigma2apriori") = 1.0,
+                     py::arg("rejectThreshold") = 0.0, py::arg("minRays") = 3, py::return_value_policy::move)
+        .def_static("setMaximalNumberOfIterations", &ForwardIntersection::setMaximalNumberOfIterations);
+
     py::class_<AiconProject>(m, "AiconProject")
         .def_property_readonly("camera", [](AiconProject &p) { return p.camera ? p.camera.get() : (p.cameras.empty() ? nullptr : p.cameras[0].get()); },
                                py::return_value_policy::reference_internal)

@@ -627,4 +627,68 @@ void DirectLinearTransformation::applyExteriorOrientation(DLTCoefficients &coeff
     eo.get(ParameterType::CAMERA_KAPPA).setValue(kappa);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// ForwardIntersection (include/jaicov_intersect.h) on the device
+// ---------------------------------------------------------------------------------------------------------------
+std::vector<ForwardIntersection::Result> ForwardIntersection::intersectAll(const std::vector<Camera *> &cameras, double sigma2apriori,
+                                                                           double rejectThreshold, int minRays) {
+    struct Ray { int image; ImageCoordinate *ic; };
+    std::vector<ObjectCoordinate *> points;                               // first-seen order
+    std::unordered_map<ObjectCoordinate *, size_t> indexOf;
+    std::vector<std::vector<Ray>> rays;
+    std::vector<double> io, eo;
+    int n_images = 0;
+    for (Camera *cam : cameras) {
+        InteriorOrientation &ior = cam->getInteriorOrientation();
+        for (auto &im : cam->images()) {
+            for (int k = 0; k < 3; k++) io.push_back(ior.at(k)->getValue());
+            for (int k = 0; k < 6; k++) eo.push_back(im->getExteriorOrientation().at(k)->getValue());
+            for (auto &ic : im->coordinates()) {
+                ObjectCoordinate *oc = ic->getObjectCoordinate();
+                auto it = indexOf.find(oc);
+                if (it == indexOf.end()) {
+                    it = indexOf.emplace(oc, points.size()).first;
+                    points.push_back(oc);
+                    rays.emplace_back();
+                }
+                rays[it->second].push_back({n_images, ic.get()});
+            }
+            n_images++;
+        }
+    }
+    const int n = (int)points.size();
+    std::vector<int32_t> begin(1, 0), image;
+    std::vector<double> xy, var;
+    for (auto &rs : rays) {
+        for (const Ray &r : rs) {
+            image.push_back(r.image);
+            xy.push_back(r.ic->getX().getValue()); xy.push_back(r.ic->getY().getValue());
+            var.push_back(r.ic->getX().getVariance()); var.push_back(r.ic->getY().getVariance());
+            var.push_back(r.ic->getCorrelationCoefficientXY());
+        }
+        begin.push_back((int32_t)image.size());
+    }
+    std::vector<double> out((size_t)JAICOV_ISECT_OUT_PER_POINT * n);
+    std::vector<int32_t> status(n), iterations(n);
+    std::vector<uint8_t> used(image.size());
+    const int rc = jaicov_isect_points(n, begin.data(), image.data(), xy.data(), var.data(), n_images, io.data(), eo.data(), sigma2apriori,
+                                       maximalNumberOfIterations_, rejectThreshold, minRays, out.data(), status.data(), iterations.data(),
+                                       used.data(), nullptr, nullptr);
+    if (rc != JAICOV_OK) throw std::runtime_error("jaicov_isect_points failed with status " + std::to_string(rc));
+    std::vector<Result> res(n);
+    for (int p = 0; p < n; p++) {
+        Result &r = res[p];
+        r.point = points[p];
+        r.status = status[p];
+        r.iterations = iterations[p];
+        r.rays = begin[p + 1] - begin[p];
+        for (int k = begin[p]; k < begin[p + 1]; k++) r.raysUsed += used[k];
+        for (int k = 0; k < JAICOV_ISECT_OUT_PER_POINT; k++) r.values[k] = out[(size_t)JAICOV_ISECT_OUT_PER_POINT * p + k];
+        if (r.status == JAICOV_ISECT_OK || r.status == JAICOV_ISECT_NOT_CONVERGED) {
+            r.point->getX().setValue(r.values[0]); r.point->getY().setValue(r.values[1]); r.point->getZ().setValue(r.values[2]);
+        }
+    }
+    return res;
+}
+
 }  // namespace jaicov::host

@@ -28,6 +28,7 @@
 #include "../../include/jaicov_neq.h"
 #include "../../include/jaicov_transform.h"
 #include "../../include/jaicov_dlt.h"
+#include "../../include/jaicov_intersect.h"
 #include "../../include/jaicov_reliability.h"
 #include "../../include/jaicov_datum.h"
 
@@ -643,6 +644,28 @@ public:
     static void setMaximalNumberOfIterations(int n) { maximalNumberOfIterations_ = n; }
 private:
     static inline int maximalNumberOfIterations_ = 5000;     // DefaultValue.getMaximalNumberOfIterations()
+};
+
+// Spatial forward intersection of object points from oriented images on the device (include/jaicov_intersect.h).  The reference has no
+// counterpart: it reads the start values of its object points from a file.  intersectAll() makes one device call for every
+// ObjectCoordinate that an image of `cameras` observes.  The points come in first-seen order (cameras, their images, each image's
+// coordinates: the order in which BA:667-782 numbers them); a point's rays are its image coordinates in that same order, with their
+// variances and correlation coefficient; interior and exterior orientation are the cameras' and images' current values (no distortion).
+// X, Y, Z are written into every point whose status is JAICOV_ISECT_OK or JAICOV_ISECT_NOT_CONVERGED; the other points keep their values.
+// A device error (no GPU, out of memory) throws std::runtime_error.
+class ForwardIntersection {
+public:
+    struct Result {
+        ObjectCoordinate *point = nullptr;
+        int status = -1, iterations = 0, rays = 0, raysUsed = 0;
+        double values[JAICOV_ISECT_OUT_PER_POINT] = {};      // X, Y, Z, qXX, qXY, qXZ, qYY, qYZ, qZZ, Omega, largest angle
+    };
+    static std::vector<Result> intersectAll(const std::vector<Camera *> &cameras, double sigma2apriori = 1.0, double rejectThreshold = 0.0,
+                                            int minRays = 3);
+    static int getMaximalNumberOfIterations() { return maximalNumberOfIterations_; }
+    static void setMaximalNumberOfIterations(int n) { maximalNumberOfIterations_ = n; }
+private:
+    static inline int maximalNumberOfIterations_ = 50;
 };
 
 }  // namespace jaicov::host

@@ -1,6 +1,6 @@
 /*
  * JNI shim between NativeNormalEquationEngine (Java) and the C ABI of include/jaicov_neq.h, include/jaicov_transform.h,
- * include/jaicov_dlt.h, include/jaicov_reliability.h and include/jaicov_datum.h.
+ * include/jaicov_dlt.h, include/jaicov_reliability.h, include/jaicov_datum.h and include/jaicov_intersect.h.
  * The build image has no JDK, so this file is not built by __graft_entry__.build(); on a box with a JDK:
  *   gcc -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -I../../include jaicov_jni.c \
  *       -L../../bundle-adjustment_amd/csrc -ljaicov_neq -o libjaicov_jni.so
@@ -22,6 +22,7 @@
 #include "jaicov_neq.h"
 #include "jaicov_transform.h"
 #include "jaicov_dlt.h"
+#include "jaicov_intersect.h"
 #include "jaicov_reliability.h"
 #include "jaicov_datum.h"
 
@@ -629,5 +630,69 @@ JNIEXPORT jint JNICALL NAT(dltAdjust)(JNIEnv *e, jclass k, jintArray obsBegin, j
     if (pxyz) (*e)->ReleaseDoubleArrayElements(e, xyz, pxyz, JNI_ABORT);
     if (pxy) (*e)->ReleaseDoubleArrayElements(e, xy, pxy, JNI_ABORT);
     (*e)->ReleaseIntArrayElements(e, obsBegin, pb, JNI_ABORT);
+    return rc;
+}
+
+/* --- include/jaicov_intersect.h: forward intersection of a batch of object points (no engine) ----------------------------------- */
+/* inputs through Get<Type>ArrayElements copies (JNI_ABORT); var, iterations, rayUsed and rayQ may be null; status, iterations and
+ * rayUsed come back through long[] as for the DLT. */
+JNIEXPORT jint JNICALL NAT(isectPoints)(JNIEnv *e, jclass k, jintArray rayBegin, jintArray rayImage, jdoubleArray xy, jdoubleArray var,
+                                        jint nImages, jdoubleArray imageIo, jdoubleArray imageEo, jdouble sigma2apriori, jint maxIterations,
+                                        jdouble rejectThreshold, jint minRays, jdoubleArray out, jlongArray status, jlongArray iterations,
+                                        jlongArray rayUsed, jdoubleArray rayQ) {
+    (void)k;
+    const jsize nb = (*e)->GetArrayLength(e, rayBegin);
+    if (nb < 1 || nImages < 0) return JAICOV_ERR_BAD_ARGUMENT;
+    const jsize n = nb - 1;
+    if ((*e)->GetArrayLength(e, imageIo) < 3 * nImages || (*e)->GetArrayLength(e, imageEo) < 6 * nImages ||
+        (*e)->GetArrayLength(e, out) < JAICOV_ISECT_OUT_PER_POINT * n || (*e)->GetArrayLength(e, status) < n ||
+        (iterations && (*e)->GetArrayLength(e, iterations) < n))
+        return JAICOV_ERR_BAD_ARGUMENT;
+    jint *pb = (*e)->GetIntArrayElements(e, rayBegin, NULL);
+    if (!pb) return JAICOV_ERR_OUT_OF_MEMORY;
+    const jint nr = pb[n];
+    if (nr < 0 || (*e)->GetArrayLength(e, rayImage) < nr || (*e)->GetArrayLength(e, xy) < 2 * nr ||
+        (var && (*e)->GetArrayLength(e, var) < 3 * nr) || (rayUsed && (*e)->GetArrayLength(e, rayUsed) < nr) ||
+        (rayQ && (*e)->GetArrayLength(e, rayQ) < nr)) {
+        (*e)->ReleaseIntArrayElements(e, rayBegin, pb, JNI_ABORT);
+        return JAICOV_ERR_BAD_ARGUMENT;
+    }
+    jint *pi = (*e)->GetIntArrayElements(e, rayImage, NULL);
+    jdouble *pxy = pi ? (*e)->GetDoubleArrayElements(e, xy, NULL) : NULL;
+    jdouble *pvar = (pxy && var) ? (*e)->GetDoubleArrayElements(e, var, NULL) : NULL;
+    jdouble *pio = pxy ? (*e)->GetDoubleArrayElements(e, imageIo, NULL) : NULL;
+    jdouble *peo = pio ? (*e)->GetDoubleArrayElements(e, imageEo, NULL) : NULL;
+    const size_t np1 = (size_t)(n > 0 ? n : 1), nr1 = (size_t)(nr > 0 ? nr : 1), nl = np1 > nr1 ? np1 : nr1;
+    double *po = (double *)malloc(sizeof(double) * JAICOV_ISECT_OUT_PER_POINT * np1);
+    int32_t *ps = (int32_t *)malloc(sizeof(int32_t) * 2 * np1);
+    uint8_t *pu = (uint8_t *)malloc(nr1);
+    double *pq = (double *)malloc(sizeof(double) * nr1);
+    jlong *pl = (jlong *)malloc(sizeof(jlong) * nl);
+    int rc = JAICOV_ERR_OUT_OF_MEMORY;
+    if (peo && (pvar || !var) && po && ps && pu && pq && pl) {
+        rc = jaicov_isect_points((int32_t)n, (const int32_t *)pb, (const int32_t *)pi, pxy, pvar, (int32_t)nImages, pio, peo, sigma2apriori,
+                                 (int32_t)maxIterations, rejectThreshold, (int32_t)minRays, po, ps, ps + n, pu, pq, NULL);
+        if (rc == JAICOV_OK) {
+            (*e)->SetDoubleArrayRegion(e, out, 0, JAICOV_ISECT_OUT_PER_POINT * n, po);
+            for (jsize i = 0; i < n; i++) pl[i] = (jlong)ps[i];
+            (*e)->SetLongArrayRegion(e, status, 0, n, pl);
+            if (iterations) {
+                for (jsize i = 0; i < n; i++) pl[i] = (jlong)ps[n + i];
+                (*e)->SetLongArrayRegion(e, iterations, 0, n, pl);
+            }
+            if (rayUsed) {
+                for (jsize i = 0; i < nr; i++) pl[i] = (jlong)pu[i];
+                (*e)->SetLongArrayRegion(e, rayUsed, 0, nr, pl);
+            }
+            if (rayQ) (*e)->SetDoubleArrayRegion(e, rayQ, 0, nr, pq);
+        }
+    }
+    free(po); free(ps); free(pu); free(pq); free(pl);
+    if (peo) (*e)->ReleaseDoubleArrayElements(e, imageEo, peo, JNI_ABORT);
+    if (pio) (*e)->ReleaseDoubleArrayElements(e, imageIo, pio, JNI_ABORT);
+    if (pvar) (*e)->ReleaseDoubleArrayElements(e, var, pvar, JNI_ABORT);
+    if (pxy) (*e)->ReleaseDoubleArrayElements(e, xy, pxy, JNI_ABORT);
+    if (pi) (*e)->ReleaseIntArrayElements(e, rayImage, pi, JNI_ABORT);
+    (*e)->ReleaseIntArrayElements(e, rayBegin, pb, JNI_ABORT);
     return rc;
 }

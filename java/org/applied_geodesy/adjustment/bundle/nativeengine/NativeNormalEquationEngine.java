@@ -270,6 +270,31 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 		return status;
 	}
 
+	/** jaicov_isect status values (include/jaicov_intersect.h) */
+	public static final int ISECT_OK = 0, ISECT_NOT_CONVERGED = 1, ISECT_TOO_FEW_RAYS = 2, ISECT_SINGULAR = 3, ISECT_NOT_FINITE = 4;
+
+	/**
+	 * Spatial forward intersection of every object point of a batch from the image rays that see it, on the device, with no engine
+	 * (include/jaicov_intersect.h; the reference has no counterpart: it reads the points' start values from a file).  rayBegin (n + 1
+	 * CSR offsets) selects each point's rays; rayImage = the image of each ray; xy = 2 doubles per ray; var (may be null: unit
+	 * weights) = variance x, variance y, correlation coefficient per ray (PartialDerivativeFactory.java:308-319); imageIo = x0, y0, c
+	 * and imageEo = X0, Y0, Z0, omega, phi, kappa per image.  out receives 11 values per point (X, Y, Z, the six cofactors, Omega, the
+	 * largest angle between two rays); iterations, rayUsed and rayQ may be null.  The result is the status per point; a point whose
+	 * status is ISECT_TOO_FEW_RAYS, ISECT_SINGULAR or ISECT_NOT_FINITE has NaN values.
+	 */
+	public static long[] intersectPoints(int[] rayBegin, int[] rayImage, double[] xy, double[] var, double[] imageIo, double[] imageEo,
+	                                     double sigma2apriori, int maxIterations, double rejectThreshold, int minRays, double[] out,
+	                                     long[] iterations, long[] rayUsed, double[] rayQ) {
+		int n = rayBegin.length - 1;
+		long[] status = new long[Math.max(n, 0)];
+		int rc = isectPoints(rayBegin, rayImage, xy, var, imageIo.length / 3, imageIo, imageEo, sigma2apriori, maxIterations, rejectThreshold,
+		                     minRays, out, status, iterations, rayUsed, rayQ);
+		if (rc == -1) throw new IllegalArgumentException("jaicov_isect_points: bad argument");
+		if (rc == -4) throw new OutOfMemoryError("jaicov_isect_points");
+		if (rc != 0) throw new IllegalStateException("jaicov_isect_points failed with status " + rc);
+		return status;
+	}
+
 	@Override public void close() { if (handle != 0) { destroy(handle); handle = 0; } }
 
 	private void check(int status) {
@@ -327,4 +352,5 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 	private static native int datumTransform(long h, int[] pointDatum);
 	private static native int datumApply(long h, double[] v, double[] out, int n);
 	private static native int dltAdjust(int[] obsBegin, double[] xy, double[] xyz, double[] io, int[] ioFixed, int[] restrictions, int maxIterations, double[] out, long[] status, long[] solves);
+	private static native int isectPoints(int[] rayBegin, int[] rayImage, double[] xy, double[] var, int nImages, double[] imageIo, double[] imageEo, double sigma2apriori, int maxIterations, double rejectThreshold, int minRays, double[] out, long[] status, long[] iterations, long[] rayUsed, double[] rayQ);
 }
