@@ -20,7 +20,8 @@ struct BatchedSpdInverse {
     double *Qb = nullptr;           // [cap] (L L')^-1, FULL symmetric square after run()
     double *Db = nullptr;           // [cap] refinement only: copy of the input matrices, FULL squares (filled by the caller beside Lb)
     double *S1 = nullptr, *S2 = nullptr;   // [cap] refinement workspace
-    bool refine = false;            // one Newton-Schulz step on every inverse, residual by error-free splitting (batchinv.hip)
+    bool refine = false;            // one Newton-Schulz step on every inverse, residual by error-free splitting (batchinv.hip): set by init() when
+                                    // asked for and mp <= 8192 (beyond that the leading product is no longer exact: the inverses stay as W'W leaves them)
     double *invd = nullptr;         // [cap][nb] inverses of the diagonal blocks
     int *d_info = nullptr;          // 0, or 1 + the first failing pivot of some matrix of the chunk
     hipError_t init(hipStream_t s, int padded_order, int matrices_per_chunk, bool with_refinement);

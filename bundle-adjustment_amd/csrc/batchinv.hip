@@ -57,7 +57,8 @@ __global__ __launch_bounds__(256) void symmetrize_batched_kernel(double *M, long
 // R = I - D X (~5e-11) cannot be formed in fp64 either: its terms are ~1e7 times larger than the result.  Split instead (Ozaki's
 // error-free scheme, one level): D = D1 + D2, X = X1 + X2 with D1 = the leading 20 bits of every entry relative to its ROW's largest,
 // X1 likewise relative to its COLUMN's largest.  Then every product D1[i][k] X1[k][j] is an integer multiple of one unit u_ij and the
-// sum of 1024 of them stays below 2^53 u_ij: the fp64 matrix cores compute D1 X1 EXACTLY, whatever their summation order.  The rest,
+// sum of up to 8192 of them stays below 2^53 u_ij (20 + 20 + 13 bits): the fp64 matrix cores compute D1 X1 EXACTLY, whatever their
+// summation order -- for every padded order up to 8192, which is where init() stops refining.  The rest,
 // D1 X2 + D2 X, is 2^-20 of the size, so its fp64 rounding (1e-16 relative to ITS terms) is ~1e-15 absolute: R is known to 3-4
 // digits of itself, and X + X R has the forward error of R^2 plus fp64 rounding of X (measured on the host: 2.9e-11 -> 1.2e-14).
 // Three exact-or-small GEMMs + one for X R per matrix; the slices are relative to powers of two, so slicing itself is exact.
@@ -68,7 +69,7 @@ constexpr int SLICE_BITS = 20;
 __global__ __launch_bounds__(256) void slice_rows_kernel(const double *src, double *hi, double *lo, long ld, long msz, int mp) {
     __shared__ double red[256];
     const long base = (long)blockIdx.y * msz + (long)blockIdx.x * ld;
-    double v[8];                       // mp <= 2048: the row stays in registers; longer rows (the solver's inverse, below) are read twice
+    double v[8];                       // mp <= 2048: the row stays in registers; longer rows (dispersions and the solver's inverse up to 8192) are read twice
     const bool cached = mp <= 2048;
     double mx = 0.0;
     if (cached) {
@@ -135,7 +136,7 @@ hipError_t BatchedSpdInverse::init(hipStream_t s, int padded_order, int matrices
     HIPCHK(hipMalloc(&Lb, sq));
     HIPCHK(hipMalloc(&Wb, sq));
     HIPCHK(hipMalloc(&Qb, sq));
-    refine = with_refinement && mp <= 2048;
+    refine = with_refinement && mp <= 8192;      // the bound of the exactness argument above (20 + 20 + log2(mp) <= 53 bits), not of the row cache
     if (refine) {
         HIPCHK(hipMalloc(&Db, sq));
         HIPCHK(hipMalloc(&S1, sq));

@@ -2071,6 +2071,40 @@ extern "C" int jaicov_debug_potrf_factor(int n, const double *A, double *L_out) 
     return status;
 }
 
+// debug: one step of newton_schulz_exact (batchinv.hip) on host matrices: M and Q0 full symmetric squares, n x n row-major, n a multiple
+// of 128 up to 8192.  On the device they stand with the leading dimension the solver gives them (n + 128, its right-hand-side rows beside the
+// factor, filled with NaN here), not n.  Q_out = the refined inverse; R_out (optional) = the residual square I - M Q0 as the step formed it, before the product
+// Q0 R -- tests/test_gpu_inverse_refinement.py holds both
+extern "C" int jaicov_debug_newton_schulz(int n, const double *M, const double *Q0, double *Q_out, double *R_out) {
+    std::string err;
+    if (check_device(err)) return JAICOV_ERR_NO_DEVICE;
+    if (n <= 0 || n % 128 || n > 8192 || !M || !Q0 || !Q_out) return JAICOV_ERR_BAD_ARGUMENT;
+    hipStream_t s;
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return JAICOV_ERR_DEVICE;
+    const long ld = (long)n + 128;
+    const size_t sq = (size_t)n * ld, row = (size_t)n * sizeof(double);
+    double *buf = nullptr;                                   // M, Q, W, T1, T2, T3
+    int status = JAICOV_OK;
+    do {
+        if (hipMalloc(&buf, 6 * sq * sizeof(double)) != hipSuccess) { status = JAICOV_ERR_OUT_OF_MEMORY; break; }
+        double *dM = buf, *dQ = buf + sq, *dW = buf + 2 * sq, *T1 = buf + 3 * sq, *T2 = buf + 4 * sq, *T3 = buf + 5 * sq;
+        // M and Q start as NaN (all bits set) and the work squares as zero: the columns n .. n + 127, where the solver keeps its right-hand-side
+        // rows, then hold NaN beside both operands, and a slice or product that read up to ld instead of n would show in every entry
+        if (hipMemsetAsync(buf, 0xFF, 2 * sq * sizeof(double), s) != hipSuccess ||
+            hipMemsetAsync(buf + 2 * sq, 0, 4 * sq * sizeof(double), s) != hipSuccess ||
+            hipMemcpy2DAsync(dM, ld * sizeof(double), M, row, row, n, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpy2DAsync(dQ, ld * sizeof(double), Q0, row, row, n, hipMemcpyHostToDevice, s) != hipSuccess ||
+            newton_schulz_exact(s, n, ld, dM, dQ, dW, T1, T2, T3) != hipSuccess ||
+            hipMemcpy2DAsync(Q_out, row, dQ, ld * sizeof(double), row, n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            (R_out && hipMemcpy2DAsync(R_out, row, T3, ld * sizeof(double), row, n, hipMemcpyDeviceToHost, s) != hipSuccess))   // (the product Q0 R went to T1)
+            status = JAICOV_ERR_DEVICE;
+    } while (0);
+    if (hipStreamSynchronize(s) != hipSuccess) status = status == JAICOV_OK ? JAICOV_ERR_DEVICE : status;
+    hipFree(buf);
+    hipStreamDestroy(s);
+    return status;
+}
+
 // C (M x N row-major) = alpha * op(A) op(B) + beta * C on the device, host buffers in/out (kernel parity + timing)
 extern "C" int jaicov_dense_gemm(int32_t alay, int32_t blay, int32_t M, int32_t N, int32_t K, double alpha, const double *A,
                                  int64_t lda, const double *B, int64_t ldb, double beta, double *C, int64_t ldc,

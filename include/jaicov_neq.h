@@ -183,7 +183,9 @@ typedef struct jaicov_engine_options {
                                       create, with the residual formed by error-free splitting on the fp64 matrix cores (batchinv.hip): the
                                       forward error of inv(D) falls from cond(D) * eps (3e-11 at config 4, the reference's dpptrf + dpptri the
                                       same) to ~1e-14, and with it the error of N = A' inv(D) A against the exactly assembled system.  Four
-                                      more GEMMs per matrix (+80 ms of engine creation at config 4).  < 0: off.                              */
+                                      more GEMMs per matrix (+80 ms of engine creation at config 4).  Every dispersion of up to 8192 rows
+                                      (4096 points; padded to a multiple of 128) gets the step; a larger one keeps its fp64 inverse, since the
+                                      leading product of the split is exact up to that order only.  < 0: off.                               */
     int32_t  expansion_exchange;   /* != 0 on a SHARDED engine (image_begin/image_end): the caller promises to sum
                                       jaicov_neq_expansion_buffer() over the ranks between accumulate and the inverting solve, so that
                                       MatrixInversion.FULL is expanded from the reduced inverse on a shard too (JAICOV_INVERT_FULL_EXPANDED;

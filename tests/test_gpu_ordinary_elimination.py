@@ -144,7 +144,8 @@ def test_problems_that_do_not_qualify_keep_the_full_order_path(oracle_mod):
 def test_batched_dispersion_inverse_matches_the_references_dpptri(oracle_mod, m_points):
     """DOPG:82-86 at engine creation: all dispersions of one padded order are inverted in one set of batched launches (batchinv.hip).
     jaicov_neq_get_block_weight returns inv(D) in the CALLER's observation order (the engine keeps blocks column-sorted);
-    oracle_dispersion_to_weight = dpptrf + dpptri of D / sigma0^2.  Orders 4 .. 570: one to five diagonal blocks (ragged last level of the triangular inverse), two padded orders in one problem."""
+    oracle_dispersion_to_weight = dpptrf + dpptri of D / sigma0^2.  Orders 4 .. 570: one to five diagonal blocks (ragged last level of the triangular inverse), two padded orders in one problem.
+    The 1e-9 is the distance to the reference's fp64 algorithm, not the accuracy of the weights: that is held against certified truth in tests/test_gpu_weight_refinement.py."""
     fp = scene.make_scene(6, int(m_points / 0.55) + 12, m_points, dist=scene.DIST_RADIAL, weights="block", n_control=4, control_dense=True)
     o = oracle_mod.Oracle(fp)
     s2 = fp.sigma2apriori
