@@ -9,9 +9,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "devbuf.h"
+
 namespace jaicov {
 
-struct BatchedSpdInverse {
+struct BatchedSpdInverse {     // the buffers go with the object: synchronise `stream` before it leaves scope on a success path
     hipStream_t stream = nullptr;
     int mp = 0, nb = 0, cap = 0;    // padded order (multiple of 128), block columns, matrices per chunk
     long ld = 0, msz = 0;           // leading dimension (= mp) and doubles per matrix (mp * mp)
@@ -24,8 +26,8 @@ struct BatchedSpdInverse {
                                     // asked for and mp <= 8192 (beyond that the leading product is no longer exact: the inverses stay as W'W leaves them)
     double *invd = nullptr;         // [cap][nb] inverses of the diagonal blocks
     int *d_info = nullptr;          // 0, or 1 + the first failing pivot of some matrix of the chunk
+    DevBag store;                   // the owner of the buffers above
     hipError_t init(hipStream_t s, int padded_order, int matrices_per_chunk, bool with_refinement);
-    void release();
     // Lb[0..count) hold the matrices (lower triangle, identity on the padding's diagonal; with `refine` also Db[0..count), full
     // squares) -> Qb[0..count) their inverses.
     // Everything is enqueued on `stream`; *info_out is valid after the stream has been synchronised (run() does not synchronise).

@@ -3,14 +3,9 @@
 
 #include "gemm_f64.h"
 #include "potrf_diag.h"
+#include "status.h"
 
 namespace jaicov {
-
-#define HIPCHK(x)                                  \
-    do {                                           \
-        hipError_t _e = (x);                       \
-        if (_e != hipSuccess) return _e;           \
-    } while (0)
 
 // diagonal block k of every matrix of the chunk: Cholesky + inverse in LDS (potrf_diag.h), one workgroup per matrix
 __global__ __launch_bounds__(256) void potrf_diag_batched_kernel(double *A, long ld, long strideA, double *inv_out, long stride_inv,
@@ -132,26 +127,21 @@ hipError_t BatchedSpdInverse::init(hipStream_t s, int padded_order, int matrices
     stream = s;
     mp = padded_order; nb = mp / 128; cap = matrices_per_chunk;
     ld = mp; msz = (long)mp * mp;
-    const size_t sq = (size_t)cap * msz * sizeof(double);
-    HIPCHK(hipMalloc(&Lb, sq));
-    HIPCHK(hipMalloc(&Wb, sq));
-    HIPCHK(hipMalloc(&Qb, sq));
+    const size_t sq = (size_t)cap * msz;
+    HIPCHK(store.alloc(&Lb, sq));
+    HIPCHK(store.alloc(&Wb, sq));
+    HIPCHK(store.alloc(&Qb, sq));
     refine = with_refinement && mp <= 8192;      // the bound of the exactness argument above (20 + 20 + log2(mp) <= 53 bits), not of the row cache
     if (refine) {
-        HIPCHK(hipMalloc(&Db, sq));
-        HIPCHK(hipMalloc(&S1, sq));
-        HIPCHK(hipMalloc(&S2, sq));
+        HIPCHK(store.alloc(&Db, sq));
+        HIPCHK(store.alloc(&S1, sq));
+        HIPCHK(store.alloc(&S2, sq));
     }
-    HIPCHK(hipMalloc(&invd, (size_t)cap * nb * 16384 * sizeof(double)));
+    HIPCHK(store.alloc(&invd, (size_t)cap * nb * 16384));
     HIPCHK(hipMemsetAsync(invd, 0, (size_t)cap * nb * 16384 * sizeof(double), s));   // the diagonal kernel writes the lower parts only
-    HIPCHK(hipMalloc(&d_info, sizeof(int)));
+    HIPCHK(store.alloc(&d_info, 1));
     HIPCHK(hipMemsetAsync(d_info, 0, sizeof(int), s));
     return hipSuccess;
-}
-
-void BatchedSpdInverse::release() {
-    hipFree(Lb); hipFree(Wb); hipFree(Qb); hipFree(invd); hipFree(d_info); hipFree(Db); hipFree(S1); hipFree(S2);
-    Lb = Wb = Qb = invd = Db = S1 = S2 = nullptr; d_info = nullptr;
 }
 
 hipError_t BatchedSpdInverse::run(int count) {

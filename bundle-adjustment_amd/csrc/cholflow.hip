@@ -54,14 +54,9 @@
 #include "dense.h"
 #include "gemm_f64.h"
 #include "potrf_diag.h"
+#include "status.h"
 
 namespace jaicov {
-
-#define HIPCHK(x)                                  \
-    do {                                           \
-        hipError_t _e = (x);                       \
-        if (_e != hipSuccess) return _e;           \
-    } while (0)
 
 constexpr int FLOW_FIN = 1 << 20;        // task.w = k1 | FLOW_FIN: finish the tile after the updates
 // Split update ranges (the late block columns' tiles: each has ~100 block-column steps to do one after the other, is drawn late -- tickets go

@@ -3,14 +3,22 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/jaicov_neq.h"
+#include "devbuf.h"
 
 namespace jaicov {
 
-struct DatumState;
+// S of the last jaicov_datum_transform and its work buffer, kept by the engine
+struct DatumState {
+    bool valid = false;              // S of the last transform belongs to the cofactor matrix at hand
+    int order = 0, d = 0;
+    std::vector<double> Z, B;        // [order][d], [d][order]: S = I - Z B'
+    DevBuf<double> work;             // B' [d][np] | Y [np][d] | (Z, Y~) [np][2d] | table [nbk][nbk][128][d]
+};
 
 // What the datum transformation reads and writes of an engine.  Pointers stay owned by the engine.
 struct DatumView {
@@ -23,7 +31,7 @@ struct DatumView {
     int order = 0;
     int d = 0;
     int n_points = 0;
-    DatumState **state = nullptr;      // the engine's slot for S of the last transform and the work buffers (freed by jaicov_neq_destroy)
+    std::unique_ptr<DatumState> *state = nullptr;   // the engine's slot for S of the last transform and the work buffer
     std::string *err = nullptr;        // jaicov_neq_last_error text
 };
 
@@ -33,6 +41,5 @@ void engine_datum_view(jaicov_engine *e, DatumView *v);
 int engine_datum_rows(jaicov_engine *e, const uint8_t *mask, std::vector<double> &B, int stride);
 // An inverting solve replaces the cofactor matrix: S of an earlier transform no longer applies
 void datum_state_invalidate(DatumState *s);
-void datum_state_free(DatumState *s);
 
 }  // namespace jaicov

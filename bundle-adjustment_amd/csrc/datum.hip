@@ -18,25 +18,12 @@
 
 #include "../../include/jaicov_datum.h"
 #include "datum.h"
+#include "status.h"
 
 namespace jaicov {
 
-struct DatumState {
-    bool valid = false;              // S of the last transform belongs to the cofactor matrix at hand
-    int order = 0, d = 0;
-    std::vector<double> Z, B;        // [order][d], [d][order]: S = I - Z B'
-    double *work = nullptr;          // device: B' [d][np] | Y [np][d] | (Z, Y~) [np][2d] | table [nbk][nbk][128][d]
-    size_t work_len = 0;
-};
-
 void datum_state_invalidate(DatumState *s) {
     if (s) s->valid = false;
-}
-
-void datum_state_free(DatumState *s) {
-    if (!s) return;
-    if (s->work) hipFree(s->work);
-    delete s;
 }
 
 // One workgroup per lower tile (I, J), J <= I, in four slabs of 32 rows.  Row part: thread (rr, seg) holds row rr of the slab,
@@ -276,38 +263,24 @@ static bool datum_small_inverse(int d, const double *M, double *Minv) {
 
 using namespace jaicov;
 
-#define DFAIL(v, code, msg)     \
-    do {                        \
-        *(v).err = (msg);       \
-        return (code);          \
-    } while (0)
-#define DHIP(v, x)                                                                                   \
-    do {                                                                                             \
-        hipError_t _err = (x);                                                                       \
-        if (_err != hipSuccess) {                                                                    \
-            *(v).err = std::string(#x) + ": " + hipGetErrorString(_err);                             \
-            return _err == hipErrorOutOfMemory ? JAICOV_ERR_OUT_OF_MEMORY : JAICOV_ERR_DEVICE;         \
-        }                                                                                            \
-    } while (0)
-
 extern "C" int jaicov_datum_transform(jaicov_engine *e, const uint8_t *point_datum, int32_t n_points) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     DatumView v;
     engine_datum_view(e, &v);
-    if (v.d == 0) DFAIL(v, JAICOV_ERR_UNSUPPORTED, "datum transformation: the network has no datum defect (d = 0)");
-    if (v.sharded) DFAIL(v, JAICOV_ERR_UNSUPPORTED, "datum transformation on a sharded engine");
-    if (!v.have_q) DFAIL(v, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
-    if (!point_datum || n_points != v.n_points) DFAIL(v, JAICOV_ERR_BAD_ARGUMENT, "point_datum must hold one flag per object point");
+    if (v.d == 0) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "datum transformation: the network has no datum defect (d = 0)");
+    if (v.sharded) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "datum transformation on a sharded engine");
+    if (!v.have_q) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
+    if (!point_datum || n_points != v.n_points) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "point_datum must hold one flag per object point");
     const int n = v.order, d = v.d, nbk = (n + 127) / 128, np = nbk * 128;
     std::vector<double> B;
     int rc = engine_datum_rows(e, point_datum, B, np);
     if (rc) return rc;
-    DHIP(v, hipSetDevice(v.device));
+    HIPE(*v.err, hipSetDevice(v.device));
     // G^: the unknowns x border block (rows d .. n-1, columns 0 .. d-1)
     std::vector<double> G((size_t)n * d, 0.0);
-    DHIP(v, hipMemcpy2DAsync(G.data() + (size_t)d * d, d * sizeof(double), v.Q + (long)d * v.ld, v.ld * sizeof(double),
+    HIPE(*v.err, hipMemcpy2DAsync(G.data() + (size_t)d * d, d * sizeof(double), v.Q + (long)d * v.ld, v.ld * sizeof(double),
                              d * sizeof(double), n - d, hipMemcpyDeviceToHost, v.stream));
-    DHIP(v, hipStreamSynchronize(v.stream));
+    HIPE(*v.err, hipStreamSynchronize(v.stream));
     // C = (B' G^)^-1, Z = G^ C
     double M[49], Cm[49];
     for (int a = 0; a < d; a++)
@@ -316,7 +289,7 @@ extern "C" int jaicov_datum_transform(jaicov_engine *e, const uint8_t *point_dat
             for (int i = d; i < n; i++) s += B[(size_t)a * np + i] * G[(size_t)i * d + b];
             M[a * d + b] = s;
         }
-    if (!datum_small_inverse(d, M, Cm)) DFAIL(v, JAICOV_ERR_SINGULAR, "the new datum points do not fix the frame (B' G^ is singular)");
+    if (!datum_small_inverse(d, M, Cm)) FAIL(*v.err, JAICOV_ERR_SINGULAR, "the new datum points do not fix the frame (B' G^ is singular)");
     std::vector<double> Z((size_t)n * d, 0.0);
     for (int i = d; i < n; i++)
         for (int a = 0; a < d; a++) {
@@ -325,22 +298,15 @@ extern "C" int jaicov_datum_transform(jaicov_engine *e, const uint8_t *point_dat
             Z[(size_t)i * d + a] = s;
         }
     // work buffers, kept with the engine
-    DatumState *&st = *v.state;
-    if (!st) st = new DatumState();
-    const size_t len = (size_t)d * np * 4 + (size_t)nbk * nbk * 128 * d;
-    if (st->work_len < len) {
-        if (st->work) hipFree(st->work);
-        st->work = nullptr;
-        st->work_len = 0;
-        DHIP(v, hipMalloc(&st->work, len * sizeof(double)));
-        st->work_len = len;
-    }
-    double *dB = st->work, *dY = dB + (size_t)d * np, *dZY = dY + (size_t)d * np, *dP = dZY + (size_t)2 * d * np;
-    DHIP(v, hipMemcpyAsync(dB, B.data(), (size_t)d * np * sizeof(double), hipMemcpyHostToDevice, v.stream));
-    DHIP(v, launch_y_d(d, v.stream, v.Q, v.ld, n, dB, np, nbk, dP, dY));
+    if (!*v.state) v.state->reset(new DatumState());
+    DatumState *st = v.state->get();
+    HIPE(*v.err, st->work.reserve((size_t)d * np * 4 + (size_t)nbk * nbk * 128 * d));
+    double *dB = st->work.get(), *dY = dB + (size_t)d * np, *dZY = dY + (size_t)d * np, *dP = dZY + (size_t)2 * d * np;
+    HIPE(*v.err, hipMemcpyAsync(dB, B.data(), (size_t)d * np * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    HIPE(*v.err, launch_y_d(d, v.stream, v.Q, v.ld, n, dB, np, nbk, dP, dY));
     std::vector<double> Y((size_t)np * d);
-    DHIP(v, hipMemcpyAsync(Y.data(), dY, Y.size() * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    DHIP(v, hipStreamSynchronize(v.stream));
+    HIPE(*v.err, hipMemcpyAsync(Y.data(), dY, Y.size() * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    HIPE(*v.err, hipStreamSynchronize(v.stream));
     // W = B' Y (symmetric: its two triangles averaged), Y~ = Y - Z W / 2
     double W[49];
     for (int a = 0; a < d; a++)
@@ -359,10 +325,10 @@ extern "C" int jaicov_datum_transform(jaicov_engine *e, const uint8_t *point_dat
             ZY[(size_t)i * 2 * d + a] = Z[(size_t)i * d + a];
             ZY[(size_t)i * 2 * d + d + a] = Y[(size_t)i * d + a] - 0.5 * s;
         }
-    DHIP(v, hipMemcpyAsync(dZY, ZY.data(), ZY.size() * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    HIPE(*v.err, hipMemcpyAsync(dZY, ZY.data(), ZY.size() * sizeof(double), hipMemcpyHostToDevice, v.stream));
     st->valid = false;      // from here on Q changes: the S of an earlier transform no longer applies to it
-    DHIP(v, launch_update_d(d, v.stream, v.Q, v.ld, n, dZY));
-    DHIP(v, hipStreamSynchronize(v.stream));
+    HIPE(*v.err, launch_update_d(d, v.stream, v.Q, v.ld, n, dZY));
+    HIPE(*v.err, hipStreamSynchronize(v.stream));
     // S = I - Z B' for jaicov_datum_apply
     st->order = n;
     st->d = d;
@@ -377,9 +343,9 @@ extern "C" int jaicov_datum_apply(jaicov_engine *e, const double *x, double *out
     if (!e || !x || !out) return JAICOV_ERR_BAD_ARGUMENT;
     DatumView v;
     engine_datum_view(e, &v);
-    const DatumState *st = *v.state;
-    if (!st || !st->valid) DFAIL(v, JAICOV_ERR_BAD_STATE, "no datum transformation since the last inverting solve");
-    if (n != st->order) DFAIL(v, JAICOV_ERR_BAD_ARGUMENT, "n must be the order of the transformed cofactor matrix");
+    const DatumState *st = v.state->get();
+    if (!st || !st->valid) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no datum transformation since the last inverting solve");
+    if (n != st->order) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "n must be the order of the transformed cofactor matrix");
     const int d = st->d;
     double t[7];
     for (int a = 0; a < d; a++) {

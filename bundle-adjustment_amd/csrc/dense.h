@@ -98,6 +98,9 @@ struct DenseSolver {     // not copyable: it holds owners
     // A failure leaves nothing behind.
     hipError_t init(hipStream_t s, int n_padded, bool with_inverse, bool with_rhs_rows = false, const DenseSolver *share = nullptr);
     hipError_t acquire(bool with_inverse, const DenseSolver *share);      // init's body
+    // the inverse's squares, two allocations of the solver's order: Q, and with want_W also W.  What is there already stays (engine.hip
+    // reserves them before the solve that needs them, jaicov_neq_prepare_inverse)
+    hipError_t reserve_inverse(bool want_W);
     ~DenseSolver() { release(); }
     double *rhs_row(int q) const { return L + (long)(nfact + q) * ld; }   // row q of the right-hand sides / of Z = Y L^-T
     void release();            // everything goes back: buffers, events, the leased streams (synchronised by stream_release)

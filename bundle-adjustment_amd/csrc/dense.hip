@@ -13,14 +13,9 @@
 
 #include "gemm_f64.h"
 #include "potrf_diag.h"
+#include "status.h"
 
 namespace jaicov {
-
-#define HIPCHK(x)                                  \
-    do {                                           \
-        hipError_t _e = (x);                       \
-        if (_e != hipSuccess) return _e;           \
-    } while (0)
 
 __global__ __launch_bounds__(256) void potrf_diag_kernel(double *A, long ld, double *inv_out, int *info, int blk, int dbg) {
     __shared__ double S[128 * DP];
@@ -927,6 +922,13 @@ extern "C" void jaicov_debug_stream_census(int *out8) {
         if (kv.first.second >= 0 && kv.first.second < 4) out8[4 + kv.first.second] += (int)kv.second.size();
 }
 
+// tests / DESIGN.md: device memory that the library's owners (devbuf.h) hold in this process: [0] bytes, [1] allocations.  Complete, since
+// nothing else in the library allocates
+extern "C" void jaicov_debug_device_census(long long *out2) {
+    out2[0] = device_live[0].load();
+    out2[1] = device_live[1].load();
+}
+
 int device_cu_count() {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) return cus;
@@ -1005,16 +1007,20 @@ hipError_t DenseSolver::acquire(bool with_inverse, const DenseSolver *share) {
         HIPCHK(hipMemcpy(tile_map_store.get(), all.data(), all.size() * sizeof(int2), hipMemcpyHostToDevice));
         for (auto &w : where) tile_maps.emplace(w.first, std::make_pair(tile_map_store.get() + w.second.first, w.second.second));
     }
-    if (with_inverse) {
-        HIPCHK(store.W.reserve(sq));
-        HIPCHK(store.Q.reserve(sq));
-        W = store.W.get(); Q = store.Q.get();
-    }
+    if (with_inverse) HIPCHK(reserve_inverse(true));
     if (flow_wanted && dstream && flow.init(FlowView{L, ld, invd, d_info, nfact, n, stream, pstream, dstream}, hooks) != hipSuccess) {
         // the stream-scheduled factorisation remains: it wants the masked stream of the trailing updates after all
         (void)hipGetLastError();
         ustream = masked(ustream, ustream_lease, STREAM_UPDATE_CUS);
     }
+    return hipSuccess;
+}
+
+hipError_t DenseSolver::reserve_inverse(bool want_W) {
+    const size_t sq = (size_t)n * ld;
+    if (want_W) HIPCHK(store.W.reserve(sq));
+    HIPCHK(store.Q.reserve(sq));
+    W = store.W.get(); Q = store.Q.get();
     return hipSuccess;
 }
 
@@ -1462,70 +1468,61 @@ __global__ __launch_bounds__(256) void mfma_peak_kernel(double *out, int iters) 
     if (s == 123.456) out[0] = s;
 }
 
-hipError_t mfma_peak_bench(int blocks, int iters, float *ms_out, double *tflops) {
-    double *out = nullptr;
-    HIPCHK(hipMalloc(&out, 8));
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    hipLaunchKernelGGL(mfma_peak_kernel, dim3(blocks), dim3(256), 0, nullptr, out, iters);
-    hipEventRecord(e0, nullptr);
-    hipLaunchKernelGGL(mfma_peak_kernel, dim3(blocks), dim3(256), 0, nullptr, out, iters);
-    hipEventRecord(e1, nullptr);
-    hipEventSynchronize(e1);
-    hipEventElapsedTime(ms_out, e0, e1);
+// the MFMA peak kernel twice on `st`, the second launch timed
+static hipError_t peak_on_stream(hipStream_t st, int blocks, int iters, float *ms_out, double *tflops) {
+    DevBuf<double> out;
+    DevEvent e0, e1;
+    HIPCHK(out.reserve(1));
+    HIPCHK(e0.create());
+    HIPCHK(e1.create());
+    hipLaunchKernelGGL(mfma_peak_kernel, dim3(blocks), dim3(256), 0, st, out.get(), iters);
+    hipEventRecord(e0.get(), st);
+    hipLaunchKernelGGL(mfma_peak_kernel, dim3(blocks), dim3(256), 0, st, out.get(), iters);
+    hipEventRecord(e1.get(), st);
+    hipEventSynchronize(e1.get());
+    hipEventElapsedTime(ms_out, e0.get(), e1.get());
     *tflops = (double)blocks * 4.0 * (iters < 0 ? -iters : iters) * 16.0 * 2048.0 / (*ms_out * 1e-3) / 1e12;
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    hipFree(out);
     return hipGetLastError();
 }
+
+hipError_t mfma_peak_bench(int blocks, int iters, float *ms_out, double *tflops) { return peak_on_stream(nullptr, blocks, iters, ms_out, tflops); }
 
 // does hipExtStreamCreateWithCUMask work here?  runs the MFMA peak kernel on a stream restricted by `mask` (8 words)
 hipError_t cumask_bench(const uint32_t *mask, int blocks, int iters, float *ms_out, double *tflops) {
     hipStream_t st;
     HIPCHK(hipExtStreamCreateWithCUMask(&st, 8, mask));
-    double *out = nullptr;
-    HIPCHK(hipMalloc(&out, 8));
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    hipLaunchKernelGGL(mfma_peak_kernel, dim3(blocks), dim3(256), 0, st, out, iters);
-    hipEventRecord(e0, st);
-    hipLaunchKernelGGL(mfma_peak_kernel, dim3(blocks), dim3(256), 0, st, out, iters);
-    hipEventRecord(e1, st);
-    hipEventSynchronize(e1);
-    hipEventElapsedTime(ms_out, e0, e1);
-    *tflops = (double)blocks * 4.0 * iters * 16.0 * 2048.0 / (*ms_out * 1e-3) / 1e12;
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    hipFree(out);
+    const hipError_t err = peak_on_stream(st, blocks, iters, ms_out, tflops);
     hipStreamDestroy(st);
-    return hipGetLastError();
+    return err;
 }
 
 // timing hook for the diagonal-block kernel (diagnostics): `iters` back-to-back launches on an SPD 128x128 block
 hipError_t diag_kernel_bench(int dbg, int iters, float *ms_out) {
-    double *A = nullptr, *inv = nullptr;
-    int *info = nullptr;
-    HIPCHK(hipMalloc(&A, 16384 * sizeof(double)));
-    HIPCHK(hipMalloc(&inv, 16384 * sizeof(double)));
-    HIPCHK(hipMalloc(&info, sizeof(int)));
-    double *h = new double[16384];
+    DevBuf<double> A_store, inv_store;
+    DevBuf<int> info_store;
+    DevEvent ev0, ev1;
+    HIPCHK(A_store.reserve(16384));
+    HIPCHK(inv_store.reserve(16384));
+    HIPCHK(info_store.reserve(1));
+    HIPCHK(ev0.create());
+    HIPCHK(ev1.create());
+    double *A = A_store.get(), *inv = inv_store.get();
+    int *info = info_store.get();
+    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
+    std::vector<double> h(16384);
     for (int r = 0; r < 128; r++)
         for (int c = 0; c < 128; c++) h[r * 128 + c] = (r == c) ? 4.0 : 0.5 / (1.0 + (r > c ? r - c : c - r));
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
     hipMemset(inv, 0, 16384 * sizeof(double));
     hipMemset(info, 0, sizeof(int));
     hipEventRecord(e0, nullptr);
     for (int i = 0; i < iters; i++) {
-        hipMemcpyAsync(A, h, 16384 * sizeof(double), hipMemcpyHostToDevice, nullptr);
+        hipMemcpyAsync(A, h.data(), 16384 * sizeof(double), hipMemcpyHostToDevice, nullptr);
         hipLaunchKernelGGL(potrf_diag_kernel, dim3(1), dim3(256), 0, nullptr, A, 128L, inv, info, 0, dbg);
     }
     hipEventRecord(e1, nullptr);
     hipEventSynchronize(e1);
     hipEventElapsedTime(ms_out, e0, e1);
     *ms_out /= iters;
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    hipFree(A); hipFree(inv); hipFree(info);
-    delete[] h;
     return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 #include "ba_kernels.h"
 #include "gemm_f32.h"
 #include "gemm_f64.h"
+#include "status.h"
 
 namespace jaicov {
 
@@ -102,35 +103,27 @@ hipError_t DenseMode::init(int max_m, int max_k1, int n_blocks, bool single) {
     long want = (long)(((size_t)32 << 30) / per_image);
     if (want < 1) want = 1;
     batch = n_blocks < want ? (n_blocks > 0 ? n_blocks : 1) : (int)want;
-    hipError_t he;
-    if ((he = hipMalloc(&Ppad, (size_t)batch * mpad * mpad * es)) != hipSuccess) return he;
-    if ((he = hipMalloc(&Apad, (size_t)batch * mpad * kpad * es)) != hipSuccess) return he;
-    if ((he = hipMalloc(&Bbuf, (size_t)batch * mpad * kpad * es)) != hipSuccess) return he;
-    if ((he = hipMalloc(&Sbuf, (size_t)batch * kpad * kpad * es)) != hipSuccess) return he;
-    if ((he = hipMalloc(&cmap, (size_t)batch * kpad * sizeof(int32_t))) != hipSuccess) return he;
-    if ((he = hipEventCreate(&ev0)) != hipSuccess) return he;
-    return hipEventCreate(&ev1);
-}
-
-void DenseMode::release() {
-    hipFree(Ppad); hipFree(Apad); hipFree(Bbuf); hipFree(Sbuf); hipFree(cmap);
-    if (ev0) hipEventDestroy(ev0);
-    if (ev1) hipEventDestroy(ev1);
-    Ppad = Apad = Bbuf = Sbuf = nullptr; cmap = nullptr; ev0 = ev1 = nullptr;
+    HIPCHK(Ppad.reserve((size_t)batch * mpad * mpad * es));
+    HIPCHK(Apad.reserve((size_t)batch * mpad * kpad * es));
+    HIPCHK(Bbuf.reserve((size_t)batch * mpad * kpad * es));
+    HIPCHK(Sbuf.reserve((size_t)batch * kpad * kpad * es));
+    HIPCHK(cmap.reserve((size_t)batch * kpad));
+    HIPCHK(ev0.create());
+    return ev1.create();
 }
 
 template <typename T>
 static hipError_t dm_batch(DenseMode &d, hipStream_t s, const DevProblem &p, const int32_t *blk_list, int first, int nb,
                            int n_list, const double *rowsA, const double *rowsW, double sigma2, double *N, double *n) {
     const int mpad = d.mpad, kpad = d.kpad;
-    T *Ppad = (T *)d.Ppad, *Apad = (T *)d.Apad, *Bbuf = (T *)d.Bbuf, *Sbuf = (T *)d.Sbuf;
+    T *Ppad = (T *)d.Ppad.get(), *Apad = (T *)d.Apad.get(), *Bbuf = (T *)d.Bbuf.get(), *Sbuf = (T *)d.Sbuf.get();
     hipError_t he = hipMemsetAsync(Apad, 0, (size_t)nb * mpad * kpad * sizeof(T), s);
     if (he != hipSuccess) return he;
     hipLaunchKernelGGL(dm_pack_weight_kernel<T>, dim3((mpad + 255) / 256, mpad, nb), dim3(256), 0, s, p, blk_list, first, n_list,
                        Ppad, mpad);
     hipLaunchKernelGGL(dm_pack_rows_kernel<T>, dim3((mpad + 255) / 256, nb), dim3(256), 0, s, p, blk_list, first, n_list, rowsA,
-                       rowsW, Apad, d.cmap, mpad, kpad);
-    if ((he = hipEventRecord(d.ev0, s)) != hipSuccess) return he;
+                       rowsW, Apad, d.cmap.get(), mpad, kpad);
+    if ((he = hipEventRecord(d.ev0.get(), s)) != hipSuccess) return he;
     if (sizeof(T) == sizeof(double)) {
         GemmArgs g1{};   // B = P A
         g1.A = (const double *)Ppad; g1.lda = mpad; g1.B = (const double *)Apad; g1.ldb = kpad; g1.C = (double *)Bbuf; g1.ldc = kpad;
@@ -154,8 +147,8 @@ static hipError_t dm_batch(DenseMode &d, hipStream_t s, const DevProblem &p, con
         g2.strideA = (long)mpad * kpad; g2.strideB = (long)mpad * kpad; g2.strideC = (long)kpad * kpad;
         if ((he = gemm_f32(s, LAY_XC, LAY_XC, g2, nb)) != hipSuccess) return he;
     }
-    if ((he = hipEventRecord(d.ev1, s)) != hipSuccess) return he;
-    hipLaunchKernelGGL(dm_scatter_kernel<T>, dim3((kpad + 255) / 256, kpad, nb), dim3(256), 0, s, (const T *)Sbuf, d.cmap, first,
+    if ((he = hipEventRecord(d.ev1.get(), s)) != hipSuccess) return he;
+    hipLaunchKernelGGL(dm_scatter_kernel<T>, dim3((kpad + 255) / 256, kpad, nb), dim3(256), 0, s, (const T *)Sbuf, d.cmap.get(), first,
                        n_list, kpad, sigma2, N, p.ld, n);
     return hipGetLastError();
 }
@@ -170,9 +163,9 @@ hipError_t DenseMode::assemble(hipStream_t s, const DevProblem &p, const int32_t
                              : dm_batch<double>(*this, s, p, blk_list, first, nb, n_list, rowsA, rowsW, sigma2, N, n);
         if (he != hipSuccess) return he;
         if (gemm_ms) {
-            if ((he = hipEventSynchronize(ev1)) != hipSuccess) return he;
+            if ((he = hipEventSynchronize(ev1.get())) != hipSuccess) return he;
             float ms = 0.f;
-            hipEventElapsedTime(&ms, ev0, ev1);
+            hipEventElapsedTime(&ms, ev0.get(), ev1.get());
             total += ms;
         }
     }

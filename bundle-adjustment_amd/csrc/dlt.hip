@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "../../include/jaicov_dlt.h"
+#include "devbuf.h"
 #include "dlt.h"
 
 #pragma clang fp contract(off)
@@ -551,21 +552,20 @@ extern "C" int jaicov_dlt_adjust(int32_t n_images, const int32_t *obs_begin, con
 
     hipStream_t s;
     if (hipStreamCreate(&s) != hipSuccess) return JAICOV_ERR_DEVICE;
-    int rc = JAICOV_OK;
-    int32_t *d_begin = nullptr, *d_status = nullptr, *d_solves = nullptr;
-    double *d_xy = nullptr, *d_xyz = nullptr, *d_io = nullptr, *d_out = nullptr;
-    uint8_t *d_fixed = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    const size_t ni = (size_t)n_images, no = (size_t)(n_obs > 0 ? n_obs : 1);
-    do {
-        if (hipMalloc(&d_begin, (ni + 1) * sizeof(int32_t)) != hipSuccess || hipMalloc(&d_xy, 2 * no * sizeof(double)) != hipSuccess ||
-            hipMalloc(&d_xyz, 3 * no * sizeof(double)) != hipSuccess || hipMalloc(&d_io, 3 * ni * sizeof(double)) != hipSuccess ||
-            (io_fixed && hipMalloc(&d_fixed, 3 * ni) != hipSuccess) || hipMalloc(&d_out, JAICOV_DLT_OUT_PER_IMAGE * ni * sizeof(double)) != hipSuccess ||
-            hipMalloc(&d_status, ni * sizeof(int32_t)) != hipSuccess || (solves && hipMalloc(&d_solves, ni * sizeof(int32_t)) != hipSuccess)) {
-            rc = JAICOV_ERR_OUT_OF_MEMORY;
-            break;
-        }
+    const int rc = [&]() -> int {      // the owners go before the stream does
+        int32_t *d_begin = nullptr, *d_status = nullptr, *d_solves = nullptr;
+        double *d_xy = nullptr, *d_xyz = nullptr, *d_io = nullptr, *d_out = nullptr;
+        uint8_t *d_fixed = nullptr;
+        DevBag bag;
+        DevEvent ev0, ev1;
+        if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+        const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
+        const size_t ni = (size_t)n_images, no = (size_t)(n_obs > 0 ? n_obs : 1);
+        if (bag.alloc(&d_begin, ni + 1) != hipSuccess || bag.alloc(&d_xy, 2 * no) != hipSuccess || bag.alloc(&d_xyz, 3 * no) != hipSuccess ||
+            bag.alloc(&d_io, 3 * ni) != hipSuccess || (io_fixed && bag.alloc(&d_fixed, 3 * ni) != hipSuccess) ||
+            bag.alloc(&d_out, JAICOV_DLT_OUT_PER_IMAGE * ni) != hipSuccess || bag.alloc(&d_status, ni) != hipSuccess ||
+            (solves && bag.alloc(&d_solves, ni) != hipSuccess))
+            return JAICOV_ERR_OUT_OF_MEMORY;
         hipMemcpyAsync(d_begin, obs_begin, (ni + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
         if (n_obs > 0) {
             hipMemcpyAsync(d_xy, xy, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
@@ -576,17 +576,15 @@ extern "C" int jaicov_dlt_adjust(int32_t n_images, const int32_t *obs_begin, con
         hipEventRecord(e0, s);
         hipLaunchKernelGGL(dlt_adjust_kernel, dim3(n_images), dim3(64), 0, s, d_begin, d_xy, d_xyz, d_io, d_fixed, rs, (int)max_iterations,
                            d_out, d_status, d_solves);
-        if (hipGetLastError() != hipSuccess) { rc = JAICOV_ERR_DEVICE; break; }
+        if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
         hipEventRecord(e1, s);
         hipMemcpyAsync(out, d_out, JAICOV_DLT_OUT_PER_IMAGE * ni * sizeof(double), hipMemcpyDeviceToHost, s);
         hipMemcpyAsync(status, d_status, ni * sizeof(int32_t), hipMemcpyDeviceToHost, s);
         if (solves) hipMemcpyAsync(solves, d_solves, ni * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        if (hipStreamSynchronize(s) != hipSuccess) { rc = JAICOV_ERR_DEVICE; break; }
+        if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
         if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-    } while (0);
-    hipStreamSynchronize(s);
-    hipFree(d_begin); hipFree(d_xy); hipFree(d_xyz); hipFree(d_io); hipFree(d_fixed); hipFree(d_out); hipFree(d_status); hipFree(d_solves);
-    hipEventDestroy(e0); hipEventDestroy(e1);
+        return JAICOV_OK;
+    }();
     hipStreamDestroy(s);
     return rc;
 }

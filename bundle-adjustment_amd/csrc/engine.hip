@@ -22,6 +22,7 @@
 #include "devbuf.h"
 #include "gemm_f64.h"
 #include "reliability.h"
+#include "status.h"
 #include "transform.h"
 
 namespace jaicov {
@@ -199,17 +200,19 @@ __global__ void store_inv_kernel(const double *__restrict__ Q, long ld, int m, d
 struct jaicov_engine {
     std::string err = "";
     int device = 0;
+    // The engine's stream.  Declared before, so destroyed after, every member that synchronises or frees on it: both solvers, dm, the
+    // bag, the events and the states below.  jaicov_neq_destroy relies on that order.
+    StreamLease stream_lease;
+    hipStream_t stream = nullptr;   // ... as every launch names it
     int flow_retries = 0;      // dataflow factorisations that were abandoned and repeated (solve)
     DevBuf<double> ns_work;    // three squares of the inverse's Newton-Schulz step (orders <= 8192, option inverse_refinement)
     int refine_steps = 1;      // iterative refinement of the step (refine.hip): engine option `refinement` / JAICOV_REFINE
     double *d_Braw = nullptr, *d_ref = nullptr;   // unscaled datum rows; rhs | tmp | delta
     DevBuf<double> refP;       // partial-sum table of the refinement's residual
     double last_refine_correction = 0.0;   // max |correction| / max |dx| of the last refinement step (diagnostics)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // assembly: camera-side kernels on a side stream (assemble.hip)
-    StreamLease stream_lease;   // the engine's stream ...
-    hipStream_t stream = nullptr;   // ... as every launch names it
+    DevEvent ev_fork, ev_join;      // assembly: camera-side kernels on a side stream (assemble.hip)
     DevProblem p{};
-    std::vector<void *> allocs;
+    DevBag bag;                     // every device buffer that lives as long as the engine; the raw pointers below and in p, pp, sb are views of it
     // host copies
     jaicov_engine_options opts{};
     int U = 0, Upad = 0, d = 0, datum_flags = 0, n_slots = 0;
@@ -235,7 +238,7 @@ struct jaicov_engine {
     size_t expF_len = 0;             // the length in use (the allocation only grows)
     bool exp_ready = false;          // d_expF belongs to the system accumulated last and has been handed out (jaicov_neq_expansion_buffer)
     int q_order = 0;                 // order of the cofactor matrix on the device (U, or e0 for the reduced one)
-    bool q_reduced = false, solverS_has_inverse = false;
+    bool q_reduced = false;
     std::vector<int> h_blk_images;   // image of every block handled by this engine
     std::vector<int32_t> h_caller_block; // internal image block -> the caller's block index (-1: an ordinary image served as a block); empty: identity
     std::vector<int32_t> h_perm_local;   // per image point of a dense block: engine position -> caller's position inside the block (empty: identity)
@@ -258,7 +261,6 @@ struct jaicov_engine {
     double *d_omega = nullptr, *d_G = nullptr, *d_H = nullptr, *d_F = nullptr, *d_E = nullptr;
     int32_t *d_idx = nullptr;
     DenseSolver solver;
-    bool solver_has_inverse = false;
     enum { ST_NEW, ST_PARAMS, ST_ACCUMULATED, ST_BUILT, ST_SOLVED } state = ST_NEW;
     bool have_Q = false, rows_valid = false, reduced = false;
     bool deterministic = true;   // engine option `deterministic` (default on): fixed summation order in the assembly of the image groups
@@ -269,54 +271,34 @@ struct jaicov_engine {
     double timings[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double create_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // jaicov_neq_create: [0] whole call, [1] host time in the dispersion uploads, [2] dispersions -> weights (wall),
                                                       // [3] validation + tables (the plan, create_plan.h) + structure upload, [4] work buffers + full-order solver, [5] EO pre-elimination buffers + reduced solver
-    hipEvent_t ev[10] = {};
+    DevEvent ev[10];
     bool pp_plain_ok = false;   // the point x point gather may store its strips (see PPGather::plain)
-    hipEvent_t ev_first = nullptr, ev_all = nullptr;   // solve(): first panel's columns / whole matrix copied into the solver
-    hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;       // solve(): device part of a refinement step
-    jaicov::XformState *xform = nullptr;               // result of jaicov_xform_run (transform.hip), kept until the next run / release
-    jaicov::RelState *rel = nullptr;                   // result of jaicov_rel_run (reliability.hip), kept until the next run / release
+    DevEvent ev_first, ev_all;   // solve(): first panel's columns / whole matrix copied into the solver
+    DevEvent ev_r0, ev_r1;       // solve(): device part of a refinement step
+    std::unique_ptr<jaicov::XformState> xform;         // result of jaicov_xform_run (transform.hip), kept until the next run / release
+    std::unique_ptr<jaicov::RelState> rel;             // result of jaicov_rel_run (reliability.hip), kept until the next run / release
     const double *d_ll_diag = nullptr;                 // [2 n_ip + n_dg_rows]: diag(D) of every image coordinate (engine order) and direct row
     double sigma2_acc = 0.0;                           // sigma0^2 of the last accumulate
     double q_sigma2 = 0.0, q_lambda = 0.0;             // sigma0^2 and damping of the build whose system the cofactor matrix inverts
     std::vector<double> q_vals;                        // slot values of that build: the datum rows of jaicov_datum_transform (datum.hip)
-    jaicov::DatumState *datum = nullptr;               // S of the last jaicov_datum_transform and its work buffers
+    std::unique_ptr<jaicov::DatumState> datum;         // S of the last jaicov_datum_transform and its work buffers
 };
-
-#define FAIL(e, code, msg)                 \
-    do {                                   \
-        (e)->err = (msg);                  \
-        return (code);                     \
-    } while (0)
-#define HIPE(e, x)                                                                        \
-    do {                                                                                  \
-        hipError_t _err = (x);                                                            \
-        if (_err != hipSuccess) {                                                         \
-            (e)->err = std::string(#x) + ": " + hipGetErrorString(_err);                  \
-            return _err == hipErrorOutOfMemory ? JAICOV_ERR_OUT_OF_MEMORY : JAICOV_ERR_DEVICE; \
-        }                                                                                 \
-    } while (0)
-#define TRY(x) do { const int _rc = (x); if (_rc) return _rc; } while (0)      // a callee's status (JAICOV_*), passed on
 
 template <typename T, typename P>      // P: T or const T
 static int upload(jaicov_engine *e, const T *src, size_t count, P **dst) {
     *dst = nullptr;
     if (count == 0) return JAICOV_OK;
-    void *ptr = nullptr;
-    HIPE(e, hipMalloc(&ptr, count * sizeof(T)));
-    e->allocs.push_back(ptr);
-    HIPE(e, hipMemcpy(ptr, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *dst = (P *)ptr;
+    T *ptr = nullptr;
+    HIPE(e->err, e->bag.alloc(&ptr, count));
+    HIPE(e->err, hipMemcpy(ptr, src, count * sizeof(T), hipMemcpyHostToDevice));
+    *dst = ptr;
     return JAICOV_OK;
 }
 template <typename T>
 static int dalloc(jaicov_engine *e, size_t count, T **dst, bool zero = false) {
-    *dst = nullptr;
     if (count == 0) count = 1;
-    void *ptr = nullptr;
-    HIPE(e, hipMalloc(&ptr, count * sizeof(T)));
-    e->allocs.push_back(ptr);
-    if (zero) HIPE(e, hipMemset(ptr, 0, count * sizeof(T)));
-    *dst = (T *)ptr;
+    HIPE(e->err, e->bag.alloc(dst, count));
+    if (zero) HIPE(e->err, hipMemset(*dst, 0, count * sizeof(T)));
     return JAICOV_OK;
 }
 
@@ -401,7 +383,7 @@ static int invert_dispersions(jaicov_engine *e, std::vector<DispItem> &items) {
     std::stable_sort(items.begin(), items.end(), [](const DispItem &a, const DispItem &b) { return (a.m + 127) / 128 < (b.m + 127) / 128; });
     StreamLease copy_lease(jaicov::STREAM_PLAIN);      // (goes back to the pool, synchronised, on every way out; so do the events)
     const hipStream_t cstream = copy_lease.get();
-    if (!cstream) FAIL(e, JAICOV_ERR_DEVICE, "no stream for the dispersion uploads");
+    if (!cstream) FAIL(e->err, JAICOV_ERR_DEVICE, "no stream for the dispersion uploads");
     DevEvent ev_up[2], ev_free[2];
     int status = JAICOV_OK;
     std::string msg;
@@ -421,13 +403,14 @@ static int invert_dispersions(jaicov_engine *e, std::vector<DispItem> &items) {
         const bool refine = e->opts.dispersion_refinement >= 0;
         int cap = (int)std::max<size_t>(1, std::min<size_t>(64, ((size_t)4 << 30) / ((refine ? 6 : 3) * msz * sizeof(double))));
         cap = std::min(cap, count);
-        BatchedSpdInverse bi;
+        BatchedSpdInverse bi;             // (its buffers and the bag's are freed at the end of this pass of the loop, both streams synchronised)
+        DevBag stage;
         double *d_stage[2] = {nullptr, nullptr};
         DispDesc *d_desc = nullptr;
         std::vector<DispDesc> desc(count);
         hipError_t he = bi.init(e->stream, mp, cap, refine);
-        for (int b = 0; b < 2 && he == hipSuccess; b++) he = hipMalloc(&d_stage[b], (size_t)cap * mm * sizeof(double));
-        if (he == hipSuccess) he = hipMalloc(&d_desc, (size_t)count * sizeof(DispDesc));
+        for (int b = 0; b < 2 && he == hipSuccess; b++) he = stage.alloc(&d_stage[b], (size_t)cap * mm);
+        if (he == hipSuccess) he = stage.alloc(&d_desc, (size_t)count);
         if (he == hipSuccess) {
             for (int t = 0; t < count; t++) {
                 const int c = t / cap, b = c & 1;
@@ -457,15 +440,13 @@ static int invert_dispersions(jaicov_engine *e, std::vector<DispItem> &items) {
         if (he == hipSuccess) he = hipMemcpyAsync(&info, bi.d_info, sizeof(int), hipMemcpyDeviceToHost, e->stream);
         if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
         hipStreamSynchronize(cstream);
-        bi.release();
-        hipFree(d_stage[0]); hipFree(d_stage[1]); hipFree(d_desc);
         if (he != hipSuccess) { status = he == hipErrorOutOfMemory ? JAICOV_ERR_OUT_OF_MEMORY : JAICOV_ERR_DEVICE; msg = std::string("inversion of the dispersion matrices: ") + hipGetErrorString(he); }
         else if (info != 0) { status = JAICOV_ERR_SINGULAR; msg = "dispersion matrix is not positive definite (MatrixNotSPDException, DOPG:85-86)"; }
         g0 = g1;
     }
     e->create_ms[1] = up_ms;
     e->create_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_all).count();
-    if (status != JAICOV_OK) FAIL(e, status, msg);
+    if (status != JAICOV_OK) FAIL(e->err, status, msg);
     return JAICOV_OK;
 }
 
@@ -477,19 +458,7 @@ extern "C" void jaicov_neq_destroy(jaicov_engine *e) {
     if (!e) return;
     hipSetDevice(e->device);
     if (e->stream) hipStreamSynchronize(e->stream);
-    jaicov::xform_state_free(e->xform);
-    jaicov::rel_state_free(e->rel);
-    jaicov::datum_state_free(e->datum);
-    e->solver.release();
-    e->solverS.release();
-    e->dm.release();
-    for (void *ptr : e->allocs) hipFree(ptr);
-    for (auto &evt : e->ev)
-        if (evt) hipEventDestroy(evt);
-    for (hipEvent_t evt : {e->ev_fork, e->ev_join, e->ev_first, e->ev_all, e->ev_r0, e->ev_r1})
-        if (evt) hipEventDestroy(evt);
-    e->stream_lease = StreamLease();
-    delete e;
+    delete e;      // every member frees what it holds; the stream's lease goes last (see the member)
 }
 
 // ---- engine creation, second stage: what happens on the device.  The first stage, every decision and table that needs
@@ -497,14 +466,11 @@ extern "C" void jaicov_neq_destroy(jaicov_engine *e) {
 static int acquire_stream_and_events(jaicov_engine *e) {
     e->stream_lease = StreamLease(jaicov::STREAM_PLAIN);
     e->stream = e->stream_lease.get();
-    if (!e->stream) FAIL(e, JAICOV_ERR_DEVICE, "no stream");
-    for (auto &evt : e->ev) HIPE(e, hipEventCreate(&evt));
-    HIPE(e, hipEventCreateWithFlags(&e->ev_first, hipEventDisableTiming));
-    HIPE(e, hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-    HIPE(e, hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-    HIPE(e, hipEventCreateWithFlags(&e->ev_all, hipEventDisableTiming));
-    HIPE(e, hipEventCreate(&e->ev_r0));
-    HIPE(e, hipEventCreate(&e->ev_r1));
+    if (!e->stream) FAIL(e->err, JAICOV_ERR_DEVICE, "no stream");
+    for (auto &evt : e->ev) HIPE(e->err, evt.create());
+    for (DevEvent *evt : {&e->ev_first, &e->ev_fork, &e->ev_join, &e->ev_all}) HIPE(e->err, evt->create(hipEventDisableTiming));
+    HIPE(e->err, e->ev_r0.create());
+    HIPE(e->err, e->ev_r1.create());
     return JAICOV_OK;
 }
 
@@ -673,7 +639,7 @@ static int alloc_work_buffers(jaicov_engine *e, const CreatePlan &pl) {
     TRY(dalloc(e, (size_t)64, &e->d_E, true));
     TRY(dalloc(e, (size_t)1, &e->d_omega, true));
     TRY(dalloc(e, (size_t)std::max(1, e->n_blk_list) * 16 * KC_MAX * (KC_MAX + 1), &e->d_cc_partial));
-    HIPE(e, e->solver.init(e->stream, e->Upad, false, true));
+    HIPE(e->err, e->solver.init(e->stream, e->Upad, false, true));
     return JAICOV_OK;
 }
 
@@ -696,7 +662,7 @@ static int init_elimination(jaicov_engine *e, const CreatePlan &pl) {
     e->e0 = pl.e0;
     // the solver of the reduced system is created here, with its streams, not at the first solve: stream creation
     // order matters when the host also runs RCCL (bench.py: communicator after the engine)
-    HIPE(e, e->solverS.init(e->stream, ((pl.e0 + 127) / 128) * 128, false, true, &e->solver));      // never at work beside the full-order solver: shares its side streams
+    HIPE(e->err, e->solverS.init(e->stream, ((pl.e0 + 127) / 128) * 128, false, true, &e->solver));      // never at work beside the full-order solver: shares its side streams
     e->solverS_ready = true;
     return JAICOV_OK;
 }
@@ -722,16 +688,16 @@ static double ms_since(std::chrono::steady_clock::time_point t) {
 }
 
 static int create_impl(jaicov_engine *e, const jaicov_problem_desc *desc) {
-    HIPE(e, hipSetDevice(e->device));
+    HIPE(e->err, hipSetDevice(e->device));
     e->deterministic = e->opts.deterministic >= 0;      // 0 = default = ON since round 4 (costs 0.3 ms per pass at config 4); < 0: arrival-order sums
     e->refine_steps = e->opts.refinement == 0 ? 1 : (e->opts.refinement < 0 ? 0 : std::min(e->opts.refinement, 4));
     hipDeviceProp_t prop;
-    HIPE(e, hipGetDeviceProperties(&prop, e->device));
+    HIPE(e->err, hipGetDeviceProperties(&prop, e->device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        FAIL(e, JAICOV_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+        FAIL(e->err, JAICOV_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
     auto t = std::chrono::steady_clock::now();
     CreatePlan pl;
-    if (!build_create_plan(pl, *desc, e->opts, assembly_form())) FAIL(e, pl.status, pl.err);
+    if (!build_create_plan(pl, *desc, e->opts, assembly_form())) FAIL(e->err, pl.status, pl.err);
     adopt_decisions(e, pl);
     TRY(acquire_stream_and_events(e));      // a refused description has created nothing on the device
     TRY(upload_structure(e, pl));
@@ -742,13 +708,13 @@ static int create_impl(jaicov_engine *e, const jaicov_problem_desc *desc) {
     e->create_ms[4] = ms_since(t);
     t = std::chrono::steady_clock::now();
     if (pl.dense_mode) {
-        HIPE(e, e->dm.init(pl.max_m, pl.max_k1, e->n_blk_list, e->opts.assembly_mode == 2));
+        HIPE(e->err, e->dm.init(pl.max_m, pl.max_k1, e->n_blk_list, e->opts.assembly_mode == 2));
         e->dense_mode = true;
     } else if (pl.schur_ok)
         TRY(init_elimination(e, pl));
     e->create_ms[5] = ms_since(t);
     keep_host_tables(e, pl);
-    HIPE(e, hipStreamSynchronize(e->stream));
+    HIPE(e->err, hipStreamSynchronize(e->stream));
     return JAICOV_OK;
 }
 
@@ -782,10 +748,10 @@ extern "C" size_t jaicov_neq_packed_length(const jaicov_engine *e) { return e ? 
 
 extern "C" int jaicov_neq_set_parameters(jaicov_engine *e, const double *slots, size_t n) {
     if (!e || !slots || n != (size_t)e->n_slots) return JAICOV_ERR_BAD_ARGUMENT;
-    HIPE(e, hipSetDevice(e->device));
+    HIPE(e->err, hipSetDevice(e->device));
     memcpy(e->h_vals.data(), slots, n * sizeof(double));
-    HIPE(e, hipMemcpyAsync(e->d_vals, e->h_vals.data(), n * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    HIPE(e, hipStreamSynchronize(e->stream));
+    HIPE(e->err, hipMemcpyAsync(e->d_vals, e->h_vals.data(), n * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIPE(e->err, hipStreamSynchronize(e->stream));
     e->rows_valid = false;
     if (e->state == jaicov_engine::ST_NEW) e->state = jaicov_engine::ST_PARAMS;
     return JAICOV_OK;
@@ -799,22 +765,22 @@ extern "C" int jaicov_neq_get_parameters(jaicov_engine *e, double *slots, size_t
 
 static int ensure_rows(jaicov_engine *e) {
     if (e->rows_valid) return JAICOV_OK;
-    HIPE(e, launch_rows(e->stream, e->p, e->d_vals, e->ip0, e->ip_count, e->d_rowsA, e->d_rowsW));
+    HIPE(e->err, launch_rows(e->stream, e->p, e->d_vals, e->ip0, e->ip_count, e->d_rowsA, e->d_rowsW));
     e->rows_valid = true;
     return JAICOV_OK;
 }
 
 extern "C" int jaicov_neq_accumulate(jaicov_engine *e, double sigma2) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    if (e->state == jaicov_engine::ST_NEW) FAIL(e, JAICOV_ERR_BAD_STATE, "set_parameters first");
-    if (!(sigma2 > 0)) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "variance of unit weight must be positive (DOPG:68-69)");
-    HIPE(e, hipSetDevice(e->device));
+    if (e->state == jaicov_engine::ST_NEW) FAIL(e->err, JAICOV_ERR_BAD_STATE, "set_parameters first");
+    if (!(sigma2 > 0)) FAIL(e->err, JAICOV_ERR_BAD_ARGUMENT, "variance of unit weight must be positive (DOPG:68-69)");
+    HIPE(e->err, hipSetDevice(e->device));
     e->reduced = false;          // a packed buffer of an earlier accumulate must not be unpacked over this one
     e->sigma2_acc = sigma2;
     const size_t sq = (size_t)e->Upad * e->Upad;
-    HIPE(e, hipEventRecord(e->ev[0], e->stream));
+    HIPE(e->err, hipEventRecord(e->ev[0].get(), e->stream));
     TRY(ensure_rows(e));
-    HIPE(e, hipEventRecord(e->ev[1], e->stream));
+    HIPE(e->err, hipEventRecord(e->ev[1].get(), e->stream));
     e->schur_active = e->schur_ok && e->inverse_mode_next != JAICOV_INVERT_FULL;
     // The point x point gather owns every entry of rows cmin..cmax from column cmin on: when it runs before everything
     // else that adds into that region it stores its strips, and the region needs neither zeroing nor reading back.
@@ -834,34 +800,34 @@ extern "C" int jaicov_neq_accumulate(jaicov_engine *e, double sigma2) {
             zero_rows(slo, std::min(shi + 1, rows), slo);
             zero_rows(std::min(shi + 1, rows), rows, rows);
         }
-        HIPE(e, hipMemsetAsync(e->d_N + sq, 0, (size_t)e->Upad * sizeof(double), e->stream));
+        HIPE(e->err, hipMemsetAsync(e->d_N + sq, 0, (size_t)e->Upad * sizeof(double), e->stream));
     }
     if (!plain)
-        HIPE(e, launch_assemble_small(e->stream, e->p, e->d_seg_begin, e->d_seg_end, e->n_seg, e->d_rowsA, e->d_rowsW, sigma2, e->d_N, e->d_n));
+        HIPE(e->err, launch_assemble_small(e->stream, e->p, e->d_seg_begin, e->d_seg_end, e->n_seg, e->d_rowsA, e->d_rowsW, sigma2, e->d_N, e->d_n));
     SchurBufs sb = e->sb;
     sb.active = e->schur_active;
     sb.lambda = e->lambda_acc;
     if (e->schur_active) {
-        HIPE(e, hipMemsetAsync(e->sb.info, 0, sizeof(int), e->stream));
-        HIPE(e, hipMemsetAsync(e->sb.diagcorr, 0, (size_t)e->Upad * sizeof(double), e->stream));
+        HIPE(e->err, hipMemsetAsync(e->sb.info, 0, sizeof(int), e->stream));
+        HIPE(e->err, hipMemsetAsync(e->sb.diagcorr, 0, (size_t)e->Upad * sizeof(double), e->stream));
     }
     if (e->dense_mode) {
         float ms = 0.f;
-        HIPE(e, e->dm.assemble(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->d_rowsA, e->d_rowsW, sigma2, e->d_N, e->d_n,
+        HIPE(e->err, e->dm.assemble(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->d_rowsA, e->d_rowsW, sigma2, e->d_N, e->d_n,
                                e->solver.profile ? &ms : nullptr));
         if (e->solver.profile) { e->dm_stat_passes += 1.0; e->dm_stat_ms += ms; e->dm_stat_flops += e->dm_flops_per_pass; }
     } else {
         PPGather ppg = e->pp;
         ppg.plain = plain ? 1 : 0;
         ppg.ug = sb.active ? sb.Ug : nullptr;
-        HIPE(e, launch_assemble_blocks(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->max_m, e->d_blk_ip_list, e->n_blk_ip,
+        HIPE(e->err, launch_assemble_blocks(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->max_m, e->d_blk_ip_list, e->n_blk_ip,
                                        e->d_rowsA, e->d_rowsW, e->d_T, sigma2, e->d_N, e->d_n, ppg, sb, e->d_cc_partial,
-                                       e->solver.pstream, e->ev_fork, e->ev_join));   // side stream: the solver's (idle during the assembly)
+                                       e->solver.pstream, e->ev_fork.get(), e->ev_join.get()));   // side stream: the solver's (idle during the assembly)
     }
     if (plain)   // the images outside the dense blocks come after the stores
-        HIPE(e, launch_assemble_small(e->stream, e->p, e->d_seg_begin, e->d_seg_end, e->n_seg, e->d_rowsA, e->d_rowsW, sigma2, e->d_N, e->d_n));
-    if (e->opts.apply_shared) HIPE(e, launch_shared_groups(e->stream, e->p, e->d_vals, sigma2, e->d_N, e->d_n, nullptr, nullptr));
-    HIPE(e, hipEventRecord(e->ev[2], e->stream));
+        HIPE(e->err, launch_assemble_small(e->stream, e->p, e->d_seg_begin, e->d_seg_end, e->n_seg, e->d_rowsA, e->d_rowsW, sigma2, e->d_N, e->d_n));
+    if (e->opts.apply_shared) HIPE(e->err, launch_shared_groups(e->stream, e->p, e->d_vals, sigma2, e->d_N, e->d_n, nullptr, nullptr));
+    HIPE(e->err, hipEventRecord(e->ev[2].get(), e->stream));
     e->exp_ready = false;            // the expansion buffer of an earlier pass is stale now
     e->state = jaicov_engine::ST_ACCUMULATED;
     e->have_Q = false;
@@ -881,7 +847,7 @@ static int datum_rows(jaicov_engine *e, const uint8_t *mask, const double *vals,
         x0 += vals[3 * pt]; y0 += vals[3 * pt + 1]; z0 += vals[3 * pt + 2];
         count++;
     }
-    if (count < 3) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "not enough object points to realise the frame datum (BA:515-516)");
+    if (count < 3) FAIL(e->err, JAICOV_ERR_BAD_ARGUMENT, "not enough object points to realise the frame datum (BA:515-516)");
     x0 /= (double)count; y0 /= (double)count; z0 /= (double)count;
     int row = 0;
     const int f = e->datum_flags;
@@ -920,26 +886,26 @@ static int datum_rows_host(jaicov_engine *e) {
 extern "C" int jaicov_neq_finalize(jaicov_engine *e, double sigma2, double lambda, int simulation) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     (void)sigma2;
-    if (e->state != jaicov_engine::ST_ACCUMULATED) FAIL(e, JAICOV_ERR_BAD_STATE, "accumulate first");
-    HIPE(e, hipSetDevice(e->device));
+    if (e->state != jaicov_engine::ST_ACCUMULATED) FAIL(e->err, JAICOV_ERR_BAD_STATE, "accumulate first");
+    HIPE(e->err, hipSetDevice(e->device));
     TRY(datum_rows_host(e));
     if (e->reduced) {   // the host has summed the packed buffer over ranks: bring it back into the square
         const int Ua = e->schur_active ? e->e0 : e->U;
         const size_t len = (size_t)Ua * (Ua + 1) / 2;
         hipLaunchKernelGGL(unpack_kernel, dim3((Ua + 255) / 256, std::max(Ua, 1)), dim3(256), 0, e->stream, e->d_packed, (long)e->Upad, Ua, e->d_N);
-        HIPE(e, hipMemcpyAsync(e->d_n, e->d_packed + len, (size_t)Ua * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+        HIPE(e->err, hipMemcpyAsync(e->d_n, e->d_packed + len, (size_t)Ua * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
         if (e->schur_active)   // what the EO elimination took from the diagonal, summed over the ranks like N itself (LM damping)
-            HIPE(e, hipMemcpyAsync(e->sb.diagcorr, e->d_packed + len + Ua, (size_t)Ua * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+            HIPE(e->err, hipMemcpyAsync(e->sb.diagcorr, e->d_packed + len + Ua, (size_t)Ua * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
         e->reduced = false;
     }
     if (e->schur_active && lambda != e->lambda_acc && (lambda > 0 || e->lambda_acc > 0))
-        FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "EO pre-elimination: pass the damping value to accumulate2()/build() as well");
+        FAIL(e->err, JAICOV_ERR_BAD_ARGUMENT, "EO pre-elimination: pass the damping value to accumulate2()/build() as well");
     hipLaunchKernelGGL(damp_and_precond_kernel, dim3((e->Upad + 255) / 256), dim3(256), 0, e->stream, e->d_N, (long)e->Upad,
                        e->schur_active ? e->e0 : e->U, e->Upad, e->d, lambda > 0 ? lambda : 0.0, e->d_V,
                        e->schur_active ? e->sb.diagcorr : nullptr);
-    if (simulation) HIPE(e, hipMemsetAsync(e->d_n, 0, e->Upad * sizeof(double), e->stream));   // BA:830-831
+    if (simulation) HIPE(e->err, hipMemsetAsync(e->d_n, 0, e->Upad * sizeof(double), e->stream));   // BA:830-831
     e->sim_built = simulation != 0;
-    HIPE(e, hipEventRecord(e->ev[3], e->stream));
+    HIPE(e->err, hipEventRecord(e->ev[3].get(), e->stream));
     e->lambda_used = lambda;
     e->state = jaicov_engine::ST_BUILT;
     return JAICOV_OK;
@@ -948,16 +914,8 @@ extern "C" int jaicov_neq_finalize(jaicov_engine *e, double sigma2, double lambd
 // buffers of the inverse (W = L^-1 and Q, two squares of the solver's order) of the solver that factorises; for the effective mode
 // FULL_EXPANDED also the Q of the full-order solver, where the expanded matrix lives
 static int ensure_inverse_buffers(jaicov_engine *e, bool reduced_system, int mode) {
-    DenseSolver &slv = reduced_system ? e->solverS : e->solver;
-    bool &has_inv = reduced_system ? e->solverS_has_inverse : e->solver_has_inverse;
-    if (!has_inv) {
-        const size_t sq = (size_t)slv.n * slv.ld * sizeof(double);
-        HIPE(e, hipMalloc(&slv.W, sq));
-        if (!slv.Q) HIPE(e, hipMalloc(&slv.Q, sq));
-        has_inv = true;
-    }
-    if (mode == JAICOV_INVERT_FULL_EXPANDED && !e->solver.Q)
-        HIPE(e, hipMalloc(&e->solver.Q, (size_t)e->solver.n * e->solver.ld * sizeof(double)));
+    HIPE(e->err, (reduced_system ? e->solverS : e->solver).reserve_inverse(true));
+    if (mode == JAICOV_INVERT_FULL_EXPANDED) HIPE(e->err, e->solver.reserve_inverse(false));
     return JAICOV_OK;
 }
 
@@ -987,7 +945,7 @@ extern "C" int jaicov_neq_prepare_inverse(jaicov_engine *e, int inverse_follows)
     // the inverse's buffers are allocated HERE, when the final pass is announced (BA:250: known before the build), not inside
     // the solve: hipMalloc of 2 x 1.8 .. 2.6 GB cost the first inverting solve 45 ms at config 4
     if (inverse_follows == JAICOV_INVERT_NONE) return JAICOV_OK;
-    HIPE(e, hipSetDevice(e->device));
+    HIPE(e->err, hipSetDevice(e->device));
     const bool reduced = e->schur_ok && (inverse_follows == JAICOV_INVERT_REDUCED || inverse_follows == JAICOV_INVERT_FULL_EXPANDED) && e->solverS_ready;
     return ensure_inverse_buffers(e, reduced, inverse_follows);
 }
@@ -1017,19 +975,19 @@ extern "C" int jaicov_neq_build(jaicov_engine *e, double sigma2, double lambda, 
 
 static int reduce_buffer_impl(jaicov_engine *e, void **device_ptr, size_t *count, bool sync) {
     if (!e || !device_ptr || !count) return JAICOV_ERR_BAD_ARGUMENT;
-    if (e->state != jaicov_engine::ST_ACCUMULATED) FAIL(e, JAICOV_ERR_BAD_STATE, "accumulate first");
-    HIPE(e, hipSetDevice(e->device));
+    if (e->state != jaicov_engine::ST_ACCUMULATED) FAIL(e->err, JAICOV_ERR_BAD_STATE, "accumulate first");
+    HIPE(e->err, hipSetDevice(e->device));
     // packed lower triangle (== UPLO='U' packed) followed by n: one contiguous array the collective sums as it is.
     // With the EO pre-elimination only the reduced system (order e0) exists.
     const int Ua = e->schur_active ? e->e0 : e->U;
     const size_t len = (size_t)Ua * (Ua + 1) / 2;
     if (!e->d_packed) TRY(dalloc(e, (size_t)e->U * (e->U + 1) / 2 + 2 * (size_t)e->U, &e->d_packed));
     hipLaunchKernelGGL(pack_kernel, dim3((Ua + 255) / 256, std::max(Ua, 1)), dim3(256), 0, e->stream, e->d_N, (long)e->Upad, Ua, e->d_packed);
-    HIPE(e, hipMemcpyAsync(e->d_packed + len, e->d_n, (size_t)Ua * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    HIPE(e->err, hipMemcpyAsync(e->d_packed + len, e->d_n, (size_t)Ua * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
     // with the EO pre-elimination the LM damping needs diag(N) - diag(N_reduced), also a sum over the ranks' images
     if (e->schur_active)
-        HIPE(e, hipMemcpyAsync(e->d_packed + len + Ua, e->sb.diagcorr, (size_t)Ua * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-    if (sync) HIPE(e, hipStreamSynchronize(e->stream));   // the caller's collective runs on its own stream
+        HIPE(e->err, hipMemcpyAsync(e->d_packed + len + Ua, e->sb.diagcorr, (size_t)Ua * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    if (sync) HIPE(e->err, hipStreamSynchronize(e->stream));   // the caller's collective runs on its own stream
     e->reduced = true;
     *device_ptr = e->d_packed;
     *count = len + Ua + (e->schur_active ? (size_t)Ua : 0);
@@ -1111,7 +1069,7 @@ struct Solve {
         if (invert == JAICOV_INVERT_FULL_EXPANDED && !schur) invert = JAICOV_INVERT_FULL;     // the system at hand was assembled unreduced
         expand = invert == JAICOV_INVERT_FULL_EXPANDED;
         if (schur && invert == JAICOV_INVERT_FULL)
-            FAIL(e, JAICOV_ERR_BAD_STATE, "the normal equations were assembled with the EO blocks pre-eliminated: call "
+            FAIL(e->err, JAICOV_ERR_BAD_STATE, "the normal equations were assembled with the EO blocks pre-eliminated: call "
                                           "jaicov_neq_prepare_inverse(e, JAICOV_INVERT_FULL) before the build whose solve shall invert");
         slv.profile = e->solver.profile;
         slv.flops_order = (double)U;
@@ -1125,10 +1083,10 @@ struct Solve {
     // What d = 0 does save is the round trip between the substitution and the first refinement step (factor_and_substitute).
     int border_rows() {
         int hinfo = 0;   // status of the per-image EO eliminations, fetched in the same round trip
-        HIPE(e, hipMemcpyAsync(e->h_V.data(), e->d_V, Upad * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-        if (schur) HIPE(e, hipMemcpyAsync(&hinfo, e->sb.info, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-        HIPE(e, hipStreamSynchronize(e->stream));
-        if (hinfo != 0) FAIL(e, JAICOV_ERR_SINGULAR, "exterior orientation block of image " + std::to_string(hinfo - 1000000) + " is not positive definite");
+        HIPE(e->err, hipMemcpyAsync(e->h_V.data(), e->d_V, Upad * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        if (schur) HIPE(e->err, hipMemcpyAsync(&hinfo, e->sb.info, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        HIPE(e->err, hipStreamSynchronize(e->stream));
+        if (hinfo != 0) FAIL(e->err, JAICOV_ERR_SINGULAR, "exterior orientation block of image " + std::to_string(hinfo - 1000000) + " is not positive definite");
         Bh.assign((size_t)8 * Upad, 0.0);
         for (int a = 0; a < d; a++) {
             double s = 0.0;
@@ -1137,12 +1095,12 @@ struct Solve {
                 Bh[(size_t)a * Upad + c] = v;
                 s += v * v;
             }
-            if (!(s > 0.0)) FAIL(e, JAICOV_ERR_SINGULAR, "empty datum condition row");
+            if (!(s > 0.0)) FAIL(e->err, JAICOV_ERR_SINGULAR, "empty datum condition row");
             R[a] = 1.0 / sqrt(s);
             for (int c = d; c < U; c++) Bh[(size_t)a * Upad + c] *= R[a];
         }
-        if (d > 0) HIPE(e, hipMemcpyAsync(e->d_B, Bh.data(), (size_t)d * Upad * sizeof(double), hipMemcpyHostToDevice, e->stream));
-        HIPE(e, hipEventRecord(e->ev[4], e->stream));
+        if (d > 0) HIPE(e->err, hipMemcpyAsync(e->d_B, Bh.data(), (size_t)d * Upad * sizeof(double), hipMemcpyHostToDevice, e->stream));
+        HIPE(e->err, hipEventRecord(e->ev[4].get(), e->stream));
         return JAICOV_OK;
     }
     // ---- iterative refinement (refine.hip): residual of the unscaled bordered system in two-fold precision, one forward and
@@ -1152,25 +1110,25 @@ struct Solve {
     // The device's part of a step: refine_begin, then whatever gives d_dx its value, then refine_step.
     int refine_begin() {
         const int nbk = Up / 128;
-        HIPE(e, e->refP.reserve((size_t)nbk * nbk * 256));      // ahead of the event: an allocation is no part of the step's time
-        HIPE(e, hipEventRecord(e->ev_r0, e->stream));
+        HIPE(e->err, e->refP.reserve((size_t)nbk * nbk * 256));      // ahead of the event: an allocation is no part of the step's time
+        HIPE(e->err, hipEventRecord(e->ev_r0.get(), e->stream));
         return JAICOV_OK;
     }
     // residual of d_dx, delta = M^-1 residual, and delta on its way to the host (complete once the stream has been synchronised)
     int refine_step(const RefineBorder &bd, std::vector<double> &delta) {
         double *d_rhs = e->d_ref, *d_tmp = e->d_ref + Upad, *d_delta = e->d_ref + 2 * (size_t)Upad;
-        HIPE(e, launch_residual_dd(e->stream, e->d_N, (long)Upad, U, d, Up, e->d_dx, e->d_n, e->d_V, e->d_Braw, e->d_B, (long)Upad,
+        HIPE(e->err, launch_residual_dd(e->stream, e->d_N, (long)Upad, U, d, Up, e->d_dx, e->d_n, e->d_V, e->d_Braw, e->d_B, (long)Upad,
                                    bd, e->refP.get(), d_rhs));
-        HIPE(e, slv.solve_rhs(d_rhs, d_tmp, d_delta));
-        HIPE(e, hipEventRecord(e->ev_r1, e->stream));
+        HIPE(e->err, slv.solve_rhs(d_rhs, d_tmp, d_delta));
+        HIPE(e->err, hipEventRecord(e->ev_r1.get(), e->stream));
         delta.assign((size_t)Up, 0.0);
-        HIPE(e, hipMemcpyAsync(delta.data(), d_delta, delta.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        HIPE(e->err, hipMemcpyAsync(delta.data(), d_delta, delta.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
         return JAICOV_OK;
     }
     // a completed step: its time, dx += the correction that belongs to delta (d = 0: V delta), max |correction| / max |dx|
     int apply_correction(const RefineBorder &bd, const std::vector<double> &dl, double *dx_out) {
         float ms1 = 0.f;
-        hipEventElapsedTime(&ms1, e->ev_r0, e->ev_r1);
+        hipEventElapsedTime(&ms1, e->ev_r0.get(), e->ev_r1.get());
         refine_ms += ms1;
         double dk[7] = {0, 0, 0, 0, 0, 0, 0};
         border_multipliers(dl.data(), bd.rk, dk);
@@ -1179,7 +1137,7 @@ struct Solve {
             double dy = dl[c];
             for (int a = 0; a < d; a++) dy -= X[(size_t)(1 + a) * vs + c] * dk[a];
             const double corr = e->h_V[c] * dy;
-            if (!std::isfinite(corr)) FAIL(e, JAICOV_ERR_NOT_FINITE, "non-finite refinement step");
+            if (!std::isfinite(corr)) FAIL(e->err, JAICOV_ERR_NOT_FINITE, "non-finite refinement step");
             dx_out[c] += corr;
             cmax = std::max(cmax, fabs(corr)); xmax = std::max(xmax, fabs(dx_out[c]));
         }
@@ -1200,27 +1158,27 @@ struct Solve {
         const int c1 = std::min(slv.first_panel_cols(), Up);
         int info = 0;
         for (int attempt = 0;; attempt++) {
-            HIPE(e, slv.begin_refactor());      // the side stream's premultiply of the last pass may still read the old factor: nothing writes L before this
+            HIPE(e->err, slv.begin_refactor());      // the side stream's premultiply of the last pass may still read the old factor: nothing writes L before this
             if (!fused)
                 hipLaunchKernelGGL(scale_copy_kernel, dim3((c1 + 255) / 256, Up), dim3(256), 0, e->stream, e->d_N, (long)Upad, slv.L, ld, U,
                                    Up, d, e->d_V, e->d_B, Upad, 0, c1);
-            HIPE(e, hipMemsetAsync(slv.rhs_row(0), 0, (size_t)128 * ld * sizeof(double), e->stream));
+            HIPE(e->err, hipMemsetAsync(slv.rhs_row(0), 0, (size_t)128 * ld * sizeof(double), e->stream));
             hipLaunchKernelGGL(scale_vec_kernel, dim3((Up + 255) / 256), dim3(256), 0, e->stream, e->d_n, e->d_V, slv.rhs_row(0), U, Up, d);
             if (d > 0)
-                HIPE(e, hipMemcpy2DAsync(slv.rhs_row(1), (size_t)ld * sizeof(double), e->d_B, (size_t)Upad * sizeof(double),
+                HIPE(e->err, hipMemcpy2DAsync(slv.rhs_row(1), (size_t)ld * sizeof(double), e->d_B, (size_t)Upad * sizeof(double),
                                          (size_t)Up * sizeof(double), (size_t)d, hipMemcpyDeviceToDevice, e->stream));
-            HIPE(e, hipEventRecord(e->ev_first, e->stream));
+            HIPE(e->err, hipEventRecord(e->ev_first.get(), e->stream));
             if (!fused && c1 < Up)
                 hipLaunchKernelGGL(scale_copy_kernel, dim3((Up - c1 + 255) / 256, Up), dim3(256), 0, e->stream, e->d_N, (long)Upad, slv.L,
                                    ld, U, Up, d, e->d_V, e->d_B, Upad, c1, Up);
-            HIPE(e, hipEventRecord(e->ev_all, e->stream));
+            HIPE(e->err, hipEventRecord(e->ev_all.get(), e->stream));
             if (fused) slv.flow.set_source(e->d_N, (long)Upad, e->d_V, e->d_B, Upad, d, U);
-            HIPE(e, slv.potrf(e->ev_first, e->ev_all));
-            HIPE(e, hipEventRecord(e->ev[5], e->stream));
-            HIPE(e, slv.backsolve_aug(e->d_G, vs, nrhs));           // G <- L^-T (L^-1 Y)   (row 0: y~, rows 1..d: G^)
-            HIPE(e, hipEventRecord(e->ev[6], e->stream));
+            HIPE(e->err, slv.potrf(e->ev_first.get(), e->ev_all.get()));
+            HIPE(e->err, hipEventRecord(e->ev[5].get(), e->stream));
+            HIPE(e->err, slv.backsolve_aug(e->d_G, vs, nrhs));           // G <- L^-T (L^-1 Y)   (row 0: y~, rows 1..d: G^)
+            HIPE(e->err, hipEventRecord(e->ev[6].get(), e->stream));
             X.assign((size_t)nrhs * vs, 0.0);
-            HIPE(e, hipMemcpyAsync(X.data(), e->d_G, X.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+            HIPE(e->err, hipMemcpyAsync(X.data(), e->d_G, X.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
             fast_refined = false;
             if (d == 0 && e->refine_steps >= 1 && !e->sim_built) {
                 // first refinement step without the host: dx = V y on the device, residual of the unscaled system in two-fold precision,
@@ -1238,8 +1196,8 @@ struct Solve {
             }
             break;
         }
-        if (info < 0) FAIL(e, JAICOV_ERR_DEVICE, "factorisation did not complete on the device (code " + std::to_string(info) + ")");
-        if (info != 0) FAIL(e, JAICOV_ERR_SINGULAR, "normal-equation matrix is singular / not positive definite at pivot " + std::to_string(info));
+        if (info < 0) FAIL(e->err, JAICOV_ERR_DEVICE, "factorisation did not complete on the device (code " + std::to_string(info) + ")");
+        if (info != 0) FAIL(e->err, JAICOV_ERR_SINGULAR, "normal-equation matrix is singular / not positive definite at pivot " + std::to_string(info));
         return JAICOV_OK;
     }
     // ---- rank-d border algebra on the host ---------------------------------------------------------------------
@@ -1249,7 +1207,7 @@ struct Solve {
         if (d > 0) {
             for (int a = 0; a < d; a++)
                 for (int b = 0; b < d; b++) Sm[a * d + b] = border_dot(a, &X[(size_t)(1 + b) * vs]);
-            if (!small_inverse(d, Sm, Sinv)) FAIL(e, JAICOV_ERR_SINGULAR, "datum conditions are linearly dependent");
+            if (!small_inverse(d, Sm, Sinv)) FAIL(e->err, JAICOV_ERR_SINGULAR, "datum conditions are linearly dependent");
             const double no_rk[7] = {0, 0, 0, 0, 0, 0, 0};
             border_multipliers(X.data(), no_rk, kh);
             for (int c = d; c < U; c++) {
@@ -1260,7 +1218,7 @@ struct Solve {
         }
         for (int c = 0; c < U; c++) dx_out[c] = c < d ? R[c] * kh[c] : e->h_V[c] * y[c];
         for (int c = 0; c < U; c++)
-            if (!std::isfinite(dx_out[c])) FAIL(e, JAICOV_ERR_NOT_FINITE, "non-finite step");
+            if (!std::isfinite(dx_out[c])) FAIL(e->err, JAICOV_ERR_NOT_FINITE, "non-finite step");
         return JAICOV_OK;
     }
     // the step the device took on its own (d = 0: no border algebra), then the others with the host in between
@@ -1277,20 +1235,20 @@ struct Solve {
             }
             TRY(refine_begin());
             if (d > 0 && step == 0)
-                HIPE(e, hipMemcpyAsync(e->d_Braw, e->hB.data(), (size_t)d * Upad * sizeof(double), hipMemcpyHostToDevice, e->stream));
-            HIPE(e, hipMemcpyAsync(e->d_dx, dx_out, (size_t)U * sizeof(double), hipMemcpyHostToDevice, e->stream));
+                HIPE(e->err, hipMemcpyAsync(e->d_Braw, e->hB.data(), (size_t)d * Upad * sizeof(double), hipMemcpyHostToDevice, e->stream));
+            HIPE(e->err, hipMemcpyAsync(e->d_dx, dx_out, (size_t)U * sizeof(double), hipMemcpyHostToDevice, e->stream));
             std::vector<double> dl;
             TRY(refine_step(bd, dl));
-            HIPE(e, hipStreamSynchronize(e->stream));
+            HIPE(e->err, hipStreamSynchronize(e->stream));
             TRY(apply_correction(bd, dl, dx_out));
         }
         return JAICOV_OK;
     }
     // EO step of every image of this engine: dx_E = L_E^-T U' (w - A_r dx_R), from d_dx into d_xE   (schur.hip)
     int eo_backsub() {
-        HIPE(e, launch_omega(e->stream, e->p, e->d_in_block, e->ip0, e->ip_count, e->d_blk_list, 0, e->max_m, e->d_rowsA,
+        HIPE(e->err, launch_omega(e->stream, e->p, e->d_in_block, e->ip0, e->ip_count, e->d_blk_list, 0, e->max_m, e->d_rowsA,
                              e->d_rowsW, e->d_dx, 1.0, e->d_vbuf, e->d_omega));
-        HIPE(e, launch_schur_backsub(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->sb.U, e->sb.Linv, e->d_vbuf, e->d_xE));
+        HIPE(e->err, launch_schur_backsub(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->sb.U, e->sb.Linv, e->d_vbuf, e->d_xE));
         return JAICOV_OK;
     }
     // Round 5: once in ~10 runs of the GPU test-suite a solve returned an EO step of EXACT zeros for every image (N, n and the reduced
@@ -1301,15 +1259,15 @@ struct Solve {
         for (int img : e->h_blk_images)
             for (int k = 0; k < 6 && all_zero; k++) all_zero = xE[(size_t)6 * img + k] == 0.0;
         if (!all_zero) return JAICOV_OK;
-        HIPE(e, hipDeviceSynchronize());
-        HIPE(e, hipMemcpy(xE.data(), e->d_xE, xE.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPE(e->err, hipDeviceSynchronize());
+        HIPE(e->err, hipMemcpy(xE.data(), e->d_xE, xE.size() * sizeof(double), hipMemcpyDeviceToHost));
         bool still = true;
         for (int img : e->h_blk_images)
             for (int k = 0; k < 6 && still; k++) still = xE[(size_t)6 * img + k] == 0.0;
         if (still) {      // the kernel itself left zeros: run the two kernels once more
             TRY(eo_backsub());
-            HIPE(e, hipStreamSynchronize(e->stream));
-            HIPE(e, hipMemcpy(xE.data(), e->d_xE, xE.size() * sizeof(double), hipMemcpyDeviceToHost));
+            HIPE(e->err, hipStreamSynchronize(e->stream));
+            HIPE(e->err, hipMemcpy(xE.data(), e->d_xE, xE.size() * sizeof(double), hipMemcpyDeviceToHost));
         }
         fprintf(stderr, "jaicov: the exterior-orientation step came back as exact zeros; %s\n",
                 still ? "the back-substitution was run again" : "a second, blocking copy had the values (the first copy returned before the data)");
@@ -1326,27 +1284,27 @@ struct Solve {
         if (schur && quirk) {
             // what the reference's last pass leaves in the EO entries of dx under MatrixInversion.REDUCED (quirk Q1): V_c^2 n_c
             std::vector<double> xq((size_t)6 * e->p.n_images);
-            HIPE(e, hipMemcpyAsync(xq.data(), e->sb.xq, xq.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-            HIPE(e, hipStreamSynchronize(e->stream));
+            HIPE(e->err, hipMemcpyAsync(xq.data(), e->sb.xq, xq.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+            HIPE(e->err, hipStreamSynchronize(e->stream));
             for (int img : e->h_blk_images)
                 for (int k = 0; k < 6; k++) dx_out[e->e0 + 6 * img + k] = xq[(size_t)6 * img + k];
         } else if (schur) {
-            HIPE(e, hipMemcpyAsync(e->d_dx, dx_out, (size_t)e->U * sizeof(double), hipMemcpyHostToDevice, e->stream));
+            HIPE(e->err, hipMemcpyAsync(e->d_dx, dx_out, (size_t)e->U * sizeof(double), hipMemcpyHostToDevice, e->stream));
             TRY(eo_backsub());
             std::vector<double> xE((size_t)6 * e->p.n_images);
-            HIPE(e, hipMemcpyAsync(xE.data(), e->d_xE, xE.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-            HIPE(e, hipStreamSynchronize(e->stream));
+            HIPE(e->err, hipMemcpyAsync(xE.data(), e->d_xE, xE.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+            HIPE(e->err, hipStreamSynchronize(e->stream));
             TRY(eo_zero_step_guard(xE));
             for (int img : e->h_blk_images)
                 for (int k = 0; k < 6; k++) {
                     dx_out[e->e0 + 6 * img + k] = xE[(size_t)6 * img + k];
-                    if (!std::isfinite(xE[(size_t)6 * img + k])) FAIL(e, JAICOV_ERR_NOT_FINITE, "non-finite step");
+                    if (!std::isfinite(xE[(size_t)6 * img + k])) FAIL(e->err, JAICOV_ERR_NOT_FINITE, "non-finite step");
                 }
         } else if (quirk) {
             // full-order path (no EO pre-elimination possible): the same quirk from the assembled right-hand side, V_c^2 n_c
             std::vector<double> hn((size_t)e->U);
-            HIPE(e, hipMemcpyAsync(hn.data(), e->d_n, hn.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-            HIPE(e, hipStreamSynchronize(e->stream));
+            HIPE(e->err, hipMemcpyAsync(hn.data(), e->d_n, hn.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+            HIPE(e->err, hipStreamSynchronize(e->stream));
             const int ns = e->n_slots, s_eo = ns - 6 * e->p.n_images;
             for (int sl = s_eo; sl < ns; sl++) {
                 const int c = e->h_slot_col[sl];
@@ -1359,21 +1317,21 @@ struct Solve {
     // which IS the block of Qxx that belongs to the datum border, points, interior orientation and distortion
     // (MatrixInversion.REDUCED / PRE_ELIMINATION, BA:261-267: solve(N, n, numRows, true) on the reduced system).
     int invert_and_expand() {
-        HIPE(e, slv.trtri());
-        HIPE(e, slv.lauum());
+        HIPE(e->err, slv.trtri());
+        HIPE(e->err, slv.lauum());
         if (e->opts.inverse_refinement >= 0 && Up <= 8192) {
             // One Newton-Schulz step on Q = inv(M) with the residual I - M Q formed exactly (batchinv.hip): M is materialised once more
             // (scaled, with the datum border's term; the factor in slv.L is not needed again before the next factorisation), W is free
             // after lauum(), three more squares are kept with the engine.
             const size_t sq = (size_t)Up * ld;
-            HIPE(e, e->ns_work.reserve(3 * sq));
+            HIPE(e->err, e->ns_work.reserve(3 * sq));
             double *ns = e->ns_work.get();
-            HIPE(e, slv.begin_refactor());
-            HIPE(e, slv.symmetrize(slv.Q));
+            HIPE(e->err, slv.begin_refactor());
+            HIPE(e->err, slv.symmetrize(slv.Q));
             hipLaunchKernelGGL(scale_copy_kernel, dim3((Up + 255) / 256, Up), dim3(256), 0, e->stream, e->d_N, (long)Upad, slv.L, ld, U,
                                Up, d, e->d_V, e->d_B, Upad, 0, Up);
-            HIPE(e, slv.symmetrize(slv.L));
-            HIPE(e, newton_schulz_exact(e->stream, Up, ld, slv.L, slv.Q, slv.W, ns, ns + sq, ns + 2 * sq));
+            HIPE(e->err, slv.symmetrize(slv.L));
+            HIPE(e->err, newton_schulz_exact(e->stream, Up, ld, slv.L, slv.Q, slv.W, ns, ns + sq, ns + 2 * sq));
         }
         // H = Sinv G^ ; F = R (Sinv G^) V ; E = R (I - Sinv) R
         std::vector<double> H((size_t)8 * Upad, 0.0), F((size_t)8 * Upad, 0.0);
@@ -1388,9 +1346,9 @@ struct Solve {
             for (int b = 0; b < d; b++) E[a * d + b] = R[a] * ((a == b ? 1.0 : 0.0) - Sinv[a * d + b]) * R[b];
         }
         if (d > 0) {
-            HIPE(e, hipMemcpyAsync(e->d_H, H.data(), (size_t)d * Upad * sizeof(double), hipMemcpyHostToDevice, e->stream));
-            HIPE(e, hipMemcpyAsync(e->d_F, F.data(), (size_t)d * Upad * sizeof(double), hipMemcpyHostToDevice, e->stream));
-            HIPE(e, hipMemcpyAsync(e->d_E, E, (size_t)d * d * sizeof(double), hipMemcpyHostToDevice, e->stream));
+            HIPE(e->err, hipMemcpyAsync(e->d_H, H.data(), (size_t)d * Upad * sizeof(double), hipMemcpyHostToDevice, e->stream));
+            HIPE(e->err, hipMemcpyAsync(e->d_F, F.data(), (size_t)d * Upad * sizeof(double), hipMemcpyHostToDevice, e->stream));
+            HIPE(e->err, hipMemcpyAsync(e->d_E, E, (size_t)d * d * sizeof(double), hipMemcpyHostToDevice, e->stream));
         }
         hipLaunchKernelGGL(qfix_kernel, dim3((Up + 255) / 256, Up), dim3(256), 0, e->stream, slv.Q, ld, U, Upad, d,
                            e->d_V, e->d_G + vs, (long)vs, e->d_H, e->d_F, e->d_E, Up);
@@ -1401,45 +1359,45 @@ struct Solve {
     int expand_cofactor() {
         size_t I6, UpS;
         if (!expansion_fits(e, &I6, &UpS))
-            FAIL(e, JAICOV_ERR_UNSUPPORTED, "FULL_EXPANDED: more exterior orientations than the workspace holds; use JAICOV_INVERT_FULL");
+            FAIL(e->err, JAICOV_ERR_UNSUPPORTED, "FULL_EXPANDED: more exterior orientations than the workspace holds; use JAICOV_INVERT_FULL");
         const int I6p = (int)I6;
         double *Fm = slv.W, *T1 = Fm + (size_t)I6p * Up, *T2 = T1 + (size_t)I6p * Up;
         const double *LinvAll = e->sb.Linv;
         if (e->all_images) {
-            HIPE(e, hipMemsetAsync(Fm, 0, (size_t)I6p * Up * sizeof(double), e->stream));
-            HIPE(e, launch_schur_expand_f(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->d_rowsA, e->sb.U, e->sb.Linv, e->sb.G, Fm, (long)Up));
+            HIPE(e->err, hipMemsetAsync(Fm, 0, (size_t)I6p * Up * sizeof(double), e->stream));
+            HIPE(e->err, launch_schur_expand_f(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->d_rowsA, e->sb.U, e->sb.Linv, e->sb.G, Fm, (long)Up));
         } else {      // a shard: F and L_E^-1 of EVERY image, summed over the ranks by the caller (jaicov_neq_expansion_buffer)
             if (!e->exp_ready || e->expF_len != (size_t)I6p * Up + (size_t)36 * e->p.n_images)
-                FAIL(e, JAICOV_ERR_BAD_STATE, "FULL_EXPANDED on a sharded engine: all-reduce jaicov_neq_expansion_buffer() between accumulate and solve");
-            HIPE(e, hipMemcpyAsync(Fm, e->expF.get(), (size_t)I6p * Up * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+                FAIL(e->err, JAICOV_ERR_BAD_STATE, "FULL_EXPANDED on a sharded engine: all-reduce jaicov_neq_expansion_buffer() between accumulate and solve");
+            HIPE(e->err, hipMemcpyAsync(Fm, e->expF.get(), (size_t)I6p * Up * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
             // the summed L_E^-1 records are READ from the buffer, never copied over sb.Linv: that array must keep zeros for the
             // foreign images, or the next pass's expansion buffer would carry their stale records into the sum (ADVICE r4, high:
             // a second sharded FULL_EXPANDED pass gave R times the EO cofactors)
             LinvAll = e->expF.get() + (size_t)I6p * Up;
         }
-        HIPE(e, slv.symmetrize(slv.Q));
+        HIPE(e->err, slv.symmetrize(slv.Q));
         GemmArgs g1{};
         g1.A = Fm; g1.lda = Up; g1.B = slv.Q; g1.ldb = ld; g1.C = T1; g1.ldc = Up;
         g1.M = I6p; g1.N = Up; g1.K = Up; g1.alpha = -1.0; g1.beta = 0.0; g1.kmode = KMODE_FULL;
-        HIPE(e, gemm_f64(e->stream, LAY_KC, LAY_KC, g1));             // Q_RR symmetric: F Q_RR = F Q_RR'
+        HIPE(e->err, gemm_f64(e->stream, LAY_KC, LAY_KC, g1));             // Q_RR symmetric: F Q_RR = F Q_RR'
         GemmArgs g2{};
         g2.A = T1; g2.lda = Up; g2.B = Fm; g2.ldb = Up; g2.C = T2; g2.ldc = I6p;
         g2.M = I6p; g2.N = I6p; g2.K = Up; g2.alpha = -1.0; g2.beta = 0.0; g2.kmode = KMODE_FULL; g2.lower_only = 1;
-        HIPE(e, gemm_f64(e->stream, LAY_KC, LAY_KC, g2));
+        HIPE(e->err, gemm_f64(e->stream, LAY_KC, LAY_KC, g2));
         hipLaunchKernelGGL(expand_cofactor_kernel, dim3((e->U + 255) / 256, e->U), dim3(256), 0, e->stream, e->solver.Q, e->solver.ld,
                            e->U, e->e0, slv.Q, ld, T1, (long)Up, T2, (long)I6p, LinvAll);
         return JAICOV_OK;
     }
     // end of the device's work, what the cofactor matrix at hand is, the timings
     int finish() {
-        HIPE(e, hipEventRecord(e->ev[7], e->stream));
-        HIPE(e, hipStreamSynchronize(e->stream));
+        HIPE(e->err, hipEventRecord(e->ev[7].get(), e->stream));
+        HIPE(e->err, hipStreamSynchronize(e->stream));
         if (invert) {
             e->have_Q = true;
             e->q_sigma2 = e->sigma2_acc;
             e->q_lambda = e->lambda_used;
             e->q_vals = e->h_vals;
-            jaicov::datum_state_invalidate(e->datum);
+            jaicov::datum_state_invalidate(e->datum.get());
             e->q_reduced = schur && !expand;
             e->q_order = expand ? e->U : U;
         }
@@ -1449,13 +1407,13 @@ struct Solve {
             slv.stat_launches = slv.stat_ms = slv.stat_flops = 0.0;
         }
         float ms;
-        hipEventElapsedTime(&ms, e->ev[0], e->ev[1]); e->timings[0] = ms;
-        hipEventElapsedTime(&ms, e->ev[1], e->ev[2]); e->timings[1] = ms;
-        hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); e->timings[2] = ms;
-        hipEventElapsedTime(&ms, e->ev[4], e->ev[5]); e->timings[3] = ms;
-        hipEventElapsedTime(&ms, e->ev[5], e->ev[6]); e->timings[4] = ms + refine_ms;   // substitution + refinement steps
-        hipEventElapsedTime(&ms, e->ev[6], e->ev[7]); e->timings[5] = std::max(0.f, ms - refine_ms);   // the refinement sits between these events: counted under [4]
-        hipEventElapsedTime(&ms, e->ev[0], e->ev[7]); e->timings[7] = ms;
+        hipEventElapsedTime(&ms, e->ev[0].get(), e->ev[1].get()); e->timings[0] = ms;
+        hipEventElapsedTime(&ms, e->ev[1].get(), e->ev[2].get()); e->timings[1] = ms;
+        hipEventElapsedTime(&ms, e->ev[2].get(), e->ev[3].get()); e->timings[2] = ms;
+        hipEventElapsedTime(&ms, e->ev[4].get(), e->ev[5].get()); e->timings[3] = ms;
+        hipEventElapsedTime(&ms, e->ev[5].get(), e->ev[6].get()); e->timings[4] = ms + refine_ms;   // substitution + refinement steps
+        hipEventElapsedTime(&ms, e->ev[6].get(), e->ev[7].get()); e->timings[5] = std::max(0.f, ms - refine_ms);   // the refinement sits between these events: counted under [4]
+        hipEventElapsedTime(&ms, e->ev[0].get(), e->ev[7].get()); e->timings[7] = ms;
         e->state = jaicov_engine::ST_SOLVED;
         return JAICOV_OK;
     }
@@ -1463,8 +1421,8 @@ struct Solve {
 
 extern "C" int jaicov_neq_solve(jaicov_engine *e, int invert, double *dx_out) {
     if (!e || !dx_out) return JAICOV_ERR_BAD_ARGUMENT;
-    if (e->state != jaicov_engine::ST_BUILT) FAIL(e, JAICOV_ERR_BAD_STATE, "build first");
-    HIPE(e, hipSetDevice(e->device));
+    if (e->state != jaicov_engine::ST_BUILT) FAIL(e->err, JAICOV_ERR_BAD_STATE, "build first");
+    HIPE(e->err, hipSetDevice(e->device));
     if (invert < 0 || invert > JAICOV_INVERT_FULL_EXPANDED) return JAICOV_ERR_BAD_ARGUMENT;
     Solve s(e);
     TRY(s.solve_mode(invert));
@@ -1480,20 +1438,20 @@ extern "C" int jaicov_neq_solve(jaicov_engine *e, int invert, double *dx_out) {
 extern "C" int jaicov_neq_expansion_buffer(jaicov_engine *e, void **device_ptr, size_t *count) {
     if (!e || !device_ptr || !count) return JAICOV_ERR_BAD_ARGUMENT;
     if (e->state != jaicov_engine::ST_ACCUMULATED || !e->schur_active || !e->solverS_ready)
-        FAIL(e, JAICOV_ERR_BAD_STATE, "expansion buffer: accumulate a pre-eliminated system first (prepare_inverse(JAICOV_INVERT_FULL_EXPANDED))");
-    HIPE(e, hipSetDevice(e->device));
+        FAIL(e->err, JAICOV_ERR_BAD_STATE, "expansion buffer: accumulate a pre-eliminated system first (prepare_inverse(JAICOV_INVERT_FULL_EXPANDED))");
+    HIPE(e->err, hipSetDevice(e->device));
     size_t I6p, Up;
     expansion_fits(e, &I6p, &Up);
     const size_t len = I6p * Up + (size_t)36 * e->p.n_images;
-    HIPE(e, e->expF.reserve(len));
+    HIPE(e->err, e->expF.reserve(len));
     e->expF_len = len;
     double *d_expF = e->expF.get();
     TRY(ensure_rows(e));
-    HIPE(e, hipMemsetAsync(d_expF, 0, I6p * Up * sizeof(double), e->stream));       // foreign images' bands: zero
-    HIPE(e, launch_schur_expand_f(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->d_rowsA, e->sb.U, e->sb.Linv, e->sb.G, d_expF, (long)Up));
+    HIPE(e->err, hipMemsetAsync(d_expF, 0, I6p * Up * sizeof(double), e->stream));       // foreign images' bands: zero
+    HIPE(e->err, launch_schur_expand_f(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->d_rowsA, e->sb.U, e->sb.Linv, e->sb.G, d_expF, (long)Up));
     // L_E^-1: written for this engine's images only (blk_elim_kernel), zero elsewhere since create
-    HIPE(e, hipMemcpyAsync(d_expF + I6p * Up, e->sb.Linv, (size_t)36 * e->p.n_images * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-    HIPE(e, hipStreamSynchronize(e->stream));
+    HIPE(e->err, hipMemcpyAsync(d_expF + I6p * Up, e->sb.Linv, (size_t)36 * e->p.n_images * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    HIPE(e->err, hipStreamSynchronize(e->stream));
     e->exp_ready = true;
     *device_ptr = d_expF;
     *count = len;
@@ -1502,7 +1460,7 @@ extern "C" int jaicov_neq_expansion_buffer(jaicov_engine *e, void **device_ptr, 
 
 extern "C" int jaicov_neq_eo_step_buffer(jaicov_engine *e, void **device_ptr, size_t *count) {
     if (!e || !device_ptr || !count) return JAICOV_ERR_BAD_ARGUMENT;
-    if (e->state != jaicov_engine::ST_SOLVED || !e->schur_active || !e->d_xE) FAIL(e, JAICOV_ERR_BAD_STATE, "no pre-eliminated exterior orientations: solve a reduced system first");
+    if (e->state != jaicov_engine::ST_SOLVED || !e->schur_active || !e->d_xE) FAIL(e->err, JAICOV_ERR_BAD_STATE, "no pre-eliminated exterior orientations: solve a reduced system first");
     *device_ptr = e->d_xE;
     *count = (size_t)6 * e->p.n_images;
     return JAICOV_OK;
@@ -1510,19 +1468,19 @@ extern "C" int jaicov_neq_eo_step_buffer(jaicov_engine *e, void **device_ptr, si
 
 extern "C" int jaicov_neq_omega(jaicov_engine *e, double sigma2, const double *dx, double *omega) {
     if (!e || !dx || !omega) return JAICOV_ERR_BAD_ARGUMENT;
-    if (e->state == jaicov_engine::ST_NEW) FAIL(e, JAICOV_ERR_BAD_STATE, "set_parameters first");
-    HIPE(e, hipSetDevice(e->device));
+    if (e->state == jaicov_engine::ST_NEW) FAIL(e->err, JAICOV_ERR_BAD_STATE, "set_parameters first");
+    HIPE(e->err, hipSetDevice(e->device));
     TRY(ensure_rows(e));
-    hipEvent_t t0 = e->ev[8], t1 = e->ev[9];
-    HIPE(e, hipEventRecord(t0, e->stream));
-    HIPE(e, hipMemcpyAsync(e->d_dx, dx, (size_t)e->U * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    HIPE(e, hipMemsetAsync(e->d_omega, 0, sizeof(double), e->stream));
-    HIPE(e, launch_omega(e->stream, e->p, e->d_in_block, e->ip0, e->ip_count, e->d_blk_list, e->n_blk_list, e->max_m,
+    hipEvent_t t0 = e->ev[8].get(), t1 = e->ev[9].get();
+    HIPE(e->err, hipEventRecord(t0, e->stream));
+    HIPE(e->err, hipMemcpyAsync(e->d_dx, dx, (size_t)e->U * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIPE(e->err, hipMemsetAsync(e->d_omega, 0, sizeof(double), e->stream));
+    HIPE(e->err, launch_omega(e->stream, e->p, e->d_in_block, e->ip0, e->ip_count, e->d_blk_list, e->n_blk_list, e->max_m,
                          e->d_rowsA, e->d_rowsW, e->d_dx, sigma2, e->d_vbuf, e->d_omega));
-    if (e->opts.apply_shared) HIPE(e, launch_shared_groups(e->stream, e->p, e->d_vals, sigma2, nullptr, nullptr, e->d_dx, e->d_omega));
-    HIPE(e, hipEventRecord(t1, e->stream));
-    HIPE(e, hipMemcpyAsync(omega, e->d_omega, sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPE(e, hipStreamSynchronize(e->stream));
+    if (e->opts.apply_shared) HIPE(e->err, launch_shared_groups(e->stream, e->p, e->d_vals, sigma2, nullptr, nullptr, e->d_dx, e->d_omega));
+    HIPE(e->err, hipEventRecord(t1, e->stream));
+    HIPE(e->err, hipMemcpyAsync(omega, e->d_omega, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPE(e->err, hipStreamSynchronize(e->stream));
     float ms;
     hipEventElapsedTime(&ms, t0, t1);
     e->timings[6] = ms;
@@ -1531,7 +1489,7 @@ extern "C" int jaicov_neq_omega(jaicov_engine *e, double sigma2, const double *d
 
 extern "C" int jaicov_neq_update(jaicov_engine *e, const double *dx, double *max_abs_dx) {
     if (!e || !dx) return JAICOV_ERR_BAD_ARGUMENT;
-    HIPE(e, hipSetDevice(e->device));
+    HIPE(e->err, hipSetDevice(e->device));
     double mx = 0.0;
     for (int s = 0; s < e->n_slots; s++) {
         const int c = e->h_slot_col[s];
@@ -1542,8 +1500,8 @@ extern "C" int jaicov_neq_update(jaicov_engine *e, const double *dx, double *max
         }
     }
     if (max_abs_dx) *max_abs_dx = mx;
-    HIPE(e, hipMemcpyAsync(e->d_vals, e->h_vals.data(), (size_t)e->n_slots * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    HIPE(e, hipStreamSynchronize(e->stream));
+    HIPE(e->err, hipMemcpyAsync(e->d_vals, e->h_vals.data(), (size_t)e->n_slots * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIPE(e->err, hipStreamSynchronize(e->stream));
     e->rows_valid = false;
     return JAICOV_OK;
 }
@@ -1551,21 +1509,21 @@ extern "C" int jaicov_neq_update(jaicov_engine *e, const double *dx, double *max
 extern "C" int jaicov_neq_get_normal(jaicov_engine *e, double *N_packed, size_t len, double *n, size_t Ulen) {
     if (!e || !N_packed || !n) return JAICOV_ERR_BAD_ARGUMENT;
     if (e->state != jaicov_engine::ST_BUILT && e->state != jaicov_engine::ST_SOLVED && e->state != jaicov_engine::ST_ACCUMULATED)
-        FAIL(e, JAICOV_ERR_BAD_STATE, "build first");
+        FAIL(e->err, JAICOV_ERR_BAD_STATE, "build first");
     const int U = e->U;
     if (len != (size_t)U * (U + 1) / 2 || Ulen != (size_t)U) return JAICOV_ERR_BAD_ARGUMENT;
-    HIPE(e, hipSetDevice(e->device));
+    HIPE(e->err, hipSetDevice(e->device));
     // with the exterior orientations pre-eliminated only the reduced system (order e0) was assembled: the rows from e0 on
     // of the square are neither zeroed nor written in such a pass.  The header's contract: reduced system in the leading
     // e0 rows / columns, zeros elsewhere.
     const int Ua = e->schur_active ? e->e0 : U;
     const size_t lenA = (size_t)Ua * (Ua + 1) / 2;
     DevBuf<double> ap;
-    HIPE(e, ap.reserve(std::max<size_t>(lenA, 1)));
+    HIPE(e->err, ap.reserve(std::max<size_t>(lenA, 1)));
     hipLaunchKernelGGL(pack_kernel, dim3((Ua + 255) / 256, std::max(Ua, 1)), dim3(256), 0, e->stream, e->d_N, (long)e->Upad, Ua, ap.get());
-    HIPE(e, hipMemcpyAsync(N_packed, ap.get(), lenA * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPE(e, hipMemcpyAsync(n, e->d_n, Ua * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPE(e, hipStreamSynchronize(e->stream));
+    HIPE(e->err, hipMemcpyAsync(N_packed, ap.get(), lenA * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPE(e->err, hipMemcpyAsync(n, e->d_n, Ua * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPE(e->err, hipStreamSynchronize(e->stream));
     if (lenA < len) memset(N_packed + lenA, 0, (len - lenA) * sizeof(double));
     for (int c = Ua; c < U; c++) n[c] = 0.0;
     // the datum border lives on the host (rows 0..d-1): K[r][c] = B[r][c]  (BA:548-593), packed index r + c(c+1)/2
@@ -1577,16 +1535,16 @@ extern "C" int jaicov_neq_get_normal(jaicov_engine *e, double *N_packed, size_t 
 
 extern "C" int jaicov_neq_get_cofactor(jaicov_engine *e, double *Q_packed, size_t len) {
     if (!e || !Q_packed) return JAICOV_ERR_BAD_ARGUMENT;
-    if (!e->have_Q) FAIL(e, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first (MatrixInversion.NONE, BA:1177)");
+    if (!e->have_Q) FAIL(e->err, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first (MatrixInversion.NONE, BA:1177)");
     const int U = e->q_order;
-    if (len != (size_t)U * (U + 1) / 2) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "cofactor buffer length must be order(order+1)/2 with order = jaicov_neq_cofactor_order()");
-    HIPE(e, hipSetDevice(e->device));
+    if (len != (size_t)U * (U + 1) / 2) FAIL(e->err, JAICOV_ERR_BAD_ARGUMENT, "cofactor buffer length must be order(order+1)/2 with order = jaicov_neq_cofactor_order()");
+    HIPE(e->err, hipSetDevice(e->device));
     const DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
     DevBuf<double> ap;
-    HIPE(e, ap.reserve(std::max<size_t>(len, 1)));
+    HIPE(e->err, ap.reserve(std::max<size_t>(len, 1)));
     hipLaunchKernelGGL(pack_kernel, dim3((U + 255) / 256, std::max(U, 1)), dim3(256), 0, e->stream, qs.Q, qs.ld, U, ap.get());
-    HIPE(e, hipMemcpyAsync(Q_packed, ap.get(), len * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPE(e, hipStreamSynchronize(e->stream));
+    HIPE(e->err, hipMemcpyAsync(Q_packed, ap.get(), len * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPE(e->err, hipStreamSynchronize(e->stream));
     return JAICOV_OK;
 }
 
@@ -1648,26 +1606,26 @@ void jaicov::engine_datum_view(jaicov_engine *e, DatumView *v) {
 }
 
 int jaicov::engine_datum_rows(jaicov_engine *e, const uint8_t *mask, std::vector<double> &B, int stride) {
-    if (e->q_vals.size() != (size_t)e->n_slots) FAIL(e, JAICOV_ERR_BAD_STATE, "no inverting solve has recorded its parameter values");
+    if (e->q_vals.size() != (size_t)e->n_slots) FAIL(e->err, JAICOV_ERR_BAD_STATE, "no inverting solve has recorded its parameter values");
     B.assign((size_t)e->d * stride, 0.0);
     return datum_rows(e, mask, e->q_vals.data(), B, stride);
 }
 
 static int cofactor_sub_impl(jaicov_engine *e, const int32_t *idx, int32_t k, double scale, double *out) {
     if (!e || !idx || !out || k <= 0) return JAICOV_ERR_BAD_ARGUMENT;
-    if (!e->have_Q) FAIL(e, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
+    if (!e->have_Q) FAIL(e->err, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
     for (int i = 0; i < k; i++)
         if (idx[i] < 0 || idx[i] >= e->q_order) return JAICOV_ERR_BAD_ARGUMENT;
     const DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
-    HIPE(e, hipSetDevice(e->device));
+    HIPE(e->err, hipSetDevice(e->device));
     DevBuf<int32_t> d_idx;
     DevBuf<double> d_out;
-    HIPE(e, d_idx.reserve((size_t)k));
-    HIPE(e, d_out.reserve((size_t)k * k));
-    HIPE(e, hipMemcpyAsync(d_idx.get(), idx, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIPE(e->err, d_idx.reserve((size_t)k));
+    HIPE(e->err, d_out.reserve((size_t)k * k));
+    HIPE(e->err, hipMemcpyAsync(d_idx.get(), idx, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(gather_sub_kernel, dim3(((size_t)k * k + 255) / 256), dim3(256), 0, e->stream, qs.Q, qs.ld, d_idx.get(), k, d_out.get(), scale);
-    HIPE(e, hipMemcpyAsync(out, d_out.get(), (size_t)k * k * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPE(e, hipStreamSynchronize(e->stream));
+    HIPE(e->err, hipMemcpyAsync(out, d_out.get(), (size_t)k * k * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPE(e->err, hipStreamSynchronize(e->stream));
     return JAICOV_OK;
 }
 
@@ -1681,14 +1639,14 @@ extern "C" int jaicov_neq_get_dispersion_sub(jaicov_engine *e, double sigma2_apo
 
 extern "C" int jaicov_neq_get_rows(jaicov_engine *e, int32_t ip_begin, int32_t ip_count, double *w, double *A) {
     if (!e || !w || !A || ip_begin < e->ip0 || ip_count < 0 || ip_begin + ip_count > e->ip0 + e->ip_count) return JAICOV_ERR_BAD_ARGUMENT;
-    if (e->state == jaicov_engine::ST_NEW) FAIL(e, JAICOV_ERR_BAD_STATE, "set_parameters first");
-    HIPE(e, hipSetDevice(e->device));
+    if (e->state == jaicov_engine::ST_NEW) FAIL(e->err, JAICOV_ERR_BAD_STATE, "set_parameters first");
+    HIPE(e->err, hipSetDevice(e->device));
     TRY(ensure_rows(e));
     const size_t S = (size_t)e->p.n_ip;
     std::vector<double> hA((size_t)2 * KROW * S), hW(2 * S);
-    HIPE(e, hipMemcpyAsync(hA.data(), e->d_rowsA, hA.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPE(e, hipMemcpyAsync(hW.data(), e->d_rowsW, hW.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPE(e, hipStreamSynchronize(e->stream));
+    HIPE(e->err, hipMemcpyAsync(hA.data(), e->d_rowsA, hA.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPE(e->err, hipMemcpyAsync(hW.data(), e->d_rowsW, hW.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPE(e->err, hipStreamSynchronize(e->stream));
     for (int i = 0; i < ip_count; i++) {
         const size_t ip = e->ip_old2new.empty() ? (size_t)ip_begin + i : (size_t)e->ip_old2new[(size_t)ip_begin + i];
         w[2 * i] = hW[ip]; w[2 * i + 1] = hW[S + ip];
@@ -1738,13 +1696,13 @@ extern "C" int jaicov_neq_get_block_weight(jaicov_engine *e, int32_t block, doub
             if (e->h_caller_block[g] == block) internal = (int)g;
         block = internal;
     }
-    if (block < 0 || block >= (int)e->h_blk_mine.size() || !e->h_blk_mine[block]) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "no such image block on this engine");
+    if (block < 0 || block >= (int)e->h_blk_mine.size() || !e->h_blk_mine[block]) FAIL(e->err, JAICOV_ERR_BAD_ARGUMENT, "no such image block on this engine");
     const int b = e->h_blk_ip_begin[block], mpts = e->h_blk_ip_begin[block + 1] - b, m = 2 * mpts;
-    if (len != (size_t)m * m) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "len must be (2 * points of the block)^2");
-    HIPE(e, hipSetDevice(e->device));
-    if (e->h_blk_w_off[block] < 0) FAIL(e, JAICOV_ERR_BAD_ARGUMENT, "this block has no dispersion of its own");
+    if (len != (size_t)m * m) FAIL(e->err, JAICOV_ERR_BAD_ARGUMENT, "len must be (2 * points of the block)^2");
+    HIPE(e->err, hipSetDevice(e->device));
+    if (e->h_blk_w_off[block] < 0) FAIL(e->err, JAICOV_ERR_BAD_ARGUMENT, "this block has no dispersion of its own");
     std::vector<double> w((size_t)m * m);
-    HIPE(e, hipMemcpy(w.data(), e->p.blk_w + e->h_blk_w_off[block], w.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPE(e->err, hipMemcpy(w.data(), e->p.blk_w + e->h_blk_w_off[block], w.size() * sizeof(double), hipMemcpyDeviceToHost));
     const int32_t *perm = e->h_perm_local.empty() ? nullptr : e->h_perm_local.data() + b;
     for (int i = 0; i < m; i++) {
         const int si = perm ? 2 * perm[i >> 1] + (i & 1) : i;
@@ -1766,7 +1724,7 @@ extern "C" int jaicov_neq_last_timings(jaicov_engine *e, double *ms, int32_t n) 
 // the engine pre-eliminates the exterior orientations in every pass whenever the problem allows it)
 extern "C" int jaicov_neq_estimate(jaicov_engine *e, const jaicov_estimate_options *o, jaicov_estimate_result *res) {
     if (!e || !o || !res || o->struct_size != sizeof(jaicov_estimate_options)) return JAICOV_ERR_BAD_ARGUMENT;
-    if (e->state == jaicov_engine::ST_NEW) FAIL(e, JAICOV_ERR_BAD_STATE, "set_parameters first");
+    if (e->state == jaicov_engine::ST_NEW) FAIL(e->err, JAICOV_ERR_BAD_STATE, "set_parameters first");
     const double SQRT_EPS = sqrt(EPS53);
     if (o->invert < 0 || o->invert > JAICOV_INVERT_FULL_EXPANDED) return JAICOV_ERR_BAD_ARGUMENT;
     // MatrixInversion.FULL: all of Qxx, computed from the EO-reduced system where the engine can (jaicov_neq.h, FULL_EXPANDED)
@@ -1860,16 +1818,17 @@ extern "C" int jaicov_dense_spd_solve_packed(int32_t n, double *ap, double *b, i
     hipStream_t s;
     if (hipStreamCreate(&s) != hipSuccess) return JAICOV_ERR_DEVICE;
     const int np = ((n + 127) / 128) * 128;
-    DenseSolver ds;
-    int status = JAICOV_OK;
-    double *d_ap = nullptr, *d_Y = nullptr;
-    const size_t len = (size_t)n * (n + 1) / 2;
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    do {
-        if (ds.init(s, np, invert != 0, true) != hipSuccess) { status = JAICOV_ERR_OUT_OF_MEMORY; break; }
-        if (hipMalloc(&d_ap, len * sizeof(double)) != hipSuccess) { status = JAICOV_ERR_OUT_OF_MEMORY; break; }
-        hipMalloc(&d_Y, (size_t)DENSE_MAX_RHS * np * sizeof(double));
+    const int status = [&]() -> int {      // the solver and the buffers go before the stream does
+        DenseSolver ds;
+        DevBuf<double> ap_store, Y_store;
+        DevEvent ev0, ev1;
+        const size_t len = (size_t)n * (n + 1) / 2;
+        if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+        const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
+        if (ds.init(s, np, invert != 0, true) != hipSuccess || ap_store.reserve(len) != hipSuccess ||
+            Y_store.reserve((size_t)DENSE_MAX_RHS * np) != hipSuccess)
+            return JAICOV_ERR_OUT_OF_MEMORY;
+        double *d_ap = ap_store.get(), *d_Y = Y_store.get();
         hipMemcpyAsync(d_ap, ap, len * sizeof(double), hipMemcpyHostToDevice, s);
         int info = 0;
         for (int attempt = 0;; attempt++) {      // an abandoned dataflow factorisation (-9) is repeated: the packed input is still there
@@ -1893,20 +1852,17 @@ extern "C" int jaicov_dense_spd_solve_packed(int32_t n, double *ap, double *b, i
             }
             break;
         }
-        if (info < 0) { status = JAICOV_ERR_DEVICE; break; }
-        if (info != 0) { status = JAICOV_ERR_SINGULAR; break; }
+        if (info < 0) return JAICOV_ERR_DEVICE;
+        if (info != 0) return JAICOV_ERR_SINGULAR;
         for (int q = 0; q < nrhs; q++) hipMemcpyAsync(b + (size_t)q * n, d_Y + (size_t)q * np, n * sizeof(double), hipMemcpyDeviceToHost, s);
         if (invert) {
             hipLaunchKernelGGL(pack_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, ds.Q, ds.ld, n, d_ap);
             hipMemcpyAsync(ap, d_ap, len * sizeof(double), hipMemcpyDeviceToHost, s);
         }
-        if (hipStreamSynchronize(s) != hipSuccess) status = JAICOV_ERR_DEVICE;
+        const bool ok = hipStreamSynchronize(s) == hipSuccess;
         if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-    } while (0);
-    hipStreamSynchronize(s);
-    hipFree(d_ap); hipFree(d_Y);
-    ds.release();
-    hipEventDestroy(e0); hipEventDestroy(e1);
+        return ok ? JAICOV_OK : JAICOV_ERR_DEVICE;
+    }();
     hipStreamDestroy(s);
     return status;
 }
@@ -1950,8 +1906,11 @@ extern "C" int jaicov_debug_gemm_trace(int M, int K, int lower_only, long long *
     std::string err;
     if (check_device(err)) return JAICOV_ERR_NO_DEVICE;
     const int tm = M / 128, tiles = lower_only ? tm * (tm + 1) / 2 : tm * tm;
-    double *dA = nullptr, *dC = nullptr; long long *dT = nullptr;
-    hipMalloc(&dA, (size_t)M * K * 8); hipMalloc(&dC, (size_t)M * M * 8); hipMalloc(&dT, (size_t)tiles * 64);
+    DevBuf<double> A_store, C_store;
+    DevBuf<long long> T_store;
+    if (A_store.reserve((size_t)M * K) != hipSuccess || C_store.reserve((size_t)M * M) != hipSuccess || T_store.reserve((size_t)tiles * 8) != hipSuccess)
+        return JAICOV_ERR_OUT_OF_MEMORY;
+    double *dA = A_store.get(), *dC = C_store.get(); long long *dT = T_store.get();
     hipMemset(dC, 0, (size_t)M * M * 8); hipMemset(dT, 0, (size_t)tiles * 64);
     {   // random operands (the matrix pipe draws more power on them than on zeros) and a warm chip
         std::vector<double> h((size_t)M * K);
@@ -1970,7 +1929,6 @@ extern "C" int jaicov_debug_gemm_trace(int M, int K, int lower_only, long long *
     hipError_t he = gemm_f64(nullptr, LAY_KC, LAY_KC, g, 1, 0, tag);
     he = he == hipSuccess ? hipDeviceSynchronize() : he;
     hipMemcpy(out, dT, (size_t)tiles * 64, hipMemcpyDeviceToHost);
-    hipFree(dA); hipFree(dC); hipFree(dT);
     return he == hipSuccess ? JAICOV_OK : JAICOV_ERR_DEVICE;
 }
 
@@ -2011,36 +1969,35 @@ extern "C" int jaicov_debug_potrf_bench(int n, int reps, double *ms_out, long lo
     if (n <= 0 || n % 128 || reps < 1 || !ms_out) return JAICOV_ERR_BAD_ARGUMENT;
     hipStream_t s;
     if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return JAICOV_ERR_DEVICE;
-    DenseSolver ds;
-    int status = JAICOV_OK;
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    do {
-        if (ds.init(s, n, false, true) != hipSuccess) { status = JAICOV_ERR_OUT_OF_MEMORY; break; }
+    const int status = [&]() -> int {      // the solver goes before the stream does
+        DenseSolver ds;
+        DevEvent ev0, ev1;
+        if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+        const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
+        if (ds.init(s, n, false, true) != hipSuccess) return JAICOV_ERR_OUT_OF_MEMORY;
         if (trace_out && ds.flow.ready()) ds.flow.enable_trace(true);
         for (int r = 0; r < reps; r++) {
             hipLaunchKernelGGL(fill_spd_kernel, dim3((ds.n + 255) / 256, ds.n), dim3(256), 0, s, ds.L, ds.ld, ds.n, n);
             hipEventRecord(e0, s);
             const hipError_t pe = ds.potrf();
-            if (pe != hipSuccess) { fprintf(stderr, "potrf: %s\n", hipGetErrorString(pe)); status = JAICOV_ERR_DEVICE; break; }
+            if (pe != hipSuccess) { fprintf(stderr, "potrf: %s\n", hipGetErrorString(pe)); return JAICOV_ERR_DEVICE; }
             hipEventRecord(e1, s);
             const int info = ds.fetch_info();
             if (info < 0) fprintf(stderr, "potrf: info %d (flow_ready %d)\n", info, (int)ds.flow.ready());
             float ms = 0;
             hipEventElapsedTime(&ms, e0, e1);
             ms_out[r] = ms;
-            if (info < 0) { status = JAICOV_ERR_DEVICE; break; }
-            if (info != 0) { status = JAICOV_ERR_SINGULAR; break; }
+            if (info < 0) return JAICOV_ERR_DEVICE;
+            if (info != 0) return JAICOV_ERR_SINGULAR;
         }
-        if (status == JAICOV_OK && trace_out && ds.flow.trace()) {
+        if (trace_out && ds.flow.trace()) {
             const long long cnt = std::min<long long>(trace_cap, (long long)ds.flow.trace_words());   // per task, then per block column (chain kernel)
             hipMemcpy(trace_out, ds.flow.trace(), (size_t)cnt * sizeof(long long), hipMemcpyDeviceToHost);
         }
         if (tasks_out) *tasks_out = ds.flow.ready() ? ds.flow.n_tasks() : 0;
-    } while (0);
-    hipStreamSynchronize(s);
-    ds.release();
-    hipEventDestroy(e0); hipEventDestroy(e1);
+        hipStreamSynchronize(s);
+        return JAICOV_OK;
+    }();
     hipStreamDestroy(s);
     return status;
 }
@@ -2053,20 +2010,19 @@ extern "C" int jaicov_debug_potrf_factor(int n, const double *A, double *L_out) 
     if (n <= 0 || n % 128 || !A || !L_out) return JAICOV_ERR_BAD_ARGUMENT;
     hipStream_t s;
     if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return JAICOV_ERR_DEVICE;
-    DenseSolver ds;
-    int status = JAICOV_OK;
-    do {
-        if (ds.init(s, n, false, true) != hipSuccess) { status = JAICOV_ERR_OUT_OF_MEMORY; break; }
+    const int status = [&]() -> int {      // the solver goes before the stream does
+        DenseSolver ds;
+        if (ds.init(s, n, false, true) != hipSuccess) return JAICOV_ERR_OUT_OF_MEMORY;
         hipLaunchKernelGGL(fill_spd_kernel, dim3((ds.n + 255) / 256, ds.n), dim3(256), 0, s, ds.L, ds.ld, ds.n, n);   // incl. the right-hand-side rows
-        if (hipMemcpy2DAsync(ds.L, ds.ld * sizeof(double), A, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyHostToDevice, s) != hipSuccess) { status = JAICOV_ERR_DEVICE; break; }
-        if (ds.potrf() != hipSuccess) { status = JAICOV_ERR_DEVICE; break; }
+        if (hipMemcpy2DAsync(ds.L, ds.ld * sizeof(double), A, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyHostToDevice, s) != hipSuccess) return JAICOV_ERR_DEVICE;
+        if (ds.potrf() != hipSuccess) return JAICOV_ERR_DEVICE;
         const int info = ds.fetch_info();
-        if (info < 0) { status = JAICOV_ERR_DEVICE; break; }
-        if (info > 0) { status = JAICOV_ERR_SINGULAR; break; }
-        if (hipMemcpy2DAsync(L_out, (size_t)n * sizeof(double), ds.L, ds.ld * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, s) != hipSuccess) status = JAICOV_ERR_DEVICE;
-    } while (0);
-    hipStreamSynchronize(s);
-    ds.release();
+        if (info < 0) return JAICOV_ERR_DEVICE;
+        if (info > 0) return JAICOV_ERR_SINGULAR;
+        const bool copied = hipMemcpy2DAsync(L_out, (size_t)n * sizeof(double), ds.L, ds.ld * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, s) == hipSuccess;
+        hipStreamSynchronize(s);
+        return copied ? JAICOV_OK : JAICOV_ERR_DEVICE;
+    }();
     hipStreamDestroy(s);
     return status;
 }
@@ -2083,10 +2039,10 @@ extern "C" int jaicov_debug_newton_schulz(int n, const double *M, const double *
     if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return JAICOV_ERR_DEVICE;
     const long ld = (long)n + 128;
     const size_t sq = (size_t)n * ld, row = (size_t)n * sizeof(double);
-    double *buf = nullptr;                                   // M, Q, W, T1, T2, T3
-    int status = JAICOV_OK;
-    do {
-        if (hipMalloc(&buf, 6 * sq * sizeof(double)) != hipSuccess) { status = JAICOV_ERR_OUT_OF_MEMORY; break; }
+    const int status = [&]() -> int {      // the buffer goes before the stream does
+        DevBuf<double> store;                                // M, Q, W, T1, T2, T3
+        if (store.reserve(6 * sq) != hipSuccess) return JAICOV_ERR_OUT_OF_MEMORY;
+        double *buf = store.get();
         double *dM = buf, *dQ = buf + sq, *dW = buf + 2 * sq, *T1 = buf + 3 * sq, *T2 = buf + 4 * sq, *T3 = buf + 5 * sq;
         // M and Q start as NaN (all bits set) and the work squares as zero: the columns n .. n + 127, where the solver keeps its right-hand-side
         // rows, then hold NaN beside both operands, and a slice or product that read up to ld instead of n would show in every entry
@@ -2097,10 +2053,9 @@ extern "C" int jaicov_debug_newton_schulz(int n, const double *M, const double *
             newton_schulz_exact(s, n, ld, dM, dQ, dW, T1, T2, T3) != hipSuccess ||
             hipMemcpy2DAsync(Q_out, row, dQ, ld * sizeof(double), row, n, hipMemcpyDeviceToHost, s) != hipSuccess ||
             (R_out && hipMemcpy2DAsync(R_out, row, T3, ld * sizeof(double), row, n, hipMemcpyDeviceToHost, s) != hipSuccess))   // (the product Q0 R went to T1)
-            status = JAICOV_ERR_DEVICE;
-    } while (0);
-    if (hipStreamSynchronize(s) != hipSuccess) status = status == JAICOV_OK ? JAICOV_ERR_DEVICE : status;
-    hipFree(buf);
+            return JAICOV_ERR_DEVICE;
+        return hipStreamSynchronize(s) == hipSuccess ? JAICOV_OK : JAICOV_ERR_DEVICE;
+    }();
     hipStreamDestroy(s);
     return status;
 }
@@ -2115,19 +2070,18 @@ extern "C" int jaicov_dense_gemm(int32_t alay, int32_t blay, int32_t M, int32_t 
     int rc = check_device(err);
     if (rc) return rc;
     const size_t sa = (size_t)(alay == LAY_KC ? M : K) * lda, sb = (size_t)(blay == LAY_KC ? N : K) * ldb, sc = (size_t)M * ldc;
-    double *dA = nullptr, *dB = nullptr, *dC = nullptr;
-    if (hipMalloc(&dA, sa * 8) != hipSuccess || hipMalloc(&dB, sb * 8) != hipSuccess || hipMalloc(&dC, sc * 8) != hipSuccess) {
-        hipFree(dA); hipFree(dB); hipFree(dC);
-        return JAICOV_ERR_OUT_OF_MEMORY;
-    }
+    DevBuf<double> A_store, B_store, C_store;
+    DevEvent ev0, ev1;
+    if (A_store.reserve(sa) != hipSuccess || B_store.reserve(sb) != hipSuccess || C_store.reserve(sc) != hipSuccess) return JAICOV_ERR_OUT_OF_MEMORY;
+    if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+    double *dA = A_store.get(), *dB = B_store.get(), *dC = C_store.get();
+    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
     hipMemcpy(dA, A, sa * 8, hipMemcpyHostToDevice);
     hipMemcpy(dB, B, sb * 8, hipMemcpyHostToDevice);
     hipMemcpy(dC, C, sc * 8, hipMemcpyHostToDevice);
     GemmArgs g{};
     g.A = dA; g.B = dB; g.C = dC; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
     g.alpha = alpha; g.beta = beta; g.lower_only = lower_only; g.kmode = kmode;
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
     hipError_t he = gemm_f64(nullptr, alay, blay, g);
     hipMemcpy(C, dC, sc * 8, hipMemcpyDeviceToHost);
     if (repeats > 0) {
@@ -2140,7 +2094,5 @@ extern "C" int jaicov_dense_gemm(int32_t alay, int32_t blay, int32_t M, int32_t 
         if (ms_out) *ms_out = ms / repeats;
     }
     he = he == hipSuccess ? hipDeviceSynchronize() : he;
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    hipFree(dA); hipFree(dB); hipFree(dC);
     return he == hipSuccess ? JAICOV_OK : JAICOV_ERR_DEVICE;
 }

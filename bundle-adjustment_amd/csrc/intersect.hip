@@ -21,7 +21,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/jaicov_intersect.h"
+#include "devbuf.h"
 #include "intersect.h"
 
 #pragma clang fp contract(off)
@@ -317,25 +320,22 @@ extern "C" int jaicov_isect_points(int32_t n_points, const int32_t *ray_begin, c
 
     hipStream_t s;
     if (hipStreamCreate(&s) != hipSuccess) return JAICOV_ERR_DEVICE;
-    int rc = JAICOV_OK;
-    int32_t *d_begin = nullptr, *d_image = nullptr, *d_outcome = nullptr, *h_outcome = nullptr;
-    double *d_xy = nullptr, *d_var = nullptr, *d_io = nullptr, *d_eo = nullptr, *d_out = nullptr, *d_q = nullptr;
-    uint8_t *d_used = nullptr;
-    IsectImage *d_rec = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    const size_t np = (size_t)n_points, nr = (size_t)(n_rays > 0 ? n_rays : 1), ni = (size_t)(n_images > 0 ? n_images : 1);
-    do {
-        if (hipMalloc(&d_begin, (np + 1) * sizeof(int32_t)) != hipSuccess || hipMalloc(&d_image, nr * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc(&d_xy, 2 * nr * sizeof(double)) != hipSuccess || (var && hipMalloc(&d_var, 3 * nr * sizeof(double)) != hipSuccess) ||
-            hipMalloc(&d_io, 3 * ni * sizeof(double)) != hipSuccess || hipMalloc(&d_eo, 6 * ni * sizeof(double)) != hipSuccess ||
-            hipMalloc(&d_rec, ni * sizeof(IsectImage)) != hipSuccess ||
-            hipMalloc(&d_out, JAICOV_ISECT_OUT_PER_POINT * np * sizeof(double)) != hipSuccess ||
-            hipMalloc(&d_outcome, 2 * np * sizeof(int32_t)) != hipSuccess || !(h_outcome = (int32_t *)malloc(2 * np * sizeof(int32_t))) ||
-            hipMalloc(&d_used, nr) != hipSuccess || (ray_q && hipMalloc(&d_q, nr * sizeof(double)) != hipSuccess)) {
-            rc = JAICOV_ERR_OUT_OF_MEMORY;
-            break;
-        }
+    const int rc = [&]() -> int {      // the owners go before the stream does
+        int32_t *d_begin = nullptr, *d_image = nullptr, *d_outcome = nullptr;
+        double *d_xy = nullptr, *d_var = nullptr, *d_io = nullptr, *d_eo = nullptr, *d_out = nullptr, *d_q = nullptr;
+        uint8_t *d_used = nullptr;
+        IsectImage *d_rec = nullptr;
+        DevBag bag;
+        DevEvent ev0, ev1;
+        if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+        const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
+        const size_t np = (size_t)n_points, nr = (size_t)(n_rays > 0 ? n_rays : 1), ni = (size_t)(n_images > 0 ? n_images : 1);
+        std::vector<int32_t> h_outcome(2 * np);
+        if (bag.alloc(&d_begin, np + 1) != hipSuccess || bag.alloc(&d_image, nr) != hipSuccess || bag.alloc(&d_xy, 2 * nr) != hipSuccess ||
+            (var && bag.alloc(&d_var, 3 * nr) != hipSuccess) || bag.alloc(&d_io, 3 * ni) != hipSuccess || bag.alloc(&d_eo, 6 * ni) != hipSuccess ||
+            bag.alloc(&d_rec, ni) != hipSuccess || bag.alloc(&d_out, JAICOV_ISECT_OUT_PER_POINT * np) != hipSuccess ||
+            bag.alloc(&d_outcome, 2 * np) != hipSuccess || bag.alloc(&d_used, nr) != hipSuccess || (ray_q && bag.alloc(&d_q, nr) != hipSuccess))
+            return JAICOV_ERR_OUT_OF_MEMORY;
         hipMemcpyAsync(d_begin, ray_begin, (np + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
         if (n_rays > 0) {
             hipMemcpyAsync(d_image, ray_image, (size_t)n_rays * sizeof(int32_t), hipMemcpyHostToDevice, s);
@@ -352,24 +352,20 @@ extern "C" int jaicov_isect_points(int32_t n_points, const int32_t *ray_begin, c
             hipLaunchKernelGGL(isect_image_kernel, dim3((n_images + 255) / 256), dim3(256), 0, s, (int)n_images, d_io, d_eo, d_rec);
         hipLaunchKernelGGL(isect_points_kernel, dim3(n_points), dim3(64), 0, s, d_begin, d_image, d_xy, d_var, d_rec, sigma2apriori,
                            (int)max_iterations, reject_threshold * reject_threshold, (int)min_rays, d_out, d_outcome, d_used, d_q);
-        if (hipGetLastError() != hipSuccess) { rc = JAICOV_ERR_DEVICE; break; }
+        if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
         hipEventRecord(e1, s);
         hipMemcpyAsync(out, d_out, JAICOV_ISECT_OUT_PER_POINT * np * sizeof(double), hipMemcpyDeviceToHost, s);
-        hipMemcpyAsync(h_outcome, d_outcome, 2 * np * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        hipMemcpyAsync(h_outcome.data(), d_outcome, 2 * np * sizeof(int32_t), hipMemcpyDeviceToHost, s);
         if (ray_used && n_rays > 0) hipMemcpyAsync(ray_used, d_used, (size_t)n_rays, hipMemcpyDeviceToHost, s);
         if (ray_q && n_rays > 0) hipMemcpyAsync(ray_q, d_q, (size_t)n_rays * sizeof(double), hipMemcpyDeviceToHost, s);
-        if (hipStreamSynchronize(s) != hipSuccess) { rc = JAICOV_ERR_DEVICE; break; }
+        if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
         for (size_t p = 0; p < np; p++) {
             status[p] = h_outcome[2 * p];
             if (iterations) iterations[p] = h_outcome[2 * p + 1];
         }
         if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-    } while (0);
-    hipStreamSynchronize(s);
-    hipFree(d_begin); hipFree(d_image); hipFree(d_xy); hipFree(d_var); hipFree(d_io); hipFree(d_eo); hipFree(d_rec); hipFree(d_out);
-    hipFree(d_outcome); hipFree(d_used); hipFree(d_q);
-    free(h_outcome);
-    hipEventDestroy(e0); hipEventDestroy(e1);
+        return JAICOV_OK;
+    }();
     hipStreamDestroy(s);
     return rc;
 }

@@ -3,15 +3,22 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/jaicov_neq.h"
 #include "ba_kernels.h"
+#include "devbuf.h"
 
 namespace jaicov {
 
-struct RelState;
+// result of jaicov_rel_run, kept by the engine until the next run / release
+struct RelState {
+    long n_rows = 0;
+    DevBuf<double> out;                   // [4][n_rows]: v, qvv, r, t in the caller's row order
+    double summary[6] = {0, 0, 0, 0, 0, 0};  // rel_summary_kernel's five, then the damping of the build Qxx inverts
+};
 
 // What the reliability analysis reads of an engine.  Pointers stay owned by the engine.
 struct RelView {
@@ -33,12 +40,11 @@ struct RelView {
     const std::vector<int32_t> *ip_old2new = nullptr;   // empty, or the engine position of the caller's image point
     const std::vector<int32_t> *blk_ip_begin = nullptr; // engine image blocks (ordinary images served as blocks included)
     const std::vector<int64_t> *blk_w_off = nullptr;    // their weight offsets in p->blk_w (< 0: 2 x 2 weights)
-    RelState **state = nullptr;        // the engine's slot for the result (freed by jaicov_neq_destroy)
+    std::unique_ptr<RelState> *state = nullptr;   // the engine's slot for the result
     std::string *err = nullptr;        // jaicov_neq_last_error text
 };
 
 // Fills the view; with rows != 0 it also brings the compact rows up to the current parameter values first (returns a jaicov_status).
 int engine_rel_view(jaicov_engine *e, RelView *v, int rows);
-void rel_state_free(RelState *s);
 
 }  // namespace jaicov

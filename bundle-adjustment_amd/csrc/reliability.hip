@@ -29,6 +29,7 @@
 #include "../../include/jaicov_reliability.h"
 #include "gemm_f64.h"
 #include "reliability.h"
+#include "status.h"
 
 namespace jaicov {
 
@@ -39,18 +40,6 @@ constexpr int RL_RC = 2 * RL_TP;          // rows of a chunk (32)
 constexpr int RL_K = 64;                  // inner dimension of the shared-column GEMM: [Y | A_s], 2 KC_MAX = 58 padded to 16
 constexpr double RL_UNCONTROLLED = 1e-10; // (P Q_vv P)_ii <= this * P_ii: the observation is not controlled, t = NaN
 static_assert(2 * KC_MAX <= RL_K && RL_K % GEMM_BK == 0, "[Y | A_s] must fit the inner dimension of the shared-column GEMM");
-
-struct RelState {
-    long n_rows = 0;
-    double *d_out = nullptr;              // [4][n_rows]: v, qvv, r, t in the caller's row order
-    double summary[6] = {0, 0, 0, 0, 0, 0};  // rel_summary_kernel's five, then the damping of the build Qxx inverts
-};
-
-void rel_state_free(RelState *s) {
-    if (!s) return;
-    hipFree(s->d_out);
-    delete s;
-}
 
 __device__ __forceinline__ double rl_q(const double *__restrict__ Q, long ld, int i, int j) {
     return i >= j ? Q[(long)i * ld + j] : Q[(long)j * ld + i];
@@ -444,35 +433,7 @@ __global__ __launch_bounds__(256) void rel_summary_kernel(const double *__restri
 
 using namespace jaicov;
 
-#define RL_FAIL(v, code, msg) \
-    do {                      \
-        *(v).err = (msg);     \
-        return (code);        \
-    } while (0)
-#define RL_HIP(v, x)                                                                           \
-    do {                                                                                       \
-        hipError_t _err = (x);                                                                 \
-        if (_err != hipSuccess) {                                                              \
-            *(v).err = std::string(#x) + ": " + hipGetErrorString(_err);                       \
-            return _err == hipErrorOutOfMemory ? JAICOV_ERR_OUT_OF_MEMORY : JAICOV_ERR_DEVICE; \
-        }                                                                                      \
-    } while (0)
-
 namespace {
-// device buffers of one run, freed on every exit
-struct RelWork {
-    std::vector<void *> ptrs;
-    ~RelWork() {
-        for (void *q : ptrs) hipFree(q);
-    }
-    template <typename T>
-    hipError_t alloc(T **dst, size_t count) {
-        *dst = nullptr;
-        hipError_t he = hipMalloc((void **)dst, std::max<size_t>(count, 1) * sizeof(T));
-        if (he == hipSuccess) ptrs.push_back(*dst);
-        return he;
-    }
-};
 constexpr size_t RL_BATCH_BYTES = (size_t)1 << 30;   // work buffers of the dense blocks per batch
 }  // namespace
 
@@ -482,29 +443,29 @@ static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx) {
     const double s0 = v.sigma2;
     const long n_ip = p.n_ip, n_rows = s->n_rows;
     const hipStream_t st = v.stream;
-    RelWork w;
+    DevBag w;                                           // device buffers of this run, freed on every exit
     s->summary[5] = v.lambda;
-    RL_HIP(v, w.alloc(&s->d_out, 4 * (size_t)n_rows));
-    w.ptrs.pop_back();                                  // the result belongs to the state
+    HIPE(*v.err, s->out.reserve(std::max<size_t>(4 * (size_t)n_rows, 1)));   // the result belongs to the state
+    double *const d_res = s->out.get();
     if (n_rows == 0) return JAICOV_OK;
     double *d_dx = nullptr, *d_v = nullptr, *d_sum = nullptr;
-    RL_HIP(v, w.alloc(&d_dx, (size_t)v.U));
-    RL_HIP(v, w.alloc(&d_v, 2 * (size_t)n_ip));
-    RL_HIP(v, w.alloc(&d_sum, 5));
-    if (dx) RL_HIP(v, hipMemcpyAsync(d_dx, dx, (size_t)v.U * sizeof(double), hipMemcpyHostToDevice, st));
-    else RL_HIP(v, hipMemsetAsync(d_dx, 0, (size_t)v.U * sizeof(double), st));
+    HIPE(*v.err, w.alloc(&d_dx, (size_t)v.U));
+    HIPE(*v.err, w.alloc(&d_v, 2 * (size_t)n_ip));
+    HIPE(*v.err, w.alloc(&d_sum, 5));
+    if (dx) HIPE(*v.err, hipMemcpyAsync(d_dx, dx, (size_t)v.U * sizeof(double), hipMemcpyHostToDevice, st));
+    else HIPE(*v.err, hipMemsetAsync(d_dx, 0, (size_t)v.U * sizeof(double), st));
     // engine position -> the caller's image point
     int32_t *d_new2old = nullptr;
     if (!v.ip_old2new->empty() && n_ip > 0) {
         std::vector<int32_t> new2old(n_ip);
         for (long o = 0; o < n_ip; o++) new2old[(*v.ip_old2new)[o]] = (int32_t)o;
-        RL_HIP(v, w.alloc(&d_new2old, (size_t)n_ip));
-        RL_HIP(v, hipMemcpyAsync(d_new2old, new2old.data(), (size_t)n_ip * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        RL_HIP(v, hipStreamSynchronize(st));        // new2old is a host temporary
+        HIPE(*v.err, w.alloc(&d_new2old, (size_t)n_ip));
+        HIPE(*v.err, hipMemcpyAsync(d_new2old, new2old.data(), (size_t)n_ip * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIPE(*v.err, hipStreamSynchronize(st));        // new2old is a host temporary
     }
     if (n_ip > 0) {
         hipLaunchKernelGGL(rel_v_kernel, dim3((unsigned)((n_ip + 255) / 256)), dim3(256), 0, st, p, v.rowsA, v.rowsW, d_dx, d_v);
-        RL_HIP(v, hipGetLastError());
+        HIPE(*v.err, hipGetLastError());
         // which image points have 2 x 2 weights (ordinary groups, or ordinary images served as blocks with compact weights)
         const std::vector<int32_t> &bb = *v.blk_ip_begin;
         const std::vector<int64_t> &bw = *v.blk_w_off;
@@ -518,8 +479,8 @@ static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx) {
             for (int q = bb[g]; q < bb[g + 1]; q++) dense[q] = 1;
         }
         std::vector<int32_t> ip_image(n_ip);
-        RL_HIP(v, hipMemcpyAsync(ip_image.data(), p.ip_image, (size_t)n_ip * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        RL_HIP(v, hipStreamSynchronize(st));
+        HIPE(*v.err, hipMemcpyAsync(ip_image.data(), p.ip_image, (size_t)n_ip * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPE(*v.err, hipStreamSynchronize(st));
         std::vector<int2> chunks;
         for (long q = 0; q < n_ip;) {
             if (dense[q]) { q++; continue; }
@@ -530,11 +491,11 @@ static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx) {
         }
         if (!chunks.empty()) {
             int2 *d_chunks = nullptr;
-            RL_HIP(v, w.alloc(&d_chunks, chunks.size()));
-            RL_HIP(v, hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+            HIPE(*v.err, w.alloc(&d_chunks, chunks.size()));
+            HIPE(*v.err, hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * sizeof(int2), hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL(rel_points_kernel, dim3((unsigned)chunks.size()), dim3(RL_PTS), 0, st, p, d_chunks, v.Q, v.ld, v.rowsA, d_v,
-                               v.ll_diag, d_new2old, s0, s2t, n_rows, s->d_out);
-            RL_HIP(v, hipGetLastError());
+                               v.ll_diag, d_new2old, s0, s2t, n_rows, d_res);
+            HIPE(*v.err, hipGetLastError());
         }
         if (!dense_blocks.empty()) {
             const int nd = (int)dense_blocks.size();
@@ -546,13 +507,13 @@ static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx) {
             const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)nd, cap));
             int32_t *d_bl = nullptr;
             double *d_H = nullptr, *d_P = nullptr, *d_G = nullptr, *d_L = nullptr, *d_R = nullptr;
-            RL_HIP(v, w.alloc(&d_bl, (size_t)nd));
-            RL_HIP(v, w.alloc(&d_H, nb * sq));
-            RL_HIP(v, w.alloc(&d_P, nb * sq));
-            RL_HIP(v, w.alloc(&d_G, nb * sq));
-            RL_HIP(v, w.alloc(&d_L, (size_t)nb * mpad * RL_K));
-            RL_HIP(v, w.alloc(&d_R, (size_t)nb * mpad * RL_K));
-            RL_HIP(v, hipMemcpyAsync(d_bl, dense_blocks.data(), (size_t)nd * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIPE(*v.err, w.alloc(&d_bl, (size_t)nd));
+            HIPE(*v.err, w.alloc(&d_H, nb * sq));
+            HIPE(*v.err, w.alloc(&d_P, nb * sq));
+            HIPE(*v.err, w.alloc(&d_G, nb * sq));
+            HIPE(*v.err, w.alloc(&d_L, (size_t)nb * mpad * RL_K));
+            HIPE(*v.err, w.alloc(&d_R, (size_t)nb * mpad * RL_K));
+            HIPE(*v.err, hipMemcpyAsync(d_bl, dense_blocks.data(), (size_t)nd * sizeof(int32_t), hipMemcpyHostToDevice, st));
             for (int b0 = 0; b0 < nd; b0 += nb) {
                 const int n = std::min(nb, nd - b0);
                 const int32_t *bl = d_bl + b0;
@@ -561,41 +522,41 @@ static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx) {
                     const long mp = bb[dense_blocks[k] + 1] - bb[dense_blocks[k]], nch = (mp + RL_TP - 1) / RL_TP;
                     tmax = std::max(tmax, nch * (nch + 1) / 2);
                 }
-                RL_HIP(v, hipMemsetAsync(d_H, 0, n * sq * sizeof(double), st));
+                HIPE(*v.err, hipMemsetAsync(d_H, 0, n * sq * sizeof(double), st));
                 hipLaunchKernelGGL(rel_prep_kernel, dim3(mpad / RL_PTS, n), dim3(RL_PTS), 0, st, p, bl, mpad, v.Q, v.ld, v.rowsA, d_L, d_R);
                 hipLaunchKernelGGL(rel_pp_kernel, dim3((unsigned)tmax, n), dim3(256), 0, st, p, bl, mpad, v.Q, v.ld, v.rowsA, d_H);
                 hipLaunchKernelGGL(rel_pad_kernel, dim3(mpad / 256 + (mpad % 256 ? 1 : 0), mpad, n), dim3(256), 0, st, p, bl, mpad, s0, d_P);
-                RL_HIP(v, hipGetLastError());
+                HIPE(*v.err, hipGetLastError());
                 GemmArgs g1{};   // H += [Y | A_s] [A_s | U]'
                 g1.A = d_L; g1.lda = RL_K; g1.B = d_R; g1.ldb = RL_K; g1.C = d_H; g1.ldc = mpad;
                 g1.M = mpad; g1.N = mpad; g1.K = RL_K; g1.alpha = 1.0; g1.beta = 1.0; g1.kmode = KMODE_FULL;
                 g1.strideA = (long)mpad * RL_K; g1.strideB = (long)mpad * RL_K; g1.strideC = (long)sq;
-                RL_HIP(v, gemm_f64(st, LAY_KC, LAY_KC, g1, n));
+                HIPE(*v.err, gemm_f64(st, LAY_KC, LAY_KC, g1, n));
                 GemmArgs g2{};   // G = H P  (P symmetric: P(k, j) = P[j][k])
                 g2.A = d_H; g2.lda = mpad; g2.B = d_P; g2.ldb = mpad; g2.C = d_G; g2.ldc = mpad;
                 g2.M = mpad; g2.N = mpad; g2.K = mpad; g2.alpha = 1.0; g2.beta = 0.0; g2.kmode = KMODE_FULL;
                 g2.strideA = (long)sq; g2.strideB = (long)sq; g2.strideC = (long)sq;
-                RL_HIP(v, gemm_f64(st, LAY_KC, LAY_KC, g2, n));
+                HIPE(*v.err, gemm_f64(st, LAY_KC, LAY_KC, g2, n));
                 hipLaunchKernelGGL(rel_block_kernel, dim3(mpad / 256 + (mpad % 256 ? 1 : 0), n), dim3(256), 0, st, p, bl, mpad, d_H, d_P, d_G,
-                                   d_v, v.ll_diag, d_new2old, s0, s2t, n_rows, s->d_out);
-                RL_HIP(v, hipGetLastError());
+                                   d_v, v.ll_diag, d_new2old, s0, s2t, n_rows, d_res);
+                HIPE(*v.err, hipGetLastError());
             }
         }
     }
     if (p.n_sb > 0) {
         hipLaunchKernelGGL(rel_scalebar_kernel, dim3((p.n_sb + 63) / 64), dim3(64), 0, st, p, v.d_vals, v.Q, v.ld, d_dx, s0, s2t, 2 * n_ip,
-                           n_rows, s->d_out);
-        RL_HIP(v, hipGetLastError());
+                           n_rows, d_res);
+        HIPE(*v.err, hipGetLastError());
     }
     if (p.n_dg > 0) {
         hipLaunchKernelGGL(rel_direct_kernel, dim3(p.n_dg), dim3(256), 0, st, p, v.d_vals, v.Q, v.ld, d_dx, v.ll_diag + 2 * n_ip, s0, s2t,
-                           2 * n_ip + p.n_sb, n_rows, s->d_out);
-        RL_HIP(v, hipGetLastError());
+                           2 * n_ip + p.n_sb, n_rows, d_res);
+        HIPE(*v.err, hipGetLastError());
     }
-    hipLaunchKernelGGL(rel_summary_kernel, dim3(1), dim3(256), 0, st, s->d_out, n_rows, d_sum);
-    RL_HIP(v, hipGetLastError());
-    RL_HIP(v, hipMemcpyAsync(s->summary, d_sum, 5 * sizeof(double), hipMemcpyDeviceToHost, st));
-    RL_HIP(v, hipStreamSynchronize(st));
+    hipLaunchKernelGGL(rel_summary_kernel, dim3(1), dim3(256), 0, st, d_res, n_rows, d_sum);
+    HIPE(*v.err, hipGetLastError());
+    HIPE(*v.err, hipMemcpyAsync(s->summary, d_sum, 5 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPE(*v.err, hipStreamSynchronize(st));
     return JAICOV_OK;
 }
 
@@ -603,28 +564,26 @@ extern "C" int jaicov_rel_run(jaicov_engine *e, double sigma2_test, const double
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     RelView v;
     engine_rel_view(e, &v, 0);
-    if (v.sharded) RL_FAIL(v, JAICOV_ERR_UNSUPPORTED, "reliability needs an engine that holds every observation (not a shard)");
-    if (!(sigma2_test > 0) || !std::isfinite(sigma2_test)) RL_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "sigma2_test must be positive and finite");
+    if (v.sharded) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "reliability needs an engine that holds every observation (not a shard)");
+    if (!(sigma2_test > 0) || !std::isfinite(sigma2_test)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "sigma2_test must be positive and finite");
     if (!v.full_q)
-        RL_FAIL(v, JAICOV_ERR_BAD_STATE, "no full cofactor matrix: solve with JAICOV_INVERT_FULL or JAICOV_INVERT_FULL_EXPANDED first");
+        FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no full cofactor matrix: solve with JAICOV_INVERT_FULL or JAICOV_INVERT_FULL_EXPANDED first");
     const DevProblem &p0 = *v.p;
     const long rows = 2 * (long)p0.n_ip + p0.n_sb + p0.n_dg_rows;
-    if (rows > INT32_MAX) RL_FAIL(v, JAICOV_ERR_UNSUPPORTED, "more than 2^31 - 1 observation rows");
-    RL_HIP(v, hipSetDevice(v.device));
+    if (rows > INT32_MAX) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "more than 2^31 - 1 observation rows");
+    HIPE(*v.err, hipSetDevice(v.device));
     int rc = engine_rel_view(e, &v, 1);    // the compact rows of the current parameter values
     if (rc != JAICOV_OK) return rc;
     // the arguments are accepted: the previous result goes
-    rel_state_free(*v.state);
-    *v.state = nullptr;
-    RelState *s = new RelState();
+    v.state->reset();
+    std::unique_ptr<RelState> s(new RelState());
     s->n_rows = rows;
-    rc = rel_run_impl(v, s, sigma2_test, dx);
+    rc = rel_run_impl(v, s.get(), sigma2_test, dx);
     if (rc != JAICOV_OK) {
         hipStreamSynchronize(v.stream);
-        rel_state_free(s);
         return rc;
     }
-    *v.state = s;
+    *v.state = std::move(s);
     if (n_rows) *n_rows = (int32_t)rows;
     return JAICOV_OK;
 }
@@ -632,7 +591,7 @@ extern "C" int jaicov_rel_run(jaicov_engine *e, double sigma2_test, const double
 static RelState *rl_result(jaicov_engine *e, RelView &v) {
     engine_rel_view(e, &v, 0);
     if (!*v.state) *v.err = "no reliability result: call jaicov_rel_run first";
-    return *v.state;
+    return v.state->get();
 }
 
 extern "C" int jaicov_rel_get(jaicov_engine *e, double *vres, double *qvv, double *r, double *t, int32_t n) {
@@ -640,13 +599,13 @@ extern "C" int jaicov_rel_get(jaicov_engine *e, double *vres, double *qvv, doubl
     RelView v;
     RelState *s = rl_result(e, v);
     if (!s) return JAICOV_ERR_BAD_STATE;
-    if (n != s->n_rows) RL_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "n must equal the number of observation rows of the last run");
+    if (n != s->n_rows) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "n must equal the number of observation rows of the last run");
     if (n == 0) return JAICOV_OK;
-    RL_HIP(v, hipSetDevice(v.device));
+    HIPE(*v.err, hipSetDevice(v.device));
     double *dst[4] = {vres, qvv, r, t};
     for (int k = 0; k < 4; k++)
-        if (dst[k]) RL_HIP(v, hipMemcpyAsync(dst[k], s->d_out + k * (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    RL_HIP(v, hipStreamSynchronize(v.stream));
+        if (dst[k]) HIPE(*v.err, hipMemcpyAsync(dst[k], s->out.get() + k * (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    HIPE(*v.err, hipStreamSynchronize(v.stream));
     return JAICOV_OK;
 }
 
@@ -655,7 +614,7 @@ extern "C" int jaicov_rel_summary(jaicov_engine *e, double *out, int32_t n) {
     RelView v;
     RelState *s = rl_result(e, v);
     if (!s) return JAICOV_ERR_BAD_STATE;
-    if ((n != 5 && n != 6) || !out) RL_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "the summary has 5 entries (6 with the damping value)");
+    if ((n != 5 && n != 6) || !out) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "the summary has 5 entries (6 with the damping value)");
     memcpy(out, s->summary, (size_t)n * sizeof(double));
     return JAICOV_OK;
 }
@@ -667,8 +626,7 @@ extern "C" int jaicov_rel_release(jaicov_engine *e) {
     if (*v.state) {
         hipSetDevice(v.device);
         hipStreamSynchronize(v.stream);
-        rel_state_free(*v.state);
-        *v.state = nullptr;
+        v.state->reset();
     }
     return JAICOV_OK;
 }

@@ -3,15 +3,26 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/jaicov_neq.h"
 #include "ba_kernels.h"
+#include "devbuf.h"
 
 namespace jaicov {
 
-struct XformState;
+// result of jaicov_xform_run, kept by the engine until the next run / release
+struct XformState {
+    int nT = 0;                           // transformed points
+    long R = 0;                           // rows = 3 nT
+    std::vector<int32_t> ids;             // (point, src, ref) per transformed point
+    DevBuf<double> xyz, Jv, ap;
+    DevBuf<int32_t> tp, Jc;
+    DevBuf<int2> chunks;
+    int n_chunks = 0;
+};
 
 // What the transformation reads of an engine: the cofactor matrix (lower, row-major square, as gather_sub_kernel reads it), the
 // device slot vector and the structure.  Pointers stay owned by the engine.
@@ -25,11 +36,10 @@ struct XformView {
     const double *d_vals = nullptr;    // current slot vector on the device
     const DevProblem *p = nullptr;     // counts + device tables (ip_image / ip_point: every image point of the problem)
     const std::vector<int32_t> *slot_col = nullptr;   // column of every slot (JAICOV_COL_FIXED for fixed parameters)
-    XformState **state = nullptr;      // the engine's slot for the result (freed by jaicov_neq_destroy)
+    std::unique_ptr<XformState> *state = nullptr;   // the engine's slot for the result
     std::string *err = nullptr;        // jaicov_neq_last_error text
 };
 
 void engine_xform_view(jaicov_engine *e, XformView *v);
-void xform_state_free(XformState *s);
 
 }  // namespace jaicov

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/jaicov_transform.h"
+#include "status.h"
 #include "transform.h"
 
 namespace jaicov {
@@ -31,22 +32,6 @@ constexpr int XF_PR = 3 * XF_TP;          // point rows / columns of a chunk (48
 constexpr int XF_NC = XF_PR + 12;         // + the 6 + 6 exterior-orientation columns (60)
 constexpr int XF_NT = 256;                // threads per workgroup of the product
 constexpr int XF_ZPT = (XF_PR * XF_NC + XF_NT - 1) / XF_NT;   // Z entries per thread (12)
-
-struct XformState {
-    int nT = 0;                           // transformed points
-    long R = 0;                           // rows = 3 nT
-    std::vector<int32_t> ids;             // (point, src, ref) per transformed point
-    double *d_xyz = nullptr, *d_Jv = nullptr, *d_ap = nullptr;
-    int32_t *d_tp = nullptr, *d_Jc = nullptr;
-    int2 *d_chunks = nullptr;
-    int n_chunks = 0;
-};
-
-void xform_state_free(XformState *s) {
-    if (!s) return;
-    hipFree(s->d_xyz); hipFree(s->d_Jv); hipFree(s->d_ap); hipFree(s->d_tp); hipFree(s->d_Jc); hipFree(s->d_chunks);
-    delete s;
-}
 
 // R(omega, phi, kappa) of the collinearity rows (rows.hip, PDF:125-135), row-major, and its derivatives by omega, phi, kappa
 __device__ __forceinline__ void xf_rotation(const double *eo, double R[9], double dR[3][9]) {
@@ -229,25 +214,6 @@ __global__ __launch_bounds__(256) void xform_blocks_kernel(const double *__restr
 
 using namespace jaicov;
 
-#define XF_FAIL(v, code, msg) \
-    do {                      \
-        *(v).err = (msg);     \
-        return (code);        \
-    } while (0)
-#define XF_HIP(v, x)                                                                           \
-    do {                                                                                       \
-        hipError_t _err = (x);                                                                 \
-        if (_err != hipSuccess) {                                                              \
-            *(v).err = std::string(#x) + ": " + hipGetErrorString(_err);                       \
-            return _err == hipErrorOutOfMemory ? JAICOV_ERR_OUT_OF_MEMORY : JAICOV_ERR_DEVICE; \
-        }                                                                                      \
-    } while (0)
-
-template <typename T>
-static hipError_t xf_alloc(T **dst, size_t count) {
-    return hipMalloc((void **)dst, std::max<size_t>(count, 1) * sizeof(T));
-}
-
 static int xform_run_impl(XformView &v, XformState *s, double sigma2) {
     const DevProblem &p = *v.p;
     const int nT = s->nT;
@@ -263,21 +229,21 @@ static int xform_run_impl(XformView &v, XformState *s, double sigma2) {
         t += n;
     }
     s->n_chunks = (int)chunks.size();
-    XF_HIP(v, xf_alloc(&s->d_tp, 3 * (size_t)nT));
-    XF_HIP(v, xf_alloc(&s->d_xyz, 3 * (size_t)nT));
-    XF_HIP(v, xf_alloc(&s->d_Jv, 45 * (size_t)nT));
-    XF_HIP(v, xf_alloc(&s->d_Jc, 15 * (size_t)nT));
-    XF_HIP(v, xf_alloc(&s->d_chunks, chunks.size()));
-    XF_HIP(v, xf_alloc(&s->d_ap, packed));
-    XF_HIP(v, hipMemcpyAsync(s->d_tp, s->ids.data(), 3 * (size_t)nT * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-    XF_HIP(v, hipMemcpyAsync(s->d_chunks, chunks.data(), chunks.size() * sizeof(int2), hipMemcpyHostToDevice, v.stream));
-    hipLaunchKernelGGL(xform_rows_kernel, dim3((nT + 255) / 256), dim3(256), 0, v.stream, p, v.d_vals, s->d_tp, nT, s->d_xyz, s->d_Jv, s->d_Jc);
-    XF_HIP(v, hipGetLastError());
+    HIPE(*v.err, s->tp.reserve(3 * (size_t)nT));
+    HIPE(*v.err, s->xyz.reserve(3 * (size_t)nT));
+    HIPE(*v.err, s->Jv.reserve(45 * (size_t)nT));
+    HIPE(*v.err, s->Jc.reserve(15 * (size_t)nT));
+    HIPE(*v.err, s->chunks.reserve(chunks.size()));
+    HIPE(*v.err, s->ap.reserve(packed));
+    HIPE(*v.err, hipMemcpyAsync(s->tp.get(), s->ids.data(), 3 * (size_t)nT * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+    HIPE(*v.err, hipMemcpyAsync(s->chunks.get(), chunks.data(), chunks.size() * sizeof(int2), hipMemcpyHostToDevice, v.stream));
+    hipLaunchKernelGGL(xform_rows_kernel, dim3((nT + 255) / 256), dim3(256), 0, v.stream, p, v.d_vals, s->tp.get(), nT, s->xyz.get(), s->Jv.get(), s->Jc.get());
+    HIPE(*v.err, hipGetLastError());
     const long nc = (long)chunks.size(), tiles = nc * (nc + 1) / 2;
     const unsigned grid = (unsigned)std::min<long>(tiles, 1L << 24);
-    hipLaunchKernelGGL(xform_cov_kernel, dim3(grid), dim3(XF_NT), 0, v.stream, v.Q, v.ld, s->d_chunks, tiles, s->d_Jv, s->d_Jc, sigma2, s->d_ap);
-    XF_HIP(v, hipGetLastError());
-    XF_HIP(v, hipStreamSynchronize(v.stream));
+    hipLaunchKernelGGL(xform_cov_kernel, dim3(grid), dim3(XF_NT), 0, v.stream, v.Q, v.ld, s->chunks.get(), tiles, s->Jv.get(), s->Jc.get(), sigma2, s->ap.get());
+    HIPE(*v.err, hipGetLastError());
+    HIPE(*v.err, hipStreamSynchronize(v.stream));
     return JAICOV_OK;
 }
 
@@ -287,27 +253,27 @@ extern "C" int jaicov_xform_run(jaicov_engine *e, const int32_t *points, int32_t
     XformView v;
     engine_xform_view(e, &v);
     if (!v.full_q)
-        XF_FAIL(v, JAICOV_ERR_BAD_STATE, "no full cofactor matrix: solve with JAICOV_INVERT_FULL or JAICOV_INVERT_FULL_EXPANDED first");
+        FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no full cofactor matrix: solve with JAICOV_INVERT_FULL or JAICOV_INVERT_FULL_EXPANDED first");
     const DevProblem &p = *v.p;
     if (n_points < 0 || n_pairs < 0 || (n_points > 0 && !points) || (n_pairs > 0 && (!pair_ref || !pair_src)))
-        XF_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "point / pair arrays missing or negative counts");
-    if (!std::isfinite(sigma2)) XF_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "sigma2 must be finite");
+        FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "point / pair arrays missing or negative counts");
+    if (!std::isfinite(sigma2)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "sigma2 must be finite");
     std::vector<uint8_t> seen(p.n_points, 0);
     for (int i = 0; i < n_points; i++) {
-        if (points[i] < 0 || points[i] >= p.n_points) XF_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "point index out of range");
-        if (seen[points[i]]) XF_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "duplicate point (the reference takes a Set)");
+        if (points[i] < 0 || points[i] >= p.n_points) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "point index out of range");
+        if (seen[points[i]]) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "duplicate point (the reference takes a Set)");
         seen[points[i]] = 1;
     }
     for (int k = 0; k < n_pairs; k++)
         if (pair_ref[k] < 0 || pair_ref[k] >= p.n_images || pair_src[k] < 0 || pair_src[k] >= p.n_images)
-            XF_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "image index out of range");
-    XF_HIP(v, hipSetDevice(v.device));
+            FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "image index out of range");
+    HIPE(*v.err, hipSetDevice(v.device));
     // which points each source image observes (CTEO:83 image.get(point) != null): CSR over the problem's image points
     std::vector<int32_t> ip_image(p.n_ip), ip_point(p.n_ip);
     if (p.n_ip > 0) {
-        XF_HIP(v, hipMemcpyAsync(ip_image.data(), p.ip_image, (size_t)p.n_ip * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-        XF_HIP(v, hipMemcpyAsync(ip_point.data(), p.ip_point, (size_t)p.n_ip * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-        XF_HIP(v, hipStreamSynchronize(v.stream));
+        HIPE(*v.err, hipMemcpyAsync(ip_image.data(), p.ip_image, (size_t)p.n_ip * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPE(*v.err, hipMemcpyAsync(ip_point.data(), p.ip_point, (size_t)p.n_ip * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+        HIPE(*v.err, hipStreamSynchronize(v.stream));
     }
     std::vector<int32_t> img_begin(p.n_images + 1, 0), img_pts(p.n_ip);
     for (int q = 0; q < p.n_ip; q++) img_begin[ip_image[q] + 1]++;
@@ -324,27 +290,25 @@ extern "C" int jaicov_xform_run(jaicov_engine *e, const int32_t *points, int32_t
             if (stamp[points[i]] == k) { ids.push_back(points[i]); ids.push_back(S); ids.push_back(T); }
     }
     // the arguments are accepted: the previous result goes
-    xform_state_free(*v.state);
-    *v.state = nullptr;
-    XformState *s = new XformState();
+    v.state->reset();
+    std::unique_ptr<XformState> s(new XformState());
     s->ids = std::move(ids);
     s->nT = (int)(s->ids.size() / 3);
     s->R = 3 * (long)s->nT;
-    const int rc = xform_run_impl(v, s, sigma2);
+    const int rc = xform_run_impl(v, s.get(), sigma2);
     if (rc != JAICOV_OK) {
         hipStreamSynchronize(v.stream);
-        xform_state_free(s);
         return rc;
     }
-    *v.state = s;
     if (n_transformed) *n_transformed = s->nT;
+    *v.state = std::move(s);
     return JAICOV_OK;
 }
 
 static XformState *xf_result(jaicov_engine *e, XformView &v) {
     engine_xform_view(e, &v);
     if (!*v.state) *v.err = "no transformation result: call jaicov_xform_run first";
-    return *v.state;
+    return v.state->get();
 }
 
 extern "C" int jaicov_xform_get_coordinates(jaicov_engine *e, double *xyz, int32_t *ids, int32_t n) {
@@ -352,12 +316,12 @@ extern "C" int jaicov_xform_get_coordinates(jaicov_engine *e, double *xyz, int32
     XformView v;
     XformState *s = xf_result(e, v);
     if (!s) return JAICOV_ERR_BAD_STATE;
-    if (n != s->nT) XF_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "n must equal the number of transformed points");
+    if (n != s->nT) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "n must equal the number of transformed points");
     if (ids && n > 0) memcpy(ids, s->ids.data(), 3 * (size_t)n * sizeof(int32_t));
     if (xyz && n > 0) {
-        XF_HIP(v, hipSetDevice(v.device));
-        XF_HIP(v, hipMemcpyAsync(xyz, s->d_xyz, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-        XF_HIP(v, hipStreamSynchronize(v.stream));
+        HIPE(*v.err, hipSetDevice(v.device));
+        HIPE(*v.err, hipMemcpyAsync(xyz, s->xyz.get(), 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+        HIPE(*v.err, hipStreamSynchronize(v.stream));
     }
     return JAICOV_OK;
 }
@@ -368,12 +332,12 @@ extern "C" int jaicov_xform_get_covariance(jaicov_engine *e, double *packed, siz
     XformState *s = xf_result(e, v);
     if (!s) return JAICOV_ERR_BAD_STATE;
     const size_t want = (size_t)s->R * (s->R + 1) / 2;
-    if (len != want) XF_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "covariance buffer length must be R(R+1)/2");
+    if (len != want) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "covariance buffer length must be R(R+1)/2");
     if (want == 0) return JAICOV_OK;
-    if (!packed) XF_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "covariance buffer missing");
-    XF_HIP(v, hipSetDevice(v.device));
-    XF_HIP(v, hipMemcpyAsync(packed, s->d_ap, want * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    XF_HIP(v, hipStreamSynchronize(v.stream));
+    if (!packed) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "covariance buffer missing");
+    HIPE(*v.err, hipSetDevice(v.device));
+    HIPE(*v.err, hipMemcpyAsync(packed, s->ap.get(), want * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    HIPE(*v.err, hipStreamSynchronize(v.stream));
     return JAICOV_OK;
 }
 
@@ -382,22 +346,18 @@ extern "C" int jaicov_xform_get_covariance_sub(jaicov_engine *e, const int32_t *
     XformView v;
     XformState *s = xf_result(e, v);
     if (!s) return JAICOV_ERR_BAD_STATE;
-    if (!rows || !out || k <= 0) XF_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "rows / out missing or k <= 0");
+    if (!rows || !out || k <= 0) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "rows / out missing or k <= 0");
     for (int i = 0; i < k; i++)
-        if (rows[i] < 0 || rows[i] >= s->R) XF_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "row index out of range");
-    XF_HIP(v, hipSetDevice(v.device));
-    int32_t *d_rows = nullptr;
-    double *d_out = nullptr;
-    XF_HIP(v, hipMalloc(&d_rows, (size_t)k * sizeof(int32_t)));
-    hipError_t he = hipMalloc(&d_out, (size_t)k * k * sizeof(double));
-    if (he == hipSuccess) he = hipMemcpyAsync(d_rows, rows, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, v.stream);
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(xform_sub_kernel, dim3((unsigned)(((size_t)k * k + 255) / 256)), dim3(256), 0, v.stream, s->d_ap, d_rows, k, d_out);
-        he = hipMemcpyAsync(out, d_out, (size_t)k * k * sizeof(double), hipMemcpyDeviceToHost, v.stream);
-    }
-    if (he == hipSuccess) he = hipStreamSynchronize(v.stream);
-    hipFree(d_rows); hipFree(d_out);
-    XF_HIP(v, he);
+        if (rows[i] < 0 || rows[i] >= s->R) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "row index out of range");
+    HIPE(*v.err, hipSetDevice(v.device));
+    DevBuf<int32_t> d_rows;
+    DevBuf<double> d_out;
+    HIPE(*v.err, d_rows.reserve((size_t)k));
+    HIPE(*v.err, d_out.reserve((size_t)k * k));
+    HIPE(*v.err, hipMemcpyAsync(d_rows.get(), rows, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+    hipLaunchKernelGGL(xform_sub_kernel, dim3((unsigned)(((size_t)k * k + 255) / 256)), dim3(256), 0, v.stream, s->ap.get(), d_rows.get(), k, d_out.get());
+    HIPE(*v.err, hipMemcpyAsync(out, d_out.get(), (size_t)k * k * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    HIPE(*v.err, hipStreamSynchronize(v.stream));
     return JAICOV_OK;
 }
 
@@ -406,17 +366,15 @@ extern "C" int jaicov_xform_get_point_blocks(jaicov_engine *e, double *out, int3
     XformView v;
     XformState *s = xf_result(e, v);
     if (!s) return JAICOV_ERR_BAD_STATE;
-    if (n != s->nT) XF_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "n must equal the number of transformed points");
+    if (n != s->nT) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "n must equal the number of transformed points");
     if (n == 0) return JAICOV_OK;
-    if (!out) XF_FAIL(v, JAICOV_ERR_BAD_ARGUMENT, "out missing");
-    XF_HIP(v, hipSetDevice(v.device));
-    double *d_out = nullptr;
-    XF_HIP(v, hipMalloc(&d_out, 9 * (size_t)n * sizeof(double)));
-    hipLaunchKernelGGL(xform_blocks_kernel, dim3((unsigned)((9 * (size_t)n + 255) / 256)), dim3(256), 0, v.stream, s->d_ap, (long)n, d_out);
-    hipError_t he = hipMemcpyAsync(out, d_out, 9 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, v.stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(v.stream);
-    hipFree(d_out);
-    XF_HIP(v, he);
+    if (!out) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "out missing");
+    HIPE(*v.err, hipSetDevice(v.device));
+    DevBuf<double> d_out;
+    HIPE(*v.err, d_out.reserve(9 * (size_t)n));
+    hipLaunchKernelGGL(xform_blocks_kernel, dim3((unsigned)((9 * (size_t)n + 255) / 256)), dim3(256), 0, v.stream, s->ap.get(), (long)n, d_out.get());
+    HIPE(*v.err, hipMemcpyAsync(out, d_out.get(), 9 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    HIPE(*v.err, hipStreamSynchronize(v.stream));
     return JAICOV_OK;
 }
 
@@ -427,8 +385,7 @@ extern "C" int jaicov_xform_release(jaicov_engine *e) {
     if (*v.state) {
         hipSetDevice(v.device);
         hipStreamSynchronize(v.stream);
-        xform_state_free(*v.state);
-        *v.state = nullptr;
+        v.state->reset();
     }
     return JAICOV_OK;
 }

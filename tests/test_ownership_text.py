@@ -1,0 +1,44 @@
+"""csrc/devbuf.h is the only file of the library that allocates or frees device memory and creates or destroys events -- checked at
+the text level, so that the count DevBuf keeps (jaicov_debug_device_census, tests/test_gpu_ownership.py) is complete by
+construction; and the status macros exist once (csrc/status.h)."""
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "bundle-adjustment_amd", "csrc")
+
+RAW = [r"hipMalloc\w*\s*\(", r"hipExtMalloc\w*\s*\(", r"hipFree\s*\(", r"hipEvent(Create\w*|Destroy)\s*\("]
+GONE = ["XF_HIP", "RL_HIP", "DHIP", "XF_FAIL", "RL_FAIL", "DFAIL"]
+
+
+def sources():
+    names = sorted(n for n in os.listdir(CSRC) if n.endswith((".hip", ".h")))
+    assert "devbuf.h" in names and "engine.hip" in names and len(names) >= 25
+    return {n: open(os.path.join(CSRC, n)).read() for n in names}
+
+
+def code(text):
+    return re.sub(r"//[^\n]*", "", text)
+
+
+def test_only_devbuf_allocates_frees_and_makes_events():
+    src = sources()
+    for name, text in src.items():
+        if name == "devbuf.h":
+            continue
+        for pat in RAW:
+            hits = [m.group(0) for m in re.finditer(pat, code(text))]
+            assert not hits, (name, hits)
+    own = code(src["devbuf.h"])
+    for pat in RAW:                                    # the patterns do find the calls where they are allowed
+        assert re.search(pat, own), pat
+
+
+def test_status_macros_exist_once():
+    src = sources()
+    for name, text in src.items():
+        for macro in GONE:
+            assert not re.search(r"\b%s\b" % macro, text), (name, macro)
+    for macro in ("FAIL", "HIPE", "HIPCHK"):
+        where = [n for n, t in src.items() if re.search(r"#\s*define\s+%s\b" % macro, t)]
+        assert where == ["status.h"], (macro, where)
