@@ -13,11 +13,13 @@
 
 namespace jaicov {
 
-// result of jaicov_rel_run, kept by the engine until the next run / release
+// result of jaicov_rel_run / jaicov_rel_run_points, kept by the engine until the next run / release
 struct RelState {
     long n_rows = 0;
     DevBuf<double> out;                   // [4][n_rows]: v, qvv, r, t in the caller's row order
     double summary[6] = {0, 0, 0, 0, 0, 0};  // rel_summary_kernel's five, then the damping of the build Qxx inverts
+    long n_points = -1;                   // image points of the table below; -1: a plain jaicov_rel_run, no table
+    DevBuf<double> points;                // [JAICOV_REL_POINT_COLUMNS][n_points] in the caller's order (jaicov_rel_run_points)
 };
 
 // What the reliability analysis reads of an engine.  Pointers stay owned by the engine.

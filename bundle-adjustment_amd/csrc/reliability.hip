@@ -12,6 +12,17 @@
 //   rel_scalebar_kernel, rel_direct_kernel   the other observation groups
 //   rel_summary_kernel  sum r, max |t| and its row, NaN count, min r in one workgroup
 //
+// Leave-one-out table of every image point (include/jaicov_reliability_points.h), launched by jaicov_rel_run_points only, after
+// the kernels above, which it runs unchanged:
+//   rel_points_loo_kernel     image points with 2 x 2 weights: H, P as in rel_points_kernel, then M = P - P H P, nabla^ = -inv(M) g
+//                             and the shift -Q[P(q), cols(q)] A_q' P nabla^ over the point's own 3 + kc columns, all per lane
+//   rel_block_points_kernel   dense blocks, one thread per image point, after G = H P: g, M = P_S - (P G)_SS (sums over
+//                             j = 0 .. m-1 in order), the closed-form columns; nabla^ goes to a work buffer
+//   rel_shift_pp_kernel       dense blocks: sum_j Q[P(q), P(j)] a_p(j) c_q[j], c_q = P[:, S_q] nabla^_q, one workgroup per pair of
+//                             16-point chunks (rel_pp_kernel's staging of Q), one partial sum per (point, chunk)
+//   rel_shift_kernel          dense blocks, one thread per image point: A_s' c_q (kc sums over j in order), Q[P(q), S] of it, the
+//                             partial sums added in chunk order; the sum order does not depend on the images per batch
+//
 // H of a dense block.  A row of image point q has its 3 point columns P(q) and the kc <= 29 shared columns S of the image (IO,
 // distortion, EO).  With a_p, a_s the two parts of a row:
 //   H_rs = a_p(r)' Q[P(r), P(s)] a_p(s) + y(r)' a_s(s) + a_s(r)' u(s),   y(r) = Q[S, P(r)] a_p(r),  u(s) = y(s) + Q[S, S] a_s(s).
@@ -27,6 +38,7 @@
 #include <vector>
 
 #include "../../include/jaicov_reliability.h"
+#include "../../include/jaicov_reliability_points.h"
 #include "gemm_f64.h"
 #include "reliability.h"
 #include "status.h"
@@ -322,6 +334,314 @@ __global__ __launch_bounds__(256) void rel_block_kernel(DevProblem p, const int3
     rl_store(out, n_rows, rl_row(new2old, ipb + (i >> 1), i & 1), vb[i], lld[2 * (long)ipb + i] / s0 - h, 1.0 - gii, rl_t(pv, pii - php, pii, s2t));
 }
 
+// ---- leave-one-out table of every image point (include/jaicov_reliability_points.h) ----------------------------------------------
+struct RelPointArgs {
+    double lambda0, omega;
+    int dof;
+};
+
+// Columns 0-10 of image point o (the caller's index) of the table pt[JAICOV_REL_POINT_COLUMNS][n] from g = (P v)_S, P_S and
+// N = (P A Qxx A' P)_SS; M = P_S - N.  Returns nabla^ = -inv(M) g, NaN where the point is not controlled.  The eigenvalues of M and
+// of inv(M) N (= those of inv(M) P_S less 1) are the closed forms of a 2 x 2 matrix.
+__device__ __forceinline__ double2 rl_point_columns(double g0, double g1, double pxx, double pxy, double pyy, double nxx, double nxy,
+                                                    double nyy, double s2t, RelPointArgs pa, long n, long o, double *__restrict__ pt) {
+    const double mxx = pxx - nxx, mxy = pxy - nxy, myy = pyy - nyy;
+    const double half = 0.5 * (mxx + myy), dev = hypot(0.5 * (mxx - myy), mxy);
+    const double mu_max = half + dev;
+    const double det = fma(mxx, myy, -(mxy * mxy));
+    const double mu_min = mu_max > 0.0 ? det / mu_max : half - dev;
+    pt[5 * n + o] = mxx;
+    pt[6 * n + o] = mxy;
+    pt[7 * n + o] = myy;
+    const double nan = (double)NAN;
+    if (!(mu_min > RL_UNCONTROLLED * fmax(pxx, pyy))) {
+        for (int c = 0; c < 5; c++) pt[c * n + o] = nan;
+        for (int c = 8; c < 11; c++) pt[c * n + o] = nan;
+        return make_double2(nan, nan);
+    }
+    const double nx = -(myy * g0 - mxy * g1) / det, ny = -(mxx * g1 - mxy * g0) / det;
+    const double q = -(g0 * nx + g1 * ny);
+    pt[o] = q;
+    pt[n + o] = q / (2.0 * s2t);
+    const double rest = pa.omega - q;
+    pt[2 * n + o] = (pa.dof > 2 && pa.omega > 0.0 && rest > 0.0) ? (0.5 * q) / (rest / (double)(pa.dof - 2)) : nan;
+    pt[3 * n + o] = nx;
+    pt[4 * n + o] = ny;
+    pt[8 * n + o] = sqrt(pa.lambda0 * s2t / mu_min);
+    pt[9 * n + o] = sqrt(pa.lambda0 * s2t / mu_max);
+    // lambda_max(inv(M) N): the larger root of det(M) l^2 - (mxx nyy + myy nxx - 2 mxy nxy) l + det(N) = 0
+    const double tr = mxx * nyy + myy * nxx - 2.0 * mxy * nxy, detn = fma(nxx, nyy, -(nxy * nxy));
+    const double lmax = (tr + sqrt(fmax(tr * tr - 4.0 * det * detn, 0.0))) / (2.0 * det);
+    pt[10 * n + o] = sqrt(pa.lambda0 * fmax(lmax, 0.0));
+    return make_double2(nx, ny);
+}
+
+// The image points of rel_points_kernel's chunks once more: H and P as there, then the point's columns and its shift.
+__global__ __launch_bounds__(RL_PTS) void rel_points_loo_kernel(DevProblem p, const int2 *__restrict__ chunks, const double *__restrict__ Q, long ld,
+                                                                const double *__restrict__ rowsA, const double *__restrict__ v,
+                                                                const int32_t *__restrict__ new2old, double s0, double s2t, RelPointArgs pa,
+                                                                double *__restrict__ pt) {
+    __shared__ double sQ[KC_MAX * KC_MAX];
+    __shared__ double sA[2 * KC_MAX * RL_PTS];   // the shared part a_s of both rows of every point: [row][column][lane]
+    __shared__ int scol[KC_MAX];
+    const int tid = threadIdx.x;
+    const int2 ch = chunks[blockIdx.x];
+    const int img = p.ip_image[ch.x], cam = p.image_camera[img], jb = p.cam_dist_begin[cam];
+    const int kc = 9 + p.cam_dist_begin[cam + 1] - jb;
+    const long S = p.n_ip;
+    if (tid < kc) scol[tid] = rl_col(p, img, cam, jb, tid);
+    __syncthreads();
+    for (int i = tid; i < kc * kc; i += RL_PTS) {
+        const int a = i / kc, b = i - a * kc;
+        const int qa = scol[a], qb = scol[b];
+        sQ[a * KC_MAX + b] = (qa < 0 || qb < 0) ? 0.0 : rl_q(Q, ld, qa, qb);
+    }
+    __syncthreads();
+    if (tid >= ch.y) return;
+    const int ip = ch.x + tid, pnt = p.ip_point[ip];
+    double *my0 = sA + tid, *my1 = sA + KC_MAX * RL_PTS + tid;   // column c of row 0 / 1 at [c * RL_PTS]
+    for (int c = 0; c < kc; c++) {
+        const bool f = scol[c] >= 0;
+        my0[c * RL_PTS] = f ? rowsA[(long)(2 * rl_local(c)) * S + ip] : 0.0;
+        my1[c * RL_PTS] = f ? rowsA[(long)(2 * rl_local(c) + 1) * S + ip] : 0.0;
+    }
+    int pc[3];
+    double ap[2][3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        pc[a] = p.point_col[3 * pnt + a];
+        ap[0][a] = pc[a] >= 0 ? rowsA[(long)(2 * a) * S + ip] : 0.0;
+        ap[1][a] = pc[a] >= 0 ? rowsA[(long)(2 * a + 1) * S + ip] : 0.0;
+    }
+    double h00 = 0.0, h01 = 0.0, h11 = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            if (pc[a] < 0 || pc[b] < 0) continue;
+            const double q = rl_q(Q, ld, pc[a], pc[b]);
+            h00 = fma(ap[0][a], q * ap[0][b], h00);
+            h01 = fma(ap[0][a], q * ap[1][b], h01);
+            h11 = fma(ap[1][a], q * ap[1][b], h11);
+        }
+    for (int c = 0; c < kc; c++) {
+        const int qc = scol[c];
+        if (qc < 0) continue;
+        double y0 = 0.0, y1 = 0.0, z0 = 0.0, z1 = 0.0;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            if (pc[a] < 0) continue;
+            const double q = rl_q(Q, ld, qc, pc[a]);
+            y0 = fma(q, ap[0][a], y0);
+            y1 = fma(q, ap[1][a], y1);
+        }
+        for (int b = 0; b < kc; b++) {
+            const double q = sQ[c * KC_MAX + b];
+            z0 = fma(q, my0[b * RL_PTS], z0);
+            z1 = fma(q, my1[b * RL_PTS], z1);
+        }
+        const double a0 = my0[c * RL_PTS], a1 = my1[c * RL_PTS];
+        h00 += a0 * (2.0 * y0 + z0);
+        h11 += a1 * (2.0 * y1 + z1);
+        h01 += y0 * a1 + a0 * (y1 + z1);
+    }
+    double p00, p01, p11;
+    {
+        const double vx = p.ip_var_x[ip], vy = p.ip_var_y[ip], rho = p.ip_rho[ip];
+        if (rho == 0) {
+            p00 = s0 / vx; p11 = s0 / vy; p01 = 0.0;
+        } else {
+            const double invDet = s0 / ((1.0 - rho * rho) * vx * vy);
+            p00 = invDet * vy; p11 = invDet * vx; p01 = -invDet * rho * sqrt(vx * vy);
+        }
+    }
+    // N = P H P (H has no entries outside the point's own two rows: P is 2 x 2)
+    const double g00 = h00 * p00 + h01 * p01, g01 = h00 * p01 + h01 * p11;
+    const double g10 = h01 * p00 + h11 * p01, g11 = h01 * p01 + h11 * p11;
+    const double nxx = p00 * g00 + p01 * g10, nxy = p00 * g01 + p01 * g11, nyy = p01 * g01 + p11 * g11;
+    const double v0 = v[2 * (long)ip], v1 = v[2 * (long)ip + 1];
+    const long n = p.n_ip, o = new2old ? new2old[ip] : ip;
+    const double2 nab = rl_point_columns(p00 * v0 + p01 * v1, p01 * v0 + p11 * v1, p00, p01, p11, nxx, nxy, nyy, s2t, pa, n, o, pt);
+    // shift = -Q[P(q), cols(q)] b,  b = A_q' c over the point's 3 + kc columns,  c = P nabla^
+    const double c0 = p00 * nab.x + p01 * nab.y, c1 = p01 * nab.x + p11 * nab.y;
+    double sh[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int b = 0; b < 3; b++) {
+        if (pc[b] < 0) continue;
+        const double bp = ap[0][b] * c0 + ap[1][b] * c1;
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+            if (pc[a] >= 0) sh[a] = fma(rl_q(Q, ld, pc[a], pc[b]), bp, sh[a]);
+    }
+    for (int c = 0; c < kc; c++) {
+        const int qc = scol[c];
+        if (qc < 0) continue;
+        const double bs = my0[c * RL_PTS] * c0 + my1[c * RL_PTS] * c1;
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+            if (pc[a] >= 0) sh[a] = fma(rl_q(Q, ld, pc[a], qc), bs, sh[a]);
+    }
+    const bool ok = !isnan(nab.x);
+#pragma unroll
+    for (int a = 0; a < 3; a++) pt[(11 + a) * n + o] = ok ? (pc[a] >= 0 ? -sh[a] : 0.0) : (double)NAN;
+}
+
+// Dense blocks, image point q of block bl[blockIdx.y]: grid (ceil(mpad / 2 / 256), batch).  nab: [batch][mpad / 2][2]
+__global__ __launch_bounds__(256) void rel_block_points_kernel(DevProblem p, const int32_t *__restrict__ bl, int mpad, const double *__restrict__ P,
+                                                               const double *__restrict__ G, const double *__restrict__ v,
+                                                               const int32_t *__restrict__ new2old, double s2t, RelPointArgs pa,
+                                                               double *__restrict__ nab, double *__restrict__ pt) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    const int g = bl[blockIdx.y];
+    const int ipb = p.blk_ip_begin[g], mp = p.blk_ip_begin[g + 1] - ipb, m = 2 * mp;
+    if (q >= mp) return;
+    const long off = (long)blockIdx.y * mpad * mpad;
+    const double *Pb = P + off + 2 * q, *Gb = G + off + 2 * q, *vb = v + 2 * (long)ipb;
+    double gx = 0.0, gy = 0.0, nxx = 0.0, nxy = 0.0, nyy = 0.0;
+    for (int j = 0; j < m; j++) {
+        const double pjx = Pb[(long)j * mpad], pjy = Pb[(long)j * mpad + 1];
+        const double gjx = Gb[(long)j * mpad], gjy = Gb[(long)j * mpad + 1];
+        nxx = fma(pjx, gjx, nxx);
+        nxy = fma(pjx, gjy, nxy);
+        nyy = fma(pjy, gjy, nyy);
+        gx = fma(pjx, vb[j], gx);
+        gy = fma(pjy, vb[j], gy);
+    }
+    const double pxx = Pb[(long)(2 * q) * mpad], pxy = Pb[(long)(2 * q) * mpad + 1], pyy = Pb[(long)(2 * q + 1) * mpad + 1];
+    const long o = new2old ? new2old[ipb + q] : ipb + q;
+    const double2 nb = rl_point_columns(gx, gy, pxx, pxy, pyy, nxx, nxy, nyy, s2t, pa, p.n_ip, o, pt);
+    double *dst = nab + (long)blockIdx.y * mpad + 2 * q;
+    dst[0] = nb.x;
+    dst[1] = nb.y;
+}
+
+// Dense blocks: part[bi][q][chunk][3] = sum over the points k of the chunk of Q[P(q), P(k)] (a_p(2k) c_q[2k] + a_p(2k+1) c_q[2k+1]),
+// c_q = P[:, S_q] nabla^_q.  One workgroup per chunk pair b <= a (rel_pp_kernel's grid and staging): thread (qi, ki) forms the term of
+// point qi of chunk a and point ki of chunk b and, where a != b, of point qi of chunk b and point ki of chunk a; the 16 terms of a
+// point are then added in the order of ki.  Every (point, chunk) of a block is written exactly once.  part: [batch][mpad / 2][mpad / 32][3]
+__global__ __launch_bounds__(256) void rel_shift_pp_kernel(DevProblem p, const int32_t *__restrict__ bl, int mpad, const double *__restrict__ Q, long ld,
+                                                           const double *__restrict__ rowsA, const double *__restrict__ P,
+                                                           const double *__restrict__ nab, double *__restrict__ part) {
+    __shared__ double sQ[RL_PC * (RL_PC + 1)];
+    __shared__ double sAa[RL_RC * 3], sAb[RL_RC * 3];
+    __shared__ double sT[2][RL_TP * RL_TP * 3];
+    __shared__ int colA[RL_PC], colB[RL_PC];
+    const int tid = threadIdx.x;
+    const int g = bl[blockIdx.y];
+    const int ipb = p.blk_ip_begin[g], mp = p.blk_ip_begin[g + 1] - ipb;
+    const long nch = (mp + RL_TP - 1) / RL_TP, tiles = nch * (nch + 1) / 2, t = blockIdx.x;
+    if (t >= tiles) return;
+    long a = (long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while (a * (a + 1) / 2 > t) a--;
+    while ((a + 1) * (a + 2) / 2 <= t) a++;
+    const long b = t - a * (a + 1) / 2;
+    const int pa0 = (int)a * RL_TP, pb0 = (int)b * RL_TP;
+    const int na = min(RL_TP, mp - pa0), nb = min(RL_TP, mp - pb0);
+    const long S = p.n_ip;
+    if (tid < RL_PC) {
+        const int k = tid / 3, c = tid - 3 * k;
+        colA[tid] = k < na ? p.point_col[3 * p.ip_point[ipb + pa0 + k] + c] : -1;
+        colB[tid] = k < nb ? p.point_col[3 * p.ip_point[ipb + pb0 + k] + c] : -1;
+    }
+    __syncthreads();
+    if (tid < 2 * RL_RC) {   // a_p of the 32 rows of chunk a (threads 0-31) and of chunk b (32-63)
+        const int side = tid / RL_RC, k = tid - side * RL_RC, q = k >> 1, r = k & 1;
+        const int n = side ? nb : na, p0 = side ? pb0 : pa0;
+        const int *cl = side ? colB : colA;
+        double *dst = (side ? sAb : sAa) + 3 * k;
+        for (int c = 0; c < 3; c++) dst[c] = (q < n && cl[3 * q + c] >= 0) ? rowsA[(long)(2 * c + r) * S + ipb + p0 + q] : 0.0;
+    }
+    for (int i = tid; i < RL_PC * RL_PC; i += 256) {
+        const int r = i / RL_PC, c = i - r * RL_PC;
+        const int qr = colA[r], qc = colB[c];
+        sQ[r * (RL_PC + 1) + c] = (qr < 0 || qc < 0) ? 0.0 : rl_q(Q, ld, qr, qc);
+    }
+    __syncthreads();
+    const double *Pb = P + (long)blockIdx.y * mpad * mpad, *nb_ = nab + (long)blockIdx.y * mpad;
+    const int qi = tid / RL_TP, ki = tid - qi * RL_TP;
+    const int dirs = a != b ? 2 : 1;
+    for (int d = 0; d < dirs; d++) {
+        const int nq = d ? nb : na, nk = d ? na : nb, q0 = d ? pb0 : pa0, k0 = d ? pa0 : pb0;
+        double o[3] = {0.0, 0.0, 0.0};
+        if (qi < nq && ki < nk) {
+            const int cq = 2 * (q0 + qi), rk = 2 * (k0 + ki);
+            const double nx = nb_[cq], ny = nb_[cq + 1];
+            const double c0 = fma(Pb[(long)rk * mpad + cq], nx, Pb[(long)rk * mpad + cq + 1] * ny);
+            const double c1 = fma(Pb[(long)(rk + 1) * mpad + cq], nx, Pb[(long)(rk + 1) * mpad + cq + 1] * ny);
+            const double *ak = (d ? sAa : sAb) + 6 * ki;
+            double w[3];
+#pragma unroll
+            for (int x = 0; x < 3; x++) w[x] = fma(ak[x], c0, ak[3 + x] * c1);
+#pragma unroll
+            for (int u = 0; u < 3; u++) {
+                const double *qr = d ? sQ + (3 * ki) * (RL_PC + 1) + 3 * qi + u : sQ + (3 * qi + u) * (RL_PC + 1) + 3 * ki;
+                const int st = d ? RL_PC + 1 : 1;
+                o[u] = fma(qr[0], w[0], fma(qr[st], w[1], qr[2 * st] * w[2]));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 3; u++) sT[d][(qi * RL_TP + ki) * 3 + u] = o[u];
+    }
+    __syncthreads();
+    if (tid < dirs * RL_PC) {
+        const int d = tid / RL_PC, x = tid - d * RL_PC, q = x / 3, u = x - 3 * q;
+        const int nq = d ? nb : na, q0 = d ? pb0 : pa0;
+        if (q < nq) {
+            double s = 0.0;
+            for (int k = 0; k < RL_TP; k++) s += sT[d][(q * RL_TP + k) * 3 + u];
+            const long chunk = d ? a : b;
+            part[(((long)blockIdx.y * (mpad / 2) + q0 + q) * (mpad / RL_RC) + chunk) * 3 + u] = s;
+        }
+    }
+}
+
+// Dense blocks, image point q of block bl[blockIdx.y]: grid (ceil(mpad / 2 / RL_PTS), batch).  R: rel_prep_kernel's [a_s | u] rows (a_s is
+// zero in its fixed columns and beyond kc).  shift = -(sum of the chunk partials in chunk order + Q[P(q), S] (A_s' c_q)).
+__global__ __launch_bounds__(RL_PTS) void rel_shift_kernel(DevProblem p, const int32_t *__restrict__ bl, int mpad, const double *__restrict__ Q, long ld,
+                                                           const double *__restrict__ P, const double *__restrict__ R,
+                                                           const double *__restrict__ nab, const double *__restrict__ part,
+                                                           const int32_t *__restrict__ new2old, double *__restrict__ pt) {
+    const int q = blockIdx.x * RL_PTS + threadIdx.x;
+    const int g = bl[blockIdx.y];
+    const int ipb = p.blk_ip_begin[g], mp = p.blk_ip_begin[g + 1] - ipb, m = 2 * mp;
+    if (q >= mp) return;
+    const int img = p.ip_image[ipb], cam = p.image_camera[img], jb = p.cam_dist_begin[cam];
+    const int kc = 9 + p.cam_dist_begin[cam + 1] - jb;
+    const double *Pb = P + (long)blockIdx.y * mpad * mpad + 2 * q, *Rb = R + (long)blockIdx.y * mpad * RL_K;
+    const double nx = nab[(long)blockIdx.y * mpad + 2 * q], ny = nab[(long)blockIdx.y * mpad + 2 * q + 1];
+    double acc[KC_MAX];
+#pragma unroll
+    for (int c = 0; c < KC_MAX; c++) acc[c] = 0.0;
+    for (int j = 0; j < m; j++) {
+        const double cj = fma(Pb[(long)j * mpad], nx, Pb[(long)j * mpad + 1] * ny);
+        const double *as = Rb + (long)j * RL_K;
+#pragma unroll
+        for (int c = 0; c < KC_MAX; c++) acc[c] = fma(as[c], cj, acc[c]);
+    }
+    const int pnt = p.ip_point[ipb + q];
+    int pc[3];
+    double sh[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int a = 0; a < 3; a++) pc[a] = p.point_col[3 * pnt + a];
+    const long nch = (mp + RL_TP - 1) / RL_TP;
+    const double *pq = part + ((long)blockIdx.y * (mpad / 2) + q) * (mpad / RL_RC) * 3;
+    for (long c = 0; c < nch; c++)
+#pragma unroll
+        for (int a = 0; a < 3; a++) sh[a] += pq[3 * c + a];
+#pragma unroll
+    for (int c = 0; c < KC_MAX; c++) {
+        const int qc = c < kc ? rl_col(p, img, cam, jb, c) : -1;
+        if (qc < 0) continue;
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+            if (pc[a] >= 0) sh[a] = fma(rl_q(Q, ld, pc[a], qc), acc[c], sh[a]);
+    }
+    const long n = p.n_ip, o = new2old ? new2old[ipb + q] : ipb + q;
+    const bool ok = !isnan(nx);
+#pragma unroll
+    for (int a = 0; a < 3; a++) pt[(11 + a) * n + o] = ok ? (pc[a] >= 0 ? -sh[a] : 0.0) : (double)NAN;
+}
+
 // scale bars (PDF:210-283): one thread each; row = row0 + s
 __global__ __launch_bounds__(64) void rel_scalebar_kernel(DevProblem p, const double *__restrict__ vals, const double *__restrict__ Q, long ld,
                                                           const double *__restrict__ dx, double s0, double s2t, long row0, long n_rows,
@@ -438,7 +758,9 @@ constexpr size_t RL_BATCH_BYTES = (size_t)1 << 30;   // work buffers of the dens
 }  // namespace
 
 
-static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx) {
+// pa != nullptr: the table of the image points as well (jaicov_rel_run_points); everything it adds is launched after the plain run's
+// kernels of the same group, which stay what they are
+static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx, const RelPointArgs *pa) {
     const DevProblem &p = *v.p;
     const double s0 = v.sigma2;
     const long n_ip = p.n_ip, n_rows = s->n_rows;
@@ -447,6 +769,11 @@ static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx) {
     s->summary[5] = v.lambda;
     HIPE(*v.err, s->out.reserve(std::max<size_t>(4 * (size_t)n_rows, 1)));   // the result belongs to the state
     double *const d_res = s->out.get();
+    if (pa) {
+        HIPE(*v.err, s->points.reserve(std::max<size_t>(JAICOV_REL_POINT_COLUMNS * (size_t)n_ip, 1)));
+        s->n_points = n_ip;
+    }
+    double *const d_pt = s->points.get();
     if (n_rows == 0) return JAICOV_OK;
     double *d_dx = nullptr, *d_v = nullptr, *d_sum = nullptr;
     HIPE(*v.err, w.alloc(&d_dx, (size_t)v.U));
@@ -496,12 +823,18 @@ static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx) {
             hipLaunchKernelGGL(rel_points_kernel, dim3((unsigned)chunks.size()), dim3(RL_PTS), 0, st, p, d_chunks, v.Q, v.ld, v.rowsA, d_v,
                                v.ll_diag, d_new2old, s0, s2t, n_rows, d_res);
             HIPE(*v.err, hipGetLastError());
+            if (pa) {
+                hipLaunchKernelGGL(rel_points_loo_kernel, dim3((unsigned)chunks.size()), dim3(RL_PTS), 0, st, p, d_chunks, v.Q, v.ld, v.rowsA,
+                                   d_v, d_new2old, s0, s2t, *pa, d_pt);
+                HIPE(*v.err, hipGetLastError());
+            }
         }
         if (!dense_blocks.empty()) {
             const int nd = (int)dense_blocks.size();
             const int mpad = (max_m + 127) / 128 * 128;
             const size_t sq = (size_t)mpad * mpad;
-            const size_t per = (3 * sq + 2 * (size_t)mpad * RL_K) * sizeof(double);
+            const size_t n_nab = (size_t)mpad, n_part = (size_t)(mpad / 2) * (mpad / RL_RC) * 3;   // per block, table run only
+            const size_t per = (3 * sq + 2 * (size_t)mpad * RL_K + (pa ? n_nab + n_part : 0)) * sizeof(double);
             size_t cap = RL_BATCH_BYTES / per;
             if (const char *hook = getenv("JAICOV_REL_BATCH")) cap = std::min<size_t>(cap, (size_t)std::max(1, atoi(hook)));   // test hook
             const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)nd, cap));
@@ -513,6 +846,11 @@ static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx) {
             HIPE(*v.err, w.alloc(&d_G, nb * sq));
             HIPE(*v.err, w.alloc(&d_L, (size_t)nb * mpad * RL_K));
             HIPE(*v.err, w.alloc(&d_R, (size_t)nb * mpad * RL_K));
+            double *d_nab = nullptr, *d_part = nullptr;
+            if (pa) {
+                HIPE(*v.err, w.alloc(&d_nab, nb * n_nab));
+                HIPE(*v.err, w.alloc(&d_part, nb * n_part));
+            }
             HIPE(*v.err, hipMemcpyAsync(d_bl, dense_blocks.data(), (size_t)nd * sizeof(int32_t), hipMemcpyHostToDevice, st));
             for (int b0 = 0; b0 < nd; b0 += nb) {
                 const int n = std::min(nb, nd - b0);
@@ -540,6 +878,16 @@ static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx) {
                 hipLaunchKernelGGL(rel_block_kernel, dim3(mpad / 256 + (mpad % 256 ? 1 : 0), n), dim3(256), 0, st, p, bl, mpad, d_H, d_P, d_G,
                                    d_v, v.ll_diag, d_new2old, s0, s2t, n_rows, d_res);
                 HIPE(*v.err, hipGetLastError());
+                if (pa) {
+                    const int mp_pad = mpad / 2;
+                    hipLaunchKernelGGL(rel_block_points_kernel, dim3((mp_pad + 255) / 256, n), dim3(256), 0, st, p, bl, mpad, d_P, d_G, d_v,
+                                       d_new2old, s2t, *pa, d_nab, d_pt);
+                    hipLaunchKernelGGL(rel_shift_pp_kernel, dim3((unsigned)tmax, n), dim3(256), 0, st, p, bl, mpad, v.Q, v.ld, v.rowsA, d_P,
+                                       d_nab, d_part);
+                    hipLaunchKernelGGL(rel_shift_kernel, dim3((mp_pad + RL_PTS - 1) / RL_PTS, n), dim3(RL_PTS), 0, st, p, bl, mpad, v.Q, v.ld,
+                                       d_P, d_R, d_nab, d_part, d_new2old, d_pt);
+                    HIPE(*v.err, hipGetLastError());
+                }
             }
         }
     }
@@ -560,12 +908,15 @@ static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx) {
     return JAICOV_OK;
 }
 
-extern "C" int jaicov_rel_run(jaicov_engine *e, double sigma2_test, const double *dx, int32_t *n_rows) {
+// jaicov_rel_run (pa == nullptr) and jaicov_rel_run_points
+static int rel_run_checked(jaicov_engine *e, double sigma2_test, const double *dx, const RelPointArgs *pa, int32_t *n_rows,
+                           int32_t *n_image_points) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     RelView v;
     engine_rel_view(e, &v, 0);
     if (v.sharded) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "reliability needs an engine that holds every observation (not a shard)");
     if (!(sigma2_test > 0) || !std::isfinite(sigma2_test)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "sigma2_test must be positive and finite");
+    if (pa && (!(pa->lambda0 > 0) || !std::isfinite(pa->lambda0))) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "lambda0 must be positive and finite");
     if (!v.full_q)
         FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no full cofactor matrix: solve with JAICOV_INVERT_FULL or JAICOV_INVERT_FULL_EXPANDED first");
     const DevProblem &p0 = *v.p;
@@ -578,14 +929,25 @@ extern "C" int jaicov_rel_run(jaicov_engine *e, double sigma2_test, const double
     v.state->reset();
     std::unique_ptr<RelState> s(new RelState());
     s->n_rows = rows;
-    rc = rel_run_impl(v, s.get(), sigma2_test, dx);
+    rc = rel_run_impl(v, s.get(), sigma2_test, dx, pa);
     if (rc != JAICOV_OK) {
         hipStreamSynchronize(v.stream);
         return rc;
     }
     *v.state = std::move(s);
     if (n_rows) *n_rows = (int32_t)rows;
+    if (n_image_points) *n_image_points = (int32_t)p0.n_ip;
     return JAICOV_OK;
+}
+
+extern "C" int jaicov_rel_run(jaicov_engine *e, double sigma2_test, const double *dx, int32_t *n_rows) {
+    return rel_run_checked(e, sigma2_test, dx, nullptr, n_rows, nullptr);
+}
+
+extern "C" int jaicov_rel_run_points(jaicov_engine *e, double sigma2_test, const double *dx, double lambda0, double omega, int32_t dof,
+                                     int32_t *n_rows, int32_t *n_image_points) {
+    const RelPointArgs pa{lambda0, omega, (int)dof};
+    return rel_run_checked(e, sigma2_test, dx, &pa, n_rows, n_image_points);
 }
 
 static RelState *rl_result(jaicov_engine *e, RelView &v) {
@@ -605,6 +967,21 @@ extern "C" int jaicov_rel_get(jaicov_engine *e, double *vres, double *qvv, doubl
     double *dst[4] = {vres, qvv, r, t};
     for (int k = 0; k < 4; k++)
         if (dst[k]) HIPE(*v.err, hipMemcpyAsync(dst[k], s->out.get() + k * (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    HIPE(*v.err, hipStreamSynchronize(v.stream));
+    return JAICOV_OK;
+}
+
+extern "C" int jaicov_rel_get_points(jaicov_engine *e, double *out, int32_t n) {
+    if (!e) return JAICOV_ERR_BAD_ARGUMENT;
+    RelView v;
+    RelState *s = rl_result(e, v);
+    if (!s) return JAICOV_ERR_BAD_STATE;
+    if (s->n_points < 0) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no table of the image points: the last run was a plain jaicov_rel_run");
+    if (n != s->n_points || (n > 0 && !out))
+        FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "n must equal the number of image points of the last run, and out must not be NULL");
+    if (n == 0) return JAICOV_OK;
+    HIPE(*v.err, hipSetDevice(v.device));
+    HIPE(*v.err, hipMemcpyAsync(out, s->points.get(), JAICOV_REL_POINT_COLUMNS * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, v.stream));
     HIPE(*v.err, hipStreamSynchronize(v.stream));
     return JAICOV_OK;
 }

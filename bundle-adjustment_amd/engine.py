@@ -1,5 +1,6 @@
 """ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` / ``include/jaicov_transform.h`` /
-``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_datum.h`` / ``include/jaicov_intersect.h``
+``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_reliability_points.h`` /
+``include/jaicov_datum.h`` / ``include/jaicov_intersect.h``
 (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
@@ -45,6 +46,8 @@ XFORM_EXPORTS = [
 DLT_EXPORTS = ["jaicov_dlt_adjust"]
 # include/jaicov_reliability.h: residuals, redundancy numbers and test values of every observation on the device
 REL_EXPORTS = ["jaicov_rel_run", "jaicov_rel_get", "jaicov_rel_summary", "jaicov_rel_release"]
+# include/jaicov_reliability_points.h: the leave-one-out table of every image point beside them
+REL_POINT_EXPORTS = ["jaicov_rel_run_points", "jaicov_rel_get_points"]
 # include/jaicov_datum.h: the cofactor matrix re-expressed in another datum (S-transformation) on the device
 DATUM_EXPORTS = ["jaicov_datum_transform", "jaicov_datum_apply"]
 # jaicov_dlt_restriction (DirectLinearTransformation.RestrictionType, DT:51-58 order) and the per-image status values
@@ -157,6 +160,8 @@ def load_library():
     L.jaicov_rel_get.argtypes = [vp, _pd, _pd, _pd, _pd, C.c_int32]
     L.jaicov_rel_summary.argtypes = [vp, _pd, C.c_int32]
     L.jaicov_rel_release.argtypes = [vp]
+    L.jaicov_rel_run_points.argtypes = [vp, C.c_double, _pd, C.c_double, C.c_double, C.c_int32, _pi, _pi]
+    L.jaicov_rel_get_points.argtypes = [vp, _pd, C.c_int32]
     L.jaicov_datum_transform.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int32]
     L.jaicov_datum_apply.argtypes = [vp, _pd, _pd, C.c_int32]
     L.jaicov_dlt_adjust.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pi, C.c_int32, C.c_int32, _pd, _pi, _pi, _pd]
@@ -168,6 +173,10 @@ def load_library():
 
 # Engine.reliability: one entry per observation row (include/jaicov_reliability.h)
 Reliability = namedtuple("Reliability", ["v", "qvv", "r", "t"])
+# Engine.reliability_points: one entry per image point, the columns of include/jaicov_reliability_points.h in their order
+REL_POINT_COLUMNS = 14
+PointReliability = namedtuple("PointReliability", ["q", "T_prio", "T_post", "nabla_x", "nabla_y", "Mxx", "Mxy", "Myy", "mdb_major",
+                                                   "mdb_minor", "delta_ext", "dX", "dY", "dZ"])
 
 
 def _p(a):
@@ -237,6 +246,7 @@ class Engine:
 
     # loop body ----------------------------------------------------------------------------------------------
     def build(self, sigma2, lam=0.0, simulation=False):
+        self._sigma2_build = float(sigma2)      # reliability_points forms its default Omega with the weights of this build
         self._chk(self.L.jaicov_neq_build(self._h, sigma2, lam, int(simulation)))
 
     def accumulate(self, sigma2, lam=0.0):
@@ -255,6 +265,7 @@ class Engine:
         return int(self.L.jaicov_neq_cofactor_order(self._h))
 
     def finalize(self, sigma2, lam=0.0, simulation=False):
+        self._sigma2_build = float(sigma2)
         self._chk(self.L.jaicov_neq_finalize(self._h, sigma2, lam, int(simulation)))
 
     def reduce_buffer(self):
@@ -380,6 +391,27 @@ class Engine:
         self._chk(self.L.jaicov_rel_get(self._h, *[_p(a) for a in out], n.value))
         return Reliability(*out)
 
+    def reliability_points(self, sigma2_test, dx=None, lambda0=17.075, omega=None, dof=None):
+        """reliability() and, for every image point, what taking it out would do (include/jaicov_reliability_points.h): the drop q of
+        Omega, the joint tests T_prio and T_post, the estimated gross error, M = (P Q_vv P)_SS, the minimal detectable bias, the
+        external reliability and the shift of the point's own object coordinates.  omega None = Omega of dx (or of a zero step) with
+        the variance factor of the last build (the problem's a-priori one after estimate()); dof None = n - u + d.  Returns (Reliability, PointReliability)."""
+        d = None if dx is None else np.ascontiguousarray(dx, np.float64)
+        if d is not None and d.size != self.fp.n_unknowns:
+            raise ValueError("dx must have U entries")
+        if omega is None:
+            omega = self.omega(getattr(self, "_sigma2_build", self.fp.sigma2apriori), np.zeros(max(self.U, 1)) if d is None else d)
+        if dof is None:
+            dof = self.fp.degree_of_freedom      # n - u + d; the columns of a datum border are not parameters
+        n = C.c_int32(0); k = C.c_int32(0)
+        self._chk(self.L.jaicov_rel_run_points(self._h, float(sigma2_test), None if d is None else _p(d), float(lambda0), float(omega),
+                                               int(dof), C.byref(n), C.byref(k)))
+        out = [np.zeros(n.value) for _ in range(4)]
+        self._chk(self.L.jaicov_rel_get(self._h, *[_p(a) for a in out], n.value))
+        tab = np.zeros((REL_POINT_COLUMNS, k.value))
+        self._chk(self.L.jaicov_rel_get_points(self._h, _p(tab), k.value))
+        return Reliability(*out), PointReliability(*tab)
+
     def reliability_summary(self):
         """(sum r, max |t|, its row, rows with NaN t, min r, damping of the inverted build) of the last reliability run."""
         out = np.zeros(6)
@@ -449,6 +481,7 @@ class Engine:
         o.struct_size = C.sizeof(EstimateOptions)
         o.max_iterations = max_iter; o.invert = int(invert); o.simulation = int(simulation)
         o.lambda0 = lam0; o.sigma2apriori = self.fp.sigma2apriori if sigma2 is None else sigma2
+        self._sigma2_build = float(o.sigma2apriori)
         res = EstimateResult()
         self._chk(self.L.jaicov_neq_estimate(self._h, C.byref(o), C.byref(res)))
         return self.get_parameters(), res

@@ -145,6 +145,14 @@ PYBIND11_MODULE(_jaicov_host, m) {
             auto arr = [](const std::vector<double> &x) { return py::array_t<double>((py::ssize_t)x.size(), x.data()); };
             return py::make_tuple(arr(o.v), arr(o.qvv), arr(o.r), arr(o.t));
         }, py::arg("sigma2Test"), "(v, qvv, r, t) of every observation row (include/jaicov_reliability.h)")
+        .def("imagePointReliability", [](BundleAdjustment &b, double sigma2Test, double lambda0) {
+            auto o = b.imagePointReliability(sigma2Test, lambda0);
+            auto arr = [](const std::vector<double> &x) { return py::array_t<double>((py::ssize_t)x.size(), x.data()); };
+            return py::make_tuple(arr(o.q), arr(o.Tprio), arr(o.Tpost), arr(o.nablaX), arr(o.nablaY), arr(o.Mxx), arr(o.Mxy), arr(o.Myy),
+                                  arr(o.mdbMajor), arr(o.mdbMinor), arr(o.deltaExt), arr(o.dX), arr(o.dY), arr(o.dZ));
+        }, py::arg("sigma2Test"), py::arg("lambda0") = 17.075,
+             "(q, T_prio, T_post, nabla_x, nabla_y, Mxx, Mxy, Myy, mdb_major, mdb_minor, delta_ext, dX, dY, dZ) of every image point "
+             "(include/jaicov_reliability_points.h)")
         .def("transformDatum", &BundleAdjustment::transformDatum,
              "re-express the cofactor matrix in the datum of the points flagged now (include/jaicov_datum.h)")
         .def("useCentroidedCoordinates", &BundleAdjustment::useCentroidedCoordinates)

@@ -479,6 +479,22 @@ BundleAdjustment::ObservationReliability BundleAdjustment::observationReliabilit
     return o;
 }
 
+BundleAdjustment::ImagePointReliability BundleAdjustment::imagePointReliability(double sigma2Test, double lambda0) const {
+    if (!engine_ || inversion_ != MatrixInversion::FULL)
+        throw std::runtime_error("no full cofactor matrix: run estimateModel with MatrixInversion.FULL first");
+    int32_t rows = 0, n = 0;
+    int rc = jaicov_rel_run_points(engine_, sigma2Test, nullptr, lambda0, omega_, (int32_t)getDegreeOfFreedom(), &rows, &n);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_rel_run_points: ") + jaicov_neq_last_error(engine_));
+    std::vector<double> tab((size_t)JAICOV_REL_POINT_COLUMNS * (size_t)n);
+    rc = jaicov_rel_get_points(engine_, tab.data(), n);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_rel_get_points: ") + jaicov_neq_last_error(engine_));
+    ImagePointReliability o;
+    std::vector<double> *cols[JAICOV_REL_POINT_COLUMNS] = {&o.q, &o.Tprio, &o.Tpost, &o.nablaX, &o.nablaY, &o.Mxx, &o.Mxy, &o.Myy,
+                                                           &o.mdbMajor, &o.mdbMinor, &o.deltaExt, &o.dX, &o.dY, &o.dZ};
+    for (int c = 0; c < JAICOV_REL_POINT_COLUMNS; c++) cols[c]->assign(tab.begin() + (size_t)c * n, tab.begin() + (size_t)(c + 1) * n);
+    return o;
+}
+
 void BundleAdjustment::transformDatum() {
     if (!engine_ || inversion_ == MatrixInversion::NONE || !hasCofactorMatrix())
         throw std::runtime_error("no cofactor matrix: run estimateModel with MatrixInversion FULL or REDUCED first");

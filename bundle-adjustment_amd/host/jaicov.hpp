@@ -30,6 +30,7 @@
 #include "../../include/jaicov_dlt.h"
 #include "../../include/jaicov_intersect.h"
 #include "../../include/jaicov_reliability.h"
+#include "../../include/jaicov_reliability_points.h"
 #include "../../include/jaicov_datum.h"
 
 namespace jaicov::host {
@@ -515,6 +516,14 @@ public:
         std::vector<double> v, qvv, r, t;
     };
     ObservationReliability observationReliability(double sigma2Test) const;
+    // What taking an image point out would do, for every image point in the order of the images' image coordinates (the order of
+    // the rows above, one entry per pair): the columns of include/jaicov_reliability_points.h, from jaicov_rel_run_points with a zero
+    // step, the Omega and the degrees of freedom of the finished estimateModel.  lambda0: the non-centrality behind the minimal
+    // detectable bias and the external reliability (17.075 is Baarda's value for alpha 0.1 % and power 80 %).  Needs MatrixInversion.FULL.
+    struct ImagePointReliability {
+        std::vector<double> q, Tprio, Tpost, nablaX, nablaY, Mxx, Mxy, Myy, mdbMajor, mdbMinor, deltaExt, dX, dY, dZ;
+    };
+    ImagePointReliability imagePointReliability(double sigma2Test, double lambda0 = 17.075) const;
     // The cofactor matrix of the last estimateModel re-expressed, on the device, in the datum of the points whose isDatum() flag is
     // set NOW (Baarda's S-transformation, include/jaicov_datum.h): re-flag the points, then call.  Needs a free network (d > 0)
     // and MatrixInversion FULL or REDUCED; cofactorSub, getCofactorMatrix and the writers see the new datum afterwards.

@@ -31,6 +31,9 @@
  *   others: its t_i is NaN (the report prints "---").
  *   A directly observed FIXED parameter has a zero row of A: r = 1.
  *
+ * Image points as a whole.  The joint test of both coordinates of an image point, its estimated gross error and what deleting it would
+ * do to Omega and to its object point are in jaicov_reliability_points.h; that run fills the four vectors of this header as well.
+ *
  * Determinism.  Every output entry is one fixed-order sum: two runs give the same bits.
  *
  * The environment is not an interface: JAICOV_REL_BATCH (a test hook, tests/test_gpu_reliability.py) caps the images per batch of the
