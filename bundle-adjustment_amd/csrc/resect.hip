@@ -1,0 +1,719 @@
+// resect.hip -- spatial resection of many images in one launch (include/jaicov_resect.h): start values of the exterior orientation
+// from known object points and a known interior orientation.  The call has no counterpart in the reference; its collinearity
+// equations, derivatives and weights are those of derivation/PartialDerivativeFactory.java (PDF), its preconditioning that of
+// NormalEquationSystem.java (NES).
+//
+// One wave (one workgroup of 64 lanes) works one image; the reduction, the two linear starts, the Gauss-Newton loop, the evaluation
+// pass and the rejection rounds all run inside it, with no host round trip.  As for the DLT and the intersection
+// the work per image is a chain of small dependent steps: latency bounds it, and many resident single-wave workgroups hide it.
+//   Sums.  Lane l takes observations l, l + 64, ... and keeps the partial sums of the pass; the lanes are combined by an xor butterfly,
+//   whose order is fixed and which leaves the same bits in every lane.  What follows is therefore wave-uniform: the sums and the
+//   image's state (reduction, unknowns, rotation, the plane's axes) lie in LDS, where every lane stores the same words; every lane
+//   runs the small algebra on them (Cholesky of order 11 and 8 in place in LDS, of order 6 in registers, the polar factor, the Jacobi
+//   sweeps), and every branch on its outcome is taken by the whole wave.  Observations are staged RESECT_CHUNK at a time in LDS; an
+//   image with at most RESECT_CHUNK keeps them resident.
+//   One pass routine serves every kind of sum (centroid, scatter, space start, plane start, step, evaluation), so that it is compiled
+//   once; its RESECT_NACC accumulators are the large per-lane state, and every index into them is a compile-time constant.
+// Floating-point contraction is off in this file: every product and sum is rounded on its own, as tests/resection_reference.py rounds it.
+#include <hip/hip_runtime.h>
+
+#include <float.h>
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../../include/jaicov_resect.h"
+#include "devbuf.h"
+#include "resect.h"
+
+#pragma clang fp contract(off)
+
+namespace jaicov {
+namespace {
+
+enum { RS_CENTROID = 0, RS_SCATTER, RS_SPACE, RS_EVAL_SPACE, RS_PLANE, RS_EVAL_PLANE, RS_STEP, RS_EVAL };
+
+// A value that is the same in every lane, said so to the compiler: the sums come out of the butterfly equal in all lanes, but the
+// compiler cannot know it, and would mask every branch on them lane by lane and keep both sides' values alive across it.
+__device__ inline int rs_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ inline bool rs_uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
+
+// index of (i, j >= i) in an upper triangle of order N packed row by row
+template <int N>
+__device__ constexpr int rs_ix(int i, int j) { return i * N - i * (i - 1) / 2 + (j - i); }
+
+// A (packed upper, order N) x = b by Jacobi preconditioning (NES:82-91) and Cholesky; Q (may be NULL, packed upper): the inverse of A.
+// A is overwritten by the factor, so that no second triangle is live beside the pass's sums.
+template <int N>
+__device__ inline int rs_solve(double *U, const double *b, double *x, double *Q) {
+    const double EPS = ldexp(1.0, -53), SQRT_EPS = sqrt(EPS);
+    constexpr int LEN = N * (N + 1) / 2;
+    double z = 0.0;                       // NaN unless every value is finite
+#pragma unroll
+    for (int k = 0; k < LEN; k++) z += U[k] * 0.0;
+#pragma unroll
+    for (int k = 0; k < N; k++) z += b[k] * 0.0;
+    if (rs_uniform(z != 0.0)) return JAICOV_RESECT_NOT_FINITE;
+    double V[N];                          // U'U = V A V, U upper
+#pragma unroll
+    for (int i = 0; i < N; i++) V[i] = U[rs_ix<N>(i, i)] > EPS ? 1.0 / sqrt(U[rs_ix<N>(i, i)]) : 1.0;
+#pragma unroll
+    for (int i = 0; i < N; i++)
+#pragma unroll
+        for (int j = i; j < N; j++) U[rs_ix<N>(i, j)] = U[rs_ix<N>(i, j)] * (V[i] * V[j]);
+    bool singular = false;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < j; k++) s += U[rs_ix<N>(k, j)] * U[rs_ix<N>(k, j)];
+        const double p = U[rs_ix<N>(j, j)] - s;
+        singular = singular || !(p > SQRT_EPS);
+        const double d = sqrt(p);
+        U[rs_ix<N>(j, j)] = d;
+#pragma unroll
+        for (int i = j + 1; i < N; i++) {
+            double r = 0.0;
+#pragma unroll
+            for (int k = 0; k < j; k++) r += U[rs_ix<N>(k, i)] * U[rs_ix<N>(k, j)];
+            U[rs_ix<N>(j, i)] = (U[rs_ix<N>(j, i)] - r) / d;
+        }
+    }
+    if (rs_uniform(singular)) return JAICOV_RESECT_SINGULAR;      // every pivot after the first bad one is garbage and is not used
+    if (x) {
+        double y[N];
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            double r = 0.0;
+#pragma unroll
+            for (int k = 0; k < i; k++) r += U[rs_ix<N>(k, i)] * y[k];
+            y[i] = (V[i] * b[i] - r) / U[rs_ix<N>(i, i)];
+        }
+#pragma unroll
+        for (int i = N - 1; i >= 0; i--) {
+            double r = 0.0;
+#pragma unroll
+            for (int k = i + 1; k < N; k++) r += U[rs_ix<N>(i, k)] * y[k];
+            y[i] = (y[i] - r) / U[rs_ix<N>(i, i)];
+        }
+#pragma unroll
+        for (int i = 0; i < N; i++) x[i] = V[i] * y[i];
+    }
+    if (Q) {
+        double W[LEN];                    // W = inverse of U, upper: W[i][j], j >= i
+#pragma unroll
+        for (int j = 0; j < N; j++) {
+            W[rs_ix<N>(j, j)] = 1.0 / U[rs_ix<N>(j, j)];
+#pragma unroll
+            for (int i = j - 1; i >= 0; i--) {
+                double r = 0.0;
+#pragma unroll
+                for (int k = i + 1; k <= j; k++) r += U[rs_ix<N>(i, k)] * W[rs_ix<N>(k, j)];
+                W[rs_ix<N>(i, j)] = -r / U[rs_ix<N>(i, i)];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < N; i++)
+#pragma unroll
+            for (int j = i; j < N; j++) {                 // inverse of V A V = W W'
+                double r = 0.0;
+#pragma unroll
+                for (int k = j; k < N; k++) r += W[rs_ix<N>(i, k)] * W[rs_ix<N>(j, k)];
+                Q[rs_ix<N>(i, j)] = r * (V[i] * V[j]);
+            }
+    }
+    return JAICOV_RESECT_OK;
+}
+
+// The same solve for the linear starts (order 11 or 8), on a system held in LDS: U (packed upper, overwritten by the factor), b
+// (overwritten by x), V.  Every lane runs it on the same words and stores what every other lane stores, so it needs no barrier and
+// its loops stay rolled: the triangle of order 11 unrolled into registers beside the pass's sums does not fit the register file.
+__device__ inline int rs_solve_lds(int n, double *U, double *b, double *V) {
+    const double EPS = ldexp(1.0, -53), SQRT_EPS = sqrt(EPS);
+    auto ix = [n](int i, int j) { return i * n - i * (i - 1) / 2 + (j - i); };
+    bool finite = true;
+    for (int k = 0; k < n * (n + 1) / 2; k++) finite = finite && isfinite(U[k]);
+    for (int k = 0; k < n; k++) finite = finite && isfinite(b[k]);
+    if (rs_uniform(!finite)) return JAICOV_RESECT_NOT_FINITE;
+    for (int i = 0; i < n; i++) V[i] = U[ix(i, i)] > EPS ? 1.0 / sqrt(U[ix(i, i)]) : 1.0;
+    for (int i = 0; i < n; i++)
+        for (int j = i; j < n; j++) U[ix(i, j)] = U[ix(i, j)] * (V[i] * V[j]);
+    for (int j = 0; j < n; j++) {
+        double s = 0.0;
+        for (int k = 0; k < j; k++) s += U[ix(k, j)] * U[ix(k, j)];
+        const double p = U[ix(j, j)] - s;
+        if (rs_uniform(!(p > SQRT_EPS))) return JAICOV_RESECT_SINGULAR;
+        const double d = sqrt(p);
+        U[ix(j, j)] = d;
+        for (int i = j + 1; i < n; i++) {
+            double r = 0.0;
+            for (int k = 0; k < j; k++) r += U[ix(k, i)] * U[ix(k, j)];
+            U[ix(j, i)] = (U[ix(j, i)] - r) / d;
+        }
+    }
+    for (int i = 0; i < n; i++) {
+        double r = 0.0;
+        for (int k = 0; k < i; k++) r += U[ix(k, i)] * b[k];
+        b[i] = (V[i] * b[i] - r) / U[ix(i, i)];
+    }
+    for (int i = n - 1; i >= 0; i--) {
+        double r = 0.0;
+        for (int k = i + 1; k < n; k++) r += U[ix(i, k)] * b[k];
+        b[i] = (b[i] - r) / U[ix(i, i)];
+    }
+    for (int i = 0; i < n; i++) b[i] = V[i] * b[i];
+    return JAICOV_RESECT_OK;
+}
+
+// the orthogonal polar factor of X (3 x 3, row-major), in place: Newton's iteration from X / sqrt(|X|_F^2 / 3)
+__device__ inline void rs_polar(double *X) {
+    double f = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; k++) f += X[k] * X[k];
+    f = sqrt(f / 3.0);
+#pragma unroll
+    for (int k = 0; k < 9; k++) X[k] = X[k] / f;
+    for (int step = 0; step < RESECT_POLAR_STEPS; step++) {
+        double C[9];                                      // cofactors: row i of C = row i+1 x row i+2
+        C[0] = X[4] * X[8] - X[5] * X[7]; C[1] = X[5] * X[6] - X[3] * X[8]; C[2] = X[3] * X[7] - X[4] * X[6];
+        C[3] = X[7] * X[2] - X[8] * X[1]; C[4] = X[8] * X[0] - X[6] * X[2]; C[5] = X[6] * X[1] - X[7] * X[0];
+        C[6] = X[1] * X[5] - X[2] * X[4]; C[7] = X[2] * X[3] - X[0] * X[5]; C[8] = X[0] * X[4] - X[1] * X[3];
+        const double det = X[0] * C[0] + X[1] * C[1] + X[2] * C[2];
+#pragma unroll
+        for (int k = 0; k < 9; k++) X[k] = 0.5 * (X[k] + C[k] / det);
+    }
+}
+
+// one Jacobi rotation in the plane (p, q) of a symmetric 3 x 3 matrix; r is the third index; wp, wq: the eigenvector rows p and q
+__device__ inline void rs_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double *wp, double *wq) {
+    if (rs_uniform(apq == 0.0)) return;
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    app = app - t * apq; aqq = aqq + t * apq; apq = 0.0;
+    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
+    arp = rp; arq = rq;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double vp = c * wp[k] - s * wq[k], vq = s * wp[k] + c * wq[k];
+        wp[k] = vp; wq[k] = vq;
+    }
+}
+
+// eigenvectors of the scatter matrix S (00 01 02 11 12 22) as the rows of E: e1, e2 (falling eigenvalue), n with det = +1
+__device__ inline void rs_eigen(const double *S, double *E) {
+    double a00 = S[0], a01 = S[1], a02 = S[2], a11 = S[3], a12 = S[4], a22 = S[5];
+    double W[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    for (int sweep = 0; sweep < RESECT_JACOBI_SWEEPS; sweep++) {
+        rs_rotate(a00, a11, a01, a02, a12, W, W + 3);
+        rs_rotate(a00, a22, a02, a01, a12, W, W + 6);
+        rs_rotate(a11, a22, a12, a01, a02, W + 3, W + 6);
+    }
+    auto order = [&](double &la, double &lb, double *wa, double *wb) {      // the larger eigenvalue first; equal ones keep their order
+        if (rs_uniform(!(la < lb))) return;
+        const double l = la; la = lb; lb = l;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { const double w = wa[k]; wa[k] = wb[k]; wb[k] = w; }
+    };
+    order(a00, a11, W, W + 3);
+    order(a11, a22, W + 3, W + 6);
+    order(a00, a11, W, W + 3);
+    const double n0 = W[1] * W[5] - W[2] * W[4], n1 = W[2] * W[3] - W[0] * W[5], n2 = W[0] * W[4] - W[1] * W[3];   // e1 x e2
+    if (n0 * W[6] + n1 * W[7] + n2 * W[8] < 0.0) { W[6] = -W[6]; W[7] = -W[7]; W[8] = -W[8]; }
+#pragma unroll
+    for (int k = 0; k < 9; k++) E[k] = W[k];
+}
+
+// R(omega, phi, kappa), PDF:125-135, row-major.  Lanes 0, 1, 2 take the sine and cosine of one angle each and hand them to the wave,
+// so that the kernel holds one copy of sincos and of its constants, not three.
+__device__ inline void rs_rotation(int lane, const double *par, double *R, double &sk, double &ck) {
+    const double angle = lane == 0 ? par[3] : lane == 1 ? par[4] : par[5];
+    double sn, cs;
+    sincos(angle, &sn, &cs);
+    const double so = __shfl(sn, 0), co = __shfl(cs, 0), sp = __shfl(sn, 1), cp = __shfl(cs, 1);
+    sk = __shfl(sn, 2); ck = __shfl(cs, 2);
+    R[0] = cp * ck;                 R[1] = -cp * sk;                R[2] = sp;
+    R[3] = co * sk + so * sp * ck;  R[4] = co * ck - so * sp * sk;  R[5] = -so * cp;
+    R[6] = so * sk - co * sp * ck;  R[7] = so * ck + co * sp * sk;  R[8] = co * cp;
+}
+
+// the six reduced unknowns of the pose p = M P + t (M row-major): X0 = -R t with R = M', and the angles of R (omega by lane 0, kappa
+// by lane 1: one copy of atan2)
+__device__ inline void rs_pose(int lane, const double *M, const double *t, double *par) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) par[k] = -(M[k] * t[0] + M[3 + k] * t[1] + M[6 + k] * t[2]);
+    const double a = atan2(lane == 0 ? -M[7] : -M[3], lane == 0 ? M[8] : M[0]);   // r23 = M[2][1], r33 = M[2][2]; r12 = M[1][0], r11 = M[0][0]
+    par[3] = __shfl(a, 0);
+    par[4] = asin(fmin(1.0, fmax(-1.0, M[6])));                                   // r13 = M[2][0]
+    par[5] = __shfl(a, 1);
+}
+
+// where the state of an image lies in LDS (doubles): every lane stores the same words there and reads them back
+enum { RS_XC = 0, RS_S = 3, RS_PAR = 4, RS_R = 10, RS_SK = 19, RS_CK = 20, RS_E = 21, RS_CAND = 30, RS_NSTATE = 37 };
+
+__global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32_t *__restrict__ obs_begin, const double *__restrict__ xy,
+                                                           const double *__restrict__ xyz, const double *__restrict__ var,
+                                                           const double *__restrict__ image_io, const double *__restrict__ eo_start,
+                                                           double s0, int max_iter, double thr2, int min_points,
+                                                           double *__restrict__ out, int32_t *__restrict__ outcome, uint8_t *used,
+                                                           double *__restrict__ obs_q) {
+    __shared__ double sx[RESECT_CHUNK], sy[RESECT_CHUNK], sp11[RESECT_CHUNK], sp12[RESECT_CHUNK], sp22[RESECT_CHUNK];
+    __shared__ double sX[RESECT_CHUNK], sY[RESECT_CHUNK], sZ[RESECT_CHUNK];
+    __shared__ uint8_t sused[RESECT_CHUNK];
+    // The sums of the last pass, the same in every lane after the butterfly, and the image's state: Xc, s, the six unknowns, R with
+    // sin and cos of kappa, the plane's axes e1 e2 n, the space candidate's unknowns and Omega.  They live in LDS, not in registers:
+    // between two passes the registers hold the small algebra, during a pass the lane's partial sums, never both.
+    // The workgroup is one wave (RESECT_LANES == 64, the launch and the launch bound use the same constant), and all of this rests on
+    // it: every lane stores the same value to the same word and reads it back, rs_solve_lds reads and rewrites sA in place, and no
+    // barrier stands between such a store and the reads that follow, because the LDS operations of one wave complete in order.
+    // With more than one wave per workgroup none of it would hold.
+    static_assert(RESECT_LANES == 64, "one wave per image: the uniform state in LDS relies on it");
+    __shared__ double sA[66 + 11 + 1], sV[11], sP[RS_NSTATE];
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const long k0 = obs_begin[g];
+    const int m = obs_begin[g + 1] - obs_begin[g];
+    double *og = out + (long)JAICOV_RESECT_OUT_PER_IMAGE * g;
+    int iters = 0;
+    // a failed image: NaN in the values and in q, no observation used, start kind 0.  Taken by the whole wave.
+    auto fail = [&](int st) {
+        if (lane < JAICOV_RESECT_OUT_PER_IMAGE) og[lane] = NAN;
+        if (lane == 0) { outcome[3L * g] = st; outcome[3L * g + 1] = iters; outcome[3L * g + 2] = 0; }
+        for (int t = lane; t < m; t += 64) {
+            used[k0 + t] = 0;
+            if (obs_q) obs_q[k0 + t] = NAN;
+        }
+    };
+    const double x0 = image_io[3L * g], y0 = image_io[3L * g + 1], c = image_io[3L * g + 2];
+    bool given = eo_start != nullptr;
+#pragma unroll
+    for (int k = 0; k < 6; k++) given = given && isfinite(eo_start[6L * g + k]);
+    const bool too_few = m < (given ? 3 : 4);
+    const bool resident = m <= RESECT_CHUNK;
+    // observations c0 .. c0 + nc - 1 into LDS, with their weights (PDF:308-319)
+    auto stage = [&](int c0, int nc) {
+        __syncthreads();
+        for (int t = lane; t < nc; t += 64) {
+            const long k = k0 + c0 + t;
+            sx[t] = xy[2 * k]; sy[t] = xy[2 * k + 1];
+            sX[t] = xyz[3 * k]; sY[t] = xyz[3 * k + 1]; sZ[t] = xyz[3 * k + 2];
+            double p11 = 1.0, p12 = 0.0, p22 = 1.0;
+            if (var) {
+                const double vx = var[3 * k], vy = var[3 * k + 1], rho = var[3 * k + 2];
+                if (rho == 0.0) {
+                    p11 = s0 / vx; p22 = s0 / vy;
+                } else {
+                    const double inv = s0 / ((1.0 - rho * rho) * vx * vy);
+                    p11 = inv * vy; p22 = inv * vx; p12 = -inv * rho * sqrt(vx * vy);
+                }
+            }
+            sp11[t] = p11; sp12[t] = p12; sp22[t] = p22;
+            sused[t] = used[k];
+        }
+        __syncthreads();
+    };
+
+    // one pass over the image's observations: the sums of the used ones, combined over the lanes, into sA; RS_EVAL also writes q of
+    // every observation and finds the used one with the largest q (the lowest index among equal values)
+    auto pass = [&](int mode, double &qmax, int &qidx) {
+        double acc[RESECT_NACC];
+#pragma unroll
+        for (int a = 0; a < RESECT_NACC; a++) acc[a] = 0.0;
+        qmax = -1.0; qidx = INT_MAX;
+        const bool want_q = mode == RS_EVAL && obs_q;
+        for (int c0 = 0; c0 < m; c0 += RESECT_CHUNK) {
+            const int nc = min(RESECT_CHUNK, m - c0);
+            if (!resident) stage(c0, nc);
+            for (int t = lane; t < nc; t += 64) {
+                const bool in = sused[t] != 0;
+                if (!in && !want_q) continue;
+                if (mode == RS_CENTROID) {
+                    acc[0] += sX[t]; acc[1] += sY[t]; acc[2] += sZ[t];
+                    continue;
+                }
+                const double d0 = sX[t] - sP[RS_XC], d1 = sY[t] - sP[RS_XC + 1], d2 = sZ[t] - sP[RS_XC + 2];
+                if (mode == RS_SCATTER) {
+                    acc[0] += d0 * d0; acc[1] += d0 * d1; acc[2] += d0 * d2; acc[3] += d1 * d1; acc[4] += d1 * d2; acc[5] += d2 * d2;
+                    continue;
+                }
+                const double s = sP[RS_S];
+                const double P0 = d0 / s, P1 = d1 / s, P2 = d2 / s;
+                if (mode == RS_SPACE) {
+                    const double u = -(sx[t] - x0) / c, v = -(sy[t] - y0) / c;
+                    // Of the 66 + 11 sums of the two rows a = (P 1 | 0 | -u P), b = (0 | P 1 | -v P) only 51 differ: the blocks of
+                    // m1 and of m2 are the same sums, the block between them is zero, and a term a_i a_j + b_i b_j with one
+                    // product zero is the other product to the bit.  They are dealt out to the 11 x 11 system after the butterfly.
+                    const double G[4] = {P0, P1, P2, 1.0};
+                    const double au[3] = {-(u * P0), -(u * P1), -(u * P2)}, bv[3] = {-(v * P0), -(v * P1), -(v * P2)};
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+#pragma unroll
+                        for (int j = i; j < 4; j++) acc[rs_ix<4>(i, j)] += G[i] * G[j];
+#pragma unroll
+                        for (int j = 0; j < 3; j++) { acc[10 + 3 * i + j] += G[i] * au[j]; acc[22 + 3 * i + j] += G[i] * bv[j]; }
+                        acc[40 + i] += G[i] * u;
+                        acc[44 + i] += G[i] * v;
+                    }
+#pragma unroll
+                    for (int i = 0; i < 3; i++) {
+#pragma unroll
+                        for (int j = i; j < 3; j++) acc[34 + rs_ix<3>(i, j)] += au[i] * au[j] + bv[i] * bv[j];
+                        acc[48 + i] += au[i] * u + bv[i] * v;
+                    }
+                } else if (mode == RS_PLANE) {
+                    const double u = -(sx[t] - x0) / c, v = -(sy[t] - y0) / c;
+                    const double pa = sP[RS_E] * P0 + sP[RS_E + 1] * P1 + sP[RS_E + 2] * P2;
+                    const double pb = sP[RS_E + 3] * P0 + sP[RS_E + 4] * P1 + sP[RS_E + 5] * P2;
+                    const double a[8] = {pa, pb, 1.0, 0.0, 0.0, 0.0, -(u * pa), -(u * pb)};
+                    const double b[8] = {0.0, 0.0, 0.0, pa, pb, 1.0, -(v * pa), -(v * pb)};
+#pragma unroll
+                    for (int i = 0; i < 8; i++) {
+#pragma unroll
+                        for (int j = i; j < 8; j++) acc[rs_ix<8>(i, j)] += a[i] * a[j] + b[i] * b[j];
+                        acc[36 + i] += a[i] * u + b[i] * v;
+                    }
+                } else {                                  // the collinearity equations at the unknowns, in the reduced coordinates
+                    const double *R = sP + RS_R;
+                    const double sk = sP[RS_SK], ck = sP[RS_CK];
+                    const double dX = P0 - sP[RS_PAR], dY = P1 - sP[RS_PAR + 1], dZ = P2 - sP[RS_PAR + 2];
+                    const double kx = R[0] * dX + R[3] * dY + R[6] * dZ;                   // PDF:141-143
+                    const double ky = R[1] * dX + R[4] * dY + R[7] * dZ;
+                    const double N = R[2] * dX + R[5] * dY + R[8] * dZ;
+                    const double xs = -c * (kx / N), ys = -c * (ky / N);                  // PDF:145-149
+                    const double go = R[8] * dY - R[5] * dZ, gp = ky * sk - kx * ck;
+                    const double ax[6] = {(R[2] * xs + c * R[0]) / N, (R[5] * xs + c * R[3]) / N, (R[8] * xs + c * R[6]) / N,   // PDF:165-167
+                                          (xs * go + c * (R[6] * dY - R[3] * dZ)) / N, (xs * gp + c * N * ck) / N, ys};        // PDF:169-171
+                    const double ay[6] = {(R[2] * ys + c * R[1]) / N, (R[5] * ys + c * R[4]) / N, (R[8] * ys + c * R[7]) / N,   // PDF:183-185
+                                          (ys * go + c * (R[7] * dY - R[4] * dZ)) / N, (ys * gp - c * N * sk) / N, -xs};       // PDF:187-189
+                    const double w0 = sx[t] - (x0 + xs), w1 = sy[t] - (y0 + ys);
+                    const double p11 = sp11[t], p12 = sp12[t], p22 = sp22[t];
+                    const double pw0 = p11 * w0 + p12 * w1, pw1 = p12 * w0 + p22 * w1;
+                    const double q = w0 * pw0 + w1 * pw1;
+                    if (want_q) obs_q[k0 + c0 + t] = q;
+                    if (!in) continue;
+                    double px[6], py[6];
+#pragma unroll
+                    for (int i = 0; i < 6; i++) { px[i] = p11 * ax[i] + p12 * ay[i]; py[i] = p12 * ax[i] + p22 * ay[i]; }
+#pragma unroll
+                    for (int i = 0; i < 6; i++) {
+#pragma unroll
+                        for (int j = i; j < 6; j++) acc[rs_ix<6>(i, j)] += ax[i] * px[j] + ay[i] * py[j];
+                        acc[21 + i] += ax[i] * pw0 + ay[i] * pw1;
+                    }
+                    acc[27] += q;
+                    if (q > qmax) { qmax = q; qidx = c0 + t; }
+                }
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+            for (int a = 0; a < RESECT_NACC_STEP; a++) acc[a] += __shfl_xor(acc[a], off);
+            if (mode == RS_SPACE || mode == RS_PLANE) {
+#pragma unroll
+                for (int a = RESECT_NACC_STEP; a < RESECT_NACC; a++) acc[a] += __shfl_xor(acc[a], off);
+            }
+            const double oq = __shfl_xor(qmax, off);
+            const int oi = __shfl_xor(qidx, off);
+            if (oq > qmax || (oq == qmax && oi < qidx)) { qmax = oq; qidx = oi; }
+        }
+        __syncthreads();                                  // the last reads of the state and of the sums before
+        if (mode == RS_SPACE) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+#pragma unroll
+                for (int j = i; j < 4; j++) sA[rs_ix<11>(i, j)] = sA[rs_ix<11>(4 + i, 4 + j)] = acc[rs_ix<4>(i, j)];
+#pragma unroll
+                for (int j = 0; j < 4; j++) sA[rs_ix<11>(i, 4 + j)] = 0.0;
+#pragma unroll
+                for (int j = 0; j < 3; j++) { sA[rs_ix<11>(i, 8 + j)] = acc[10 + 3 * i + j]; sA[rs_ix<11>(4 + i, 8 + j)] = acc[22 + 3 * i + j]; }
+                sA[66 + i] = acc[40 + i];
+                sA[70 + i] = acc[44 + i];
+            }
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+#pragma unroll
+                for (int j = i; j < 3; j++) sA[rs_ix<11>(8 + i, 8 + j)] = acc[34 + rs_ix<3>(i, j)];
+                sA[74 + i] = acc[48 + i];
+            }
+        } else {
+#pragma unroll
+            for (int a = 0; a < RESECT_NACC_PLANE; a++) sA[a] = acc[a];
+        }
+        __syncthreads();
+    };
+
+    if (resident && !too_few) stage(0, m);
+    const double SQRT_EPS = sqrt(ldexp(1.0, -53));
+    int nused = m, st = JAICOV_RESECT_OK, kind = JAICOV_RESECT_START_GIVEN;
+    double qmax = -1.0;
+    int qidx = INT_MAX, cand_st = JAICOV_RESECT_SINGULAR; // the space candidate (sP[RS_CAND ...]) exists, or why it does not
+    bool have_cand = false, new_angles = false;
+    int failed = too_few ? JAICOV_RESECT_TOO_FEW_POINTS : -1;
+    // one loop over the passes of all rounds, so that the pass, the rotation and the pose are compiled once:
+    // CENTROID -> SCATTER (-> SPACE -> EVAL_SPACE) -> PLANE -> EVAL_PLANE -> STEP ... STEP -> EVAL (-> CENTROID of the next round)
+    int mode = RS_CENTROID, it = 0;
+    while (failed < 0) {
+        mode = rs_uniform(mode);
+        if (new_angles) { rs_rotation(lane, sP + RS_PAR, sP + RS_R, sP[RS_SK], sP[RS_CK]); new_angles = false; }
+        pass(mode, qmax, qidx);
+        double M[9], t[3];                                // a linear start's pose p = M P + t, when it has one
+        bool new_pose = false, choose = false;
+        int plane_st = JAICOV_RESECT_OK;
+        if (mode == RS_CENTROID) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) sP[RS_XC + k] = sA[k] / (double)nused;
+            mode = RS_SCATTER;
+        } else if (mode == RS_SCATTER) {
+            const double s2 = ((sA[0] + sA[3]) + sA[5]) / (double)nused, s = sqrt(s2);
+            sP[RS_S] = s;
+            st = JAICOV_RESECT_NOT_CONVERGED; it = 0;
+            if (rs_uniform(!isfinite(s2))) {
+                failed = JAICOV_RESECT_NOT_FINITE;
+            } else if (rs_uniform(!(s > 0.0))) {
+                failed = JAICOV_RESECT_SINGULAR;
+            } else if (given) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    sP[RS_PAR + k] = (eo_start[6L * g + k] - sP[RS_XC + k]) / s;
+                    sP[RS_PAR + 3 + k] = eo_start[6L * g + 3 + k];
+                }
+                new_angles = true;
+                kind = JAICOV_RESECT_START_GIVEN;
+                mode = RS_STEP;
+            } else if (nused < 4) {
+                failed = JAICOV_RESECT_TOO_FEW_POINTS;
+            } else {
+                double S[6], E[9];
+#pragma unroll
+                for (int k = 0; k < 6; k++) S[k] = sA[k];
+                rs_eigen(S, E);
+#pragma unroll
+                for (int k = 0; k < 9; k++) sP[RS_E + k] = E[k];
+                have_cand = false; cand_st = JAICOV_RESECT_SINGULAR;
+                mode = nused >= 6 ? RS_SPACE : RS_PLANE;
+            }
+        } else if (mode == RS_SPACE) {
+            cand_st = rs_solve_lds(11, sA, sA + 66, sV);
+            mode = RS_PLANE;
+            if (cand_st == JAICOV_RESECT_OK) {
+                const double *h = sA + 66;
+                double Mt[9] = {h[0], h[1], h[2], h[4], h[5], h[6], h[8], h[9], h[10]};
+                t[0] = h[3]; t[1] = h[7]; t[2] = 1.0;
+                const double det = Mt[0] * (Mt[4] * Mt[8] - Mt[5] * Mt[7]) + Mt[1] * (Mt[5] * Mt[6] - Mt[3] * Mt[8]) +
+                                   Mt[2] * (Mt[3] * Mt[7] - Mt[4] * Mt[6]);
+                const double sg = det < 0.0 ? -1.0 : 1.0;
+#pragma unroll
+                for (int k = 0; k < 9; k++) { Mt[k] = sg * Mt[k]; M[k] = Mt[k]; }
+#pragma unroll
+                for (int k = 0; k < 3; k++) t[k] = sg * t[k];
+                rs_polar(M);
+                double mu = 0.0;
+#pragma unroll
+                for (int k = 0; k < 9; k++) mu += M[k] * Mt[k];
+                mu = mu / 3.0;
+#pragma unroll
+                for (int k = 0; k < 3; k++) t[k] = t[k] / mu;
+                new_pose = true;
+                mode = RS_EVAL_SPACE;
+            }
+        } else if (mode == RS_EVAL_SPACE) {
+            have_cand = rs_uniform(isfinite(sA[27]));
+            if (!have_cand) cand_st = JAICOV_RESECT_NOT_FINITE;
+            sP[RS_CAND + 6] = sA[27];
+#pragma unroll
+            for (int k = 0; k < 6; k++) sP[RS_CAND + k] = sP[RS_PAR + k];
+            mode = RS_PLANE;
+        } else if (mode == RS_PLANE) {
+            plane_st = rs_solve_lds(8, sA, sA + 36, sV);
+            choose = plane_st != JAICOV_RESECT_OK;
+            if (plane_st == JAICOV_RESECT_OK) {
+                const double *h = sA + 36, *E = sP + RS_E;
+                const double l1 = sqrt(h[0] * h[0] + h[3] * h[3] + h[6] * h[6]), l2 = sqrt(h[1] * h[1] + h[4] * h[4] + h[7] * h[7]);
+                const double lam = (l1 + l2) / 2.0, sg = c > 0.0 ? -1.0 : 1.0;                    // c t3 < 0, t3 = sg / lam
+                const double r1[3] = {sg * (h[0] / lam), sg * (h[3] / lam), sg * (h[6] / lam)};
+                const double r2[3] = {sg * (h[1] / lam), sg * (h[4] / lam), sg * (h[7] / lam)};
+                t[0] = sg * (h[2] / lam); t[1] = sg * (h[5] / lam); t[2] = sg * (1.0 / lam);
+                const double r3[3] = {r1[1] * r2[2] - r1[2] * r2[1], r1[2] * r2[0] - r1[0] * r2[2], r1[0] * r2[1] - r1[1] * r2[0]};
+                double B[9] = {r1[0], r2[0], r3[0], r1[1], r2[1], r3[1], r1[2], r2[2], r3[2]};           // columns r1 r2 r3
+                rs_polar(B);
+#pragma unroll
+                for (int i = 0; i < 3; i++)                                                           // B [e1 e2 n]': the rows of E
+#pragma unroll
+                    for (int j = 0; j < 3; j++) M[3 * i + j] = B[3 * i] * E[j] + B[3 * i + 1] * E[3 + j] + B[3 * i + 2] * E[6 + j];
+                new_pose = true;
+                mode = RS_EVAL_PLANE;
+            }
+        } else if (mode == RS_EVAL_PLANE) {
+            plane_st = rs_uniform(isfinite(sA[27])) ? JAICOV_RESECT_OK : JAICOV_RESECT_NOT_FINITE;
+            choose = true;
+        } else if (mode == RS_STEP) {
+            double A[21], b[6], dx[6];
+#pragma unroll
+            for (int k = 0; k < 21; k++) A[k] = sA[k];
+#pragma unroll
+            for (int k = 0; k < 6; k++) b[k] = sA[21 + k];
+            int ss = rs_solve<6>(A, b, dx, nullptr);
+            iters++;
+            if (ss == JAICOV_RESECT_OK) {
+                double z = 0.0;                           // NaN unless every value is finite
+#pragma unroll
+                for (int k = 0; k < 6; k++) z += dx[k] * 0.0;
+                if (rs_uniform(z != 0.0)) ss = JAICOV_RESECT_NOT_FINITE;
+            }
+            if (ss != JAICOV_RESECT_OK) {
+                failed = ss;
+            } else {
+                double step = 0.0;
+#pragma unroll
+                for (int k = 0; k < 6; k++) { sP[RS_PAR + k] = sP[RS_PAR + k] + dx[k]; step = fmax(step, fabs(dx[k])); }
+                new_angles = true;
+                if (rs_uniform(step <= SQRT_EPS)) { st = JAICOV_RESECT_OK; mode = RS_EVAL; }
+                else if (++it >= max_iter) mode = RS_EVAL;
+            }
+        } else {                                          // RS_EVAL: Q is taken from these sums after the loop
+            if (rs_uniform(thr2 > 0.0 && nused > min_points && qmax > thr2 && qidx < m)) {
+                if (lane == 0) { used[k0 + qidx] = 0; if (resident) sused[qidx] = 0; }
+                __syncthreads();                          // the withdrawal is visible to every lane before the next pass reads it
+                nused--;
+                mode = RS_CENTROID;
+            } else {
+                break;
+            }
+        }
+        if (choose) {                  // the choice: the smaller Omega at the start values, on a tie the plane start
+            const bool have_plane = plane_st == JAICOV_RESECT_OK;
+            if (!have_plane && !have_cand) {
+                failed = plane_st == JAICOV_RESECT_NOT_FINITE || cand_st == JAICOV_RESECT_NOT_FINITE ? JAICOV_RESECT_NOT_FINITE
+                                                                                                     : JAICOV_RESECT_SINGULAR;
+            } else if (rs_uniform(have_cand && (!have_plane || sP[RS_CAND + 6] < sA[27]))) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) sP[RS_PAR + k] = sP[RS_CAND + k];
+                new_angles = true;
+                kind = JAICOV_RESECT_START_SPACE;
+            } else {
+                kind = JAICOV_RESECT_START_PLANE;
+            }
+            mode = RS_STEP;
+        }
+        if (new_pose) { rs_pose(lane, M, t, sP + RS_PAR); new_angles = true; }
+    }
+    double o[JAICOV_RESECT_OUT_PER_IMAGE];
+    if (failed < 0) {
+        double A[21], b[6], Q[21];
+#pragma unroll
+        for (int k = 0; k < 21; k++) A[k] = sA[k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) b[k] = sA[21 + k];
+        const int se = rs_solve<6>(A, b, nullptr, Q);
+        if (se != JAICOV_RESECT_OK) failed = se;
+        const double s = sP[RS_S];
+#pragma unroll
+        for (int k = 0; k < 3; k++) { o[k] = sP[RS_XC + k] + s * sP[RS_PAR + k]; o[3 + k] = sP[RS_PAR + 3 + k]; }
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int j = i; j < 6; j++) {
+                const double f = (i < 3 ? s : 1.0) * (j < 3 ? s : 1.0);     // X0 = Xc + s X0r
+                o[6 + rs_ix<6>(i, j)] = Q[rs_ix<6>(i, j)] * f;
+            }
+        o[27] = sA[27];
+        double z = 0.0;
+#pragma unroll
+        for (int k = 0; k < JAICOV_RESECT_OUT_PER_IMAGE; k++) z += o[k] * 0.0;
+        if (failed < 0 && rs_uniform(z != 0.0)) failed = JAICOV_RESECT_NOT_FINITE;
+    }
+    if (failed >= 0) { fail(failed); return; }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < JAICOV_RESECT_OUT_PER_IMAGE; k++) og[k] = o[k];
+        outcome[3L * g] = st;
+        outcome[3L * g + 1] = iters;
+        outcome[3L * g + 2] = kind;
+    }
+}
+
+bool resect_device_ok() {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return false;
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
+    return strncmp(prop.gcnArchName, "gfx950", 6) == 0;
+}
+
+}  // namespace
+}  // namespace jaicov
+
+using namespace jaicov;
+
+extern "C" int jaicov_resect_images(int32_t n_images, const int32_t *obs_begin, const double *xy, const double *xyz, const double *var,
+                                    const double *image_io, const double *eo_start, double sigma2apriori, int32_t max_iterations,
+                                    double reject_threshold, int32_t min_points, double *out, int32_t *status, int32_t *iterations,
+                                    int32_t *start_kind, uint8_t *obs_used, double *obs_q, double *ms_out) {
+    // argument checks, host only
+    if (n_images < 0 || !obs_begin) return JAICOV_ERR_BAD_ARGUMENT;
+    if (!(sigma2apriori > 0.0) || max_iterations < 1 || min_points < 3 || !(reject_threshold >= 0.0)) return JAICOV_ERR_BAD_ARGUMENT;
+    if (n_images > 0 && (!out || !status || !image_io)) return JAICOV_ERR_BAD_ARGUMENT;
+    if (obs_begin[0] != 0) return JAICOV_ERR_BAD_ARGUMENT;
+    for (int32_t g = 0; g < n_images; g++)
+        if (obs_begin[g + 1] < obs_begin[g]) return JAICOV_ERR_BAD_ARGUMENT;
+    const long n_obs = obs_begin[n_images];
+    if (n_obs > 0 && (!xy || !xyz)) return JAICOV_ERR_BAD_ARGUMENT;
+    if (var)
+        for (long k = 0; k < n_obs; k++)
+            if (!(var[3 * k] > 0.0) || !(var[3 * k + 1] > 0.0) || !(fabs(var[3 * k + 2]) < 1.0)) return JAICOV_ERR_BAD_ARGUMENT;
+
+    if (!resect_device_ok()) return JAICOV_ERR_NO_DEVICE;
+    if (ms_out) *ms_out = 0.0;
+    if (n_images == 0) return JAICOV_OK;
+
+    hipStream_t s;
+    if (hipStreamCreate(&s) != hipSuccess) return JAICOV_ERR_DEVICE;
+    const int rc = [&]() -> int {      // the owners go before the stream does
+        int32_t *d_begin = nullptr, *d_outcome = nullptr;
+        double *d_xy = nullptr, *d_xyz = nullptr, *d_var = nullptr, *d_io = nullptr, *d_eo = nullptr, *d_out = nullptr, *d_q = nullptr;
+        uint8_t *d_used = nullptr;
+        DevBag bag;
+        DevEvent ev0, ev1;
+        if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+        const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
+        const size_t ni = (size_t)n_images, no = (size_t)(n_obs > 0 ? n_obs : 1);
+        std::vector<int32_t> h_outcome(3 * ni);
+        if (bag.alloc(&d_begin, ni + 1) != hipSuccess || bag.alloc(&d_xy, 2 * no) != hipSuccess || bag.alloc(&d_xyz, 3 * no) != hipSuccess ||
+            (var && bag.alloc(&d_var, 3 * no) != hipSuccess) || bag.alloc(&d_io, 3 * ni) != hipSuccess ||
+            (eo_start && bag.alloc(&d_eo, 6 * ni) != hipSuccess) || bag.alloc(&d_out, JAICOV_RESECT_OUT_PER_IMAGE * ni) != hipSuccess ||
+            bag.alloc(&d_outcome, 3 * ni) != hipSuccess || bag.alloc(&d_used, no) != hipSuccess || (obs_q && bag.alloc(&d_q, no) != hipSuccess))
+            return JAICOV_ERR_OUT_OF_MEMORY;
+        hipMemcpyAsync(d_begin, obs_begin, (ni + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
+        if (n_obs > 0) {
+            hipMemcpyAsync(d_xy, xy, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+            hipMemcpyAsync(d_xyz, xyz, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+            if (var) hipMemcpyAsync(d_var, var, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+        }
+        hipMemcpyAsync(d_io, image_io, 3 * ni * sizeof(double), hipMemcpyHostToDevice, s);
+        if (eo_start) hipMemcpyAsync(d_eo, eo_start, 6 * ni * sizeof(double), hipMemcpyHostToDevice, s);
+        hipMemsetAsync(d_used, 1, no, s);                                  // every observation starts as used
+        hipEventRecord(e0, s);
+        hipLaunchKernelGGL(resect_images_kernel, dim3(n_images), dim3(RESECT_LANES), 0, s, d_begin, d_xy, d_xyz, d_var, d_io, d_eo, sigma2apriori,
+                           (int)max_iterations, reject_threshold * reject_threshold, (int)min_points, d_out, d_outcome, d_used, d_q);
+        if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
+        hipEventRecord(e1, s);
+        hipMemcpyAsync(out, d_out, JAICOV_RESECT_OUT_PER_IMAGE * ni * sizeof(double), hipMemcpyDeviceToHost, s);
+        hipMemcpyAsync(h_outcome.data(), d_outcome, 3 * ni * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        if (obs_used && n_obs > 0) hipMemcpyAsync(obs_used, d_used, (size_t)n_obs, hipMemcpyDeviceToHost, s);
+        if (obs_q && n_obs > 0) hipMemcpyAsync(obs_q, d_q, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost, s);
+        if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
+        for (size_t g = 0; g < ni; g++) {
+            status[g] = h_outcome[3 * g];
+            if (iterations) iterations[g] = h_outcome[3 * g + 1];
+            if (start_kind) start_kind[g] = h_outcome[3 * g + 2];
+        }
+        if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
+        return JAICOV_OK;
+    }();
+    hipStreamDestroy(s);
+    return rc;
+}

@@ -1,6 +1,6 @@
 """ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` / ``include/jaicov_transform.h`` /
 ``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_reliability_points.h`` /
-``include/jaicov_datum.h`` / ``include/jaicov_intersect.h``
+``include/jaicov_datum.h`` / ``include/jaicov_intersect.h`` / ``include/jaicov_resect.h``
 (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
@@ -57,6 +57,10 @@ DLT_CONVERGED, DLT_NOT_CONVERGED, DLT_TOO_FEW_POINTS, DLT_SINGULAR, DLT_NOT_FINI
 # include/jaicov_intersect.h: forward intersection of a batch of object points from oriented images (stand-alone, no engine)
 ISECT_EXPORTS = ["jaicov_isect_points"]
 ISECT_OK, ISECT_NOT_CONVERGED, ISECT_TOO_FEW_RAYS, ISECT_SINGULAR, ISECT_NOT_FINITE = range(5)
+# include/jaicov_resect.h: spatial resection of a batch of images from known object points (stand-alone, no engine)
+RESECT_EXPORTS = ["jaicov_resect_images"]
+RESECT_OK, RESECT_NOT_CONVERGED, RESECT_TOO_FEW_POINTS, RESECT_SINGULAR, RESECT_NOT_FINITE = range(5)
+RESECT_START_GIVEN, RESECT_START_SPACE, RESECT_START_PLANE = range(3)
 
 KROW = 32  # 12 + JAICOV_MAX_DIST_PER_CAMERA
 INVERT_NONE, INVERT_FULL, INVERT_REDUCED = 0, 1, 2   # MatrixInversion (BundleAdjustment.java:65-70)
@@ -167,6 +171,8 @@ def load_library():
     L.jaicov_dlt_adjust.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pi, C.c_int32, C.c_int32, _pd, _pi, _pi, _pd]
     L.jaicov_isect_points.argtypes = [C.c_int32, _pi, _pi, _pd, _pd, C.c_int32, _pd, _pd, C.c_double, C.c_int32, C.c_double, C.c_int32,
                                       _pd, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
+    L.jaicov_resect_images.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, _pd, _pd, C.c_double, C.c_int32, C.c_double, C.c_int32,
+                                       _pd, _pi, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
     _LIB = L
     return L
 
@@ -575,6 +581,58 @@ def intersect_problem(fp: FlatProblem, values=None, with_status=False, **kw):
     out, status, _, _, _ = intersect_points(begin, fp.ip_image[order], np.stack([fp.ip_x, fp.ip_y], 1)[order], var, io, eo, **kw)
     ok = status <= ISECT_NOT_CONVERGED
     v[:3 * fp.n_points].reshape(-1, 3)[ok] = out[ok, :3]
+    return (v, out, status) if with_status else v
+
+
+def resect_images(obs_begin, xy, xyz, var, image_io, eo_start=None, sigma2apriori=1.0, max_iterations=50, reject_threshold=0.0,
+                  min_points=4, with_time=False):
+    """Spatial resection of every image of a batch from its known object points (include/jaicov_resect.h).  obs_begin: (n + 1,) CSR
+    offsets of the images' observations; xy: (n_obs, 2); xyz: (n_obs, 3) the object point of each observation; var: (n_obs, 3) var_x,
+    var_y, rho or None (unit weights); image_io: (n, 3) x0, y0, c of each image's camera; eo_start: (n, 6) or None, an image whose six
+    values are all finite starts from them, any other from the linear start.  Returns (out (n, 28): X0, Y0, Z0, omega, phi, kappa, the
+    21 entries of the upper triangle of Q, Omega; status (n,); iterations (n,); start_kind (n,); obs_used (n_obs,); obs_q (n_obs,)),
+    plus the kernel time in ms with with_time."""
+    L = load_library()
+    ob = np.ascontiguousarray(obs_begin, np.int32).ravel()
+    n = ob.size - 1
+    xy = np.ascontiguousarray(xy, np.float64).reshape(-1)
+    xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1)
+    var = None if var is None else np.ascontiguousarray(var, np.float64).reshape(-1)
+    io = np.ascontiguousarray(image_io, np.float64).reshape(-1)
+    eo = None if eo_start is None else np.ascontiguousarray(eo_start, np.float64).reshape(-1)
+    n_obs = xy.size // 2
+    if xy.size % 2 or xyz.size != 3 * n_obs or (var is not None and var.size != 3 * n_obs) or io.size != 3 * max(n, 0) or \
+            (eo is not None and eo.size != 6 * max(n, 0)) or (ob.size and ob[-1] != n_obs):
+        raise EngineError(-1, "resect images: array sizes do not agree")
+    out = np.zeros((max(n, 0), 28)); status = np.zeros(max(n, 0), np.int32); iterations = np.zeros(max(n, 0), np.int32)
+    kind = np.zeros(max(n, 0), np.int32); used = np.zeros(n_obs, np.uint8); q = np.zeros(n_obs)
+    ms = np.zeros(1)
+    null = C.cast(None, _pd)
+    rc = L.jaicov_resect_images(n, ob.ctypes.data_as(_pi), _p(xy), _p(xyz), _p(var) if var is not None else null, _p(io),
+                                _p(eo) if eo is not None else null, float(sigma2apriori), int(max_iterations), float(reject_threshold),
+                                int(min_points), _p(out), status.ctypes.data_as(_pi), iterations.ctypes.data_as(_pi),
+                                kind.ctypes.data_as(_pi), used.ctypes.data_as(C.POINTER(C.c_uint8)), _p(q), _p(ms))
+    if rc != 0:
+        raise EngineError(rc, "resect images")
+    return (out, status, iterations, kind, used, q) + ((float(ms[0]),) if with_time else ())
+
+
+def resect_problem(fp: FlatProblem, values=None, with_status=False, **kw):
+    """Start values of a FlatProblem's exterior orientations by spatial resection: the observations of every image are its image
+    points in the problem's order (a stable sort of ip_image) with their ip_var_x, ip_var_y, ip_rho; the object points and the
+    interior orientation come from the slot vector `values` (default fp.values).  Returns the slot vector with the orientation of
+    every resected image replaced (an image whose status is TOO_FEW_POINTS, SINGULAR or NOT_FINITE keeps its values); with_status
+    also (out, status).  kw: as resect_images (sigma2apriori defaults to the problem's)."""
+    v = np.array(fp.values if values is None else values, np.float64)
+    order = np.argsort(fp.ip_image, kind="stable")
+    begin = np.concatenate([[0], np.cumsum(np.bincount(fp.ip_image, minlength=fp.n_images))]).astype(np.int32)
+    io = v[3 * fp.n_points:3 * fp.n_points + 3 * fp.n_cameras].reshape(-1, 3)[fp.image_camera]
+    xyz = v[:3 * fp.n_points].reshape(-1, 3)[np.asarray(fp.ip_point)[order]]
+    var = np.stack([fp.ip_var_x, fp.ip_var_y, fp.ip_rho], 1)[order]
+    kw.setdefault("sigma2apriori", fp.sigma2apriori)
+    out, status = resect_images(begin, np.stack([fp.ip_x, fp.ip_y], 1)[order], xyz, var, io, **kw)[:2]
+    ok = status <= RESECT_NOT_CONVERGED
+    v[fp.slot_eo(0):].reshape(-1, 6)[ok] = out[ok, :6]
     return (v, out, status) if with_status else v
 
 

@@ -265,6 +265,19 @@ PYBIND11_MODULE(_jaicov_host, m) {
     isect.def_static("intersectAll", &ForwardIntersection::intersectAll, py::arg("cameras"), py::arg("sigma2apriori") = 1.0,
                      py::arg("rejectThreshold") = 0.0, py::arg("minRays") = 3, py::return_value_policy::move)
         .def_static("setMaximalNumberOfIterations", &ForwardIntersection::setMaximalNumberOfIterations);
+    py::class_<SpatialResection> resect(m, "SpatialResection");
+    py::class_<SpatialResection::Result>(resect, "Result")
+        .def_property_readonly("image", [](SpatialResection::Result &r) { return r.image; }, py::return_value_policy::reference)
+        .def_readonly("status", &SpatialResection::Result::status)
+        .def_readonly("iterations", &SpatialResection::Result::iterations)
+        .def_readonly("startKind", &SpatialResection::Result::startKind)
+        .def_readonly("points", &SpatialResection::Result::points)
+        .def_readonly("pointsUsed", &SpatialResection::Result::pointsUsed)
+        .def("values", [](SpatialResection::Result &r) { return std::vector<double>(r.values, r.values + JAICOV_RESECT_OUT_PER_IMAGE); });
+    resect.def_static("resectAll", &SpatialResection::resectAll, py::arg("cameras"), py::arg("fromCurrentValues") = false,
+                      py::arg("sigma2apriori") = 1.0, py::arg("rejectThreshold") = 0.0, py::arg("minPoints") = 4)
+        .def_static("getMaximalNumberOfIterations", &SpatialResection::getMaximalNumberOfIterations)
+        .def_static("setMaximalNumberOfIterations", &SpatialResection::setMaximalNumberOfIterations);
 
     py::class_<AiconProject>(m, "AiconProject")
         .def_property_readonly("camera", [](AiconProject &p) { return p.camera ? p.camera.get() : (p.cameras.empty() ? nullptr : p.cameras[0].get()); },

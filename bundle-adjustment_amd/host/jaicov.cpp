@@ -707,4 +707,52 @@ std::vector<ForwardIntersection::Result> ForwardIntersection::intersectAll(const
     return res;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// SpatialResection (include/jaicov_resect.h) on the device
+// ---------------------------------------------------------------------------------------------------------------
+std::vector<SpatialResection::Result> SpatialResection::resectAll(const std::vector<Camera *> &cameras, bool fromCurrentValues,
+                                                                  double sigma2apriori, double rejectThreshold, int minPoints) {
+    std::vector<Image *> images;
+    std::vector<int32_t> begin(1, 0);
+    std::vector<double> xy, xyz, var, io, eo;
+    for (Camera *cam : cameras) {
+        InteriorOrientation &ior = cam->getInteriorOrientation();
+        for (auto &im : cam->images()) {
+            images.push_back(im.get());
+            for (int k = 0; k < 3; k++) io.push_back(ior.at(k)->getValue());
+            for (int k = 0; k < 6; k++) eo.push_back(im->getExteriorOrientation().at(k)->getValue());
+            for (auto &ic : im->coordinates()) {
+                ObjectCoordinate *oc = ic->getObjectCoordinate();
+                xy.push_back(ic->getX().getValue()); xy.push_back(ic->getY().getValue());
+                xyz.push_back(oc->getX().getValue()); xyz.push_back(oc->getY().getValue()); xyz.push_back(oc->getZ().getValue());
+                var.push_back(ic->getX().getVariance()); var.push_back(ic->getY().getVariance());
+                var.push_back(ic->getCorrelationCoefficientXY());
+            }
+            begin.push_back((int32_t)(xy.size() / 2));
+        }
+    }
+    const int n = (int)images.size();
+    std::vector<double> out((size_t)JAICOV_RESECT_OUT_PER_IMAGE * n);
+    std::vector<int32_t> status(n), iterations(n), kind(n);
+    std::vector<uint8_t> used(xy.size() / 2);
+    const int rc = jaicov_resect_images(n, begin.data(), xy.data(), xyz.data(), var.data(), io.data(), fromCurrentValues ? eo.data() : nullptr,
+                                        sigma2apriori, maximalNumberOfIterations_, rejectThreshold, minPoints, out.data(), status.data(),
+                                        iterations.data(), kind.data(), used.data(), nullptr, nullptr);
+    if (rc != JAICOV_OK) throw std::runtime_error("jaicov_resect_images failed with status " + std::to_string(rc));
+    std::vector<Result> res(n);
+    for (int g = 0; g < n; g++) {
+        Result &r = res[g];
+        r.image = images[g];
+        r.status = status[g];
+        r.iterations = iterations[g];
+        r.startKind = kind[g];
+        r.points = begin[g + 1] - begin[g];
+        for (int k = begin[g]; k < begin[g + 1]; k++) r.pointsUsed += used[k];
+        for (int k = 0; k < JAICOV_RESECT_OUT_PER_IMAGE; k++) r.values[k] = out[(size_t)JAICOV_RESECT_OUT_PER_IMAGE * g + k];
+        if (r.status == JAICOV_RESECT_OK || r.status == JAICOV_RESECT_NOT_CONVERGED)
+            for (int k = 0; k < 6; k++) r.image->getExteriorOrientation().at(k)->setValue(r.values[k]);
+    }
+    return res;
+}
+
 }  // namespace jaicov::host

@@ -29,6 +29,7 @@
 #include "../../include/jaicov_transform.h"
 #include "../../include/jaicov_dlt.h"
 #include "../../include/jaicov_intersect.h"
+#include "../../include/jaicov_resect.h"
 #include "../../include/jaicov_reliability.h"
 #include "../../include/jaicov_reliability_points.h"
 #include "../../include/jaicov_datum.h"
@@ -671,6 +672,28 @@ public:
     };
     static std::vector<Result> intersectAll(const std::vector<Camera *> &cameras, double sigma2apriori = 1.0, double rejectThreshold = 0.0,
                                             int minRays = 3);
+    static int getMaximalNumberOfIterations() { return maximalNumberOfIterations_; }
+    static void setMaximalNumberOfIterations(int n) { maximalNumberOfIterations_ = n; }
+private:
+    static inline int maximalNumberOfIterations_ = 50;
+};
+
+// Spatial resection of images from known object points on the device (include/jaicov_resect.h).  The reference has no counterpart.
+// resectAll() makes one device call for every image of `cameras`, in the cameras' and their images' order.  An image's observations
+// are its image coordinates in its own order, with their variances and correlation coefficient; the object points are the current
+// values of the coordinates' ObjectCoordinates, taken as free of error; the interior orientation is the camera's (no distortion).
+// With fromCurrentValues the images' current exterior orientations are the start values, otherwise every image takes the linear
+// start.  X0 .. kappa are written into every image whose status is JAICOV_RESECT_OK or JAICOV_RESECT_NOT_CONVERGED; the other images
+// keep their values.  A device error (no GPU, out of memory) throws std::runtime_error.
+class SpatialResection {
+public:
+    struct Result {
+        Image *image = nullptr;
+        int status = -1, iterations = 0, startKind = 0, points = 0, pointsUsed = 0;
+        double values[JAICOV_RESECT_OUT_PER_IMAGE] = {};     // X0, Y0, Z0, omega, phi, kappa, the upper triangle of Q, Omega
+    };
+    static std::vector<Result> resectAll(const std::vector<Camera *> &cameras, bool fromCurrentValues = false, double sigma2apriori = 1.0,
+                                         double rejectThreshold = 0.0, int minPoints = 4);
     static int getMaximalNumberOfIterations() { return maximalNumberOfIterations_; }
     static void setMaximalNumberOfIterations(int n) { maximalNumberOfIterations_ = n; }
 private:

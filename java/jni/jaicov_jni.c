@@ -1,6 +1,7 @@
 /*
  * JNI shim between NativeNormalEquationEngine (Java) and the C ABI of include/jaicov_neq.h, include/jaicov_transform.h,
- * include/jaicov_dlt.h, include/jaicov_reliability.h, include/jaicov_datum.h and include/jaicov_intersect.h.
+ * include/jaicov_dlt.h, include/jaicov_reliability.h, include/jaicov_datum.h, include/jaicov_intersect.h and
+ * include/jaicov_resect.h.
  * The build image has no JDK, so this file is not built by __graft_entry__.build(); on a box with a JDK:
  *   gcc -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -I../../include jaicov_jni.c \
  *       -L../../bundle-adjustment_amd/csrc -ljaicov_neq -o libjaicov_jni.so
@@ -23,6 +24,7 @@
 #include "jaicov_transform.h"
 #include "jaicov_dlt.h"
 #include "jaicov_intersect.h"
+#include "jaicov_resect.h"
 #include "jaicov_reliability.h"
 #include "jaicov_datum.h"
 
@@ -694,5 +696,69 @@ JNIEXPORT jint JNICALL NAT(isectPoints)(JNIEnv *e, jclass k, jintArray rayBegin,
     if (pxy) (*e)->ReleaseDoubleArrayElements(e, xy, pxy, JNI_ABORT);
     if (pi) (*e)->ReleaseIntArrayElements(e, rayImage, pi, JNI_ABORT);
     (*e)->ReleaseIntArrayElements(e, rayBegin, pb, JNI_ABORT);
+    return rc;
+}
+
+/* --- include/jaicov_resect.h: spatial resection of a batch of images (no engine) -------------------------------------------------- */
+/* inputs through Get<Type>ArrayElements copies (JNI_ABORT); var, eoStart, iterations, startKind, obsUsed and obsQ may be null; status,
+ * iterations, startKind and obsUsed come back through long[] as for the intersection. */
+JNIEXPORT jint JNICALL NAT(resectImages)(JNIEnv *e, jclass k, jintArray obsBegin, jdoubleArray xy, jdoubleArray xyz, jdoubleArray var,
+                                         jdoubleArray imageIo, jdoubleArray eoStart, jdouble sigma2apriori, jint maxIterations,
+                                         jdouble rejectThreshold, jint minPoints, jdoubleArray out, jlongArray status, jlongArray iterations,
+                                         jlongArray startKind, jlongArray obsUsed, jdoubleArray obsQ) {
+    (void)k;
+    const jsize nb = (*e)->GetArrayLength(e, obsBegin);
+    if (nb < 1) return JAICOV_ERR_BAD_ARGUMENT;
+    const jsize n = nb - 1;
+    if ((*e)->GetArrayLength(e, imageIo) < 3 * n || (eoStart && (*e)->GetArrayLength(e, eoStart) < 6 * n) ||
+        (*e)->GetArrayLength(e, out) < JAICOV_RESECT_OUT_PER_IMAGE * n || (*e)->GetArrayLength(e, status) < n ||
+        (iterations && (*e)->GetArrayLength(e, iterations) < n) || (startKind && (*e)->GetArrayLength(e, startKind) < n))
+        return JAICOV_ERR_BAD_ARGUMENT;
+    jint *pb = (*e)->GetIntArrayElements(e, obsBegin, NULL);
+    if (!pb) return JAICOV_ERR_OUT_OF_MEMORY;
+    const jint no = pb[n];
+    if (no < 0 || (*e)->GetArrayLength(e, xy) < 2 * no || (*e)->GetArrayLength(e, xyz) < 3 * no ||
+        (var && (*e)->GetArrayLength(e, var) < 3 * no) || (obsUsed && (*e)->GetArrayLength(e, obsUsed) < no) ||
+        (obsQ && (*e)->GetArrayLength(e, obsQ) < no)) {
+        (*e)->ReleaseIntArrayElements(e, obsBegin, pb, JNI_ABORT);
+        return JAICOV_ERR_BAD_ARGUMENT;
+    }
+    jdouble *pxy = (*e)->GetDoubleArrayElements(e, xy, NULL);
+    jdouble *pxyz = pxy ? (*e)->GetDoubleArrayElements(e, xyz, NULL) : NULL;
+    jdouble *pvar = (pxyz && var) ? (*e)->GetDoubleArrayElements(e, var, NULL) : NULL;
+    jdouble *pio = pxyz ? (*e)->GetDoubleArrayElements(e, imageIo, NULL) : NULL;
+    jdouble *peo = (pio && eoStart) ? (*e)->GetDoubleArrayElements(e, eoStart, NULL) : NULL;
+    const size_t ni1 = (size_t)(n > 0 ? n : 1), no1 = (size_t)(no > 0 ? no : 1), nl = ni1 > no1 ? ni1 : no1;
+    double *po = (double *)malloc(sizeof(double) * JAICOV_RESECT_OUT_PER_IMAGE * ni1);
+    int32_t *ps = (int32_t *)malloc(sizeof(int32_t) * 3 * ni1);
+    uint8_t *pu = (uint8_t *)malloc(no1);
+    double *pq = (double *)malloc(sizeof(double) * no1);
+    jlong *pl = (jlong *)malloc(sizeof(jlong) * nl);
+    int rc = JAICOV_ERR_OUT_OF_MEMORY;
+    if (pio && (pvar || !var) && (peo || !eoStart) && po && ps && pu && pq && pl) {
+        rc = jaicov_resect_images((int32_t)n, (const int32_t *)pb, pxy, pxyz, pvar, pio, peo, sigma2apriori, (int32_t)maxIterations,
+                                  rejectThreshold, (int32_t)minPoints, po, ps, ps + n, ps + 2 * n, pu, pq, NULL);
+        if (rc == JAICOV_OK) {
+            (*e)->SetDoubleArrayRegion(e, out, 0, JAICOV_RESECT_OUT_PER_IMAGE * n, po);
+            jlongArray dst[3] = {status, iterations, startKind};
+            for (int a = 0; a < 3; a++) {
+                if (!dst[a]) continue;
+                for (jsize i = 0; i < n; i++) pl[i] = (jlong)ps[(size_t)a * n + i];
+                (*e)->SetLongArrayRegion(e, dst[a], 0, n, pl);
+            }
+            if (obsUsed) {
+                for (jsize i = 0; i < no; i++) pl[i] = (jlong)pu[i];
+                (*e)->SetLongArrayRegion(e, obsUsed, 0, no, pl);
+            }
+            if (obsQ) (*e)->SetDoubleArrayRegion(e, obsQ, 0, no, pq);
+        }
+    }
+    free(po); free(ps); free(pu); free(pq); free(pl);
+    if (peo) (*e)->ReleaseDoubleArrayElements(e, eoStart, peo, JNI_ABORT);
+    if (pio) (*e)->ReleaseDoubleArrayElements(e, imageIo, pio, JNI_ABORT);
+    if (pvar) (*e)->ReleaseDoubleArrayElements(e, var, pvar, JNI_ABORT);
+    if (pxyz) (*e)->ReleaseDoubleArrayElements(e, xyz, pxyz, JNI_ABORT);
+    if (pxy) (*e)->ReleaseDoubleArrayElements(e, xy, pxy, JNI_ABORT);
+    (*e)->ReleaseIntArrayElements(e, obsBegin, pb, JNI_ABORT);
     return rc;
 }

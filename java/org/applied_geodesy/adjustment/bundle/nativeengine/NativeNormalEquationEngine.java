@@ -295,6 +295,33 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 		return status;
 	}
 
+	/** jaicov_resect status values and start kinds (include/jaicov_resect.h) */
+	public static final int RESECT_OK = 0, RESECT_NOT_CONVERGED = 1, RESECT_TOO_FEW_POINTS = 2, RESECT_SINGULAR = 3, RESECT_NOT_FINITE = 4;
+	public static final int RESECT_START_GIVEN = 0, RESECT_START_SPACE = 1, RESECT_START_PLANE = 2;
+
+	/**
+	 * Spatial resection of every image of a batch from the known object points it sees and its known interior orientation, on the
+	 * device, with no engine (include/jaicov_resect.h; the reference has no counterpart).  obsBegin (n + 1 CSR offsets) selects each
+	 * image's observations; xy = 2 doubles and xyz = 3 doubles (the object point) per observation; var (may be null: unit weights) =
+	 * variance x, variance y, correlation coefficient per observation (PartialDerivativeFactory.java:308-319); imageIo = x0, y0, c per
+	 * image, c of either sign; eoStart (may be null) = X0, Y0, Z0, omega, phi, kappa per image: an image whose six values are finite
+	 * starts from them, any other from the linear start.  out receives 28 values per image (X0, Y0, Z0, omega, phi, kappa, the upper
+	 * triangle of the cofactor matrix, Omega); iterations, startKind, obsUsed and obsQ may be null.  The result is the status per image;
+	 * an image whose status is RESECT_TOO_FEW_POINTS, RESECT_SINGULAR or RESECT_NOT_FINITE has NaN values.
+	 */
+	public static long[] resectImages(int[] obsBegin, double[] xy, double[] xyz, double[] var, double[] imageIo, double[] eoStart,
+	                                  double sigma2apriori, int maxIterations, double rejectThreshold, int minPoints, double[] out,
+	                                  long[] iterations, long[] startKind, long[] obsUsed, double[] obsQ) {
+		int n = obsBegin.length - 1;
+		long[] status = new long[Math.max(n, 0)];
+		int rc = resectImages(obsBegin, xy, xyz, var, imageIo, eoStart, sigma2apriori, maxIterations, rejectThreshold, minPoints, out, status,
+		                      iterations, startKind, obsUsed, obsQ);
+		if (rc == -1) throw new IllegalArgumentException("jaicov_resect_images: bad argument");
+		if (rc == -4) throw new OutOfMemoryError("jaicov_resect_images");
+		if (rc != 0) throw new IllegalStateException("jaicov_resect_images failed with status " + rc);
+		return status;
+	}
+
 	@Override public void close() { if (handle != 0) { destroy(handle); handle = 0; } }
 
 	private void check(int status) {
@@ -353,4 +380,5 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 	private static native int datumApply(long h, double[] v, double[] out, int n);
 	private static native int dltAdjust(int[] obsBegin, double[] xy, double[] xyz, double[] io, int[] ioFixed, int[] restrictions, int maxIterations, double[] out, long[] status, long[] solves);
 	private static native int isectPoints(int[] rayBegin, int[] rayImage, double[] xy, double[] var, int nImages, double[] imageIo, double[] imageEo, double sigma2apriori, int maxIterations, double rejectThreshold, int minRays, double[] out, long[] status, long[] iterations, long[] rayUsed, double[] rayQ);
+	private static native int resectImages(int[] obsBegin, double[] xy, double[] xyz, double[] var, double[] imageIo, double[] eoStart, double sigma2apriori, int maxIterations, double rejectThreshold, int minPoints, double[] out, long[] status, long[] iterations, long[] startKind, long[] obsUsed, double[] obsQ);
 }
