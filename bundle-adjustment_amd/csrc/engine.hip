@@ -2066,6 +2066,7 @@ extern "C" int jaicov_dense_gemm(int32_t alay, int32_t blay, int32_t M, int32_t 
                                  int32_t lower_only, int32_t kmode, int32_t repeats, double *ms_out) {
 
     if (M % 128 || N % 128 || K % 16 || M <= 0 || N <= 0 || K <= 0 || !A || !B || !C) return JAICOV_ERR_BAD_ARGUMENT;
+    if (alpha == 0.0) return JAICOV_ERR_BAD_ARGUMENT;      // gemm_f64_plan refuses it: the kernel forms (beta/alpha) C
     std::string err;
     int rc = check_device(err);
     if (rc) return rc;
@@ -2095,4 +2096,113 @@ extern "C" int jaicov_dense_gemm(int32_t alay, int32_t blay, int32_t M, int32_t 
     }
     he = he == hipSuccess ? hipDeviceSynchronize() : he;
     return he == hipSuccess ? JAICOV_OK : JAICOV_ERR_DEVICE;
+}
+
+// debug: ONE launch of gemm_f64() with every argument of the launcher in the caller's hand (tests/test_gpu_gemm_family.py), and the plan
+// of that launch without a device (plan_only, tests/test_gemm_plan.py).  Not declared under include/: no product calls it.
+//   A, B, C: host buffers of n_A, n_B, n_C doubles.  c_alias 1 / 2: C is A / B -- one device buffer holds the operand's n_A / n_B doubles,
+//   the launch gets the same pointer twice, and the whole buffer comes back in C (n_C must equal that count).  A == B with n_A == n_B: one
+//   buffer, the same pointer for both operands.  tile_map: n_map (row, col) pairs, row < 0 = no tile.
+//   plan_out[7] = {hipError_t of the plan, TM, TN, tag, grid x, y, z}; filled whenever the arguments themselves are in order.
+// Refused with JAICOV_ERR_BAD_ARGUMENT, before anything is uploaded: what the plan refuses (alpha == 0, in place with more than one
+// column tile), tag >= 2 (the timing experiments: wrong results on purpose), and every extent, leading dimension, stride, count or map
+// entry with which an access of the launch could leave the uploaded buffers.  The test of that is the full rectangle of each operand in
+// every batch of the batch rectangle (batch_sum_limit only removes batches), so it does not depend on the k ranges or the map.
+struct jaicov_debug_gemm_args {
+    uint32_t struct_size;
+    int32_t alay, blay, M, N, K;
+    double alpha, beta;
+    const double *A; int64_t n_A;
+    const double *B; int64_t n_B;
+    double *C; int64_t n_C;
+    int64_t lda, ldb, ldc;
+    int32_t c_alias, lower_only, kmode, batch, batch2;
+    int64_t strideA, strideB, strideC, strideA2, strideB2, strideC2;
+    int32_t batch_sum_limit, small_tiles, tag;
+    const int32_t *tile_map; int32_t n_map;
+    int32_t plan_only;
+    int32_t *plan_out;
+};
+extern "C" int jaicov_debug_gemm(const jaicov_debug_gemm_args *a) {
+    if (!a || a->struct_size != sizeof(jaicov_debug_gemm_args)) return JAICOV_ERR_BAD_ARGUMENT;
+    if (a->M <= 0 || a->N <= 0 || a->K <= 0 || a->M % 128 || a->N % 128 || a->K % 16 || a->M > 32768 || a->N > 32768 || a->K > 32768) return JAICOV_ERR_BAD_ARGUMENT;
+    if ((a->alay != LAY_KC && a->alay != LAY_XC) || (a->blay != LAY_KC && a->blay != LAY_XC) || a->kmode < KMODE_FULL || a->kmode > KMODE_GE_COL) return JAICOV_ERR_BAD_ARGUMENT;
+    if (a->c_alias < 0 || a->c_alias > 2 || a->batch < 1 || a->batch2 < 1 || a->batch > 1024 || a->batch2 > 1024 || a->batch_sum_limit < 0) return JAICOV_ERR_BAD_ARGUMENT;
+    if (a->tag < 0 || a->tag >= 2 || a->n_map < 0 || (a->n_map > 0 && !a->tile_map) || a->n_map > (1 << 22)) return JAICOV_ERR_BAD_ARGUMENT;
+    if (a->lower_only && a->M != a->N) return JAICOV_ERR_BAD_ARGUMENT;
+    const bool same_ab = a->A == a->B && a->n_A == a->n_B;
+    // the plan sees the aliasing through pointer equality alone: stand-ins with the same equalities as the device pointers will have
+    static const double stand_in[3] = {0, 0, 0};
+    GemmArgs g{};
+    g.A = stand_in; g.B = same_ab ? stand_in : stand_in + 1;
+    g.C = const_cast<double *>(a->c_alias == 1 ? g.A : a->c_alias == 2 ? g.B : stand_in + 2);
+    g.lda = a->lda; g.ldb = a->ldb; g.ldc = a->ldc; g.M = a->M; g.N = a->N; g.K = a->K; g.alpha = a->alpha; g.beta = a->beta;
+    g.lower_only = a->lower_only != 0; g.kmode = a->kmode;
+    g.strideA = a->strideA; g.strideB = a->strideB; g.strideC = a->strideC;
+    g.strideA2 = a->strideA2; g.strideB2 = a->strideB2; g.strideC2 = a->strideC2;
+    g.batch_sum_limit = a->batch_sum_limit;
+    g.tile_map = a->n_map > 0 ? reinterpret_cast<const int2 *>(stand_in) : nullptr; g.n_map = a->n_map;
+    const GemmPlan p = gemm_f64_plan(a->alay, a->blay, g, a->batch, a->small_tiles, a->tag, a->batch2);
+    if (a->plan_out) {
+        const int32_t out[7] = {(int32_t)p.status, p.TM, p.TN, p.tag, (int32_t)p.grid_x, (int32_t)p.grid_y, (int32_t)p.grid_z};
+        std::copy(out, out + 7, a->plan_out);
+    }
+    if (p.status != hipSuccess || p.TM == 0) return JAICOV_ERR_BAD_ARGUMENT;
+    if (a->plan_only) return JAICOV_OK;
+
+    // ---- every access of the launch stays inside the buffers: decided here, on the host -------------------------------------------------
+    if (!a->A || !a->B || !a->C) return JAICOV_ERR_BAD_ARGUMENT;
+    const int64_t a_rows = a->alay == LAY_KC ? a->M : a->K, a_cols = a->alay == LAY_KC ? a->K : a->M;
+    const int64_t b_rows = a->blay == LAY_KC ? a->N : a->K, b_cols = a->blay == LAY_KC ? a->K : a->N;
+    auto inside = [&](int64_t rows, int64_t cols, int64_t ld, int64_t s1, int64_t s2, int64_t count) {   // all factors are bounded above: no overflow
+        if (ld < cols || ld > (1 << 20) || ld % 2 || s1 % 2 || s2 % 2 ||       // (even: the kernel loads the operands in pairs of doubles)
+            s1 < 0 || s2 < 0 || s1 > ((int64_t)1 << 32) || s2 > ((int64_t)1 << 32) || count <= 0) return false;
+        return (a->batch - 1) * s1 + (a->batch2 - 1) * s2 + (rows - 1) * ld + cols <= count;
+    };
+    const int64_t count_c = a->c_alias == 1 ? a->n_A : a->c_alias == 2 ? a->n_B : a->n_C;
+    if (!inside(a_rows, a_cols, a->lda, a->strideA, a->strideA2, a->n_A) || !inside(b_rows, b_cols, a->ldb, a->strideB, a->strideB2, a->n_B) ||
+        !inside(a->M, a->N, a->ldc, a->strideC, a->strideC2, count_c) || a->n_C != count_c)
+        return JAICOV_ERR_BAD_ARGUMENT;
+    if (p.use_map) {       // in tiles of the plan's instance; the lower grid takes what the map says, so the map decides what is written
+        if ((int64_t)p.grid_x != a->n_map) return JAICOV_ERR_BAD_ARGUMENT;
+        for (int i = 0; i < a->n_map; i++) {
+            const int r = a->tile_map[2 * i], c = a->tile_map[2 * i + 1];
+            if (r >= 0 && (r >= a->M / p.TM || c < 0 || c >= a->N / p.TN)) return JAICOV_ERR_BAD_ARGUMENT;
+        }
+    }
+    std::string err;
+    const int rc = check_device(err);
+    if (rc) return rc;
+    {
+        DevBuf<double> A_store, B_store, C_store;
+        DevBuf<int2> map_store;
+        if (A_store.reserve((size_t)a->n_A) != hipSuccess || (!same_ab && B_store.reserve((size_t)a->n_B) != hipSuccess) ||
+            (a->c_alias == 0 && C_store.reserve((size_t)a->n_C) != hipSuccess) || (p.use_map && map_store.reserve((size_t)a->n_map) != hipSuccess))
+            return JAICOV_ERR_OUT_OF_MEMORY;
+        double *dA = A_store.get(), *dB = same_ab ? dA : B_store.get();
+        double *dC = a->c_alias == 1 ? dA : a->c_alias == 2 ? dB : C_store.get();
+        if (hipMemcpy(dA, a->A, (size_t)a->n_A * 8, hipMemcpyHostToDevice) != hipSuccess ||
+            (!same_ab && hipMemcpy(dB, a->B, (size_t)a->n_B * 8, hipMemcpyHostToDevice) != hipSuccess) ||
+            (a->c_alias == 0 && hipMemcpy(dC, a->C, (size_t)a->n_C * 8, hipMemcpyHostToDevice) != hipSuccess) ||
+            (p.use_map && hipMemcpy(map_store.get(), a->tile_map, (size_t)a->n_map * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess))
+            return JAICOV_ERR_DEVICE;
+        g.A = dA; g.B = dB; g.C = dC;
+        g.tile_map = p.use_map ? map_store.get() : nullptr; g.n_map = p.use_map ? a->n_map : 0;
+        const GemmPlan q = gemm_f64_plan(a->alay, a->blay, g, a->batch, a->small_tiles, a->tag, a->batch2);   // the device pointers alias as the stand-ins did
+        if (q.status != p.status || q.TM != p.TM || q.TN != p.TN || q.tag != p.tag || q.grid_x != p.grid_x || q.use_map != p.use_map) return JAICOV_ERR_BAD_STATE;
+        hipError_t he = gemm_f64(nullptr, a->alay, a->blay, g, a->batch, a->small_tiles, a->tag, a->batch2);
+        he = he == hipSuccess ? hipDeviceSynchronize() : he;
+        if (he != hipSuccess) return JAICOV_ERR_DEVICE;
+        if (hipMemcpy(a->C, dC, (size_t)a->n_C * 8, hipMemcpyDeviceToHost) != hipSuccess) return JAICOV_ERR_DEVICE;
+    }
+    return JAICOV_OK;
+}
+
+// debug: xcd_tile_map(T) of gemm_f64.h as (row, col) pairs; returns the number of pairs (out == NULL or cap too small: nothing else)
+extern "C" int jaicov_debug_xcd_tile_map(int T, int32_t *out, int cap) {
+    if (T < 1 || T > 4096) return JAICOV_ERR_BAD_ARGUMENT;
+    const std::vector<int2> m = xcd_tile_map(T);
+    if (out && cap >= (int)m.size())
+        for (size_t i = 0; i < m.size(); i++) { out[2 * i] = m[i].x; out[2 * i + 1] = m[i].y; }
+    return (int)m.size();
 }

@@ -36,7 +36,7 @@ struct GemmArgs {
     double *C;
     long lda, ldb, ldc;
     int M, N, K;         // multiples of 128 / 128 / 16
-    double alpha, beta;  // C = alpha*A*B + beta*C
+    double alpha, beta;  // C = alpha*A*B + beta*C.  alpha != 0: the kernel forms (beta/alpha) C first, gemm_f64() refuses alpha == 0
     int lower_only;      // square tile grid: skip tiles with tile_col > tile_row
     int kmode;           // restrict the k range per tile (triangular operands), see KMODE_*
     long strideA, strideB, strideC;  // batch strides (blockIdx.y)
@@ -287,52 +287,87 @@ inline std::vector<int2> xcd_tile_map(int T) {
 // 64-tile latency variant; `small_tiles` < 0 = that rule, 0 = never, 1 = always (rectangular KMODE_FULL calls only).
 constexpr int GEMM_SMALL_TILE_LIMIT = 480;
 constexpr int GEMM_TINY_TILE_LIMIT = 256;   // 64-tiles below which the 32-tile variant is used
-inline hipError_t gemm_f64(hipStream_t s, int alay, int blay, const GemmArgs &g, int batch = 1, int small_tiles = -1, int tag = 0, int batch2 = 1) {
-    if (g.M <= 0 || g.N <= 0) return hipSuccess;
+
+// What one call of gemm_f64() launches: the kernel instance <alay, blay, TM, TN, tag> and its grid.  Host arithmetic alone, so
+// that the choice can be read without a device (jaicov_debug_gemm with plan_only, tests/test_gemm_plan.py).
+//   status != hipSuccess: the call is refused and nothing is launched.  TM == 0 with hipSuccess: nothing to do (M or N <= 0).
+//   use_map: the instance reads g.tile_map (the lower-triangular 64-tile instance has an order of its own and ignores it).
+// Refused:
+//   alpha == 0: the accumulators start from (beta/alpha) C, which is not finite then.  No caller scales by zero, and the hot
+//     kernel gets no second path for it.
+//   C == A or C == B with more than one column tile of the instance: a workgroup would overwrite operand rows that the
+//     workgroups of the other column tiles still read.  (The 64 x 64 lower instance always has two or more.)
+//   C == B with more than one workgroup per batch: every workgroup reads ALL of B (one column tile) and writes its own rows of
+//     it.  C == A is the in-place form the callers use: there a workgroup reads and writes its own rows only.
+struct GemmPlan {
+    hipError_t status;
+    int TM, TN, tag;
+    unsigned grid_x, grid_y, grid_z;
+    bool use_map;
+};
+
+inline GemmPlan gemm_f64_plan(int alay, int blay, const GemmArgs &g, int batch = 1, int small_tiles = -1, int tag = 0, int batch2 = 1) {
+    GemmPlan p{hipSuccess, 0, 0, 0, 0, (unsigned)batch, (unsigned)batch2, false};
+    if (g.M <= 0 || g.N <= 0) return p;
+    const GemmPlan refused{hipErrorInvalidValue, 0, 0, 0, 0, 0, 0, false};
+    if (g.alpha == 0.0) return refused;
     const int tm = g.M / 128, tn = g.N / 128;
     const int tiles = g.lower_only ? tm * (tm + 1) / 2 : tm * tn;
-    dim3 grid(g.tile_map ? g.n_map : tiles, batch, batch2), block(256);
-    if (g.lower_only && small_tiles == 1 && g.kmode == KMODE_FULL && alay == LAY_KC && blay == LAY_KC && g.M == g.N) {
+    const bool kckc = alay == LAY_KC && blay == LAY_KC;
+    const bool in_place = g.C == g.A || g.C == g.B;
+    if (in_place && tn != 1) return refused;
+    if (g.lower_only && small_tiles == 1 && g.kmode == KMODE_FULL && kckc && g.M == g.N) {
         // lower-triangular grid in 64-tiles: 4x the workgroups, a quarter of the time each.  For the trailing update of
         // the factorisation's tail, where the panel chain on the other stream waits for its workgroups to retire.
-        GemmArgs h = g;
-        h.tile_map = nullptr; h.n_map = 0;
+        if (in_place) return refused;
         const int t64 = g.M / 64;
-        grid.x = t64 * (t64 + 1) / 2;
-        if (tag == 1) hipLaunchKernelGGL((gemm_f64_kernel<LAY_KC, LAY_KC, 64, 64, 1>), grid, block, 0, s, h);
-        else hipLaunchKernelGGL((gemm_f64_kernel<LAY_KC, LAY_KC, 64, 64>), grid, block, 0, s, h);
-        return hipGetLastError();
+        p.TM = p.TN = 64;
+        p.tag = tag == 1;
+        p.grid_x = (unsigned)(t64 * (t64 + 1) / 2);
+        return p;
     }
-    const bool can_small = !g.lower_only && g.kmode == KMODE_FULL && alay == LAY_KC && blay == LAY_KC;
+    const bool can_small = !g.lower_only && g.kmode == KMODE_FULL && kckc;
     if (can_small && (small_tiles > 0 || (small_tiles < 0 && tiles * batch < GEMM_SMALL_TILE_LIMIT))) {
         // even the 64-tile leaves most SIMDs idle when only a few block rows remain; a wave then spends its k-step in
         // 16 dependent-issue MFMAs.  The 32-tile (one MFMA tile per wave) cuts that to 4.
         const bool tiny = small_tiles < 0 && tiles * batch * 4 < GEMM_TINY_TILE_LIMIT;
-        if (g.C == g.A || g.C == g.B) {   // in place (one column tile): keep the whole row of C in one workgroup
-            if (tn != 1) return hipErrorInvalidValue;
-            if (tiny) {
-                grid.x = tiles * 4;
-                hipLaunchKernelGGL((gemm_f64_kernel<LAY_KC, LAY_KC, 32, 128>), grid, block, 0, s, g);
-            } else {
-                grid.x = tiles * 2;
-                hipLaunchKernelGGL((gemm_f64_kernel<LAY_KC, LAY_KC, 64, 128>), grid, block, 0, s, g);
-            }
-        } else if (tiny) {
-            grid.x = tiles * 16;
-            hipLaunchKernelGGL((gemm_f64_kernel<LAY_KC, LAY_KC, 32, 32>), grid, block, 0, s, g);
-        } else {
-            grid.x = tiles * 4;
-            hipLaunchKernelGGL((gemm_f64_kernel<LAY_KC, LAY_KC, 64, 64>), grid, block, 0, s, g);
-        }
-        return hipGetLastError();
+        if (g.C == g.B) return refused;
+        p.TM = tiny ? 32 : 64;
+        p.TN = in_place ? 128 : p.TM;   // in place (one column tile): keep the whole row of C in one workgroup
+        p.grid_x = (unsigned)(tiles * (128 / p.TM) * (128 / p.TN));
+        return p;
     }
-    if (alay == LAY_KC && blay == LAY_KC && tag == 2) hipLaunchKernelGGL((gemm_f64_kernel<LAY_KC, LAY_KC, 128, 128, 2>), grid, block, 0, s, g);
-    else if (alay == LAY_KC && blay == LAY_KC && tag == 3) hipLaunchKernelGGL((gemm_f64_kernel<LAY_KC, LAY_KC, 128, 128, 3>), grid, block, 0, s, g);
-    else if (alay == LAY_KC && blay == LAY_KC && tag == 1) hipLaunchKernelGGL((gemm_f64_kernel<LAY_KC, LAY_KC, 128, 128, 1>), grid, block, 0, s, g);
-    else if (alay == LAY_KC && blay == LAY_KC) hipLaunchKernelGGL((gemm_f64_kernel<LAY_KC, LAY_KC>), grid, block, 0, s, g);
-    else if (alay == LAY_KC && blay == LAY_XC) hipLaunchKernelGGL((gemm_f64_kernel<LAY_KC, LAY_XC>), grid, block, 0, s, g);
-    else if (alay == LAY_XC && blay == LAY_XC) hipLaunchKernelGGL((gemm_f64_kernel<LAY_XC, LAY_XC>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((gemm_f64_kernel<LAY_XC, LAY_KC>), grid, block, 0, s, g);
+    if (g.C == g.B && tm != 1) return refused;
+    p.TM = p.TN = 128;
+    p.tag = kckc && tag >= 1 && tag <= 3 ? tag : 0;   // TAG 2, 3: the timing experiments (wrong results)
+    p.use_map = g.tile_map != nullptr;
+    p.grid_x = (unsigned)(p.use_map ? g.n_map : tiles);
+    return p;
+}
+
+inline hipError_t gemm_f64(hipStream_t s, int alay, int blay, const GemmArgs &g, int batch = 1, int small_tiles = -1, int tag = 0, int batch2 = 1) {
+    const GemmPlan p = gemm_f64_plan(alay, blay, g, batch, small_tiles, tag, batch2);
+    if (p.status != hipSuccess || p.TM == 0) return p.status;
+    GemmArgs h = g;
+    if (!p.use_map) { h.tile_map = nullptr; h.n_map = 0; }
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z), block(256);
+#define JAICOV_GEMM_LAUNCH(...) hipLaunchKernelGGL((gemm_f64_kernel<__VA_ARGS__>), grid, block, 0, s, h); break
+    switch (p.TM * 10000 + p.TN * 10 + p.tag + (p.TM == 128 ? 1000000 * (2 * alay + blay) : 0)) {   // one case per instance of the plan
+        case 1281280: JAICOV_GEMM_LAUNCH(LAY_KC, LAY_KC);
+        case 1281281: JAICOV_GEMM_LAUNCH(LAY_KC, LAY_KC, 128, 128, 1);
+        case 1281282: JAICOV_GEMM_LAUNCH(LAY_KC, LAY_KC, 128, 128, 2);
+        case 1281283: JAICOV_GEMM_LAUNCH(LAY_KC, LAY_KC, 128, 128, 3);
+        case 2281280: JAICOV_GEMM_LAUNCH(LAY_KC, LAY_XC);
+        case 3281280: JAICOV_GEMM_LAUNCH(LAY_XC, LAY_KC);
+        case 4281280: JAICOV_GEMM_LAUNCH(LAY_XC, LAY_XC);
+        case 640640: JAICOV_GEMM_LAUNCH(LAY_KC, LAY_KC, 64, 64);
+        case 640641: JAICOV_GEMM_LAUNCH(LAY_KC, LAY_KC, 64, 64, 1);
+        case 641280: JAICOV_GEMM_LAUNCH(LAY_KC, LAY_KC, 64, 128);
+        case 320320: JAICOV_GEMM_LAUNCH(LAY_KC, LAY_KC, 32, 32);
+        case 321280: JAICOV_GEMM_LAUNCH(LAY_KC, LAY_KC, 32, 128);
+        default: return hipErrorInvalidValue;   // a plan without an instance: a missing kernel is an error
+    }
+#undef JAICOV_GEMM_LAUNCH
     return hipGetLastError();
 }
 

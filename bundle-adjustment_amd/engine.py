@@ -646,3 +646,64 @@ def dense_gemm(alay, blay, A, B, C_in, M, N, K, alpha=1.0, beta=0.0, lower_only=
     if rc != 0:
         raise EngineError(rc, "dense gemm")
     return Cm, float(ms[0])
+
+
+class DebugGemmArgs(C.Structure):
+    """jaicov_debug_gemm_args (csrc/engine.hip)"""
+    _fields_ = [("struct_size", C.c_uint32), ("alay", C.c_int32), ("blay", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+                ("alpha", C.c_double), ("beta", C.c_double), ("A", C.c_void_p), ("n_A", C.c_int64), ("B", C.c_void_p), ("n_B", C.c_int64),
+                ("C", C.c_void_p), ("n_C", C.c_int64), ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64),
+                ("c_alias", C.c_int32), ("lower_only", C.c_int32), ("kmode", C.c_int32), ("batch", C.c_int32), ("batch2", C.c_int32),
+                ("strideA", C.c_int64), ("strideB", C.c_int64), ("strideC", C.c_int64),
+                ("strideA2", C.c_int64), ("strideB2", C.c_int64), ("strideC2", C.c_int64),
+                ("batch_sum_limit", C.c_int32), ("small_tiles", C.c_int32), ("tag", C.c_int32),
+                ("tile_map", C.c_void_p), ("n_map", C.c_int32), ("plan_only", C.c_int32), ("plan_out", C.c_void_p)]
+
+
+def debug_gemm(alay, blay, M, N, K, alpha, beta, A=None, B=None, C_in=None, lda=0, ldb=0, ldc=0, c_alias=0, lower_only=0, kmode=0,
+               batch=1, batch2=1, strides=(0, 0, 0, 0, 0, 0), batch_sum_limit=0, small_tiles=-1, tag=0, tile_map=None, plan_only=False):
+    """One launch of the fp64 GEMM launcher through jaicov_debug_gemm, every argument in the caller's hand.  A, B, C_in: flat float64
+    buffers (B may be the same array as A: one device buffer then; with c_alias 1 / 2 C_in is ignored and C is A / B on the device).
+    tile_map: (n, 2) int32.  Returns (status, plan, C): plan = (hipError_t, TM, TN, tag, grid x, y, z), C = the C buffer after the launch
+    (a copy; None with plan_only).  The status is returned, not raised: the refusals are what the tests ask for."""
+    L = load_library()
+    a = DebugGemmArgs()
+    a.struct_size = C.sizeof(DebugGemmArgs)
+    a.alay, a.blay, a.M, a.N, a.K, a.alpha, a.beta = alay, blay, M, N, K, alpha, beta
+    a.lda, a.ldb, a.ldc = lda, ldb, ldc
+    a.c_alias, a.lower_only, a.kmode, a.batch, a.batch2 = c_alias, int(lower_only), kmode, batch, batch2
+    a.strideA, a.strideB, a.strideC, a.strideA2, a.strideB2, a.strideC2 = strides
+    a.batch_sum_limit, a.small_tiles, a.tag, a.plan_only = batch_sum_limit, small_tiles, tag, int(bool(plan_only))
+    plan = np.full(7, -1, np.int32)
+    a.plan_out = plan.ctypes.data
+    keep = [plan]
+    if tile_map is not None:
+        tm = np.ascontiguousarray(tile_map, np.int32).reshape(-1, 2)
+        keep.append(tm)
+        a.tile_map, a.n_map = tm.ctypes.data, tm.shape[0]
+    Cm = None
+    if not plan_only:
+        for x in (A, B):
+            assert x.dtype == np.float64 and x.ndim == 1 and x.flags.c_contiguous
+        a.A, a.n_A, a.B, a.n_B = A.ctypes.data, A.size, B.ctypes.data, B.size
+        Cm = (A if c_alias == 1 else B if c_alias == 2 else np.ascontiguousarray(C_in, np.float64).reshape(-1)).copy()
+        a.C, a.n_C = Cm.ctypes.data, Cm.size
+    else:            # the plan looks at the aliasing alone: A == B is told by equal pointers and counts
+        a.A, a.n_A, a.B, a.n_B = 1, 0, (1 if B is A and A is not None else 2), 0
+    L.jaicov_debug_gemm.argtypes = [C.c_void_p]
+    L.jaicov_debug_gemm.restype = C.c_int
+    rc = L.jaicov_debug_gemm(C.addressof(a))
+    return rc, tuple(int(v) for v in plan), Cm
+
+
+def debug_xcd_tile_map(T):
+    """xcd_tile_map(T) of csrc/gemm_f64.h as an (n, 2) int32 array; no device needed."""
+    L = load_library()
+    L.jaicov_debug_xcd_tile_map.argtypes = [C.c_int, C.c_void_p, C.c_int]
+    L.jaicov_debug_xcd_tile_map.restype = C.c_int
+    n = L.jaicov_debug_xcd_tile_map(T, None, 0)
+    if n < 0:
+        raise EngineError(n, "xcd tile map")
+    out = np.zeros((n, 2), np.int32)
+    assert L.jaicov_debug_xcd_tile_map(T, out.ctypes.data, n) == n
+    return out

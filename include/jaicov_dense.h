@@ -22,7 +22,8 @@ int jaicov_dense_spd_solve_packed(int32_t n, double *ap, double *b, int32_t nrhs
 
 /* Parity / timing hook of the fp64 MFMA GEMM family (csrc/gemm_f64.h): C = alpha op(A) op(B) + beta C, row-major C.
  * alay/blay: 0 = k contiguous, 1 = m resp. n contiguous.  M,N multiples of 128, K multiple of 16.
- * kmode: 0 full, 1 k < (tile_row+1)*128, 2 k >= tile_row*128, 3 k >= tile_col*128.  Host buffers. */
+ * kmode: 0 full, 1 k < (tile_row+1)*128, 2 k >= tile_row*128, 3 k >= tile_col*128.  Host buffers.
+ * alpha == 0 is refused with JAICOV_ERR_BAD_ARGUMENT: the kernels form (beta/alpha) C before the products. */
 int jaicov_dense_gemm(int32_t alay, int32_t blay, int32_t M, int32_t N, int32_t K, double alpha, const double *A,
                       int64_t lda, const double *B, int64_t ldb, double beta, double *C, int64_t ldc,
                       int32_t lower_only, int32_t kmode, int32_t repeats, double *ms_out);

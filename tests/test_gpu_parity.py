@@ -16,6 +16,8 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("alay,blay,kmode,lower", [(0, 0, 0, False), (0, 0, 0, True), (0, 1, 3, False), (0, 1, 1, False),
                                                     (1, 1, 2, True), (1, 0, 0, False)])
 def test_gemm_f64_family(alay, blay, kmode, lower):
+    # The first case (KC, KC, full k range, 256 x 384 = 6 tiles) does NOT run the 128-tile instance: below 64 64-tiles the launcher's size
+    # rule picks gemm_f64_kernel<KC, KC, 32, 32>.  Every instance is reached on purpose, with its plan asserted, in test_gpu_gemm_family.py.
     rng = np.random.default_rng(5)
     M, N, K = 256, 384 if not lower else 256, 256
     if kmode in (1, 2):
