@@ -1,0 +1,844 @@
+// relorient.hip -- relative orientation of many image pairs in one launch (include/jaicov_relorient.h): start values of the first two
+// exterior orientations of a block without control points, from the image points two images share.  The call has no counterpart in
+// the reference; its rotation is that of derivation/PartialDerivativeFactory.java (PDF), its dispersions PDF:308-319 inverted, its
+// preconditioning that of NormalEquationSystem.java (NES).
+//
+// One wave (one workgroup of 64 lanes) works one pair; the two linear starts, the cheirality count, every Gauss-Newton run, the
+// choice and the rejection rounds all run inside it, with no host round trip.  The layout is that of resect.hip:
+//   Sums.  Lane l takes observations l, l + 64, ... and keeps the partial sums of the pass; the lanes are combined by an xor butterfly,
+//   whose order is fixed and which leaves the same bits in every lane.  What follows is therefore wave-uniform: the sums, the
+//   candidate slots, the starts and the pair's state (b, angles, R, the tangent basis) lie in LDS, where every lane stores the same
+//   words; every lane runs the small algebra on them (Jacobi sweeps of order 9 and Cholesky of order 8 in place in LDS, Jacobi of
+//   order 3 and Cholesky of order 5 in registers), and every branch on its outcome is taken by the whole wave.  Observations are
+//   staged RELOR_CHUNK at a time in LDS as rays and ray cofactors; a pair with at most RELOR_CHUNK keeps them resident.
+//   One pass routine serves every kind of sum (space start, plane start, cheirality, step, evaluation), so that it is compiled once;
+//   its RELOR_NACC accumulators are the large per-lane state, and every index into them is a compile-time constant.
+// The small routines (solve, Jacobi of order 3) restate those of resect.hip, which keeps its own in its own translation unit.
+// Floating-point contraction is off in this file: every product and sum is rounded on its own, as tests/relorient_reference.py rounds it.
+#include <hip/hip_runtime.h>
+
+#include <float.h>
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../../include/jaicov_relorient.h"
+#include "devbuf.h"
+#include "relorient.h"
+
+#pragma clang fp contract(off)
+
+namespace jaicov {
+namespace {
+
+enum { RO_BEGIN = 0, RO_SPACE, RO_PLANE, RO_CHEIR, RO_STEP, RO_EVAL, RO_FINAL };
+
+// A value that is the same in every lane, said so to the compiler (resect.hip: rs_uniform)
+__device__ inline int ro_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ inline bool ro_uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
+
+// index of (i, j >= i) in an upper triangle of order N packed row by row
+template <int N>
+__device__ constexpr int ro_ix(int i, int j) { return i * N - i * (i - 1) / 2 + (j - i); }
+
+// A (packed upper, order N) x = b by Jacobi preconditioning (NES:82-91) and Cholesky; Q (may be NULL, packed upper): the inverse of A.
+// A is overwritten by the factor.
+template <int N>
+__device__ inline int ro_solve(double *U, const double *b, double *x, double *Q) {
+    const double EPS = ldexp(1.0, -53), SQRT_EPS = sqrt(EPS);
+    constexpr int LEN = N * (N + 1) / 2;
+    double z = 0.0;                       // NaN unless every value is finite
+#pragma unroll
+    for (int k = 0; k < LEN; k++) z += U[k] * 0.0;
+#pragma unroll
+    for (int k = 0; k < N; k++) z += b[k] * 0.0;
+    if (ro_uniform(z != 0.0)) return JAICOV_RELOR_NOT_FINITE;
+    double V[N];                          // U'U = V A V, U upper
+#pragma unroll
+    for (int i = 0; i < N; i++) V[i] = U[ro_ix<N>(i, i)] > EPS ? 1.0 / sqrt(U[ro_ix<N>(i, i)]) : 1.0;
+#pragma unroll
+    for (int i = 0; i < N; i++)
+#pragma unroll
+        for (int j = i; j < N; j++) U[ro_ix<N>(i, j)] = U[ro_ix<N>(i, j)] * (V[i] * V[j]);
+    bool singular = false;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < j; k++) s += U[ro_ix<N>(k, j)] * U[ro_ix<N>(k, j)];
+        const double p = U[ro_ix<N>(j, j)] - s;
+        singular = singular || !(p > SQRT_EPS);
+        const double d = sqrt(p);
+        U[ro_ix<N>(j, j)] = d;
+#pragma unroll
+        for (int i = j + 1; i < N; i++) {
+            double r = 0.0;
+#pragma unroll
+            for (int k = 0; k < j; k++) r += U[ro_ix<N>(k, i)] * U[ro_ix<N>(k, j)];
+            U[ro_ix<N>(j, i)] = (U[ro_ix<N>(j, i)] - r) / d;
+        }
+    }
+    if (ro_uniform(singular)) return JAICOV_RELOR_SINGULAR;       // every pivot after the first bad one is garbage and is not used
+    if (x) {
+        double y[N];
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            double r = 0.0;
+#pragma unroll
+            for (int k = 0; k < i; k++) r += U[ro_ix<N>(k, i)] * y[k];
+            y[i] = (V[i] * b[i] - r) / U[ro_ix<N>(i, i)];
+        }
+#pragma unroll
+        for (int i = N - 1; i >= 0; i--) {
+            double r = 0.0;
+#pragma unroll
+            for (int k = i + 1; k < N; k++) r += U[ro_ix<N>(i, k)] * y[k];
+            y[i] = (y[i] - r) / U[ro_ix<N>(i, i)];
+        }
+#pragma unroll
+        for (int i = 0; i < N; i++) x[i] = V[i] * y[i];
+    }
+    if (Q) {
+        double W[LEN];                    // W = inverse of U, upper: W[i][j], j >= i
+#pragma unroll
+        for (int j = 0; j < N; j++) {
+            W[ro_ix<N>(j, j)] = 1.0 / U[ro_ix<N>(j, j)];
+#pragma unroll
+            for (int i = j - 1; i >= 0; i--) {
+                double r = 0.0;
+#pragma unroll
+                for (int k = i + 1; k <= j; k++) r += U[ro_ix<N>(i, k)] * W[ro_ix<N>(k, j)];
+                W[ro_ix<N>(i, j)] = -r / U[ro_ix<N>(i, i)];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < N; i++)
+#pragma unroll
+            for (int j = i; j < N; j++) {                 // inverse of V A V = W W'
+                double r = 0.0;
+#pragma unroll
+                for (int k = j; k < N; k++) r += W[ro_ix<N>(i, k)] * W[ro_ix<N>(j, k)];
+                Q[ro_ix<N>(i, j)] = r * (V[i] * V[j]);
+            }
+    }
+    return JAICOV_RELOR_OK;
+}
+
+// The same solve for the homography (order 8), on a system held in LDS: U (packed upper, overwritten by the factor), b (overwritten
+// by x), V.  Every lane runs it on the same words and stores what every other lane stores, so it needs no barrier; its loops stay rolled.
+__device__ inline int ro_solve_lds(int n, double *U, double *b, double *V) {
+    const double EPS = ldexp(1.0, -53), SQRT_EPS = sqrt(EPS);
+    auto ix = [n](int i, int j) { return i * n - i * (i - 1) / 2 + (j - i); };
+    bool finite = true;
+    for (int k = 0; k < n * (n + 1) / 2; k++) finite = finite && isfinite(U[k]);
+    for (int k = 0; k < n; k++) finite = finite && isfinite(b[k]);
+    if (ro_uniform(!finite)) return JAICOV_RELOR_NOT_FINITE;
+    for (int i = 0; i < n; i++) V[i] = U[ix(i, i)] > EPS ? 1.0 / sqrt(U[ix(i, i)]) : 1.0;
+    for (int i = 0; i < n; i++)
+        for (int j = i; j < n; j++) U[ix(i, j)] = U[ix(i, j)] * (V[i] * V[j]);
+    for (int j = 0; j < n; j++) {
+        double s = 0.0;
+        for (int k = 0; k < j; k++) s += U[ix(k, j)] * U[ix(k, j)];
+        const double p = U[ix(j, j)] - s;
+        if (ro_uniform(!(p > SQRT_EPS))) return JAICOV_RELOR_SINGULAR;
+        const double d = sqrt(p);
+        U[ix(j, j)] = d;
+        for (int i = j + 1; i < n; i++) {
+            double r = 0.0;
+            for (int k = 0; k < j; k++) r += U[ix(k, i)] * U[ix(k, j)];
+            U[ix(j, i)] = (U[ix(j, i)] - r) / d;
+        }
+    }
+    for (int i = 0; i < n; i++) {
+        double r = 0.0;
+        for (int k = 0; k < i; k++) r += U[ix(k, i)] * b[k];
+        b[i] = (V[i] * b[i] - r) / U[ix(i, i)];
+    }
+    for (int i = n - 1; i >= 0; i--) {
+        double r = 0.0;
+        for (int k = i + 1; k < n; k++) r += U[ix(i, k)] * b[k];
+        b[i] = (b[i] - r) / U[ix(i, i)];
+    }
+    for (int i = 0; i < n; i++) b[i] = V[i] * b[i];
+    return JAICOV_RELOR_OK;
+}
+
+// the Jacobi rotation that annuls a_pq: t = tan, c = cos, s = sin of its angle
+__device__ inline void ro_angle(double app, double aqq, double apq, double &t, double &c, double &s) {
+    const double theta = (aqq - app) / (2.0 * apq);
+    t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    c = 1.0 / sqrt(t * t + 1.0);
+    s = t * c;
+}
+
+// RELOR_SWEEPS9 sweeps of cyclic Jacobi over the symmetric 9 x 9 matrix A (full, in LDS); W (in LDS, the unit matrix on entry): its rows
+// become the eigenvectors.  Every lane runs it on the same words; the loops stay rolled.
+__device__ inline void ro_jacobi9(double *A, double *W) {
+    for (int sweep = 0; sweep < RELOR_SWEEPS9; sweep++)
+        for (int p = 0; p < 8; p++)
+            for (int q = p + 1; q < 9; q++) {
+                const double apq = A[9 * p + q];
+                if (ro_uniform(apq == 0.0)) continue;
+                double t, c, s;
+                ro_angle(A[9 * p + p], A[9 * q + q], apq, t, c, s);
+                for (int k = 0; k < 9; k++) {
+                    if (k == p || k == q) continue;
+                    const double akp = A[9 * k + p], akq = A[9 * k + q];
+                    const double kp = c * akp - s * akq, kq = s * akp + c * akq;
+                    A[9 * k + p] = kp; A[9 * p + k] = kp;
+                    A[9 * k + q] = kq; A[9 * q + k] = kq;
+                }
+                A[9 * p + p] = A[9 * p + p] - t * apq;
+                A[9 * q + q] = A[9 * q + q] + t * apq;
+                A[9 * p + q] = 0.0; A[9 * q + p] = 0.0;
+                for (int k = 0; k < 9; k++) {
+                    const double wp = W[9 * p + k], wq = W[9 * q + k];
+                    W[9 * p + k] = c * wp - s * wq;
+                    W[9 * q + k] = s * wp + c * wq;
+                }
+            }
+}
+
+// one Jacobi rotation in the plane (p, q) of a symmetric 3 x 3 matrix; r is the third index; wp, wq: the eigenvector rows p and q
+__device__ inline void ro_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double *wp, double *wq) {
+    if (ro_uniform(apq == 0.0)) return;
+    double t, c, s;
+    ro_angle(app, aqq, apq, t, c, s);
+    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
+    arp = rp; arq = rq;
+    app = app - t * apq; aqq = aqq + t * apq; apq = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double vp = c * wp[k] - s * wq[k], vq = s * wp[k] + c * wq[k];
+        wp[k] = vp; wq[k] = vq;
+    }
+}
+
+// eigenvalues (falling) and eigenvectors (rows of E, det = +1) of the symmetric matrix S (00 01 02 11 12 22)
+__device__ inline void ro_eigen3(const double *S, double *lam, double *E) {
+    double a00 = S[0], a01 = S[1], a02 = S[2], a11 = S[3], a12 = S[4], a22 = S[5];
+    double W[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    for (int sweep = 0; sweep < RELOR_SWEEPS3; sweep++) {
+        ro_rotate(a00, a11, a01, a02, a12, W, W + 3);
+        ro_rotate(a00, a22, a02, a01, a12, W, W + 6);
+        ro_rotate(a11, a22, a12, a01, a02, W + 3, W + 6);
+    }
+    auto order = [&](double &la, double &lb, double *wa, double *wb) {      // the larger eigenvalue first; equal ones keep their order
+        if (ro_uniform(!(la < lb))) return;
+        const double l = la; la = lb; lb = l;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { const double w = wa[k]; wa[k] = wb[k]; wb[k] = w; }
+    };
+    order(a00, a11, W, W + 3);
+    order(a11, a22, W + 3, W + 6);
+    order(a00, a11, W, W + 3);
+    const double n0 = W[1] * W[5] - W[2] * W[4], n1 = W[2] * W[3] - W[0] * W[5], n2 = W[0] * W[4] - W[1] * W[3];   // e1 x e2
+    if (n0 * W[6] + n1 * W[7] + n2 * W[8] < 0.0) { W[6] = -W[6]; W[7] = -W[7]; W[8] = -W[8]; }
+    lam[0] = a00; lam[1] = a11; lam[2] = a22;
+#pragma unroll
+    for (int k = 0; k < 9; k++) E[k] = W[k];
+}
+
+__device__ inline void ro_cross(const double *a, const double *b, double *c) {
+    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// a candidate slot: M, b and M b
+__device__ inline void ro_slot(double *slot, const double *M, const double *b, double sign) {
+    const double bs[3] = {sign * b[0], sign * b[1], sign * b[2]};
+#pragma unroll
+    for (int k = 0; k < 9; k++) slot[k] = M[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        slot[9 + k] = bs[k];
+        slot[12 + k] = M[3 * k] * bs[0] + M[3 * k + 1] * bs[1] + M[3 * k + 2] * bs[2];
+    }
+}
+
+// where the state of a pair lies in LDS (doubles): every lane stores the same words there and reads them back
+enum { RO_PAR = 0, RO_R = 6, RO_SO = 15, RO_CO = 16, RO_E1 = 17, RO_E2 = 20, RO_NSTATE = 23 };
+
+__global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int32_t *__restrict__ obs_begin, const double *__restrict__ xy_a,
+                                                            const double *__restrict__ xy_b, const double *__restrict__ var_a,
+                                                            const double *__restrict__ var_b, const double *__restrict__ pair_io,
+                                                            const double *__restrict__ start, double s0, int max_iter, double thr2,
+                                                            int min_points, double *__restrict__ out, int32_t *__restrict__ outcome,
+                                                            uint8_t *used, double *__restrict__ obs_q) {
+    __shared__ double sua[RELOR_CHUNK], sva[RELOR_CHUNK], sub[RELOR_CHUNK], svb[RELOR_CHUNK];
+    __shared__ double sqa[3][RELOR_CHUNK], sqb[3][RELOR_CHUNK];
+    __shared__ uint8_t sused[RELOR_CHUNK];
+    __shared__ int scount[RELOR_SLOTS * RELOR_LANES];     // points in front, per slot and lane
+    // The sums of the last pass, the same in every lane after the butterfly (sA: the 9 x 9 matrix and its eigenvectors, or the
+    // homography's system, or a step's), the candidate slots (sC), the starts and the best run so far (sS, sB: b, angles, Omega) and
+    // the pair's state (sP).  The workgroup is one wave, and all of this rests on it: every lane stores the same value to the same word
+    // and reads it back, and no barrier stands between such a store and the reads that follow, because the LDS operations of one wave
+    // complete in order.
+    static_assert(RELOR_LANES == 64, "one wave per pair: the uniform state in LDS relies on it");
+    __shared__ double sA[81 + 81], sV[8], sC[RELOR_SLOTS * RELOR_SLOT_LEN], sS[RELOR_STARTS * 6], sB[7], sP[RO_NSTATE];
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const long k0 = obs_begin[g];
+    const int m = obs_begin[g + 1] - obs_begin[g];
+    double *og = out + (long)JAICOV_RELOR_OUT_PER_PAIR * g;
+    // the pair's whole-number state (counters, masks, statuses), the same in every lane.  It lies in LDS like the rest of the uniform
+    // state: held in scalar registers across the passes it cost 22 more spilled SGPRs.
+    __shared__ int sI[14];
+    int &iters = sI[0];
+    iters = 0;
+    // a failed pair: NaN in the values and in q, no observation used, start kind 0.  Taken by the whole wave.
+    auto fail = [&](int st) {
+        if (lane < JAICOV_RELOR_OUT_PER_PAIR) og[lane] = NAN;
+        if (lane == 0) { outcome[3L * g] = st; outcome[3L * g + 1] = iters; outcome[3L * g + 2] = 0; }
+        for (int t = lane; t < m; t += 64) {
+            used[k0 + t] = 0;
+            if (obs_q) obs_q[k0 + t] = NAN;
+        }
+    };
+    const double *io = pair_io + 6L * g;                   // x0, y0, c of a, then of b: read where they are used, not held
+    bool given = start != nullptr;
+#pragma unroll
+    for (int k = 0; k < 6; k++) given = given && isfinite(start[6L * g + k]);
+    const int few = given ? 5 : 6;
+    const bool resident = m <= RELOR_CHUNK;
+    // observations c0 .. c0 + nc - 1 into LDS as rays, with the cofactors of the rays (PDF:308-319 inverted, over sigma2 and c^2)
+    auto stage = [&](int c0, int nc) {
+        __syncthreads();
+        const double xa0 = io[0], ya0 = io[1], ca = io[2], xb0 = io[3], yb0 = io[4], cb = io[5];
+        const double ca2 = ca * ca, cb2 = cb * cb;
+        for (int t = lane; t < nc; t += 64) {
+            const long k = k0 + c0 + t;
+            sua[t] = -(xy_a[2 * k] - xa0) / ca; sva[t] = -(xy_a[2 * k + 1] - ya0) / ca;
+            sub[t] = -(xy_b[2 * k] - xb0) / cb; svb[t] = -(xy_b[2 * k + 1] - yb0) / cb;
+            double q11 = 1.0 / ca2, q12 = 0.0, q22 = 1.0 / ca2;
+            if (var_a) {
+                const double vx = var_a[3 * k], vy = var_a[3 * k + 1], rho = var_a[3 * k + 2];
+                q11 = vx / s0 / ca2; q22 = vy / s0 / ca2;
+                q12 = rho == 0.0 ? 0.0 : rho * sqrt(vx * vy) / s0 / ca2;
+            }
+            sqa[0][t] = q11; sqa[1][t] = q12; sqa[2][t] = q22;
+            q11 = 1.0 / cb2; q12 = 0.0; q22 = 1.0 / cb2;
+            if (var_b) {
+                const double vx = var_b[3 * k], vy = var_b[3 * k + 1], rho = var_b[3 * k + 2];
+                q11 = vx / s0 / cb2; q22 = vy / s0 / cb2;
+                q12 = rho == 0.0 ? 0.0 : rho * sqrt(vx * vy) / s0 / cb2;
+            }
+            sqb[0][t] = q11; sqb[1][t] = q12; sqb[2][t] = q22;
+            sused[t] = used[k];
+        }
+        __syncthreads();
+    };
+
+    int &mask = sI[1];                                    // the candidate slots that exist
+    mask = 0;
+    // one pass over the pair's observations: the sums of the used ones, combined over the lanes, into sA; RO_FINAL also writes q of
+    // every observation and finds the used one with the largest q (the lowest index among equal values)
+    auto pass = [&](int mode, double &qmax, int &qidx) {
+        double acc[RELOR_NACC];
+#pragma unroll
+        for (int a = 0; a < RELOR_NACC; a++) acc[a] = 0.0;
+        qmax = -1.0; qidx = INT_MAX;
+        const bool want_q = mode == RO_FINAL && obs_q;
+        if (mode == RO_CHEIR) {
+#pragma unroll 1
+            for (int s = 0; s < RELOR_SLOTS; s++) scount[64 * s + lane] = 0;
+        }
+        for (int c0 = 0; c0 < m; c0 += RELOR_CHUNK) {
+            const int nc = min(RELOR_CHUNK, m - c0);
+            if (!resident) stage(c0, nc);
+            for (int t = lane; t < nc; t += 64) {
+                const bool in = sused[t] != 0;
+                if (!in && !want_q) continue;
+                const double ua = sua[t], va = sva[t], ub = sub[t], vb = svb[t];
+                if (mode == RO_SPACE) {
+                    const double k[9] = {ub * ua, ub * va, ub, vb * ua, vb * va, vb, ua, va, 1.0};
+#pragma unroll
+                    for (int i = 0; i < 9; i++)
+#pragma unroll
+                        for (int j = i; j < 9; j++) acc[ro_ix<9>(i, j)] += k[i] * k[j];
+                } else if (mode == RO_PLANE) {
+                    const double a[8] = {ua, va, 1.0, 0.0, 0.0, 0.0, -(ub * ua), -(ub * va)};
+                    const double b[8] = {0.0, 0.0, 0.0, ua, va, 1.0, -(vb * ua), -(vb * va)};
+#pragma unroll
+                    for (int i = 0; i < 8; i++) {
+#pragma unroll
+                        for (int j = i; j < 8; j++) acc[ro_ix<8>(i, j)] += a[i] * a[j] + b[i] * b[j];
+                        acc[36 + i] += a[i] * ub + b[i] * vb;
+                    }
+                } else if (mode == RO_CHEIR) {
+                    // the slots' counts are kept per lane in LDS, not among the sums: the loop over the slots stays rolled, and a slot's
+                    // M is read where it is used instead of being held for all twelve across the loop over the observations
+                    const double bb = ub * ub + vb * vb + 1.0, ca = io[2], cb = io[5];
+#pragma unroll 1
+                    for (int s = 0; s < RELOR_SLOTS; s++) {
+                        if (!ro_uniform((mask >> s) & 1)) continue;
+                        const double *M = sC + RELOR_SLOT_LEN * s, *mb = M + 12;
+                        const double a0 = M[0] * ua + M[1] * va + M[2], a1 = M[3] * ua + M[4] * va + M[5], a2 = M[6] * ua + M[7] * va + M[8];
+                        const double aa = a0 * a0 + a1 * a1 + a2 * a2;
+                        const double ab = a0 * ub + a1 * vb + a2;
+                        const double ra = a0 * mb[0] + a1 * mb[1] + a2 * mb[2];
+                        const double rb = ub * mb[0] + vb * mb[1] + mb[2];
+                        const double det = aa * bb - ab * ab, na = ra * bb - ab * rb, nb = ab * ra - aa * rb;
+                        if (det > 0.0 && ca * na < 0.0 && cb * nb < 0.0) scount[64 * s + lane] += 1;
+                    }
+                } else {                                  // the coplanarity condition at the unknowns
+                    const double *b = sP + RO_PAR, *R = sP + RO_R, *e1 = sP + RO_E1, *e2 = sP + RO_E2;
+                    const double so = sP[RO_SO], co = sP[RO_CO];
+                    const double p0 = b[1] - b[2] * va, p1 = b[2] * ua - b[0], p2 = b[0] * va - b[1] * ua;
+                    const double r0 = R[0] * ub + R[1] * vb + R[2], r1 = R[3] * ub + R[4] * vb + R[5], r2 = R[6] * ub + R[7] * vb + R[8];
+                    const double gk = r0 * p0 + r1 * p1 + r2 * p2;
+                    const double t0 = R[0] * p0 + R[3] * p1 + R[6] * p2, t1 = R[1] * p0 + R[4] * p1 + R[7] * p2;
+                    const double g0 = r1 * b[2] - r2 * b[1], g1 = r2 * b[0] - r0 * b[2];
+                    const double qa11 = sqa[0][t], qa12 = sqa[1][t], qa22 = sqa[2][t], qb11 = sqb[0][t], qb12 = sqb[1][t], qb22 = sqb[2][t];
+                    const double cof = (g0 * (qa11 * g0 + qa12 * g1) + g1 * (qa12 * g0 + qa22 * g1)) +
+                                       (t0 * (qb11 * t0 + qb12 * t1) + t1 * (qb12 * t0 + qb22 * t1));
+                    const double pw = 1.0 / cof, pg = pw * gk, q = pg * gk;
+                    if (want_q) obs_q[k0 + c0 + t] = q;
+                    if (!in) continue;
+                    double a[5];
+                    {
+                        const double f0 = e1[1] - e1[2] * va, f1 = e1[2] * ua - e1[0], f2 = e1[0] * va - e1[1] * ua;
+                        a[0] = r0 * f0 + r1 * f1 + r2 * f2;
+                    }
+                    {
+                        const double f0 = e2[1] - e2[2] * va, f1 = e2[2] * ua - e2[0], f2 = e2[0] * va - e2[1] * ua;
+                        a[1] = r0 * f0 + r1 * f1 + r2 * f2;
+                    }
+                    a[2] = p2 * r1 - p1 * r2;
+                    a[3] = p0 * (co * r2 - so * r1) + p1 * (so * r0) - p2 * (co * r0);
+                    a[4] = ub * t1 - vb * t0;
+#pragma unroll
+                    for (int i = 0; i < 5; i++) {
+#pragma unroll
+                        for (int j = i; j < 5; j++) acc[ro_ix<5>(i, j)] += a[i] * (pw * a[j]);
+                        acc[15 + i] += -(a[i] * pg);
+                    }
+                    acc[20] += q;
+                    if (mode == RO_FINAL && q > qmax) { qmax = q; qidx = c0 + t; }
+                }
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+            for (int a = 0; a < RELOR_NACC_STEP; a++) acc[a] += __shfl_xor(acc[a], off);
+            if (mode == RO_SPACE || mode == RO_PLANE) {
+#pragma unroll
+                for (int a = RELOR_NACC_STEP; a < RELOR_NACC; a++) acc[a] += __shfl_xor(acc[a], off);
+            }
+            const double oq = __shfl_xor(qmax, off);
+            const int oi = __shfl_xor(qidx, off);
+            if (oq > qmax || (oq == qmax && oi < qidx)) { qmax = oq; qidx = oi; }
+        }
+        __syncthreads();                                  // the last reads of the state and of the sums before
+        if (mode == RO_CHEIR) {                           // whole numbers: their sum does not depend on its order
+#pragma unroll 1
+            for (int s = 0; s < RELOR_SLOTS; s++) {
+                int n = scount[64 * s + lane];
+                for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+                sA[s] = (double)n;
+            }
+        } else if (mode == RO_SPACE) {
+#pragma unroll
+            for (int i = 0; i < 9; i++)
+#pragma unroll
+                for (int j = 0; j < 9; j++) {
+                    sA[9 * i + j] = acc[i <= j ? ro_ix<9>(i, j) : ro_ix<9>(j, i)];
+                    sA[81 + 9 * i + j] = i == j ? 1.0 : 0.0;
+                }
+        } else {
+#pragma unroll
+            for (int a = 0; a < RELOR_NACC_PLANE; a++) sA[a] = acc[a];
+        }
+        __syncthreads();
+    };
+
+    const double SQRT_EPS = sqrt(ldexp(1.0, -53));
+    int &nused = sI[2], &kind = sI[3];
+    nused = m; kind = JAICOV_RELOR_START_GIVEN;
+    double qmax = -1.0;
+    int qidx = INT_MAX;
+    // the starts of the round (sS) with their kinds (2 bits each), the one that runs (cur) and its status, the best run so far (sB)
+    int &nstarts = sI[4], &kinds = sI[5], &cur = sI[6], &cst = sI[7], &it = sI[8], &bst = sI[9], &bkind = sI[10];
+    nstarts = 0; kinds = 0; cur = 0; cst = JAICOV_RELOR_NOT_CONVERGED; it = 0; bst = -1; bkind = 0;
+    int &not_finite = sI[11], &new_state = sI[12], &failed = sI[13];
+    not_finite = 0; new_state = 0;
+    failed = m < few ? JAICOV_RELOR_TOO_FEW_POINTS : -1;
+    if (ro_uniform(resident && failed < 0)) stage(0, m);
+    // one loop over the passes of all rounds, so that the pass, the rotation and the angles of a start are compiled once:
+    // BEGIN (-> SPACE) -> PLANE -> CHEIR -> [STEP ... STEP -> EVAL] per start -> FINAL (-> BEGIN of the next round)
+    int mode = RO_BEGIN;
+    while (ro_uniform(failed < 0)) {
+        mode = ro_uniform(mode);
+        if (ro_uniform(new_state != 0)) {
+            // R(omega, phi, kappa), PDF:125-135: lanes 0, 1, 2 take the sine and cosine of one angle each (one copy of sincos)
+            const double angle = lane == 0 ? sP[RO_PAR + 3] : lane == 1 ? sP[RO_PAR + 4] : sP[RO_PAR + 5];
+            double sn, cs;
+            sincos(angle, &sn, &cs);
+            const double so = __shfl(sn, 0), co = __shfl(cs, 0), sp = __shfl(sn, 1), cp = __shfl(cs, 1), sk = __shfl(sn, 2), ck = __shfl(cs, 2);
+            double *R = sP + RO_R;
+            R[0] = cp * ck;                 R[1] = -cp * sk;                R[2] = sp;
+            R[3] = co * sk + so * sp * ck;  R[4] = co * ck - so * sp * sk;  R[5] = -so * cp;
+            R[6] = so * sk - co * sp * ck;  R[7] = so * ck + co * sp * sk;  R[8] = co * cp;
+            sP[RO_SO] = so; sP[RO_CO] = co;
+            // the tangent basis at b
+            const double b[3] = {sP[RO_PAR], sP[RO_PAR + 1], sP[RO_PAR + 2]};
+            int ax = 0;
+            if (fabs(b[1]) < fabs(b[0])) ax = 1;
+            if (fabs(b[2]) < fabs(ax == 0 ? b[0] : b[1])) ax = 2;
+            ax = ro_uniform(ax);
+            const double e[3] = {ax == 0 ? 1.0 : 0.0, ax == 1 ? 1.0 : 0.0, ax == 2 ? 1.0 : 0.0};
+            double f[3], e1[3], e2[3];
+            ro_cross(b, e, f);
+            const double ln = sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+#pragma unroll
+            for (int k = 0; k < 3; k++) e1[k] = f[k] / ln;
+            ro_cross(b, e1, e2);
+#pragma unroll
+            for (int k = 0; k < 3; k++) { sP[RO_E1 + k] = e1[k]; sP[RO_E2 + k] = e2[k]; }
+            new_state = 0;
+        }
+        if (mode != RO_BEGIN) pass(mode, qmax, qidx);
+        bool advance = false;                             // the running start is done: the next one, or the choice
+        if (mode == RO_BEGIN) {
+            nstarts = 0; kinds = 0; cur = 0; bst = -1; not_finite = 0; mask = 0;
+            if (ro_uniform(nused < few)) {
+                failed = JAICOV_RELOR_TOO_FEW_POINTS;
+            } else if (given) {
+                const double *s = start + 6L * g;
+                const double ln = sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+#pragma unroll
+                for (int k = 0; k < 3; k++) { sP[RO_PAR + k] = s[k] / ln; sP[RO_PAR + 3 + k] = s[3 + k]; }
+                nstarts = 1; kinds = JAICOV_RELOR_START_GIVEN;
+                new_state = 1; cst = JAICOV_RELOR_NOT_CONVERGED; it = 0;
+                mode = RO_STEP;
+            } else {
+                mode = ro_uniform(nused >= 8) ? RO_SPACE : RO_PLANE;
+            }
+        } else if (mode == RO_SPACE) {
+            mode = RO_PLANE;
+            bool finite = true;
+            for (int k = 0; k < 81; k++) finite = finite && isfinite(sA[k]);
+            if (ro_uniform(!finite)) {
+                not_finite = 1;
+            } else {
+                ro_jacobi9(sA, sA + 81);
+                int i0 = 0;
+                for (int i = 1; i < 9; i++)
+                    if (sA[10 * i] < sA[10 * i0]) i0 = i;
+                i0 = ro_uniform(i0);
+                double l1 = INFINITY, lmax = sA[10 * i0];
+                for (int i = 0; i < 9; i++) {
+                    const double l = sA[10 * i];
+                    if (i != i0 && l < l1) l1 = l;
+                    if (l > lmax) lmax = l;
+                }
+                if (ro_uniform(l1 > SQRT_EPS * lmax)) {
+                    const double r2 = sqrt(2.0);
+                    double E[9], S[6], lam[3], V[9], C[9], D[9], Mp[9], Mm[9];
+#pragma unroll
+                    for (int k = 0; k < 9; k++) E[k] = sA[81 + 9 * i0 + k] * r2;
+                    S[0] = E[0] * E[0] + E[3] * E[3] + E[6] * E[6]; S[1] = E[0] * E[1] + E[3] * E[4] + E[6] * E[7];
+                    S[2] = E[0] * E[2] + E[3] * E[5] + E[6] * E[8]; S[3] = E[1] * E[1] + E[4] * E[4] + E[7] * E[7];
+                    S[4] = E[1] * E[2] + E[4] * E[5] + E[7] * E[8]; S[5] = E[2] * E[2] + E[5] * E[5] + E[8] * E[8];
+                    ro_eigen3(S, lam, V);
+                    const double *n = V + 6;
+                    ro_cross(E + 3, E + 6, C); ro_cross(E + 6, E, C + 3); ro_cross(E, E + 3, C + 6);
+                    ro_cross(E, n, D); ro_cross(E + 3, n, D + 3); ro_cross(E + 6, n, D + 6);
+#pragma unroll
+                    for (int k = 0; k < 9; k++) { Mp[k] = C[k] - D[k]; Mm[k] = C[k] + D[k]; }
+                    ro_slot(sC, Mp, n, 1.0); ro_slot(sC + RELOR_SLOT_LEN, Mp, n, -1.0);
+                    ro_slot(sC + 2 * RELOR_SLOT_LEN, Mm, n, 1.0); ro_slot(sC + 3 * RELOR_SLOT_LEN, Mm, n, -1.0);
+                    mask |= 0xF;
+                }
+            }
+        } else if (mode == RO_PLANE) {
+            const int ps = ro_solve_lds(8, sA, sA + 36, sV);
+            if (ps == JAICOV_RELOR_NOT_FINITE) not_finite = 1;
+            if (ps == JAICOV_RELOR_OK) {
+                const double *h = sA + 36;
+                double H[9] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], 1.0}, S[6], lam[3], V[9];
+                S[0] = H[0] * H[0] + H[3] * H[3] + H[6] * H[6]; S[1] = H[0] * H[1] + H[3] * H[4] + H[6] * H[7];
+                S[2] = H[0] * H[2] + H[3] * H[5] + H[6] * H[8]; S[3] = H[1] * H[1] + H[4] * H[4] + H[7] * H[7];
+                S[4] = H[1] * H[2] + H[4] * H[5] + H[7] * H[8]; S[5] = H[2] * H[2] + H[5] * H[5] + H[8] * H[8];
+                ro_eigen3(S, lam, V);
+                const double l1 = lam[0] / lam[1], l3 = lam[2] / lam[1];
+                if (ro_uniform(lam[1] > 0.0 && l1 - l3 > SQRT_EPS)) {
+                    const double f = sqrt(lam[1]);
+#pragma unroll
+                    for (int k = 0; k < 9; k++) H[k] = H[k] / f;
+                    const double wa = sqrt(fmax(1.0 - l3, 0.0)), wc = sqrt(fmax(l1 - 1.0, 0.0)), den = sqrt(l1 - l3);
+                    const double *v1 = V, *v2 = V + 3, *v3 = V + 6;
+#pragma unroll 1
+                    for (int is = 0; is < 2; is++) {
+                        const double s = is == 0 ? 1.0 : -1.0;
+                        double u[3], nr[3], h2[3], hu[3], hn[3];
+#pragma unroll
+                        for (int k = 0; k < 3; k++) u[k] = (wa * v1[k] + s * (wc * v3[k])) / den;
+                        ro_cross(v2, u, nr);
+#pragma unroll
+                        for (int i = 0; i < 3; i++) {
+                            h2[i] = H[3 * i] * v2[0] + H[3 * i + 1] * v2[1] + H[3 * i + 2] * v2[2];
+                            hu[i] = H[3 * i] * u[0] + H[3 * i + 1] * u[1] + H[3 * i + 2] * u[2];
+                            hn[i] = H[3 * i] * nr[0] + H[3 * i + 1] * nr[1] + H[3 * i + 2] * nr[2];
+                        }
+#pragma unroll 1
+                        for (int ig = 0; ig < 2; ig++) {
+                            const double sg = ig == 0 ? 1.0 : -1.0;
+                            const double w1[3] = {sg * h2[0], sg * h2[1], sg * h2[2]}, w2[3] = {sg * hu[0], sg * hu[1], sg * hu[2]};
+                            double w3[3], M[9], t[3], bd[3];
+                            ro_cross(w1, w2, w3);
+#pragma unroll
+                            for (int i = 0; i < 3; i++) {
+#pragma unroll
+                                for (int j = 0; j < 3; j++) M[3 * i + j] = w1[i] * v2[j] + w2[i] * u[j] + w3[i] * nr[j];
+                                t[i] = sg * hn[i] - w3[i];
+                            }
+#pragma unroll
+                            for (int k = 0; k < 3; k++) bd[k] = -(M[k] * t[0] + M[3 + k] * t[1] + M[6 + k] * t[2]);
+                            const double ln = sqrt(bd[0] * bd[0] + bd[1] * bd[1] + bd[2] * bd[2]);
+                            if (ro_uniform(!(ln > 0.0))) continue;
+#pragma unroll
+                            for (int k = 0; k < 3; k++) bd[k] = bd[k] / ln;
+                            const int slot = 4 + 4 * is + 2 * ig;
+                            ro_slot(sC + RELOR_SLOT_LEN * slot, M, bd, 1.0);
+                            ro_slot(sC + RELOR_SLOT_LEN * (slot + 1), M, bd, -1.0);
+                            mask |= 3 << slot;
+                        }
+                    }
+                }
+            }
+            if (ro_uniform(mask == 0)) failed = ro_uniform(not_finite != 0) ? JAICOV_RELOR_NOT_FINITE : JAICOV_RELOR_SINGULAR;
+            else mode = RO_CHEIR;
+        } else if (mode == RO_CHEIR) {
+            // the slots that go on, 4 bits each: the best of the space start, the (at most two) best of the plane start
+            int picks = 0, space = -1, plane = -1;
+            for (int s = 0; s < 4; s++)
+                if (((mask >> s) & 1) && (space < 0 || sA[s] > sA[space])) space = s;
+            for (int s = 4; s < RELOR_SLOTS; s++)
+                if (((mask >> s) & 1) && (plane < 0 || sA[s] > sA[plane])) plane = s;
+            space = ro_uniform(space); plane = ro_uniform(plane);
+            if (space >= 0) { picks |= space << (4 * nstarts); kinds |= JAICOV_RELOR_START_SPACE << (2 * nstarts); nstarts++; }
+            if (plane >= 0) {
+                int taken = 0;
+                for (int s = plane; s < RELOR_SLOTS && taken < 2; s++)
+                    if (ro_uniform(((mask >> s) & 1) && sA[s] == sA[plane])) {
+                        picks |= s << (4 * nstarts); kinds |= JAICOV_RELOR_START_PLANE << (2 * nstarts); nstarts++; taken++;
+                    }
+            }
+            nstarts = ro_uniform(nstarts); picks = ro_uniform(picks); kinds = ro_uniform(kinds);
+#pragma unroll 1
+            for (int j = 0; j < ro_uniform(nstarts); j++) {
+                // b and the angles of R = M' (omega by lane 0, kappa by lane 1: one copy of atan2)
+                const double *M = sC + RELOR_SLOT_LEN * ((picks >> (4 * j)) & 15);
+                const double a = atan2(lane == 0 ? -M[7] : -M[3], lane == 0 ? M[8] : M[0]);
+                double *par = sS + 6 * j;
+                par[0] = M[9]; par[1] = M[10]; par[2] = M[11];
+                par[3] = __shfl(a, 0);
+                par[4] = asin(fmin(1.0, fmax(-1.0, M[6])));
+                par[5] = __shfl(a, 1);
+            }
+#pragma unroll
+            for (int k = 0; k < 6; k++) sP[RO_PAR + k] = sS[k];
+            new_state = 1; cst = JAICOV_RELOR_NOT_CONVERGED; it = 0; cur = 0;
+            mode = RO_STEP;
+        } else if (mode == RO_STEP) {
+            double A[15], b[5], dx[5];
+#pragma unroll
+            for (int k = 0; k < 15; k++) A[k] = sA[k];
+#pragma unroll
+            for (int k = 0; k < 5; k++) b[k] = sA[15 + k];
+            int ss = ro_solve<5>(A, b, dx, nullptr);
+            iters++;
+            if (ss == JAICOV_RELOR_OK) {
+                double z = 0.0;                           // NaN unless every value is finite
+#pragma unroll
+                for (int k = 0; k < 5; k++) z += dx[k] * 0.0;
+                if (ro_uniform(z != 0.0)) ss = JAICOV_RELOR_NOT_FINITE;
+            }
+            if (ss != JAICOV_RELOR_OK) {
+                if (ss == JAICOV_RELOR_NOT_FINITE) not_finite = 1;
+                advance = true;
+            } else {
+                double bn[3], step = 0.0;
+#pragma unroll
+                for (int k = 0; k < 3; k++) bn[k] = sP[RO_PAR + k] + (dx[0] * sP[RO_E1 + k] + dx[1] * sP[RO_E2 + k]);
+                const double ln = sqrt(bn[0] * bn[0] + bn[1] * bn[1] + bn[2] * bn[2]);
+#pragma unroll
+                for (int k = 0; k < 3; k++) { sP[RO_PAR + k] = bn[k] / ln; sP[RO_PAR + 3 + k] = sP[RO_PAR + 3 + k] + dx[2 + k]; }
+#pragma unroll
+                for (int k = 0; k < 5; k++) step = fmax(step, fabs(dx[k]));
+                new_state = 1;
+                if (ro_uniform(step <= SQRT_EPS)) { cst = JAICOV_RELOR_OK; mode = RO_EVAL; }
+                else if (ro_uniform(++it >= max_iter)) mode = RO_EVAL;
+            }
+        } else if (mode == RO_EVAL) {
+            const double omega = sA[20];
+            if (ro_uniform(!isfinite(omega))) {
+                not_finite = 1;
+            } else if (ro_uniform(bst < 0 || cst < bst || (cst == bst && omega < sB[6] - SQRT_EPS * sB[6]))) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) sB[k] = sP[RO_PAR + k];
+                sB[6] = omega;
+                bst = cst; bkind = (kinds >> (2 * cur)) & 3;
+            }
+            advance = true;
+        } else {                                          // RO_FINAL: Q is taken from these sums after the loop
+            if (ro_uniform(thr2 > 0.0 && nused > min_points && qmax > thr2 && qidx < m)) {
+                if (lane == 0) { used[k0 + qidx] = 0; if (resident) sused[qidx] = 0; }
+                __syncthreads();                          // the withdrawal is visible to every lane before the next pass reads it
+                nused--;
+                mode = RO_BEGIN;
+            } else {
+                break;
+            }
+        }
+        if (advance) {
+            cur++;
+            if (ro_uniform(cur < nstarts)) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) sP[RO_PAR + k] = sS[6 * cur + k];
+                new_state = 1; cst = JAICOV_RELOR_NOT_CONVERGED; it = 0;
+                mode = RO_STEP;
+            } else if (ro_uniform(bst < 0)) {
+                failed = ro_uniform(not_finite != 0) ? JAICOV_RELOR_NOT_FINITE : JAICOV_RELOR_SINGULAR;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 6; k++) sP[RO_PAR + k] = sB[k];
+                new_state = 1; kind = bkind;
+                mode = RO_FINAL;
+            }
+        }
+    }
+    double o[JAICOV_RELOR_OUT_PER_PAIR];
+    if (ro_uniform(failed < 0)) {
+        double A[15], b[5], Q[15];
+#pragma unroll
+        for (int k = 0; k < 15; k++) A[k] = sA[k];
+#pragma unroll
+        for (int k = 0; k < 5; k++) b[k] = sA[15 + k];
+        const int se = ro_solve<5>(A, b, nullptr, Q);
+        if (se != JAICOV_RELOR_OK) failed = se;
+        const double *e1 = sP + RO_E1, *e2 = sP + RO_E2;
+#pragma unroll
+        for (int k = 0; k < 6; k++) o[k] = sP[RO_PAR + k];
+#pragma unroll
+        for (int i = 0; i < 6; i++)                       // J Q5 J', J = [e1 e2 0; 0 0 I3]
+#pragma unroll
+            for (int j = i; j < 6; j++) {
+                double v;
+                if (i < 3 && j < 3) {
+                    const double t0 = e1[i] * Q[ro_ix<5>(0, 0)] + e2[i] * Q[ro_ix<5>(0, 1)];
+                    const double t1 = e1[i] * Q[ro_ix<5>(0, 1)] + e2[i] * Q[ro_ix<5>(1, 1)];
+                    v = t0 * e1[j] + t1 * e2[j];
+                } else if (i < 3) {
+                    v = e1[i] * Q[ro_ix<5>(0, j - 1)] + e2[i] * Q[ro_ix<5>(1, j - 1)];
+                } else {
+                    v = Q[ro_ix<5>(i - 1, j - 1)];
+                }
+                o[6 + ro_ix<6>(i, j)] = v;
+            }
+        o[27] = sA[20];
+        double z = 0.0;
+#pragma unroll
+        for (int k = 0; k < JAICOV_RELOR_OUT_PER_PAIR; k++) z += o[k] * 0.0;
+        if (ro_uniform(failed < 0 && z != 0.0)) failed = JAICOV_RELOR_NOT_FINITE;
+    }
+    if (ro_uniform(failed >= 0)) { fail(ro_uniform(failed)); return; }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < JAICOV_RELOR_OUT_PER_PAIR; k++) og[k] = o[k];
+        outcome[3L * g] = bst;
+        outcome[3L * g + 1] = iters;
+        outcome[3L * g + 2] = kind;
+    }
+}
+
+bool relor_device_ok() {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return false;
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
+    return strncmp(prop.gcnArchName, "gfx950", 6) == 0;
+}
+
+}  // namespace
+}  // namespace jaicov
+
+using namespace jaicov;
+
+extern "C" int jaicov_relorient_pairs(int32_t n_pairs, const int32_t *obs_begin, const double *xy_a, const double *xy_b, const double *var_a,
+                                      const double *var_b, const double *pair_io, const double *start, double sigma2apriori,
+                                      int32_t max_iterations, double reject_threshold, int32_t min_points, double *out, int32_t *status,
+                                      int32_t *iterations, int32_t *start_kind, uint8_t *obs_used, double *obs_q, double *ms_out) {
+    // argument checks, host only
+    if (n_pairs < 0 || !obs_begin) return JAICOV_ERR_BAD_ARGUMENT;
+    if (!(sigma2apriori > 0.0) || max_iterations < 1 || min_points < 5 || !(reject_threshold >= 0.0)) return JAICOV_ERR_BAD_ARGUMENT;
+    if (n_pairs > 0 && (!out || !status || !pair_io)) return JAICOV_ERR_BAD_ARGUMENT;
+    if (obs_begin[0] != 0) return JAICOV_ERR_BAD_ARGUMENT;
+    for (int32_t g = 0; g < n_pairs; g++)
+        if (obs_begin[g + 1] < obs_begin[g]) return JAICOV_ERR_BAD_ARGUMENT;
+    const long n_obs = obs_begin[n_pairs];
+    if (n_obs > 0 && (!xy_a || !xy_b)) return JAICOV_ERR_BAD_ARGUMENT;
+    for (const double *var : {var_a, var_b})
+        if (var)
+            for (long k = 0; k < n_obs; k++)
+                if (!(var[3 * k] > 0.0) || !(var[3 * k + 1] > 0.0) || !(fabs(var[3 * k + 2]) < 1.0)) return JAICOV_ERR_BAD_ARGUMENT;
+
+    if (!relor_device_ok()) return JAICOV_ERR_NO_DEVICE;
+    if (ms_out) *ms_out = 0.0;
+    if (n_pairs == 0) return JAICOV_OK;
+
+    hipStream_t s;
+    if (hipStreamCreate(&s) != hipSuccess) return JAICOV_ERR_DEVICE;
+    const int rc = [&]() -> int {      // the owners go before the stream does
+        int32_t *d_begin = nullptr, *d_outcome = nullptr;
+        double *d_xa = nullptr, *d_xb = nullptr, *d_va = nullptr, *d_vb = nullptr, *d_io = nullptr, *d_start = nullptr, *d_out = nullptr,
+               *d_q = nullptr;
+        uint8_t *d_used = nullptr;
+        DevBag bag;
+        DevEvent ev0, ev1;
+        if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+        const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
+        const size_t np = (size_t)n_pairs, no = (size_t)(n_obs > 0 ? n_obs : 1);
+        std::vector<int32_t> h_outcome(3 * np);
+        if (bag.alloc(&d_begin, np + 1) != hipSuccess || bag.alloc(&d_xa, 2 * no) != hipSuccess || bag.alloc(&d_xb, 2 * no) != hipSuccess ||
+            (var_a && bag.alloc(&d_va, 3 * no) != hipSuccess) || (var_b && bag.alloc(&d_vb, 3 * no) != hipSuccess) ||
+            bag.alloc(&d_io, 6 * np) != hipSuccess || (start && bag.alloc(&d_start, 6 * np) != hipSuccess) ||
+            bag.alloc(&d_out, JAICOV_RELOR_OUT_PER_PAIR * np) != hipSuccess || bag.alloc(&d_outcome, 3 * np) != hipSuccess ||
+            bag.alloc(&d_used, no) != hipSuccess || (obs_q && bag.alloc(&d_q, no) != hipSuccess))
+            return JAICOV_ERR_OUT_OF_MEMORY;
+        hipMemcpyAsync(d_begin, obs_begin, (np + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
+        if (n_obs > 0) {
+            hipMemcpyAsync(d_xa, xy_a, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+            hipMemcpyAsync(d_xb, xy_b, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+            if (var_a) hipMemcpyAsync(d_va, var_a, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+            if (var_b) hipMemcpyAsync(d_vb, var_b, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+        }
+        hipMemcpyAsync(d_io, pair_io, 6 * np * sizeof(double), hipMemcpyHostToDevice, s);
+        if (start) hipMemcpyAsync(d_start, start, 6 * np * sizeof(double), hipMemcpyHostToDevice, s);
+        hipMemsetAsync(d_used, 1, no, s);                                  // every observation starts as used
+        hipEventRecord(e0, s);
+        hipLaunchKernelGGL(relorient_pairs_kernel, dim3(n_pairs), dim3(RELOR_LANES), 0, s, d_begin, d_xa, d_xb, d_va, d_vb, d_io, d_start,
+                           sigma2apriori, (int)max_iterations, reject_threshold * reject_threshold, (int)min_points, d_out, d_outcome, d_used,
+                           d_q);
+        if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
+        hipEventRecord(e1, s);
+        hipMemcpyAsync(out, d_out, JAICOV_RELOR_OUT_PER_PAIR * np * sizeof(double), hipMemcpyDeviceToHost, s);
+        hipMemcpyAsync(h_outcome.data(), d_outcome, 3 * np * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        if (obs_used && n_obs > 0) hipMemcpyAsync(obs_used, d_used, (size_t)n_obs, hipMemcpyDeviceToHost, s);
+        if (obs_q && n_obs > 0) hipMemcpyAsync(obs_q, d_q, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost, s);
+        if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
+        for (size_t g = 0; g < np; g++) {
+            status[g] = h_outcome[3 * g];
+            if (iterations) iterations[g] = h_outcome[3 * g + 1];
+            if (start_kind) start_kind[g] = h_outcome[3 * g + 2];
+        }
+        if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
+        return JAICOV_OK;
+    }();
+    hipStreamDestroy(s);
+    return rc;
+}

@@ -1,6 +1,7 @@
 """ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` / ``include/jaicov_transform.h`` /
 ``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_reliability_points.h`` /
-``include/jaicov_datum.h`` / ``include/jaicov_intersect.h`` / ``include/jaicov_resect.h``
+``include/jaicov_datum.h`` / ``include/jaicov_intersect.h`` / ``include/jaicov_resect.h`` /
+``include/jaicov_relorient.h``
 (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
@@ -61,6 +62,10 @@ ISECT_OK, ISECT_NOT_CONVERGED, ISECT_TOO_FEW_RAYS, ISECT_SINGULAR, ISECT_NOT_FIN
 RESECT_EXPORTS = ["jaicov_resect_images"]
 RESECT_OK, RESECT_NOT_CONVERGED, RESECT_TOO_FEW_POINTS, RESECT_SINGULAR, RESECT_NOT_FINITE = range(5)
 RESECT_START_GIVEN, RESECT_START_SPACE, RESECT_START_PLANE = range(3)
+# include/jaicov_relorient.h: relative orientation of a batch of image pairs from their common image points (stand-alone, no engine)
+RELOR_EXPORTS = ["jaicov_relorient_pairs"]
+RELOR_OK, RELOR_NOT_CONVERGED, RELOR_TOO_FEW_POINTS, RELOR_SINGULAR, RELOR_NOT_FINITE = range(5)
+RELOR_START_GIVEN, RELOR_START_SPACE, RELOR_START_PLANE = range(3)
 
 KROW = 32  # 12 + JAICOV_MAX_DIST_PER_CAMERA
 INVERT_NONE, INVERT_FULL, INVERT_REDUCED = 0, 1, 2   # MatrixInversion (BundleAdjustment.java:65-70)
@@ -173,6 +178,8 @@ def load_library():
                                       _pd, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
     L.jaicov_resect_images.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, _pd, _pd, C.c_double, C.c_int32, C.c_double, C.c_int32,
                                        _pd, _pi, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
+    L.jaicov_relorient_pairs.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, _pd, _pd, _pd, C.c_double, C.c_int32, C.c_double, C.c_int32,
+                                         _pd, _pi, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
     _LIB = L
     return L
 
@@ -634,6 +641,66 @@ def resect_problem(fp: FlatProblem, values=None, with_status=False, **kw):
     ok = status <= RESECT_NOT_CONVERGED
     v[fp.slot_eo(0):].reshape(-1, 6)[ok] = out[ok, :6]
     return (v, out, status) if with_status else v
+
+
+def relorient_pairs(obs_begin, xy_a, xy_b, var_a, var_b, pair_io, start=None, sigma2apriori=1.0, max_iterations=50, reject_threshold=0.0,
+                    min_points=6, with_time=False):
+    """Relative orientation of every image pair of a batch from its common image points (include/jaicov_relorient.h).  obs_begin:
+    (n + 1,) CSR offsets of the pairs' observations; xy_a, xy_b: (n_obs, 2) the image point of observation k in image a and in image
+    b; var_a, var_b: (n_obs, 3) var_x, var_y, rho or None; pair_io: (n, 6) x0, y0, c of image a's camera, then of image b's; start:
+    (n, 6) or None, a pair whose six values are all finite starts from them, any other from the linear starts.  Returns (out (n, 28):
+    X0, Y0, Z0 (unit length), omega, phi, kappa of image b in the frame of image a, the 21 entries of the upper triangle of their
+    cofactor matrix, Omega; status (n,); iterations (n,); start_kind (n,); obs_used (n_obs,); obs_q (n_obs,)), plus the kernel time
+    in ms with with_time."""
+    L = load_library()
+    ob = np.ascontiguousarray(obs_begin, np.int32).ravel()
+    n = ob.size - 1
+    xa = np.ascontiguousarray(xy_a, np.float64).reshape(-1)
+    xb = np.ascontiguousarray(xy_b, np.float64).reshape(-1)
+    va = None if var_a is None else np.ascontiguousarray(var_a, np.float64).reshape(-1)
+    vb = None if var_b is None else np.ascontiguousarray(var_b, np.float64).reshape(-1)
+    io = np.ascontiguousarray(pair_io, np.float64).reshape(-1)
+    st = None if start is None else np.ascontiguousarray(start, np.float64).reshape(-1)
+    n_obs = xa.size // 2
+    if xa.size % 2 or xb.size != xa.size or (va is not None and va.size != 3 * n_obs) or (vb is not None and vb.size != 3 * n_obs) or \
+            io.size != 6 * max(n, 0) or (st is not None and st.size != 6 * max(n, 0)) or (ob.size and ob[-1] != n_obs):
+        raise EngineError(-1, "relorient pairs: array sizes do not agree")
+    out = np.zeros((max(n, 0), 28)); status = np.zeros(max(n, 0), np.int32); iterations = np.zeros(max(n, 0), np.int32)
+    kind = np.zeros(max(n, 0), np.int32); used = np.zeros(n_obs, np.uint8); q = np.zeros(n_obs)
+    ms = np.zeros(1)
+    null = C.cast(None, _pd)
+    rc = L.jaicov_relorient_pairs(n, ob.ctypes.data_as(_pi), _p(xa), _p(xb), _p(va) if va is not None else null,
+                                  _p(vb) if vb is not None else null, _p(io), _p(st) if st is not None else null, float(sigma2apriori),
+                                  int(max_iterations), float(reject_threshold), int(min_points), _p(out), status.ctypes.data_as(_pi),
+                                  iterations.ctypes.data_as(_pi), kind.ctypes.data_as(_pi), used.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                  _p(q), _p(ms))
+    if rc != 0:
+        raise EngineError(rc, "relorient pairs")
+    return (out, status, iterations, kind, used, q) + ((float(ms[0]),) if with_time else ())
+
+
+def relorient_problem(fp: FlatProblem, image_a, image_b, base_length=1.0, values=None, with_status=False, **kw):
+    """Start values of two exterior orientations of a FlatProblem by relative orientation: the observations are the image points of the
+    object points both images see, in rising point number, with their ip_var_x, ip_var_y, ip_rho; the interior orientations come from
+    the slot vector `values` (default fp.values).  Returns the slot vector with image a at the origin with zero angles and image b at
+    the result, its X0 times base_length (a pair whose status is TOO_FEW_POINTS, SINGULAR or NOT_FINITE keeps both images' values);
+    with_status also (out (28,), status).  kw: as relorient_pairs (sigma2apriori defaults to the problem's)."""
+    v = np.array(fp.values if values is None else values, np.float64)
+    img, pt = np.asarray(fp.ip_image), np.asarray(fp.ip_point)
+    ia, ib = np.flatnonzero(img == image_a), np.flatnonzero(img == image_b)
+    _, ja, jb = np.intersect1d(pt[ia], pt[ib], return_indices=True)
+    ia, ib = ia[ja], ib[jb]
+    cam = v[3 * fp.n_points:3 * fp.n_points + 3 * fp.n_cameras].reshape(-1, 3)[fp.image_camera]
+    xy = np.stack([fp.ip_x, fp.ip_y], 1)
+    var = np.stack([fp.ip_var_x, fp.ip_var_y, fp.ip_rho], 1)
+    kw.setdefault("sigma2apriori", fp.sigma2apriori)
+    out, status = relorient_pairs([0, ia.size], xy[ia], xy[ib], var[ia], var[ib], np.concatenate([cam[image_a], cam[image_b]]), **kw)[:2]
+    if status[0] <= RELOR_NOT_CONVERGED:
+        eo = v[fp.slot_eo(0):].reshape(-1, 6)
+        eo[image_a] = 0.0
+        eo[image_b, :3] = base_length * out[0, :3]
+        eo[image_b, 3:] = out[0, 3:6]
+    return (v, out[0], int(status[0])) if with_status else v
 
 
 def dense_gemm(alay, blay, A, B, C_in, M, N, K, alpha=1.0, beta=0.0, lower_only=False, kmode=0, repeats=0):

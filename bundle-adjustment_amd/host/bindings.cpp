@@ -278,6 +278,21 @@ PYBIND11_MODULE(_jaicov_host, m) {
                       py::arg("sigma2apriori") = 1.0, py::arg("rejectThreshold") = 0.0, py::arg("minPoints") = 4)
         .def_static("getMaximalNumberOfIterations", &SpatialResection::getMaximalNumberOfIterations)
         .def_static("setMaximalNumberOfIterations", &SpatialResection::setMaximalNumberOfIterations);
+    py::class_<RelativeOrientation> relor(m, "RelativeOrientation");
+    py::class_<RelativeOrientation::Result>(relor, "Result")
+        .def_property_readonly("a", [](RelativeOrientation::Result &r) { return r.a; }, py::return_value_policy::reference)
+        .def_property_readonly("b", [](RelativeOrientation::Result &r) { return r.b; }, py::return_value_policy::reference)
+        .def_readonly("status", &RelativeOrientation::Result::status)
+        .def_readonly("iterations", &RelativeOrientation::Result::iterations)
+        .def_readonly("startKind", &RelativeOrientation::Result::startKind)
+        .def_readonly("points", &RelativeOrientation::Result::points)
+        .def_readonly("pointsUsed", &RelativeOrientation::Result::pointsUsed)
+        .def("values", [](RelativeOrientation::Result &r) { return std::vector<double>(r.values, r.values + JAICOV_RELOR_OUT_PER_PAIR); });
+    relor.def_static("orientAll", &RelativeOrientation::orientAll, py::arg("pairs"), py::arg("fromCurrentValues") = false,
+                     py::arg("sigma2apriori") = 1.0, py::arg("rejectThreshold") = 0.0, py::arg("minPoints") = 6)
+        .def_static("apply", &RelativeOrientation::apply, py::arg("result"), py::arg("baseLength") = 1.0)
+        .def_static("getMaximalNumberOfIterations", &RelativeOrientation::getMaximalNumberOfIterations)
+        .def_static("setMaximalNumberOfIterations", &RelativeOrientation::setMaximalNumberOfIterations);
 
     py::class_<AiconProject>(m, "AiconProject")
         .def_property_readonly("camera", [](AiconProject &p) { return p.camera ? p.camera.get() : (p.cameras.empty() ? nullptr : p.cameras[0].get()); },

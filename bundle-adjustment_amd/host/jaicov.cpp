@@ -755,4 +755,83 @@ std::vector<SpatialResection::Result> SpatialResection::resectAll(const std::vec
     return res;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// RelativeOrientation (include/jaicov_relorient.h) on the device
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+// R(omega, phi, kappa), PDF:125-135, row-major
+void rotationOf(const double *a, double *R) {
+    const double so = std::sin(a[0]), co = std::cos(a[0]), sp = std::sin(a[1]), cp = std::cos(a[1]), sk = std::sin(a[2]), ck = std::cos(a[2]);
+    R[0] = cp * ck;                 R[1] = -cp * sk;                R[2] = sp;
+    R[3] = co * sk + so * sp * ck;  R[4] = co * ck - so * sp * sk;  R[5] = -so * cp;
+    R[6] = so * sk - co * sp * ck;  R[7] = so * ck + co * sp * sk;  R[8] = co * cp;
+}
+}  // namespace
+
+std::vector<RelativeOrientation::Result> RelativeOrientation::orientAll(const std::vector<std::pair<Image *, Image *>> &pairs,
+                                                                        bool fromCurrentValues, double sigma2apriori, double rejectThreshold,
+                                                                        int minPoints) {
+    std::vector<int32_t> begin(1, 0);
+    std::vector<double> xa, xb, va, vb, io, start;
+    for (const auto &pr : pairs) {
+        std::unordered_map<ObjectCoordinate *, ImageCoordinate *> inB;
+        for (auto &ic : pr.second->coordinates()) inB.emplace(ic->getObjectCoordinate(), ic.get());
+        for (auto &ic : pr.first->coordinates()) {
+            auto it = inB.find(ic->getObjectCoordinate());
+            if (it == inB.end()) continue;
+            ImageCoordinate *jc = it->second;
+            xa.push_back(ic->getX().getValue()); xa.push_back(ic->getY().getValue());
+            xb.push_back(jc->getX().getValue()); xb.push_back(jc->getY().getValue());
+            va.push_back(ic->getX().getVariance()); va.push_back(ic->getY().getVariance()); va.push_back(ic->getCorrelationCoefficientXY());
+            vb.push_back(jc->getX().getVariance()); vb.push_back(jc->getY().getVariance()); vb.push_back(jc->getCorrelationCoefficientXY());
+        }
+        begin.push_back((int32_t)(xa.size() / 2));
+        double ea[6], eb[6], Ra[9], Rb[9];
+        for (Image *im : {pr.first, pr.second})
+            for (int k = 0; k < 3; k++) io.push_back(im->getReference()->getInteriorOrientation().at(k)->getValue());
+        for (int k = 0; k < 6; k++) {
+            ea[k] = pr.first->getExteriorOrientation().at(k)->getValue();
+            eb[k] = pr.second->getExteriorOrientation().at(k)->getValue();
+        }
+        rotationOf(ea + 3, Ra); rotationOf(eb + 3, Rb);
+        double M[9];                                                       // Ra' Rb, and Ra' (X0_b - X0_a)
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) M[3 * i + j] = Ra[i] * Rb[j] + Ra[3 + i] * Rb[3 + j] + Ra[6 + i] * Rb[6 + j];
+            start.push_back(Ra[i] * (eb[0] - ea[0]) + Ra[3 + i] * (eb[1] - ea[1]) + Ra[6 + i] * (eb[2] - ea[2]));
+        }
+        start.push_back(std::atan2(-M[5], M[8]));
+        start.push_back(std::asin(std::min(1.0, std::max(-1.0, M[2]))));
+        start.push_back(std::atan2(-M[1], M[0]));
+    }
+    const int n = (int)pairs.size();
+    std::vector<double> out((size_t)JAICOV_RELOR_OUT_PER_PAIR * n);
+    std::vector<int32_t> status(n), iterations(n), kind(n);
+    std::vector<uint8_t> used(xa.size() / 2);
+    const int rc = jaicov_relorient_pairs(n, begin.data(), xa.data(), xb.data(), va.data(), vb.data(), io.data(),
+                                          fromCurrentValues ? start.data() : nullptr, sigma2apriori, maximalNumberOfIterations_, rejectThreshold,
+                                          minPoints, out.data(), status.data(), iterations.data(), kind.data(), used.data(), nullptr, nullptr);
+    if (rc != JAICOV_OK) throw std::runtime_error("jaicov_relorient_pairs failed with status " + std::to_string(rc));
+    std::vector<Result> res(n);
+    for (int g = 0; g < n; g++) {
+        Result &r = res[g];
+        r.a = pairs[g].first; r.b = pairs[g].second;
+        r.status = status[g];
+        r.iterations = iterations[g];
+        r.startKind = kind[g];
+        r.points = begin[g + 1] - begin[g];
+        for (int k = begin[g]; k < begin[g + 1]; k++) r.pointsUsed += used[k];
+        for (int k = 0; k < JAICOV_RELOR_OUT_PER_PAIR; k++) r.values[k] = out[(size_t)JAICOV_RELOR_OUT_PER_PAIR * g + k];
+    }
+    return res;
+}
+
+bool RelativeOrientation::apply(const Result &r, double baseLength) {
+    if (r.status != JAICOV_RELOR_OK && r.status != JAICOV_RELOR_NOT_CONVERGED) return false;
+    for (int k = 0; k < 6; k++) {
+        r.a->getExteriorOrientation().at(k)->setValue(0.0);
+        r.b->getExteriorOrientation().at(k)->setValue(k < 3 ? baseLength * r.values[k] : r.values[k]);
+    }
+    return true;
+}
+
 }  // namespace jaicov::host

@@ -30,6 +30,7 @@
 #include "../../include/jaicov_dlt.h"
 #include "../../include/jaicov_intersect.h"
 #include "../../include/jaicov_resect.h"
+#include "../../include/jaicov_relorient.h"
 #include "../../include/jaicov_reliability.h"
 #include "../../include/jaicov_reliability_points.h"
 #include "../../include/jaicov_datum.h"
@@ -694,6 +695,29 @@ public:
     };
     static std::vector<Result> resectAll(const std::vector<Camera *> &cameras, bool fromCurrentValues = false, double sigma2apriori = 1.0,
                                          double rejectThreshold = 0.0, int minPoints = 4);
+    static int getMaximalNumberOfIterations() { return maximalNumberOfIterations_; }
+    static void setMaximalNumberOfIterations(int n) { maximalNumberOfIterations_ = n; }
+private:
+    static inline int maximalNumberOfIterations_ = 50;
+};
+
+// Relative orientation of image pairs from their common image points on the device (include/jaicov_relorient.h).  The reference has
+// no counterpart.  orientAll() makes one device call for every pair (a, b).  A pair's observations are the image coordinates of the
+// ObjectCoordinates both images observe, in the order of image a's coordinates, with their variances and correlation coefficients;
+// the interior orientations are those of the images' cameras (no distortion).  With fromCurrentValues the current exterior
+// orientation of image b relative to that of image a is the start value, otherwise every pair takes the linear starts.  Nothing is
+// written into the images: apply() puts image a at the origin with zero angles and image b at the result, its X0 times baseLength,
+// where the status is JAICOV_RELOR_OK or JAICOV_RELOR_NOT_CONVERGED.  A device error (no GPU, out of memory) throws std::runtime_error.
+class RelativeOrientation {
+public:
+    struct Result {
+        Image *a = nullptr, *b = nullptr;
+        int status = -1, iterations = 0, startKind = 0, points = 0, pointsUsed = 0;
+        double values[JAICOV_RELOR_OUT_PER_PAIR] = {};       // X0, Y0, Z0 (unit length), omega, phi, kappa, the upper triangle of Q, Omega
+    };
+    static std::vector<Result> orientAll(const std::vector<std::pair<Image *, Image *>> &pairs, bool fromCurrentValues = false,
+                                         double sigma2apriori = 1.0, double rejectThreshold = 0.0, int minPoints = 6);
+    static bool apply(const Result &result, double baseLength = 1.0);
     static int getMaximalNumberOfIterations() { return maximalNumberOfIterations_; }
     static void setMaximalNumberOfIterations(int n) { maximalNumberOfIterations_ = n; }
 private:

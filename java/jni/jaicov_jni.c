@@ -1,7 +1,7 @@
 /*
  * JNI shim between NativeNormalEquationEngine (Java) and the C ABI of include/jaicov_neq.h, include/jaicov_transform.h,
- * include/jaicov_dlt.h, include/jaicov_reliability.h, include/jaicov_datum.h, include/jaicov_intersect.h and
- * include/jaicov_resect.h.
+ * include/jaicov_dlt.h, include/jaicov_reliability.h, include/jaicov_datum.h, include/jaicov_intersect.h,
+ * include/jaicov_resect.h and include/jaicov_relorient.h.
  * The build image has no JDK, so this file is not built by __graft_entry__.build(); on a box with a JDK:
  *   gcc -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -I../../include jaicov_jni.c \
  *       -L../../bundle-adjustment_amd/csrc -ljaicov_neq -o libjaicov_jni.so
@@ -25,6 +25,7 @@
 #include "jaicov_dlt.h"
 #include "jaicov_intersect.h"
 #include "jaicov_resect.h"
+#include "jaicov_relorient.h"
 #include "jaicov_reliability.h"
 #include "jaicov_datum.h"
 
@@ -759,6 +760,72 @@ JNIEXPORT jint JNICALL NAT(resectImages)(JNIEnv *e, jclass k, jintArray obsBegin
     if (pvar) (*e)->ReleaseDoubleArrayElements(e, var, pvar, JNI_ABORT);
     if (pxyz) (*e)->ReleaseDoubleArrayElements(e, xyz, pxyz, JNI_ABORT);
     if (pxy) (*e)->ReleaseDoubleArrayElements(e, xy, pxy, JNI_ABORT);
+    (*e)->ReleaseIntArrayElements(e, obsBegin, pb, JNI_ABORT);
+    return rc;
+}
+
+/* --- include/jaicov_relorient.h: relative orientation of a batch of image pairs (no engine) ---------------------------------------- */
+/* inputs through Get<Type>ArrayElements copies (JNI_ABORT); varA, varB, start, iterations, startKind, obsUsed and obsQ may be null; status,
+ * iterations, startKind and obsUsed come back through long[] as for the resection. */
+JNIEXPORT jint JNICALL NAT(orientPairs)(JNIEnv *e, jclass k, jintArray obsBegin, jdoubleArray xyA, jdoubleArray xyB, jdoubleArray varA,
+                                        jdoubleArray varB, jdoubleArray pairIo, jdoubleArray start, jdouble sigma2apriori, jint maxIterations,
+                                        jdouble rejectThreshold, jint minPoints, jdoubleArray out, jlongArray status, jlongArray iterations,
+                                        jlongArray startKind, jlongArray obsUsed, jdoubleArray obsQ) {
+    (void)k;
+    const jsize nb = (*e)->GetArrayLength(e, obsBegin);
+    if (nb < 1) return JAICOV_ERR_BAD_ARGUMENT;
+    const jsize n = nb - 1;
+    if ((*e)->GetArrayLength(e, pairIo) < 6 * n || (start && (*e)->GetArrayLength(e, start) < 6 * n) ||
+        (*e)->GetArrayLength(e, out) < JAICOV_RELOR_OUT_PER_PAIR * n || (*e)->GetArrayLength(e, status) < n ||
+        (iterations && (*e)->GetArrayLength(e, iterations) < n) || (startKind && (*e)->GetArrayLength(e, startKind) < n))
+        return JAICOV_ERR_BAD_ARGUMENT;
+    jint *pb = (*e)->GetIntArrayElements(e, obsBegin, NULL);
+    if (!pb) return JAICOV_ERR_OUT_OF_MEMORY;
+    const jint no = pb[n];
+    if (no < 0 || (*e)->GetArrayLength(e, xyA) < 2 * no || (*e)->GetArrayLength(e, xyB) < 2 * no ||
+        (varA && (*e)->GetArrayLength(e, varA) < 3 * no) || (varB && (*e)->GetArrayLength(e, varB) < 3 * no) ||
+        (obsUsed && (*e)->GetArrayLength(e, obsUsed) < no) || (obsQ && (*e)->GetArrayLength(e, obsQ) < no)) {
+        (*e)->ReleaseIntArrayElements(e, obsBegin, pb, JNI_ABORT);
+        return JAICOV_ERR_BAD_ARGUMENT;
+    }
+    jdouble *pxa = (*e)->GetDoubleArrayElements(e, xyA, NULL);
+    jdouble *pxb = pxa ? (*e)->GetDoubleArrayElements(e, xyB, NULL) : NULL;
+    jdouble *pva = (pxb && varA) ? (*e)->GetDoubleArrayElements(e, varA, NULL) : NULL;
+    jdouble *pvb = (pxb && varB) ? (*e)->GetDoubleArrayElements(e, varB, NULL) : NULL;
+    jdouble *pio = pxb ? (*e)->GetDoubleArrayElements(e, pairIo, NULL) : NULL;
+    jdouble *pst = (pio && start) ? (*e)->GetDoubleArrayElements(e, start, NULL) : NULL;
+    const size_t np1 = (size_t)(n > 0 ? n : 1), no1 = (size_t)(no > 0 ? no : 1), nl = np1 > no1 ? np1 : no1;
+    double *po = (double *)malloc(sizeof(double) * JAICOV_RELOR_OUT_PER_PAIR * np1);
+    int32_t *ps = (int32_t *)malloc(sizeof(int32_t) * 3 * np1);
+    uint8_t *pu = (uint8_t *)malloc(no1);
+    double *pq = (double *)malloc(sizeof(double) * no1);
+    jlong *pl = (jlong *)malloc(sizeof(jlong) * nl);
+    int rc = JAICOV_ERR_OUT_OF_MEMORY;
+    if (pio && (pva || !varA) && (pvb || !varB) && (pst || !start) && po && ps && pu && pq && pl) {
+        rc = jaicov_relorient_pairs((int32_t)n, (const int32_t *)pb, pxa, pxb, pva, pvb, pio, pst, sigma2apriori, (int32_t)maxIterations,
+                                    rejectThreshold, (int32_t)minPoints, po, ps, ps + n, ps + 2 * n, pu, pq, NULL);
+        if (rc == JAICOV_OK) {
+            (*e)->SetDoubleArrayRegion(e, out, 0, JAICOV_RELOR_OUT_PER_PAIR * n, po);
+            jlongArray dst[3] = {status, iterations, startKind};
+            for (int a = 0; a < 3; a++) {
+                if (!dst[a]) continue;
+                for (jsize i = 0; i < n; i++) pl[i] = (jlong)ps[(size_t)a * n + i];
+                (*e)->SetLongArrayRegion(e, dst[a], 0, n, pl);
+            }
+            if (obsUsed) {
+                for (jsize i = 0; i < no; i++) pl[i] = (jlong)pu[i];
+                (*e)->SetLongArrayRegion(e, obsUsed, 0, no, pl);
+            }
+            if (obsQ) (*e)->SetDoubleArrayRegion(e, obsQ, 0, no, pq);
+        }
+    }
+    free(po); free(ps); free(pu); free(pq); free(pl);
+    if (pst) (*e)->ReleaseDoubleArrayElements(e, start, pst, JNI_ABORT);
+    if (pio) (*e)->ReleaseDoubleArrayElements(e, pairIo, pio, JNI_ABORT);
+    if (pvb) (*e)->ReleaseDoubleArrayElements(e, varB, pvb, JNI_ABORT);
+    if (pva) (*e)->ReleaseDoubleArrayElements(e, varA, pva, JNI_ABORT);
+    if (pxb) (*e)->ReleaseDoubleArrayElements(e, xyB, pxb, JNI_ABORT);
+    if (pxa) (*e)->ReleaseDoubleArrayElements(e, xyA, pxa, JNI_ABORT);
     (*e)->ReleaseIntArrayElements(e, obsBegin, pb, JNI_ABORT);
     return rc;
 }

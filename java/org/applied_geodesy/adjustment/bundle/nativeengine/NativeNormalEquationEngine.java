@@ -322,6 +322,34 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 		return status;
 	}
 
+	/** jaicov_relorient status values and start kinds (include/jaicov_relorient.h) */
+	public static final int RELOR_OK = 0, RELOR_NOT_CONVERGED = 1, RELOR_TOO_FEW_POINTS = 2, RELOR_SINGULAR = 3, RELOR_NOT_FINITE = 4;
+	public static final int RELOR_START_GIVEN = 0, RELOR_START_SPACE = 1, RELOR_START_PLANE = 2;
+
+	/**
+	 * Relative orientation of every image pair of a batch from the image points the two images share and their known interior
+	 * orientations, on the device, with no engine (include/jaicov_relorient.h; the reference has no counterpart).  obsBegin (n + 1 CSR
+	 * offsets) selects each pair's observations; xyA and xyB = 2 doubles per observation, the same object point in image a and in image
+	 * b; varA, varB (either may be null) = variance x, variance y, correlation coefficient per observation
+	 * (PartialDerivativeFactory.java:308-319); pairIo = x0, y0, c of image a's camera, then of image b's, per pair, c of either sign;
+	 * start (may be null) = X0, Y0, Z0, omega, phi, kappa of image b in the frame of image a per pair: a pair whose six values are
+	 * finite starts from them, any other from the linear starts.  out receives 28 values per pair (X0, Y0, Z0 of unit length, omega, phi,
+	 * kappa, the upper triangle of the cofactor matrix, Omega); iterations, startKind, obsUsed and obsQ may be null.  The result is the
+	 * status per pair; a pair whose status is RELOR_TOO_FEW_POINTS, RELOR_SINGULAR or RELOR_NOT_FINITE has NaN values.
+	 */
+	public static long[] orientPairs(int[] obsBegin, double[] xyA, double[] xyB, double[] varA, double[] varB, double[] pairIo, double[] start,
+	                                 double sigma2apriori, int maxIterations, double rejectThreshold, int minPoints, double[] out,
+	                                 long[] iterations, long[] startKind, long[] obsUsed, double[] obsQ) {
+		int n = obsBegin.length - 1;
+		long[] status = new long[Math.max(n, 0)];
+		int rc = orientPairs(obsBegin, xyA, xyB, varA, varB, pairIo, start, sigma2apriori, maxIterations, rejectThreshold, minPoints, out, status,
+		                     iterations, startKind, obsUsed, obsQ);
+		if (rc == -1) throw new IllegalArgumentException("jaicov_relorient_pairs: bad argument");
+		if (rc == -4) throw new OutOfMemoryError("jaicov_relorient_pairs");
+		if (rc != 0) throw new IllegalStateException("jaicov_relorient_pairs failed with status " + rc);
+		return status;
+	}
+
 	@Override public void close() { if (handle != 0) { destroy(handle); handle = 0; } }
 
 	private void check(int status) {
@@ -381,4 +409,5 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 	private static native int dltAdjust(int[] obsBegin, double[] xy, double[] xyz, double[] io, int[] ioFixed, int[] restrictions, int maxIterations, double[] out, long[] status, long[] solves);
 	private static native int isectPoints(int[] rayBegin, int[] rayImage, double[] xy, double[] var, int nImages, double[] imageIo, double[] imageEo, double sigma2apriori, int maxIterations, double rejectThreshold, int minRays, double[] out, long[] status, long[] iterations, long[] rayUsed, double[] rayQ);
 	private static native int resectImages(int[] obsBegin, double[] xy, double[] xyz, double[] var, double[] imageIo, double[] eoStart, double sigma2apriori, int maxIterations, double rejectThreshold, int minPoints, double[] out, long[] status, long[] iterations, long[] startKind, long[] obsUsed, double[] obsQ);
+	private static native int orientPairs(int[] obsBegin, double[] xyA, double[] xyB, double[] varA, double[] varB, double[] pairIo, double[] start, double sigma2apriori, int maxIterations, double rejectThreshold, int minPoints, double[] out, long[] status, long[] iterations, long[] startKind, long[] obsUsed, double[] obsQ);
 }

@@ -1,0 +1,593 @@
+"""Independent restatement of the relative orientation of include/jaicov_relorient.h for its tests.  TEST INFRASTRUCTURE ONLY.
+
+One pair at a time, in numpy: the rotation is PartialDerivativeFactory.java:125-135 (= PDF), the dispersions are PDF:308-319 inverted,
+the preconditioning NES:82-91 (resection_reference.solve).  Every term of an observation is rounded as the kernel rounds it (one
+rounding per product, sum and quotient, no contraction).  The sums over a pair's observations run in plain observation order by
+default; with order="lanes" they run in the kernel's order (resection_reference.sums).  The small algebra after the sums (Jacobi sweeps
+of order 9 and 3, Cholesky, the two decompositions) is written with the kernel's order of operations.  Outputs and status follow the
+ABI (NaN after a failure), so they compare one to one with the device.
+"""
+from __future__ import annotations
+
+import math
+import os
+import sys
+
+import numpy as np
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _ROOT not in sys.path:
+    sys.path.insert(0, _ROOT)
+
+import resection_reference as X  # noqa: E402
+from bundle_adjustment_amd import scene  # noqa: E402
+
+OK, NOT_CONVERGED, TOO_FEW_POINTS, SINGULAR, NOT_FINITE = range(5)
+START_GIVEN, START_SPACE, START_PLANE = range(3)
+EPS = 2.0 ** -53
+SQRT_EPS = math.sqrt(EPS)
+NOUT = 28
+SWEEPS9 = 10
+SWEEPS3 = 6
+NCAND = 12                        # 4 of the space start, 8 of the plane start
+sums, solve, wrap, scene_of = X.sums, X.solve, X.wrap, X.scene_of
+
+
+def cofactors(var, sigma2, c, m):
+    """(q11, q12, q22) of every ray: the dispersion of the image point over sigma2 (PDF:308-319 inverted), over c^2"""
+    c2 = c * c
+    with np.errstate(all="ignore"):
+        if var is None:
+            return np.full(m, 1.0 / c2), np.zeros(m), np.full(m, 1.0 / c2)
+        vx, vy, rho = var[:, 0], var[:, 1], var[:, 2]
+        return vx / sigma2 / c2, np.where(rho == 0, 0.0, rho * np.sqrt(vx * vy) / sigma2 / c2), vy / sigma2 / c2
+
+
+def rotate(A, p, q, r_idx, W):
+    """one Jacobi rotation in the plane (p, q) of the symmetric matrix A (lists), eigenvector rows W; r_idx: the other indices"""
+    apq = A[p][q]
+    if apq == 0.0:
+        return
+    with np.errstate(all="ignore"):
+        theta = float((np.float64(A[q][q]) - A[p][p]) / (2.0 * apq))
+    t = math.copysign(1.0, theta) / (abs(theta) + math.sqrt(theta * theta + 1.0))
+    c = 1.0 / math.sqrt(t * t + 1.0)
+    s = t * c
+    for k in r_idx:
+        kp, kq = c * A[k][p] - s * A[k][q], s * A[k][p] + c * A[k][q]
+        A[k][p] = A[p][k] = kp
+        A[k][q] = A[q][k] = kq
+    A[p][p] = A[p][p] - t * apq
+    A[q][q] = A[q][q] + t * apq
+    A[p][q] = A[q][p] = 0.0
+    for k in range(len(W[p])):
+        vp, vq = c * W[p][k] - s * W[q][k], s * W[p][k] + c * W[q][k]
+        W[p][k] = vp; W[q][k] = vq
+
+
+def eigen3(S):
+    """(eigenvalues falling, rows e1 e2 e3 with det = +1) of the symmetric 3 x 3 matrix S: SWEEPS3 of cyclic Jacobi"""
+    A = [[float(S[i][j]) for j in range(3)] for i in range(3)]
+    W = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]
+    for _ in range(SWEEPS3):
+        for p, q, r in ((0, 1, 2), (0, 2, 1), (1, 2, 0)):
+            rotate(A, p, q, (r,), W)
+    lam = [A[0][0], A[1][1], A[2][2]]
+    for a, b in ((0, 1), (1, 2), (0, 1)):
+        if lam[a] < lam[b]:
+            lam[a], lam[b] = lam[b], lam[a]
+            W[a], W[b] = W[b], W[a]
+    n = cross(W[0], W[1])
+    if n[0] * W[2][0] + n[1] * W[2][1] + n[2] * W[2][2] < 0.0:
+        W[2] = [-v for v in W[2]]
+    return lam, W
+
+
+def cross(a, b):
+    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+
+def space_candidates(ua, va, ub, vb, sel, order):
+    """(status, [(M, b)] * 4): the essential matrix from the 9 x 9 moment matrix and its four decompositions"""
+    o = np.ones_like(ua)
+    k = [ub * ua, ub * va, ub, vb * ua, vb * va, vb, ua, va, o]
+    with np.errstate(all="ignore"):
+        S = sums(np.array([k[i] * k[j] for i in range(9) for j in range(i, 9)]), sel, order)
+    if not np.all(np.isfinite(S)):
+        return NOT_FINITE, []
+    A = [[0.0] * 9 for _ in range(9)]
+    t = 0
+    for i in range(9):
+        for j in range(i, 9):
+            A[i][j] = A[j][i] = float(S[t]); t += 1
+    W = [[1.0 if i == j else 0.0 for j in range(9)] for i in range(9)]
+    for _ in range(SWEEPS9):
+        for p in range(8):
+            for q in range(p + 1, 9):
+                rotate(A, p, q, [r for r in range(9) if r != p and r != q], W)
+    lam = [A[i][i] for i in range(9)]
+    i0 = 0
+    for i in range(1, 9):
+        if lam[i] < lam[i0]:
+            i0 = i
+    l1, lmax = math.inf, lam[i0]
+    for i in range(9):
+        if i != i0 and lam[i] < l1:
+            l1 = lam[i]
+        if lam[i] > lmax:
+            lmax = lam[i]
+    if not l1 > SQRT_EPS * lmax:
+        return SINGULAR, []
+    r2 = math.sqrt(2.0)
+    E = [[W[i0][3 * i + j] * r2 for j in range(3)] for i in range(3)]
+    S3 = [[E[0][j] * E[0][k] + E[1][j] * E[1][k] + E[2][j] * E[2][k] for k in range(3)] for j in range(3)]
+    _, V = eigen3(S3)
+    n = V[2]
+    C = [cross(E[1], E[2]), cross(E[2], E[0]), cross(E[0], E[1])]
+    D = [cross(E[i], n) for i in range(3)]
+    Mp = [[C[i][j] - D[i][j] for j in range(3)] for i in range(3)]
+    Mm = [[C[i][j] + D[i][j] for j in range(3)] for i in range(3)]
+    nn = [-v for v in n]
+    return OK, [(Mp, n), (Mp, nn), (Mm, n), (Mm, nn)]
+
+
+def plane_candidates(ua, va, ub, vb, sel, order):
+    """(status, [(M, b) or None] * 8): the homography a -> b and its decompositions, both signs of H and of b"""
+    z, o = np.zeros_like(ua), np.ones_like(ua)
+    with np.errstate(all="ignore"):
+        a = np.stack([ua, va, o, z, z, z, -(ub * ua), -(ub * va)])
+        b = np.stack([z, z, z, ua, va, o, -(vb * ua), -(vb * va)])
+    N, n = X._normal_of_rows(a, b, ub, vb, sel, order)
+    st, h = solve(N, n)
+    if st != OK:
+        return st, []
+    H = [[h[0], h[1], h[2]], [h[3], h[4], h[5]], [h[6], h[7], 1.0]]
+    S3 = [[H[0][j] * H[0][k] + H[1][j] * H[1][k] + H[2][j] * H[2][k] for k in range(3)] for j in range(3)]
+    lam, V = eigen3(S3)
+    if not lam[1] > 0.0:
+        return SINGULAR, []
+    f = math.sqrt(lam[1])
+    l1, l3 = lam[0] / lam[1], lam[2] / lam[1]
+    if not l1 - l3 > SQRT_EPS:
+        return SINGULAR, []
+    H = [[H[i][j] / f for j in range(3)] for i in range(3)]
+    ca, cc, den = math.sqrt(max(1.0 - l3, 0.0)), math.sqrt(max(l1 - 1.0, 0.0)), math.sqrt(l1 - l3)
+    v1, v2, v3 = V
+    mul = lambda A, x: [A[i][0] * x[0] + A[i][1] * x[1] + A[i][2] * x[2] for i in range(3)]      # noqa: E731
+    out = []
+    for s in (1.0, -1.0):
+        u = [(ca * v1[k] + s * (cc * v3[k])) / den for k in range(3)]
+        nrm = cross(v2, u)
+        h2, hu, hn = mul(H, v2), mul(H, u), mul(H, nrm)
+        for sg in (1.0, -1.0):
+            w1, w2 = [sg * v for v in h2], [sg * v for v in hu]
+            w3 = cross(w1, w2)
+            M = [[w1[i] * v2[j] + w2[i] * u[j] + w3[i] * nrm[j] for j in range(3)] for i in range(3)]
+            t = [sg * hn[i] - w3[i] for i in range(3)]
+            bd = [-(M[0][k] * t[0] + M[1][k] * t[1] + M[2][k] * t[2]) for k in range(3)]
+            ln = math.sqrt(bd[0] * bd[0] + bd[1] * bd[1] + bd[2] * bd[2])
+            if not ln > 0.0:
+                out += [None, None]
+                continue
+            bp = [v / ln for v in bd]
+            out += [(M, bp), (M, [-v for v in bp])]
+    return OK, out
+
+
+def in_front(M, b, ua, va, ub, vb, ca, cb):
+    """per point: both depths of lambda_a M d_a - lambda_b d_b = M b on the camera's side (c lambda < 0)"""
+    mb = [M[i][0] * b[0] + M[i][1] * b[1] + M[i][2] * b[2] for i in range(3)]
+    with np.errstate(all="ignore"):
+        a = [M[i][0] * ua + M[i][1] * va + M[i][2] for i in range(3)]
+        aa = a[0] * a[0] + a[1] * a[1] + a[2] * a[2]
+        ab = a[0] * ub + a[1] * vb + a[2]
+        bb = ub * ub + vb * vb + 1.0
+        ra = a[0] * mb[0] + a[1] * mb[1] + a[2] * mb[2]
+        rb = ub * mb[0] + vb * mb[1] + mb[2]
+        det = aa * bb - ab * ab
+        na = ra * bb - ab * rb
+        nb = ab * ra - aa * rb
+        return (det > 0.0) & (ca * na < 0.0) & (cb * nb < 0.0)
+
+
+def pose(M, b):
+    """b and the angles of R = M'"""
+    return np.array([b[0], b[1], b[2], math.atan2(-M[2][1], M[2][2]), math.asin(min(1.0, max(-1.0, M[2][0]))),
+                     math.atan2(-M[1][0], M[0][0])])
+
+
+def tangent(b):
+    """e1, e2 of the plane across b: e = the unit axis of the smallest |b_i| (lowest index on a tie), e1 = b x e / |.|, e2 = b x e1"""
+    k = 0
+    for i in (1, 2):
+        if abs(b[i]) < abs(b[k]):
+            k = i
+    e = [0.0, 0.0, 0.0]; e[k] = 1.0
+    f = cross(b, e)
+    ln = math.sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2])
+    e1 = [v / ln for v in f]
+    return e1, cross(b, e1)
+
+
+def normal(par, e1, e2, obs, sel, order):
+    """N (5, 5), n (5,) of the step (N dx = n), Omega over sel, and q of every observation, at b = par[:3] and the angles par[3:]"""
+    ua, va, ub, vb, qa, qb = obs
+    b = [float(v) for v in par[:3]]
+    so, co = math.sin(par[3]), math.cos(par[3])
+    R = X.rotation(par)[0]
+    with np.errstate(all="ignore"):
+        p = [b[1] - b[2] * va, b[2] * ua - b[0], b[0] * va - b[1] * ua]
+        r = [R[i, 0] * ub + R[i, 1] * vb + R[i, 2] for i in range(3)]
+        g = r[0] * p[0] + r[1] * p[1] + r[2] * p[2]
+        s0 = R[0, 0] * p[0] + R[1, 0] * p[1] + R[2, 0] * p[2]
+        s1 = R[0, 1] * p[0] + R[1, 1] * p[1] + R[2, 1] * p[2]
+        g0 = r[1] * b[2] - r[2] * b[1]
+        g1 = r[2] * b[0] - r[0] * b[2]
+        cof = (g0 * (qa[0] * g0 + qa[1] * g1) + g1 * (qa[1] * g0 + qa[2] * g1)) + \
+              (s0 * (qb[0] * s0 + qb[1] * s1) + s1 * (qb[1] * s0 + qb[2] * s1))
+        pw = 1.0 / cof
+        pg = pw * g
+        q = pg * g
+        a = []
+        for e in (e1, e2):
+            f = [e[1] - e[2] * va, e[2] * ua - e[0], e[0] * va - e[1] * ua]
+            a.append(r[0] * f[0] + r[1] * f[1] + r[2] * f[2])
+        a.append(p[2] * r[1] - p[1] * r[2])
+        a.append(p[0] * (co * r[2] - so * r[1]) + p[1] * (so * r[0]) - p[2] * (co * r[0]))
+        a.append(ub * s1 - vb * s0)
+        T = [a[i] * (pw * a[j]) for i in range(5) for j in range(i, 5)]
+        T += [-(a[i] * pg) for i in range(5)]
+        T.append(q)
+        S = sums(np.array(T), sel, order)
+    N = np.zeros((5, 5))
+    N[np.triu_indices(5)] = S[:15]
+    N = N + np.triu(N, 1).T
+    return N, S[15:20], S[20], q
+
+
+def relorient_pair(xy_a, xy_b, var_a, var_b, io, start=None, sigma2=1.0, max_iterations=50, reject_threshold=0.0, min_points=6,
+                   order="plain", info=None):
+    """One pair from its common points: (out[28], status, iterations, start_kind, used (m,), q (m,)).  info (a dict): the candidates
+    of the last round as (kind, status, Omega, par) in their order, and the index of the one returned."""
+    xy_a = np.asarray(xy_a, np.float64).reshape(-1, 2)
+    m = xy_a.shape[0]
+    xy_b = np.asarray(xy_b, np.float64).reshape(m, 2)
+    io = [float(v) for v in io]
+    nan = np.full(NOUT, np.nan)
+    iterations = 0
+    fail = lambda st: (nan, st, iterations, START_GIVEN, np.zeros(m, np.uint8), np.full(m, np.nan))      # noqa: E731
+    given = start is not None and bool(np.all(np.isfinite(start)))
+    few = 5 if given else 6
+    if m < few:
+        return fail(TOO_FEW_POINTS)
+    with np.errstate(all="ignore"):
+        ua, va = -(xy_a[:, 0] - io[0]) / io[2], -(xy_a[:, 1] - io[1]) / io[2]
+        ub, vb = -(xy_b[:, 0] - io[3]) / io[5], -(xy_b[:, 1] - io[4]) / io[5]
+    qa = cofactors(None if var_a is None else np.asarray(var_a, np.float64).reshape(m, 3), sigma2, io[2], m)
+    qb = cofactors(None if var_b is None else np.asarray(var_b, np.float64).reshape(m, 3), sigma2, io[5], m)
+    obs = (ua, va, ub, vb, qa, qb)
+    used = np.ones(m, bool)
+    while True:
+        sel = np.flatnonzero(used)
+        if sel.size < few:
+            return fail(TOO_FEW_POINTS)
+        not_finite = False
+        starts = []                                # (kind, par)
+        if given:
+            s = np.asarray(start, np.float64)
+            with np.errstate(all="ignore"):
+                ln = math.sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2])
+                starts.append((START_GIVEN, np.array([s[0] / ln, s[1] / ln, s[2] / ln, s[3], s[4], s[5]])))
+        else:
+            cands = [None] * NCAND
+            if sel.size >= 8:
+                st, c4 = space_candidates(ua, va, ub, vb, sel, order)
+                not_finite |= st == NOT_FINITE
+                cands[:len(c4)] = c4
+            st, c8 = plane_candidates(ua, va, ub, vb, sel, order)
+            not_finite |= st == NOT_FINITE
+            cands[4:4 + len(c8)] = c8
+            count = [-1] * NCAND
+            for k, c in enumerate(cands):
+                if c is not None:
+                    count[k] = int(in_front(c[0], c[1], ua, va, ub, vb, io[2], io[5])[sel].sum())
+            if max(count[:4]) >= 0:
+                k = count.index(max(count[:4]), 0, 4)
+                starts.append((START_SPACE, pose(*cands[k])))
+            if max(count[4:]) >= 0:
+                best = max(count[4:])
+                for k in [k for k in range(4, NCAND) if count[k] == best][:2]:
+                    starts.append((START_PLANE, pose(*cands[k])))
+        runs = []
+        for kind, par in starts:
+            status = NOT_CONVERGED
+            for _ in range(max_iterations):
+                e1, e2 = tangent(par[:3])
+                N, n, _om, _q = normal(par, e1, e2, obs, sel, order)
+                iterations += 1
+                st, dx = solve(N, n)
+                if st == OK and not np.all(np.isfinite(dx)):
+                    st = NOT_FINITE
+                if st != OK:
+                    status = st
+                    break
+                bn = [par[k] + (dx[0] * e1[k] + dx[1] * e2[k]) for k in range(3)]
+                ln = math.sqrt(bn[0] * bn[0] + bn[1] * bn[1] + bn[2] * bn[2])
+                par = np.array([bn[0] / ln, bn[1] / ln, bn[2] / ln, par[3] + dx[2], par[4] + dx[3], par[5] + dx[4]])
+                if np.abs(dx).max() <= SQRT_EPS:
+                    status = OK
+                    break
+            if status > NOT_CONVERGED:
+                not_finite |= status == NOT_FINITE
+                continue
+            omega = normal(par, *tangent(par[:3]), obs, sel, order)[2]
+            if not np.isfinite(omega):
+                not_finite = True
+                continue
+            runs.append((kind, status, float(omega), par))
+        if not runs:
+            return fail(NOT_FINITE if not_finite else SINGULAR)
+        win = 0
+        for k in range(1, len(runs)):
+            if runs[k][1] < runs[win][1] or (runs[k][1] == runs[win][1] and runs[k][2] < runs[win][2] - SQRT_EPS * runs[win][2]):
+                win = k
+        if info is not None:
+            info["runs"] = runs; info["win"] = win
+        kind, status, _, par = runs[win]
+        e1, e2 = tangent(par[:3])
+        N, n, omega, q = normal(par, e1, e2, obs, sel, order)
+        if reject_threshold > 0 and sel.size > min_points and q[sel].max() > reject_threshold * reject_threshold:
+            used[sel[int(np.argmax(q[sel]))]] = False
+            continue
+        break
+    st, Q = solve(N, n, inverse=True)
+    if st != OK:
+        return fail(st)
+    J = np.zeros((6, 5))
+    J[:3, 0] = e1; J[:3, 1] = e2; J[3, 2] = J[4, 3] = J[5, 4] = 1.0
+    Q6 = np.zeros((6, 6))
+    for i in range(6):                            # the kernel's order: T = J Q, then T J'
+        for j in range(i, 6):
+            if i < 3 and j < 3:
+                t0 = e1[i] * Q[0, 0] + e2[i] * Q[0, 1]
+                t1 = e1[i] * Q[0, 1] + e2[i] * Q[1, 1]
+                Q6[i, j] = t0 * e1[j] + t1 * e2[j]
+            elif i < 3:
+                Q6[i, j] = e1[i] * Q[0, j - 1] + e2[i] * Q[1, j - 1]
+            else:
+                Q6[i, j] = Q[i - 1, j - 1]
+    out = np.zeros(NOUT)
+    out[:6] = par
+    out[6:27] = Q6[np.triu_indices(6)]
+    out[27] = omega
+    if not np.all(np.isfinite(out)):
+        return fail(NOT_FINITE)
+    return out, status, iterations, kind, used.astype(np.uint8), q
+
+
+def relorient(obs_begin, xy_a, xy_b, var_a, var_b, pair_io, start=None, info=None, **kw):
+    """Every pair of a CSR batch, as engine.relorient_pairs takes it: (out (n, 28), status, iterations, start_kind, obs_used, obs_q)."""
+    ob = np.asarray(obs_begin, np.int64)
+    n = ob.size - 1
+    xy_a = np.asarray(xy_a, np.float64).reshape(-1, 2); xy_b = np.asarray(xy_b, np.float64).reshape(-1, 2)
+    var_a = None if var_a is None else np.asarray(var_a, np.float64).reshape(-1, 3)
+    var_b = None if var_b is None else np.asarray(var_b, np.float64).reshape(-1, 3)
+    io = np.asarray(pair_io, np.float64).reshape(-1, 6)
+    s = None if start is None else np.asarray(start, np.float64).reshape(-1, 6)
+    out = np.zeros((n, NOUT)); st = np.zeros(n, np.int32); it = np.zeros(n, np.int32); kind = np.zeros(n, np.int32)
+    used = np.zeros(xy_a.shape[0], np.uint8); q = np.zeros(xy_a.shape[0])
+    for g in range(n):
+        sl = slice(ob[g], ob[g + 1])
+        inf = None if info is None else {}
+        out[g], st[g], it[g], kind[g], used[sl], q[sl] = relorient_pair(
+            xy_a[sl], xy_b[sl], None if var_a is None else var_a[sl], None if var_b is None else var_b[sl], io[g],
+            None if s is None else s[g], info=inf, **kw)
+        if info is not None:
+            info[g] = inf
+    return out, st, it, kind, used, q
+
+
+# ---- truth and batches -------------------------------------------------------------------------------------------------------------
+def relative_truth(ea, eb):
+    """(b (unit), omega, phi, kappa, base length) of image b in the frame of image a, from two exterior orientations"""
+    Ra, Rb = scene.rotation(*ea[3:]), scene.rotation(*eb[3:])
+    b = Ra.T @ (eb[:3] - ea[:3])
+    ln = float(np.linalg.norm(b))
+    return np.concatenate([b / ln, scene.angles_from_rotation(Ra.T @ Rb)]), ln
+
+
+def pose_error(out, truth):
+    """(largest difference of the base direction, of the rotation matrix's entries) between out[:, :6] and truth (n, 6)"""
+    db = np.abs(out[:, :3] - truth[:, :3]).max()
+    dr = max(np.abs(scene.rotation(*o[3:6]) - scene.rotation(*t[3:6])).max() for o, t in zip(out, truth))
+    return float(db), float(dr)
+
+
+def cat(parts):
+    """one batch of several: parts of (obs_begin, xy_a, xy_b, var_a, var_b, io, start)"""
+    begin = np.concatenate([[0], np.cumsum(np.concatenate([np.diff(p[0]) for p in parts]))]).astype(np.int32)
+    return (begin,) + tuple(np.concatenate([p[k] for p in parts]) for k in range(1, 7))
+
+
+def pairs_of_scene(fp, pairs, exact=False, c=None, c_b=None, counts=None):
+    """Pairs of a scene's images, matched by point: (obs_begin, xy_a, xy_b, var_a, var_b, io (n, 6), start (n, 6) of NaN), truth (n, 6),
+    base lengths.  exact: distortion- and noise-free observations; c, c_b override the principal distance of every image a / b (of
+    both with c alone); counts[k]: keep the first counts[k] common points of pair k."""
+    import dlt_reference as D
+    pts, io, eo = D.scene_truth(fp)
+    img, pt = np.asarray(fp.ip_image), np.asarray(fp.ip_point)
+    x, y = np.asarray(fp.ip_x, np.float64), np.asarray(fp.ip_y, np.float64)
+    var = np.stack([fp.ip_var_x, fp.ip_var_y, fp.ip_rho], 1)
+    ca = io[2] if c is None else c
+    cb = ca if c_b is None else c_b
+
+    def facing(e, cc):                             # the scene's cameras look along -r3 (c > 0); one with c < 0 is turned to look along +r3
+        if cc * io[2] > 0:
+            return e
+        Rf = scene.rotation(*e[3:]) @ np.diag([1.0, -1.0, -1.0])
+        return np.concatenate([e[:3], scene.angles_from_rotation(Rf)])
+    A, B, VA, VB, n_, T, L = [], [], [], [], [], [], []
+    for k, (a, b) in enumerate(pairs):
+        ia, ib = np.flatnonzero(img == a), np.flatnonzero(img == b)
+        common, ja, jb = np.intersect1d(pt[ia], pt[ib], return_indices=True)
+        if counts is not None:
+            common, ja, jb = common[:counts[k]], ja[:counts[k]], jb[:counts[k]]
+        ia, ib = ia[ja], ib[jb]
+        if exact or c is not None or c_b is not None:
+            xa = np.stack(scene.project(ca, io[0], io[1], facing(eo[a], ca), pts[common], scene.R0_EX, [])[:2], 1)
+            xb = np.stack(scene.project(cb, io[0], io[1], facing(eo[b], cb), pts[common], scene.R0_EX, [])[:2], 1)
+        else:
+            xa, xb = np.stack([x[ia], y[ia]], 1), np.stack([x[ib], y[ib]], 1)
+        A.append(xa); B.append(xb); VA.append(var[ia]); VB.append(var[ib]); n_.append(len(common))
+        t, ln = relative_truth(facing(eo[a], ca), facing(eo[b], cb))
+        T.append(t); L.append(ln)
+    begin = np.concatenate([[0], np.cumsum(n_)]).astype(np.int32)
+    pio = np.tile([io[0], io[1], ca, io[0], io[1], cb], (len(pairs), 1))
+    return (begin, np.concatenate(A), np.concatenate(B), np.concatenate(VA), np.concatenate(VB), pio,
+            np.full((len(pairs), 6), np.nan)), np.array(T), np.array(L)
+
+
+def with_noise(batch, seed=2, sigma=scene.SIGMA_IMG):
+    rng = np.random.default_rng(seed)
+    return (batch[0], batch[1] + rng.normal(0, sigma, batch[1].shape), batch[2] + rng.normal(0, sigma, batch[2].shape)) + batch[3:]
+
+
+def plane_batch(counts, thickness=0.0, seed=4, c=scene.C_EX, noise=0.0, extent=2000.0):
+    """Pairs over a field of counts[g] points within thickness * extent of the plane Z = 0, two cameras 1.5 extents away at oblique
+    angles: (batch, truth, base lengths)"""
+    rng = np.random.default_rng(seed)
+    A, B, T, L = [], [], [], []
+    for m in counts:
+        pts = np.stack([rng.uniform(-0.5 * extent, 0.5 * extent, m), rng.uniform(-0.5 * extent, 0.5 * extent, m),
+                        thickness * rng.uniform(-0.5 * extent, 0.5 * extent, m)], 1)
+        es = []
+        for _ in range(2):
+            o, p, k = rng.uniform(-0.5, 0.5), rng.uniform(-0.5, 0.5), rng.uniform(-3.0, 3.0)
+            R = scene.rotation(o, p, k)
+            X0 = (1.5 * extent if c > 0 else -1.5 * extent) * R[:, 2] + rng.uniform(-0.1 * extent, 0.1 * extent, 3)
+            es.append(np.array([X0[0], X0[1], X0[2], o, p, k]))
+        for e, dst in zip(es, (A, B)):
+            dst.append(np.stack(scene.project(c, scene.X0_EX, scene.Y0_EX, e, pts, scene.R0_EX, [])[:2], 1))
+        t, ln = relative_truth(*es)
+        T.append(t); L.append(ln)
+    begin = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    xa, xb = np.concatenate(A), np.concatenate(B)
+    var = np.tile([scene.SIGMA_IMG ** 2, scene.SIGMA_IMG ** 2, 0.0], (xa.shape[0], 1))
+    io = np.tile([scene.X0_EX, scene.Y0_EX, c] * 2, (len(counts), 1))
+    batch = (begin, xa, xb, var, var.copy(), io, np.full((len(counts), 6), np.nan))
+    return (with_noise(batch, seed + 1, noise) if noise else batch), np.array(T), np.array(L)
+
+
+SCENE_PAIRS = [(0, 1), (2, 5), (1, 3), (4, 0)]
+COUNTS = [5, 6, 7, 8, 9, 63, 64, 65, 127, 128, 129, 200]      # both sides of the lane width (64) and of the LDS chunk (128)
+LANE_PAIRS = [(k, (k + 1 + k % 3) % 12) for k in range(12)]
+
+
+def lane_batch(exact=False):
+    """12 pairs of the all-points scene (12 images x 200 points) in shuffled order, pair k with the first COUNTS[k] common points.  The
+    pair of 5 points has start values (the truth turned by 0.01 rad in every angle, its base moved by 0.01); every other pair has NaN
+    there.  Returns (batch, counts, truth)."""
+    order = np.random.default_rng(3).permutation(12)
+    pairs = [LANE_PAIRS[k] for k in order]
+    counts = np.array([COUNTS[k] for k in order])
+    batch, truth, _ = pairs_of_scene(scene_of("all_points"), pairs, exact=exact, counts=counts)
+    start = batch[6]
+    start[counts == 5] = truth[counts == 5] + [0.01, -0.01, 0.01, 0.01, -0.01, 0.01]
+    return batch, counts, truth
+
+
+def lane_batch_with_gross_errors():
+    """lane_batch on exact observations with N(0, 0.0005) noise and one gross error of 1 mm = 2 000 sigma in image a or b of every pair
+    of at least 63 points, on its first observation or on observation 70 mod count: (batch, counts, planted observations)"""
+    batch, counts, _ = lane_batch(exact=True)
+    batch = with_noise(batch, 5)
+    ob = batch[0]
+    big = np.flatnonzero(counts >= 63)
+    bad = ob[big] + np.where(np.arange(big.size) % 2 == 0, 0, 70 % counts[big])
+    batch[1][bad[0::2]] += 1.0
+    batch[2][bad[1::2]] += 1.0
+    return batch, counts, bad
+
+
+def gross_error_batch(sigmas=50.0, seed=7):
+    """pairs of cfg2, exact + N(0, sigma) noise, one gross error of `sigmas` sigma in x and y of image b on one random observation of
+    each pair: (batch, planted)"""
+    batch, _, _ = pairs_of_scene(scene_of("cfg2"), SCENE_PAIRS, exact=True)
+    batch = with_noise(batch, seed)
+    rng = np.random.default_rng(seed)
+    ob = batch[0]
+    planted = np.array([rng.integers(ob[g], ob[g + 1]) for g in range(ob.size - 1)])
+    batch[2][planted] += rng.choice([-1.0, 1.0], (planted.size, 2)) * sigmas * scene.SIGMA_IMG
+    return batch, planted
+
+
+def mixed_start_batch():
+    """pairs of cfg2 with start values (the truth moved by 0.02) for every second pair, NaN in one value of every other"""
+    batch, truth, _ = pairs_of_scene(scene_of("cfg2"), SCENE_PAIRS)
+    start = truth + np.array([0.02, -0.02, 0.02, 0.02, -0.02, 0.02])
+    start[1::2, 4] = np.nan
+    return batch[:6] + (start,)
+
+
+def degenerate_batch():
+    """A good pair of cfg2, the same image twice (no base), a pair with a NaN coordinate, 5 points without start values, the good pair
+    again: (batch, expected status of the five)"""
+    (ob, xa, xb, va, vb, io, _), _, _ = pairs_of_scene(scene_of("cfg2"), [(0, 1), (2, 5)])
+    g, h = slice(ob[0], ob[1]), slice(ob[1], ob[1] + 12)
+    bad = xb[h].copy(); bad[3, 1] = np.nan
+    A = np.concatenate([xa[g], xa[g], xa[h], xa[g][:5], xa[g]])
+    B = np.concatenate([xb[g], xa[g], bad, xb[g][:5], xb[g]])
+    VA = np.concatenate([va[g], va[g], va[h], va[g][:5], va[g]])
+    VB = np.concatenate([vb[g], va[g], vb[h], vb[g][:5], vb[g]])
+    n = ob[1] - ob[0]
+    begin = np.cumsum([0, n, n, 12, 5, n]).astype(np.int32)
+    return (begin, A, B, VA, VB, io[[0, 0, 1, 0, 0]], np.full((5, 6), np.nan)), [OK, SINGULAR, NOT_FINITE, TOO_FEW_POINTS, OK]
+
+
+def pair_batch_from_problem(fp, pairs, values=None):
+    """engine.relorient_problem's batch for pairs of a FlatProblem's images: common points in rising point number"""
+    v = np.asarray(fp.values if values is None else values, np.float64)
+    cam = v[3 * fp.n_points:3 * fp.n_points + 3 * fp.n_cameras].reshape(-1, 3)[fp.image_camera]
+    img, pt = np.asarray(fp.ip_image), np.asarray(fp.ip_point)
+    xy = np.stack([fp.ip_x, fp.ip_y], 1)
+    var = np.stack([fp.ip_var_x, fp.ip_var_y, fp.ip_rho], 1)
+    parts = []
+    for a, b in pairs:
+        ia, ib = np.flatnonzero(img == a), np.flatnonzero(img == b)
+        _, ja, jb = np.intersect1d(pt[ia], pt[ib], return_indices=True)
+        ia, ib = ia[ja], ib[jb]
+        parts.append((np.array([0, ia.size]), xy[ia], xy[ib], var[ia], var[ib], np.concatenate([cam[a], cam[b]])[None], np.full((1, 6), np.nan)))
+    return cat(parts)
+
+
+def best_pairs(fp, n=4):
+    """the n image pairs of a FlatProblem with the most common points, (a, b) with a < b, falling count, then rising (a, b)"""
+    see = np.zeros((fp.n_images, fp.n_points), np.int64)
+    see[np.asarray(fp.ip_image), np.asarray(fp.ip_point)] = 1
+    common = np.triu(see @ see.T, 1)
+    order = np.argsort(-common.ravel(), kind="stable")[:n]
+    return [(int(k // fp.n_images), int(k % fp.n_images)) for k in order]
+
+
+def parity_inputs(example_base=None):
+    """Every input on which tests/test_gpu_relorient.py holds the device against this restatement: (name, batch, keywords).
+    tests/test_relorient_abi.py runs the restatement on each of them in both summation orders."""
+    inputs = []
+    for name in ("tiny", "cfg2"):
+        fp = scene_of(name)
+        batch = pairs_of_scene(fp, SCENE_PAIRS)[0]
+        inputs.append((f"{name} weights", batch, dict(sigma2=fp.sigma2apriori)))
+        inputs.append((f"{name} unit weights", batch[:3] + (None, None) + batch[5:], {}))
+        inputs.append((f"{name} c < 0", with_noise(pairs_of_scene(fp, SCENE_PAIRS, c=-scene.C_EX)[0]), {}))
+        inputs.append((f"{name} two cameras", with_noise(pairs_of_scene(fp, SCENE_PAIRS, c=scene.C_EX, c_b=-1.7 * scene.C_EX)[0]), {}))
+    inputs.append(("plane field 1 %", plane_batch([6, 8, 12, 40], thickness=0.01, noise=scene.SIGMA_IMG)[0], {}))
+    inputs.append(("lane boundaries", lane_batch()[0], {}))
+    inputs.append(("lane boundaries with rejection", lane_batch_with_gross_errors()[0], dict(reject_threshold=30.0, min_points=6)))
+    inputs.append(("mixed starts", mixed_start_batch(), {}))
+    inputs.append(("gross errors", gross_error_batch()[0], dict(reject_threshold=5.0, min_points=8)))
+    inputs.append(("degenerate", degenerate_batch()[0], {}))
+    inputs.append(("one iteration", pairs_of_scene(scene_of("cfg2"), SCENE_PAIRS)[0], dict(max_iterations=1)))
+    if example_base is not None:
+        fp = X.example_problem(example_base)
+        inputs.append(("bundled block", pair_batch_from_problem(fp, best_pairs(fp)), dict(sigma2=fp.sigma2apriori)))
+    return inputs
