@@ -1153,16 +1153,16 @@ static bool flow_kernels_overlap(hipStream_t dstream) {
     if (cached >= 0) return cached != 0;
     DevBuf<int> d;
     int h[2] = {0, 0};
-    hipStream_t s2 = nullptr;
+    DevStream s2;
     bool ok = d.reserve(2) == hipSuccess && hipMemset(d.get(), 0, 2 * sizeof(int)) == hipSuccess &&
-              hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+              s2.create(hipStreamNonBlocking) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
     if (ok) {
         hipLaunchKernelGGL(flow_probe_wait_kernel, dim3(1), dim3(1), 0, dstream, d.get(), d.get() + 1);
-        hipLaunchKernelGGL(flow_probe_set_kernel, dim3(1), dim3(1), 0, s2, d.get());
-        ok = hipStreamSynchronize(dstream) == hipSuccess && hipStreamSynchronize(s2) == hipSuccess &&
+        hipLaunchKernelGGL(flow_probe_set_kernel, dim3(1), dim3(1), 0, s2.get(), d.get());
+        ok = hipStreamSynchronize(dstream) == hipSuccess && hipStreamSynchronize(s2.get()) == hipSuccess &&
              hipMemcpy(h, d.get(), 2 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
     }
-    if (s2) hipStreamDestroy(s2);
+    s2.reset();
     cached = ok && h[1] == 1 ? 1 : 0;
     if (!cached && flow_hooks().verbose) fprintf(stderr, "jaicov: kernels do not overlap on this host: dataflow factorisation runs as one kernel with inline diagonal blocks\n");
     return cached != 0;
@@ -1274,11 +1274,10 @@ static int flow_grid_size() {
     return std::max(1, std::min(FLOW_MAX_GRID, 2 * (cus > 0 ? cus : 256)));
 }
 extern "C" int jaicov_debug_flow_residency(int *out8) {       // tests / DESIGN.md: {valid, XCDs, shader engines, dealt, resident min, queued max, keep, 0}
-    hipStream_t s = nullptr;
     StreamLease d(STREAM_DIAGONAL_CUS);
-    if (!d.get() || hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return -1;
-    const FlowResidency r = flow_measure_residency(s, d.get(), flow_grid_size(), 2);
-    hipStreamDestroy(s);
+    DevStream s;
+    if (!d.get() || s.create(hipStreamNonBlocking) != hipSuccess) return -1;
+    const FlowResidency r = flow_measure_residency(s.get(), d.get(), flow_grid_size(), 2);
     out8[0] = r.valid; out8[1] = r.n_xcd; out8[2] = r.n_se; out8[3] = r.dealt; out8[4] = r.resident_min; out8[5] = r.queued_max; out8[6] = r.keep; out8[7] = r.se_cap;
     return 0;
 }

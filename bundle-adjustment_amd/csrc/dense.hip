@@ -1489,11 +1489,9 @@ hipError_t mfma_peak_bench(int blocks, int iters, float *ms_out, double *tflops)
 
 // does hipExtStreamCreateWithCUMask work here?  runs the MFMA peak kernel on a stream restricted by `mask` (8 words)
 hipError_t cumask_bench(const uint32_t *mask, int blocks, int iters, float *ms_out, double *tflops) {
-    hipStream_t st;
-    HIPCHK(hipExtStreamCreateWithCUMask(&st, 8, mask));
-    const hipError_t err = peak_on_stream(st, blocks, iters, ms_out, tflops);
-    hipStreamDestroy(st);
-    return err;
+    DevStream st;
+    HIPCHK(st.create_with_cu_mask(8, mask));
+    return peak_on_stream(st.get(), blocks, iters, ms_out, tflops);
 }
 
 // timing hook for the diagonal-block kernel (diagnostics): `iters` back-to-back launches on an SPD 128x128 block

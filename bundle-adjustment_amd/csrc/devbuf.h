@@ -1,10 +1,11 @@
-// Move-only owners of what the HIP runtime hands out: a device allocation, an event, a host-mapped allocation.  Each frees its
-// resource exactly once, in its destructor, so a function may leave through an error return with any of them half acquired.
+// Move-only owners of what the HIP runtime hands out: a device allocation, an event, a stream, a host-mapped allocation.  Each frees
+// its resource exactly once, in its destructor, so a function may leave through an error return with any of them half acquired.
 // This header is the only place of the library that allocates or frees device memory and creates or destroys events, so the
-// count it keeps (device_live) is complete.
+// count it keeps (device_live) is complete; beside the stream pool of dense.hip it is also the only one that creates or destroys streams.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <stdint.h>
 
 #include <algorithm>
 #include <atomic>
@@ -90,6 +91,32 @@ class DevEvent {
     }
     void reset() { if (ev_) hipEventDestroy(ev_); ev_ = nullptr; }
     hipEvent_t get() const { return ev_; }
+};
+
+// A stream with the lifetime of one call.  Declared before the other owners of a function, it is destroyed after them: the buffers
+// and events that its work uses go first.  (The pooled streams of dense.hip, which live as long as the process, are another thing.)
+class DevStream {
+    hipStream_t s_ = nullptr;
+  public:
+    DevStream() = default;
+    DevStream(DevStream &&o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+    DevStream &operator=(DevStream &&o) noexcept { std::swap(s_, o.s_); return *this; }
+    ~DevStream() { reset(); }
+    hipError_t create(unsigned flags = hipStreamDefault) {
+        reset();
+        const hipError_t err = hipStreamCreateWithFlags(&s_, flags);
+        if (err != hipSuccess) s_ = nullptr;
+        return err;
+    }
+    // a stream restricted to the compute units of `mask` (`words` 32-bit words)
+    hipError_t create_with_cu_mask(unsigned words, const uint32_t *mask) {
+        reset();
+        const hipError_t err = hipExtStreamCreateWithCUMask(&s_, words, mask);
+        if (err != hipSuccess) s_ = nullptr;
+        return err;
+    }
+    void reset() { if (s_) hipStreamDestroy(s_); s_ = nullptr; }
+    hipStream_t get() const { return s_; }
 };
 
 // host memory that the device can address (hipHostMallocMapped): words a kernel and the host pass to each other while the kernel runs

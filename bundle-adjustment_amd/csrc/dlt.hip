@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "../../include/jaicov_dlt.h"
+#include "batchcall.h"
 #include "devbuf.h"
 #include "dlt.h"
 
@@ -505,15 +506,6 @@ __global__ __launch_bounds__(64) void dlt_adjust_kernel(const int32_t *__restric
     }
 }
 
-bool dlt_device_ok() {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return false;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    return strncmp(prop.gcnArchName, "gfx950", 6) == 0;
-}
-
 }  // namespace
 }  // namespace jaicov
 
@@ -526,9 +518,7 @@ extern "C" int jaicov_dlt_adjust(int32_t n_images, const int32_t *obs_begin, con
     if (n_images < 0 || n_restrictions < 0 || max_iterations < 0 || !obs_begin) return JAICOV_ERR_BAD_ARGUMENT;
     if (n_restrictions > 0 && !restrictions) return JAICOV_ERR_BAD_ARGUMENT;
     if (n_images > 0 && (!io || !out || !status)) return JAICOV_ERR_BAD_ARGUMENT;
-    if (obs_begin[0] != 0) return JAICOV_ERR_BAD_ARGUMENT;
-    for (int32_t g = 0; g < n_images; g++)
-        if (obs_begin[g + 1] < obs_begin[g]) return JAICOV_ERR_BAD_ARGUMENT;
+    if (!ranges_ok(n_images, obs_begin)) return JAICOV_ERR_BAD_ARGUMENT;
     const long n_obs = obs_begin[n_images];
     if (n_obs > 0 && (!xy || !xyz)) return JAICOV_ERR_BAD_ARGUMENT;
     // DT:269-278: duplicates dropped in first-seen order, IDENTICAL dropped when both FIXED_PRINCIPLE_DISTANCE_* are present
@@ -546,45 +536,42 @@ extern "C" int jaicov_dlt_adjust(int32_t n_images, const int32_t *obs_begin, con
         if (!(drop_identical && order[r] == JAICOV_DLT_IDENTICAL_PRINCIPLE_DISTANCE)) rs.id[rs.n++] = order[r];
     for (int r = rs.n; r < DLT_MAX_RESTR; r++) rs.id[r] = 0;
 
-    if (!dlt_device_ok()) return JAICOV_ERR_NO_DEVICE;
+    if (!device_is_gfx950()) return JAICOV_ERR_NO_DEVICE;
     if (ms_out) *ms_out = 0.0;
     if (n_images == 0) return JAICOV_OK;
 
-    hipStream_t s;
-    if (hipStreamCreate(&s) != hipSuccess) return JAICOV_ERR_DEVICE;
-    const int rc = [&]() -> int {      // the owners go before the stream does
-        int32_t *d_begin = nullptr, *d_status = nullptr, *d_solves = nullptr;
-        double *d_xy = nullptr, *d_xyz = nullptr, *d_io = nullptr, *d_out = nullptr;
-        uint8_t *d_fixed = nullptr;
-        DevBag bag;
-        DevEvent ev0, ev1;
-        if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-        const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
-        const size_t ni = (size_t)n_images, no = (size_t)(n_obs > 0 ? n_obs : 1);
-        if (bag.alloc(&d_begin, ni + 1) != hipSuccess || bag.alloc(&d_xy, 2 * no) != hipSuccess || bag.alloc(&d_xyz, 3 * no) != hipSuccess ||
-            bag.alloc(&d_io, 3 * ni) != hipSuccess || (io_fixed && bag.alloc(&d_fixed, 3 * ni) != hipSuccess) ||
-            bag.alloc(&d_out, JAICOV_DLT_OUT_PER_IMAGE * ni) != hipSuccess || bag.alloc(&d_status, ni) != hipSuccess ||
-            (solves && bag.alloc(&d_solves, ni) != hipSuccess))
-            return JAICOV_ERR_OUT_OF_MEMORY;
-        hipMemcpyAsync(d_begin, obs_begin, (ni + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
-        if (n_obs > 0) {
-            hipMemcpyAsync(d_xy, xy, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-            hipMemcpyAsync(d_xyz, xyz, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-        }
-        hipMemcpyAsync(d_io, io, 3 * ni * sizeof(double), hipMemcpyHostToDevice, s);
-        if (io_fixed) hipMemcpyAsync(d_fixed, io_fixed, 3 * ni, hipMemcpyHostToDevice, s);
-        hipEventRecord(e0, s);
-        hipLaunchKernelGGL(dlt_adjust_kernel, dim3(n_images), dim3(64), 0, s, d_begin, d_xy, d_xyz, d_io, d_fixed, rs, (int)max_iterations,
-                           d_out, d_status, d_solves);
-        if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
-        hipEventRecord(e1, s);
-        hipMemcpyAsync(out, d_out, JAICOV_DLT_OUT_PER_IMAGE * ni * sizeof(double), hipMemcpyDeviceToHost, s);
-        hipMemcpyAsync(status, d_status, ni * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        if (solves) hipMemcpyAsync(solves, d_solves, ni * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
-        if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-        return JAICOV_OK;
-    }();
-    hipStreamDestroy(s);
-    return rc;
+    DevStream stream;                  // first, so that the other owners go before the stream does
+    if (stream.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipStream_t s = stream.get();
+    int32_t *d_begin = nullptr, *d_status = nullptr, *d_solves = nullptr;
+    double *d_xy = nullptr, *d_xyz = nullptr, *d_io = nullptr, *d_out = nullptr;
+    uint8_t *d_fixed = nullptr;
+    DevBag bag;
+    DevEvent ev0, ev1;
+    if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
+    const size_t ni = (size_t)n_images, no = (size_t)(n_obs > 0 ? n_obs : 1);
+    if (bag.alloc(&d_begin, ni + 1) != hipSuccess || bag.alloc(&d_xy, 2 * no) != hipSuccess || bag.alloc(&d_xyz, 3 * no) != hipSuccess ||
+        bag.alloc(&d_io, 3 * ni) != hipSuccess || (io_fixed && bag.alloc(&d_fixed, 3 * ni) != hipSuccess) ||
+        bag.alloc(&d_out, JAICOV_DLT_OUT_PER_IMAGE * ni) != hipSuccess || bag.alloc(&d_status, ni) != hipSuccess ||
+        (solves && bag.alloc(&d_solves, ni) != hipSuccess))
+        return JAICOV_ERR_OUT_OF_MEMORY;
+    hipMemcpyAsync(d_begin, obs_begin, (ni + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
+    if (n_obs > 0) {
+        hipMemcpyAsync(d_xy, xy, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+        hipMemcpyAsync(d_xyz, xyz, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+    }
+    hipMemcpyAsync(d_io, io, 3 * ni * sizeof(double), hipMemcpyHostToDevice, s);
+    if (io_fixed) hipMemcpyAsync(d_fixed, io_fixed, 3 * ni, hipMemcpyHostToDevice, s);
+    hipEventRecord(e0, s);
+    hipLaunchKernelGGL(dlt_adjust_kernel, dim3(n_images), dim3(64), 0, s, d_begin, d_xy, d_xyz, d_io, d_fixed, rs, (int)max_iterations,
+                       d_out, d_status, d_solves);
+    if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
+    hipEventRecord(e1, s);
+    hipMemcpyAsync(out, d_out, JAICOV_DLT_OUT_PER_IMAGE * ni * sizeof(double), hipMemcpyDeviceToHost, s);
+    hipMemcpyAsync(status, d_status, ni * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (solves) hipMemcpyAsync(solves, d_solves, ni * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
+    if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
+    return JAICOV_OK;
 }

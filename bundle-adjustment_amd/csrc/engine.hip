@@ -1815,56 +1815,53 @@ extern "C" int jaicov_dense_spd_solve_packed(int32_t n, double *ap, double *b, i
     std::string err;
     int rc = check_device(err);
     if (rc) return rc;
-    hipStream_t s;
-    if (hipStreamCreate(&s) != hipSuccess) return JAICOV_ERR_DEVICE;
+    DevStream stream;                  // first, so that the solver and the buffers go before the stream does
+    if (stream.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipStream_t s = stream.get();
     const int np = ((n + 127) / 128) * 128;
-    const int status = [&]() -> int {      // the solver and the buffers go before the stream does
-        DenseSolver ds;
-        DevBuf<double> ap_store, Y_store;
-        DevEvent ev0, ev1;
-        const size_t len = (size_t)n * (n + 1) / 2;
-        if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-        const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
-        if (ds.init(s, np, invert != 0, true) != hipSuccess || ap_store.reserve(len) != hipSuccess ||
-            Y_store.reserve((size_t)DENSE_MAX_RHS * np) != hipSuccess)
-            return JAICOV_ERR_OUT_OF_MEMORY;
-        double *d_ap = ap_store.get(), *d_Y = Y_store.get();
-        hipMemcpyAsync(d_ap, ap, len * sizeof(double), hipMemcpyHostToDevice, s);
-        int info = 0;
-        for (int attempt = 0;; attempt++) {      // an abandoned dataflow factorisation (-9) is repeated: the packed input is still there
-            // identity padding, then unpack the lower triangle
-            hipLaunchKernelGGL(load_disp_kernel, dim3((np + 255) / 256, np), dim3(256), 0, s, (const double *)nullptr, 0, ds.L, ds.ld, np, (const int32_t *)nullptr);
-            hipLaunchKernelGGL(unpack_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, d_ap, ds.ld, n, ds.L);
-            hipMemsetAsync(ds.rhs_row(0), 0, (size_t)128 * ds.ld * sizeof(double), s);
-            for (int q = 0; q < nrhs; q++) hipMemcpyAsync(ds.rhs_row(q), b + (size_t)q * n, n * sizeof(double), hipMemcpyHostToDevice, s);
-            hipEventRecord(e0, s);
-            if (ds.potrf() != hipSuccess) { info = -1; break; }
-            if (nrhs > 0) ds.backsolve_aug(d_Y, np, nrhs);
-            if (invert) {
-                ds.trtri();
-                ds.lauum();
-            }
-            hipEventRecord(e1, s);
-            info = ds.fetch_info();
-            if (info == -9 && attempt < 2) {
-                fprintf(stderr, "jaicov: factorisation abandoned on the device (a wait ran into its time limit); repeating it (%d)\n", attempt + 1);
-                continue;
-            }
-            break;
-        }
-        if (info < 0) return JAICOV_ERR_DEVICE;
-        if (info != 0) return JAICOV_ERR_SINGULAR;
-        for (int q = 0; q < nrhs; q++) hipMemcpyAsync(b + (size_t)q * n, d_Y + (size_t)q * np, n * sizeof(double), hipMemcpyDeviceToHost, s);
+    DenseSolver ds;
+    DevBuf<double> ap_store, Y_store;
+    DevEvent ev0, ev1;
+    const size_t len = (size_t)n * (n + 1) / 2;
+    if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
+    if (ds.init(s, np, invert != 0, true) != hipSuccess || ap_store.reserve(len) != hipSuccess ||
+        Y_store.reserve((size_t)DENSE_MAX_RHS * np) != hipSuccess)
+        return JAICOV_ERR_OUT_OF_MEMORY;
+    double *d_ap = ap_store.get(), *d_Y = Y_store.get();
+    hipMemcpyAsync(d_ap, ap, len * sizeof(double), hipMemcpyHostToDevice, s);
+    int info = 0;
+    for (int attempt = 0;; attempt++) {      // an abandoned dataflow factorisation (-9) is repeated: the packed input is still there
+        // identity padding, then unpack the lower triangle
+        hipLaunchKernelGGL(load_disp_kernel, dim3((np + 255) / 256, np), dim3(256), 0, s, (const double *)nullptr, 0, ds.L, ds.ld, np, (const int32_t *)nullptr);
+        hipLaunchKernelGGL(unpack_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, d_ap, ds.ld, n, ds.L);
+        hipMemsetAsync(ds.rhs_row(0), 0, (size_t)128 * ds.ld * sizeof(double), s);
+        for (int q = 0; q < nrhs; q++) hipMemcpyAsync(ds.rhs_row(q), b + (size_t)q * n, n * sizeof(double), hipMemcpyHostToDevice, s);
+        hipEventRecord(e0, s);
+        if (ds.potrf() != hipSuccess) { info = -1; break; }
+        if (nrhs > 0) ds.backsolve_aug(d_Y, np, nrhs);
         if (invert) {
-            hipLaunchKernelGGL(pack_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, ds.Q, ds.ld, n, d_ap);
-            hipMemcpyAsync(ap, d_ap, len * sizeof(double), hipMemcpyDeviceToHost, s);
+            ds.trtri();
+            ds.lauum();
         }
-        const bool ok = hipStreamSynchronize(s) == hipSuccess;
-        if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-        return ok ? JAICOV_OK : JAICOV_ERR_DEVICE;
-    }();
-    hipStreamDestroy(s);
-    return status;
+        hipEventRecord(e1, s);
+        info = ds.fetch_info();
+        if (info == -9 && attempt < 2) {
+            fprintf(stderr, "jaicov: factorisation abandoned on the device (a wait ran into its time limit); repeating it (%d)\n", attempt + 1);
+            continue;
+        }
+        break;
+    }
+    if (info < 0) return JAICOV_ERR_DEVICE;
+    if (info != 0) return JAICOV_ERR_SINGULAR;
+    for (int q = 0; q < nrhs; q++) hipMemcpyAsync(b + (size_t)q * n, d_Y + (size_t)q * np, n * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (invert) {
+        hipLaunchKernelGGL(pack_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, ds.Q, ds.ld, n, d_ap);
+        hipMemcpyAsync(ap, d_ap, len * sizeof(double), hipMemcpyDeviceToHost, s);
+    }
+    const bool ok = hipStreamSynchronize(s) == hipSuccess;
+    if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
+    return ok ? JAICOV_OK : JAICOV_ERR_DEVICE;
 }
 
 namespace jaicov { hipError_t diag_kernel_bench(int dbg, int iters, float *ms_out); hipError_t mfma_peak_bench(int, int, float *, double *); }
@@ -1967,39 +1964,36 @@ extern "C" int jaicov_debug_potrf_bench(int n, int reps, double *ms_out, long lo
     std::string err;
     if (check_device(err)) return JAICOV_ERR_NO_DEVICE;
     if (n <= 0 || n % 128 || reps < 1 || !ms_out) return JAICOV_ERR_BAD_ARGUMENT;
-    hipStream_t s;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return JAICOV_ERR_DEVICE;
-    const int status = [&]() -> int {      // the solver goes before the stream does
-        DenseSolver ds;
-        DevEvent ev0, ev1;
-        if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-        const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
-        if (ds.init(s, n, false, true) != hipSuccess) return JAICOV_ERR_OUT_OF_MEMORY;
-        if (trace_out && ds.flow.ready()) ds.flow.enable_trace(true);
-        for (int r = 0; r < reps; r++) {
-            hipLaunchKernelGGL(fill_spd_kernel, dim3((ds.n + 255) / 256, ds.n), dim3(256), 0, s, ds.L, ds.ld, ds.n, n);
-            hipEventRecord(e0, s);
-            const hipError_t pe = ds.potrf();
-            if (pe != hipSuccess) { fprintf(stderr, "potrf: %s\n", hipGetErrorString(pe)); return JAICOV_ERR_DEVICE; }
-            hipEventRecord(e1, s);
-            const int info = ds.fetch_info();
-            if (info < 0) fprintf(stderr, "potrf: info %d (flow_ready %d)\n", info, (int)ds.flow.ready());
-            float ms = 0;
-            hipEventElapsedTime(&ms, e0, e1);
-            ms_out[r] = ms;
-            if (info < 0) return JAICOV_ERR_DEVICE;
-            if (info != 0) return JAICOV_ERR_SINGULAR;
-        }
-        if (trace_out && ds.flow.trace()) {
-            const long long cnt = std::min<long long>(trace_cap, (long long)ds.flow.trace_words());   // per task, then per block column (chain kernel)
-            hipMemcpy(trace_out, ds.flow.trace(), (size_t)cnt * sizeof(long long), hipMemcpyDeviceToHost);
-        }
-        if (tasks_out) *tasks_out = ds.flow.ready() ? ds.flow.n_tasks() : 0;
-        hipStreamSynchronize(s);
-        return JAICOV_OK;
-    }();
-    hipStreamDestroy(s);
-    return status;
+    DevStream stream;                  // first, so that the solver goes before the stream does
+    if (stream.create(hipStreamNonBlocking) != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipStream_t s = stream.get();
+    DenseSolver ds;
+    DevEvent ev0, ev1;
+    if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
+    if (ds.init(s, n, false, true) != hipSuccess) return JAICOV_ERR_OUT_OF_MEMORY;
+    if (trace_out && ds.flow.ready()) ds.flow.enable_trace(true);
+    for (int r = 0; r < reps; r++) {
+        hipLaunchKernelGGL(fill_spd_kernel, dim3((ds.n + 255) / 256, ds.n), dim3(256), 0, s, ds.L, ds.ld, ds.n, n);
+        hipEventRecord(e0, s);
+        const hipError_t pe = ds.potrf();
+        if (pe != hipSuccess) { fprintf(stderr, "potrf: %s\n", hipGetErrorString(pe)); return JAICOV_ERR_DEVICE; }
+        hipEventRecord(e1, s);
+        const int info = ds.fetch_info();
+        if (info < 0) fprintf(stderr, "potrf: info %d (flow_ready %d)\n", info, (int)ds.flow.ready());
+        float ms = 0;
+        hipEventElapsedTime(&ms, e0, e1);
+        ms_out[r] = ms;
+        if (info < 0) return JAICOV_ERR_DEVICE;
+        if (info != 0) return JAICOV_ERR_SINGULAR;
+    }
+    if (trace_out && ds.flow.trace()) {
+        const long long cnt = std::min<long long>(trace_cap, (long long)ds.flow.trace_words());   // per task, then per block column (chain kernel)
+        hipMemcpy(trace_out, ds.flow.trace(), (size_t)cnt * sizeof(long long), hipMemcpyDeviceToHost);
+    }
+    if (tasks_out) *tasks_out = ds.flow.ready() ? ds.flow.n_tasks() : 0;
+    hipStreamSynchronize(s);
+    return JAICOV_OK;
 }
 
 // debug: factor a host matrix (n x n row-major, lower part used, n a multiple of 128) with DenseSolver::potrf and return the
@@ -2008,23 +2002,20 @@ extern "C" int jaicov_debug_potrf_factor(int n, const double *A, double *L_out) 
     std::string err;
     if (check_device(err)) return JAICOV_ERR_NO_DEVICE;
     if (n <= 0 || n % 128 || !A || !L_out) return JAICOV_ERR_BAD_ARGUMENT;
-    hipStream_t s;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return JAICOV_ERR_DEVICE;
-    const int status = [&]() -> int {      // the solver goes before the stream does
-        DenseSolver ds;
-        if (ds.init(s, n, false, true) != hipSuccess) return JAICOV_ERR_OUT_OF_MEMORY;
-        hipLaunchKernelGGL(fill_spd_kernel, dim3((ds.n + 255) / 256, ds.n), dim3(256), 0, s, ds.L, ds.ld, ds.n, n);   // incl. the right-hand-side rows
-        if (hipMemcpy2DAsync(ds.L, ds.ld * sizeof(double), A, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyHostToDevice, s) != hipSuccess) return JAICOV_ERR_DEVICE;
-        if (ds.potrf() != hipSuccess) return JAICOV_ERR_DEVICE;
-        const int info = ds.fetch_info();
-        if (info < 0) return JAICOV_ERR_DEVICE;
-        if (info > 0) return JAICOV_ERR_SINGULAR;
-        const bool copied = hipMemcpy2DAsync(L_out, (size_t)n * sizeof(double), ds.L, ds.ld * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, s) == hipSuccess;
-        hipStreamSynchronize(s);
-        return copied ? JAICOV_OK : JAICOV_ERR_DEVICE;
-    }();
-    hipStreamDestroy(s);
-    return status;
+    DevStream stream;                  // first, so that the solver goes before the stream does
+    if (stream.create(hipStreamNonBlocking) != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipStream_t s = stream.get();
+    DenseSolver ds;
+    if (ds.init(s, n, false, true) != hipSuccess) return JAICOV_ERR_OUT_OF_MEMORY;
+    hipLaunchKernelGGL(fill_spd_kernel, dim3((ds.n + 255) / 256, ds.n), dim3(256), 0, s, ds.L, ds.ld, ds.n, n);   // incl. the right-hand-side rows
+    if (hipMemcpy2DAsync(ds.L, ds.ld * sizeof(double), A, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyHostToDevice, s) != hipSuccess) return JAICOV_ERR_DEVICE;
+    if (ds.potrf() != hipSuccess) return JAICOV_ERR_DEVICE;
+    const int info = ds.fetch_info();
+    if (info < 0) return JAICOV_ERR_DEVICE;
+    if (info > 0) return JAICOV_ERR_SINGULAR;
+    const bool copied = hipMemcpy2DAsync(L_out, (size_t)n * sizeof(double), ds.L, ds.ld * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, s) == hipSuccess;
+    hipStreamSynchronize(s);
+    return copied ? JAICOV_OK : JAICOV_ERR_DEVICE;
 }
 
 // debug: one step of newton_schulz_exact (batchinv.hip) on host matrices: M and Q0 full symmetric squares, n x n row-major, n a multiple
@@ -2035,29 +2026,26 @@ extern "C" int jaicov_debug_newton_schulz(int n, const double *M, const double *
     std::string err;
     if (check_device(err)) return JAICOV_ERR_NO_DEVICE;
     if (n <= 0 || n % 128 || n > 8192 || !M || !Q0 || !Q_out) return JAICOV_ERR_BAD_ARGUMENT;
-    hipStream_t s;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return JAICOV_ERR_DEVICE;
+    DevStream stream;                  // first, so that the buffer goes before the stream does
+    if (stream.create(hipStreamNonBlocking) != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipStream_t s = stream.get();
     const long ld = (long)n + 128;
     const size_t sq = (size_t)n * ld, row = (size_t)n * sizeof(double);
-    const int status = [&]() -> int {      // the buffer goes before the stream does
-        DevBuf<double> store;                                // M, Q, W, T1, T2, T3
-        if (store.reserve(6 * sq) != hipSuccess) return JAICOV_ERR_OUT_OF_MEMORY;
-        double *buf = store.get();
-        double *dM = buf, *dQ = buf + sq, *dW = buf + 2 * sq, *T1 = buf + 3 * sq, *T2 = buf + 4 * sq, *T3 = buf + 5 * sq;
-        // M and Q start as NaN (all bits set) and the work squares as zero: the columns n .. n + 127, where the solver keeps its right-hand-side
-        // rows, then hold NaN beside both operands, and a slice or product that read up to ld instead of n would show in every entry
-        if (hipMemsetAsync(buf, 0xFF, 2 * sq * sizeof(double), s) != hipSuccess ||
-            hipMemsetAsync(buf + 2 * sq, 0, 4 * sq * sizeof(double), s) != hipSuccess ||
-            hipMemcpy2DAsync(dM, ld * sizeof(double), M, row, row, n, hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpy2DAsync(dQ, ld * sizeof(double), Q0, row, row, n, hipMemcpyHostToDevice, s) != hipSuccess ||
-            newton_schulz_exact(s, n, ld, dM, dQ, dW, T1, T2, T3) != hipSuccess ||
-            hipMemcpy2DAsync(Q_out, row, dQ, ld * sizeof(double), row, n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            (R_out && hipMemcpy2DAsync(R_out, row, T3, ld * sizeof(double), row, n, hipMemcpyDeviceToHost, s) != hipSuccess))   // (the product Q0 R went to T1)
-            return JAICOV_ERR_DEVICE;
-        return hipStreamSynchronize(s) == hipSuccess ? JAICOV_OK : JAICOV_ERR_DEVICE;
-    }();
-    hipStreamDestroy(s);
-    return status;
+    DevBuf<double> store;                                // M, Q, W, T1, T2, T3
+    if (store.reserve(6 * sq) != hipSuccess) return JAICOV_ERR_OUT_OF_MEMORY;
+    double *buf = store.get();
+    double *dM = buf, *dQ = buf + sq, *dW = buf + 2 * sq, *T1 = buf + 3 * sq, *T2 = buf + 4 * sq, *T3 = buf + 5 * sq;
+    // M and Q start as NaN (all bits set) and the work squares as zero: the columns n .. n + 127, where the solver keeps its right-hand-side
+    // rows, then hold NaN beside both operands, and a slice or product that read up to ld instead of n would show in every entry
+    if (hipMemsetAsync(buf, 0xFF, 2 * sq * sizeof(double), s) != hipSuccess ||
+        hipMemsetAsync(buf + 2 * sq, 0, 4 * sq * sizeof(double), s) != hipSuccess ||
+        hipMemcpy2DAsync(dM, ld * sizeof(double), M, row, row, n, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpy2DAsync(dQ, ld * sizeof(double), Q0, row, row, n, hipMemcpyHostToDevice, s) != hipSuccess ||
+        newton_schulz_exact(s, n, ld, dM, dQ, dW, T1, T2, T3) != hipSuccess ||
+        hipMemcpy2DAsync(Q_out, row, dQ, ld * sizeof(double), row, n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        (R_out && hipMemcpy2DAsync(R_out, row, T3, ld * sizeof(double), row, n, hipMemcpyDeviceToHost, s) != hipSuccess))   // (the product Q0 R went to T1)
+        return JAICOV_ERR_DEVICE;
+    return hipStreamSynchronize(s) == hipSuccess ? JAICOV_OK : JAICOV_ERR_DEVICE;
 }
 
 // C (M x N row-major) = alpha * op(A) op(B) + beta * C on the device, host buffers in/out (kernel parity + timing)

@@ -24,13 +24,19 @@
 #include <vector>
 
 #include "../../include/jaicov_intersect.h"
+#include "batchcall.h"
 #include "devbuf.h"
 #include "intersect.h"
+#include "wavealg.h"
 
 #pragma clang fp contract(off)
 
 namespace jaicov {
 namespace {
+
+// one set of status values in all the start-value kernels (wavealg.h)
+static_assert(JAICOV_ISECT_OK == WAVE_OK && JAICOV_ISECT_SINGULAR == WAVE_SINGULAR && JAICOV_ISECT_NOT_FINITE == WAVE_NOT_FINITE,
+              "wavealg.h returns the public status values");
 
 enum { ISECT_START = 0, ISECT_STEP = 1, ISECT_EVAL = 2 };
 constexpr int ISECT_NACC = 10;        // N00 N01 N02 N11 N12 N22, n0 n1 n2, Omega
@@ -152,15 +158,7 @@ __global__ __launch_bounds__(64) void isect_points_kernel(const int32_t *__restr
             simg[t] = ray_image[k];
             sx[t] = xy[2 * k]; sy[t] = xy[2 * k + 1];
             double p11 = 1.0, p12 = 0.0, p22 = 1.0;
-            if (var) {
-                const double vx = var[3 * k], vy = var[3 * k + 1], rho = var[3 * k + 2];
-                if (rho == 0.0) {
-                    p11 = s0 / vx; p22 = s0 / vy;
-                } else {
-                    const double inv = s0 / ((1.0 - rho * rho) * vx * vy);
-                    p11 = inv * vy; p22 = inv * vx; p12 = -inv * rho * sqrt(vx * vy);
-                }
-            }
+            if (var) obs_weight(var[3 * k], var[3 * k + 1], var[3 * k + 2], s0, p11, p12, p22);
             sp11[t] = p11; sp12[t] = p12; sp22[t] = p22;
             sused[t] = used[k];
         }
@@ -187,9 +185,7 @@ __global__ __launch_bounds__(64) void isect_points_kernel(const int32_t *__restr
         }
         for (int off = 32; off > 0; off >>= 1) {
             for (int a = 0; a < ISECT_NACC; a++) acc[a] += __shfl_xor(acc[a], off);
-            const double oq = __shfl_xor(qmax, off);
-            const int oi = __shfl_xor(qidx, off);
-            if (oq > qmax || (oq == qmax && oi < qidx)) { qmax = oq; qidx = oi; }
+            wave_argmax_combine(qmax, qidx, off);
         }
     };
 
@@ -281,15 +277,6 @@ __global__ __launch_bounds__(64) void isect_points_kernel(const int32_t *__restr
     }
 }
 
-bool isect_device_ok() {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return false;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    return strncmp(prop.gcnArchName, "gfx950", 6) == 0;
-}
-
 }  // namespace
 }  // namespace jaicov
 
@@ -304,68 +291,62 @@ extern "C" int jaicov_isect_points(int32_t n_points, const int32_t *ray_begin, c
     if (!(sigma2apriori > 0.0) || max_iterations < 1 || min_rays < 2 || !(reject_threshold >= 0.0)) return JAICOV_ERR_BAD_ARGUMENT;
     if (n_points > 0 && (!out || !status)) return JAICOV_ERR_BAD_ARGUMENT;
     if (n_images > 0 && (!image_io || !image_eo)) return JAICOV_ERR_BAD_ARGUMENT;
-    if (ray_begin[0] != 0) return JAICOV_ERR_BAD_ARGUMENT;
-    for (int32_t p = 0; p < n_points; p++)
-        if (ray_begin[p + 1] < ray_begin[p]) return JAICOV_ERR_BAD_ARGUMENT;
+    if (!ranges_ok(n_points, ray_begin)) return JAICOV_ERR_BAD_ARGUMENT;
     const long n_rays = ray_begin[n_points];
     if (n_rays > 0 && (!ray_image || !xy)) return JAICOV_ERR_BAD_ARGUMENT;
-    for (long k = 0; k < n_rays; k++) {
+    for (long k = 0; k < n_rays; k++)
         if (ray_image[k] < 0 || ray_image[k] >= n_images) return JAICOV_ERR_BAD_ARGUMENT;
-        if (var && (!(var[3 * k] > 0.0) || !(var[3 * k + 1] > 0.0) || !(fabs(var[3 * k + 2]) < 1.0))) return JAICOV_ERR_BAD_ARGUMENT;
-    }
+    if (!dispersions_ok(var, n_rays)) return JAICOV_ERR_BAD_ARGUMENT;
 
-    if (!isect_device_ok()) return JAICOV_ERR_NO_DEVICE;
+    if (!device_is_gfx950()) return JAICOV_ERR_NO_DEVICE;
     if (ms_out) *ms_out = 0.0;
     if (n_points == 0) return JAICOV_OK;
 
-    hipStream_t s;
-    if (hipStreamCreate(&s) != hipSuccess) return JAICOV_ERR_DEVICE;
-    const int rc = [&]() -> int {      // the owners go before the stream does
-        int32_t *d_begin = nullptr, *d_image = nullptr, *d_outcome = nullptr;
-        double *d_xy = nullptr, *d_var = nullptr, *d_io = nullptr, *d_eo = nullptr, *d_out = nullptr, *d_q = nullptr;
-        uint8_t *d_used = nullptr;
-        IsectImage *d_rec = nullptr;
-        DevBag bag;
-        DevEvent ev0, ev1;
-        if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-        const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
-        const size_t np = (size_t)n_points, nr = (size_t)(n_rays > 0 ? n_rays : 1), ni = (size_t)(n_images > 0 ? n_images : 1);
-        std::vector<int32_t> h_outcome(2 * np);
-        if (bag.alloc(&d_begin, np + 1) != hipSuccess || bag.alloc(&d_image, nr) != hipSuccess || bag.alloc(&d_xy, 2 * nr) != hipSuccess ||
-            (var && bag.alloc(&d_var, 3 * nr) != hipSuccess) || bag.alloc(&d_io, 3 * ni) != hipSuccess || bag.alloc(&d_eo, 6 * ni) != hipSuccess ||
-            bag.alloc(&d_rec, ni) != hipSuccess || bag.alloc(&d_out, JAICOV_ISECT_OUT_PER_POINT * np) != hipSuccess ||
-            bag.alloc(&d_outcome, 2 * np) != hipSuccess || bag.alloc(&d_used, nr) != hipSuccess || (ray_q && bag.alloc(&d_q, nr) != hipSuccess))
-            return JAICOV_ERR_OUT_OF_MEMORY;
-        hipMemcpyAsync(d_begin, ray_begin, (np + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
-        if (n_rays > 0) {
-            hipMemcpyAsync(d_image, ray_image, (size_t)n_rays * sizeof(int32_t), hipMemcpyHostToDevice, s);
-            hipMemcpyAsync(d_xy, xy, 2 * (size_t)n_rays * sizeof(double), hipMemcpyHostToDevice, s);
-            if (var) hipMemcpyAsync(d_var, var, 3 * (size_t)n_rays * sizeof(double), hipMemcpyHostToDevice, s);
-        }
-        if (n_images > 0) {
-            hipMemcpyAsync(d_io, image_io, 3 * (size_t)n_images * sizeof(double), hipMemcpyHostToDevice, s);
-            hipMemcpyAsync(d_eo, image_eo, 6 * (size_t)n_images * sizeof(double), hipMemcpyHostToDevice, s);
-        }
-        hipMemsetAsync(d_used, 1, nr, s);                                  // every ray starts as used
-        hipEventRecord(e0, s);
-        if (n_images > 0)
-            hipLaunchKernelGGL(isect_image_kernel, dim3((n_images + 255) / 256), dim3(256), 0, s, (int)n_images, d_io, d_eo, d_rec);
-        hipLaunchKernelGGL(isect_points_kernel, dim3(n_points), dim3(64), 0, s, d_begin, d_image, d_xy, d_var, d_rec, sigma2apriori,
-                           (int)max_iterations, reject_threshold * reject_threshold, (int)min_rays, d_out, d_outcome, d_used, d_q);
-        if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
-        hipEventRecord(e1, s);
-        hipMemcpyAsync(out, d_out, JAICOV_ISECT_OUT_PER_POINT * np * sizeof(double), hipMemcpyDeviceToHost, s);
-        hipMemcpyAsync(h_outcome.data(), d_outcome, 2 * np * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        if (ray_used && n_rays > 0) hipMemcpyAsync(ray_used, d_used, (size_t)n_rays, hipMemcpyDeviceToHost, s);
-        if (ray_q && n_rays > 0) hipMemcpyAsync(ray_q, d_q, (size_t)n_rays * sizeof(double), hipMemcpyDeviceToHost, s);
-        if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
-        for (size_t p = 0; p < np; p++) {
-            status[p] = h_outcome[2 * p];
-            if (iterations) iterations[p] = h_outcome[2 * p + 1];
-        }
-        if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-        return JAICOV_OK;
-    }();
-    hipStreamDestroy(s);
-    return rc;
+    DevStream stream;                  // first, so that the other owners go before the stream does
+    if (stream.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipStream_t s = stream.get();
+    int32_t *d_begin = nullptr, *d_image = nullptr, *d_outcome = nullptr;
+    double *d_xy = nullptr, *d_var = nullptr, *d_io = nullptr, *d_eo = nullptr, *d_out = nullptr, *d_q = nullptr;
+    uint8_t *d_used = nullptr;
+    IsectImage *d_rec = nullptr;
+    DevBag bag;
+    DevEvent ev0, ev1;
+    if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
+    const size_t np = (size_t)n_points, nr = (size_t)(n_rays > 0 ? n_rays : 1), ni = (size_t)(n_images > 0 ? n_images : 1);
+    std::vector<int32_t> h_outcome(2 * np);
+    if (bag.alloc(&d_begin, np + 1) != hipSuccess || bag.alloc(&d_image, nr) != hipSuccess || bag.alloc(&d_xy, 2 * nr) != hipSuccess ||
+        (var && bag.alloc(&d_var, 3 * nr) != hipSuccess) || bag.alloc(&d_io, 3 * ni) != hipSuccess || bag.alloc(&d_eo, 6 * ni) != hipSuccess ||
+        bag.alloc(&d_rec, ni) != hipSuccess || bag.alloc(&d_out, JAICOV_ISECT_OUT_PER_POINT * np) != hipSuccess ||
+        bag.alloc(&d_outcome, 2 * np) != hipSuccess || bag.alloc(&d_used, nr) != hipSuccess || (ray_q && bag.alloc(&d_q, nr) != hipSuccess))
+        return JAICOV_ERR_OUT_OF_MEMORY;
+    hipMemcpyAsync(d_begin, ray_begin, (np + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
+    if (n_rays > 0) {
+        hipMemcpyAsync(d_image, ray_image, (size_t)n_rays * sizeof(int32_t), hipMemcpyHostToDevice, s);
+        hipMemcpyAsync(d_xy, xy, 2 * (size_t)n_rays * sizeof(double), hipMemcpyHostToDevice, s);
+        if (var) hipMemcpyAsync(d_var, var, 3 * (size_t)n_rays * sizeof(double), hipMemcpyHostToDevice, s);
+    }
+    if (n_images > 0) {
+        hipMemcpyAsync(d_io, image_io, 3 * (size_t)n_images * sizeof(double), hipMemcpyHostToDevice, s);
+        hipMemcpyAsync(d_eo, image_eo, 6 * (size_t)n_images * sizeof(double), hipMemcpyHostToDevice, s);
+    }
+    hipMemsetAsync(d_used, 1, nr, s);                                  // every ray starts as used
+    hipEventRecord(e0, s);
+    if (n_images > 0)
+        hipLaunchKernelGGL(isect_image_kernel, dim3((n_images + 255) / 256), dim3(256), 0, s, (int)n_images, d_io, d_eo, d_rec);
+    hipLaunchKernelGGL(isect_points_kernel, dim3(n_points), dim3(64), 0, s, d_begin, d_image, d_xy, d_var, d_rec, sigma2apriori,
+                       (int)max_iterations, reject_threshold * reject_threshold, (int)min_rays, d_out, d_outcome, d_used, d_q);
+    if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
+    hipEventRecord(e1, s);
+    hipMemcpyAsync(out, d_out, JAICOV_ISECT_OUT_PER_POINT * np * sizeof(double), hipMemcpyDeviceToHost, s);
+    hipMemcpyAsync(h_outcome.data(), d_outcome, 2 * np * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (ray_used && n_rays > 0) hipMemcpyAsync(ray_used, d_used, (size_t)n_rays, hipMemcpyDeviceToHost, s);
+    if (ray_q && n_rays > 0) hipMemcpyAsync(ray_q, d_q, (size_t)n_rays * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
+    for (size_t p = 0; p < np; p++) {
+        status[p] = h_outcome[2 * p];
+        if (iterations) iterations[p] = h_outcome[2 * p + 1];
+    }
+    if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
+    return JAICOV_OK;
 }

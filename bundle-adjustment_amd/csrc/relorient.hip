@@ -13,7 +13,6 @@
 //   staged RELOR_CHUNK at a time in LDS as rays and ray cofactors; a pair with at most RELOR_CHUNK keeps them resident.
 //   One pass routine serves every kind of sum (space start, plane start, cheirality, step, evaluation), so that it is compiled once;
 //   its RELOR_NACC accumulators are the large per-lane state, and every index into them is a compile-time constant.
-// The small routines (solve, Jacobi of order 3) restate those of resect.hip, which keeps its own in its own translation unit.
 // Floating-point contraction is off in this file: every product and sum is rounded on its own, as tests/relorient_reference.py rounds it.
 #include <hip/hip_runtime.h>
 
@@ -27,8 +26,10 @@
 #include <vector>
 
 #include "../../include/jaicov_relorient.h"
+#include "batchcall.h"
 #include "devbuf.h"
 #include "relorient.h"
+#include "wavealg.h"
 
 #pragma clang fp contract(off)
 
@@ -37,143 +38,9 @@ namespace {
 
 enum { RO_BEGIN = 0, RO_SPACE, RO_PLANE, RO_CHEIR, RO_STEP, RO_EVAL, RO_FINAL };
 
-// A value that is the same in every lane, said so to the compiler (resect.hip: rs_uniform)
-__device__ inline int ro_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ inline bool ro_uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
-
-// index of (i, j >= i) in an upper triangle of order N packed row by row
-template <int N>
-__device__ constexpr int ro_ix(int i, int j) { return i * N - i * (i - 1) / 2 + (j - i); }
-
-// A (packed upper, order N) x = b by Jacobi preconditioning (NES:82-91) and Cholesky; Q (may be NULL, packed upper): the inverse of A.
-// A is overwritten by the factor.
-template <int N>
-__device__ inline int ro_solve(double *U, const double *b, double *x, double *Q) {
-    const double EPS = ldexp(1.0, -53), SQRT_EPS = sqrt(EPS);
-    constexpr int LEN = N * (N + 1) / 2;
-    double z = 0.0;                       // NaN unless every value is finite
-#pragma unroll
-    for (int k = 0; k < LEN; k++) z += U[k] * 0.0;
-#pragma unroll
-    for (int k = 0; k < N; k++) z += b[k] * 0.0;
-    if (ro_uniform(z != 0.0)) return JAICOV_RELOR_NOT_FINITE;
-    double V[N];                          // U'U = V A V, U upper
-#pragma unroll
-    for (int i = 0; i < N; i++) V[i] = U[ro_ix<N>(i, i)] > EPS ? 1.0 / sqrt(U[ro_ix<N>(i, i)]) : 1.0;
-#pragma unroll
-    for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int j = i; j < N; j++) U[ro_ix<N>(i, j)] = U[ro_ix<N>(i, j)] * (V[i] * V[j]);
-    bool singular = false;
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < j; k++) s += U[ro_ix<N>(k, j)] * U[ro_ix<N>(k, j)];
-        const double p = U[ro_ix<N>(j, j)] - s;
-        singular = singular || !(p > SQRT_EPS);
-        const double d = sqrt(p);
-        U[ro_ix<N>(j, j)] = d;
-#pragma unroll
-        for (int i = j + 1; i < N; i++) {
-            double r = 0.0;
-#pragma unroll
-            for (int k = 0; k < j; k++) r += U[ro_ix<N>(k, i)] * U[ro_ix<N>(k, j)];
-            U[ro_ix<N>(j, i)] = (U[ro_ix<N>(j, i)] - r) / d;
-        }
-    }
-    if (ro_uniform(singular)) return JAICOV_RELOR_SINGULAR;       // every pivot after the first bad one is garbage and is not used
-    if (x) {
-        double y[N];
-#pragma unroll
-        for (int i = 0; i < N; i++) {
-            double r = 0.0;
-#pragma unroll
-            for (int k = 0; k < i; k++) r += U[ro_ix<N>(k, i)] * y[k];
-            y[i] = (V[i] * b[i] - r) / U[ro_ix<N>(i, i)];
-        }
-#pragma unroll
-        for (int i = N - 1; i >= 0; i--) {
-            double r = 0.0;
-#pragma unroll
-            for (int k = i + 1; k < N; k++) r += U[ro_ix<N>(i, k)] * y[k];
-            y[i] = (y[i] - r) / U[ro_ix<N>(i, i)];
-        }
-#pragma unroll
-        for (int i = 0; i < N; i++) x[i] = V[i] * y[i];
-    }
-    if (Q) {
-        double W[LEN];                    // W = inverse of U, upper: W[i][j], j >= i
-#pragma unroll
-        for (int j = 0; j < N; j++) {
-            W[ro_ix<N>(j, j)] = 1.0 / U[ro_ix<N>(j, j)];
-#pragma unroll
-            for (int i = j - 1; i >= 0; i--) {
-                double r = 0.0;
-#pragma unroll
-                for (int k = i + 1; k <= j; k++) r += U[ro_ix<N>(i, k)] * W[ro_ix<N>(k, j)];
-                W[ro_ix<N>(i, j)] = -r / U[ro_ix<N>(i, i)];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < N; i++)
-#pragma unroll
-            for (int j = i; j < N; j++) {                 // inverse of V A V = W W'
-                double r = 0.0;
-#pragma unroll
-                for (int k = j; k < N; k++) r += W[ro_ix<N>(i, k)] * W[ro_ix<N>(j, k)];
-                Q[ro_ix<N>(i, j)] = r * (V[i] * V[j]);
-            }
-    }
-    return JAICOV_RELOR_OK;
-}
-
-// The same solve for the homography (order 8), on a system held in LDS: U (packed upper, overwritten by the factor), b (overwritten
-// by x), V.  Every lane runs it on the same words and stores what every other lane stores, so it needs no barrier; its loops stay rolled.
-__device__ inline int ro_solve_lds(int n, double *U, double *b, double *V) {
-    const double EPS = ldexp(1.0, -53), SQRT_EPS = sqrt(EPS);
-    auto ix = [n](int i, int j) { return i * n - i * (i - 1) / 2 + (j - i); };
-    bool finite = true;
-    for (int k = 0; k < n * (n + 1) / 2; k++) finite = finite && isfinite(U[k]);
-    for (int k = 0; k < n; k++) finite = finite && isfinite(b[k]);
-    if (ro_uniform(!finite)) return JAICOV_RELOR_NOT_FINITE;
-    for (int i = 0; i < n; i++) V[i] = U[ix(i, i)] > EPS ? 1.0 / sqrt(U[ix(i, i)]) : 1.0;
-    for (int i = 0; i < n; i++)
-        for (int j = i; j < n; j++) U[ix(i, j)] = U[ix(i, j)] * (V[i] * V[j]);
-    for (int j = 0; j < n; j++) {
-        double s = 0.0;
-        for (int k = 0; k < j; k++) s += U[ix(k, j)] * U[ix(k, j)];
-        const double p = U[ix(j, j)] - s;
-        if (ro_uniform(!(p > SQRT_EPS))) return JAICOV_RELOR_SINGULAR;
-        const double d = sqrt(p);
-        U[ix(j, j)] = d;
-        for (int i = j + 1; i < n; i++) {
-            double r = 0.0;
-            for (int k = 0; k < j; k++) r += U[ix(k, i)] * U[ix(k, j)];
-            U[ix(j, i)] = (U[ix(j, i)] - r) / d;
-        }
-    }
-    for (int i = 0; i < n; i++) {
-        double r = 0.0;
-        for (int k = 0; k < i; k++) r += U[ix(k, i)] * b[k];
-        b[i] = (V[i] * b[i] - r) / U[ix(i, i)];
-    }
-    for (int i = n - 1; i >= 0; i--) {
-        double r = 0.0;
-        for (int k = i + 1; k < n; k++) r += U[ix(i, k)] * b[k];
-        b[i] = (b[i] - r) / U[ix(i, i)];
-    }
-    for (int i = 0; i < n; i++) b[i] = V[i] * b[i];
-    return JAICOV_RELOR_OK;
-}
-
-// the Jacobi rotation that annuls a_pq: t = tan, c = cos, s = sin of its angle
-__device__ inline void ro_angle(double app, double aqq, double apq, double &t, double &c, double &s) {
-    const double theta = (aqq - app) / (2.0 * apq);
-    t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    c = 1.0 / sqrt(t * t + 1.0);
-    s = t * c;
-}
+// the solves' statuses (wavealg.h) go out as the call's own
+static_assert(JAICOV_RELOR_OK == WAVE_OK && JAICOV_RELOR_SINGULAR == WAVE_SINGULAR && JAICOV_RELOR_NOT_FINITE == WAVE_NOT_FINITE,
+              "wavealg.h returns the public status values");
 
 // RELOR_SWEEPS9 sweeps of cyclic Jacobi over the symmetric 9 x 9 matrix A (full, in LDS); W (in LDS, the unit matrix on entry): its rows
 // become the eigenvectors.  Every lane runs it on the same words; the loops stay rolled.
@@ -182,9 +49,9 @@ __device__ inline void ro_jacobi9(double *A, double *W) {
         for (int p = 0; p < 8; p++)
             for (int q = p + 1; q < 9; q++) {
                 const double apq = A[9 * p + q];
-                if (ro_uniform(apq == 0.0)) continue;
+                if (wave_uniform(apq == 0.0)) continue;
                 double t, c, s;
-                ro_angle(A[9 * p + p], A[9 * q + q], apq, t, c, s);
+                jacobi_angle(A[9 * p + p], A[9 * q + q], apq, t, c, s);
                 for (int k = 0; k < 9; k++) {
                     if (k == p || k == q) continue;
                     const double akp = A[9 * k + p], akq = A[9 * k + q];
@@ -201,46 +68,6 @@ __device__ inline void ro_jacobi9(double *A, double *W) {
                     W[9 * q + k] = s * wp + c * wq;
                 }
             }
-}
-
-// one Jacobi rotation in the plane (p, q) of a symmetric 3 x 3 matrix; r is the third index; wp, wq: the eigenvector rows p and q
-__device__ inline void ro_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double *wp, double *wq) {
-    if (ro_uniform(apq == 0.0)) return;
-    double t, c, s;
-    ro_angle(app, aqq, apq, t, c, s);
-    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
-    arp = rp; arq = rq;
-    app = app - t * apq; aqq = aqq + t * apq; apq = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const double vp = c * wp[k] - s * wq[k], vq = s * wp[k] + c * wq[k];
-        wp[k] = vp; wq[k] = vq;
-    }
-}
-
-// eigenvalues (falling) and eigenvectors (rows of E, det = +1) of the symmetric matrix S (00 01 02 11 12 22)
-__device__ inline void ro_eigen3(const double *S, double *lam, double *E) {
-    double a00 = S[0], a01 = S[1], a02 = S[2], a11 = S[3], a12 = S[4], a22 = S[5];
-    double W[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-    for (int sweep = 0; sweep < RELOR_SWEEPS3; sweep++) {
-        ro_rotate(a00, a11, a01, a02, a12, W, W + 3);
-        ro_rotate(a00, a22, a02, a01, a12, W, W + 6);
-        ro_rotate(a11, a22, a12, a01, a02, W + 3, W + 6);
-    }
-    auto order = [&](double &la, double &lb, double *wa, double *wb) {      // the larger eigenvalue first; equal ones keep their order
-        if (ro_uniform(!(la < lb))) return;
-        const double l = la; la = lb; lb = l;
-#pragma unroll
-        for (int k = 0; k < 3; k++) { const double w = wa[k]; wa[k] = wb[k]; wb[k] = w; }
-    };
-    order(a00, a11, W, W + 3);
-    order(a11, a22, W + 3, W + 6);
-    order(a00, a11, W, W + 3);
-    const double n0 = W[1] * W[5] - W[2] * W[4], n1 = W[2] * W[3] - W[0] * W[5], n2 = W[0] * W[4] - W[1] * W[3];   // e1 x e2
-    if (n0 * W[6] + n1 * W[7] + n2 * W[8] < 0.0) { W[6] = -W[6]; W[7] = -W[7]; W[8] = -W[8]; }
-    lam[0] = a00; lam[1] = a11; lam[2] = a22;
-#pragma unroll
-    for (int k = 0; k < 9; k++) E[k] = W[k];
 }
 
 __device__ inline void ro_cross(const double *a, const double *b, double *c) {
@@ -357,14 +184,14 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
 #pragma unroll
                     for (int i = 0; i < 9; i++)
 #pragma unroll
-                        for (int j = i; j < 9; j++) acc[ro_ix<9>(i, j)] += k[i] * k[j];
+                        for (int j = i; j < 9; j++) acc[tri_ix<9>(i, j)] += k[i] * k[j];
                 } else if (mode == RO_PLANE) {
                     const double a[8] = {ua, va, 1.0, 0.0, 0.0, 0.0, -(ub * ua), -(ub * va)};
                     const double b[8] = {0.0, 0.0, 0.0, ua, va, 1.0, -(vb * ua), -(vb * va)};
 #pragma unroll
                     for (int i = 0; i < 8; i++) {
 #pragma unroll
-                        for (int j = i; j < 8; j++) acc[ro_ix<8>(i, j)] += a[i] * a[j] + b[i] * b[j];
+                        for (int j = i; j < 8; j++) acc[tri_ix<8>(i, j)] += a[i] * a[j] + b[i] * b[j];
                         acc[36 + i] += a[i] * ub + b[i] * vb;
                     }
                 } else if (mode == RO_CHEIR) {
@@ -373,7 +200,7 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
                     const double bb = ub * ub + vb * vb + 1.0, ca = io[2], cb = io[5];
 #pragma unroll 1
                     for (int s = 0; s < RELOR_SLOTS; s++) {
-                        if (!ro_uniform((mask >> s) & 1)) continue;
+                        if (!wave_uniform((mask >> s) & 1)) continue;
                         const double *M = sC + RELOR_SLOT_LEN * s, *mb = M + 12;
                         const double a0 = M[0] * ua + M[1] * va + M[2], a1 = M[3] * ua + M[4] * va + M[5], a2 = M[6] * ua + M[7] * va + M[8];
                         const double aa = a0 * a0 + a1 * a1 + a2 * a2;
@@ -412,7 +239,7 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
 #pragma unroll
                     for (int i = 0; i < 5; i++) {
 #pragma unroll
-                        for (int j = i; j < 5; j++) acc[ro_ix<5>(i, j)] += a[i] * (pw * a[j]);
+                        for (int j = i; j < 5; j++) acc[tri_ix<5>(i, j)] += a[i] * (pw * a[j]);
                         acc[15 + i] += -(a[i] * pg);
                     }
                     acc[20] += q;
@@ -427,9 +254,7 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
 #pragma unroll
                 for (int a = RELOR_NACC_STEP; a < RELOR_NACC; a++) acc[a] += __shfl_xor(acc[a], off);
             }
-            const double oq = __shfl_xor(qmax, off);
-            const int oi = __shfl_xor(qidx, off);
-            if (oq > qmax || (oq == qmax && oi < qidx)) { qmax = oq; qidx = oi; }
+            wave_argmax_combine(qmax, qidx, off);
         }
         __syncthreads();                                  // the last reads of the state and of the sums before
         if (mode == RO_CHEIR) {                           // whole numbers: their sum does not depend on its order
@@ -444,7 +269,7 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
             for (int i = 0; i < 9; i++)
 #pragma unroll
                 for (int j = 0; j < 9; j++) {
-                    sA[9 * i + j] = acc[i <= j ? ro_ix<9>(i, j) : ro_ix<9>(j, i)];
+                    sA[9 * i + j] = acc[i <= j ? tri_ix<9>(i, j) : tri_ix<9>(j, i)];
                     sA[81 + 9 * i + j] = i == j ? 1.0 : 0.0;
                 }
         } else {
@@ -465,13 +290,13 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
     int &not_finite = sI[11], &new_state = sI[12], &failed = sI[13];
     not_finite = 0; new_state = 0;
     failed = m < few ? JAICOV_RELOR_TOO_FEW_POINTS : -1;
-    if (ro_uniform(resident && failed < 0)) stage(0, m);
+    if (wave_uniform(resident && failed < 0)) stage(0, m);
     // one loop over the passes of all rounds, so that the pass, the rotation and the angles of a start are compiled once:
     // BEGIN (-> SPACE) -> PLANE -> CHEIR -> [STEP ... STEP -> EVAL] per start -> FINAL (-> BEGIN of the next round)
     int mode = RO_BEGIN;
-    while (ro_uniform(failed < 0)) {
-        mode = ro_uniform(mode);
-        if (ro_uniform(new_state != 0)) {
+    while (wave_uniform(failed < 0)) {
+        mode = wave_uniform(mode);
+        if (wave_uniform(new_state != 0)) {
             // R(omega, phi, kappa), PDF:125-135: lanes 0, 1, 2 take the sine and cosine of one angle each (one copy of sincos)
             const double angle = lane == 0 ? sP[RO_PAR + 3] : lane == 1 ? sP[RO_PAR + 4] : sP[RO_PAR + 5];
             double sn, cs;
@@ -487,7 +312,7 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
             int ax = 0;
             if (fabs(b[1]) < fabs(b[0])) ax = 1;
             if (fabs(b[2]) < fabs(ax == 0 ? b[0] : b[1])) ax = 2;
-            ax = ro_uniform(ax);
+            ax = wave_uniform(ax);
             const double e[3] = {ax == 0 ? 1.0 : 0.0, ax == 1 ? 1.0 : 0.0, ax == 2 ? 1.0 : 0.0};
             double f[3], e1[3], e2[3];
             ro_cross(b, e, f);
@@ -503,7 +328,7 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
         bool advance = false;                             // the running start is done: the next one, or the choice
         if (mode == RO_BEGIN) {
             nstarts = 0; kinds = 0; cur = 0; bst = -1; not_finite = 0; mask = 0;
-            if (ro_uniform(nused < few)) {
+            if (wave_uniform(nused < few)) {
                 failed = JAICOV_RELOR_TOO_FEW_POINTS;
             } else if (given) {
                 const double *s = start + 6L * g;
@@ -514,27 +339,27 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
                 new_state = 1; cst = JAICOV_RELOR_NOT_CONVERGED; it = 0;
                 mode = RO_STEP;
             } else {
-                mode = ro_uniform(nused >= 8) ? RO_SPACE : RO_PLANE;
+                mode = wave_uniform(nused >= 8) ? RO_SPACE : RO_PLANE;
             }
         } else if (mode == RO_SPACE) {
             mode = RO_PLANE;
             bool finite = true;
             for (int k = 0; k < 81; k++) finite = finite && isfinite(sA[k]);
-            if (ro_uniform(!finite)) {
+            if (wave_uniform(!finite)) {
                 not_finite = 1;
             } else {
                 ro_jacobi9(sA, sA + 81);
                 int i0 = 0;
                 for (int i = 1; i < 9; i++)
                     if (sA[10 * i] < sA[10 * i0]) i0 = i;
-                i0 = ro_uniform(i0);
+                i0 = wave_uniform(i0);
                 double l1 = INFINITY, lmax = sA[10 * i0];
                 for (int i = 0; i < 9; i++) {
                     const double l = sA[10 * i];
                     if (i != i0 && l < l1) l1 = l;
                     if (l > lmax) lmax = l;
                 }
-                if (ro_uniform(l1 > SQRT_EPS * lmax)) {
+                if (wave_uniform(l1 > SQRT_EPS * lmax)) {
                     const double r2 = sqrt(2.0);
                     double E[9], S[6], lam[3], V[9], C[9], D[9], Mp[9], Mm[9];
 #pragma unroll
@@ -542,7 +367,7 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
                     S[0] = E[0] * E[0] + E[3] * E[3] + E[6] * E[6]; S[1] = E[0] * E[1] + E[3] * E[4] + E[6] * E[7];
                     S[2] = E[0] * E[2] + E[3] * E[5] + E[6] * E[8]; S[3] = E[1] * E[1] + E[4] * E[4] + E[7] * E[7];
                     S[4] = E[1] * E[2] + E[4] * E[5] + E[7] * E[8]; S[5] = E[2] * E[2] + E[5] * E[5] + E[8] * E[8];
-                    ro_eigen3(S, lam, V);
+                    wave_eigen3<RELOR_SWEEPS3>(S, lam, V);
                     const double *n = V + 6;
                     ro_cross(E + 3, E + 6, C); ro_cross(E + 6, E, C + 3); ro_cross(E, E + 3, C + 6);
                     ro_cross(E, n, D); ro_cross(E + 3, n, D + 3); ro_cross(E + 6, n, D + 6);
@@ -554,7 +379,7 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
                 }
             }
         } else if (mode == RO_PLANE) {
-            const int ps = ro_solve_lds(8, sA, sA + 36, sV);
+            const int ps = wave_solve_lds(8, sA, sA + 36, sV);
             if (ps == JAICOV_RELOR_NOT_FINITE) not_finite = 1;
             if (ps == JAICOV_RELOR_OK) {
                 const double *h = sA + 36;
@@ -562,9 +387,9 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
                 S[0] = H[0] * H[0] + H[3] * H[3] + H[6] * H[6]; S[1] = H[0] * H[1] + H[3] * H[4] + H[6] * H[7];
                 S[2] = H[0] * H[2] + H[3] * H[5] + H[6] * H[8]; S[3] = H[1] * H[1] + H[4] * H[4] + H[7] * H[7];
                 S[4] = H[1] * H[2] + H[4] * H[5] + H[7] * H[8]; S[5] = H[2] * H[2] + H[5] * H[5] + H[8] * H[8];
-                ro_eigen3(S, lam, V);
+                wave_eigen3<RELOR_SWEEPS3>(S, lam, V);
                 const double l1 = lam[0] / lam[1], l3 = lam[2] / lam[1];
-                if (ro_uniform(lam[1] > 0.0 && l1 - l3 > SQRT_EPS)) {
+                if (wave_uniform(lam[1] > 0.0 && l1 - l3 > SQRT_EPS)) {
                     const double f = sqrt(lam[1]);
 #pragma unroll
                     for (int k = 0; k < 9; k++) H[k] = H[k] / f;
@@ -598,7 +423,7 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
 #pragma unroll
                             for (int k = 0; k < 3; k++) bd[k] = -(M[k] * t[0] + M[3 + k] * t[1] + M[6 + k] * t[2]);
                             const double ln = sqrt(bd[0] * bd[0] + bd[1] * bd[1] + bd[2] * bd[2]);
-                            if (ro_uniform(!(ln > 0.0))) continue;
+                            if (wave_uniform(!(ln > 0.0))) continue;
 #pragma unroll
                             for (int k = 0; k < 3; k++) bd[k] = bd[k] / ln;
                             const int slot = 4 + 4 * is + 2 * ig;
@@ -609,7 +434,7 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
                     }
                 }
             }
-            if (ro_uniform(mask == 0)) failed = ro_uniform(not_finite != 0) ? JAICOV_RELOR_NOT_FINITE : JAICOV_RELOR_SINGULAR;
+            if (wave_uniform(mask == 0)) failed = wave_uniform(not_finite != 0) ? JAICOV_RELOR_NOT_FINITE : JAICOV_RELOR_SINGULAR;
             else mode = RO_CHEIR;
         } else if (mode == RO_CHEIR) {
             // the slots that go on, 4 bits each: the best of the space start, the (at most two) best of the plane start
@@ -618,18 +443,18 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
                 if (((mask >> s) & 1) && (space < 0 || sA[s] > sA[space])) space = s;
             for (int s = 4; s < RELOR_SLOTS; s++)
                 if (((mask >> s) & 1) && (plane < 0 || sA[s] > sA[plane])) plane = s;
-            space = ro_uniform(space); plane = ro_uniform(plane);
+            space = wave_uniform(space); plane = wave_uniform(plane);
             if (space >= 0) { picks |= space << (4 * nstarts); kinds |= JAICOV_RELOR_START_SPACE << (2 * nstarts); nstarts++; }
             if (plane >= 0) {
                 int taken = 0;
                 for (int s = plane; s < RELOR_SLOTS && taken < 2; s++)
-                    if (ro_uniform(((mask >> s) & 1) && sA[s] == sA[plane])) {
+                    if (wave_uniform(((mask >> s) & 1) && sA[s] == sA[plane])) {
                         picks |= s << (4 * nstarts); kinds |= JAICOV_RELOR_START_PLANE << (2 * nstarts); nstarts++; taken++;
                     }
             }
-            nstarts = ro_uniform(nstarts); picks = ro_uniform(picks); kinds = ro_uniform(kinds);
+            nstarts = wave_uniform(nstarts); picks = wave_uniform(picks); kinds = wave_uniform(kinds);
 #pragma unroll 1
-            for (int j = 0; j < ro_uniform(nstarts); j++) {
+            for (int j = 0; j < wave_uniform(nstarts); j++) {
                 // b and the angles of R = M' (omega by lane 0, kappa by lane 1: one copy of atan2)
                 const double *M = sC + RELOR_SLOT_LEN * ((picks >> (4 * j)) & 15);
                 const double a = atan2(lane == 0 ? -M[7] : -M[3], lane == 0 ? M[8] : M[0]);
@@ -649,13 +474,13 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
             for (int k = 0; k < 15; k++) A[k] = sA[k];
 #pragma unroll
             for (int k = 0; k < 5; k++) b[k] = sA[15 + k];
-            int ss = ro_solve<5>(A, b, dx, nullptr);
+            int ss = wave_solve<5>(A, b, dx, nullptr);
             iters++;
             if (ss == JAICOV_RELOR_OK) {
                 double z = 0.0;                           // NaN unless every value is finite
 #pragma unroll
                 for (int k = 0; k < 5; k++) z += dx[k] * 0.0;
-                if (ro_uniform(z != 0.0)) ss = JAICOV_RELOR_NOT_FINITE;
+                if (wave_uniform(z != 0.0)) ss = JAICOV_RELOR_NOT_FINITE;
             }
             if (ss != JAICOV_RELOR_OK) {
                 if (ss == JAICOV_RELOR_NOT_FINITE) not_finite = 1;
@@ -670,14 +495,14 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
 #pragma unroll
                 for (int k = 0; k < 5; k++) step = fmax(step, fabs(dx[k]));
                 new_state = 1;
-                if (ro_uniform(step <= SQRT_EPS)) { cst = JAICOV_RELOR_OK; mode = RO_EVAL; }
-                else if (ro_uniform(++it >= max_iter)) mode = RO_EVAL;
+                if (wave_uniform(step <= SQRT_EPS)) { cst = JAICOV_RELOR_OK; mode = RO_EVAL; }
+                else if (wave_uniform(++it >= max_iter)) mode = RO_EVAL;
             }
         } else if (mode == RO_EVAL) {
             const double omega = sA[20];
-            if (ro_uniform(!isfinite(omega))) {
+            if (wave_uniform(!isfinite(omega))) {
                 not_finite = 1;
-            } else if (ro_uniform(bst < 0 || cst < bst || (cst == bst && omega < sB[6] - SQRT_EPS * sB[6]))) {
+            } else if (wave_uniform(bst < 0 || cst < bst || (cst == bst && omega < sB[6] - SQRT_EPS * sB[6]))) {
 #pragma unroll
                 for (int k = 0; k < 6; k++) sB[k] = sP[RO_PAR + k];
                 sB[6] = omega;
@@ -685,7 +510,7 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
             }
             advance = true;
         } else {                                          // RO_FINAL: Q is taken from these sums after the loop
-            if (ro_uniform(thr2 > 0.0 && nused > min_points && qmax > thr2 && qidx < m)) {
+            if (wave_uniform(thr2 > 0.0 && nused > min_points && qmax > thr2 && qidx < m)) {
                 if (lane == 0) { used[k0 + qidx] = 0; if (resident) sused[qidx] = 0; }
                 __syncthreads();                          // the withdrawal is visible to every lane before the next pass reads it
                 nused--;
@@ -696,13 +521,13 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
         }
         if (advance) {
             cur++;
-            if (ro_uniform(cur < nstarts)) {
+            if (wave_uniform(cur < nstarts)) {
 #pragma unroll
                 for (int k = 0; k < 6; k++) sP[RO_PAR + k] = sS[6 * cur + k];
                 new_state = 1; cst = JAICOV_RELOR_NOT_CONVERGED; it = 0;
                 mode = RO_STEP;
-            } else if (ro_uniform(bst < 0)) {
-                failed = ro_uniform(not_finite != 0) ? JAICOV_RELOR_NOT_FINITE : JAICOV_RELOR_SINGULAR;
+            } else if (wave_uniform(bst < 0)) {
+                failed = wave_uniform(not_finite != 0) ? JAICOV_RELOR_NOT_FINITE : JAICOV_RELOR_SINGULAR;
             } else {
 #pragma unroll
                 for (int k = 0; k < 6; k++) sP[RO_PAR + k] = sB[k];
@@ -712,13 +537,13 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
         }
     }
     double o[JAICOV_RELOR_OUT_PER_PAIR];
-    if (ro_uniform(failed < 0)) {
+    if (wave_uniform(failed < 0)) {
         double A[15], b[5], Q[15];
 #pragma unroll
         for (int k = 0; k < 15; k++) A[k] = sA[k];
 #pragma unroll
         for (int k = 0; k < 5; k++) b[k] = sA[15 + k];
-        const int se = ro_solve<5>(A, b, nullptr, Q);
+        const int se = wave_solve<5>(A, b, nullptr, Q);
         if (se != JAICOV_RELOR_OK) failed = se;
         const double *e1 = sP + RO_E1, *e2 = sP + RO_E2;
 #pragma unroll
@@ -729,23 +554,23 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
             for (int j = i; j < 6; j++) {
                 double v;
                 if (i < 3 && j < 3) {
-                    const double t0 = e1[i] * Q[ro_ix<5>(0, 0)] + e2[i] * Q[ro_ix<5>(0, 1)];
-                    const double t1 = e1[i] * Q[ro_ix<5>(0, 1)] + e2[i] * Q[ro_ix<5>(1, 1)];
+                    const double t0 = e1[i] * Q[tri_ix<5>(0, 0)] + e2[i] * Q[tri_ix<5>(0, 1)];
+                    const double t1 = e1[i] * Q[tri_ix<5>(0, 1)] + e2[i] * Q[tri_ix<5>(1, 1)];
                     v = t0 * e1[j] + t1 * e2[j];
                 } else if (i < 3) {
-                    v = e1[i] * Q[ro_ix<5>(0, j - 1)] + e2[i] * Q[ro_ix<5>(1, j - 1)];
+                    v = e1[i] * Q[tri_ix<5>(0, j - 1)] + e2[i] * Q[tri_ix<5>(1, j - 1)];
                 } else {
-                    v = Q[ro_ix<5>(i - 1, j - 1)];
+                    v = Q[tri_ix<5>(i - 1, j - 1)];
                 }
-                o[6 + ro_ix<6>(i, j)] = v;
+                o[6 + tri_ix<6>(i, j)] = v;
             }
         o[27] = sA[20];
         double z = 0.0;
 #pragma unroll
         for (int k = 0; k < JAICOV_RELOR_OUT_PER_PAIR; k++) z += o[k] * 0.0;
-        if (ro_uniform(failed < 0 && z != 0.0)) failed = JAICOV_RELOR_NOT_FINITE;
+        if (wave_uniform(failed < 0 && z != 0.0)) failed = JAICOV_RELOR_NOT_FINITE;
     }
-    if (ro_uniform(failed >= 0)) { fail(ro_uniform(failed)); return; }
+    if (wave_uniform(failed >= 0)) { fail(wave_uniform(failed)); return; }
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < JAICOV_RELOR_OUT_PER_PAIR; k++) og[k] = o[k];
@@ -753,15 +578,6 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
         outcome[3L * g + 1] = iters;
         outcome[3L * g + 2] = kind;
     }
-}
-
-bool relor_device_ok() {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return false;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    return strncmp(prop.gcnArchName, "gfx950", 6) == 0;
 }
 
 }  // namespace
@@ -777,68 +593,60 @@ extern "C" int jaicov_relorient_pairs(int32_t n_pairs, const int32_t *obs_begin,
     if (n_pairs < 0 || !obs_begin) return JAICOV_ERR_BAD_ARGUMENT;
     if (!(sigma2apriori > 0.0) || max_iterations < 1 || min_points < 5 || !(reject_threshold >= 0.0)) return JAICOV_ERR_BAD_ARGUMENT;
     if (n_pairs > 0 && (!out || !status || !pair_io)) return JAICOV_ERR_BAD_ARGUMENT;
-    if (obs_begin[0] != 0) return JAICOV_ERR_BAD_ARGUMENT;
-    for (int32_t g = 0; g < n_pairs; g++)
-        if (obs_begin[g + 1] < obs_begin[g]) return JAICOV_ERR_BAD_ARGUMENT;
+    if (!ranges_ok(n_pairs, obs_begin)) return JAICOV_ERR_BAD_ARGUMENT;
     const long n_obs = obs_begin[n_pairs];
     if (n_obs > 0 && (!xy_a || !xy_b)) return JAICOV_ERR_BAD_ARGUMENT;
-    for (const double *var : {var_a, var_b})
-        if (var)
-            for (long k = 0; k < n_obs; k++)
-                if (!(var[3 * k] > 0.0) || !(var[3 * k + 1] > 0.0) || !(fabs(var[3 * k + 2]) < 1.0)) return JAICOV_ERR_BAD_ARGUMENT;
+    if (!dispersions_ok(var_a, n_obs) || !dispersions_ok(var_b, n_obs)) return JAICOV_ERR_BAD_ARGUMENT;
 
-    if (!relor_device_ok()) return JAICOV_ERR_NO_DEVICE;
+    if (!device_is_gfx950()) return JAICOV_ERR_NO_DEVICE;
     if (ms_out) *ms_out = 0.0;
     if (n_pairs == 0) return JAICOV_OK;
 
-    hipStream_t s;
-    if (hipStreamCreate(&s) != hipSuccess) return JAICOV_ERR_DEVICE;
-    const int rc = [&]() -> int {      // the owners go before the stream does
-        int32_t *d_begin = nullptr, *d_outcome = nullptr;
-        double *d_xa = nullptr, *d_xb = nullptr, *d_va = nullptr, *d_vb = nullptr, *d_io = nullptr, *d_start = nullptr, *d_out = nullptr,
-               *d_q = nullptr;
-        uint8_t *d_used = nullptr;
-        DevBag bag;
-        DevEvent ev0, ev1;
-        if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-        const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
-        const size_t np = (size_t)n_pairs, no = (size_t)(n_obs > 0 ? n_obs : 1);
-        std::vector<int32_t> h_outcome(3 * np);
-        if (bag.alloc(&d_begin, np + 1) != hipSuccess || bag.alloc(&d_xa, 2 * no) != hipSuccess || bag.alloc(&d_xb, 2 * no) != hipSuccess ||
-            (var_a && bag.alloc(&d_va, 3 * no) != hipSuccess) || (var_b && bag.alloc(&d_vb, 3 * no) != hipSuccess) ||
-            bag.alloc(&d_io, 6 * np) != hipSuccess || (start && bag.alloc(&d_start, 6 * np) != hipSuccess) ||
-            bag.alloc(&d_out, JAICOV_RELOR_OUT_PER_PAIR * np) != hipSuccess || bag.alloc(&d_outcome, 3 * np) != hipSuccess ||
-            bag.alloc(&d_used, no) != hipSuccess || (obs_q && bag.alloc(&d_q, no) != hipSuccess))
-            return JAICOV_ERR_OUT_OF_MEMORY;
-        hipMemcpyAsync(d_begin, obs_begin, (np + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
-        if (n_obs > 0) {
-            hipMemcpyAsync(d_xa, xy_a, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-            hipMemcpyAsync(d_xb, xy_b, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-            if (var_a) hipMemcpyAsync(d_va, var_a, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-            if (var_b) hipMemcpyAsync(d_vb, var_b, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-        }
-        hipMemcpyAsync(d_io, pair_io, 6 * np * sizeof(double), hipMemcpyHostToDevice, s);
-        if (start) hipMemcpyAsync(d_start, start, 6 * np * sizeof(double), hipMemcpyHostToDevice, s);
-        hipMemsetAsync(d_used, 1, no, s);                                  // every observation starts as used
-        hipEventRecord(e0, s);
-        hipLaunchKernelGGL(relorient_pairs_kernel, dim3(n_pairs), dim3(RELOR_LANES), 0, s, d_begin, d_xa, d_xb, d_va, d_vb, d_io, d_start,
-                           sigma2apriori, (int)max_iterations, reject_threshold * reject_threshold, (int)min_points, d_out, d_outcome, d_used,
-                           d_q);
-        if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
-        hipEventRecord(e1, s);
-        hipMemcpyAsync(out, d_out, JAICOV_RELOR_OUT_PER_PAIR * np * sizeof(double), hipMemcpyDeviceToHost, s);
-        hipMemcpyAsync(h_outcome.data(), d_outcome, 3 * np * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        if (obs_used && n_obs > 0) hipMemcpyAsync(obs_used, d_used, (size_t)n_obs, hipMemcpyDeviceToHost, s);
-        if (obs_q && n_obs > 0) hipMemcpyAsync(obs_q, d_q, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost, s);
-        if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
-        for (size_t g = 0; g < np; g++) {
-            status[g] = h_outcome[3 * g];
-            if (iterations) iterations[g] = h_outcome[3 * g + 1];
-            if (start_kind) start_kind[g] = h_outcome[3 * g + 2];
-        }
-        if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-        return JAICOV_OK;
-    }();
-    hipStreamDestroy(s);
-    return rc;
+    DevStream stream;                  // first, so that the other owners go before the stream does
+    if (stream.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipStream_t s = stream.get();
+    int32_t *d_begin = nullptr, *d_outcome = nullptr;
+    double *d_xa = nullptr, *d_xb = nullptr, *d_va = nullptr, *d_vb = nullptr, *d_io = nullptr, *d_start = nullptr, *d_out = nullptr,
+           *d_q = nullptr;
+    uint8_t *d_used = nullptr;
+    DevBag bag;
+    DevEvent ev0, ev1;
+    if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
+    const size_t np = (size_t)n_pairs, no = (size_t)(n_obs > 0 ? n_obs : 1);
+    std::vector<int32_t> h_outcome(3 * np);
+    if (bag.alloc(&d_begin, np + 1) != hipSuccess || bag.alloc(&d_xa, 2 * no) != hipSuccess || bag.alloc(&d_xb, 2 * no) != hipSuccess ||
+        (var_a && bag.alloc(&d_va, 3 * no) != hipSuccess) || (var_b && bag.alloc(&d_vb, 3 * no) != hipSuccess) ||
+        bag.alloc(&d_io, 6 * np) != hipSuccess || (start && bag.alloc(&d_start, 6 * np) != hipSuccess) ||
+        bag.alloc(&d_out, JAICOV_RELOR_OUT_PER_PAIR * np) != hipSuccess || bag.alloc(&d_outcome, 3 * np) != hipSuccess ||
+        bag.alloc(&d_used, no) != hipSuccess || (obs_q && bag.alloc(&d_q, no) != hipSuccess))
+        return JAICOV_ERR_OUT_OF_MEMORY;
+    hipMemcpyAsync(d_begin, obs_begin, (np + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
+    if (n_obs > 0) {
+        hipMemcpyAsync(d_xa, xy_a, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+        hipMemcpyAsync(d_xb, xy_b, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+        if (var_a) hipMemcpyAsync(d_va, var_a, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+        if (var_b) hipMemcpyAsync(d_vb, var_b, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+    }
+    hipMemcpyAsync(d_io, pair_io, 6 * np * sizeof(double), hipMemcpyHostToDevice, s);
+    if (start) hipMemcpyAsync(d_start, start, 6 * np * sizeof(double), hipMemcpyHostToDevice, s);
+    hipMemsetAsync(d_used, 1, no, s);                                  // every observation starts as used
+    hipEventRecord(e0, s);
+    hipLaunchKernelGGL(relorient_pairs_kernel, dim3(n_pairs), dim3(RELOR_LANES), 0, s, d_begin, d_xa, d_xb, d_va, d_vb, d_io, d_start,
+                       sigma2apriori, (int)max_iterations, reject_threshold * reject_threshold, (int)min_points, d_out, d_outcome, d_used,
+                       d_q);
+    if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
+    hipEventRecord(e1, s);
+    hipMemcpyAsync(out, d_out, JAICOV_RELOR_OUT_PER_PAIR * np * sizeof(double), hipMemcpyDeviceToHost, s);
+    hipMemcpyAsync(h_outcome.data(), d_outcome, 3 * np * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (obs_used && n_obs > 0) hipMemcpyAsync(obs_used, d_used, (size_t)n_obs, hipMemcpyDeviceToHost, s);
+    if (obs_q && n_obs > 0) hipMemcpyAsync(obs_q, d_q, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
+    for (size_t g = 0; g < np; g++) {
+        status[g] = h_outcome[3 * g];
+        if (iterations) iterations[g] = h_outcome[3 * g + 1];
+        if (start_kind) start_kind[g] = h_outcome[3 * g + 2];
+    }
+    if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
+    return JAICOV_OK;
 }

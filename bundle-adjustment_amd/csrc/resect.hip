@@ -27,8 +27,10 @@
 #include <vector>
 
 #include "../../include/jaicov_resect.h"
+#include "batchcall.h"
 #include "devbuf.h"
 #include "resect.h"
+#include "wavealg.h"
 
 #pragma clang fp contract(off)
 
@@ -37,137 +39,9 @@ namespace {
 
 enum { RS_CENTROID = 0, RS_SCATTER, RS_SPACE, RS_EVAL_SPACE, RS_PLANE, RS_EVAL_PLANE, RS_STEP, RS_EVAL };
 
-// A value that is the same in every lane, said so to the compiler: the sums come out of the butterfly equal in all lanes, but the
-// compiler cannot know it, and would mask every branch on them lane by lane and keep both sides' values alive across it.
-__device__ inline int rs_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ inline bool rs_uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
-
-// index of (i, j >= i) in an upper triangle of order N packed row by row
-template <int N>
-__device__ constexpr int rs_ix(int i, int j) { return i * N - i * (i - 1) / 2 + (j - i); }
-
-// A (packed upper, order N) x = b by Jacobi preconditioning (NES:82-91) and Cholesky; Q (may be NULL, packed upper): the inverse of A.
-// A is overwritten by the factor, so that no second triangle is live beside the pass's sums.
-template <int N>
-__device__ inline int rs_solve(double *U, const double *b, double *x, double *Q) {
-    const double EPS = ldexp(1.0, -53), SQRT_EPS = sqrt(EPS);
-    constexpr int LEN = N * (N + 1) / 2;
-    double z = 0.0;                       // NaN unless every value is finite
-#pragma unroll
-    for (int k = 0; k < LEN; k++) z += U[k] * 0.0;
-#pragma unroll
-    for (int k = 0; k < N; k++) z += b[k] * 0.0;
-    if (rs_uniform(z != 0.0)) return JAICOV_RESECT_NOT_FINITE;
-    double V[N];                          // U'U = V A V, U upper
-#pragma unroll
-    for (int i = 0; i < N; i++) V[i] = U[rs_ix<N>(i, i)] > EPS ? 1.0 / sqrt(U[rs_ix<N>(i, i)]) : 1.0;
-#pragma unroll
-    for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int j = i; j < N; j++) U[rs_ix<N>(i, j)] = U[rs_ix<N>(i, j)] * (V[i] * V[j]);
-    bool singular = false;
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < j; k++) s += U[rs_ix<N>(k, j)] * U[rs_ix<N>(k, j)];
-        const double p = U[rs_ix<N>(j, j)] - s;
-        singular = singular || !(p > SQRT_EPS);
-        const double d = sqrt(p);
-        U[rs_ix<N>(j, j)] = d;
-#pragma unroll
-        for (int i = j + 1; i < N; i++) {
-            double r = 0.0;
-#pragma unroll
-            for (int k = 0; k < j; k++) r += U[rs_ix<N>(k, i)] * U[rs_ix<N>(k, j)];
-            U[rs_ix<N>(j, i)] = (U[rs_ix<N>(j, i)] - r) / d;
-        }
-    }
-    if (rs_uniform(singular)) return JAICOV_RESECT_SINGULAR;      // every pivot after the first bad one is garbage and is not used
-    if (x) {
-        double y[N];
-#pragma unroll
-        for (int i = 0; i < N; i++) {
-            double r = 0.0;
-#pragma unroll
-            for (int k = 0; k < i; k++) r += U[rs_ix<N>(k, i)] * y[k];
-            y[i] = (V[i] * b[i] - r) / U[rs_ix<N>(i, i)];
-        }
-#pragma unroll
-        for (int i = N - 1; i >= 0; i--) {
-            double r = 0.0;
-#pragma unroll
-            for (int k = i + 1; k < N; k++) r += U[rs_ix<N>(i, k)] * y[k];
-            y[i] = (y[i] - r) / U[rs_ix<N>(i, i)];
-        }
-#pragma unroll
-        for (int i = 0; i < N; i++) x[i] = V[i] * y[i];
-    }
-    if (Q) {
-        double W[LEN];                    // W = inverse of U, upper: W[i][j], j >= i
-#pragma unroll
-        for (int j = 0; j < N; j++) {
-            W[rs_ix<N>(j, j)] = 1.0 / U[rs_ix<N>(j, j)];
-#pragma unroll
-            for (int i = j - 1; i >= 0; i--) {
-                double r = 0.0;
-#pragma unroll
-                for (int k = i + 1; k <= j; k++) r += U[rs_ix<N>(i, k)] * W[rs_ix<N>(k, j)];
-                W[rs_ix<N>(i, j)] = -r / U[rs_ix<N>(i, i)];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < N; i++)
-#pragma unroll
-            for (int j = i; j < N; j++) {                 // inverse of V A V = W W'
-                double r = 0.0;
-#pragma unroll
-                for (int k = j; k < N; k++) r += W[rs_ix<N>(i, k)] * W[rs_ix<N>(j, k)];
-                Q[rs_ix<N>(i, j)] = r * (V[i] * V[j]);
-            }
-    }
-    return JAICOV_RESECT_OK;
-}
-
-// The same solve for the linear starts (order 11 or 8), on a system held in LDS: U (packed upper, overwritten by the factor), b
-// (overwritten by x), V.  Every lane runs it on the same words and stores what every other lane stores, so it needs no barrier and
-// its loops stay rolled: the triangle of order 11 unrolled into registers beside the pass's sums does not fit the register file.
-__device__ inline int rs_solve_lds(int n, double *U, double *b, double *V) {
-    const double EPS = ldexp(1.0, -53), SQRT_EPS = sqrt(EPS);
-    auto ix = [n](int i, int j) { return i * n - i * (i - 1) / 2 + (j - i); };
-    bool finite = true;
-    for (int k = 0; k < n * (n + 1) / 2; k++) finite = finite && isfinite(U[k]);
-    for (int k = 0; k < n; k++) finite = finite && isfinite(b[k]);
-    if (rs_uniform(!finite)) return JAICOV_RESECT_NOT_FINITE;
-    for (int i = 0; i < n; i++) V[i] = U[ix(i, i)] > EPS ? 1.0 / sqrt(U[ix(i, i)]) : 1.0;
-    for (int i = 0; i < n; i++)
-        for (int j = i; j < n; j++) U[ix(i, j)] = U[ix(i, j)] * (V[i] * V[j]);
-    for (int j = 0; j < n; j++) {
-        double s = 0.0;
-        for (int k = 0; k < j; k++) s += U[ix(k, j)] * U[ix(k, j)];
-        const double p = U[ix(j, j)] - s;
-        if (rs_uniform(!(p > SQRT_EPS))) return JAICOV_RESECT_SINGULAR;
-        const double d = sqrt(p);
-        U[ix(j, j)] = d;
-        for (int i = j + 1; i < n; i++) {
-            double r = 0.0;
-            for (int k = 0; k < j; k++) r += U[ix(k, i)] * U[ix(k, j)];
-            U[ix(j, i)] = (U[ix(j, i)] - r) / d;
-        }
-    }
-    for (int i = 0; i < n; i++) {
-        double r = 0.0;
-        for (int k = 0; k < i; k++) r += U[ix(k, i)] * b[k];
-        b[i] = (V[i] * b[i] - r) / U[ix(i, i)];
-    }
-    for (int i = n - 1; i >= 0; i--) {
-        double r = 0.0;
-        for (int k = i + 1; k < n; k++) r += U[ix(i, k)] * b[k];
-        b[i] = (b[i] - r) / U[ix(i, i)];
-    }
-    for (int i = 0; i < n; i++) b[i] = V[i] * b[i];
-    return JAICOV_RESECT_OK;
-}
+// the solves' statuses (wavealg.h) go out as the call's own
+static_assert(JAICOV_RESECT_OK == WAVE_OK && JAICOV_RESECT_SINGULAR == WAVE_SINGULAR && JAICOV_RESECT_NOT_FINITE == WAVE_NOT_FINITE,
+              "wavealg.h returns the public status values");
 
 // the orthogonal polar factor of X (3 x 3, row-major), in place: Newton's iteration from X / sqrt(|X|_F^2 / 3)
 __device__ inline void rs_polar(double *X) {
@@ -188,44 +62,10 @@ __device__ inline void rs_polar(double *X) {
     }
 }
 
-// one Jacobi rotation in the plane (p, q) of a symmetric 3 x 3 matrix; r is the third index; wp, wq: the eigenvector rows p and q
-__device__ inline void rs_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double *wp, double *wq) {
-    if (rs_uniform(apq == 0.0)) return;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    app = app - t * apq; aqq = aqq + t * apq; apq = 0.0;
-    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
-    arp = rp; arq = rq;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const double vp = c * wp[k] - s * wq[k], vq = s * wp[k] + c * wq[k];
-        wp[k] = vp; wq[k] = vq;
-    }
-}
-
 // eigenvectors of the scatter matrix S (00 01 02 11 12 22) as the rows of E: e1, e2 (falling eigenvalue), n with det = +1
 __device__ inline void rs_eigen(const double *S, double *E) {
-    double a00 = S[0], a01 = S[1], a02 = S[2], a11 = S[3], a12 = S[4], a22 = S[5];
-    double W[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-    for (int sweep = 0; sweep < RESECT_JACOBI_SWEEPS; sweep++) {
-        rs_rotate(a00, a11, a01, a02, a12, W, W + 3);
-        rs_rotate(a00, a22, a02, a01, a12, W, W + 6);
-        rs_rotate(a11, a22, a12, a01, a02, W + 3, W + 6);
-    }
-    auto order = [&](double &la, double &lb, double *wa, double *wb) {      // the larger eigenvalue first; equal ones keep their order
-        if (rs_uniform(!(la < lb))) return;
-        const double l = la; la = lb; lb = l;
-#pragma unroll
-        for (int k = 0; k < 3; k++) { const double w = wa[k]; wa[k] = wb[k]; wb[k] = w; }
-    };
-    order(a00, a11, W, W + 3);
-    order(a11, a22, W + 3, W + 6);
-    order(a00, a11, W, W + 3);
-    const double n0 = W[1] * W[5] - W[2] * W[4], n1 = W[2] * W[3] - W[0] * W[5], n2 = W[0] * W[4] - W[1] * W[3];   // e1 x e2
-    if (n0 * W[6] + n1 * W[7] + n2 * W[8] < 0.0) { W[6] = -W[6]; W[7] = -W[7]; W[8] = -W[8]; }
-#pragma unroll
-    for (int k = 0; k < 9; k++) E[k] = W[k];
+    double lam[3];
+    wave_eigen3<RESECT_JACOBI_SWEEPS>(S, lam, E);
 }
 
 // R(omega, phi, kappa), PDF:125-135, row-major.  Lanes 0, 1, 2 take the sine and cosine of one angle each and hand them to the wave,
@@ -268,7 +108,7 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
     // sin and cos of kappa, the plane's axes e1 e2 n, the space candidate's unknowns and Omega.  They live in LDS, not in registers:
     // between two passes the registers hold the small algebra, during a pass the lane's partial sums, never both.
     // The workgroup is one wave (RESECT_LANES == 64, the launch and the launch bound use the same constant), and all of this rests on
-    // it: every lane stores the same value to the same word and reads it back, rs_solve_lds reads and rewrites sA in place, and no
+    // it: every lane stores the same value to the same word and reads it back, wave_solve_lds reads and rewrites sA in place, and no
     // barrier stands between such a store and the reads that follow, because the LDS operations of one wave complete in order.
     // With more than one wave per workgroup none of it would hold.
     static_assert(RESECT_LANES == 64, "one wave per image: the uniform state in LDS relies on it");
@@ -301,15 +141,7 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
             sx[t] = xy[2 * k]; sy[t] = xy[2 * k + 1];
             sX[t] = xyz[3 * k]; sY[t] = xyz[3 * k + 1]; sZ[t] = xyz[3 * k + 2];
             double p11 = 1.0, p12 = 0.0, p22 = 1.0;
-            if (var) {
-                const double vx = var[3 * k], vy = var[3 * k + 1], rho = var[3 * k + 2];
-                if (rho == 0.0) {
-                    p11 = s0 / vx; p22 = s0 / vy;
-                } else {
-                    const double inv = s0 / ((1.0 - rho * rho) * vx * vy);
-                    p11 = inv * vy; p22 = inv * vx; p12 = -inv * rho * sqrt(vx * vy);
-                }
-            }
+            if (var) obs_weight(var[3 * k], var[3 * k + 1], var[3 * k + 2], s0, p11, p12, p22);
             sp11[t] = p11; sp12[t] = p12; sp22[t] = p22;
             sused[t] = used[k];
         }
@@ -351,7 +183,7 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
 #pragma unroll
                     for (int i = 0; i < 4; i++) {
 #pragma unroll
-                        for (int j = i; j < 4; j++) acc[rs_ix<4>(i, j)] += G[i] * G[j];
+                        for (int j = i; j < 4; j++) acc[tri_ix<4>(i, j)] += G[i] * G[j];
 #pragma unroll
                         for (int j = 0; j < 3; j++) { acc[10 + 3 * i + j] += G[i] * au[j]; acc[22 + 3 * i + j] += G[i] * bv[j]; }
                         acc[40 + i] += G[i] * u;
@@ -360,7 +192,7 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
 #pragma unroll
                     for (int i = 0; i < 3; i++) {
 #pragma unroll
-                        for (int j = i; j < 3; j++) acc[34 + rs_ix<3>(i, j)] += au[i] * au[j] + bv[i] * bv[j];
+                        for (int j = i; j < 3; j++) acc[34 + tri_ix<3>(i, j)] += au[i] * au[j] + bv[i] * bv[j];
                         acc[48 + i] += au[i] * u + bv[i] * v;
                     }
                 } else if (mode == RS_PLANE) {
@@ -372,7 +204,7 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
 #pragma unroll
                     for (int i = 0; i < 8; i++) {
 #pragma unroll
-                        for (int j = i; j < 8; j++) acc[rs_ix<8>(i, j)] += a[i] * a[j] + b[i] * b[j];
+                        for (int j = i; j < 8; j++) acc[tri_ix<8>(i, j)] += a[i] * a[j] + b[i] * b[j];
                         acc[36 + i] += a[i] * u + b[i] * v;
                     }
                 } else {                                  // the collinearity equations at the unknowns, in the reduced coordinates
@@ -400,7 +232,7 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
 #pragma unroll
                     for (int i = 0; i < 6; i++) {
 #pragma unroll
-                        for (int j = i; j < 6; j++) acc[rs_ix<6>(i, j)] += ax[i] * px[j] + ay[i] * py[j];
+                        for (int j = i; j < 6; j++) acc[tri_ix<6>(i, j)] += ax[i] * px[j] + ay[i] * py[j];
                         acc[21 + i] += ax[i] * pw0 + ay[i] * pw1;
                     }
                     acc[27] += q;
@@ -415,27 +247,25 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
 #pragma unroll
                 for (int a = RESECT_NACC_STEP; a < RESECT_NACC; a++) acc[a] += __shfl_xor(acc[a], off);
             }
-            const double oq = __shfl_xor(qmax, off);
-            const int oi = __shfl_xor(qidx, off);
-            if (oq > qmax || (oq == qmax && oi < qidx)) { qmax = oq; qidx = oi; }
+            wave_argmax_combine(qmax, qidx, off);
         }
         __syncthreads();                                  // the last reads of the state and of the sums before
         if (mode == RS_SPACE) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
 #pragma unroll
-                for (int j = i; j < 4; j++) sA[rs_ix<11>(i, j)] = sA[rs_ix<11>(4 + i, 4 + j)] = acc[rs_ix<4>(i, j)];
+                for (int j = i; j < 4; j++) sA[tri_ix<11>(i, j)] = sA[tri_ix<11>(4 + i, 4 + j)] = acc[tri_ix<4>(i, j)];
 #pragma unroll
-                for (int j = 0; j < 4; j++) sA[rs_ix<11>(i, 4 + j)] = 0.0;
+                for (int j = 0; j < 4; j++) sA[tri_ix<11>(i, 4 + j)] = 0.0;
 #pragma unroll
-                for (int j = 0; j < 3; j++) { sA[rs_ix<11>(i, 8 + j)] = acc[10 + 3 * i + j]; sA[rs_ix<11>(4 + i, 8 + j)] = acc[22 + 3 * i + j]; }
+                for (int j = 0; j < 3; j++) { sA[tri_ix<11>(i, 8 + j)] = acc[10 + 3 * i + j]; sA[tri_ix<11>(4 + i, 8 + j)] = acc[22 + 3 * i + j]; }
                 sA[66 + i] = acc[40 + i];
                 sA[70 + i] = acc[44 + i];
             }
 #pragma unroll
             for (int i = 0; i < 3; i++) {
 #pragma unroll
-                for (int j = i; j < 3; j++) sA[rs_ix<11>(8 + i, 8 + j)] = acc[34 + rs_ix<3>(i, j)];
+                for (int j = i; j < 3; j++) sA[tri_ix<11>(8 + i, 8 + j)] = acc[34 + tri_ix<3>(i, j)];
                 sA[74 + i] = acc[48 + i];
             }
         } else {
@@ -456,7 +286,7 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
     // CENTROID -> SCATTER (-> SPACE -> EVAL_SPACE) -> PLANE -> EVAL_PLANE -> STEP ... STEP -> EVAL (-> CENTROID of the next round)
     int mode = RS_CENTROID, it = 0;
     while (failed < 0) {
-        mode = rs_uniform(mode);
+        mode = wave_uniform(mode);
         if (new_angles) { rs_rotation(lane, sP + RS_PAR, sP + RS_R, sP[RS_SK], sP[RS_CK]); new_angles = false; }
         pass(mode, qmax, qidx);
         double M[9], t[3];                                // a linear start's pose p = M P + t, when it has one
@@ -470,9 +300,9 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
             const double s2 = ((sA[0] + sA[3]) + sA[5]) / (double)nused, s = sqrt(s2);
             sP[RS_S] = s;
             st = JAICOV_RESECT_NOT_CONVERGED; it = 0;
-            if (rs_uniform(!isfinite(s2))) {
+            if (wave_uniform(!isfinite(s2))) {
                 failed = JAICOV_RESECT_NOT_FINITE;
-            } else if (rs_uniform(!(s > 0.0))) {
+            } else if (wave_uniform(!(s > 0.0))) {
                 failed = JAICOV_RESECT_SINGULAR;
             } else if (given) {
 #pragma unroll
@@ -496,7 +326,7 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
                 mode = nused >= 6 ? RS_SPACE : RS_PLANE;
             }
         } else if (mode == RS_SPACE) {
-            cand_st = rs_solve_lds(11, sA, sA + 66, sV);
+            cand_st = wave_solve_lds(11, sA, sA + 66, sV);
             mode = RS_PLANE;
             if (cand_st == JAICOV_RESECT_OK) {
                 const double *h = sA + 66;
@@ -520,14 +350,14 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
                 mode = RS_EVAL_SPACE;
             }
         } else if (mode == RS_EVAL_SPACE) {
-            have_cand = rs_uniform(isfinite(sA[27]));
+            have_cand = wave_uniform(isfinite(sA[27]));
             if (!have_cand) cand_st = JAICOV_RESECT_NOT_FINITE;
             sP[RS_CAND + 6] = sA[27];
 #pragma unroll
             for (int k = 0; k < 6; k++) sP[RS_CAND + k] = sP[RS_PAR + k];
             mode = RS_PLANE;
         } else if (mode == RS_PLANE) {
-            plane_st = rs_solve_lds(8, sA, sA + 36, sV);
+            plane_st = wave_solve_lds(8, sA, sA + 36, sV);
             choose = plane_st != JAICOV_RESECT_OK;
             if (plane_st == JAICOV_RESECT_OK) {
                 const double *h = sA + 36, *E = sP + RS_E;
@@ -547,7 +377,7 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
                 mode = RS_EVAL_PLANE;
             }
         } else if (mode == RS_EVAL_PLANE) {
-            plane_st = rs_uniform(isfinite(sA[27])) ? JAICOV_RESECT_OK : JAICOV_RESECT_NOT_FINITE;
+            plane_st = wave_uniform(isfinite(sA[27])) ? JAICOV_RESECT_OK : JAICOV_RESECT_NOT_FINITE;
             choose = true;
         } else if (mode == RS_STEP) {
             double A[21], b[6], dx[6];
@@ -555,13 +385,13 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
             for (int k = 0; k < 21; k++) A[k] = sA[k];
 #pragma unroll
             for (int k = 0; k < 6; k++) b[k] = sA[21 + k];
-            int ss = rs_solve<6>(A, b, dx, nullptr);
+            int ss = wave_solve<6>(A, b, dx, nullptr);
             iters++;
             if (ss == JAICOV_RESECT_OK) {
                 double z = 0.0;                           // NaN unless every value is finite
 #pragma unroll
                 for (int k = 0; k < 6; k++) z += dx[k] * 0.0;
-                if (rs_uniform(z != 0.0)) ss = JAICOV_RESECT_NOT_FINITE;
+                if (wave_uniform(z != 0.0)) ss = JAICOV_RESECT_NOT_FINITE;
             }
             if (ss != JAICOV_RESECT_OK) {
                 failed = ss;
@@ -570,11 +400,11 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
 #pragma unroll
                 for (int k = 0; k < 6; k++) { sP[RS_PAR + k] = sP[RS_PAR + k] + dx[k]; step = fmax(step, fabs(dx[k])); }
                 new_angles = true;
-                if (rs_uniform(step <= SQRT_EPS)) { st = JAICOV_RESECT_OK; mode = RS_EVAL; }
+                if (wave_uniform(step <= SQRT_EPS)) { st = JAICOV_RESECT_OK; mode = RS_EVAL; }
                 else if (++it >= max_iter) mode = RS_EVAL;
             }
         } else {                                          // RS_EVAL: Q is taken from these sums after the loop
-            if (rs_uniform(thr2 > 0.0 && nused > min_points && qmax > thr2 && qidx < m)) {
+            if (wave_uniform(thr2 > 0.0 && nused > min_points && qmax > thr2 && qidx < m)) {
                 if (lane == 0) { used[k0 + qidx] = 0; if (resident) sused[qidx] = 0; }
                 __syncthreads();                          // the withdrawal is visible to every lane before the next pass reads it
                 nused--;
@@ -588,7 +418,7 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
             if (!have_plane && !have_cand) {
                 failed = plane_st == JAICOV_RESECT_NOT_FINITE || cand_st == JAICOV_RESECT_NOT_FINITE ? JAICOV_RESECT_NOT_FINITE
                                                                                                      : JAICOV_RESECT_SINGULAR;
-            } else if (rs_uniform(have_cand && (!have_plane || sP[RS_CAND + 6] < sA[27]))) {
+            } else if (wave_uniform(have_cand && (!have_plane || sP[RS_CAND + 6] < sA[27]))) {
 #pragma unroll
                 for (int k = 0; k < 6; k++) sP[RS_PAR + k] = sP[RS_CAND + k];
                 new_angles = true;
@@ -607,7 +437,7 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
         for (int k = 0; k < 21; k++) A[k] = sA[k];
 #pragma unroll
         for (int k = 0; k < 6; k++) b[k] = sA[21 + k];
-        const int se = rs_solve<6>(A, b, nullptr, Q);
+        const int se = wave_solve<6>(A, b, nullptr, Q);
         if (se != JAICOV_RESECT_OK) failed = se;
         const double s = sP[RS_S];
 #pragma unroll
@@ -617,13 +447,13 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
 #pragma unroll
             for (int j = i; j < 6; j++) {
                 const double f = (i < 3 ? s : 1.0) * (j < 3 ? s : 1.0);     // X0 = Xc + s X0r
-                o[6 + rs_ix<6>(i, j)] = Q[rs_ix<6>(i, j)] * f;
+                o[6 + tri_ix<6>(i, j)] = Q[tri_ix<6>(i, j)] * f;
             }
         o[27] = sA[27];
         double z = 0.0;
 #pragma unroll
         for (int k = 0; k < JAICOV_RESECT_OUT_PER_IMAGE; k++) z += o[k] * 0.0;
-        if (failed < 0 && rs_uniform(z != 0.0)) failed = JAICOV_RESECT_NOT_FINITE;
+        if (failed < 0 && wave_uniform(z != 0.0)) failed = JAICOV_RESECT_NOT_FINITE;
     }
     if (failed >= 0) { fail(failed); return; }
     if (lane == 0) {
@@ -633,15 +463,6 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
         outcome[3L * g + 1] = iters;
         outcome[3L * g + 2] = kind;
     }
-}
-
-bool resect_device_ok() {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return false;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    return strncmp(prop.gcnArchName, "gfx950", 6) == 0;
 }
 
 }  // namespace
@@ -657,63 +478,56 @@ extern "C" int jaicov_resect_images(int32_t n_images, const int32_t *obs_begin, 
     if (n_images < 0 || !obs_begin) return JAICOV_ERR_BAD_ARGUMENT;
     if (!(sigma2apriori > 0.0) || max_iterations < 1 || min_points < 3 || !(reject_threshold >= 0.0)) return JAICOV_ERR_BAD_ARGUMENT;
     if (n_images > 0 && (!out || !status || !image_io)) return JAICOV_ERR_BAD_ARGUMENT;
-    if (obs_begin[0] != 0) return JAICOV_ERR_BAD_ARGUMENT;
-    for (int32_t g = 0; g < n_images; g++)
-        if (obs_begin[g + 1] < obs_begin[g]) return JAICOV_ERR_BAD_ARGUMENT;
+    if (!ranges_ok(n_images, obs_begin)) return JAICOV_ERR_BAD_ARGUMENT;
     const long n_obs = obs_begin[n_images];
     if (n_obs > 0 && (!xy || !xyz)) return JAICOV_ERR_BAD_ARGUMENT;
-    if (var)
-        for (long k = 0; k < n_obs; k++)
-            if (!(var[3 * k] > 0.0) || !(var[3 * k + 1] > 0.0) || !(fabs(var[3 * k + 2]) < 1.0)) return JAICOV_ERR_BAD_ARGUMENT;
+    if (!dispersions_ok(var, n_obs)) return JAICOV_ERR_BAD_ARGUMENT;
 
-    if (!resect_device_ok()) return JAICOV_ERR_NO_DEVICE;
+    if (!device_is_gfx950()) return JAICOV_ERR_NO_DEVICE;
     if (ms_out) *ms_out = 0.0;
     if (n_images == 0) return JAICOV_OK;
 
-    hipStream_t s;
-    if (hipStreamCreate(&s) != hipSuccess) return JAICOV_ERR_DEVICE;
-    const int rc = [&]() -> int {      // the owners go before the stream does
-        int32_t *d_begin = nullptr, *d_outcome = nullptr;
-        double *d_xy = nullptr, *d_xyz = nullptr, *d_var = nullptr, *d_io = nullptr, *d_eo = nullptr, *d_out = nullptr, *d_q = nullptr;
-        uint8_t *d_used = nullptr;
-        DevBag bag;
-        DevEvent ev0, ev1;
-        if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-        const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
-        const size_t ni = (size_t)n_images, no = (size_t)(n_obs > 0 ? n_obs : 1);
-        std::vector<int32_t> h_outcome(3 * ni);
-        if (bag.alloc(&d_begin, ni + 1) != hipSuccess || bag.alloc(&d_xy, 2 * no) != hipSuccess || bag.alloc(&d_xyz, 3 * no) != hipSuccess ||
-            (var && bag.alloc(&d_var, 3 * no) != hipSuccess) || bag.alloc(&d_io, 3 * ni) != hipSuccess ||
-            (eo_start && bag.alloc(&d_eo, 6 * ni) != hipSuccess) || bag.alloc(&d_out, JAICOV_RESECT_OUT_PER_IMAGE * ni) != hipSuccess ||
-            bag.alloc(&d_outcome, 3 * ni) != hipSuccess || bag.alloc(&d_used, no) != hipSuccess || (obs_q && bag.alloc(&d_q, no) != hipSuccess))
-            return JAICOV_ERR_OUT_OF_MEMORY;
-        hipMemcpyAsync(d_begin, obs_begin, (ni + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
-        if (n_obs > 0) {
-            hipMemcpyAsync(d_xy, xy, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-            hipMemcpyAsync(d_xyz, xyz, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-            if (var) hipMemcpyAsync(d_var, var, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-        }
-        hipMemcpyAsync(d_io, image_io, 3 * ni * sizeof(double), hipMemcpyHostToDevice, s);
-        if (eo_start) hipMemcpyAsync(d_eo, eo_start, 6 * ni * sizeof(double), hipMemcpyHostToDevice, s);
-        hipMemsetAsync(d_used, 1, no, s);                                  // every observation starts as used
-        hipEventRecord(e0, s);
-        hipLaunchKernelGGL(resect_images_kernel, dim3(n_images), dim3(RESECT_LANES), 0, s, d_begin, d_xy, d_xyz, d_var, d_io, d_eo, sigma2apriori,
-                           (int)max_iterations, reject_threshold * reject_threshold, (int)min_points, d_out, d_outcome, d_used, d_q);
-        if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
-        hipEventRecord(e1, s);
-        hipMemcpyAsync(out, d_out, JAICOV_RESECT_OUT_PER_IMAGE * ni * sizeof(double), hipMemcpyDeviceToHost, s);
-        hipMemcpyAsync(h_outcome.data(), d_outcome, 3 * ni * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        if (obs_used && n_obs > 0) hipMemcpyAsync(obs_used, d_used, (size_t)n_obs, hipMemcpyDeviceToHost, s);
-        if (obs_q && n_obs > 0) hipMemcpyAsync(obs_q, d_q, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost, s);
-        if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
-        for (size_t g = 0; g < ni; g++) {
-            status[g] = h_outcome[3 * g];
-            if (iterations) iterations[g] = h_outcome[3 * g + 1];
-            if (start_kind) start_kind[g] = h_outcome[3 * g + 2];
-        }
-        if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-        return JAICOV_OK;
-    }();
-    hipStreamDestroy(s);
-    return rc;
+    DevStream stream;                  // first, so that the other owners go before the stream does
+    if (stream.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipStream_t s = stream.get();
+    int32_t *d_begin = nullptr, *d_outcome = nullptr;
+    double *d_xy = nullptr, *d_xyz = nullptr, *d_var = nullptr, *d_io = nullptr, *d_eo = nullptr, *d_out = nullptr, *d_q = nullptr;
+    uint8_t *d_used = nullptr;
+    DevBag bag;
+    DevEvent ev0, ev1;
+    if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
+    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
+    const size_t ni = (size_t)n_images, no = (size_t)(n_obs > 0 ? n_obs : 1);
+    std::vector<int32_t> h_outcome(3 * ni);
+    if (bag.alloc(&d_begin, ni + 1) != hipSuccess || bag.alloc(&d_xy, 2 * no) != hipSuccess || bag.alloc(&d_xyz, 3 * no) != hipSuccess ||
+        (var && bag.alloc(&d_var, 3 * no) != hipSuccess) || bag.alloc(&d_io, 3 * ni) != hipSuccess ||
+        (eo_start && bag.alloc(&d_eo, 6 * ni) != hipSuccess) || bag.alloc(&d_out, JAICOV_RESECT_OUT_PER_IMAGE * ni) != hipSuccess ||
+        bag.alloc(&d_outcome, 3 * ni) != hipSuccess || bag.alloc(&d_used, no) != hipSuccess || (obs_q && bag.alloc(&d_q, no) != hipSuccess))
+        return JAICOV_ERR_OUT_OF_MEMORY;
+    hipMemcpyAsync(d_begin, obs_begin, (ni + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
+    if (n_obs > 0) {
+        hipMemcpyAsync(d_xy, xy, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+        hipMemcpyAsync(d_xyz, xyz, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+        if (var) hipMemcpyAsync(d_var, var, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
+    }
+    hipMemcpyAsync(d_io, image_io, 3 * ni * sizeof(double), hipMemcpyHostToDevice, s);
+    if (eo_start) hipMemcpyAsync(d_eo, eo_start, 6 * ni * sizeof(double), hipMemcpyHostToDevice, s);
+    hipMemsetAsync(d_used, 1, no, s);                                  // every observation starts as used
+    hipEventRecord(e0, s);
+    hipLaunchKernelGGL(resect_images_kernel, dim3(n_images), dim3(RESECT_LANES), 0, s, d_begin, d_xy, d_xyz, d_var, d_io, d_eo, sigma2apriori,
+                       (int)max_iterations, reject_threshold * reject_threshold, (int)min_points, d_out, d_outcome, d_used, d_q);
+    if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
+    hipEventRecord(e1, s);
+    hipMemcpyAsync(out, d_out, JAICOV_RESECT_OUT_PER_IMAGE * ni * sizeof(double), hipMemcpyDeviceToHost, s);
+    hipMemcpyAsync(h_outcome.data(), d_outcome, 3 * ni * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (obs_used && n_obs > 0) hipMemcpyAsync(obs_used, d_used, (size_t)n_obs, hipMemcpyDeviceToHost, s);
+    if (obs_q && n_obs > 0) hipMemcpyAsync(obs_q, d_q, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
+    for (size_t g = 0; g < ni; g++) {
+        status[g] = h_outcome[3 * g];
+        if (iterations) iterations[g] = h_outcome[3 * g + 1];
+        if (start_kind) start_kind[g] = h_outcome[3 * g + 2];
+    }
+    if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
+    return JAICOV_OK;
 }

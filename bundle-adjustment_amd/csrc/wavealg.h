@@ -1,0 +1,223 @@
+// wavealg.h -- the small algebra that the single-wave start-value kernels (intersect.hip, resect.hip, relorient.hip) run on
+// wave-uniform values.  What the kernels rely on:
+//   Every lane runs these routines on the same words.  Their inputs come out of an xor butterfly, whose order is fixed and which
+//   leaves the same bits in every lane, so every lane computes the same results and every branch is taken by the whole wave.  The
+//   compiler cannot know that: wave_uniform says so, or it would mask every such branch lane by lane and keep both sides' values
+//   alive across it.
+//   The LDS variants (wave_solve_lds) read and rewrite their system in place.  Every lane stores what every other lane stores, and no
+//   barrier stands between such a store and the reads that follow: the workgroup is one wave, and the LDS operations of one wave
+//   complete in order.  With more than one wave per workgroup none of it would hold.
+// Floating-point contraction is off in this header: every product and sum is rounded on its own, in the order written here, which is
+// the order of the restatements in tests/resection_reference.py (solve, rotate, eigen).
+// The intersection's isect_solve3 is not here: it is a hand-unrolled solve of order 3 with another summation order and a restatement
+// of its own (tests/intersect_reference.py: solve3).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+
+#pragma clang fp contract(off)
+
+namespace jaicov {
+
+// what a solve returns; the public JAICOV_*_OK, _SINGULAR and _NOT_FINITE of the calls that use it have these values
+enum WaveStatus { WAVE_OK = 0, WAVE_SINGULAR = 3, WAVE_NOT_FINITE = 4 };
+
+// a value that is the same in every lane, said so to the compiler
+__device__ inline int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ inline bool wave_uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
+
+// index of (i, j >= i) in an upper triangle of order N packed row by row
+template <int N>
+__device__ constexpr int tri_ix(int i, int j) { return i * N - i * (i - 1) / 2 + (j - i); }
+
+// A (packed upper, order N) x = b by Jacobi preconditioning (NES:82-91) and Cholesky; Q (may be NULL, packed upper): the inverse of A.
+// A is overwritten by the factor, so that no second triangle is live beside the caller's sums.  Everything is unrolled into registers.
+template <int N>
+__device__ inline WaveStatus wave_solve(double *U, const double *b, double *x, double *Q) {
+    const double EPS = ldexp(1.0, -53), SQRT_EPS = sqrt(EPS);
+    constexpr int LEN = N * (N + 1) / 2;
+    double z = 0.0;                       // NaN unless every value is finite
+#pragma unroll
+    for (int k = 0; k < LEN; k++) z += U[k] * 0.0;
+#pragma unroll
+    for (int k = 0; k < N; k++) z += b[k] * 0.0;
+    if (wave_uniform(z != 0.0)) return WAVE_NOT_FINITE;
+    double V[N];                          // U'U = V A V, U upper
+#pragma unroll
+    for (int i = 0; i < N; i++) V[i] = U[tri_ix<N>(i, i)] > EPS ? 1.0 / sqrt(U[tri_ix<N>(i, i)]) : 1.0;
+#pragma unroll
+    for (int i = 0; i < N; i++)
+#pragma unroll
+        for (int j = i; j < N; j++) U[tri_ix<N>(i, j)] = U[tri_ix<N>(i, j)] * (V[i] * V[j]);
+    bool singular = false;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < j; k++) s += U[tri_ix<N>(k, j)] * U[tri_ix<N>(k, j)];
+        const double p = U[tri_ix<N>(j, j)] - s;
+        singular = singular || !(p > SQRT_EPS);
+        const double d = sqrt(p);
+        U[tri_ix<N>(j, j)] = d;
+#pragma unroll
+        for (int i = j + 1; i < N; i++) {
+            double r = 0.0;
+#pragma unroll
+            for (int k = 0; k < j; k++) r += U[tri_ix<N>(k, i)] * U[tri_ix<N>(k, j)];
+            U[tri_ix<N>(j, i)] = (U[tri_ix<N>(j, i)] - r) / d;
+        }
+    }
+    if (wave_uniform(singular)) return WAVE_SINGULAR;             // every pivot after the first bad one is garbage and is not used
+    if (x) {
+        double y[N];
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            double r = 0.0;
+#pragma unroll
+            for (int k = 0; k < i; k++) r += U[tri_ix<N>(k, i)] * y[k];
+            y[i] = (V[i] * b[i] - r) / U[tri_ix<N>(i, i)];
+        }
+#pragma unroll
+        for (int i = N - 1; i >= 0; i--) {
+            double r = 0.0;
+#pragma unroll
+            for (int k = i + 1; k < N; k++) r += U[tri_ix<N>(i, k)] * y[k];
+            y[i] = (y[i] - r) / U[tri_ix<N>(i, i)];
+        }
+#pragma unroll
+        for (int i = 0; i < N; i++) x[i] = V[i] * y[i];
+    }
+    if (Q) {
+        double W[LEN];                    // W = inverse of U, upper: W[i][j], j >= i
+#pragma unroll
+        for (int j = 0; j < N; j++) {
+            W[tri_ix<N>(j, j)] = 1.0 / U[tri_ix<N>(j, j)];
+#pragma unroll
+            for (int i = j - 1; i >= 0; i--) {
+                double r = 0.0;
+#pragma unroll
+                for (int k = i + 1; k <= j; k++) r += U[tri_ix<N>(i, k)] * W[tri_ix<N>(k, j)];
+                W[tri_ix<N>(i, j)] = -r / U[tri_ix<N>(i, i)];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < N; i++)
+#pragma unroll
+            for (int j = i; j < N; j++) {                 // inverse of V A V = W W'
+                double r = 0.0;
+#pragma unroll
+                for (int k = j; k < N; k++) r += W[tri_ix<N>(i, k)] * W[tri_ix<N>(j, k)];
+                Q[tri_ix<N>(i, j)] = r * (V[i] * V[j]);
+            }
+    }
+    return WAVE_OK;
+}
+
+// The same solve on a system of order n held in LDS: U (packed upper, overwritten by the factor), b (overwritten by x), V (n words).
+// Its loops stay rolled: a triangle of order 11 unrolled into registers beside a pass's sums does not fit the register file.
+__device__ inline WaveStatus wave_solve_lds(int n, double *U, double *b, double *V) {
+    const double EPS = ldexp(1.0, -53), SQRT_EPS = sqrt(EPS);
+    auto ix = [n](int i, int j) { return i * n - i * (i - 1) / 2 + (j - i); };
+    bool finite = true;
+    for (int k = 0; k < n * (n + 1) / 2; k++) finite = finite && isfinite(U[k]);
+    for (int k = 0; k < n; k++) finite = finite && isfinite(b[k]);
+    if (wave_uniform(!finite)) return WAVE_NOT_FINITE;
+    for (int i = 0; i < n; i++) V[i] = U[ix(i, i)] > EPS ? 1.0 / sqrt(U[ix(i, i)]) : 1.0;
+    for (int i = 0; i < n; i++)
+        for (int j = i; j < n; j++) U[ix(i, j)] = U[ix(i, j)] * (V[i] * V[j]);
+    for (int j = 0; j < n; j++) {
+        double s = 0.0;
+        for (int k = 0; k < j; k++) s += U[ix(k, j)] * U[ix(k, j)];
+        const double p = U[ix(j, j)] - s;
+        if (wave_uniform(!(p > SQRT_EPS))) return WAVE_SINGULAR;
+        const double d = sqrt(p);
+        U[ix(j, j)] = d;
+        for (int i = j + 1; i < n; i++) {
+            double r = 0.0;
+            for (int k = 0; k < j; k++) r += U[ix(k, i)] * U[ix(k, j)];
+            U[ix(j, i)] = (U[ix(j, i)] - r) / d;
+        }
+    }
+    for (int i = 0; i < n; i++) {
+        double r = 0.0;
+        for (int k = 0; k < i; k++) r += U[ix(k, i)] * b[k];
+        b[i] = (V[i] * b[i] - r) / U[ix(i, i)];
+    }
+    for (int i = n - 1; i >= 0; i--) {
+        double r = 0.0;
+        for (int k = i + 1; k < n; k++) r += U[ix(i, k)] * b[k];
+        b[i] = (b[i] - r) / U[ix(i, i)];
+    }
+    for (int i = 0; i < n; i++) b[i] = V[i] * b[i];
+    return WAVE_OK;
+}
+
+// the Jacobi rotation that annuls a_pq: t = tan, c = cos, s = sin of its angle
+__device__ inline void jacobi_angle(double app, double aqq, double apq, double &t, double &c, double &s) {
+    const double theta = (aqq - app) / (2.0 * apq);
+    t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    c = 1.0 / sqrt(t * t + 1.0);
+    s = t * c;
+}
+
+// one Jacobi rotation in the plane (p, q) of a symmetric 3 x 3 matrix; r is the third index; wp, wq: the eigenvector rows p and q
+__device__ inline void jacobi_rotate3(double &app, double &aqq, double &apq, double &arp, double &arq, double *wp, double *wq) {
+    if (wave_uniform(apq == 0.0)) return;
+    double t, c, s;
+    jacobi_angle(app, aqq, apq, t, c, s);
+    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
+    arp = rp; arq = rq;
+    app = app - t * apq; aqq = aqq + t * apq; apq = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double vp = c * wp[k] - s * wq[k], vq = s * wp[k] + c * wq[k];
+        wp[k] = vp; wq[k] = vq;
+    }
+}
+
+// eigenvalues (falling) and eigenvectors (rows of E, det = +1) of the symmetric matrix S (00 01 02 11 12 22), by SWEEPS cyclic sweeps
+template <int SWEEPS>
+__device__ inline void wave_eigen3(const double *S, double *lam, double *E) {
+    double a00 = S[0], a01 = S[1], a02 = S[2], a11 = S[3], a12 = S[4], a22 = S[5];
+    double W[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    for (int sweep = 0; sweep < SWEEPS; sweep++) {
+        jacobi_rotate3(a00, a11, a01, a02, a12, W, W + 3);
+        jacobi_rotate3(a00, a22, a02, a01, a12, W, W + 6);
+        jacobi_rotate3(a11, a22, a12, a01, a02, W + 3, W + 6);
+    }
+    auto order = [&](double &la, double &lb, double *wa, double *wb) {      // the larger eigenvalue first; equal ones keep their order
+        if (wave_uniform(!(la < lb))) return;
+        const double l = la; la = lb; lb = l;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { const double w = wa[k]; wa[k] = wb[k]; wb[k] = w; }
+    };
+    order(a00, a11, W, W + 3);
+    order(a11, a22, W + 3, W + 6);
+    order(a00, a11, W, W + 3);
+    const double n0 = W[1] * W[5] - W[2] * W[4], n1 = W[2] * W[3] - W[0] * W[5], n2 = W[0] * W[4] - W[1] * W[3];   // e1 x e2
+    if (n0 * W[6] + n1 * W[7] + n2 * W[8] < 0.0) { W[6] = -W[6]; W[7] = -W[7]; W[8] = -W[8]; }
+    lam[0] = a00; lam[1] = a11; lam[2] = a22;
+#pragma unroll
+    for (int k = 0; k < 9; k++) E[k] = W[k];
+}
+
+// the weights of one observation (PDF:308-319) from its dispersions vx, vy, rho.  It takes the three values, not the array and an
+// index: the loads stay with the caller's other loads of the same index, and resect.hip's kernel keeps its register allocation.
+__device__ inline void obs_weight(double vx, double vy, double rho, double s0, double &p11, double &p12, double &p22) {
+    if (rho == 0.0) {
+        p11 = s0 / vx; p12 = 0.0; p22 = s0 / vy;
+    } else {
+        const double inv = s0 / ((1.0 - rho * rho) * vx * vy);
+        p11 = inv * vy; p22 = inv * vx; p12 = -inv * rho * sqrt(vx * vy);
+    }
+}
+
+// one step of the xor butterfly over (largest q, lowest index among equal values)
+__device__ inline void wave_argmax_combine(double &qmax, int &qidx, int off) {
+    const double oq = __shfl_xor(qmax, off);
+    const int oi = __shfl_xor(qidx, off);
+    if (oq > qmax || (oq == qmax && oi < qidx)) { qmax = oq; qidx = oi; }
+}
+
+}  // namespace jaicov

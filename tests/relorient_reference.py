@@ -43,44 +43,12 @@ def cofactors(var, sigma2, c, m):
         return vx / sigma2 / c2, np.where(rho == 0, 0.0, rho * np.sqrt(vx * vy) / sigma2 / c2), vy / sigma2 / c2
 
 
-def rotate(A, p, q, r_idx, W):
-    """one Jacobi rotation in the plane (p, q) of the symmetric matrix A (lists), eigenvector rows W; r_idx: the other indices"""
-    apq = A[p][q]
-    if apq == 0.0:
-        return
-    with np.errstate(all="ignore"):
-        theta = float((np.float64(A[q][q]) - A[p][p]) / (2.0 * apq))
-    t = math.copysign(1.0, theta) / (abs(theta) + math.sqrt(theta * theta + 1.0))
-    c = 1.0 / math.sqrt(t * t + 1.0)
-    s = t * c
-    for k in r_idx:
-        kp, kq = c * A[k][p] - s * A[k][q], s * A[k][p] + c * A[k][q]
-        A[k][p] = A[p][k] = kp
-        A[k][q] = A[q][k] = kq
-    A[p][p] = A[p][p] - t * apq
-    A[q][q] = A[q][q] + t * apq
-    A[p][q] = A[q][p] = 0.0
-    for k in range(len(W[p])):
-        vp, vq = c * W[p][k] - s * W[q][k], s * W[p][k] + c * W[q][k]
-        W[p][k] = vp; W[q][k] = vq
+rotate = X.rotate                 # the 9 x 9 Jacobi below turns with the rotation of the 3 x 3 one
 
 
 def eigen3(S):
     """(eigenvalues falling, rows e1 e2 e3 with det = +1) of the symmetric 3 x 3 matrix S: SWEEPS3 of cyclic Jacobi"""
-    A = [[float(S[i][j]) for j in range(3)] for i in range(3)]
-    W = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]
-    for _ in range(SWEEPS3):
-        for p, q, r in ((0, 1, 2), (0, 2, 1), (1, 2, 0)):
-            rotate(A, p, q, (r,), W)
-    lam = [A[0][0], A[1][1], A[2][2]]
-    for a, b in ((0, 1), (1, 2), (0, 1)):
-        if lam[a] < lam[b]:
-            lam[a], lam[b] = lam[b], lam[a]
-            W[a], W[b] = W[b], W[a]
-    n = cross(W[0], W[1])
-    if n[0] * W[2][0] + n[1] * W[2][1] + n[2] * W[2][2] < 0.0:
-        W[2] = [-v for v in W[2]]
-    return lam, W
+    return X.eigen3(S, SWEEPS3)
 
 
 def cross(a, b):

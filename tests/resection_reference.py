@@ -134,28 +134,35 @@ def polar(X):
     return np.array(X, np.float64).reshape(3, 3)
 
 
-def eigen(S):
-    """rows e1, e2 (falling eigenvalue), n (det = +1) of the symmetric 3 x 3 matrix S: JACOBI_SWEEPS of cyclic Jacobi"""
+def rotate(A, p, q, r_idx, W):
+    """one Jacobi rotation in the plane (p, q) of the symmetric matrix A (lists), eigenvector rows W; r_idx: the other indices"""
+    apq = A[p][q]
+    if apq == 0.0:
+        return
+    with np.errstate(all="ignore"):
+        theta = float((np.float64(A[q][q]) - A[p][p]) / (2.0 * apq))
+    t = math.copysign(1.0, theta) / (abs(theta) + math.sqrt(theta * theta + 1.0))
+    c = 1.0 / math.sqrt(t * t + 1.0)
+    s = t * c
+    for k in r_idx:
+        kp, kq = c * A[k][p] - s * A[k][q], s * A[k][p] + c * A[k][q]
+        A[k][p] = A[p][k] = kp
+        A[k][q] = A[q][k] = kq
+    A[p][p] = A[p][p] - t * apq
+    A[q][q] = A[q][q] + t * apq
+    A[p][q] = A[q][p] = 0.0
+    for k in range(len(W[p])):
+        vp, vq = c * W[p][k] - s * W[q][k], s * W[p][k] + c * W[q][k]
+        W[p][k] = vp; W[q][k] = vq
+
+
+def eigen3(S, sweeps=JACOBI_SWEEPS):
+    """(eigenvalues falling, rows e1 e2 e3 with det = +1) of the symmetric 3 x 3 matrix S: `sweeps` of cyclic Jacobi"""
     A = [[float(S[i][j]) for j in range(3)] for i in range(3)]
     W = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]          # rows: eigenvectors
-    for _ in range(JACOBI_SWEEPS):
+    for _ in range(sweeps):
         for p, q, r in ((0, 1, 2), (0, 2, 1), (1, 2, 0)):
-            apq = A[p][q]
-            if apq == 0.0:
-                continue
-            theta = (A[q][q] - A[p][p]) / (2.0 * apq)
-            t = math.copysign(1.0, theta) / (abs(theta) + math.sqrt(theta * theta + 1.0))
-            c = 1.0 / math.sqrt(t * t + 1.0)
-            s = t * c
-            A[p][p] = A[p][p] - t * apq
-            A[q][q] = A[q][q] + t * apq
-            A[p][q] = A[q][p] = 0.0
-            rp, rq = c * A[r][p] - s * A[r][q], s * A[r][p] + c * A[r][q]
-            A[r][p] = A[p][r] = rp
-            A[r][q] = A[q][r] = rq
-            for k in range(3):
-                vp, vq = c * W[p][k] - s * W[q][k], s * W[p][k] + c * W[q][k]
-                W[p][k] = vp; W[q][k] = vq
+            rotate(A, p, q, (r,), W)
     lam = [A[0][0], A[1][1], A[2][2]]
     for a, b in ((0, 1), (1, 2), (0, 1)):         # the larger eigenvalue first; equal ones keep their order
         if lam[a] < lam[b]:
@@ -164,7 +171,12 @@ def eigen(S):
     n = [W[0][1] * W[1][2] - W[0][2] * W[1][1], W[0][2] * W[1][0] - W[0][0] * W[1][2], W[0][0] * W[1][1] - W[0][1] * W[1][0]]
     if n[0] * W[2][0] + n[1] * W[2][1] + n[2] * W[2][2] < 0.0:
         W[2] = [-v for v in W[2]]
-    return np.array(W)
+    return lam, W
+
+
+def eigen(S):
+    """rows e1, e2 (falling eigenvalue), n (det = +1) of the symmetric 3 x 3 matrix S: JACOBI_SWEEPS of cyclic Jacobi"""
+    return np.array(eigen3(S)[1])
 
 
 def rotation(par):
