@@ -5,7 +5,7 @@ import os
 
 import numpy as np
 
-from bundle_adjustment_amd import scene
+from bundle_adjustment_amd import numbering, scene
 from bundle_adjustment_amd.problem import FlatProblem
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -92,3 +92,66 @@ def corrupt(fp, what):
         return r(fp, cam_dist_begin=np.array([0, n], np.int32), dist_kind=np.full(n, 5, np.int32), dist_order=np.arange(1, n + 1, dtype=np.int32),
                  dist_col=np.full(n, -1, np.int32)), "too many"
     raise KeyError(what)
+
+
+# ---- irregular scenes (test_gpu_edge_cases.py against the oracle's full system, test_gpu_reduced_system.py against the reduced truth) ----
+def renumber(fp, *, point_fixed=None, io_fixed=None, dist_fixed=None, eo_fixed=None, **changes):
+    """Same scene, new index contract (BundleAdjustment.java:667-782) after fixing parameters / changing cameras."""
+    image_camera = changes.get("image_camera", fp.image_camera)
+    cam_dist_begin = changes.get("cam_dist_begin", fp.cam_dist_begin)
+    n_cameras = len(cam_dist_begin) - 1
+    num = numbering.number_unknowns(fp.n_points, n_cameras, image_camera, fp.ip_point, cam_dist_begin,
+                                    point_fixed=point_fixed, io_fixed=io_fixed, dist_fixed=dist_fixed, eo_fixed=eo_fixed,
+                                    sb_point_a=fp.sb_point_a, sb_point_b=fp.sb_point_b, dg_slot=changes.get("dg_slot", fp.dg_slot))
+    return dataclasses.replace(fp, n_unknowns=num["n_unknowns"], rank_defect=num["rank_defect"], datum_flags=num["datum_flags"],
+                               point_col=num["point_col"], io_col=num["io_col"], dist_col=num["dist_col"], eo_col=num["eo_col"],
+                               n_observations=0, **changes).validate()
+
+
+def two_camera_scene():
+    """(two, base): the images of `base` shared out between two cameras, the second with affinity/shear and radial A1-A3 only."""
+    base = scene.make_scene(8, 60, 36, dist=scene.DIST_FULL, weights="block", n_control=5, control_dense=True)
+    P, I = base.n_points, base.n_images
+    nd = base.dist_kind.size
+    keep = (base.dist_kind <= 1) | (base.dist_kind == 5)   # camera 1: affinity/shear (Cx, Cy) + radial A1-A3 only
+    nd1 = int(keep.sum())
+    s_io = 3 * P
+    v = base.values
+    values = np.concatenate([v[:s_io], v[s_io:s_io + 3], v[s_io:s_io + 3], v[s_io + 3:s_io + 3 + nd],
+                             v[s_io + 3:s_io + 3 + nd][keep], v[s_io + 3 + nd:]])
+    image_camera = np.array([0] * (I // 2) + [1] * (I - I // 2), np.int32)
+    two = renumber(base, image_camera=image_camera, cam_dist_begin=np.array([0, nd, nd + nd1], np.int32),
+                   cam_r0=np.array([base.cam_r0[0], base.cam_r0[0]]),
+                   dist_kind=np.concatenate([base.dist_kind, base.dist_kind[keep]]).astype(np.int32),
+                   dist_order=np.concatenate([base.dist_order, base.dist_order[keep]]).astype(np.int32),
+                   values=values, truth=None)
+    assert two.n_unknowns == base.n_unknowns + 3 + nd1
+    return two, base
+
+
+def mixed_scene():
+    """Jointly dispersed and ordinary images in one adjustment."""
+    base = scene.make_scene(8, 60, 36, dist=scene.DIST_FULL, weights="block", n_control=5, control_dense=True)
+    k = 5                                           # images 0..4 keep their joint dispersion, 5..7 fall back to sigma_x, sigma_y
+    return dataclasses.replace(base, blk_ip_begin=base.blk_ip_begin[:k + 1].copy(), blk_disp_offset=base.blk_disp_offset[:k].copy(),
+                               blk_disp=base.blk_disp[:int(base.blk_disp_offset[k])].copy(), n_observations=0).validate()
+
+
+def ragged_scene():
+    """Images with very different numbers of points (3 ... 45) in jointly dispersed groups."""
+    base = scene.make_scene(9, 45, 45, dist=scene.DIST_RADIAL, weights="block", n_control=5, control_dense=True, min_rays=2)
+    counts = np.diff(base.blk_ip_begin)
+    want = np.minimum(counts, np.array([3, 45, 5, 17, 45, 9, 33, 4, 45])[:counts.size])
+    keep = np.concatenate([np.arange(base.blk_ip_begin[i], base.blk_ip_begin[i] + want[i]) for i in range(counts.size)])
+    disp, off = [], [0]
+    for i in range(counts.size):
+        m0, m1 = 2 * int(counts[i]), 2 * int(want[i])
+        D = base.blk_disp[base.blk_disp_offset[i]:base.blk_disp_offset[i] + m0 * m0].reshape(m0, m0)[:m1, :m1]
+        disp.append(D.ravel()); off.append(off[-1] + m1 * m1)
+    rays = np.bincount(base.ip_point[keep], minlength=base.n_points)
+    assert rays.min() >= 2, "scene too thin for this test: every point needs two rays"
+    rag = dataclasses.replace(base, ip_image=base.ip_image[keep], ip_point=base.ip_point[keep], ip_x=base.ip_x[keep], ip_y=base.ip_y[keep],
+                              ip_var_x=base.ip_var_x[keep], ip_var_y=base.ip_var_y[keep], ip_rho=base.ip_rho[keep],
+                              blk_ip_begin=np.concatenate([[0], np.cumsum(want)]).astype(np.int32),
+                              blk_disp_offset=np.array(off[:-1], np.int64), blk_disp=np.concatenate(disp), n_observations=0)
+    return renumber(rag)
