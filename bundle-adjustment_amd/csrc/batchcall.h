@@ -1,4 +1,4 @@
-// batchcall.h -- what the one-shot batched calls (dlt.hip, intersect.hip, resect.hip, relorient.hip) check on the host before they
+// batchcall.h -- what the one-shot batched calls (dlt.hip, intersect.hip, resect.hip, relorient.hip, simil.hip) check on the host before they
 // touch a device.  Every argument check comes first, then the device check, so that a bad call is refused as such on any machine.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// wavealg.h -- the small algebra that the single-wave start-value kernels (intersect.hip, resect.hip, relorient.hip) run on
+// wavealg.h -- the small algebra that the single-wave start-value kernels (intersect.hip, resect.hip, relorient.hip, simil.hip) run on
 // wave-uniform values.  What the kernels rely on:
 //   Every lane runs these routines on the same words.  Their inputs come out of an xor butterfly, whose order is fixed and which
 //   leaves the same bits in every lane, so every lane computes the same results and every branch is taken by the whole wave.  The

@@ -1,7 +1,7 @@
 """ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` / ``include/jaicov_transform.h`` /
 ``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_reliability_points.h`` /
 ``include/jaicov_datum.h`` / ``include/jaicov_intersect.h`` / ``include/jaicov_resect.h`` /
-``include/jaicov_relorient.h``
+``include/jaicov_relorient.h`` / ``include/jaicov_simil.h``
 (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
@@ -66,6 +66,10 @@ RESECT_START_GIVEN, RESECT_START_SPACE, RESECT_START_PLANE = range(3)
 RELOR_EXPORTS = ["jaicov_relorient_pairs"]
 RELOR_OK, RELOR_NOT_CONVERGED, RELOR_TOO_FEW_POINTS, RELOR_SINGULAR, RELOR_NOT_FINITE = range(5)
 RELOR_START_GIVEN, RELOR_START_SPACE, RELOR_START_PLANE = range(3)
+# include/jaicov_simil.h: absolute orientation (spatial similarity transformation) of a batch of models (stand-alone, no engine)
+SIMIL_EXPORTS = ["jaicov_simil_models", "jaicov_simil_apply"]
+SIMIL_OK, SIMIL_NOT_CONVERGED, SIMIL_TOO_FEW_POINTS, SIMIL_SINGULAR, SIMIL_NOT_FINITE = range(5)
+SIMIL_START_GIVEN, SIMIL_START_CLOSED = range(2)
 
 KROW = 32  # 12 + JAICOV_MAX_DIST_PER_CAMERA
 INVERT_NONE, INVERT_FULL, INVERT_REDUCED = 0, 1, 2   # MatrixInversion (BundleAdjustment.java:65-70)
@@ -180,6 +184,9 @@ def load_library():
                                        _pd, _pi, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
     L.jaicov_relorient_pairs.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, _pd, _pd, _pd, C.c_double, C.c_int32, C.c_double, C.c_int32,
                                          _pd, _pi, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
+    L.jaicov_simil_models.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, _pd, _pd, C.c_int32, C.c_double, C.c_int32,
+                                      _pd, _pi, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
+    L.jaicov_simil_apply.argtypes = [C.c_int32, _pd, _pi, _pd, _pd, _pi, _pd, _pd, _pd, _pd]
     _LIB = L
     return L
 
@@ -701,6 +708,79 @@ def relorient_problem(fp: FlatProblem, image_a, image_b, base_length=1.0, values
         eo[image_b, :3] = base_length * out[0, :3]
         eo[image_b, 3:] = out[0, 3:6]
     return (v, out[0], int(status[0])) if with_status else v
+
+
+def similarity_models(pt_begin, src, dst, cof_src=None, cof_dst=None, start=None, max_iterations=50, reject_threshold=0.0, min_points=3,
+                      with_time=False):
+    """Absolute orientation of every model of a batch: the similarity transformation dst = T + m R src between two sets of the same
+    points (include/jaicov_simil.h).  pt_begin: (n + 1,) CSR offsets of the models' points; src, dst: (n_pts, 3) the point in the
+    model's frame and in the target frame; cof_src, cof_dst: (n_pts, 6) qXX qXY qXZ qYY qYZ qZZ or None (0 and I); start: (n, 7) Tx Ty
+    Tz m omega phi kappa or None, a model whose seven values are all finite starts from them, any other from the closed start.
+    Returns (out (n, 36): Tx, Ty, Tz, m, omega, phi, kappa, the 28 entries of the upper triangle of their cofactor matrix, Omega;
+    status (n,); iterations (n,); start_kind (n,); pt_used (n_pts,); pt_q (n_pts,)), plus the kernel time in ms with with_time."""
+    L = load_library()
+    pb = np.ascontiguousarray(pt_begin, np.int32).ravel()
+    n = pb.size - 1
+    s = np.ascontiguousarray(src, np.float64).reshape(-1)
+    d = np.ascontiguousarray(dst, np.float64).reshape(-1)
+    qs = None if cof_src is None else np.ascontiguousarray(cof_src, np.float64).reshape(-1)
+    qd = None if cof_dst is None else np.ascontiguousarray(cof_dst, np.float64).reshape(-1)
+    st = None if start is None else np.ascontiguousarray(start, np.float64).reshape(-1)
+    n_pts = s.size // 3
+    if s.size % 3 or d.size != s.size or (qs is not None and qs.size != 6 * n_pts) or (qd is not None and qd.size != 6 * n_pts) or \
+            (st is not None and st.size != 7 * max(n, 0)) or (pb.size and pb[-1] != n_pts):
+        raise EngineError(-1, "similarity models: array sizes do not agree")
+    out = np.zeros((max(n, 0), 36)); status = np.zeros(max(n, 0), np.int32); iterations = np.zeros(max(n, 0), np.int32)
+    kind = np.zeros(max(n, 0), np.int32); used = np.zeros(n_pts, np.uint8); q = np.zeros(n_pts)
+    ms = np.zeros(1)
+    null = C.cast(None, _pd)
+    rc = L.jaicov_simil_models(n, pb.ctypes.data_as(_pi), _p(s), _p(d), _p(qs) if qs is not None else null,
+                               _p(qd) if qd is not None else null, _p(st) if st is not None else null, int(max_iterations),
+                               float(reject_threshold), int(min_points), _p(out), status.ctypes.data_as(_pi),
+                               iterations.ctypes.data_as(_pi), kind.ctypes.data_as(_pi), used.ctypes.data_as(C.POINTER(C.c_uint8)),
+                               _p(q), _p(ms))
+    if rc != 0:
+        raise EngineError(rc, "similarity models")
+    return (out, status, iterations, kind, used, q) + ((float(ms[0]),) if with_time else ())
+
+
+def similarity_apply(par, pt_begin, xyz, cof=None, img_begin=None, eo=None):
+    """Carries the points and the image orientations of every model into the target frame (include/jaicov_simil.h).  par: (n, 7) or
+    the (n, 36) output of similarity_models; pt_begin: (n + 1,) CSR offsets of the models' points or None, with xyz (n_pts, 3) and cof
+    (n_pts, 6) or None; img_begin: (n + 1,) CSR offsets of the models' images or None, with eo (n_img, 6).  Returns (xyz, cof, eo) in
+    the target frame, None where the input was.  The dispersion of the seven parameters is not propagated."""
+    L = load_library()
+    par = np.asarray(par, np.float64)
+    par = np.ascontiguousarray(par.reshape(-1, par.shape[-1] if par.ndim > 1 else 7)[:, :7]).reshape(-1)
+    n = par.size // 7
+    null, nulli = C.cast(None, _pd), C.cast(None, _pi)
+
+    def ranges(begin, values, width, what):
+        if begin is None:
+            if values is not None:
+                raise EngineError(-1, f"similarity apply: {what} without their ranges")
+            return None, None
+        b = np.ascontiguousarray(begin, np.int32).ravel()
+        v = np.ascontiguousarray(values, np.float64).reshape(-1)
+        if b.size != n + 1 or v.size != width * b[-1]:
+            raise EngineError(-1, f"similarity apply: the sizes of the {what} do not agree")
+        return b, v
+    pb, x = ranges(pt_begin, xyz, 3, "points")
+    ib, e = ranges(img_begin, eo, 6, "orientations")
+    q = None if cof is None else np.ascontiguousarray(cof, np.float64).reshape(-1)
+    if q is not None and (x is None or q.size != 2 * x.size):
+        raise EngineError(-1, "similarity apply: the sizes of the cofactors do not agree")
+    xo = None if x is None else np.zeros_like(x)
+    qo = None if q is None else np.zeros_like(q)
+    eo_out = None if e is None else np.zeros_like(e)
+    rc = L.jaicov_simil_apply(n, _p(par), pb.ctypes.data_as(_pi) if pb is not None else nulli, _p(x) if x is not None else null,
+                              _p(q) if q is not None else null, ib.ctypes.data_as(_pi) if ib is not None else nulli,
+                              _p(e) if e is not None else null, _p(xo) if xo is not None else null, _p(qo) if qo is not None else null,
+                              _p(eo_out) if eo_out is not None else null)
+    if rc != 0:
+        raise EngineError(rc, "similarity apply")
+    return (None if xo is None else xo.reshape(-1, 3), None if qo is None else qo.reshape(-1, 6),
+            None if eo_out is None else eo_out.reshape(-1, 6))
 
 
 def dense_gemm(alay, blay, A, B, C_in, M, N, K, alpha=1.0, beta=0.0, lower_only=False, kmode=0, repeats=0):

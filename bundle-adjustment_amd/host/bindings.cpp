@@ -294,6 +294,28 @@ PYBIND11_MODULE(_jaicov_host, m) {
         .def_static("getMaximalNumberOfIterations", &RelativeOrientation::getMaximalNumberOfIterations)
         .def_static("setMaximalNumberOfIterations", &RelativeOrientation::setMaximalNumberOfIterations);
 
+    py::class_<SimilarityTransformation> simil(m, "SimilarityTransformation");
+    py::class_<SimilarityTransformation::Model>(simil, "Model")
+        .def(py::init<>())
+        .def_readwrite("points", &SimilarityTransformation::Model::points)
+        .def_readwrite("target", &SimilarityTransformation::Model::target)
+        .def_readwrite("cofSource", &SimilarityTransformation::Model::cofSource)
+        .def_readwrite("cofTarget", &SimilarityTransformation::Model::cofTarget);
+    py::class_<SimilarityTransformation::Result>(simil, "Result")
+        .def_readonly("status", &SimilarityTransformation::Result::status)
+        .def_readonly("iterations", &SimilarityTransformation::Result::iterations)
+        .def_readonly("startKind", &SimilarityTransformation::Result::startKind)
+        .def_readonly("points", &SimilarityTransformation::Result::points)
+        .def_readonly("pointsUsed", &SimilarityTransformation::Result::pointsUsed)
+        .def_readonly("used", &SimilarityTransformation::Result::used)
+        .def_readonly("q", &SimilarityTransformation::Result::q)
+        .def("values", [](SimilarityTransformation::Result &r) { return std::vector<double>(r.values, r.values + JAICOV_SIMIL_OUT_PER_MODEL); });
+    simil.def_static("estimateAll", &SimilarityTransformation::estimateAll, py::arg("models"), py::arg("rejectThreshold") = 0.0,
+                     py::arg("minPoints") = 3)
+        .def_static("apply", &SimilarityTransformation::apply, py::arg("result"), py::arg("points"), py::arg("images"))
+        .def_static("getMaximalNumberOfIterations", &SimilarityTransformation::getMaximalNumberOfIterations)
+        .def_static("setMaximalNumberOfIterations", &SimilarityTransformation::setMaximalNumberOfIterations);
+
     py::class_<AiconProject>(m, "AiconProject")
         .def_property_readonly("camera", [](AiconProject &p) { return p.camera ? p.camera.get() : (p.cameras.empty() ? nullptr : p.cameras[0].get()); },
                                py::return_value_policy::reference_internal)

@@ -834,4 +834,74 @@ bool RelativeOrientation::apply(const Result &r, double baseLength) {
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// SimilarityTransformation (include/jaicov_simil.h) on the device
+// ---------------------------------------------------------------------------------------------------------------
+std::vector<SimilarityTransformation::Result> SimilarityTransformation::estimateAll(const std::vector<Model> &models, double rejectThreshold,
+                                                                                    int minPoints) {
+    std::vector<int32_t> begin(1, 0);
+    std::vector<double> src, dst, qs, qd;
+    bool withSource = false, withTarget = false;
+    for (const Model &m : models) {
+        withSource = withSource || !m.cofSource.empty();
+        withTarget = withTarget || !m.cofTarget.empty();
+    }
+    for (const Model &m : models) {
+        const size_t n = m.points.size();
+        if (m.target.size() != n || (!m.cofSource.empty() && m.cofSource.size() != n) || (!m.cofTarget.empty() && m.cofTarget.size() != n))
+            throw std::invalid_argument("SimilarityTransformation: the sizes of a model's arrays do not agree");
+        for (size_t k = 0; k < n; k++) {
+            src.push_back(m.points[k]->getX().getValue()); src.push_back(m.points[k]->getY().getValue()); src.push_back(m.points[k]->getZ().getValue());
+            for (int i = 0; i < 3; i++) dst.push_back(m.target[k][i]);
+            // a batch in which some model has cofactors gives every other model the defaults: 0 for the source, I for the target
+            for (int i = 0; withSource && i < 6; i++) qs.push_back(m.cofSource.empty() ? 0.0 : m.cofSource[k][i]);
+            for (int i = 0; withTarget && i < 6; i++) qd.push_back(m.cofTarget.empty() ? (i == 0 || i == 3 || i == 5 ? 1.0 : 0.0) : m.cofTarget[k][i]);
+        }
+        begin.push_back((int32_t)(src.size() / 3));
+    }
+    const int n = (int)models.size();
+    std::vector<double> out((size_t)JAICOV_SIMIL_OUT_PER_MODEL * n), q(src.size() / 3);
+    std::vector<int32_t> status(n), iterations(n), kind(n);
+    std::vector<uint8_t> used(src.size() / 3);
+    const int rc = jaicov_simil_models(n, begin.data(), src.data(), dst.data(), withSource ? qs.data() : nullptr, withTarget ? qd.data() : nullptr,
+                                       nullptr, maximalNumberOfIterations_, rejectThreshold, minPoints, out.data(), status.data(),
+                                       iterations.data(), kind.data(), used.data(), q.data(), nullptr);
+    if (rc != JAICOV_OK) throw std::runtime_error("jaicov_simil_models failed with status " + std::to_string(rc));
+    std::vector<Result> res(n);
+    for (int g = 0; g < n; g++) {
+        Result &r = res[g];
+        r.status = status[g];
+        r.iterations = iterations[g];
+        r.startKind = kind[g];
+        r.points = begin[g + 1] - begin[g];
+        for (int k = begin[g]; k < begin[g + 1]; k++) {
+            r.pointsUsed += used[k];
+            r.used.push_back(used[k] != 0);
+            r.q.push_back(q[k]);
+        }
+        for (int k = 0; k < JAICOV_SIMIL_OUT_PER_MODEL; k++) r.values[k] = out[(size_t)JAICOV_SIMIL_OUT_PER_MODEL * g + k];
+    }
+    return res;
+}
+
+bool SimilarityTransformation::apply(const Result &r, const std::vector<ObjectCoordinate *> &points, const std::vector<Image *> &images) {
+    if (r.status != JAICOV_SIMIL_OK && r.status != JAICOV_SIMIL_NOT_CONVERGED) return false;
+    const int32_t pb[2] = {0, (int32_t)points.size()}, ib[2] = {0, (int32_t)images.size()};
+    std::vector<double> xyz, eo;
+    for (ObjectCoordinate *p : points) {
+        xyz.push_back(p->getX().getValue()); xyz.push_back(p->getY().getValue()); xyz.push_back(p->getZ().getValue());
+    }
+    for (Image *im : images)
+        for (int k = 0; k < 6; k++) eo.push_back(im->getExteriorOrientation().at(k)->getValue());
+    const int rc = jaicov_simil_apply(1, r.values, points.empty() ? nullptr : pb, xyz.data(), nullptr, images.empty() ? nullptr : ib, eo.data(),
+                                      xyz.data(), nullptr, eo.data());
+    if (rc != JAICOV_OK) throw std::runtime_error("jaicov_simil_apply failed with status " + std::to_string(rc));
+    for (size_t k = 0; k < points.size(); k++) {
+        points[k]->getX().setValue(xyz[3 * k]); points[k]->getY().setValue(xyz[3 * k + 1]); points[k]->getZ().setValue(xyz[3 * k + 2]);
+    }
+    for (size_t g = 0; g < images.size(); g++)
+        for (int k = 0; k < 6; k++) images[g]->getExteriorOrientation().at(k)->setValue(eo[6 * g + k]);
+    return true;
+}
+
 }  // namespace jaicov::host

@@ -13,6 +13,7 @@
 // What goes to the MI355X through the C ABI: createNormalEquation, applyPrecondition, MathExtension.solve, getOmega.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -31,6 +32,7 @@
 #include "../../include/jaicov_intersect.h"
 #include "../../include/jaicov_resect.h"
 #include "../../include/jaicov_relorient.h"
+#include "../../include/jaicov_simil.h"
 #include "../../include/jaicov_reliability.h"
 #include "../../include/jaicov_reliability_points.h"
 #include "../../include/jaicov_datum.h"
@@ -718,6 +720,35 @@ public:
     static std::vector<Result> orientAll(const std::vector<std::pair<Image *, Image *>> &pairs, bool fromCurrentValues = false,
                                          double sigma2apriori = 1.0, double rejectThreshold = 0.0, int minPoints = 6);
     static bool apply(const Result &result, double baseLength = 1.0);
+    static int getMaximalNumberOfIterations() { return maximalNumberOfIterations_; }
+    static void setMaximalNumberOfIterations(int n) { maximalNumberOfIterations_ = n; }
+private:
+    static inline int maximalNumberOfIterations_ = 50;
+};
+
+// Absolute orientation on the device (include/jaicov_simil.h): the spatial similarity transformation that carries a model onto a
+// target frame.  The reference has no counterpart.  estimateAll() makes one device call for every model.  A model's source
+// coordinates are the current values of its ObjectCoordinates, `target` holds the same points in the target frame (control points, or
+// another model); cofSource and cofTarget hold qXX qXY qXZ qYY qYZ qZZ per point, as ForwardIntersection returns them, and an empty
+// one means error-free (source) or the unit matrix (target).  Nothing is written into the points: apply() carries the given points
+// and the exterior orientations of the given images into the target frame with a result whose status is JAICOV_SIMIL_OK or
+// JAICOV_SIMIL_NOT_CONVERGED; the dispersion of the seven parameters is not propagated.  A device error (no GPU, out of memory) throws
+// std::runtime_error.
+class SimilarityTransformation {
+public:
+    struct Model {
+        std::vector<ObjectCoordinate *> points;
+        std::vector<std::array<double, 3>> target;
+        std::vector<std::array<double, 6>> cofSource, cofTarget;
+    };
+    struct Result {
+        int status = -1, iterations = 0, startKind = 0, points = 0, pointsUsed = 0;
+        double values[JAICOV_SIMIL_OUT_PER_MODEL] = {};      // Tx, Ty, Tz, m, omega, phi, kappa, the upper triangle of Q, Omega
+        std::vector<bool> used;                              // per point of the model
+        std::vector<double> q;
+    };
+    static std::vector<Result> estimateAll(const std::vector<Model> &models, double rejectThreshold = 0.0, int minPoints = 3);
+    static bool apply(const Result &result, const std::vector<ObjectCoordinate *> &points, const std::vector<Image *> &images);
     static int getMaximalNumberOfIterations() { return maximalNumberOfIterations_; }
     static void setMaximalNumberOfIterations(int n) { maximalNumberOfIterations_ = n; }
 private:

@@ -1,7 +1,7 @@
 /*
  * JNI shim between NativeNormalEquationEngine (Java) and the C ABI of include/jaicov_neq.h, include/jaicov_transform.h,
  * include/jaicov_dlt.h, include/jaicov_reliability.h, include/jaicov_datum.h, include/jaicov_intersect.h,
- * include/jaicov_resect.h and include/jaicov_relorient.h.
+ * include/jaicov_resect.h, include/jaicov_relorient.h and include/jaicov_simil.h.
  * The build image has no JDK, so this file is not built by __graft_entry__.build(); on a box with a JDK:
  *   gcc -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -I../../include jaicov_jni.c \
  *       -L../../bundle-adjustment_amd/csrc -ljaicov_neq -o libjaicov_jni.so
@@ -26,6 +26,7 @@
 #include "jaicov_intersect.h"
 #include "jaicov_resect.h"
 #include "jaicov_relorient.h"
+#include "jaicov_simil.h"
 #include "jaicov_reliability.h"
 #include "jaicov_datum.h"
 
@@ -827,5 +828,122 @@ JNIEXPORT jint JNICALL NAT(orientPairs)(JNIEnv *e, jclass k, jintArray obsBegin,
     if (pxb) (*e)->ReleaseDoubleArrayElements(e, xyB, pxb, JNI_ABORT);
     if (pxa) (*e)->ReleaseDoubleArrayElements(e, xyA, pxa, JNI_ABORT);
     (*e)->ReleaseIntArrayElements(e, obsBegin, pb, JNI_ABORT);
+    return rc;
+}
+
+/* --- include/jaicov_simil.h: absolute orientation of a batch of models, and the move into the target frame (no engine) -------------- */
+/* an optional double[] of at least `need` values: its copy, or NULL where the array is null; *bad is set where it is too short or the
+ * copy failed */
+static jdouble *simil_get(JNIEnv *e, jdoubleArray a, jsize need, int *bad) {
+    if (!a) return NULL;
+    if ((*e)->GetArrayLength(e, a) < need) { *bad = JAICOV_ERR_BAD_ARGUMENT; return NULL; }
+    jdouble *p = (*e)->GetDoubleArrayElements(e, a, NULL);
+    if (!p && !*bad) *bad = JAICOV_ERR_OUT_OF_MEMORY;
+    return p;
+}
+
+/* inputs through Get<Type>ArrayElements copies (JNI_ABORT); cofSrc, cofDst, start, iterations, startKind, ptUsed and ptQ may be null;
+ * status, iterations, startKind and ptUsed come back through long[] as for the relative orientation. */
+JNIEXPORT jint JNICALL NAT(similModels)(JNIEnv *e, jclass k, jintArray ptBegin, jdoubleArray src, jdoubleArray dst, jdoubleArray cofSrc,
+                                        jdoubleArray cofDst, jdoubleArray start, jint maxIterations, jdouble rejectThreshold, jint minPoints,
+                                        jdoubleArray out, jlongArray status, jlongArray iterations, jlongArray startKind, jlongArray ptUsed,
+                                        jdoubleArray ptQ) {
+    (void)k;
+    if (!ptBegin || !src || !dst || !out || !status) return JAICOV_ERR_BAD_ARGUMENT;
+    const jsize nb = (*e)->GetArrayLength(e, ptBegin);
+    if (nb < 1) return JAICOV_ERR_BAD_ARGUMENT;
+    const jsize n = nb - 1;
+    if ((*e)->GetArrayLength(e, out) < JAICOV_SIMIL_OUT_PER_MODEL * n || (*e)->GetArrayLength(e, status) < n ||
+        (iterations && (*e)->GetArrayLength(e, iterations) < n) || (startKind && (*e)->GetArrayLength(e, startKind) < n))
+        return JAICOV_ERR_BAD_ARGUMENT;
+    jint *pb = (*e)->GetIntArrayElements(e, ptBegin, NULL);
+    if (!pb) return JAICOV_ERR_OUT_OF_MEMORY;
+    const jint np = pb[n];
+    if (np < 0 || (ptUsed && (*e)->GetArrayLength(e, ptUsed) < np) || (ptQ && (*e)->GetArrayLength(e, ptQ) < np)) {
+        (*e)->ReleaseIntArrayElements(e, ptBegin, pb, JNI_ABORT);
+        return JAICOV_ERR_BAD_ARGUMENT;
+    }
+    int rc = 0;
+    jdouble *ps = simil_get(e, src, 3 * np, &rc), *pd = simil_get(e, dst, 3 * np, &rc), *pqs = simil_get(e, cofSrc, 6 * np, &rc);
+    jdouble *pqd = simil_get(e, cofDst, 6 * np, &rc), *pst = simil_get(e, start, 7 * n, &rc);
+    const size_t nm1 = (size_t)(n > 0 ? n : 1), np1 = (size_t)(np > 0 ? np : 1), nl = nm1 > np1 ? nm1 : np1;
+    double *po = (double *)malloc(sizeof(double) * JAICOV_SIMIL_OUT_PER_MODEL * nm1);
+    int32_t *pc = (int32_t *)malloc(sizeof(int32_t) * 3 * nm1);
+    uint8_t *pu = (uint8_t *)malloc(np1);
+    double *pq = (double *)malloc(sizeof(double) * np1);
+    jlong *pl = (jlong *)malloc(sizeof(jlong) * nl);
+    if (!rc && !(po && pc && pu && pq && pl)) rc = JAICOV_ERR_OUT_OF_MEMORY;
+    if (!rc) {
+        rc = jaicov_simil_models((int32_t)n, (const int32_t *)pb, ps, pd, pqs, pqd, pst, (int32_t)maxIterations, rejectThreshold,
+                                 (int32_t)minPoints, po, pc, pc + n, pc + 2 * n, pu, pq, NULL);
+        if (rc == JAICOV_OK) {
+            (*e)->SetDoubleArrayRegion(e, out, 0, JAICOV_SIMIL_OUT_PER_MODEL * n, po);
+            jlongArray to[3] = {status, iterations, startKind};
+            for (int a = 0; a < 3; a++) {
+                if (!to[a]) continue;
+                for (jsize i = 0; i < n; i++) pl[i] = (jlong)pc[(size_t)a * n + i];
+                (*e)->SetLongArrayRegion(e, to[a], 0, n, pl);
+            }
+            if (ptUsed) {
+                for (jsize i = 0; i < np; i++) pl[i] = (jlong)pu[i];
+                (*e)->SetLongArrayRegion(e, ptUsed, 0, np, pl);
+            }
+            if (ptQ) (*e)->SetDoubleArrayRegion(e, ptQ, 0, np, pq);
+        }
+    }
+    free(po); free(pc); free(pu); free(pq); free(pl);
+    if (pst) (*e)->ReleaseDoubleArrayElements(e, start, pst, JNI_ABORT);
+    if (pqd) (*e)->ReleaseDoubleArrayElements(e, cofDst, pqd, JNI_ABORT);
+    if (pqs) (*e)->ReleaseDoubleArrayElements(e, cofSrc, pqs, JNI_ABORT);
+    if (pd) (*e)->ReleaseDoubleArrayElements(e, dst, pd, JNI_ABORT);
+    if (ps) (*e)->ReleaseDoubleArrayElements(e, src, ps, JNI_ABORT);
+    (*e)->ReleaseIntArrayElements(e, ptBegin, pb, JNI_ABORT);
+    return rc;
+}
+
+/* ptBegin with xyz, cof, xyzOut, cofOut, and imgBegin with eo, eoOut, may be null; the outputs are written through scratch buffers */
+JNIEXPORT jint JNICALL NAT(similApply)(JNIEnv *e, jclass k, jdoubleArray par, jintArray ptBegin, jdoubleArray xyz, jdoubleArray cof,
+                                       jintArray imgBegin, jdoubleArray eo, jdoubleArray xyzOut, jdoubleArray cofOut, jdoubleArray eoOut) {
+    (void)k;
+    if (!par || (*e)->GetArrayLength(e, par) % 7 || (cof == NULL) != (cofOut == NULL)) return JAICOV_ERR_BAD_ARGUMENT;
+    const jsize n = (*e)->GetArrayLength(e, par) / 7;
+    if ((ptBegin && (*e)->GetArrayLength(e, ptBegin) != n + 1) || (imgBegin && (*e)->GetArrayLength(e, imgBegin) != n + 1) ||
+        (ptBegin && (!xyz || !xyzOut)) || (imgBegin && (!eo || !eoOut)))
+        return JAICOV_ERR_BAD_ARGUMENT;
+    jint *pb = ptBegin ? (*e)->GetIntArrayElements(e, ptBegin, NULL) : NULL;
+    jint *ib = imgBegin ? (*e)->GetIntArrayElements(e, imgBegin, NULL) : NULL;
+    int rc = ((ptBegin && !pb) || (imgBegin && !ib)) ? JAICOV_ERR_OUT_OF_MEMORY : 0;
+    const jint np = (!rc && pb) ? pb[n] : 0, ni = (!rc && ib) ? ib[n] : 0;
+    if (!rc && (np < 0 || ni < 0 || (np > 0 && (*e)->GetArrayLength(e, xyzOut) < 3 * np) || (np > 0 && cofOut && (*e)->GetArrayLength(e, cofOut) < 6 * np) ||
+                (ni > 0 && (*e)->GetArrayLength(e, eoOut) < 6 * ni)))
+        rc = JAICOV_ERR_BAD_ARGUMENT;
+    jdouble *pp = NULL, *px = NULL, *pq = NULL, *pe = NULL;
+    double *ox = NULL, *oq = NULL, *oe = NULL;
+    if (!rc) {
+        pp = simil_get(e, par, 7 * n, &rc);
+        px = np > 0 ? simil_get(e, xyz, 3 * np, &rc) : NULL;
+        pq = np > 0 ? simil_get(e, cof, 6 * np, &rc) : NULL;
+        pe = ni > 0 ? simil_get(e, eo, 6 * ni, &rc) : NULL;
+        ox = (double *)malloc(sizeof(double) * 3 * (size_t)(np > 0 ? np : 1));
+        oq = (double *)malloc(sizeof(double) * 6 * (size_t)(np > 0 ? np : 1));
+        oe = (double *)malloc(sizeof(double) * 6 * (size_t)(ni > 0 ? ni : 1));
+        if (!rc && !(ox && oq && oe)) rc = JAICOV_ERR_OUT_OF_MEMORY;
+    }
+    if (!rc) {
+        rc = jaicov_simil_apply((int32_t)n, pp, np > 0 ? (const int32_t *)pb : NULL, px, pq, ni > 0 ? (const int32_t *)ib : NULL, pe, ox,
+                                pq ? oq : NULL, oe);
+        if (rc == JAICOV_OK) {
+            if (np > 0) (*e)->SetDoubleArrayRegion(e, xyzOut, 0, 3 * np, ox);
+            if (np > 0 && pq) (*e)->SetDoubleArrayRegion(e, cofOut, 0, 6 * np, oq);
+            if (ni > 0) (*e)->SetDoubleArrayRegion(e, eoOut, 0, 6 * ni, oe);
+        }
+    }
+    free(ox); free(oq); free(oe);
+    if (pe) (*e)->ReleaseDoubleArrayElements(e, eo, pe, JNI_ABORT);
+    if (pq) (*e)->ReleaseDoubleArrayElements(e, cof, pq, JNI_ABORT);
+    if (px) (*e)->ReleaseDoubleArrayElements(e, xyz, px, JNI_ABORT);
+    if (pp) (*e)->ReleaseDoubleArrayElements(e, par, pp, JNI_ABORT);
+    if (ib) (*e)->ReleaseIntArrayElements(e, imgBegin, ib, JNI_ABORT);
+    if (pb) (*e)->ReleaseIntArrayElements(e, ptBegin, pb, JNI_ABORT);
     return rc;
 }

@@ -350,6 +350,47 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 		return status;
 	}
 
+	/** jaicov_simil status values and start kinds (include/jaicov_simil.h) */
+	public static final int SIMIL_OK = 0, SIMIL_NOT_CONVERGED = 1, SIMIL_TOO_FEW_POINTS = 2, SIMIL_SINGULAR = 3, SIMIL_NOT_FINITE = 4;
+	public static final int SIMIL_START_GIVEN = 0, SIMIL_START_CLOSED = 1;
+
+	/**
+	 * Absolute orientation of every model of a batch: the spatial similarity transformation dst = T + m R src between two sets of the
+	 * same points, on the device, with no engine (include/jaicov_simil.h; the reference has no counterpart).  ptBegin (n + 1 CSR
+	 * offsets) selects each model's points; src and dst = 3 doubles per point, the point in the model's frame and in the target frame;
+	 * cofSrc, cofDst (either may be null: 0 and I) = qXX qXY qXZ qYY qYZ qZZ per point; start (may be null) = Tx, Ty, Tz, m, omega, phi,
+	 * kappa per model: a model whose seven values are finite starts from them, any other from the closed start.  out receives 36
+	 * values per model (Tx, Ty, Tz, m, omega, phi, kappa, the upper triangle of their cofactor matrix, Omega); iterations, startKind,
+	 * ptUsed and ptQ may be null.  The result is the status per model; a model whose status is SIMIL_TOO_FEW_POINTS, SIMIL_SINGULAR or
+	 * SIMIL_NOT_FINITE has NaN values.
+	 */
+	public static long[] similarityModels(int[] ptBegin, double[] src, double[] dst, double[] cofSrc, double[] cofDst, double[] start,
+	                                      int maxIterations, double rejectThreshold, int minPoints, double[] out, long[] iterations,
+	                                      long[] startKind, long[] ptUsed, double[] ptQ) {
+		int n = ptBegin.length - 1;
+		long[] status = new long[Math.max(n, 0)];
+		int rc = similModels(ptBegin, src, dst, cofSrc, cofDst, start, maxIterations, rejectThreshold, minPoints, out, status, iterations,
+		                     startKind, ptUsed, ptQ);
+		if (rc == -1) throw new IllegalArgumentException("jaicov_simil_models: bad argument");
+		if (rc == -4) throw new OutOfMemoryError("jaicov_simil_models");
+		if (rc != 0) throw new IllegalStateException("jaicov_simil_models failed with status " + rc);
+		return status;
+	}
+
+	/**
+	 * Carries the points and the image orientations of every model into the target frame (include/jaicov_simil.h).  par = 7 doubles
+	 * per model, the first seven values of similarityModels' out; ptBegin (may be null: no points) with xyz (3 per point), cof (6 per
+	 * point, may be null) and their outputs xyzOut, cofOut; imgBegin (may be null: no orientations) with eo (X0, Y0, Z0, omega, phi,
+	 * kappa per image) and eoOut.  The dispersion of the seven parameters is not propagated.
+	 */
+	public static void similarityApply(double[] par, int[] ptBegin, double[] xyz, double[] cof, int[] imgBegin, double[] eo, double[] xyzOut,
+	                                   double[] cofOut, double[] eoOut) {
+		int rc = similApply(par, ptBegin, xyz, cof, imgBegin, eo, xyzOut, cofOut, eoOut);
+		if (rc == -1) throw new IllegalArgumentException("jaicov_simil_apply: bad argument");
+		if (rc == -4) throw new OutOfMemoryError("jaicov_simil_apply");
+		if (rc != 0) throw new IllegalStateException("jaicov_simil_apply failed with status " + rc);
+	}
+
 	@Override public void close() { if (handle != 0) { destroy(handle); handle = 0; } }
 
 	private void check(int status) {
@@ -410,4 +451,6 @@ public final class NativeNormalEquationEngine implements AutoCloseable {
 	private static native int isectPoints(int[] rayBegin, int[] rayImage, double[] xy, double[] var, int nImages, double[] imageIo, double[] imageEo, double sigma2apriori, int maxIterations, double rejectThreshold, int minRays, double[] out, long[] status, long[] iterations, long[] rayUsed, double[] rayQ);
 	private static native int resectImages(int[] obsBegin, double[] xy, double[] xyz, double[] var, double[] imageIo, double[] eoStart, double sigma2apriori, int maxIterations, double rejectThreshold, int minPoints, double[] out, long[] status, long[] iterations, long[] startKind, long[] obsUsed, double[] obsQ);
 	private static native int orientPairs(int[] obsBegin, double[] xyA, double[] xyB, double[] varA, double[] varB, double[] pairIo, double[] start, double sigma2apriori, int maxIterations, double rejectThreshold, int minPoints, double[] out, long[] status, long[] iterations, long[] startKind, long[] obsUsed, double[] obsQ);
+	private static native int similModels(int[] ptBegin, double[] src, double[] dst, double[] cofSrc, double[] cofDst, double[] start, int maxIterations, double rejectThreshold, int minPoints, double[] out, long[] status, long[] iterations, long[] startKind, long[] ptUsed, double[] ptQ);
+	private static native int similApply(double[] par, int[] ptBegin, double[] xyz, double[] cof, int[] imgBegin, double[] eo, double[] xyzOut, double[] cofOut, double[] eoOut);
 }
