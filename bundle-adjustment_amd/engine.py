@@ -1,7 +1,7 @@
 """ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` / ``include/jaicov_transform.h`` /
 ``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_reliability_points.h`` /
 ``include/jaicov_datum.h`` / ``include/jaicov_intersect.h`` / ``include/jaicov_resect.h`` /
-``include/jaicov_relorient.h`` / ``include/jaicov_simil.h``
+``include/jaicov_relorient.h`` / ``include/jaicov_simil.h`` / ``include/jaicov_lens.h``
 (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
@@ -16,7 +16,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from .problem import FlatProblem, ProblemDesc
+from .problem import DIST_DISTANCE_DI, FlatProblem, ProblemDesc
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libjaicov_neq.so")
@@ -70,6 +70,9 @@ RELOR_START_GIVEN, RELOR_START_SPACE, RELOR_START_PLANE = range(3)
 SIMIL_EXPORTS = ["jaicov_simil_models", "jaicov_simil_apply"]
 SIMIL_OK, SIMIL_NOT_CONVERGED, SIMIL_TOO_FEW_POINTS, SIMIL_SINGULAR, SIMIL_NOT_FINITE = range(5)
 SIMIL_START_GIVEN, SIMIL_START_CLOSED = range(2)
+# include/jaicov_lens.h: lens-distortion correction of a batch of image points and its inverse (stand-alone, no engine)
+LENS_EXPORTS = ["jaicov_lens_correct", "jaicov_lens_distort"]
+LENS_OK, LENS_NOT_CONVERGED, LENS_SINGULAR, LENS_NOT_FINITE = range(4)
 
 KROW = 32  # 12 + JAICOV_MAX_DIST_PER_CAMERA
 INVERT_NONE, INVERT_FULL, INVERT_REDUCED = 0, 1, 2   # MatrixInversion (BundleAdjustment.java:65-70)
@@ -187,6 +190,9 @@ def load_library():
     L.jaicov_simil_models.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, _pd, _pd, C.c_int32, C.c_double, C.c_int32,
                                       _pd, _pi, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
     L.jaicov_simil_apply.argtypes = [C.c_int32, _pd, _pi, _pd, _pd, _pi, _pd, _pd, _pd, _pd]
+    L.jaicov_lens_correct.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.c_int32, _pd, _pd, _pi, _pi, _pi, _pd, C.c_int32, C.c_double,
+                                      _pd, _pd, _pd, _pi, _pi, _pd]
+    L.jaicov_lens_distort.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.c_int32, _pd, _pd, _pi, _pi, _pi, _pd, _pd, _pd, _pd, _pi, _pd]
     _LIB = L
     return L
 
@@ -781,6 +787,104 @@ def similarity_apply(par, pt_begin, xyz, cof=None, img_begin=None, eo=None):
         raise EngineError(rc, "similarity apply")
     return (None if xo is None else xo.reshape(-1, 3), None if qo is None else qo.reshape(-1, 6),
             None if eo_out is None else eo_out.reshape(-1, 6))
+
+
+def _lens_call(correct, xy, camera, cam_io, cam_r0, cam_dist_begin, dist_kind, dist_order, dist_value, var, depth, max_iterations,
+               tolerance, with_jacobian, with_time):
+    L = load_library()
+    what = "lens correct" if correct else "lens distort"
+    xy = np.ascontiguousarray(xy, np.float64).reshape(-1)
+    cam = np.ascontiguousarray(camera, np.int32).ravel()
+    io = np.ascontiguousarray(cam_io, np.float64).reshape(-1)
+    r0 = np.ascontiguousarray(cam_r0, np.float64).ravel()
+    begin = np.ascontiguousarray(cam_dist_begin, np.int32).ravel()
+    kind = np.ascontiguousarray(dist_kind, np.int32).ravel()
+    order = np.ascontiguousarray(dist_order, np.int32).ravel()
+    value = np.ascontiguousarray(dist_value, np.float64).ravel()
+    var = None if var is None else np.ascontiguousarray(var, np.float64).reshape(-1)
+    depth = None if depth is None else np.ascontiguousarray(depth, np.float64).ravel()
+    n, nc = cam.size, r0.size
+    if xy.size != 2 * n or io.size != 3 * nc or begin.size != nc + 1 or kind.size != order.size or kind.size != value.size or \
+            (begin.size and begin[-1] != kind.size) or (var is not None and var.size != 3 * n) or (depth is not None and depth.size != n):
+        raise EngineError(-1, f"{what}: array sizes do not agree")
+    xy_out = np.zeros(2 * n); var_out = np.zeros(3 * n); status = np.zeros(n, np.int32); iterations = np.zeros(n, np.int32)
+    jac = np.zeros(4 * n) if with_jacobian else None
+    ms = np.zeros(1)
+    null = C.cast(None, _pd)
+    head = (n, cam.ctypes.data_as(_pi), _p(xy), _p(var) if var is not None else null, _p(depth) if depth is not None else null, nc, _p(io),
+            _p(r0), begin.ctypes.data_as(_pi), kind.ctypes.data_as(_pi), order.ctypes.data_as(_pi), _p(value))
+    tail = (_p(xy_out), _p(var_out), _p(jac) if jac is not None else null, status.ctypes.data_as(_pi))
+    if correct:
+        rc = L.jaicov_lens_correct(*head, int(max_iterations), float(tolerance), *tail, iterations.ctypes.data_as(_pi), _p(ms))
+    else:
+        rc = L.jaicov_lens_distort(*head, *tail, _p(ms))
+    if rc != 0:
+        raise EngineError(rc, what)
+    out = (xy_out.reshape(-1, 2), var_out.reshape(-1, 3), status) + ((iterations,) if correct else ())
+    return out + ((jac.reshape(-1, 2, 2),) if with_jacobian else ()) + ((float(ms[0]),) if with_time else ())
+
+
+def lens_correct(xy, camera, cam_io, cam_r0, cam_dist_begin, dist_kind, dist_order, dist_value, var=None, depth=None, max_iterations=20,
+                 tolerance=0.0, with_jacobian=False, with_time=False):
+    """Reduces measured image coordinates to those of the distortion-free camera (include/jaicov_lens.h).  xy: (n, 2); camera: (n,)
+    the camera of each point; cam_io: (C, 3) x0, y0, c; cam_r0: (C,); cam_dist_begin: (C + 1,) CSR offsets into dist_kind, dist_order,
+    dist_value; var: (n, 3) var_x, var_y, rho or None (the unit matrix is propagated); depth: (n,) N of each point or None (needed
+    only where a camera has a distance-dependent coefficient); tolerance 0: sqrt(EPS).  Returns (xy (n, 2), var (n, 3), status (n,),
+    iterations (n,)), plus J (n, 2, 2) with with_jacobian and the kernel time in ms with with_time."""
+    return _lens_call(True, xy, camera, cam_io, cam_r0, cam_dist_begin, dist_kind, dist_order, dist_value, var, depth, max_iterations,
+                      tolerance, with_jacobian, with_time)
+
+
+def lens_distort(xy, camera, cam_io, cam_r0, cam_dist_begin, dist_kind, dist_order, dist_value, var=None, depth=None, with_jacobian=False,
+                 with_time=False):
+    """Applies the cameras' distortion models to ideal image coordinates: the inverse of lens_correct, one evaluation per point
+    (include/jaicov_lens.h).  The arguments are lens_correct's.  Returns (xy (n, 2), var (n, 3), status (n,)), plus J (n, 2, 2) with
+    with_jacobian and the kernel time in ms with with_time."""
+    return _lens_call(False, xy, camera, cam_io, cam_r0, cam_dist_begin, dist_kind, dist_order, dist_value, var, depth, 1, 0.0,
+                      with_jacobian, with_time)
+
+
+def lens_tables_without_distance(cam_dist_begin, dist_kind, dist_order, dist_value):
+    """The coefficient tables without their distance-dependent (Di) entries, for a caller who knows no object space yet."""
+    begin = np.asarray(cam_dist_begin, np.int64)
+    kind = np.asarray(dist_kind, np.int32)
+    keep = kind != DIST_DISTANCE_DI
+    kept = np.concatenate([[0], np.cumsum(keep)])
+    return kept[begin].astype(np.int32), kind[keep], np.asarray(dist_order, np.int32)[keep], np.asarray(dist_value, np.float64)[keep]
+
+
+def lens_correct_problem(fp: FlatProblem, values=None, distance="ignore", with_status=False, **kw):
+    """A copy of a FlatProblem whose image points are corrected for lens distortion, so that relorient_problem, intersect_problem,
+    resect_problem and dlt_adjust take it unchanged: cameras and coefficients come from the slot vector `values` (default fp.values:
+    slot_io, slot_dist, with the problem's cam_r0 and cam_dist_begin), and ip_x, ip_y, ip_var_x, ip_var_y, ip_rho of every image point
+    are replaced by the corrected ones (a point whose status is SINGULAR or NOT_FINITE keeps its values).  distance="ignore" leaves the
+    distance-dependent coefficients out; distance="values" forms N of every image point (PDF:151) from the object points and exterior
+    orientations in `values`, for a second round once a model exists.  Joint dispersions of image blocks (blk_disp) are left as they
+    are: only the 2 x 2 dispersion of a point is propagated.  with_status also returns (status, iterations).  kw: as lens_correct."""
+    import copy
+    if distance not in ("ignore", "values"):
+        raise EngineError(-1, "lens correct problem: distance is 'ignore' or 'values'")
+    v = np.array(fp.values if values is None else values, np.float64)
+    io = v[fp.slot_io(0):fp.slot_io(0) + 3 * fp.n_cameras].reshape(-1, 3)
+    tables = (fp.cam_dist_begin, fp.dist_kind, fp.dist_order, v[fp.slot_dist(0):fp.slot_dist(0) + fp.n_dist])
+    img, pt = np.asarray(fp.ip_image), np.asarray(fp.ip_point)
+    depth = None
+    if distance == "ignore":
+        tables = lens_tables_without_distance(*tables)
+    else:
+        eo = v[fp.slot_eo(0):].reshape(-1, 6)[img]
+        so, co, sp, cp = np.sin(eo[:, 3]), np.cos(eo[:, 3]), np.sin(eo[:, 4]), np.cos(eo[:, 4])
+        d = v[:3 * fp.n_points].reshape(-1, 3)[pt] - eo[:, :3]
+        depth = sp * d[:, 0] + (-so * cp) * d[:, 1] + (co * cp) * d[:, 2]          # N = r13 dX + r23 dY + r33 dZ
+    var = np.stack([fp.ip_var_x, fp.ip_var_y, fp.ip_rho], 1)
+    xy, var_out, status, iterations = lens_correct(np.stack([fp.ip_x, fp.ip_y], 1), np.asarray(fp.image_camera)[img], io, fp.cam_r0,
+                                                   *tables, var=var, depth=depth, **kw)[:4]
+    ok = status <= LENS_NOT_CONVERGED
+    out = copy.copy(fp)
+    out.ip_x = np.where(ok, xy[:, 0], fp.ip_x); out.ip_y = np.where(ok, xy[:, 1], fp.ip_y)
+    out.ip_var_x = np.where(ok, var_out[:, 0], fp.ip_var_x); out.ip_var_y = np.where(ok, var_out[:, 1], fp.ip_var_y)
+    out.ip_rho = np.where(ok, var_out[:, 2], fp.ip_rho)
+    return (out, status, iterations) if with_status else out
 
 
 def dense_gemm(alay, blay, A, B, C_in, M, N, K, alpha=1.0, beta=0.0, lower_only=False, kmode=0, repeats=0):

@@ -316,6 +316,26 @@ PYBIND11_MODULE(_jaicov_host, m) {
         .def_static("getMaximalNumberOfIterations", &SimilarityTransformation::getMaximalNumberOfIterations)
         .def_static("setMaximalNumberOfIterations", &SimilarityTransformation::setMaximalNumberOfIterations);
 
+    py::class_<LensCorrection> lens(m, "LensCorrection");
+    py::class_<LensCorrection::Result>(lens, "Result")
+        .def(py::init<>())
+        .def_property("coordinate", [](LensCorrection::Result &r) { return r.coordinate; },
+                      [](LensCorrection::Result &r, ImageCoordinate *ic) { r.coordinate = ic; }, py::return_value_policy::reference)
+        .def_readwrite("x", &LensCorrection::Result::x)
+        .def_readwrite("y", &LensCorrection::Result::y)
+        .def_readwrite("varianceX", &LensCorrection::Result::varianceX)
+        .def_readwrite("varianceY", &LensCorrection::Result::varianceY)
+        .def_readwrite("rho", &LensCorrection::Result::rho)
+        .def_readwrite("status", &LensCorrection::Result::status)
+        .def_readwrite("iterations", &LensCorrection::Result::iterations);
+    py::class_<LensCorrection::Scope>(lens, "Scope")
+        .def(py::init<const std::vector<LensCorrection::Result> &>(), py::arg("results"))
+        .def("applied", &LensCorrection::Scope::applied);
+    lens.def_static("correctAll", &LensCorrection::correctAll, py::arg("camera"), py::arg("withDistance") = false, py::arg("tolerance") = 0.0)
+        .def_static("distortAll", &LensCorrection::distortAll, py::arg("camera"), py::arg("withDistance") = false)
+        .def_static("getMaximalNumberOfIterations", &LensCorrection::getMaximalNumberOfIterations)
+        .def_static("setMaximalNumberOfIterations", &LensCorrection::setMaximalNumberOfIterations);
+
     py::class_<AiconProject>(m, "AiconProject")
         .def_property_readonly("camera", [](AiconProject &p) { return p.camera ? p.camera.get() : (p.cameras.empty() ? nullptr : p.cameras[0].get()); },
                                py::return_value_policy::reference_internal)

@@ -904,4 +904,109 @@ bool SimilarityTransformation::apply(const Result &r, const std::vector<ObjectCo
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// LensCorrection (include/jaicov_lens.h) on the device
+// ---------------------------------------------------------------------------------------------------------------
+std::vector<LensCorrection::Result> LensCorrection::run(Camera &camera, bool correct, bool withDistance, double tolerance) {
+    // the camera's tables, as flatten() lays them out
+    InteriorOrientation &io = camera.getInteriorOrientation();
+    const double cam_io[3] = {io.getPrinciplePointX().getValue(), io.getPrinciplePointY().getValue(), io.getPrincipleDistance().getValue()};
+    double r0 = 0.0;
+    std::vector<int32_t> kind, order;
+    std::vector<double> value;
+    for (auto &m : camera.getDistortionModels()) {
+        if (m->getType() >= DistortionModel::Type::RADIAL_DISTORTION) r0 = m->getR0();
+        if (m->getType() == DistortionModel::Type::DISTANCE_DISTORTION && !withDistance) continue;
+        for (auto &p : m->parameters()) {
+            int k;
+            switch (p->getParameterType()) {
+            case ParameterType::AFFINITY_AND_SHEAR_Cx: k = JAICOV_DIST_AFFINITY_CX; break;
+            case ParameterType::AFFINITY_AND_SHEAR_Cy: k = JAICOV_DIST_AFFINITY_CY; break;
+            case ParameterType::TANGENTIAL_DISTORTION_Bx: k = JAICOV_DIST_TANGENTIAL_BX; break;
+            case ParameterType::TANGENTIAL_DISTORTION_By: k = JAICOV_DIST_TANGENTIAL_BY; break;
+            case ParameterType::TANGENTIAL_POLYNOMIAL_B: k = JAICOV_DIST_TANGENTIAL_BI; break;
+            case ParameterType::RADIAL_POLYNOMIAL_A: k = JAICOV_DIST_RADIAL_AI; break;
+            case ParameterType::ZERNIKE_POLYNOMIAL_X: k = JAICOV_DIST_ZERNIKE_X; break;
+            case ParameterType::ZERNIKE_POLYNOMIAL_Y: k = JAICOV_DIST_ZERNIKE_Y; break;
+            case ParameterType::ZERNIKE_POLYNOMIAL_Z: k = JAICOV_DIST_ZERNIKE_Z; break;
+            default: k = JAICOV_DIST_DISTANCE_DI; break;
+            }
+            kind.push_back(k); order.push_back(p->getOrder() > 0 ? p->getOrder() : 0); value.push_back(p->getValue());
+        }
+    }
+    const int32_t begin[2] = {0, (int32_t)kind.size()};
+    std::vector<Result> res;
+    std::vector<double> xy, var, depth;
+    for (auto &im : camera.images()) {
+        ExteriorOrientation &eo = im->getExteriorOrientation();
+        const double so = std::sin(eo.at(3)->getValue()), co = std::cos(eo.at(3)->getValue());
+        const double sp = std::sin(eo.at(4)->getValue()), cp = std::cos(eo.at(4)->getValue());
+        for (auto &ic : im->coordinates()) {
+            Result r;
+            r.coordinate = ic.get();
+            res.push_back(r);
+            xy.push_back(ic->getX().getValue()); xy.push_back(ic->getY().getValue());
+            var.push_back(ic->getX().getVariance()); var.push_back(ic->getY().getVariance()); var.push_back(ic->getCorrelationCoefficientXY());
+            if (withDistance) {                       // N = r13 dX + r23 dY + r33 dZ (PDF:127-135, 151)
+                ObjectCoordinate *oc = ic->getObjectCoordinate();
+                if (!oc) throw std::invalid_argument("LensCorrection: an image coordinate without its object coordinate has no distance");
+                const double dX = oc->getX().getValue() - eo.at(0)->getValue(), dY = oc->getY().getValue() - eo.at(1)->getValue(),
+                             dZ = oc->getZ().getValue() - eo.at(2)->getValue();
+                depth.push_back(sp * dX + (-so * cp) * dY + (co * cp) * dZ);
+            }
+        }
+    }
+    const int n = (int)res.size();
+    std::vector<int32_t> cam((size_t)n, 0), status((size_t)n), iterations((size_t)n, 0);
+    std::vector<double> xyo(2 * (size_t)n), varo(3 * (size_t)n);
+    const int rc = correct ? jaicov_lens_correct(n, cam.data(), xy.data(), var.data(), withDistance ? depth.data() : nullptr, 1, cam_io, &r0, begin,
+                                                 kind.data(), order.data(), value.data(), maximalNumberOfIterations_, tolerance, xyo.data(),
+                                                 varo.data(), nullptr, status.data(), iterations.data(), nullptr)
+                           : jaicov_lens_distort(n, cam.data(), xy.data(), var.data(), withDistance ? depth.data() : nullptr, 1, cam_io, &r0, begin,
+                                                 kind.data(), order.data(), value.data(), xyo.data(), varo.data(), nullptr, status.data(), nullptr);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string(correct ? "jaicov_lens_correct" : "jaicov_lens_distort") + " failed with status " + std::to_string(rc));
+    for (int k = 0; k < n; k++) {
+        Result &r = res[k];
+        r.x = xyo[2 * k]; r.y = xyo[2 * k + 1];
+        r.varianceX = varo[3 * k]; r.varianceY = varo[3 * k + 1]; r.rho = varo[3 * k + 2];
+        r.status = status[k]; r.iterations = iterations[k];
+    }
+    return res;
+}
+
+std::vector<LensCorrection::Result> LensCorrection::correctAll(Camera &camera, bool withDistance, double tolerance) {
+    return run(camera, true, withDistance, tolerance);
+}
+
+std::vector<LensCorrection::Result> LensCorrection::distortAll(Camera &camera, bool withDistance) { return run(camera, false, withDistance, 0.0); }
+
+LensCorrection::Scope::Scope(const std::vector<Result> &results) {
+    for (const Result &r : results) {
+        if (!r.coordinate || (r.status != JAICOV_LENS_OK && r.status != JAICOV_LENS_NOT_CONVERGED)) continue;
+        ImageCoordinate *ic = r.coordinate;
+        Result old = r;
+        old.x = ic->getX().getValue(); old.y = ic->getY().getValue();
+        old.varianceX = ic->getX().getVariance(); old.varianceY = ic->getY().getVariance(); old.rho = ic->getCorrelationCoefficientXY();
+        saved_.push_back(old);
+        try {
+            ic->getX().setValue(r.x); ic->getY().setValue(r.y);
+            ic->getX().setVariance(r.varianceX); ic->getY().setVariance(r.varianceY); ic->setCorrelationCoefficientXY(r.rho);
+        } catch (...) {                               // a setter refused a value: no destructor will run, so everything goes back here
+            restore();
+            throw;
+        }
+    }
+}
+
+void LensCorrection::Scope::restore() {
+    for (auto o = saved_.rbegin(); o != saved_.rend(); ++o) {
+        ImageCoordinate *ic = o->coordinate;
+        ic->getX().setValue(o->x); ic->getY().setValue(o->y);
+        ic->getX().setVariance(o->varianceX); ic->getY().setVariance(o->varianceY); ic->setCorrelationCoefficientXY(o->rho);
+    }
+    saved_.clear();
+}
+
+LensCorrection::Scope::~Scope() { restore(); }
+
 }  // namespace jaicov::host

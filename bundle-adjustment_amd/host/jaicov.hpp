@@ -33,6 +33,7 @@
 #include "../../include/jaicov_resect.h"
 #include "../../include/jaicov_relorient.h"
 #include "../../include/jaicov_simil.h"
+#include "../../include/jaicov_lens.h"
 #include "../../include/jaicov_reliability.h"
 #include "../../include/jaicov_reliability_points.h"
 #include "../../include/jaicov_datum.h"
@@ -301,6 +302,10 @@ public:
     ObservationParameter &getX() { return x_; }
     ObservationParameter &getY() { return y_; }
     double getCorrelationCoefficientXY() const { return rho_; }
+    void setCorrelationCoefficientXY(double rho) {
+        if (!(std::fabs(rho) < 1)) throw std::invalid_argument("Error, correlation coefficient rho(x,y) must be in the open interval (-1 1)");
+        rho_ = rho;
+    }
     Image *getReference() const { return img_; }
 private:
     ObjectCoordinate *oc_;
@@ -753,6 +758,44 @@ public:
     static void setMaximalNumberOfIterations(int n) { maximalNumberOfIterations_ = n; }
 private:
     static inline int maximalNumberOfIterations_ = 50;
+};
+
+// Lens-distortion correction on the device (include/jaicov_lens.h): the measured image coordinates of a camera reduced to those of the
+// distortion-free camera, with their 2 x 2 dispersion, and the inverse that applies the camera's distortion models to ideal
+// coordinates.  The reference has no counterpart.  Each call takes every image coordinate of the camera, image by image in insertion
+// order, with the current values of the interior orientation and of the distortion coefficients, and makes one device call.
+// Distance-dependent coefficients (Di) are left out unless withDistance: then N of every point (PDF:151) is formed from the current
+// values of its object point and of the image's exterior orientation; a point whose N is not finite (no values yet) or 0 comes back
+// JAICOV_LENS_NOT_FINITE.  Nothing is written into the coordinates: Scope does that for
+// as long as it lives.  A device error (no GPU, out of memory) throws std::runtime_error.
+class LensCorrection {
+public:
+    struct Result {
+        ImageCoordinate *coordinate = nullptr;
+        double x = 0, y = 0, varianceX = 0, varianceY = 0, rho = 0;
+        int status = -1, iterations = 0;
+    };
+    static std::vector<Result> correctAll(Camera &camera, bool withDistance = false, double tolerance = 0.0);
+    static std::vector<Result> distortAll(Camera &camera, bool withDistance = false);
+    static int getMaximalNumberOfIterations() { return maximalNumberOfIterations_; }
+    static void setMaximalNumberOfIterations(int n) { maximalNumberOfIterations_ = n; }
+
+    // writes the results whose status is JAICOV_LENS_OK or JAICOV_LENS_NOT_CONVERGED into their ImageCoordinates (values, variances,
+    // rho) and puts the former ones back when it goes out of scope
+    class Scope {
+    public:
+        explicit Scope(const std::vector<Result> &results);
+        ~Scope();
+        Scope(const Scope &) = delete;
+        Scope &operator=(const Scope &) = delete;
+        int applied() const { return (int)saved_.size(); }
+    private:
+        void restore();
+        std::vector<Result> saved_;
+    };
+private:
+    static std::vector<Result> run(Camera &camera, bool correct, bool withDistance, double tolerance);
+    static inline int maximalNumberOfIterations_ = 20;
 };
 
 }  // namespace jaicov::host

@@ -7,6 +7,7 @@
  * DLTPartialDerivativeFactory.java), which adjusts one image at a time on one thread.  Here every image of the call is adjusted
  * by one wave of one kernel launch (bundle-adjustment_amd/csrc/dlt.hip), the whole Gauss-Newton loop included.  It is a
  * stand-alone call with no engine (as jaicov_dense_spd_solve_packed): start values are needed before an engine means anything.
+ * Lens distortion is not modelled; jaicov_lens_correct (jaicov_lens.h) reduces measured image points of a calibrated camera beforehand.
  *
  * Semantics, per image g (observations obs_begin[g] .. obs_begin[g+1]-1, the image's homologous points in the image's order:
  * the caller has already matched the image points with the control points, DT:73-94)

@@ -13,6 +13,7 @@
  * image ray_image[k])
  *   Model.  The collinearity equations PDF:137-152 with the rotation R(omega, phi, kappa) of PDF:125-135, without distortion (the DLT
  *     models none either; the adjustment's first passes remove what is left).  c may have either sign (AICON: c < 0).
+ *     jaicov_lens_correct (jaicov_lens.h) reduces measured image points to this model beforehand, with their dispersions.
  *     Weights per ray (PDF:308-319): rho == 0: P = diag(s0/var_x, s0/var_y); else inv = s0 / ((1 - rho^2) var_x var_y),
  *     P = [[inv var_y, -inv rho sqrt(var_x var_y)], [., inv var_x]], s0 = sigma2apriori.  var == NULL: P = I.
  *   Fewer than 2 rays: JAICOV_ISECT_TOO_FEW_RAYS.

@@ -67,7 +67,8 @@
  *     two runs give the same bits, and a pair's result does not depend on what else is in the batch.
  *   Not resolved.  For an exactly planar field both decompositions of the homography are exact relative orientations, and with 5
  *     points there is no redundancy: Omega cannot tell such solutions apart, and the first in the order above is returned.  Not
- *     modelled: lens distortion in the rays; the adjustment's first passes remove what is left.
+ *     modelled: lens distortion in the rays; the adjustment's first passes remove what is left.  jaicov_lens_correct (jaicov_lens.h)
+ *     reduces measured image points to the distortion-free camera beforehand, with their dispersions.
  *
  * Output out[28 g + k]: X0, Y0, Z0, omega, phi, kappa of image b; the 21 entries of the cofactor matrix, upper triangle row by row in
  * that order; Omega.

@@ -51,7 +51,8 @@
  *   Not resolved: the two-fold ambiguity of the pose of a plane field seen nearly head-on (both poses fit within the noise; the
  *     start with the smaller Omega is taken and Gauss-Newton stays in its basin).  4 or 5 points that do not lie in a plane have the
  *     plane start only, which need not lie in the basin of the true pose: Omega tells.  Not modelled: lens distortion, as in the DLT
- *     and the intersection; the adjustment's first passes remove what is left.
+ *     and the intersection; the adjustment's first passes remove what is left.  jaicov_lens_correct (jaicov_lens.h) reduces measured
+ *     image points to the distortion-free camera beforehand, with their dispersions.
  *
  * Output out[28 g + k]: X0, Y0, Z0, omega, phi, kappa; the 21 entries of Q, upper triangle row by row in that parameter order; Omega.
  */
