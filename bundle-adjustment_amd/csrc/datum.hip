@@ -1,9 +1,9 @@
 // Baarda's S-transformation of the cofactor matrix on the device (include/jaicov_datum.h).
 //
 // The cofactor matrix Q (order n, border rows 0 .. d-1, lower part of a row-major square) is read twice and written once:
-//   1. datum_y_tile_kernel + datum_y_reduce_kernel: Y = Q B'' over the lower triangle.  Each 128 x 128 tile serves its rows and,
-//      transposed, its columns; the partial sums go to a [block row][slot] table and are added in slot order (as the refinement's
-//      symv_dd_tile_kernel does in refine.hip), so two runs give the same bits.
+//   1. sym_y_tile_kernel + sym_y_reduce_kernel (symtile.h, shared with precision.hip): Y = Q B'' over the lower triangle, rows and
+//      columns [d, n).  Each 128 x 128 tile serves its rows and, transposed, its columns; the partial sums go to a [block row][slot]
+//      table and are added in slot order, so two runs give the same bits.
 //   2. the d x d algebra on the host: G^ (the unknowns x border block, n d doubles), C = (B' G^)^-1, Z = G^ C, W = B' Y,
 //      Y~ = Y - Z W / 2.
 //   3. datum_update_kernel: Q' = Q - Z Y~' - Y~ Z' on the unknowns block, Z in the border block, 0 in the border x border block,
@@ -19,140 +19,12 @@
 #include "../../include/jaicov_datum.h"
 #include "datum.h"
 #include "status.h"
+#include "symtile.h"
 
 namespace jaicov {
 
 void datum_state_invalidate(DatumState *s) {
     if (s) s->valid = false;
-}
-
-// One workgroup per lower tile (I, J), J <= I, in four slabs of 32 rows.  Row part: thread (rr, seg) holds row rr of the slab,
-// columns 16 q + 2 seg + {0, 1}; the 8 lanes of a row are summed by butterfly.  Column part: thread (h, c) adds rows
-// 16 h .. 16 h + 15 of every slab for column c from LDS.  Entries outside rows / columns [d, n) count as zero; on a diagonal tile
-// the strict upper part is not Q and the diagonal is counted once (row part).
-// P[((I nbk + slot) 128 + i) D + a] = contribution of block column `slot` to Y[128 I + i][a].
-template <int D>
-__global__ __launch_bounds__(256) void datum_y_tile_kernel(const double *__restrict__ Q, long ld, int n, int d,
-                                                           const double *__restrict__ Bt, int np, int nbk, double *__restrict__ P) {
-    __shared__ double slab[32 * 128];        // one slab of the tile; afterwards the column partial sums [2][128][D]
-    __shared__ double bJ[D][128], bI[D][128];
-    __shared__ double rowres[128][D];
-    const int t = blockIdx.x;
-    int I = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while ((long)(I + 1) * (I + 2) / 2 <= t) ++I;
-    while ((long)I * (I + 1) / 2 > t) --I;
-    const int J = t - I * (I + 1) / 2;
-    const int tid = threadIdx.x;
-    const bool diag = I == J;
-    for (int k = tid; k < D * 128; k += 256) {
-        const int a = k >> 7, c = k & 127;
-        bJ[a][c] = Bt[(long)a * np + J * 128 + c];
-        bI[a][c] = Bt[(long)a * np + I * 128 + c];
-    }
-    __syncthreads();
-    const int rr = tid >> 3, seg = tid & 7;      // row role
-    const int cc = tid & 127, h = tid >> 7;      // column role
-    double cacc[D];
-#pragma unroll
-    for (int a = 0; a < D; a++) cacc[a] = 0.0;
-#pragma unroll 1
-    for (int s = 0; s < 4; s++) {
-        const int r = 32 * s + rr, gr = I * 128 + r;
-        const bool rowok = gr >= d && gr < n;
-        const double *qrow = Q + (long)gr * ld;
-        double v[16];
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int c0 = 16 * q + 2 * seg, gc = J * 128 + c0;
-            if (rowok && gc >= d && gc + 1 < n) {
-                const double2 x = *reinterpret_cast<const double2 *>(qrow + gc);
-                v[2 * q] = x.x; v[2 * q + 1] = x.y;
-            } else {
-                v[2 * q] = (rowok && gc >= d && gc < n) ? qrow[gc] : 0.0;
-                v[2 * q + 1] = (rowok && gc + 1 >= d && gc + 1 < n) ? qrow[gc + 1] : 0.0;
-            }
-            if (diag && c0 > r) v[2 * q] = 0.0;
-            if (diag && c0 + 1 > r) v[2 * q + 1] = 0.0;
-        }
-        double racc[D];
-#pragma unroll
-        for (int a = 0; a < D; a++) {
-            double acc = 0.0;
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                const int c0 = 16 * q + 2 * seg;
-                acc = fma(v[2 * q], bJ[a][c0], acc);
-                acc = fma(v[2 * q + 1], bJ[a][c0 + 1], acc);
-            }
-            racc[a] = acc;
-        }
-#pragma unroll
-        for (int m = 1; m < 8; m <<= 1)
-#pragma unroll
-            for (int a = 0; a < D; a++) racc[a] += __shfl_xor(racc[a], m, 64);
-        if (seg == 0)
-#pragma unroll
-            for (int a = 0; a < D; a++) rowres[r][a] = racc[a];
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int c0 = 16 * q + 2 * seg;
-            slab[rr * 128 + c0] = v[2 * q];
-            slab[rr * 128 + c0 + 1] = v[2 * q + 1];
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int k = 0; k < 16; k++) {
-            const int rl = 16 * h + k, r2 = 32 * s + rl;
-            const double x = (diag && cc == r2) ? 0.0 : slab[rl * 128 + cc];
-#pragma unroll
-            for (int a = 0; a < D; a++) cacc[a] = fma(x, bI[a][r2], cacc[a]);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int a = 0; a < D; a++) slab[(h * 128 + cc) * D + a] = cacc[a];
-    __syncthreads();
-    if (tid < 128) {
-        const size_t sz = (size_t)128 * D;
-#pragma unroll
-        for (int a = 0; a < D; a++) {
-            const double col = slab[tid * D + a] + slab[(128 + tid) * D + a];
-            if (diag) {
-                P[((size_t)I * nbk + I) * sz + (size_t)tid * D + a] = rowres[tid][a] + col;
-            } else {
-                P[((size_t)I * nbk + J) * sz + (size_t)tid * D + a] = rowres[tid][a];
-                P[((size_t)J * nbk + I) * sz + (size_t)tid * D + a] = col;
-            }
-        }
-    }
-}
-
-// Y[g][a] for the rows g of block row I: 4 groups of 128 threads add every fourth slot each (fixed order), the groups are
-// combined in group order.  Rows outside [d, n) are 0.
-template <int D>
-__global__ __launch_bounds__(512) void datum_y_reduce_kernel(const double *__restrict__ P, int nbk, int n, int d, double *__restrict__ Y) {
-    __shared__ double part[4][128][D];
-    const int I = blockIdx.x, i = threadIdx.x & 127, grp = threadIdx.x >> 7, g = I * 128 + i;
-    const size_t sz = (size_t)128 * D;
-    double acc[D];
-#pragma unroll
-    for (int a = 0; a < D; a++) acc[a] = 0.0;
-    for (int s = grp; s < nbk; s += 4) {
-        const double *p = P + ((size_t)I * nbk + s) * sz + (size_t)i * D;
-#pragma unroll
-        for (int a = 0; a < D; a++) acc[a] += p[a];
-    }
-#pragma unroll
-    for (int a = 0; a < D; a++) part[grp][i][a] = acc[a];
-    __syncthreads();
-    if (grp != 0) return;
-    const bool ok = g >= d && g < n;
-#pragma unroll
-    for (int a = 0; a < D; a++) {
-        double y = part[0][i][a];
-        for (int q = 1; q < 4; q++) y += part[q][i][a];
-        Y[(size_t)g * D + a] = ok ? y : 0.0;
-    }
 }
 
 // Q'[i][j], j <= i < n: 0 (i < d), Z[i][j] (j < d <= i), Q[i][j] - sum_a (Z[i][a] Y~[j][a] + Y~[i][a] Z[j][a]) otherwise.
@@ -191,13 +63,6 @@ __global__ __launch_bounds__(256) void datum_update_kernel(double *__restrict__ 
 }
 
 template <int D>
-static hipError_t launch_y(hipStream_t st, const double *Q, long ld, int n, int d, const double *Bt, int np, int nbk, double *P, double *Y) {
-    hipLaunchKernelGGL(datum_y_tile_kernel<D>, dim3(nbk * (nbk + 1) / 2), dim3(256), 0, st, Q, ld, n, d, Bt, np, nbk, P);
-    hipLaunchKernelGGL(datum_y_reduce_kernel<D>, dim3(nbk), dim3(512), 0, st, P, nbk, n, d, Y);
-    return hipGetLastError();
-}
-
-template <int D>
 static hipError_t launch_update(hipStream_t st, double *Q, long ld, int n, int d, const double *ZY) {
     hipLaunchKernelGGL(datum_update_kernel<D>, dim3((n + 255) / 256, (n + 31) / 32), dim3(256), 0, st, Q, ld, n, d, ZY);
     return hipGetLastError();
@@ -205,13 +70,13 @@ static hipError_t launch_update(hipStream_t st, double *Q, long ld, int n, int d
 
 static hipError_t launch_y_d(int D, hipStream_t st, const double *Q, long ld, int n, const double *Bt, int np, int nbk, double *P, double *Y) {
     switch (D) {
-    case 1: return launch_y<1>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
-    case 2: return launch_y<2>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
-    case 3: return launch_y<3>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
-    case 4: return launch_y<4>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
-    case 5: return launch_y<5>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
-    case 6: return launch_y<6>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
-    default: return launch_y<7>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
+    case 1: return launch_sym_y<1>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
+    case 2: return launch_sym_y<2>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
+    case 3: return launch_sym_y<3>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
+    case 4: return launch_sym_y<4>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
+    case 5: return launch_sym_y<5>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
+    case 6: return launch_sym_y<6>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
+    default: return launch_sym_y<7>(st, Q, ld, n, D, Bt, np, nbk, P, Y);
     }
 }
 

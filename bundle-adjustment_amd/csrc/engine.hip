@@ -21,6 +21,7 @@
 #include "dense.h"
 #include "devbuf.h"
 #include "gemm_f64.h"
+#include "precision.h"
 #include "reliability.h"
 #include "status.h"
 #include "transform.h"
@@ -282,6 +283,7 @@ struct jaicov_engine {
     double q_sigma2 = 0.0, q_lambda = 0.0;             // sigma0^2 and damping of the build whose system the cofactor matrix inverts
     std::vector<double> q_vals;                        // slot values of that build: the datum rows of jaicov_datum_transform (datum.hip)
     std::unique_ptr<jaicov::DatumState> datum;         // S of the last jaicov_datum_transform and its work buffers
+    std::unique_ptr<jaicov::PrecisionState> prec;      // work buffers of the precision calls (precision.hip)
 };
 
 template <typename T, typename P>      // P: T or const T
@@ -1602,6 +1604,25 @@ void jaicov::engine_datum_view(jaicov_engine *e, DatumView *v) {
     v->d = e->d;
     v->n_points = e->n_points;
     v->state = &e->datum;
+    v->err = &e->err;
+}
+
+// precision.hip reads the cofactor matrix, the slot vector and the slot table through this view (include/jaicov_precision.h)
+void jaicov::engine_prec_view(jaicov_engine *e, PrecView *v) {
+    const DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
+    v->device = e->device;
+    v->stream = e->stream;
+    v->have_q = e->have_Q;
+    v->reduced = e->q_reduced;
+    v->sharded = !e->all_images || !e->opts.apply_shared || e->ip0 != 0 || e->ip_count != e->p.n_ip;
+    v->Q = qs.Q;
+    v->ld = qs.ld;
+    v->order = e->q_order;
+    v->d = e->d;
+    v->d_vals = e->d_vals;
+    v->p = &e->p;
+    v->slot_col = &e->h_slot_col;
+    v->state = &e->prec;
     v->err = &e->err;
 }
 

@@ -1,7 +1,7 @@
 """ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` / ``include/jaicov_transform.h`` /
 ``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_reliability_points.h`` /
 ``include/jaicov_datum.h`` / ``include/jaicov_intersect.h`` / ``include/jaicov_resect.h`` /
-``include/jaicov_relorient.h`` / ``include/jaicov_simil.h`` / ``include/jaicov_lens.h``
+``include/jaicov_relorient.h`` / ``include/jaicov_simil.h`` / ``include/jaicov_lens.h`` / ``include/jaicov_precision.h``
 (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
@@ -51,6 +51,10 @@ REL_EXPORTS = ["jaicov_rel_run", "jaicov_rel_get", "jaicov_rel_summary", "jaicov
 REL_POINT_EXPORTS = ["jaicov_rel_run_points", "jaicov_rel_get_points"]
 # include/jaicov_datum.h: the cofactor matrix re-expressed in another datum (S-transformation) on the device
 DATUM_EXPORTS = ["jaicov_datum_transform", "jaicov_datum_apply"]
+# include/jaicov_precision.h: confidence ellipsoids, sigmas of lengths and principal components read from the cofactor matrix
+PREC_EXPORTS = ["jaicov_prec_points", "jaicov_prec_stations", "jaicov_prec_lengths", "jaicov_prec_components"]
+PREC_PARTIAL, PREC_NEGATIVE, PREC_NOT_FINITE, PREC_DEGENERATE = 1, 2, 4, 8     # status bits of a point, station or pair
+PREC_POINT_COLUMNS, PREC_STATION_COLUMNS, PREC_LENGTH_COLUMNS = 22, 25, 5
 # jaicov_dlt_restriction (DirectLinearTransformation.RestrictionType, DT:51-58 order) and the per-image status values
 DLT_IDENTICAL_PRINCIPLE_DISTANCE, DLT_ROTATION_WITHOUT_SHEAR, DLT_FIXED_PRINCIPLE_DISTANCE_X, DLT_FIXED_PRINCIPLE_DISTANCE_Y, \
     DLT_FIXED_PRINCIPAL_POINT_X, DLT_FIXED_PRINCIPAL_POINT_Y = range(6)
@@ -180,6 +184,10 @@ def load_library():
     L.jaicov_rel_get_points.argtypes = [vp, _pd, C.c_int32]
     L.jaicov_datum_transform.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int32]
     L.jaicov_datum_apply.argtypes = [vp, _pd, _pd, C.c_int32]
+    L.jaicov_prec_points.argtypes = [vp, C.c_double, C.c_double, C.c_double, _pi, C.c_int32, _pd, _pi]
+    L.jaicov_prec_stations.argtypes = [vp, C.c_double, C.c_double, C.c_double, _pi, C.c_int32, _pd, _pi]
+    L.jaicov_prec_lengths.argtypes = [vp, C.c_double, _pi, C.c_int32, _pd, _pi]
+    L.jaicov_prec_components.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, _pd, _pd, _pd, _pd, _pi]
     L.jaicov_dlt_adjust.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pi, C.c_int32, C.c_int32, _pd, _pi, _pi, _pd]
     L.jaicov_isect_points.argtypes = [C.c_int32, _pi, _pi, _pd, _pd, C.c_int32, _pd, _pd, C.c_double, C.c_int32, C.c_double, C.c_int32,
                                       _pd, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
@@ -203,6 +211,14 @@ Reliability = namedtuple("Reliability", ["v", "qvv", "r", "t"])
 REL_POINT_COLUMNS = 14
 PointReliability = namedtuple("PointReliability", ["q", "T_prio", "T_post", "nabla_x", "nabla_y", "Mxx", "Mxy", "Myy", "mdb_major",
                                                    "mdb_minor", "delta_ext", "dX", "dY", "dZ"])
+
+
+# Engine.precision_points / precision_stations: one entry per item (include/jaicov_precision.h); axes[i, j] is the unit vector of
+# semi-axis j; sigma_angles is None for points
+PointPrecision = namedtuple("PointPrecision", ["sigma", "helmert", "semi_axes", "axes", "ellipse", "direction", "eigenvalues",
+                                               "sigma_angles", "status"])
+LengthPrecision = namedtuple("LengthPrecision", ["length", "sigma", "sigma_diff", "status"])
+PrincipalComponents = namedtuple("PrincipalComponents", ["values", "vectors", "trace", "residuals", "iterations", "converged"])
 
 
 def _p(a):
@@ -462,6 +478,54 @@ class Engine:
         self._chk(self.L.jaicov_datum_apply(self._h, _p(x), _p(out), x.size))
         return out
 
+    # precision (include/jaicov_precision.h) ---------------------------------------------------------------------------------------
+    def _precision_blocks(self, fn, columns, total, sigma2, k3, k2, items):
+        idx = None if items is None else np.ascontiguousarray(items, np.int32).ravel()
+        n = total if idx is None else idx.size
+        out = np.zeros((n, columns)); status = np.zeros(n, np.int32)
+        self._chk(fn(self._h, float(sigma2), float(k3), float(k2), None if idx is None else idx.ctypes.data_as(_pi), n, _p(out),
+                     status.ctypes.data_as(_pi)))
+        return PointPrecision(out[:, 0:3], out[:, 3], out[:, 4:7], out[:, 7:16].reshape(n, 3, 3), out[:, 16:18], out[:, 18], out[:, 19:22],
+                              out[:, 22:25] if columns > PREC_POINT_COLUMNS else None, status)
+
+    def precision_points(self, sigma2, k3=1.0, k2=1.0, points=None):
+        """Standard deviations, Helmert point error, confidence ellipsoid (semi-axes k3 sqrt(sigma2 lambda) with their unit vectors as
+        rows of `axes`), horizontal ellipse (k2) and raw eigenvalues of the 3 x 3 cofactor block of every object point (or of
+        `points`), read on the device from the cofactor matrix of the last inverting solve.  Returns a PointPrecision."""
+        return self._precision_blocks(self.L.jaicov_prec_points, PREC_POINT_COLUMNS, self.fp.n_points, sigma2, k3, k2, points)
+
+    def precision_stations(self, sigma2, k3=1.0, k2=1.0, images=None):
+        """precision_points for the projection centres X0, Y0, Z0 of every image (or of `images`), with the standard deviations of
+        omega, phi, kappa in `sigma_angles`.  Needs INVERT_FULL or INVERT_FULL_EXPANDED."""
+        return self._precision_blocks(self.L.jaicov_prec_stations, PREC_STATION_COLUMNS, self.fp.n_images, sigma2, k3, k2, images)
+
+    def precision_lengths(self, sigma2, pairs):
+        """Length L between the adjusted object points of every pair (A, B), its standard deviation from the 6 x 6 block with the
+        cross-covariances, and the standard deviations of the three coordinate differences.  Returns a LengthPrecision."""
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        out = np.zeros((pr.shape[0], PREC_LENGTH_COLUMNS)); status = np.zeros(pr.shape[0], np.int32)
+        self._chk(self.L.jaicov_prec_lengths(self._h, float(sigma2), pr.ctypes.data_as(_pi), pr.shape[0], _p(out), status.ctypes.data_as(_pi)))
+        return LengthPrecision(out[:, 0], out[:, 1], out[:, 2:5], status)
+
+    def point_column_range(self):
+        """(first column, number of columns) of the coordinates of the object points that images observe: they are numbered first, so
+        their free coordinates are one leading range of the cofactor matrix (points of scale bars only follow the exterior
+        orientations and are not part of it)."""
+        return point_column_range(self.fp)
+
+    def principal_components(self, k=3, first_col=None, n_cols=None, tol=0.0, max_iterations=200):
+        """The k <= 4 largest eigenpairs of the principal sub-block of the cofactor matrix over columns [first_col, first_col + n_cols)
+        (default: point_column_range()) by subspace iteration on the device.  Returns a PrincipalComponents; `converged` is False
+        when max_iterations products were not enough (the values are those of the last one)."""
+        if first_col is None or n_cols is None:
+            first_col, n_cols = self.point_column_range()
+        kk = max(int(k), 0)
+        values = np.zeros(kk); vectors = np.zeros((kk, max(int(n_cols), 0))); res = np.zeros(kk); tr = np.zeros(1)
+        it = C.c_int32(0)
+        self._chk(self.L.jaicov_prec_components(self._h, int(first_col), int(n_cols), int(k), float(tol), int(max_iterations), _p(values),
+                                                _p(vectors), _p(tr), _p(res), C.byref(it)))
+        return PrincipalComponents(values, vectors, float(tr[0]), res, abs(it.value), it.value > 0)
+
     def get_rows(self, ip_begin, ip_count):
         w = np.zeros((ip_count, 2)); A = np.zeros((ip_count, 2, KROW))
         self._chk(self.L.jaicov_neq_get_rows(self._h, ip_begin, ip_count, _p(w), _p(A)))
@@ -511,6 +575,17 @@ class Engine:
         res = EstimateResult()
         self._chk(self.L.jaicov_neq_estimate(self._h, C.byref(o), C.byref(res)))
         return self.get_parameters(), res
+
+
+def point_column_range(fp: FlatProblem):
+    """Engine.point_column_range for a problem (no device needed)."""
+    seen = np.zeros(fp.n_points, bool)
+    seen[np.asarray(fp.ip_point)] = True
+    cols = np.asarray(fp.point_col).reshape(-1, 3)[seen].ravel()
+    cols = np.sort(cols[cols >= 0])
+    if cols.size == 0 or cols[-1] - cols[0] + 1 != cols.size:
+        raise ValueError("the columns of the image-observed points are not one contiguous range")
+    return int(cols[0]), int(cols.size)
 
 
 def dense_spd_solve_packed(ap, b=None, invert=False):

@@ -155,6 +155,30 @@ PYBIND11_MODULE(_jaicov_host, m) {
              "(include/jaicov_reliability_points.h)")
         .def("transformDatum", &BundleAdjustment::transformDatum,
              "re-express the cofactor matrix in the datum of the points flagged now (include/jaicov_datum.h)")
+        .def("pointPrecision", [](BundleAdjustment &b, double sigma2, double k3, double k2, std::vector<int32_t> points) {
+            auto t = b.pointPrecision(sigma2, k3, k2, points);
+            return py::make_tuple(py::array_t<double>({t.status.size(), (size_t)t.columns}, t.table.data()),
+                                  py::array_t<int32_t>((py::ssize_t)t.status.size(), t.status.data()));
+        }, py::arg("sigma2"), py::arg("k3") = 1.0, py::arg("k2") = 1.0, py::arg("points") = std::vector<int32_t>(),
+             "(table (n, 22), status (n,)) of the object points (include/jaicov_precision.h); no points = all")
+        .def("stationPrecision", [](BundleAdjustment &b, double sigma2, double k3, double k2, std::vector<int32_t> images) {
+            auto t = b.stationPrecision(sigma2, k3, k2, images);
+            return py::make_tuple(py::array_t<double>({t.status.size(), (size_t)t.columns}, t.table.data()),
+                                  py::array_t<int32_t>((py::ssize_t)t.status.size(), t.status.data()));
+        }, py::arg("sigma2"), py::arg("k3") = 1.0, py::arg("k2") = 1.0, py::arg("images") = std::vector<int32_t>(),
+             "(table (n, 25), status (n,)) of the projection centres (include/jaicov_precision.h); no images = all")
+        .def("lengthPrecision", [](BundleAdjustment &b, double sigma2, std::vector<int32_t> pairs) {
+            auto t = b.lengthPrecision(sigma2, pairs);
+            return py::make_tuple(py::array_t<double>({t.status.size(), (size_t)t.columns}, t.table.data()),
+                                  py::array_t<int32_t>((py::ssize_t)t.status.size(), t.status.data()));
+        }, py::arg("sigma2"), py::arg("pairs"), "(table (n, 5), status (n,)) of the lengths between the point pairs (A, B), flattened")
+        .def("principalComponents", [](BundleAdjustment &b, int firstCol, int nCols, int k, double tol, int maxIterations) {
+            auto c = b.principalComponents(firstCol, nCols, k, tol, maxIterations);
+            return py::make_tuple(py::array_t<double>((py::ssize_t)c.values.size(), c.values.data()),
+                                  py::array_t<double>({c.values.size(), (size_t)std::max(nCols, 0)}, c.vectors.data()), c.trace,
+                                  py::array_t<double>((py::ssize_t)c.residuals.size(), c.residuals.data()), c.iterations, c.converged);
+        }, py::arg("firstCol"), py::arg("nCols"), py::arg("k"), py::arg("tol") = 0.0, py::arg("maxIterations") = 200,
+             "(values, vectors (k, nCols), trace, residuals, iterations, converged) of the sub-block's largest eigenpairs")
         .def("useCentroidedCoordinates", &BundleAdjustment::useCentroidedCoordinates)
         .def("centroidCoordinates", &BundleAdjustment::centroidCoordinates)
         .def("applyAposterioriVarianceOfUnitWeight", &BundleAdjustment::applyAposterioriVarianceOfUnitWeight)

@@ -506,6 +506,64 @@ void BundleAdjustment::transformDatum() {
     qxxOnDevice_ = true;      // a copy fetched before is stale: fetched again on demand
 }
 
+// include/jaicov_precision.h on the engine of the last estimateModel
+static void requireCofactorOnEngine(const jaicov_engine *e, bool has) {
+    if (!e || !has) throw std::runtime_error("no cofactor matrix: run estimateModel with MatrixInversion FULL or REDUCED first");
+}
+
+BundleAdjustment::PrecisionTable BundleAdjustment::pointPrecision(double sigma2, double k3, double k2, const std::vector<int32_t> &points) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    PrecisionTable t;
+    t.columns = JAICOV_PREC_POINT_COLUMNS;
+    const size_t n = points.empty() ? objectCoordinates_.size() : points.size();
+    t.table.resize(n * t.columns);
+    t.status.resize(n);
+    const int rc = jaicov_prec_points(engine_, sigma2, k3, k2, points.empty() ? nullptr : points.data(), (int32_t)n, t.table.data(), t.status.data());
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_prec_points: ") + jaicov_neq_last_error(engine_));
+    return t;
+}
+
+BundleAdjustment::PrecisionTable BundleAdjustment::stationPrecision(double sigma2, double k3, double k2, const std::vector<int32_t> &images) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    PrecisionTable t;
+    t.columns = JAICOV_PREC_STATION_COLUMNS;
+    const size_t n = images.empty() ? flat.eo_col.size() / 6 : images.size();
+    t.table.resize(n * t.columns);
+    t.status.resize(n);
+    const int rc = jaicov_prec_stations(engine_, sigma2, k3, k2, images.empty() ? nullptr : images.data(), (int32_t)n, t.table.data(), t.status.data());
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_prec_stations: ") + jaicov_neq_last_error(engine_));
+    return t;
+}
+
+BundleAdjustment::PrecisionTable BundleAdjustment::lengthPrecision(double sigma2, const std::vector<int32_t> &pairs) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    if (pairs.size() % 2) throw std::runtime_error("lengthPrecision: pairs must hold two point indices per length");
+    PrecisionTable t;
+    t.columns = JAICOV_PREC_LENGTH_COLUMNS;
+    const size_t n = pairs.size() / 2;
+    t.table.resize(n * t.columns);
+    t.status.resize(n);
+    int32_t none = 0;
+    const int rc = jaicov_prec_lengths(engine_, sigma2, n ? pairs.data() : &none, (int32_t)n, t.table.data(), t.status.data());
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_prec_lengths: ") + jaicov_neq_last_error(engine_));
+    return t;
+}
+
+BundleAdjustment::PrincipalComponents BundleAdjustment::principalComponents(int firstCol, int nCols, int k, double tol, int maxIterations) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    PrincipalComponents c;
+    const size_t kk = (size_t)std::max(k, 0), nn = (size_t)std::max(nCols, 0);
+    c.values.resize(kk); c.residuals.resize(kk); c.vectors.resize(kk * nn);
+    double none = 0.0;
+    int32_t it = 0;
+    const int rc = jaicov_prec_components(engine_, firstCol, nCols, k, tol, maxIterations, kk ? c.values.data() : &none,
+                                          c.vectors.empty() ? &none : c.vectors.data(), &c.trace, kk ? c.residuals.data() : &none, &it);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_prec_components: ") + jaicov_neq_last_error(engine_));
+    c.iterations = std::abs(it);
+    c.converged = it > 0;
+    return c;
+}
+
 // CTEO:49-121: rows, coordinates and sigma2 J Qxx J' on the device (jaicov_xform_run), the results copied back
 void CoordinateTransformationExteriorOrientation::transform(const std::vector<ObjectCoordinate *> &objectCoordinatesToTransform,
                                                             const std::vector<std::pair<Image *, std::vector<Image *>>> &imagesToAlign,

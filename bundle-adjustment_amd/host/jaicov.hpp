@@ -37,6 +37,7 @@
 #include "../../include/jaicov_reliability.h"
 #include "../../include/jaicov_reliability_points.h"
 #include "../../include/jaicov_datum.h"
+#include "../../include/jaicov_precision.h"
 
 namespace jaicov::host {
 
@@ -537,6 +538,27 @@ public:
     // set NOW (Baarda's S-transformation, include/jaicov_datum.h): re-flag the points, then call.  Needs a free network (d > 0)
     // and MatrixInversion FULL or REDUCED; cofactorSub, getCofactorMatrix and the writers see the new datum afterwards.
     void transformDatum();
+    // Precision figures read on the device from the cofactor matrix of the last estimateModel (include/jaicov_precision.h; after
+    // transformDatum they speak of the new datum).  table: one row of `columns` entries per item, in the header's order; status: its
+    // JAICOV_PREC_* bits.  An empty index list means every object point / every image.  k3, k2: the caller's expansion factors of the
+    // ellipsoid and of the horizontal ellipse.  Indices are the engine's: ObjectCoordinate::index, and the images in the order of flat.eo_col.
+    struct PrecisionTable {
+        int columns = 0;
+        std::vector<double> table;
+        std::vector<int32_t> status;
+    };
+    PrecisionTable pointPrecision(double sigma2, double k3 = 1.0, double k2 = 1.0, const std::vector<int32_t> &points = {}) const;
+    PrecisionTable stationPrecision(double sigma2, double k3 = 1.0, double k2 = 1.0, const std::vector<int32_t> &images = {}) const;   // needs MatrixInversion.FULL
+    // pairs: (A, B) point indices, flattened; rows of L, sigma_L, sigma of the three coordinate differences
+    PrecisionTable lengthPrecision(double sigma2, const std::vector<int32_t> &pairs) const;
+    // The k <= 4 largest eigenpairs of the principal sub-block over columns [firstCol, firstCol + nCols) by subspace iteration
+    struct PrincipalComponents {
+        std::vector<double> values, vectors, residuals;      // vectors: k rows of nCols entries
+        double trace = 0.0;
+        int iterations = 0;
+        bool converged = false;
+    };
+    PrincipalComponents principalComponents(int firstCol, int nCols, int k, double tol = 0.0, int maxIterations = 200) const;
     const std::string &lastError() const { return lastError_; }
     jaicov_engine *nativeEngine() const { return engine_; }     // the engine of the last estimateModel (null before)
 
