@@ -1279,6 +1279,12 @@ hipError_t DenseSolver::premultiply() {
     return hipGetLastError();
 }
 
+// Which sums a solution vector is made of.  backsolve_chain_kernel<1 / 2 / 4 / 8> form every right-hand side in the same order
+// (one accumulator pair per vector, the same reduction), so a vector has the same bits under every NR and beside any other
+// vectors -- held at nrhs = 1 .. 8 by test_dense_spd_solve_at_every_count_of_right_hand_sides.  ON PURPOSE not so for ONE
+// right-hand side from chain8_min_blocks() block columns on (default 24): the polling-wave form multiplies by pre-multiplied
+// blocks P_m = L W (premultiply) instead of L and then W, other products and another summation order.  Its vector agrees with the
+// chain kernel's to rounding (the same test: 1e-13 of max|x|), not bit for bit.
 hipError_t DenseSolver::backsolve_aug(double *X, long xs, int nrhs) {
     if (!aug || nrhs < 1 || nrhs > DENSE_MAX_RHS) return hipErrorInvalidValue;
     const int nb = nfact / 128;

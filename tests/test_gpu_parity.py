@@ -72,6 +72,59 @@ def test_dense_spd_solve_one_right_hand_side(n, monkeypatch):
     np.testing.assert_allclose(x, np.linalg.solve(S, b.T).T, rtol=1e-10, atol=1e-12)
 
 
+@pytest.mark.parametrize("n", [100, 300, 1100])
+def test_dense_spd_solve_at_every_count_of_right_hand_sides(n, monkeypatch):
+    """nrhs = 1 .. 8 through the factorisation and the backward chain: backsolve_chain_kernel<1> at 1, <2> at 2, <4> at 3 and 4, <8> at
+    5 .. 8 -- every instance full and ragged (nrhs < NR) -- on one, three and nine block columns with a ragged last block.  (The
+    engine reaches these with d + 1 right-hand sides, d the datum defect; the rest of this file runs 1, 3 and 7.)  The matrices are
+    those of test_dense_spd_solve_and_inverse, the right-hand sides eight distinct random vectors, the second of them all zeros.
+    Every solution vector is held to the long-double-refined solution, and is the SAME BITS as the vector solved alone with nrhs = 1:
+    a right-hand side is one more row of the factorisation's update and one more column of the chain's sums, each formed in the
+    same order whatever rides beside it, so nothing may leak from one vector, or from the padding of a ragged nrhs, into another.
+    That holds among the backsolve_chain_kernel instances.  A single right-hand side from 24 block columns on takes the polling-wave
+    form, whose sums differ on purpose (see below and the comment at DenseSolver::backsolve_aug): 1e-13 relative there, no bit-equality.
+    nrhs = 0 with `invert` is accepted and nrhs = 9 refused with JAICOV_ERR_BAD_ARGUMENT (include/jaicov_dense.h): an argument check
+    in front of the device."""
+    from test_gpu_refinement import exact_solution
+    monkeypatch.delenv("JAICOV_CHAIN8_MIN_NB", raising=False)          # nrhs = 1 by backsolve_chain_kernel<1>, not the polling-wave form
+    rng = np.random.default_rng(n)
+    G = rng.normal(size=(n, n + 20))
+    S = G @ G.T / n + np.eye(n)
+    ap = full_to_packed(S)
+    B = rng.normal(size=(8, n))
+    B[1] = 0.0
+    ref = exact_solution(S, B.T).T
+    assert not ref[1].any()
+    alone = np.stack([engine.dense_spd_solve_packed(ap, B[q:q + 1])[0][0] for q in range(8)])
+    worst = 0.0
+    for nrhs in range(1, 9):
+        x, _, _ = engine.dense_spd_solve_packed(ap, B[:nrhs])
+        assert x.shape == (nrhs, n)
+        np.testing.assert_allclose(x, ref[:nrhs], rtol=1e-10, atol=1e-12)
+        worst = max(worst, float(np.abs(x - ref[:nrhs]).max() / np.abs(ref).max()))
+        for q in range(nrhs):
+            assert x[q].tobytes() == alone[q].tobytes(), (nrhs, q, float(np.abs(x[q] - alone[q]).max()))
+    print(f"n = {n}: nrhs 1 .. 8 worst {worst:.2e} of max|x| from the exact solution; every vector bit-equal to its solve alone")
+    # The one exception, on purpose (dense.hip, DenseSolver::backsolve_aug): ONE right-hand side in the polling-wave form (by default
+    # from 24 block columns on, here from one) multiplies by pre-multiplied blocks, other sums than the chain kernel's.  Bit-equality
+    # is replaced by 1e-13 of max|x| against the chain kernel's vector, and the exact solution holds it as it holds the others.
+    monkeypatch.setenv("JAICOV_CHAIN8_MIN_NB", "1")
+    for q in (0, 1, 5):
+        x8 = engine.dense_spd_solve_packed(ap, B[q:q + 1])[0][0]
+        np.testing.assert_allclose(x8, ref[q], rtol=1e-10, atol=1e-12)
+        dev = float(np.abs(x8 - alone[q]).max() / np.abs(ref).max())
+        print(f"n = {n}: vector {q} alone in the polling-wave form: {dev:.2e} of max|x| from the chain kernel's, bit-equal: {x8.tobytes() == alone[q].tobytes()}")
+        assert dev <= 1e-13
+    monkeypatch.delenv("JAICOV_CHAIN8_MIN_NB")
+    if n == 100:
+        x, inv, _ = engine.dense_spd_solve_packed(ap, None, invert=True)
+        assert x is None
+        np.testing.assert_allclose(packed_to_full(inv, n), np.linalg.inv(S), rtol=1e-9, atol=1e-12)
+        with pytest.raises(engine.EngineError) as ei:
+            engine.dense_spd_solve_packed(ap, rng.normal(size=(9, n)))
+        assert ei.value.code == -1
+
+
 @pytest.mark.parametrize("n", [128, 300, 1000, 2100])
 def test_dataflow_factorisation_on_small_orders(n, monkeypatch):
     """The dataflow Cholesky (csrc/cholflow.hip) is the default from 24 block columns on; forced here on 1, 3, 8 and 17
