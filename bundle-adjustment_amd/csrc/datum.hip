@@ -18,6 +18,7 @@
 
 #include "../../include/jaicov_datum.h"
 #include "datum.h"
+#include "qview.h"
 #include "status.h"
 #include "symtile.h"
 
@@ -130,8 +131,7 @@ using namespace jaicov;
 
 extern "C" int jaicov_datum_transform(jaicov_engine *e, const uint8_t *point_datum, int32_t n_points) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    DatumView v;
-    engine_datum_view(e, &v);
+    const QView v = q_view(e);
     if (v.d == 0) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "datum transformation: the network has no datum defect (d = 0)");
     if (v.sharded) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "datum transformation on a sharded engine");
     if (!v.have_q) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
@@ -163,15 +163,14 @@ extern "C" int jaicov_datum_transform(jaicov_engine *e, const uint8_t *point_dat
             Z[(size_t)i * d + a] = s;
         }
     // work buffers, kept with the engine
-    if (!*v.state) v.state->reset(new DatumState());
-    DatumState *st = v.state->get();
+    if (!v.slot->datum) v.slot->datum.reset(new DatumState());
+    DatumState *st = v.slot->datum.get();
     HIPE(*v.err, st->work.reserve((size_t)d * np * 4 + (size_t)nbk * nbk * 128 * d));
     double *dB = st->work.get(), *dY = dB + (size_t)d * np, *dZY = dY + (size_t)d * np, *dP = dZY + (size_t)2 * d * np;
     HIPE(*v.err, hipMemcpyAsync(dB, B.data(), (size_t)d * np * sizeof(double), hipMemcpyHostToDevice, v.stream));
     HIPE(*v.err, launch_y_d(d, v.stream, v.Q, v.ld, n, dB, np, nbk, dP, dY));
     std::vector<double> Y((size_t)np * d);
-    HIPE(*v.err, hipMemcpyAsync(Y.data(), dY, Y.size() * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    HIPE(*v.err, hipStreamSynchronize(v.stream));
+    TRY(q_download(v, {{Y.data(), dY, Y.size() * sizeof(double)}}));
     // W = B' Y (symmetric: its two triangles averaged), Y~ = Y - Z W / 2
     double W[49];
     for (int a = 0; a < d; a++)
@@ -206,9 +205,8 @@ extern "C" int jaicov_datum_transform(jaicov_engine *e, const uint8_t *point_dat
 
 extern "C" int jaicov_datum_apply(jaicov_engine *e, const double *x, double *out, int32_t n) {
     if (!e || !x || !out) return JAICOV_ERR_BAD_ARGUMENT;
-    DatumView v;
-    engine_datum_view(e, &v);
-    const DatumState *st = v.state->get();
+    const QView v = q_view(e);
+    const DatumState *st = v.slot->datum.get();
     if (!st || !st->valid) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no datum transformation since the last inverting solve");
     if (n != st->order) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "n must be the order of the transformed cofactor matrix");
     const int d = st->d;

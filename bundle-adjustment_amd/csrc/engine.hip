@@ -22,6 +22,7 @@
 #include "devbuf.h"
 #include "gemm_f64.h"
 #include "precision.h"
+#include "qview.h"
 #include "reliability.h"
 #include "status.h"
 #include "transform.h"
@@ -238,8 +239,6 @@ struct jaicov_engine {
     DevBuf<double> expF;             // ... a shard's caller sums them over the ranks: [F (6 images padded x reduced order padded) | Linv (36 per image)]
     size_t expF_len = 0;             // the length in use (the allocation only grows)
     bool exp_ready = false;          // d_expF belongs to the system accumulated last and has been handed out (jaicov_neq_expansion_buffer)
-    int q_order = 0;                 // order of the cofactor matrix on the device (U, or e0 for the reduced one)
-    bool q_reduced = false;
     std::vector<int> h_blk_images;   // image of every block handled by this engine
     std::vector<int32_t> h_caller_block; // internal image block -> the caller's block index (-1: an ordinary image served as a block); empty: identity
     std::vector<int32_t> h_perm_local;   // per image point of a dense block: engine position -> caller's position inside the block (empty: identity)
@@ -263,7 +262,7 @@ struct jaicov_engine {
     int32_t *d_idx = nullptr;
     DenseSolver solver;
     enum { ST_NEW, ST_PARAMS, ST_ACCUMULATED, ST_BUILT, ST_SOLVED } state = ST_NEW;
-    bool have_Q = false, rows_valid = false, reduced = false;
+    bool rows_valid = false, reduced = false;
     bool deterministic = true;   // engine option `deterministic` (default on): fixed summation order in the assembly of the image groups
     std::atomic<int> cancel{0};  // BundleAdjustment.interrupt() (BA:1455): polled by estimate() where the reference polls (BA:240, 320)
     bool sim_built = false;      // the system at hand was built with simulation != 0: the right-hand side is zero for ALL unknowns (BA:830-831)
@@ -276,14 +275,22 @@ struct jaicov_engine {
     bool pp_plain_ok = false;   // the point x point gather may store its strips (see PPGather::plain)
     DevEvent ev_first, ev_all;   // solve(): first panel's columns / whole matrix copied into the solver
     DevEvent ev_r0, ev_r1;       // solve(): device part of a refinement step
-    std::unique_ptr<jaicov::XformState> xform;         // result of jaicov_xform_run (transform.hip), kept until the next run / release
-    std::unique_ptr<jaicov::RelState> rel;             // result of jaicov_rel_run (reliability.hip), kept until the next run / release
     const double *d_ll_diag = nullptr;                 // [2 n_ip + n_dg_rows]: diag(D) of every image coordinate (engine order) and direct row
     double sigma2_acc = 0.0;                           // sigma0^2 of the last accumulate
-    double q_sigma2 = 0.0, q_lambda = 0.0;             // sigma0^2 and damping of the build whose system the cofactor matrix inverts
-    std::vector<double> q_vals;                        // slot values of that build: the datum rows of jaicov_datum_transform (datum.hip)
-    std::unique_ptr<jaicov::DatumState> datum;         // S of the last jaicov_datum_transform and its work buffers
-    std::unique_ptr<jaicov::PrecisionState> prec;      // work buffers of the precision calls (precision.hip)
+    // What an inverting solve leaves: Solve::finish records all of it at once and withdraws the S of an earlier datum transformation
+    // with it; accumulate withdraws `valid` alone (the matrix's buffer is the next factorisation's to use), the rest waits for the
+    // next inverting solve to overwrite it.
+    struct Cofactor {
+        bool valid = false;
+        int order = 0;                   // U, or e0 for the inverse of the EO-reduced system
+        bool reduced = false;            // ... which lies in solverS.Q, every other one in solver.Q
+        double sigma2 = 0.0, lambda = 0.0;   // sigma0^2 and damping of the build whose system the matrix inverts
+        std::vector<double> vals;        // slot values of that build: the datum rows of jaicov_datum_transform (datum.hip)
+    } q;
+    DenseSolver &q_solver() { return q.reduced ? solverS : solver; }   // the solver that holds the matrix
+    // What the consumers of the matrix keep (qview.h).  A result of jaicov_xform_run or jaicov_rel_run outlives a later inverting
+    // solve; only the datum state is invalidated by one.  Their buffers free on the stream: they stay declared after stream_lease.
+    jaicov::QSlots slot;
 };
 
 template <typename T, typename P>      // P: T or const T
@@ -765,7 +772,7 @@ extern "C" int jaicov_neq_get_parameters(jaicov_engine *e, double *slots, size_t
     return JAICOV_OK;
 }
 
-static int ensure_rows(jaicov_engine *e) {
+int jaicov::engine_ensure_rows(jaicov_engine *e) {
     if (e->rows_valid) return JAICOV_OK;
     HIPE(e->err, launch_rows(e->stream, e->p, e->d_vals, e->ip0, e->ip_count, e->d_rowsA, e->d_rowsW));
     e->rows_valid = true;
@@ -781,7 +788,7 @@ extern "C" int jaicov_neq_accumulate(jaicov_engine *e, double sigma2) {
     e->sigma2_acc = sigma2;
     const size_t sq = (size_t)e->Upad * e->Upad;
     HIPE(e->err, hipEventRecord(e->ev[0].get(), e->stream));
-    TRY(ensure_rows(e));
+    TRY(engine_ensure_rows(e));
     HIPE(e->err, hipEventRecord(e->ev[1].get(), e->stream));
     e->schur_active = e->schur_ok && e->inverse_mode_next != JAICOV_INVERT_FULL;
     // The point x point gather owns every entry of rows cmin..cmax from column cmin on: when it runs before everything
@@ -832,7 +839,7 @@ extern "C" int jaicov_neq_accumulate(jaicov_engine *e, double sigma2) {
     HIPE(e->err, hipEventRecord(e->ev[2].get(), e->stream));
     e->exp_ready = false;            // the expansion buffer of an earlier pass is stale now
     e->state = jaicov_engine::ST_ACCUMULATED;
-    e->have_Q = false;
+    e->q.valid = false;
     return JAICOV_OK;
 }
 
@@ -953,8 +960,8 @@ extern "C" int jaicov_neq_prepare_inverse(jaicov_engine *e, int inverse_follows)
 }
 
 extern "C" int jaicov_neq_cofactor_order(const jaicov_engine *e) {
-    if (!e || !e->have_Q) return -1;
-    return e->q_order;
+    if (!e || !e->q.valid) return -1;
+    return e->q.order;
 }
 
 extern "C" int jaicov_neq_reduced_order(const jaicov_engine *e) {
@@ -1395,13 +1402,13 @@ struct Solve {
         HIPE(e->err, hipEventRecord(e->ev[7].get(), e->stream));
         HIPE(e->err, hipStreamSynchronize(e->stream));
         if (invert) {
-            e->have_Q = true;
-            e->q_sigma2 = e->sigma2_acc;
-            e->q_lambda = e->lambda_used;
-            e->q_vals = e->h_vals;
-            jaicov::datum_state_invalidate(e->datum.get());
-            e->q_reduced = schur && !expand;
-            e->q_order = expand ? e->U : U;
+            e->q.valid = true;
+            e->q.sigma2 = e->sigma2_acc;
+            e->q.lambda = e->lambda_used;
+            e->q.vals = e->h_vals;
+            jaicov::datum_state_invalidate(e->slot.datum.get());
+            e->q.reduced = schur && !expand;
+            e->q.order = expand ? e->U : U;
         }
         slv.prof_collect();
         if (schur) {
@@ -1448,7 +1455,7 @@ extern "C" int jaicov_neq_expansion_buffer(jaicov_engine *e, void **device_ptr, 
     HIPE(e->err, e->expF.reserve(len));
     e->expF_len = len;
     double *d_expF = e->expF.get();
-    TRY(ensure_rows(e));
+    TRY(engine_ensure_rows(e));
     HIPE(e->err, hipMemsetAsync(d_expF, 0, I6p * Up * sizeof(double), e->stream));       // foreign images' bands: zero
     HIPE(e->err, launch_schur_expand_f(e->stream, e->p, e->d_blk_list, e->n_blk_list, e->d_rowsA, e->sb.U, e->sb.Linv, e->sb.G, d_expF, (long)Up));
     // L_E^-1: written for this engine's images only (blk_elim_kernel), zero elsewhere since create
@@ -1472,7 +1479,7 @@ extern "C" int jaicov_neq_omega(jaicov_engine *e, double sigma2, const double *d
     if (!e || !dx || !omega) return JAICOV_ERR_BAD_ARGUMENT;
     if (e->state == jaicov_engine::ST_NEW) FAIL(e->err, JAICOV_ERR_BAD_STATE, "set_parameters first");
     HIPE(e->err, hipSetDevice(e->device));
-    TRY(ensure_rows(e));
+    TRY(engine_ensure_rows(e));
     hipEvent_t t0 = e->ev[8].get(), t1 = e->ev[9].get();
     HIPE(e->err, hipEventRecord(t0, e->stream));
     HIPE(e->err, hipMemcpyAsync(e->d_dx, dx, (size_t)e->U * sizeof(double), hipMemcpyHostToDevice, e->stream));
@@ -1537,11 +1544,11 @@ extern "C" int jaicov_neq_get_normal(jaicov_engine *e, double *N_packed, size_t 
 
 extern "C" int jaicov_neq_get_cofactor(jaicov_engine *e, double *Q_packed, size_t len) {
     if (!e || !Q_packed) return JAICOV_ERR_BAD_ARGUMENT;
-    if (!e->have_Q) FAIL(e->err, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first (MatrixInversion.NONE, BA:1177)");
-    const int U = e->q_order;
+    if (!e->q.valid) FAIL(e->err, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first (MatrixInversion.NONE, BA:1177)");
+    const int U = e->q.order;
     if (len != (size_t)U * (U + 1) / 2) FAIL(e->err, JAICOV_ERR_BAD_ARGUMENT, "cofactor buffer length must be order(order+1)/2 with order = jaicov_neq_cofactor_order()");
     HIPE(e->err, hipSetDevice(e->device));
-    const DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
+    const DenseSolver &qs = e->q_solver();
     DevBuf<double> ap;
     HIPE(e->err, ap.reserve(std::max<size_t>(len, 1)));
     hipLaunchKernelGGL(pack_kernel, dim3((U + 255) / 256, std::max(U, 1)), dim3(256), 0, e->stream, qs.Q, qs.ld, U, ap.get());
@@ -1550,94 +1557,48 @@ extern "C" int jaicov_neq_get_cofactor(jaicov_engine *e, double *Q_packed, size_
     return JAICOV_OK;
 }
 
-// transform.hip reads Qxx, the slot vector and the structure through this view (include/jaicov_transform.h)
-void jaicov::engine_xform_view(jaicov_engine *e, XformView *v) {
-    const DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
+// every consumer of the cofactor matrix sees the engine through this view (qview.h)
+void jaicov::engine_q_view(jaicov_engine *e, QView *v) {
+    DenseSolver &qs = e->q_solver();
     v->device = e->device;
     v->stream = e->stream;
-    v->full_q = e->have_Q && !e->q_reduced && e->q_order == e->U;
     v->Q = qs.Q;
     v->ld = qs.ld;
+    v->order = e->q.order;
     v->U = e->U;
-    v->d_vals = e->d_vals;
-    v->p = &e->p;
-    v->slot_col = &e->h_slot_col;
-    v->state = &e->xform;
-    v->err = &e->err;
-}
-
-// reliability.hip reads Qxx, the rows and the weights through this view (include/jaicov_reliability.h)
-int jaicov::engine_rel_view(jaicov_engine *e, RelView *v, int rows) {
-    const DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
-    v->device = e->device;
-    v->stream = e->stream;
-    v->full_q = e->have_Q && !e->q_reduced && e->q_order == e->U;
+    v->d = e->d;
+    v->n_points = e->n_points;
+    v->have_q = e->q.valid;
+    v->reduced = e->q.reduced;
+    v->full_q = e->q.valid && !e->q.reduced && e->q.order == e->U;
     v->sharded = !e->all_images || !e->opts.apply_shared || e->ip0 != 0 || e->ip_count != e->p.n_ip;
-    v->Q = qs.Q;
-    v->ld = qs.ld;
-    v->U = e->U;
-    v->sigma2 = e->q_sigma2;
-    v->lambda = e->q_lambda;
+    v->sigma2 = e->q.sigma2;
+    v->lambda = e->q.lambda;
     v->p = &e->p;
+    v->d_vals = e->d_vals;
     v->rowsA = e->d_rowsA;
     v->rowsW = e->d_rowsW;
-    v->d_vals = e->d_vals;
     v->ll_diag = e->d_ll_diag;
+    v->slot_col = &e->h_slot_col;
     v->ip_old2new = &e->ip_old2new;
     v->blk_ip_begin = &e->h_blk_ip_begin;
     v->blk_w_off = &e->h_blk_w_off;
-    v->state = &e->rel;
-    v->err = &e->err;
-    return rows ? ensure_rows(e) : JAICOV_OK;
-}
-
-// datum.hip transforms the cofactor matrix in place through this view (include/jaicov_datum.h)
-void jaicov::engine_datum_view(jaicov_engine *e, DatumView *v) {
-    DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
-    v->device = e->device;
-    v->stream = e->stream;
-    v->have_q = e->have_Q;
-    v->sharded = !e->all_images || !e->opts.apply_shared || e->ip0 != 0 || e->ip_count != e->p.n_ip;
-    v->Q = qs.Q;
-    v->ld = qs.ld;
-    v->order = e->q_order;
-    v->d = e->d;
-    v->n_points = e->n_points;
-    v->state = &e->datum;
-    v->err = &e->err;
-}
-
-// precision.hip reads the cofactor matrix, the slot vector and the slot table through this view (include/jaicov_precision.h)
-void jaicov::engine_prec_view(jaicov_engine *e, PrecView *v) {
-    const DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
-    v->device = e->device;
-    v->stream = e->stream;
-    v->have_q = e->have_Q;
-    v->reduced = e->q_reduced;
-    v->sharded = !e->all_images || !e->opts.apply_shared || e->ip0 != 0 || e->ip_count != e->p.n_ip;
-    v->Q = qs.Q;
-    v->ld = qs.ld;
-    v->order = e->q_order;
-    v->d = e->d;
-    v->d_vals = e->d_vals;
-    v->p = &e->p;
-    v->slot_col = &e->h_slot_col;
-    v->state = &e->prec;
+    v->slot = &e->slot;
     v->err = &e->err;
 }
 
 int jaicov::engine_datum_rows(jaicov_engine *e, const uint8_t *mask, std::vector<double> &B, int stride) {
-    if (e->q_vals.size() != (size_t)e->n_slots) FAIL(e->err, JAICOV_ERR_BAD_STATE, "no inverting solve has recorded its parameter values");
+    if (e->q.vals.size() != (size_t)e->n_slots) FAIL(e->err, JAICOV_ERR_BAD_STATE, "no inverting solve has recorded its parameter values");
     B.assign((size_t)e->d * stride, 0.0);
-    return datum_rows(e, mask, e->q_vals.data(), B, stride);
+    return datum_rows(e, mask, e->q.vals.data(), B, stride);
 }
 
 static int cofactor_sub_impl(jaicov_engine *e, const int32_t *idx, int32_t k, double scale, double *out) {
     if (!e || !idx || !out || k <= 0) return JAICOV_ERR_BAD_ARGUMENT;
-    if (!e->have_Q) FAIL(e->err, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
+    if (!e->q.valid) FAIL(e->err, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
     for (int i = 0; i < k; i++)
-        if (idx[i] < 0 || idx[i] >= e->q_order) return JAICOV_ERR_BAD_ARGUMENT;
-    const DenseSolver &qs = e->q_reduced ? e->solverS : e->solver;
+        if (idx[i] < 0 || idx[i] >= e->q.order) return JAICOV_ERR_BAD_ARGUMENT;
+    const DenseSolver &qs = e->q_solver();
     HIPE(e->err, hipSetDevice(e->device));
     DevBuf<int32_t> d_idx;
     DevBuf<double> d_out;
@@ -1662,7 +1623,7 @@ extern "C" int jaicov_neq_get_rows(jaicov_engine *e, int32_t ip_begin, int32_t i
     if (!e || !w || !A || ip_begin < e->ip0 || ip_count < 0 || ip_begin + ip_count > e->ip0 + e->ip_count) return JAICOV_ERR_BAD_ARGUMENT;
     if (e->state == jaicov_engine::ST_NEW) FAIL(e->err, JAICOV_ERR_BAD_STATE, "set_parameters first");
     HIPE(e->err, hipSetDevice(e->device));
-    TRY(ensure_rows(e));
+    TRY(engine_ensure_rows(e));
     const size_t S = (size_t)e->p.n_ip;
     std::vector<double> hA((size_t)2 * KROW * S), hW(2 * S);
     HIPE(e->err, hipMemcpyAsync(hA.data(), e->d_rowsA, hA.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));

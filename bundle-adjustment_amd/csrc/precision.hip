@@ -18,6 +18,7 @@
 
 #include "../../include/jaicov_precision.h"
 #include "precision.h"
+#include "qview.h"
 #include "status.h"
 #include "symtile.h"
 
@@ -361,23 +362,22 @@ static inline uint64_t prec_splitmix(uint64_t c) {
 }
 
 // the refusals common to all calls, in the header's order (the arguments follow in the callers)
-static int prec_common(const PrecView &v) {
+static int prec_common(const QView &v) {
     if (v.sharded) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "precision figures on a sharded engine");
     if (!v.have_q) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
     return JAICOV_OK;
 }
 
-static PrecisionState *prec_state(const PrecView &v) {
-    if (!*v.state) v.state->reset(new PrecisionState());
-    return v.state->get();
+static PrecisionState *prec_state(const QView &v) {
+    if (!v.slot->prec) v.slot->prec.reset(new PrecisionState());
+    return v.slot->prec.get();
 }
 
 // points (station == false) or projection centres: the column table, the launch, the download
 static int prec_blocks(jaicov_engine *e, bool station, double sigma2, double k3, double k2, const int32_t *items, int32_t n, double *out,
                        int32_t *status) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    PrecView v;
-    engine_prec_view(e, &v);
+    const QView v = q_view(e);
     TRY(prec_common(v));
     const DevProblem &p = *v.p;
     if (station && v.reduced) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "station precision needs the exterior orientations' columns: invert FULL or FULL_EXPANDED");
@@ -407,10 +407,7 @@ static int prec_blocks(jaicov_engine *e, bool station, double sigma2, double k3,
     hipLaunchKernelGGL(prec_block_kernel, dim3((n + 255) / 256), dim3(256), 0, v.stream, v.Q, v.ld, d_tab, n, sigma2, k3, k2, ncol,
                        st->out.get(), d_status);
     HIPE(*v.err, hipGetLastError());
-    HIPE(*v.err, hipMemcpyAsync(out, st->out.get(), (size_t)ncol * n * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    HIPE(*v.err, hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-    HIPE(*v.err, hipStreamSynchronize(v.stream));
-    return JAICOV_OK;
+    return q_download(v, {{out, st->out.get(), (size_t)ncol * n * sizeof(double)}, {status, d_status, (size_t)n * sizeof(int32_t)}});
 }
 
 }  // namespace jaicov
@@ -429,8 +426,7 @@ extern "C" int jaicov_prec_stations(jaicov_engine *e, double sigma2, double k3, 
 
 extern "C" int jaicov_prec_lengths(jaicov_engine *e, double sigma2, const int32_t *pairs, int32_t n, double *out, int32_t *status) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    PrecView v;
-    engine_prec_view(e, &v);
+    const QView v = q_view(e);
     TRY(prec_common(v));
     const DevProblem &p = *v.p;
     if (!pairs || !out || !status || n < 0) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "length precision: NULL argument or a negative count");
@@ -458,17 +454,14 @@ extern "C" int jaicov_prec_lengths(jaicov_engine *e, double sigma2, const int32_
     hipLaunchKernelGGL(prec_length_kernel, dim3((n + 255) / 256), dim3(256), 0, v.stream, v.Q, v.ld, v.d_vals, d_tab, n, sigma2, st->out.get(),
                        d_status);
     HIPE(*v.err, hipGetLastError());
-    HIPE(*v.err, hipMemcpyAsync(out, st->out.get(), (size_t)JAICOV_PREC_LENGTH_COLUMNS * n * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    HIPE(*v.err, hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-    HIPE(*v.err, hipStreamSynchronize(v.stream));
-    return JAICOV_OK;
+    return q_download(v, {{out, st->out.get(), (size_t)JAICOV_PREC_LENGTH_COLUMNS * n * sizeof(double)},
+                          {status, d_status, (size_t)n * sizeof(int32_t)}});
 }
 
 extern "C" int jaicov_prec_components(jaicov_engine *e, int32_t first_col, int32_t n_cols, int32_t k, double tol, int32_t max_iterations,
                                       double *values, double *vectors, double *trace, double *residuals, int32_t *iterations) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    PrecView v;
-    engine_prec_view(e, &v);
+    const QView v = q_view(e);
     TRY(prec_common(v));
     if (!values || !vectors || !trace || !residuals || !iterations) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "principal components: NULL output");
     if (k < 1 || k > 4) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "principal components: k must be 1 .. 4");

@@ -1,0 +1,99 @@
+// The one interface between engine.hip (owner of jaicov_engine) and whatever reads the cofactor matrix an inverting solve leaves on
+// the device: transform.hip, reliability.hip, datum.hip (the one writer) and precision.hip.  A consumer adds a state struct of its own,
+// a slot for it in QSlots and its guards; the facts the guards test come from here.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <initializer_list>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/jaicov_neq.h"
+#include "ba_kernels.h"
+#include "status.h"
+
+namespace jaicov {
+
+struct XformState;       // transform.h
+struct RelState;         // reliability.h
+struct DatumState;       // datum.h
+struct PrecisionState;   // precision.h
+
+// The engine's slots for what its consumers keep.  A result (xform, rel) stays until the next run of its family or its release, a
+// later inverting solve included; an inverting solve withdraws the S of the datum state alone (datum_state_invalidate).
+struct QSlots {
+    std::unique_ptr<XformState> xform;       // result of jaicov_xform_run
+    std::unique_ptr<RelState> rel;           // result of jaicov_rel_run / jaicov_rel_run_points
+    std::unique_ptr<DatumState> datum;       // S of the last jaicov_datum_transform and its work buffer
+    std::unique_ptr<PrecisionState> prec;    // work buffers of the precision calls
+};
+
+// What a consumer sees of an engine.  Pointers stay owned by the engine.
+struct QView {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    double *Q = nullptr;               // the cofactor matrix: lower part valid (row-major square, as gather_sub_kernel reads it), leading
+    long ld = 0;                       // dimension ld, order `order`, border rows 0 .. d-1
+    int order = 0;                     // order of the matrix: U, or the first EO column for the one of the EO-reduced system
+    int U = 0;                         // the engine's full order
+    int d = 0;
+    int n_points = 0;
+    bool have_q = false;               // an inverting solve left a cofactor matrix
+    bool reduced = false;              // ... of the EO-reduced system: no columns of the exterior orientations
+    bool full_q = false;               // ... all of Qxx: have_q, not reduced, order U
+    bool sharded = false;              // the engine accumulates a range of images or leaves the shared groups to another rank
+    double sigma2 = 0.0;               // a-priori variance factor of the build whose system was inverted
+    double lambda = 0.0;               // and its damping value (jaicov_rel_summary [5]: sum r = f needs 0)
+    const DevProblem *p = nullptr;     // counts + device tables (ip_image / ip_point: every image point of the problem, in engine order)
+    const double *d_vals = nullptr;    // current slot vector on the device
+    const double *rowsA = nullptr;     // compact rows of the current parameter values (rows.hip layout [2 KROW][n_ip]) and the
+    const double *rowsW = nullptr;     // misclosures [2][n_ip]: up to date after engine_ensure_rows
+    const double *ll_diag = nullptr;   // diag(D): [2 n_ip] of the image coordinates in engine order (variances, or the dense block's
+                                       // diagonal), then [n_dg_rows] of the directly observed rows (dg_var, or the dense group's diagonal)
+    const std::vector<int32_t> *slot_col = nullptr;     // column of every slot (JAICOV_COL_FIXED for fixed parameters)
+    const std::vector<int32_t> *ip_old2new = nullptr;   // empty, or the engine position of the caller's image point
+    const std::vector<int32_t> *blk_ip_begin = nullptr; // engine image blocks (ordinary images served as blocks included)
+    const std::vector<int64_t> *blk_w_off = nullptr;    // their weight offsets in p->blk_w (< 0: 2 x 2 weights)
+    QSlots *slot = nullptr;            // the engine's slots
+    std::string *err = nullptr;        // jaicov_neq_last_error text
+};
+
+void engine_q_view(jaicov_engine *e, QView *v);
+// Brings the compact rows up to the current parameter values (a jaicov_status)
+int engine_ensure_rows(jaicov_engine *e);
+
+inline QView q_view(jaicov_engine *e) {
+    QView v;
+    engine_q_view(e, &v);
+    return v;
+}
+
+// the state a slot holds, or null with `none` as the error text
+template <typename S>
+inline S *q_result(const QView &v, const std::unique_ptr<S> &slot, const char *none) {
+    if (!slot) *v.err = none;
+    return slot.get();
+}
+
+// the device's work on the state ends before the state goes
+template <typename S>
+inline void q_release(const QView &v, std::unique_ptr<S> &slot) {
+    if (!slot) return;
+    hipSetDevice(v.device);
+    hipStreamSynchronize(v.stream);
+    slot.reset();
+}
+
+// device -> host on the engine's stream, complete on return; an entry without a destination or without bytes is skipped
+struct QCopy { void *dst; const void *src; size_t bytes; };
+inline int q_download(const QView &v, std::initializer_list<QCopy> copies) {
+    HIPE(*v.err, hipSetDevice(v.device));
+    for (const QCopy &c : copies)
+        if (c.dst && c.bytes) HIPE(*v.err, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, v.stream));
+    HIPE(*v.err, hipStreamSynchronize(v.stream));
+    return JAICOV_OK;
+}
+
+}  // namespace jaicov

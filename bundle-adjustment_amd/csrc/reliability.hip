@@ -40,6 +40,7 @@
 #include "../../include/jaicov_reliability.h"
 #include "../../include/jaicov_reliability_points.h"
 #include "gemm_f64.h"
+#include "qview.h"
 #include "reliability.h"
 #include "status.h"
 
@@ -760,7 +761,7 @@ constexpr size_t RL_BATCH_BYTES = (size_t)1 << 30;   // work buffers of the dens
 
 // pa != nullptr: the table of the image points as well (jaicov_rel_run_points); everything it adds is launched after the plain run's
 // kernels of the same group, which stay what they are
-static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx, const RelPointArgs *pa) {
+static int rel_run_impl(const QView &v, RelState *s, double s2t, const double *dx, const RelPointArgs *pa) {
     const DevProblem &p = *v.p;
     const double s0 = v.sigma2;
     const long n_ip = p.n_ip, n_rows = s->n_rows;
@@ -912,8 +913,7 @@ static int rel_run_impl(RelView &v, RelState *s, double s2t, const double *dx, c
 static int rel_run_checked(jaicov_engine *e, double sigma2_test, const double *dx, const RelPointArgs *pa, int32_t *n_rows,
                            int32_t *n_image_points) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    RelView v;
-    engine_rel_view(e, &v, 0);
+    const QView v = q_view(e);
     if (v.sharded) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "reliability needs an engine that holds every observation (not a shard)");
     if (!(sigma2_test > 0) || !std::isfinite(sigma2_test)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "sigma2_test must be positive and finite");
     if (pa && (!(pa->lambda0 > 0) || !std::isfinite(pa->lambda0))) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "lambda0 must be positive and finite");
@@ -923,10 +923,10 @@ static int rel_run_checked(jaicov_engine *e, double sigma2_test, const double *d
     const long rows = 2 * (long)p0.n_ip + p0.n_sb + p0.n_dg_rows;
     if (rows > INT32_MAX) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "more than 2^31 - 1 observation rows");
     HIPE(*v.err, hipSetDevice(v.device));
-    int rc = engine_rel_view(e, &v, 1);    // the compact rows of the current parameter values
+    int rc = engine_ensure_rows(e);    // the compact rows of the current parameter values
     if (rc != JAICOV_OK) return rc;
     // the arguments are accepted: the previous result goes
-    v.state->reset();
+    v.slot->rel.reset();
     std::unique_ptr<RelState> s(new RelState());
     s->n_rows = rows;
     rc = rel_run_impl(v, s.get(), sigma2_test, dx, pa);
@@ -934,7 +934,7 @@ static int rel_run_checked(jaicov_engine *e, double sigma2_test, const double *d
         hipStreamSynchronize(v.stream);
         return rc;
     }
-    *v.state = std::move(s);
+    v.slot->rel = std::move(s);
     if (n_rows) *n_rows = (int32_t)rows;
     if (n_image_points) *n_image_points = (int32_t)p0.n_ip;
     return JAICOV_OK;
@@ -950,46 +950,36 @@ extern "C" int jaicov_rel_run_points(jaicov_engine *e, double sigma2_test, const
     return rel_run_checked(e, sigma2_test, dx, &pa, n_rows, n_image_points);
 }
 
-static RelState *rl_result(jaicov_engine *e, RelView &v) {
-    engine_rel_view(e, &v, 0);
-    if (!*v.state) *v.err = "no reliability result: call jaicov_rel_run first";
-    return v.state->get();
-}
+static const char RL_NONE[] = "no reliability result: call jaicov_rel_run first";
 
 extern "C" int jaicov_rel_get(jaicov_engine *e, double *vres, double *qvv, double *r, double *t, int32_t n) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    RelView v;
-    RelState *s = rl_result(e, v);
+    const QView v = q_view(e);
+    RelState *s = q_result(v, v.slot->rel, RL_NONE);
     if (!s) return JAICOV_ERR_BAD_STATE;
     if (n != s->n_rows) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "n must equal the number of observation rows of the last run");
     if (n == 0) return JAICOV_OK;
-    HIPE(*v.err, hipSetDevice(v.device));
-    double *dst[4] = {vres, qvv, r, t};
-    for (int k = 0; k < 4; k++)
-        if (dst[k]) HIPE(*v.err, hipMemcpyAsync(dst[k], s->out.get() + k * (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    HIPE(*v.err, hipStreamSynchronize(v.stream));
-    return JAICOV_OK;
+    const double *src = s->out.get();
+    const size_t col = (size_t)n, bytes = col * sizeof(double);
+    return q_download(v, {{vres, src, bytes}, {qvv, src + col, bytes}, {r, src + 2 * col, bytes}, {t, src + 3 * col, bytes}});
 }
 
 extern "C" int jaicov_rel_get_points(jaicov_engine *e, double *out, int32_t n) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    RelView v;
-    RelState *s = rl_result(e, v);
+    const QView v = q_view(e);
+    RelState *s = q_result(v, v.slot->rel, RL_NONE);
     if (!s) return JAICOV_ERR_BAD_STATE;
     if (s->n_points < 0) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no table of the image points: the last run was a plain jaicov_rel_run");
     if (n != s->n_points || (n > 0 && !out))
         FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "n must equal the number of image points of the last run, and out must not be NULL");
     if (n == 0) return JAICOV_OK;
-    HIPE(*v.err, hipSetDevice(v.device));
-    HIPE(*v.err, hipMemcpyAsync(out, s->points.get(), JAICOV_REL_POINT_COLUMNS * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    HIPE(*v.err, hipStreamSynchronize(v.stream));
-    return JAICOV_OK;
+    return q_download(v, {{out, s->points.get(), JAICOV_REL_POINT_COLUMNS * (size_t)n * sizeof(double)}});
 }
 
 extern "C" int jaicov_rel_summary(jaicov_engine *e, double *out, int32_t n) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    RelView v;
-    RelState *s = rl_result(e, v);
+    const QView v = q_view(e);
+    RelState *s = q_result(v, v.slot->rel, RL_NONE);
     if (!s) return JAICOV_ERR_BAD_STATE;
     if ((n != 5 && n != 6) || !out) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "the summary has 5 entries (6 with the damping value)");
     memcpy(out, s->summary, (size_t)n * sizeof(double));
@@ -998,12 +988,7 @@ extern "C" int jaicov_rel_summary(jaicov_engine *e, double *out, int32_t n) {
 
 extern "C" int jaicov_rel_release(jaicov_engine *e) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    RelView v;
-    engine_rel_view(e, &v, 0);
-    if (*v.state) {
-        hipSetDevice(v.device);
-        hipStreamSynchronize(v.stream);
-        v.state->reset();
-    }
+    const QView v = q_view(e);
+    q_release(v, v.slot->rel);
     return JAICOV_OK;
 }

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/jaicov_transform.h"
+#include "qview.h"
 #include "status.h"
 #include "transform.h"
 
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(256) void xform_blocks_kernel(const double *__restr
 
 using namespace jaicov;
 
-static int xform_run_impl(XformView &v, XformState *s, double sigma2) {
+static int xform_run_impl(const QView &v, XformState *s, double sigma2) {
     const DevProblem &p = *v.p;
     const int nT = s->nT;
     if (nT == 0) return JAICOV_OK;
@@ -250,8 +251,7 @@ static int xform_run_impl(XformView &v, XformState *s, double sigma2) {
 extern "C" int jaicov_xform_run(jaicov_engine *e, const int32_t *points, int32_t n_points, const int32_t *pair_ref, const int32_t *pair_src,
                                 int32_t n_pairs, double sigma2, int32_t *n_transformed) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    XformView v;
-    engine_xform_view(e, &v);
+    const QView v = q_view(e);
     if (!v.full_q)
         FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no full cofactor matrix: solve with JAICOV_INVERT_FULL or JAICOV_INVERT_FULL_EXPANDED first");
     const DevProblem &p = *v.p;
@@ -267,14 +267,10 @@ extern "C" int jaicov_xform_run(jaicov_engine *e, const int32_t *points, int32_t
     for (int k = 0; k < n_pairs; k++)
         if (pair_ref[k] < 0 || pair_ref[k] >= p.n_images || pair_src[k] < 0 || pair_src[k] >= p.n_images)
             FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "image index out of range");
-    HIPE(*v.err, hipSetDevice(v.device));
     // which points each source image observes (CTEO:83 image.get(point) != null): CSR over the problem's image points
     std::vector<int32_t> ip_image(p.n_ip), ip_point(p.n_ip);
-    if (p.n_ip > 0) {
-        HIPE(*v.err, hipMemcpyAsync(ip_image.data(), p.ip_image, (size_t)p.n_ip * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-        HIPE(*v.err, hipMemcpyAsync(ip_point.data(), p.ip_point, (size_t)p.n_ip * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
-        HIPE(*v.err, hipStreamSynchronize(v.stream));
-    }
+    const size_t ip_bytes = (size_t)p.n_ip * sizeof(int32_t);
+    TRY(q_download(v, {{ip_image.data(), p.ip_image, ip_bytes}, {ip_point.data(), p.ip_point, ip_bytes}}));
     std::vector<int32_t> img_begin(p.n_images + 1, 0), img_pts(p.n_ip);
     for (int q = 0; q < p.n_ip; q++) img_begin[ip_image[q] + 1]++;
     for (int i = 0; i < p.n_images; i++) img_begin[i + 1] += img_begin[i];
@@ -290,7 +286,7 @@ extern "C" int jaicov_xform_run(jaicov_engine *e, const int32_t *points, int32_t
             if (stamp[points[i]] == k) { ids.push_back(points[i]); ids.push_back(S); ids.push_back(T); }
     }
     // the arguments are accepted: the previous result goes
-    v.state->reset();
+    v.slot->xform.reset();
     std::unique_ptr<XformState> s(new XformState());
     s->ids = std::move(ids);
     s->nT = (int)(s->ids.size() / 3);
@@ -301,50 +297,39 @@ extern "C" int jaicov_xform_run(jaicov_engine *e, const int32_t *points, int32_t
         return rc;
     }
     if (n_transformed) *n_transformed = s->nT;
-    *v.state = std::move(s);
+    v.slot->xform = std::move(s);
     return JAICOV_OK;
 }
 
-static XformState *xf_result(jaicov_engine *e, XformView &v) {
-    engine_xform_view(e, &v);
-    if (!*v.state) *v.err = "no transformation result: call jaicov_xform_run first";
-    return v.state->get();
-}
+static const char XF_NONE[] = "no transformation result: call jaicov_xform_run first";
 
 extern "C" int jaicov_xform_get_coordinates(jaicov_engine *e, double *xyz, int32_t *ids, int32_t n) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    XformView v;
-    XformState *s = xf_result(e, v);
+    const QView v = q_view(e);
+    XformState *s = q_result(v, v.slot->xform, XF_NONE);
     if (!s) return JAICOV_ERR_BAD_STATE;
     if (n != s->nT) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "n must equal the number of transformed points");
     if (ids && n > 0) memcpy(ids, s->ids.data(), 3 * (size_t)n * sizeof(int32_t));
-    if (xyz && n > 0) {
-        HIPE(*v.err, hipSetDevice(v.device));
-        HIPE(*v.err, hipMemcpyAsync(xyz, s->xyz.get(), 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-        HIPE(*v.err, hipStreamSynchronize(v.stream));
-    }
+    if (xyz && n > 0) TRY(q_download(v, {{xyz, s->xyz.get(), 3 * (size_t)n * sizeof(double)}}));
     return JAICOV_OK;
 }
 
 extern "C" int jaicov_xform_get_covariance(jaicov_engine *e, double *packed, size_t len) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    XformView v;
-    XformState *s = xf_result(e, v);
+    const QView v = q_view(e);
+    XformState *s = q_result(v, v.slot->xform, XF_NONE);
     if (!s) return JAICOV_ERR_BAD_STATE;
     const size_t want = (size_t)s->R * (s->R + 1) / 2;
     if (len != want) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "covariance buffer length must be R(R+1)/2");
     if (want == 0) return JAICOV_OK;
     if (!packed) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "covariance buffer missing");
-    HIPE(*v.err, hipSetDevice(v.device));
-    HIPE(*v.err, hipMemcpyAsync(packed, s->ap.get(), want * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    HIPE(*v.err, hipStreamSynchronize(v.stream));
-    return JAICOV_OK;
+    return q_download(v, {{packed, s->ap.get(), want * sizeof(double)}});
 }
 
 extern "C" int jaicov_xform_get_covariance_sub(jaicov_engine *e, const int32_t *rows, int32_t k, double *out) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    XformView v;
-    XformState *s = xf_result(e, v);
+    const QView v = q_view(e);
+    XformState *s = q_result(v, v.slot->xform, XF_NONE);
     if (!s) return JAICOV_ERR_BAD_STATE;
     if (!rows || !out || k <= 0) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "rows / out missing or k <= 0");
     for (int i = 0; i < k; i++)
@@ -363,8 +348,8 @@ extern "C" int jaicov_xform_get_covariance_sub(jaicov_engine *e, const int32_t *
 
 extern "C" int jaicov_xform_get_point_blocks(jaicov_engine *e, double *out, int32_t n) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    XformView v;
-    XformState *s = xf_result(e, v);
+    const QView v = q_view(e);
+    XformState *s = q_result(v, v.slot->xform, XF_NONE);
     if (!s) return JAICOV_ERR_BAD_STATE;
     if (n != s->nT) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "n must equal the number of transformed points");
     if (n == 0) return JAICOV_OK;
@@ -380,12 +365,7 @@ extern "C" int jaicov_xform_get_point_blocks(jaicov_engine *e, double *out, int3
 
 extern "C" int jaicov_xform_release(jaicov_engine *e) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    XformView v;
-    engine_xform_view(e, &v);
-    if (*v.state) {
-        hipSetDevice(v.device);
-        hipStreamSynchronize(v.stream);
-        v.state->reset();
-    }
+    const QView v = q_view(e);
+    q_release(v, v.slot->xform);
     return JAICOV_OK;
 }

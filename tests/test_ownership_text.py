@@ -12,6 +12,7 @@ RAW = [r"hipMalloc\w*\s*\(", r"hipExtMalloc\w*\s*\(", r"hipFree\s*\(", r"hipEven
 STREAMS = [r"hipStreamCreate\w*\s*\(", r"hipExtStreamCreate\w*\s*\(", r"hipStreamDestroy\s*\("]
 STREAM_HOMES = ("devbuf.h", "dense.hip")              # DevStream, and the pool of streams that live as long as the process
 GONE = ["XF_HIP", "RL_HIP", "DHIP", "XF_FAIL", "RL_FAIL", "DFAIL"]
+VIEWS_GONE = ["XformView", "RelView", "DatumView", "PrecView", "engine_xform_view", "engine_rel_view", "engine_datum_view", "engine_prec_view"]
 
 
 def sources():
@@ -59,3 +60,12 @@ def test_status_macros_exist_once():
     for macro in ("FAIL", "HIPE", "HIPCHK"):
         where = [n for n, t in src.items() if re.search(r"#\s*define\s+%s\b" % macro, t)]
         assert where == ["status.h"], (macro, where)
+
+
+def test_the_cofactor_matrix_has_one_view_and_the_shard_rule_one_place():
+    src = sources()
+    for name, text in src.items():
+        for gone in VIEWS_GONE:
+            assert not re.search(r"\b%s\b" % gone, text), (name, gone)
+    assert [n for n, t in src.items() if re.search(r"\bstruct\s+QView\s*\{", t)] == ["qview.h"]
+    assert src["engine.hip"].count("ip_count != e->p.n_ip") == 1
