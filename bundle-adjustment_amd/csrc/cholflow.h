@@ -112,7 +112,7 @@ class FlowFactor {     // move-only (its owners are)
     std::vector<int4> tasks_host_;       // the task list (report_stall)
     DevBuf<int4> tasks_;
     DevBuf<int> flags_;                  // fine-grained device memory where there is any
-    DevBuf<double> scratch_;             // [grid][128 x 128] + 64 zeros
+    DevBuf<double> scratch_;             // one-kernel form: [grid][128 x 128]; then 64 zeros (every form)
     DevBuf<double> partial_;
     DevBuf<long long> trace_;
     DevBuf<double> diag_scratch_;        // one-kernel form: work arrays of the inline diagonal blocks

@@ -95,7 +95,7 @@ struct FlowArgs {
     int d, U, bstride;
     double *diag_scratch;    // INLINE_DIAG: [grid][128 x DP + 8 x 16 x WDP] work arrays of potrf_diag_body in global memory
     const double *zeros;     // 64 zeros
-    double *scratch;         // [grid][128 x 128] per workgroup: operand of the multiplication by inv(L_jj)'
+    double *scratch;         // one-kernel form: [grid][128 x 128] per workgroup: operand of the multiplication by inv(L_jj)'
     double *partial;         // [partial buffers][128 x 128] partial sums of split update ranges (FLOW_PART)
     int *pflag;              // [partial buffers] the partial sum is in memory
     long long timeout;       // wall-clock ticks (100 MHz) a wait may take before the factorisation is abandoned
@@ -194,6 +194,7 @@ __global__ __launch_bounds__(256, 2) void chol_tile_kernel(FlowArgs g) {
     __shared__ int s_msg[4];
     const int tid = threadIdx.x;
     const int bid = (int)blockIdx.x;
+    constexpr bool REG_FINISH = !INLINE_DIAG;    // off-diagonal tiles are finished from the accumulators (no phase 1, no scratch tile)
     // Everything derived from the thread index is recomputed where it is used, from a copy of tid the compiler cannot see
     // through: hoisted out of the persistent loop those values (dozens of them) stay live across the MFMA loop, the kernel
     // spills, and a kernel with a scratch segment is admitted with fewer waves per shader engine (measured: 458 of the 496
@@ -299,6 +300,50 @@ __global__ __launch_bounds__(256, 2) void chol_tile_kernel(FlowArgs g) {
 #undef FLOW_MM
     };
 
+    // Finishing an off-diagonal tile from the accumulators (REG_FINISH: every form with a companion kernel).  Register r of an
+    // accumulator block holds rows 4r .. 4r + 3 of the block, one row per 16 lanes -- which is what v_mfma_f64_16x16x4_f64 wants as
+    // the B operand of the k-block {4r .. 4r + 3}.  So with X = C' in the accumulators, Y' = inv(L_jj) X is formed with X taken
+    // from the accumulator registers as they stand and only the inverse loaded (finish below).  transpose_acc(): the tile in the
+    // accumulators -> its transpose in the accumulators, through the operand staging array, which is free outside accumulate().
+    // The tile is 128 KB, the array 72 KB: two halves, each a set of blocks that is its own mirror image ((x < 2) == (y < 2), then
+    // the rest), so that a wave reads into exactly the registers it has just written out.  A 16 x 16 block lies with a row stride of
+    // 17 doubles: the transposed reads come out as ds_read2_b64 (16 lanes down a column per access, banks of 16 doubles), and an odd
+    // stride puts those 16 lanes on 16 banks.
+    // The sums are the pipelined loop's own, bit for bit.  That loop feeds the four lane groups of one MFMA with k = 4 KS + {0, 1, 3, 2} (its
+    // operand staging swaps the two k of every odd 16-byte segment), in ascending KS.  With `staged` the transposition leaves rows
+    // 4r + {0, 1, 3, 2} of a block in the four lane groups of register r, the inverse's fragments are loaded with the same permutation, and
+    // what is skipped (kb > mb) are products with zeros at the END of every sum: the finished tile is the one the scratch path gave.
+    constexpr int FLOW_TS = 17, FLOW_TB = 16 * FLOW_TS, FLOW_TW = 8 * FLOW_TB;
+    static_assert(4 * FLOW_TW <= 2 * FLOW_STAGE && 2 * 64 * 64 <= 2 * FLOW_STAGE, "the finish works inside the staging array");
+    auto transpose_acc = [&](const bool staged) __attribute__((always_inline)) {
+        FLOW_OPAQUE_TID(tq);
+        const int lane = tq & 63, wave = tq >> 6;
+        const int kk = staged ? (lane >> 4) ^ (lane >> 5) : lane >> 4;       // lane group -> row of its four: {0, 1, 3, 2} or as it stands
+        double *wp = smem + wave * FLOW_TW + (lane >> 4) * FLOW_TS + (lane & 15);
+        const double *rp = smem + (2 * (wave & 1) + (wave >> 1)) * FLOW_TW + (lane & 15) * FLOW_TS + kk;   // the wave across the diagonal
+#pragma unroll
+        for (int half = 0; half < 2; half++) {
+#pragma unroll
+            for (int x = 0; x < 4; x++)
+#pragma unroll
+                for (int y = 0; y < 4; y++)
+                    if (((x >> 1) == (y >> 1)) == (half == 0)) {
+#pragma unroll
+                        for (int r = 0; r < 4; r++) wp[(4 * (x >> 1) + 2 * (x & 1) + (y & 1)) * FLOW_TB + 4 * r * FLOW_TS] = acc[x][y][r];
+                    }
+            __syncthreads();
+#pragma unroll
+            for (int x = 0; x < 4; x++)
+#pragma unroll
+                for (int y = 0; y < 4; y++)
+                    if (((x >> 1) == (y >> 1)) == (half == 0)) {
+#pragma unroll
+                        for (int r = 0; r < 4; r++) acc[x][y][r] = rp[(4 * (y >> 1) + 2 * (y & 1) + (x & 1)) * FLOW_TB + 4 * r];
+                    }
+            __syncthreads();
+        }
+    };
+
     // The workgroups dispatched last on an XCD that hosts a chain workgroup take no tickets.  Those XCDs hold fewer tile
     // workgroups than the others (a CU is taken, and the dispatcher stops at the first workgroup that does not fit), so the last
     // ones of the grid stay queued there for the whole run -- and about once in 2 000-3 600 factorisations one of the last
@@ -333,9 +378,11 @@ __global__ __launch_bounds__(256, 2) void chol_tile_kernel(FlowArgs g) {
         const bool critical = ti <= tj + g.crit_span && g.crit_prio > 0;
         if (critical) __builtin_amdgcn_s_setprio(3);
         // ---- one or two phases, each: accumulators <- memory, runs of MFMA work, accumulators -> memory.  Phase 0: the tile
-        //      and its updates.  Phase 1 (off-diagonal tile that is to be finished): zeros, then C inv(L_jj)' with C read back
-        //      from this workgroup's scratch tile.  ONE load site, ONE instance of the pipelined loop and ONE store site, and the
-        //      accumulators' live range never crosses a phase: anything else made the compiler shuffle and spill them.
+        //      and its updates, and with REG_FINISH the product with inv(L_jj)' in the accumulators (an off-diagonal tile that
+        //      is to be finished).  Phase 1 (the one-kernel form only, which runs serialised and has scratch anyway): zeros, then
+        //      C inv(L_jj)' with C read back from this workgroup's scratch tile.  ONE load site, ONE instance of the pipelined
+        //      loop and ONE store site, and the accumulators' live range never crosses a phase: anything else made the compiler
+        //      shuffle and spill them.
         int k = k0;
         for (int phase = 0;; phase++) {
             // -- what has to be there before the accumulators are loaded
@@ -502,9 +549,80 @@ __global__ __launch_bounds__(256, 2) void chol_tile_kernel(FlowArgs g) {
                 if (!ok) break;
             }
             if (g.trace && phase == 0) { t_upd = wall_clock64(); c_upd = clock64(); w_upd = waited; }
+            // -- REG_FINISH: L[i][j] = C inv(L_jj)' without leaving the registers (transpose_acc above): Y' = inv(L_jj) C'
+            const bool finish_here = REG_FINISH && fin && ti != tj;
+            if (finish_here) {
+                FLOW_STAGE_MARK(k, 5);
+                transpose_acc(true);                      // X = C': wave (wr, wc) holds block rows 4 wr .. and block columns 4 wc .. of X, rows in staged order
+                FLOW_OPAQUE_TID(tq);
+                const int lane = tq & 63;
+                const int wr = __builtin_amdgcn_readfirstlane(tq >> 7), wc = __builtin_amdgcn_readfirstlane((tq >> 6) & 1);
+                // the bottom waves also multiply the top half of X (the inverse is lower triangular: the top waves never need the bottom
+                // half): the top waves leave their 64 registers in LDS lane for lane, 32 KB per wave, read back with the same lane index
+                double *pub = smem + wc * 4096 + lane;
+                if (wr == 0) {
+#pragma unroll
+                    for (int kb = 0; kb < 4; kb++)
+#pragma unroll
+                        for (int y = 0; y < 4; y++)
+#pragma unroll
+                            for (int r = 0; r < 4; r++) pub[((kb * 4 + y) * 4 + r) * 64] = acc[kb][y][r];
+                }
+                // inv(L_jj) from the diagonal kernel (the barriers of this wait also publish the top half)
+                FLOW_STAGE_MARK(k, 2);
+                if (tid == 0) {
+                    const bool r = flow_spin(g.done + (long)tj * g.fs + tj, 1, g.ctrl, g.timeout, &waited);
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                    drain_stores();
+                    s_msg[1] = r ? 1 : 0;
+                }
+                __syncthreads();
+                ok = s_msg[1] != 0;
+                __syncthreads();
+                if (!ok) break;
+                FLOW_STAGE_MARK(k, 6);
+                // In place, bottom block row first: block row mb of X is read by no block row above it.  Only kb <= mb is multiplied (36 of
+                // the 64 block pairs).  A fragment of (mb, kb), register r: inv[16 mb + (lane & 15)][16 kb + 4 r + {0, 1, 3, 2}[lane >> 4]], straight from
+                // memory (the whole block column reads the same inverse: L2), four loads for sixteen MFMAs.
+                const double *mp = g.invd + (long)tj * 16384 + (long)(64 * wr + (lane & 15)) * 128 + ((lane >> 4) ^ (lane >> 5));
+                const double *mq = mp + 64 * wr;
+#pragma unroll
+                for (int x = 3; x >= 0; x--) {
+                    d4_t tmp[4];
+#pragma unroll
+                    for (int y = 0; y < 4; y++) tmp[y] = d4_t{0.0, 0.0, 0.0, 0.0};
+                    if (wr != 0) {
+#pragma unroll
+                        for (int kb = 0; kb < 4; kb++) {
+                            double a[4];
+#pragma unroll
+                            for (int r = 0; r < 4; r++) a[r] = mp[16 * x * 128 + 16 * kb + 4 * r];
+#pragma unroll
+                            for (int r = 0; r < 4; r++)
+#pragma unroll
+                                for (int y = 0; y < 4; y++)
+                                    tmp[y] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[r], pub[((kb * 4 + y) * 4 + r) * 64], tmp[y], 0, 0, 0);
+                        }
+                    }
+#pragma unroll
+                    for (int kb = 0; kb <= x; kb++) {
+                        double a[4];
+#pragma unroll
+                        for (int r = 0; r < 4; r++) a[r] = mq[16 * x * 128 + 16 * kb + 4 * r];
+#pragma unroll
+                        for (int r = 0; r < 4; r++)
+#pragma unroll
+                            for (int y = 0; y < 4; y++) tmp[y] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[r], acc[kb][y][r], tmp[y], 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int y = 0; y < 4; y++) acc[x][y] = tmp[y];
+                }
+                __syncthreads();                          // the bottom waves have read the top half
+                transpose_acc(false);                     // Y' -> Y, the tile as the store below expects it
+            }
             // -- where the accumulators go, and which flag tells whom
-            FLOW_STAGE_MARK(k, 5 + phase);
-            const bool to_scratch = phase == 0 && fin && ti != tj;
+            if (!finish_here) FLOW_STAGE_MARK(k, 5 + phase);
+            const bool to_scratch = !REG_FINISH && phase == 0 && fin && ti != tj;
             {
                 FLOW_OPAQUE_TID(tq);
                 const long trow = 64 * (tq >> 7) + ((tq & 63) >> 4), tcol = 64 * ((tq >> 6) & 1) + (tq & 15);
@@ -545,7 +663,7 @@ __global__ __launch_bounds__(256, 2) void chol_tile_kernel(FlowArgs g) {
             }
             if (tid == 0) {
                 if (part) flow_st(g.pflag + pbuf, 1);                                      // a partial sum, for the tile's own task
-                else if (phase == 1) flow_st(g.done + (long)ti * g.fs + tj, 1);            // L[i][j] is final
+                else if (phase == 1 || finish_here) flow_st(g.done + (long)ti * g.fs + tj, 1);   // L[i][j] is final
                 else if (fin) flow_st(g.diag_ready + tj, 1);                               // updated diagonal tile, for the diagonal kernel
                 else flow_st(g.applied + (long)ti * g.fs + tj, k1 + 1);                    // partial visit (chain form: the tile is the chain workgroup's from here)
             }
@@ -1307,8 +1425,10 @@ hipError_t FlowFactor::init(const FlowView &view, const FlowHooks &hooks) {
     }
     HIPCHK(hipMemset(f.flags_.get(), 0, f.lay_.words * sizeof(int)));
     f.grid_ = flow_grid_size();
-    HIPCHK(f.scratch_.reserve((size_t)f.grid_ * 16384 + 64));
-    HIPCHK(hipMemset(f.scratch_.get() + (size_t)f.grid_ * 16384, 0, 64 * sizeof(double)));
+    // the scratch tiles belong to the one-kernel form alone (the others finish their tiles from the accumulators); the zeros to all
+    const size_t scratch_tiles = f.one_kernel_ ? (size_t)f.grid_ : 0;
+    HIPCHK(f.scratch_.reserve(scratch_tiles * 16384 + 64));
+    HIPCHK(hipMemset(f.scratch_.get() + scratch_tiles * 16384, 0, 64 * sizeof(double)));
     if (f.partials_ > 0) HIPCHK(f.partial_.reserve((size_t)f.partials_ * 16384));
     HIPCHK(f.alive_.alloc(4));
     for (int b = 0; b < 4; b++) f.alive_.get()[b] = 0;
@@ -1338,8 +1458,8 @@ hipError_t FlowFactor::factor(hipEvent_t all_ready, bool profile) {
     g.pflag = flags + lay_.pflag;
     g.partial = partial_.get();
     g.info = v_.d_info;
-    g.scratch = scratch_.get();
-    g.zeros = scratch_.get() + (size_t)grid_ * 16384;
+    g.scratch = one_kernel_ ? scratch_.get() : nullptr;
+    g.zeros = scratch_.get() + (one_kernel_ ? (size_t)grid_ : 0) * 16384;
     // time limit of a single wait, 100 MHz ticks: 0.25 s + 10 x the time the whole factorisation should take at 20 TFLOP/s
     // (order 15 104: 0.25 + 0.57 s... the longest ordinary wait there is ~2 ms)
     const double expect_ms = (double)v_.nfact * v_.nfact * v_.nfact / 3.0 / 20e9;
