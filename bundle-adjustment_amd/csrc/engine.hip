@@ -21,6 +21,7 @@
 #include "dense.h"
 #include "devbuf.h"
 #include "gemm_f64.h"
+#include "parameters.h"
 #include "precision.h"
 #include "qview.h"
 #include "reliability.h"

@@ -1,8 +1,8 @@
 """ctypes binding of the C ABI in ``include/jaicov_neq.h`` / ``include/jaicov_dense.h`` / ``include/jaicov_transform.h`` /
 ``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_reliability_points.h`` /
 ``include/jaicov_datum.h`` / ``include/jaicov_intersect.h`` / ``include/jaicov_resect.h`` /
-``include/jaicov_relorient.h`` / ``include/jaicov_simil.h`` / ``include/jaicov_lens.h`` / ``include/jaicov_precision.h``
-(``csrc/libjaicov_neq.so``).
+``include/jaicov_relorient.h`` / ``include/jaicov_simil.h`` / ``include/jaicov_lens.h`` / ``include/jaicov_precision.h`` /
+``include/jaicov_parameters.h`` (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
 library has not been built, and every call fails with ``EngineError`` when no gfx950 device is present.
@@ -55,6 +55,14 @@ DATUM_EXPORTS = ["jaicov_datum_transform", "jaicov_datum_apply"]
 PREC_EXPORTS = ["jaicov_prec_points", "jaicov_prec_stations", "jaicov_prec_lengths", "jaicov_prec_components"]
 PREC_PARTIAL, PREC_NEGATIVE, PREC_NOT_FINITE, PREC_DEGENERATE = 1, 2, 4, 8     # status bits of a point, station or pair
 PREC_POINT_COLUMNS, PREC_STATION_COLUMNS, PREC_LENGTH_COLUMNS = 22, 25, 5
+# include/jaicov_parameters.h: correlations and significance tests of the unknowns read from the cofactor matrix
+PARAM_EXPORTS = ["jaicov_par_maxima", "jaicov_par_pairs", "jaicov_par_block", "jaicov_par_tests"]
+PAR_NONPOSITIVE, PAR_NOT_FINITE, PAR_PARTIAL, PAR_EMPTY, PAR_TOO_LARGE, PAR_SINGULAR = 1, 2, 4, 8, 16, 32   # status bits
+PAR_SKIP_SAME_POINT, PAR_SKIP_SAME_IMAGE = 1, 2                                                           # flags
+PAR_CLASS_POINT, PAR_CLASS_INTERIOR, PAR_CLASS_DISTORTION, PAR_CLASS_EXTERIOR = range(4)
+PAR_CLASS_NAMES = ("point", "interior", "distortion", "exterior")
+PAR_MAX_GROUP, PAR_TEST_COLUMNS = 64, 4
+PAR_ALL_PAIRS = 0xFFFF
 # jaicov_dlt_restriction (DirectLinearTransformation.RestrictionType, DT:51-58 order) and the per-image status values
 DLT_IDENTICAL_PRINCIPLE_DISTANCE, DLT_ROTATION_WITHOUT_SHEAR, DLT_FIXED_PRINCIPLE_DISTANCE_X, DLT_FIXED_PRINCIPLE_DISTANCE_Y, \
     DLT_FIXED_PRINCIPAL_POINT_X, DLT_FIXED_PRINCIPAL_POINT_Y = range(6)
@@ -188,6 +196,10 @@ def load_library():
     L.jaicov_prec_stations.argtypes = [vp, C.c_double, C.c_double, C.c_double, _pi, C.c_int32, _pd, _pi]
     L.jaicov_prec_lengths.argtypes = [vp, C.c_double, _pi, C.c_int32, _pd, _pi]
     L.jaicov_prec_components.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, _pd, _pd, _pd, _pd, _pi]
+    L.jaicov_par_maxima.argtypes = [vp, C.c_uint32, C.c_uint32, _pd, _pi, _pi, C.c_int32]
+    L.jaicov_par_pairs.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_double, C.c_int64, _pi, _pd, C.POINTER(C.c_int64)]
+    L.jaicov_par_block.argtypes = [vp, _pi, C.c_int32, _pi, C.c_int32, _pd]
+    L.jaicov_par_tests.argtypes = [vp, C.c_double, _pi, _pi, _pd, C.c_int32, _pd, _pi]
     L.jaicov_dlt_adjust.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pi, C.c_int32, C.c_int32, _pd, _pi, _pi, _pd]
     L.jaicov_isect_points.argtypes = [C.c_int32, _pi, _pi, _pd, _pd, C.c_int32, _pd, _pd, C.c_double, C.c_int32, C.c_double, C.c_int32,
                                       _pd, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
@@ -219,6 +231,13 @@ PointPrecision = namedtuple("PointPrecision", ["sigma", "helmert", "semi_axes", 
                                                "sigma_angles", "status"])
 LengthPrecision = namedtuple("LengthPrecision", ["length", "sigma", "sigma_diff", "status"])
 PrincipalComponents = namedtuple("PrincipalComponents", ["values", "vectors", "trace", "residuals", "iterations", "converged"])
+# Engine.correlation_maxima: one entry per column of the cofactor matrix (include/jaicov_parameters.h)
+CorrelationMaxima = namedtuple("CorrelationMaxima", ["rho", "partner", "status"])
+# Engine.correlated_pairs: cols (m, 2) with i > j and rho (m,), sorted; both None when count exceeds the capacity
+CorrelatedPairs = namedtuple("CorrelatedPairs", ["cols", "rho", "count"])
+# Engine.parameter_tests: one entry per group; t is NaN unless k == 1
+ParameterTests = namedtuple("ParameterTests", ["q", "T", "k", "t", "status"])
+ColumnName = namedtuple("ColumnName", ["cls", "item", "component"])
 
 
 def _p(a):
@@ -526,6 +545,56 @@ class Engine:
                                                 _p(vectors), _p(tr), _p(res), C.byref(it)))
         return PrincipalComponents(values, vectors, float(tr[0]), res, abs(it.value), it.value > 0)
 
+    # correlations and tests of the unknowns (include/jaicov_parameters.h) ----------------------------------------------------------
+    def correlation_maxima(self, pair_mask=PAR_ALL_PAIRS, flags=0):
+        """For every column of the cofactor matrix its admissible partner of largest |rho| (the lowest among equals), in one pass
+        over the lower triangle on the device.  pair_mask bit 4 a + b: a column of class a considers partners of class b
+        (PAR_CLASS_*); flags: PAR_SKIP_SAME_POINT / PAR_SKIP_SAME_IMAGE.  Returns a CorrelationMaxima."""
+        n = self.cofactor_order()
+        if n < 0:
+            raise EngineError(-2, "no cofactor matrix: solve with invert != 0 first")
+        rho = np.zeros(n); partner = np.zeros(n, np.int32); status = np.zeros(n, np.int32)
+        self._chk(self.L.jaicov_par_maxima(self._h, int(pair_mask), int(flags), _p(rho), partner.ctypes.data_as(_pi),
+                                           status.ctypes.data_as(_pi), n))
+        return CorrelationMaxima(rho, partner, status)
+
+    def correlated_pairs(self, threshold, pair_mask=PAR_ALL_PAIRS, flags=0, capacity=1 << 16):
+        """Every pair of columns i > j with |rho| >= threshold that the mask admits in either direction, sorted by |rho| descending,
+        then i, then j.  Returns a CorrelatedPairs; `count` is always exact, cols and rho are None when it exceeds `capacity`."""
+        cap = int(capacity)
+        cols = np.zeros((max(cap, 0), 2), np.int32); rho = np.zeros(max(cap, 0)); count = C.c_int64(-1)
+        self._chk(self.L.jaicov_par_pairs(self._h, int(pair_mask), int(flags), float(threshold), cap, cols.ctypes.data_as(_pi), _p(rho),
+                                          C.byref(count)))
+        m = count.value
+        if m > cap:
+            return CorrelatedPairs(None, None, m)
+        return CorrelatedPairs(cols[:m].copy(), rho[:m].copy(), m)
+
+    def correlation_block(self, row_cols, col_cols):
+        """rho between every column of `row_cols` and every column of `col_cols`: (n_r, n_c), 1.0 where both are the same column."""
+        r = np.ascontiguousarray(row_cols, np.int32).ravel(); c = np.ascontiguousarray(col_cols, np.int32).ravel()
+        out = np.zeros((r.size, c.size))
+        self._chk(self.L.jaicov_par_block(self._h, r.ctypes.data_as(_pi), r.size, c.ctypes.data_as(_pi), c.size, _p(out)))
+        return out
+
+    def parameter_tests(self, sigma2, groups, x0=None):
+        """Test of x_g = x0_g for every group of slots in `groups` (a list of slot lists; x0: None for zeros, or lists parallel to
+        them): q = delta' inv(Q_gg) delta, T = q / (k sigma2), k free members, and the signed t of a single parameter.  No quantile
+        is evaluated.  Returns a ParameterTests."""
+        groups = [np.asarray(g, np.int32).ravel() for g in groups]
+        begin = np.concatenate([[0], np.cumsum([g.size for g in groups])]).astype(np.int32)
+        slots = np.ascontiguousarray(np.concatenate(groups) if groups else np.zeros(0), np.int32)
+        xs = None
+        if x0 is not None:
+            xs = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float64).ravel() for x in x0]) if groups else np.zeros(0), np.float64)
+            if xs.size != slots.size:
+                raise ValueError("x0 must run parallel to the groups")
+        n = len(groups)
+        out = np.zeros((n, PAR_TEST_COLUMNS)); status = np.zeros(n, np.int32)
+        self._chk(self.L.jaicov_par_tests(self._h, float(sigma2), begin.ctypes.data_as(_pi), slots.ctypes.data_as(_pi),
+                                          None if xs is None else _p(xs), n, _p(out), status.ctypes.data_as(_pi)))
+        return ParameterTests(out[:, 0], out[:, 1], out[:, 2].astype(np.int32), out[:, 3], status)
+
     def get_rows(self, ip_begin, ip_count):
         w = np.zeros((ip_count, 2)); A = np.zeros((ip_count, 2, KROW))
         self._chk(self.L.jaicov_neq_get_rows(self._h, ip_begin, ip_count, _p(w), _p(A)))
@@ -586,6 +655,29 @@ def point_column_range(fp: FlatProblem):
     if cols.size == 0 or cols[-1] - cols[0] + 1 != cols.size:
         raise ValueError("the columns of the image-observed points are not one contiguous range")
     return int(cols[0]), int(cols.size)
+
+
+def column_names(fp: FlatProblem):
+    """The ColumnName (class name, item, component) of every column of the full cofactor matrix from the flat problem (no device
+    needed): ("point", p, "X"), ("interior", camera, "x0"), ("distortion", camera, index within the camera's coefficients),
+    ("exterior", image, "omega"); a border column is ("border", row, "")."""
+    names = [ColumnName("border", c, "") for c in range(fp.n_unknowns)]
+    for p in range(fp.n_points):
+        for k in range(3):
+            if fp.point_col[p, k] >= 0:
+                names[fp.point_col[p, k]] = ColumnName("point", p, "XYZ"[k])
+    for c in range(fp.n_cameras):
+        for k in range(3):
+            if fp.io_col[c, k] >= 0:
+                names[fp.io_col[c, k]] = ColumnName("interior", c, ("x0", "y0", "c")[k])
+        for j in range(int(fp.cam_dist_begin[c]), int(fp.cam_dist_begin[c + 1])):
+            if fp.dist_col[j] >= 0:
+                names[fp.dist_col[j]] = ColumnName("distortion", c, j - int(fp.cam_dist_begin[c]))
+    for i in range(fp.n_images):
+        for k in range(6):
+            if fp.eo_col[i, k] >= 0:
+                names[fp.eo_col[i, k]] = ColumnName("exterior", i, ("X0", "Y0", "Z0", "omega", "phi", "kappa")[k])
+    return names
 
 
 def dense_spd_solve_packed(ap, b=None, invert=False):

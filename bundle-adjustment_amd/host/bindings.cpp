@@ -179,6 +179,30 @@ PYBIND11_MODULE(_jaicov_host, m) {
                                   py::array_t<double>((py::ssize_t)c.residuals.size(), c.residuals.data()), c.iterations, c.converged);
         }, py::arg("firstCol"), py::arg("nCols"), py::arg("k"), py::arg("tol") = 0.0, py::arg("maxIterations") = 200,
              "(values, vectors (k, nCols), trace, residuals, iterations, converged) of the sub-block's largest eigenpairs")
+        .def("parameterCorrelations", [](BundleAdjustment &b, uint32_t pairMask, uint32_t flags) {
+            auto c = b.parameterCorrelations(pairMask, flags);
+            return py::make_tuple(py::array_t<double>((py::ssize_t)c.rho.size(), c.rho.data()),
+                                  py::array_t<int32_t>((py::ssize_t)c.partner.size(), c.partner.data()),
+                                  py::array_t<int32_t>((py::ssize_t)c.status.size(), c.status.data()));
+        }, py::arg("pairMask") = 0xFFFFu, py::arg("flags") = 0u,
+             "(rho, partner, status) of every column: its worst-correlated admissible partner (include/jaicov_parameters.h)")
+        .def("correlatedPairs", [](BundleAdjustment &b, double threshold, uint32_t pairMask, uint32_t flags, int64_t capacity) {
+            auto p = b.correlatedPairs(threshold, pairMask, flags, capacity);
+            return py::make_tuple(py::array_t<int32_t>({p.rho.size(), (size_t)2}, p.cols.data()),
+                                  py::array_t<double>((py::ssize_t)p.rho.size(), p.rho.data()), p.count);
+        }, py::arg("threshold"), py::arg("pairMask") = 0xFFFFu, py::arg("flags") = 0u, py::arg("capacity") = (int64_t)1 << 16,
+             "(cols (m, 2), rho (m,), count) of the pairs with |rho| >= threshold, sorted; empty when count exceeds the capacity")
+        .def("correlationBlock", [](BundleAdjustment &b, std::vector<int32_t> rowCols, std::vector<int32_t> colCols) {
+            auto o = b.correlationBlock(rowCols, colCols);
+            return py::array_t<double>({rowCols.size(), colCols.size()}, o.data());
+        }, py::arg("rowCols"), py::arg("colCols"), "rho between two lists of columns, (n_r, n_c)")
+        .def("testParameters", [](BundleAdjustment &b, double sigma2, std::vector<int32_t> groupBegin, std::vector<int32_t> groupSlot,
+                                  std::vector<double> x0) {
+            auto t = b.testParameters(sigma2, groupBegin, groupSlot, x0);
+            return py::make_tuple(py::array_t<double>({t.status.size(), (size_t)JAICOV_PAR_TEST_COLUMNS}, t.table.data()),
+                                  py::array_t<int32_t>((py::ssize_t)t.status.size(), t.status.data()));
+        }, py::arg("sigma2"), py::arg("groupBegin"), py::arg("groupSlot"), py::arg("x0") = std::vector<double>(),
+             "(table (n, 4): q, T, k, t; status (n,)) of the test x_g = x0_g on groups of slots (include/jaicov_parameters.h)")
         .def("useCentroidedCoordinates", &BundleAdjustment::useCentroidedCoordinates)
         .def("centroidCoordinates", &BundleAdjustment::centroidCoordinates)
         .def("applyAposterioriVarianceOfUnitWeight", &BundleAdjustment::applyAposterioriVarianceOfUnitWeight)

@@ -564,6 +564,59 @@ BundleAdjustment::PrincipalComponents BundleAdjustment::principalComponents(int 
     return c;
 }
 
+// include/jaicov_parameters.h on the engine of the last estimateModel
+BundleAdjustment::ParameterCorrelations BundleAdjustment::parameterCorrelations(uint32_t pairMask, uint32_t flags) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    ParameterCorrelations c;
+    const int n = jaicov_neq_cofactor_order(engine_);
+    c.rho.resize((size_t)std::max(n, 1)); c.partner.resize(c.rho.size()); c.status.resize(c.rho.size());
+    const int rc = jaicov_par_maxima(engine_, pairMask, flags, c.rho.data(), c.partner.data(), c.status.data(), n);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_par_maxima: ") + jaicov_neq_last_error(engine_));
+    c.rho.resize((size_t)std::max(n, 0)); c.partner.resize(c.rho.size()); c.status.resize(c.rho.size());
+    return c;
+}
+
+BundleAdjustment::CorrelatedPairs BundleAdjustment::correlatedPairs(double threshold, uint32_t pairMask, uint32_t flags, int64_t capacity) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    CorrelatedPairs p;
+    const size_t cap = (size_t)std::max<int64_t>(capacity, 0);
+    p.cols.resize(2 * cap + 2); p.rho.resize(cap + 1);
+    const int rc = jaicov_par_pairs(engine_, pairMask, flags, threshold, capacity, p.cols.data(), p.rho.data(), &p.count);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_par_pairs: ") + jaicov_neq_last_error(engine_));
+    const size_t m = p.count > capacity ? 0 : (size_t)p.count;
+    p.cols.resize(2 * m); p.rho.resize(m);
+    return p;
+}
+
+std::vector<double> BundleAdjustment::correlationBlock(const std::vector<int32_t> &rowCols, const std::vector<int32_t> &colCols) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    std::vector<double> out(std::max<size_t>(rowCols.size() * colCols.size(), 1));
+    int32_t none = 0;
+    const int rc = jaicov_par_block(engine_, rowCols.empty() ? &none : rowCols.data(), (int32_t)rowCols.size(),
+                                    colCols.empty() ? &none : colCols.data(), (int32_t)colCols.size(), out.data());
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_par_block: ") + jaicov_neq_last_error(engine_));
+    out.resize(rowCols.size() * colCols.size());
+    return out;
+}
+
+BundleAdjustment::ParameterTests BundleAdjustment::testParameters(double sigma2, const std::vector<int32_t> &groupBegin,
+                                                                  const std::vector<int32_t> &groupSlot, const std::vector<double> &x0) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    if (groupBegin.empty() || groupBegin.back() != (int32_t)groupSlot.size() || (!x0.empty() && x0.size() != groupSlot.size()))
+        throw std::runtime_error("testParameters: groupBegin must end at groupSlot.size(), x0 must be empty or parallel to groupSlot");
+    ParameterTests t;
+    const size_t n = groupBegin.size() - 1;
+    t.table.resize(std::max<size_t>(n, 1) * JAICOV_PAR_TEST_COLUMNS);
+    t.status.resize(std::max<size_t>(n, 1));
+    int32_t none = 0;
+    const int rc = jaicov_par_tests(engine_, sigma2, groupBegin.data(), groupSlot.empty() ? &none : groupSlot.data(), x0.empty() ? nullptr : x0.data(),
+                                    (int32_t)n, t.table.data(), t.status.data());
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_par_tests: ") + jaicov_neq_last_error(engine_));
+    t.table.resize(n * JAICOV_PAR_TEST_COLUMNS);
+    t.status.resize(n);
+    return t;
+}
+
 // CTEO:49-121: rows, coordinates and sigma2 J Qxx J' on the device (jaicov_xform_run), the results copied back
 void CoordinateTransformationExteriorOrientation::transform(const std::vector<ObjectCoordinate *> &objectCoordinatesToTransform,
                                                             const std::vector<std::pair<Image *, std::vector<Image *>>> &imagesToAlign,

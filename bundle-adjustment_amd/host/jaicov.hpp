@@ -38,6 +38,7 @@
 #include "../../include/jaicov_reliability_points.h"
 #include "../../include/jaicov_datum.h"
 #include "../../include/jaicov_precision.h"
+#include "../../include/jaicov_parameters.h"
 
 namespace jaicov::host {
 
@@ -559,6 +560,29 @@ public:
         bool converged = false;
     };
     PrincipalComponents principalComponents(int firstCol, int nCols, int k, double tol = 0.0, int maxIterations = 200) const;
+    // Correlations and significance tests of the unknowns, read on the device from the cofactor matrix of the last estimateModel
+    // (include/jaicov_parameters.h; after transformDatum they speak of the new datum).  Columns are those of the cofactor matrix,
+    // slots those of the flat problem; pairMask bit 4 a + b: a column of class a considers partners of class b (JAICOV_PAR_CLASS_*).
+    struct ParameterCorrelations {
+        std::vector<double> rho;                 // one entry per column: the coefficient with its worst partner (NaN: none)
+        std::vector<int32_t> partner, status;    // -1: none; JAICOV_PAR_NONPOSITIVE / _NOT_FINITE
+    };
+    ParameterCorrelations parameterCorrelations(uint32_t pairMask = 0xFFFF, uint32_t flags = 0) const;
+    struct CorrelatedPairs {
+        int64_t count = 0;                       // always exact; cols and rho are empty when it exceeds the capacity
+        std::vector<int32_t> cols;               // i, j (i > j) of every pair, sorted by |rho| descending, then i, then j
+        std::vector<double> rho;
+    };
+    CorrelatedPairs correlatedPairs(double threshold, uint32_t pairMask = 0xFFFF, uint32_t flags = 0, int64_t capacity = 1 << 16) const;
+    // rho between every column of rowCols and every column of colCols, row-major rowCols.size() x colCols.size()
+    std::vector<double> correlationBlock(const std::vector<int32_t> &rowCols, const std::vector<int32_t> &colCols) const;
+    // test of x_g = x0_g: group g has the slots groupSlot[groupBegin[g] .. groupBegin[g + 1]); x0 empty = zeros
+    struct ParameterTests {
+        std::vector<double> table;               // rows of q, T = q / (k sigma2), k, t (JAICOV_PAR_TEST_COLUMNS)
+        std::vector<int32_t> status;             // JAICOV_PAR_* bits of every group
+    };
+    ParameterTests testParameters(double sigma2, const std::vector<int32_t> &groupBegin, const std::vector<int32_t> &groupSlot,
+                                  const std::vector<double> &x0 = {}) const;
     const std::string &lastError() const { return lastError_; }
     jaicov_engine *nativeEngine() const { return engine_; }     // the engine of the last estimateModel (null before)
 
