@@ -22,7 +22,6 @@
 
 #include "../../include/jaicov_dlt.h"
 #include "batchcall.h"
-#include "devbuf.h"
 #include "dlt.h"
 
 #pragma clang fp contract(off)
@@ -540,38 +539,19 @@ extern "C" int jaicov_dlt_adjust(int32_t n_images, const int32_t *obs_begin, con
     if (ms_out) *ms_out = 0.0;
     if (n_images == 0) return JAICOV_OK;
 
-    DevStream stream;                  // first, so that the other owners go before the stream does
-    if (stream.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-    const hipStream_t s = stream.get();
-    int32_t *d_begin = nullptr, *d_status = nullptr, *d_solves = nullptr;
-    double *d_xy = nullptr, *d_xyz = nullptr, *d_io = nullptr, *d_out = nullptr;
-    uint8_t *d_fixed = nullptr;
-    DevBag bag;
-    DevEvent ev0, ev1;
-    if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
-    const size_t ni = (size_t)n_images, no = (size_t)(n_obs > 0 ? n_obs : 1);
-    if (bag.alloc(&d_begin, ni + 1) != hipSuccess || bag.alloc(&d_xy, 2 * no) != hipSuccess || bag.alloc(&d_xyz, 3 * no) != hipSuccess ||
-        bag.alloc(&d_io, 3 * ni) != hipSuccess || (io_fixed && bag.alloc(&d_fixed, 3 * ni) != hipSuccess) ||
-        bag.alloc(&d_out, JAICOV_DLT_OUT_PER_IMAGE * ni) != hipSuccess || bag.alloc(&d_status, ni) != hipSuccess ||
-        (solves && bag.alloc(&d_solves, ni) != hipSuccess))
-        return JAICOV_ERR_OUT_OF_MEMORY;
-    hipMemcpyAsync(d_begin, obs_begin, (ni + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    if (n_obs > 0) {
-        hipMemcpyAsync(d_xy, xy, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-        hipMemcpyAsync(d_xyz, xyz, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-    }
-    hipMemcpyAsync(d_io, io, 3 * ni * sizeof(double), hipMemcpyHostToDevice, s);
-    if (io_fixed) hipMemcpyAsync(d_fixed, io_fixed, 3 * ni, hipMemcpyHostToDevice, s);
-    hipEventRecord(e0, s);
-    hipLaunchKernelGGL(dlt_adjust_kernel, dim3(n_images), dim3(64), 0, s, d_begin, d_xy, d_xyz, d_io, d_fixed, rs, (int)max_iterations,
-                       d_out, d_status, d_solves);
-    if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
-    hipEventRecord(e1, s);
-    hipMemcpyAsync(out, d_out, JAICOV_DLT_OUT_PER_IMAGE * ni * sizeof(double), hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(status, d_status, ni * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (solves) hipMemcpyAsync(solves, d_solves, ni * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
-    if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-    return JAICOV_OK;
+    BatchCall call;
+    const size_t ni = (size_t)n_images, no = (size_t)n_obs;
+    const int32_t *d_begin = call.in(obs_begin, ni + 1);
+    const double *d_xy = call.in(xy, 2 * no), *d_xyz = call.in(xyz, 3 * no), *d_io = call.in(io, 3 * ni);
+    const uint8_t *d_fixed = call.in(io_fixed, 3 * ni);
+    double *d_out = call.alloc<double>(JAICOV_DLT_OUT_PER_IMAGE * ni);
+    int32_t *d_status = call.alloc<int32_t>(ni), *d_solves = solves ? call.alloc<int32_t>(ni) : nullptr;
+    call.run([&](hipStream_t s) {
+        hipLaunchKernelGGL(dlt_adjust_kernel, dim3(n_images), dim3(64), 0, s, d_begin, d_xy, d_xyz, d_io, d_fixed, rs, (int)max_iterations,
+                           d_out, d_status, d_solves);
+    });
+    call.out(out, d_out, JAICOV_DLT_OUT_PER_IMAGE * ni);
+    call.out(status, d_status, ni);
+    call.out(solves, d_solves, ni);
+    return call.finish(ms_out);
 }

@@ -25,7 +25,6 @@
 
 #include "../../include/jaicov_intersect.h"
 #include "batchcall.h"
-#include "devbuf.h"
 #include "intersect.h"
 #include "wavealg.h"
 
@@ -47,9 +46,7 @@ __global__ void isect_image_kernel(int n_images, const double *__restrict__ io, 
     const double omega = eo[6L * i + 3], phi = eo[6L * i + 4], kappa = eo[6L * i + 5];
     const double co = cos(omega), so = sin(omega), cp = cos(phi), sp = sin(phi), ck = cos(kappa), sk = sin(kappa);
     IsectImage m;
-    m.r[0] = cp * ck;                 m.r[1] = -cp * sk;                m.r[2] = sp;              // PDF:125-135
-    m.r[3] = co * sk + so * sp * ck;  m.r[4] = co * ck - so * sp * sk;  m.r[5] = -so * cp;
-    m.r[6] = so * sk - co * sp * ck;  m.r[7] = so * ck + co * sp * sk;  m.r[8] = co * cp;
+    rotation_opk(so, co, sk, ck, sp, cp, m.r);
     for (int k = 0; k < 3; k++) m.X0[k] = eo[6L * i + k];
     m.x0 = io[3L * i]; m.y0 = io[3L * i + 1]; m.c = io[3L * i + 2];
     rec[i] = m;
@@ -139,16 +136,9 @@ __global__ __launch_bounds__(64) void isect_points_kernel(const int32_t *__restr
     const int m = ray_begin[p + 1] - ray_begin[p];
     double *op = out + (long)JAICOV_ISECT_OUT_PER_POINT * p;
     int iters = 0;
-    // a failed point: NaN in the values and in q, no ray used (Q3).  Taken by the whole wave.
-    auto fail = [&](int st) {
-        if (lane < JAICOV_ISECT_OUT_PER_POINT) op[lane] = NAN;
-        if (lane == 0) { outcome[2L * p] = st; outcome[2L * p + 1] = iters; }       // status, Gauss-Newton solves
-        for (int t = lane; t < m; t += 64) {
-            used[k0 + t] = 0;
-            if (ray_q) ray_q[k0 + t] = NAN;
-        }
-    };
-    if (m < 2) { fail(JAICOV_ISECT_TOO_FEW_RAYS); return; }
+    // this point has failed (Q3): wave_fail_item with the point's own arguments, for the four places that give up
+    auto give_up = [&](int st) { wave_fail_item<2>(lane, op, JAICOV_ISECT_OUT_PER_POINT, outcome, p, st, iters, k0, m, used, ray_q); };
+    if (m < 2) { give_up(JAICOV_ISECT_TOO_FEW_RAYS); return; }
     const bool resident = m <= ISECT_CHUNK;
     // rays c0 .. c0 + nc - 1 into LDS, with their weights (PDF:308-319)
     auto stage = [&](int c0, int nc) {
@@ -211,7 +201,7 @@ __global__ __launch_bounds__(64) void isect_points_kernel(const int32_t *__restr
             double dx[3];
             int ss = isect_solve3(acc, acc + 6, dx, nullptr);
             if (ss == JAICOV_ISECT_OK && !(isfinite(dx[0]) && isfinite(dx[1]) && isfinite(dx[2]))) ss = JAICOV_ISECT_NOT_FINITE;
-            if (ss != JAICOV_ISECT_OK) { if (mode == ISECT_STEP) iters++; fail(ss); return; }
+            if (ss != JAICOV_ISECT_OK) { if (mode == ISECT_STEP) iters++; give_up(ss); return; }
             for (int k = 0; k < 3; k++) Xr[k] += dx[k];          // START: Xr was 0
             if (mode == ISECT_START) { mode = ISECT_STEP; it = 0; st = JAICOV_ISECT_NOT_CONVERGED; continue; }
             iters++;
@@ -227,7 +217,7 @@ __global__ __launch_bounds__(64) void isect_points_kernel(const int32_t *__restr
             for (int k = 0; k < 6; k++) finite = finite && isfinite(Q[k]);
             if (!finite) se = JAICOV_ISECT_NOT_FINITE;
         }
-        if (se != JAICOV_ISECT_OK) { fail(se); return; }
+        if (se != JAICOV_ISECT_OK) { give_up(se); return; }
         if (!(thr2 > 0.0 && nused > min_rays && qmax > thr2 && qidx < m)) break;
         if (lane == 0) { used[k0 + qidx] = 0; if (resident) sused[qidx] = 0; }
         nused--;
@@ -269,7 +259,7 @@ __global__ __launch_bounds__(64) void isect_points_kernel(const int32_t *__restr
     o[10] = angle;
     bool finite = true;
     for (int k = 0; k < JAICOV_ISECT_OUT_PER_POINT; k++) finite = finite && isfinite(o[k]);
-    if (!finite) { fail(JAICOV_ISECT_NOT_FINITE); return; }
+    if (!finite) { give_up(JAICOV_ISECT_NOT_FINITE); return; }
     if (lane == 0) {
         for (int k = 0; k < JAICOV_ISECT_OUT_PER_POINT; k++) op[k] = o[k];
         outcome[2L * p] = st;
@@ -302,51 +292,23 @@ extern "C" int jaicov_isect_points(int32_t n_points, const int32_t *ray_begin, c
     if (ms_out) *ms_out = 0.0;
     if (n_points == 0) return JAICOV_OK;
 
-    DevStream stream;                  // first, so that the other owners go before the stream does
-    if (stream.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-    const hipStream_t s = stream.get();
-    int32_t *d_begin = nullptr, *d_image = nullptr, *d_outcome = nullptr;
-    double *d_xy = nullptr, *d_var = nullptr, *d_io = nullptr, *d_eo = nullptr, *d_out = nullptr, *d_q = nullptr;
-    uint8_t *d_used = nullptr;
-    IsectImage *d_rec = nullptr;
-    DevBag bag;
-    DevEvent ev0, ev1;
-    if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
-    const size_t np = (size_t)n_points, nr = (size_t)(n_rays > 0 ? n_rays : 1), ni = (size_t)(n_images > 0 ? n_images : 1);
-    std::vector<int32_t> h_outcome(2 * np);
-    if (bag.alloc(&d_begin, np + 1) != hipSuccess || bag.alloc(&d_image, nr) != hipSuccess || bag.alloc(&d_xy, 2 * nr) != hipSuccess ||
-        (var && bag.alloc(&d_var, 3 * nr) != hipSuccess) || bag.alloc(&d_io, 3 * ni) != hipSuccess || bag.alloc(&d_eo, 6 * ni) != hipSuccess ||
-        bag.alloc(&d_rec, ni) != hipSuccess || bag.alloc(&d_out, JAICOV_ISECT_OUT_PER_POINT * np) != hipSuccess ||
-        bag.alloc(&d_outcome, 2 * np) != hipSuccess || bag.alloc(&d_used, nr) != hipSuccess || (ray_q && bag.alloc(&d_q, nr) != hipSuccess))
-        return JAICOV_ERR_OUT_OF_MEMORY;
-    hipMemcpyAsync(d_begin, ray_begin, (np + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    if (n_rays > 0) {
-        hipMemcpyAsync(d_image, ray_image, (size_t)n_rays * sizeof(int32_t), hipMemcpyHostToDevice, s);
-        hipMemcpyAsync(d_xy, xy, 2 * (size_t)n_rays * sizeof(double), hipMemcpyHostToDevice, s);
-        if (var) hipMemcpyAsync(d_var, var, 3 * (size_t)n_rays * sizeof(double), hipMemcpyHostToDevice, s);
-    }
-    if (n_images > 0) {
-        hipMemcpyAsync(d_io, image_io, 3 * (size_t)n_images * sizeof(double), hipMemcpyHostToDevice, s);
-        hipMemcpyAsync(d_eo, image_eo, 6 * (size_t)n_images * sizeof(double), hipMemcpyHostToDevice, s);
-    }
-    hipMemsetAsync(d_used, 1, nr, s);                                  // every ray starts as used
-    hipEventRecord(e0, s);
-    if (n_images > 0)
-        hipLaunchKernelGGL(isect_image_kernel, dim3((n_images + 255) / 256), dim3(256), 0, s, (int)n_images, d_io, d_eo, d_rec);
-    hipLaunchKernelGGL(isect_points_kernel, dim3(n_points), dim3(64), 0, s, d_begin, d_image, d_xy, d_var, d_rec, sigma2apriori,
-                       (int)max_iterations, reject_threshold * reject_threshold, (int)min_rays, d_out, d_outcome, d_used, d_q);
-    if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
-    hipEventRecord(e1, s);
-    hipMemcpyAsync(out, d_out, JAICOV_ISECT_OUT_PER_POINT * np * sizeof(double), hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(h_outcome.data(), d_outcome, 2 * np * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (ray_used && n_rays > 0) hipMemcpyAsync(ray_used, d_used, (size_t)n_rays, hipMemcpyDeviceToHost, s);
-    if (ray_q && n_rays > 0) hipMemcpyAsync(ray_q, d_q, (size_t)n_rays * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
-    for (size_t p = 0; p < np; p++) {
-        status[p] = h_outcome[2 * p];
-        if (iterations) iterations[p] = h_outcome[2 * p + 1];
-    }
-    if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-    return JAICOV_OK;
+    BatchCall call;
+    const size_t np = (size_t)n_points, nr = (size_t)n_rays, ni = (size_t)n_images;
+    const int32_t *d_begin = call.in(ray_begin, np + 1), *d_image = call.in(ray_image, nr);
+    const double *d_xy = call.in(xy, 2 * nr), *d_var = call.in(var, 3 * nr), *d_io = call.in(image_io, 3 * ni), *d_eo = call.in(image_eo, 6 * ni);
+    IsectImage *d_rec = call.alloc<IsectImage>(ni);
+    double *d_out = call.alloc<double>(JAICOV_ISECT_OUT_PER_POINT * np), *d_q = ray_q ? call.alloc<double>(nr) : nullptr;
+    int32_t *d_outcome = call.alloc<int32_t>(2 * np);
+    uint8_t *d_used = call.filled<uint8_t>(nr, 1);                     // every ray starts as used
+    call.run([&](hipStream_t s) {
+        if (n_images > 0)
+            hipLaunchKernelGGL(isect_image_kernel, dim3((n_images + 255) / 256), dim3(256), 0, s, (int)n_images, d_io, d_eo, d_rec);
+        hipLaunchKernelGGL(isect_points_kernel, dim3(n_points), dim3(64), 0, s, d_begin, d_image, d_xy, d_var, d_rec, sigma2apriori,
+                           (int)max_iterations, reject_threshold * reject_threshold, (int)min_rays, d_out, d_outcome, d_used, d_q);
+    });
+    call.out(out, d_out, JAICOV_ISECT_OUT_PER_POINT * np);
+    call.outcomes(d_outcome, np, 2, status, iterations, nullptr);
+    call.out(ray_used, d_used, nr);
+    call.out(ray_q, d_q, nr);
+    return call.finish(ms_out);
 }

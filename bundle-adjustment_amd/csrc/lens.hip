@@ -20,7 +20,6 @@
 
 #include "../../include/jaicov_lens.h"
 #include "batchcall.h"
-#include "devbuf.h"
 
 #pragma clang fp contract(off)
 
@@ -336,50 +335,29 @@ int lens_run(int32_t n_points, const int32_t *pt_camera, const double *xy, const
     if (ms_out) *ms_out = 0.0;
     if (n_points == 0) return JAICOV_OK;
 
-    DevStream stream;                  // first, so that the other owners go before the stream does
-    if (stream.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-    const hipStream_t s = stream.get();
-    DevBag bag;
-    DevEvent ev0, ev1;
-    if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
-    const size_t np = (size_t)n_points, nc = t.cams.size(), nd = t.coef.size(), nz = t.zt_p.size();
-    int32_t *d_cam = nullptr, *d_ztp = nullptr, *d_status = nullptr, *d_it = nullptr;
-    double *d_xy = nullptr, *d_var = nullptr, *d_depth = nullptr, *d_ztc = nullptr, *d_xyo = nullptr, *d_varo = nullptr, *d_jac = nullptr;
-    LensCam *d_cams = nullptr;
-    LensCoef *d_coef = nullptr;
-    const bool want_it = CORRECT && iterations;
-    if (bag.alloc(&d_cam, np) != hipSuccess || bag.alloc(&d_xy, 2 * np) != hipSuccess || (var && var_out && bag.alloc(&d_var, 3 * np) != hipSuccess) ||
-        (depth && bag.alloc(&d_depth, np) != hipSuccess) || bag.alloc(&d_cams, nc) != hipSuccess || bag.alloc(&d_coef, nd) != hipSuccess ||
-        bag.alloc(&d_ztp, nz) != hipSuccess || bag.alloc(&d_ztc, nz) != hipSuccess || bag.alloc(&d_xyo, 2 * np) != hipSuccess ||
-        (var_out && bag.alloc(&d_varo, 3 * np) != hipSuccess) || (jac_out && bag.alloc(&d_jac, 4 * np) != hipSuccess) ||
-        bag.alloc(&d_status, np) != hipSuccess || (want_it && bag.alloc(&d_it, np) != hipSuccess))
-        return JAICOV_ERR_OUT_OF_MEMORY;
-    hipMemcpyAsync(d_cam, pt_camera, np * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    hipMemcpyAsync(d_xy, xy, 2 * np * sizeof(double), hipMemcpyHostToDevice, s);
-    if (d_var) hipMemcpyAsync(d_var, var, 3 * np * sizeof(double), hipMemcpyHostToDevice, s);
-    if (d_depth) hipMemcpyAsync(d_depth, depth, np * sizeof(double), hipMemcpyHostToDevice, s);
-    if (nc) hipMemcpyAsync(d_cams, t.cams.data(), nc * sizeof(LensCam), hipMemcpyHostToDevice, s);
-    if (nd) hipMemcpyAsync(d_coef, t.coef.data(), nd * sizeof(LensCoef), hipMemcpyHostToDevice, s);
-    if (nz) {
-        hipMemcpyAsync(d_ztp, t.zt_p.data(), nz * sizeof(int32_t), hipMemcpyHostToDevice, s);
-        hipMemcpyAsync(d_ztc, t.zt_c.data(), nz * sizeof(double), hipMemcpyHostToDevice, s);
-    }
+    BatchCall call;
+    const size_t np = (size_t)n_points;
+    const int32_t *d_cam = call.in(pt_camera, np);
+    const double *d_xy = call.in(xy, 2 * np), *d_var = call.in(var_out ? var : nullptr, 3 * np), *d_depth = call.in(depth, np);
+    const LensCam *d_cams = call.in(t.cams);
+    const LensCoef *d_coef = call.in(t.coef);
+    const int32_t *d_ztp = call.in(t.zt_p);
+    const double *d_ztc = call.in(t.zt_c);
+    double *d_xyo = call.alloc<double>(2 * np), *d_varo = var_out ? call.alloc<double>(3 * np) : nullptr,
+           *d_jac = jac_out ? call.alloc<double>(4 * np) : nullptr;
+    int32_t *d_status = call.alloc<int32_t>(np), *d_it = iterations ? call.alloc<int32_t>(np) : nullptr;   // lens_distort passes none
     const double tol = tolerance > 0.0 ? tolerance : sqrt(ldexp(1.0, -53));
-    hipEventRecord(e0, s);
-    hipLaunchKernelGGL(lens_points_kernel<CORRECT>, dim3((unsigned)((np + LENS_THREADS - 1) / LENS_THREADS)), dim3(LENS_THREADS), 0, s,
-                       (long)n_points, d_cam, d_xy, d_var, d_depth, d_cams, d_coef, d_ztp, d_ztc, (int)max_iterations, tol, d_xyo, d_varo,
-                       d_jac, d_status, d_it);
-    if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
-    hipEventRecord(e1, s);
-    hipMemcpyAsync(xy_out, d_xyo, 2 * np * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (var_out) hipMemcpyAsync(var_out, d_varo, 3 * np * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (jac_out) hipMemcpyAsync(jac_out, d_jac, 4 * np * sizeof(double), hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(status, d_status, np * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (want_it) hipMemcpyAsync(iterations, d_it, np * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
-    if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-    return JAICOV_OK;
+    call.run([&](hipStream_t s) {
+        hipLaunchKernelGGL(lens_points_kernel<CORRECT>, dim3((unsigned)((np + LENS_THREADS - 1) / LENS_THREADS)), dim3(LENS_THREADS), 0, s,
+                           (long)n_points, d_cam, d_xy, d_var, d_depth, d_cams, d_coef, d_ztp, d_ztc, (int)max_iterations, tol, d_xyo, d_varo,
+                           d_jac, d_status, d_it);
+    });
+    call.out(xy_out, d_xyo, 2 * np);
+    call.out(var_out, d_varo, 3 * np);
+    call.out(jac_out, d_jac, 4 * np);
+    call.out(status, d_status, np);
+    call.out(iterations, d_it, np);
+    return call.finish(ms_out);
 }
 
 }  // namespace

@@ -27,7 +27,6 @@
 
 #include "../../include/jaicov_relorient.h"
 #include "batchcall.h"
-#include "devbuf.h"
 #include "relorient.h"
 #include "wavealg.h"
 
@@ -115,15 +114,6 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
     __shared__ int sI[14];
     int &iters = sI[0];
     iters = 0;
-    // a failed pair: NaN in the values and in q, no observation used, start kind 0.  Taken by the whole wave.
-    auto fail = [&](int st) {
-        if (lane < JAICOV_RELOR_OUT_PER_PAIR) og[lane] = NAN;
-        if (lane == 0) { outcome[3L * g] = st; outcome[3L * g + 1] = iters; outcome[3L * g + 2] = 0; }
-        for (int t = lane; t < m; t += 64) {
-            used[k0 + t] = 0;
-            if (obs_q) obs_q[k0 + t] = NAN;
-        }
-    };
     const double *io = pair_io + 6L * g;                   // x0, y0, c of a, then of b: read where they are used, not held
     bool given = start != nullptr;
 #pragma unroll
@@ -297,15 +287,9 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
     while (wave_uniform(failed < 0)) {
         mode = wave_uniform(mode);
         if (wave_uniform(new_state != 0)) {
-            // R(omega, phi, kappa), PDF:125-135: lanes 0, 1, 2 take the sine and cosine of one angle each (one copy of sincos)
-            const double angle = lane == 0 ? sP[RO_PAR + 3] : lane == 1 ? sP[RO_PAR + 4] : sP[RO_PAR + 5];
-            double sn, cs;
-            sincos(angle, &sn, &cs);
-            const double so = __shfl(sn, 0), co = __shfl(cs, 0), sp = __shfl(sn, 1), cp = __shfl(cs, 1), sk = __shfl(sn, 2), ck = __shfl(cs, 2);
-            double *R = sP + RO_R;
-            R[0] = cp * ck;                 R[1] = -cp * sk;                R[2] = sp;
-            R[3] = co * sk + so * sp * ck;  R[4] = co * ck - so * sp * sk;  R[5] = -so * cp;
-            R[6] = so * sk - co * sp * ck;  R[7] = so * ck + co * sp * sk;  R[8] = co * cp;
+            double so, co, sp, cp, sk, ck;
+            wave_sincos3(lane, sP[RO_PAR + 3], sP[RO_PAR + 4], sP[RO_PAR + 5], so, co, sp, cp, sk, ck);
+            rotation_opk(so, co, sk, ck, sp, cp, sP + RO_R);
             sP[RO_SO] = so; sP[RO_CO] = co;
             // the tangent basis at b
             const double b[3] = {sP[RO_PAR], sP[RO_PAR + 1], sP[RO_PAR + 2]};
@@ -455,14 +439,11 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
             nstarts = wave_uniform(nstarts); picks = wave_uniform(picks); kinds = wave_uniform(kinds);
 #pragma unroll 1
             for (int j = 0; j < wave_uniform(nstarts); j++) {
-                // b and the angles of R = M' (omega by lane 0, kappa by lane 1: one copy of atan2)
+                // b and the angles of R = M': r23 = M[2][1], r33 = M[2][2], r12 = M[1][0], r11 = M[0][0], r13 = M[2][0]
                 const double *M = sC + RELOR_SLOT_LEN * ((picks >> (4 * j)) & 15);
-                const double a = atan2(lane == 0 ? -M[7] : -M[3], lane == 0 ? M[8] : M[0]);
                 double *par = sS + 6 * j;
                 par[0] = M[9]; par[1] = M[10]; par[2] = M[11];
-                par[3] = __shfl(a, 0);
-                par[4] = asin(fmin(1.0, fmax(-1.0, M[6])));
-                par[5] = __shfl(a, 1);
+                wave_angles(lane, M[7], M[8], M[3], M[0], M[6], par + 3);
             }
 #pragma unroll
             for (int k = 0; k < 6; k++) sP[RO_PAR + k] = sS[k];
@@ -570,7 +551,10 @@ __global__ __launch_bounds__(RELOR_LANES) void relorient_pairs_kernel(const int3
         for (int k = 0; k < JAICOV_RELOR_OUT_PER_PAIR; k++) z += o[k] * 0.0;
         if (wave_uniform(failed < 0 && z != 0.0)) failed = JAICOV_RELOR_NOT_FINITE;
     }
-    if (wave_uniform(failed >= 0)) { fail(wave_uniform(failed)); return; }
+    if (wave_uniform(failed >= 0)) {                      // start kind 0
+        wave_fail_item<3>(lane, og, JAICOV_RELOR_OUT_PER_PAIR, outcome, g, wave_uniform(failed), iters, k0, m, used, obs_q);
+        return;
+    }
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < JAICOV_RELOR_OUT_PER_PAIR; k++) og[k] = o[k];
@@ -602,51 +586,22 @@ extern "C" int jaicov_relorient_pairs(int32_t n_pairs, const int32_t *obs_begin,
     if (ms_out) *ms_out = 0.0;
     if (n_pairs == 0) return JAICOV_OK;
 
-    DevStream stream;                  // first, so that the other owners go before the stream does
-    if (stream.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-    const hipStream_t s = stream.get();
-    int32_t *d_begin = nullptr, *d_outcome = nullptr;
-    double *d_xa = nullptr, *d_xb = nullptr, *d_va = nullptr, *d_vb = nullptr, *d_io = nullptr, *d_start = nullptr, *d_out = nullptr,
-           *d_q = nullptr;
-    uint8_t *d_used = nullptr;
-    DevBag bag;
-    DevEvent ev0, ev1;
-    if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
-    const size_t np = (size_t)n_pairs, no = (size_t)(n_obs > 0 ? n_obs : 1);
-    std::vector<int32_t> h_outcome(3 * np);
-    if (bag.alloc(&d_begin, np + 1) != hipSuccess || bag.alloc(&d_xa, 2 * no) != hipSuccess || bag.alloc(&d_xb, 2 * no) != hipSuccess ||
-        (var_a && bag.alloc(&d_va, 3 * no) != hipSuccess) || (var_b && bag.alloc(&d_vb, 3 * no) != hipSuccess) ||
-        bag.alloc(&d_io, 6 * np) != hipSuccess || (start && bag.alloc(&d_start, 6 * np) != hipSuccess) ||
-        bag.alloc(&d_out, JAICOV_RELOR_OUT_PER_PAIR * np) != hipSuccess || bag.alloc(&d_outcome, 3 * np) != hipSuccess ||
-        bag.alloc(&d_used, no) != hipSuccess || (obs_q && bag.alloc(&d_q, no) != hipSuccess))
-        return JAICOV_ERR_OUT_OF_MEMORY;
-    hipMemcpyAsync(d_begin, obs_begin, (np + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    if (n_obs > 0) {
-        hipMemcpyAsync(d_xa, xy_a, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-        hipMemcpyAsync(d_xb, xy_b, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-        if (var_a) hipMemcpyAsync(d_va, var_a, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-        if (var_b) hipMemcpyAsync(d_vb, var_b, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-    }
-    hipMemcpyAsync(d_io, pair_io, 6 * np * sizeof(double), hipMemcpyHostToDevice, s);
-    if (start) hipMemcpyAsync(d_start, start, 6 * np * sizeof(double), hipMemcpyHostToDevice, s);
-    hipMemsetAsync(d_used, 1, no, s);                                  // every observation starts as used
-    hipEventRecord(e0, s);
-    hipLaunchKernelGGL(relorient_pairs_kernel, dim3(n_pairs), dim3(RELOR_LANES), 0, s, d_begin, d_xa, d_xb, d_va, d_vb, d_io, d_start,
-                       sigma2apriori, (int)max_iterations, reject_threshold * reject_threshold, (int)min_points, d_out, d_outcome, d_used,
-                       d_q);
-    if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
-    hipEventRecord(e1, s);
-    hipMemcpyAsync(out, d_out, JAICOV_RELOR_OUT_PER_PAIR * np * sizeof(double), hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(h_outcome.data(), d_outcome, 3 * np * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (obs_used && n_obs > 0) hipMemcpyAsync(obs_used, d_used, (size_t)n_obs, hipMemcpyDeviceToHost, s);
-    if (obs_q && n_obs > 0) hipMemcpyAsync(obs_q, d_q, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
-    for (size_t g = 0; g < np; g++) {
-        status[g] = h_outcome[3 * g];
-        if (iterations) iterations[g] = h_outcome[3 * g + 1];
-        if (start_kind) start_kind[g] = h_outcome[3 * g + 2];
-    }
-    if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-    return JAICOV_OK;
+    BatchCall call;
+    const size_t np = (size_t)n_pairs, no = (size_t)n_obs;
+    const int32_t *d_begin = call.in(obs_begin, np + 1);
+    const double *d_xa = call.in(xy_a, 2 * no), *d_xb = call.in(xy_b, 2 * no), *d_va = call.in(var_a, 3 * no), *d_vb = call.in(var_b, 3 * no),
+                 *d_io = call.in(pair_io, 6 * np), *d_start = call.in(start, 6 * np);
+    double *d_out = call.alloc<double>(JAICOV_RELOR_OUT_PER_PAIR * np), *d_q = obs_q ? call.alloc<double>(no) : nullptr;
+    int32_t *d_outcome = call.alloc<int32_t>(3 * np);
+    uint8_t *d_used = call.filled<uint8_t>(no, 1);                     // every observation starts as used
+    call.run([&](hipStream_t s) {
+        hipLaunchKernelGGL(relorient_pairs_kernel, dim3(n_pairs), dim3(RELOR_LANES), 0, s, d_begin, d_xa, d_xb, d_va, d_vb, d_io, d_start,
+                           sigma2apriori, (int)max_iterations, reject_threshold * reject_threshold, (int)min_points, d_out, d_outcome, d_used,
+                           d_q);
+    });
+    call.out(out, d_out, JAICOV_RELOR_OUT_PER_PAIR * np);
+    call.outcomes(d_outcome, np, 3, status, iterations, start_kind);
+    call.out(obs_used, d_used, no);
+    call.out(obs_q, d_q, no);
+    return call.finish(ms_out);
 }

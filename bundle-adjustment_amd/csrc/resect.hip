@@ -28,7 +28,6 @@
 
 #include "../../include/jaicov_resect.h"
 #include "batchcall.h"
-#include "devbuf.h"
 #include "resect.h"
 #include "wavealg.h"
 
@@ -68,28 +67,23 @@ __device__ inline void rs_eigen(const double *S, double *E) {
     wave_eigen3<RESECT_JACOBI_SWEEPS>(S, lam, E);
 }
 
-// R(omega, phi, kappa), PDF:125-135, row-major.  Lanes 0, 1, 2 take the sine and cosine of one angle each and hand them to the wave,
-// so that the kernel holds one copy of sincos and of its constants, not three.
+// R(omega, phi, kappa) of the unknowns par, with the sine and cosine of kappa.  Lanes 0, 1, 2 take the sine and cosine of one angle
+// each and hand them to the wave, as wave_sincos3 does; this kernel keeps the lines themselves, in which a lane loads only the angle
+// it works, because its scalar registers grow when all three angles are loaded and passed ("One shell").
 __device__ inline void rs_rotation(int lane, const double *par, double *R, double &sk, double &ck) {
     const double angle = lane == 0 ? par[3] : lane == 1 ? par[4] : par[5];
     double sn, cs;
     sincos(angle, &sn, &cs);
     const double so = __shfl(sn, 0), co = __shfl(cs, 0), sp = __shfl(sn, 1), cp = __shfl(cs, 1);
     sk = __shfl(sn, 2); ck = __shfl(cs, 2);
-    R[0] = cp * ck;                 R[1] = -cp * sk;                R[2] = sp;
-    R[3] = co * sk + so * sp * ck;  R[4] = co * ck - so * sp * sk;  R[5] = -so * cp;
-    R[6] = so * sk - co * sp * ck;  R[7] = so * ck + co * sp * sk;  R[8] = co * cp;
+    rotation_opk(so, co, sk, ck, sp, cp, R);
 }
 
-// the six reduced unknowns of the pose p = M P + t (M row-major): X0 = -R t with R = M', and the angles of R (omega by lane 0, kappa
-// by lane 1: one copy of atan2)
+// the six reduced unknowns of the pose p = M P + t (M row-major): X0 = -R t with R = M', and the angles of R
 __device__ inline void rs_pose(int lane, const double *M, const double *t, double *par) {
 #pragma unroll
     for (int k = 0; k < 3; k++) par[k] = -(M[k] * t[0] + M[3 + k] * t[1] + M[6 + k] * t[2]);
-    const double a = atan2(lane == 0 ? -M[7] : -M[3], lane == 0 ? M[8] : M[0]);   // r23 = M[2][1], r33 = M[2][2]; r12 = M[1][0], r11 = M[0][0]
-    par[3] = __shfl(a, 0);
-    par[4] = asin(fmin(1.0, fmax(-1.0, M[6])));                                   // r13 = M[2][0]
-    par[5] = __shfl(a, 1);
+    wave_angles(lane, M[7], M[8], M[3], M[0], M[6], par + 3);     // r23 = M[2][1], r33 = M[2][2], r12 = M[1][0], r11 = M[0][0], r13 = M[2][0]
 }
 
 // where the state of an image lies in LDS (doubles): every lane stores the same words there and reads them back
@@ -118,15 +112,6 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
     const int m = obs_begin[g + 1] - obs_begin[g];
     double *og = out + (long)JAICOV_RESECT_OUT_PER_IMAGE * g;
     int iters = 0;
-    // a failed image: NaN in the values and in q, no observation used, start kind 0.  Taken by the whole wave.
-    auto fail = [&](int st) {
-        if (lane < JAICOV_RESECT_OUT_PER_IMAGE) og[lane] = NAN;
-        if (lane == 0) { outcome[3L * g] = st; outcome[3L * g + 1] = iters; outcome[3L * g + 2] = 0; }
-        for (int t = lane; t < m; t += 64) {
-            used[k0 + t] = 0;
-            if (obs_q) obs_q[k0 + t] = NAN;
-        }
-    };
     const double x0 = image_io[3L * g], y0 = image_io[3L * g + 1], c = image_io[3L * g + 2];
     bool given = eo_start != nullptr;
 #pragma unroll
@@ -455,7 +440,10 @@ __global__ __launch_bounds__(RESECT_LANES) void resect_images_kernel(const int32
         for (int k = 0; k < JAICOV_RESECT_OUT_PER_IMAGE; k++) z += o[k] * 0.0;
         if (failed < 0 && wave_uniform(z != 0.0)) failed = JAICOV_RESECT_NOT_FINITE;
     }
-    if (failed >= 0) { fail(failed); return; }
+    if (failed >= 0) {                                    // start kind 0
+        wave_fail_item<3>(lane, og, JAICOV_RESECT_OUT_PER_IMAGE, outcome, g, failed, iters, k0, m, used, obs_q);
+        return;
+    }
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < JAICOV_RESECT_OUT_PER_IMAGE; k++) og[k] = o[k];
@@ -487,47 +475,21 @@ extern "C" int jaicov_resect_images(int32_t n_images, const int32_t *obs_begin, 
     if (ms_out) *ms_out = 0.0;
     if (n_images == 0) return JAICOV_OK;
 
-    DevStream stream;                  // first, so that the other owners go before the stream does
-    if (stream.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-    const hipStream_t s = stream.get();
-    int32_t *d_begin = nullptr, *d_outcome = nullptr;
-    double *d_xy = nullptr, *d_xyz = nullptr, *d_var = nullptr, *d_io = nullptr, *d_eo = nullptr, *d_out = nullptr, *d_q = nullptr;
-    uint8_t *d_used = nullptr;
-    DevBag bag;
-    DevEvent ev0, ev1;
-    if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
-    const size_t ni = (size_t)n_images, no = (size_t)(n_obs > 0 ? n_obs : 1);
-    std::vector<int32_t> h_outcome(3 * ni);
-    if (bag.alloc(&d_begin, ni + 1) != hipSuccess || bag.alloc(&d_xy, 2 * no) != hipSuccess || bag.alloc(&d_xyz, 3 * no) != hipSuccess ||
-        (var && bag.alloc(&d_var, 3 * no) != hipSuccess) || bag.alloc(&d_io, 3 * ni) != hipSuccess ||
-        (eo_start && bag.alloc(&d_eo, 6 * ni) != hipSuccess) || bag.alloc(&d_out, JAICOV_RESECT_OUT_PER_IMAGE * ni) != hipSuccess ||
-        bag.alloc(&d_outcome, 3 * ni) != hipSuccess || bag.alloc(&d_used, no) != hipSuccess || (obs_q && bag.alloc(&d_q, no) != hipSuccess))
-        return JAICOV_ERR_OUT_OF_MEMORY;
-    hipMemcpyAsync(d_begin, obs_begin, (ni + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    if (n_obs > 0) {
-        hipMemcpyAsync(d_xy, xy, 2 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-        hipMemcpyAsync(d_xyz, xyz, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-        if (var) hipMemcpyAsync(d_var, var, 3 * (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s);
-    }
-    hipMemcpyAsync(d_io, image_io, 3 * ni * sizeof(double), hipMemcpyHostToDevice, s);
-    if (eo_start) hipMemcpyAsync(d_eo, eo_start, 6 * ni * sizeof(double), hipMemcpyHostToDevice, s);
-    hipMemsetAsync(d_used, 1, no, s);                                  // every observation starts as used
-    hipEventRecord(e0, s);
-    hipLaunchKernelGGL(resect_images_kernel, dim3(n_images), dim3(RESECT_LANES), 0, s, d_begin, d_xy, d_xyz, d_var, d_io, d_eo, sigma2apriori,
-                       (int)max_iterations, reject_threshold * reject_threshold, (int)min_points, d_out, d_outcome, d_used, d_q);
-    if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
-    hipEventRecord(e1, s);
-    hipMemcpyAsync(out, d_out, JAICOV_RESECT_OUT_PER_IMAGE * ni * sizeof(double), hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(h_outcome.data(), d_outcome, 3 * ni * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (obs_used && n_obs > 0) hipMemcpyAsync(obs_used, d_used, (size_t)n_obs, hipMemcpyDeviceToHost, s);
-    if (obs_q && n_obs > 0) hipMemcpyAsync(obs_q, d_q, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
-    for (size_t g = 0; g < ni; g++) {
-        status[g] = h_outcome[3 * g];
-        if (iterations) iterations[g] = h_outcome[3 * g + 1];
-        if (start_kind) start_kind[g] = h_outcome[3 * g + 2];
-    }
-    if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-    return JAICOV_OK;
+    BatchCall call;
+    const size_t ni = (size_t)n_images, no = (size_t)n_obs;
+    const int32_t *d_begin = call.in(obs_begin, ni + 1);
+    const double *d_xy = call.in(xy, 2 * no), *d_xyz = call.in(xyz, 3 * no), *d_var = call.in(var, 3 * no), *d_io = call.in(image_io, 3 * ni),
+                 *d_eo = call.in(eo_start, 6 * ni);
+    double *d_out = call.alloc<double>(JAICOV_RESECT_OUT_PER_IMAGE * ni), *d_q = obs_q ? call.alloc<double>(no) : nullptr;
+    int32_t *d_outcome = call.alloc<int32_t>(3 * ni);
+    uint8_t *d_used = call.filled<uint8_t>(no, 1);                     // every observation starts as used
+    call.run([&](hipStream_t s) {
+        hipLaunchKernelGGL(resect_images_kernel, dim3(n_images), dim3(RESECT_LANES), 0, s, d_begin, d_xy, d_xyz, d_var, d_io, d_eo, sigma2apriori,
+                           (int)max_iterations, reject_threshold * reject_threshold, (int)min_points, d_out, d_outcome, d_used, d_q);
+    });
+    call.out(out, d_out, JAICOV_RESECT_OUT_PER_IMAGE * ni);
+    call.outcomes(d_outcome, ni, 3, status, iterations, start_kind);
+    call.out(obs_used, d_used, no);
+    call.out(obs_q, d_q, no);
+    return call.finish(ms_out);
 }

@@ -25,7 +25,6 @@
 
 #include "../../include/jaicov_simil.h"
 #include "batchcall.h"
-#include "devbuf.h"
 #include "simil.h"
 #include "wavealg.h"
 
@@ -52,13 +51,6 @@ __device__ inline void sm_angle_columns(const double *R, double so, double co, d
     for (int i = 0; i < 3; i++) ak[i] = m * (R[3 * i + 1] * x0 - R[3 * i] * x1);
 }
 
-// R(omega, phi, kappa), PDF:125-135
-__device__ inline void sm_rotation(double so, double co, double sp, double cp, double sk, double ck, double *R) {
-    R[0] = cp * ck;                 R[1] = -cp * sk;                R[2] = sp;
-    R[3] = co * sk + so * sp * ck;  R[4] = co * ck - so * sp * sk;  R[5] = -so * cp;
-    R[6] = so * sk - co * sp * ck;  R[7] = so * ck + co * sp * sk;  R[8] = co * cp;
-}
-
 __global__ __launch_bounds__(SIMIL_LANES) void simil_models_kernel(const int32_t *__restrict__ pt_begin, const double *__restrict__ src,
                                                          const double *__restrict__ dst, const double *__restrict__ cof_src,
                                                          const double *__restrict__ cof_dst, const double *__restrict__ start,
@@ -79,15 +71,6 @@ __global__ __launch_bounds__(SIMIL_LANES) void simil_models_kernel(const int32_t
     double *og = out + (long)JAICOV_SIMIL_OUT_PER_MODEL * g;
     int &iters = sI[0], &nused = sI[1], &kind = sI[2], &cst = sI[3], &it = sI[4], &new_state = sI[5], &centre = sI[6], &failed = sI[7];
     iters = 0; nused = m; kind = JAICOV_SIMIL_START_GIVEN; cst = JAICOV_SIMIL_NOT_CONVERGED; it = 0; new_state = 0; centre = 0;
-    // a failed model: NaN in the values and in q, no point used, start kind 0.  Taken by the whole wave.
-    auto fail = [&](int st) {
-        if (lane < JAICOV_SIMIL_OUT_PER_MODEL) og[lane] = NAN;
-        if (lane == 0) { outcome[3L * g] = st; outcome[3L * g + 1] = iters; outcome[3L * g + 2] = 0; }
-        for (int t = lane; t < m; t += 64) {
-            used[k0 + t] = 0;
-            if (pt_q) pt_q[k0 + t] = NAN;
-        }
-    };
     bool given = start != nullptr;
 #pragma unroll
     for (int k = 0; k < 7; k++) given = given && isfinite(start[7L * g + k]);
@@ -235,13 +218,10 @@ __global__ __launch_bounds__(SIMIL_LANES) void simil_models_kernel(const int32_t
     while (wave_uniform(failed < 0)) {
         mode = wave_uniform(mode);
         if (wave_uniform(new_state != 0)) {
-            // lanes 0, 1, 2 take the sine and cosine of one angle each (one copy of sincos)
-            const double angle = lane == 0 ? sP[SM_ANG] : lane == 1 ? sP[SM_ANG + 1] : sP[SM_ANG + 2];
-            double sn, cs;
-            sincos(angle, &sn, &cs);
-            const double so = __shfl(sn, 0), co = __shfl(cs, 0), sp = __shfl(sn, 1), cp = __shfl(cs, 1), sk = __shfl(sn, 2), ck = __shfl(cs, 2);
+            double so, co, sp, cp, sk, ck;
+            wave_sincos3(lane, sP[SM_ANG], sP[SM_ANG + 1], sP[SM_ANG + 2], so, co, sp, cp, sk, ck);
             double *R = sP + SM_R;
-            sm_rotation(so, co, sp, cp, sk, ck, R);
+            rotation_opk(so, co, sk, ck, sp, cp, R);
             sP[SM_SO] = so; sP[SM_CO] = co;
             if (wave_uniform(centre != 0)) {              // given start values: T_c = T + m R sbar
                 const double *sb = sP + SM_SB;
@@ -321,11 +301,7 @@ __global__ __launch_bounds__(SIMIL_LANES) void simil_models_kernel(const int32_t
 #pragma unroll
                     for (int k = 0; k < 9; k++) tr += R[k] * M[k];
                     const double sc = tr / s2;
-                    // omega by lane 0, kappa by lane 1: one copy of atan2
-                    const double a = atan2(lane == 0 ? -R[5] : -R[1], lane == 0 ? R[8] : R[0]);
-                    sP[SM_ANG] = __shfl(a, 0);
-                    sP[SM_ANG + 1] = asin(fmin(1.0, fmax(-1.0, R[2])));
-                    sP[SM_ANG + 2] = __shfl(a, 1);
+                    wave_angles(lane, R[5], R[8], R[1], R[0], R[2], sP + SM_ANG);
                     sP[SM_M] = sc;
 #pragma unroll
                     for (int i = 0; i < 3; i++) sP[SM_TC + i] = sP[SM_DB + i];
@@ -437,7 +413,10 @@ __global__ __launch_bounds__(SIMIL_LANES) void simil_models_kernel(const int32_t
         for (int k = 0; k < JAICOV_SIMIL_OUT_PER_MODEL; k++) z += o[k] * 0.0;
         if (wave_uniform(failed < 0 && z != 0.0)) failed = JAICOV_SIMIL_NOT_FINITE;
     }
-    if (wave_uniform(failed >= 0)) { fail(wave_uniform(failed)); return; }
+    if (wave_uniform(failed >= 0)) {                      // start kind 0
+        wave_fail_item<3>(lane, og, JAICOV_SIMIL_OUT_PER_MODEL, outcome, g, wave_uniform(failed), iters, k0, m, used, pt_q);
+        return;
+    }
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < JAICOV_SIMIL_OUT_PER_MODEL; k++) og[k] = o[k];
@@ -465,7 +444,7 @@ __global__ __launch_bounds__(SIMIL_APPLY_THREADS) void simil_apply_kernel(long n
         const bool finite = z == 0.0;
         double so, co, sp, cp, sk, ck, R[9];
         sincos(p[4], &so, &co); sincos(p[5], &sp, &cp); sincos(p[6], &sk, &ck);
-        sm_rotation(so, co, sp, cp, sk, ck, R);
+        rotation_opk(so, co, sk, ck, sp, cp, R);
         const double sc = p[3];
         const double *x = point ? xyz + 3 * k : eo + 6 * k;
         double *y = point ? xyz_out + 3 * k : eo_out + 6 * k;
@@ -490,10 +469,10 @@ __global__ __launch_bounds__(SIMIL_APPLY_THREADS) void simil_apply_kernel(long n
                             finite ? m2 * (B[3 * a] * R[3 * b] + B[3 * a + 1] * R[3 * b + 1] + B[3 * a + 2] * R[3 * b + 2]) : NAN;
             }
         } else {
-            double s2, c2, Ri[9], Rn[9];
+            double sk2, ck2, Ri[9], Rn[9];
             const double a0 = x[3], a1 = x[4], a2 = x[5];
-            sincos(a0, &so, &co); sincos(a1, &sp, &cp); sincos(a2, &s2, &c2);
-            sm_rotation(so, co, sp, cp, s2, c2, Ri);
+            sincos(a0, &so, &co); sincos(a1, &sp, &cp); sincos(a2, &sk2, &ck2);
+            rotation_opk(so, co, sk2, ck2, sp, cp, Ri);
 #pragma unroll
             for (int a = 0; a < 3; a++)
 #pragma unroll
@@ -546,49 +525,23 @@ extern "C" int jaicov_simil_models(int32_t n_models, const int32_t *pt_begin, co
     if (ms_out) *ms_out = 0.0;
     if (n_models == 0) return JAICOV_OK;
 
-    DevStream stream;                  // first, so that the other owners go before the stream does
-    if (stream.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-    const hipStream_t s = stream.get();
-    int32_t *d_begin = nullptr, *d_outcome = nullptr;
-    double *d_src = nullptr, *d_dst = nullptr, *d_qs = nullptr, *d_qd = nullptr, *d_start = nullptr, *d_out = nullptr, *d_q = nullptr;
-    uint8_t *d_used = nullptr;
-    DevBag bag;
-    DevEvent ev0, ev1;
-    if (ev0.create() != hipSuccess || ev1.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-    const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
-    const size_t nm = (size_t)n_models, np = (size_t)(n_pts > 0 ? n_pts : 1);
-    std::vector<int32_t> h_outcome(3 * nm);
-    if (bag.alloc(&d_begin, nm + 1) != hipSuccess || bag.alloc(&d_src, 3 * np) != hipSuccess || bag.alloc(&d_dst, 3 * np) != hipSuccess ||
-        (cof_src && bag.alloc(&d_qs, 6 * np) != hipSuccess) || (cof_dst && bag.alloc(&d_qd, 6 * np) != hipSuccess) ||
-        (start && bag.alloc(&d_start, 7 * nm) != hipSuccess) || bag.alloc(&d_out, JAICOV_SIMIL_OUT_PER_MODEL * nm) != hipSuccess ||
-        bag.alloc(&d_outcome, 3 * nm) != hipSuccess || bag.alloc(&d_used, np) != hipSuccess || (pt_q && bag.alloc(&d_q, np) != hipSuccess))
-        return JAICOV_ERR_OUT_OF_MEMORY;
-    hipMemcpyAsync(d_begin, pt_begin, (nm + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    if (n_pts > 0) {
-        hipMemcpyAsync(d_src, src, 3 * (size_t)n_pts * sizeof(double), hipMemcpyHostToDevice, s);
-        hipMemcpyAsync(d_dst, dst, 3 * (size_t)n_pts * sizeof(double), hipMemcpyHostToDevice, s);
-        if (cof_src) hipMemcpyAsync(d_qs, cof_src, 6 * (size_t)n_pts * sizeof(double), hipMemcpyHostToDevice, s);
-        if (cof_dst) hipMemcpyAsync(d_qd, cof_dst, 6 * (size_t)n_pts * sizeof(double), hipMemcpyHostToDevice, s);
-    }
-    if (start) hipMemcpyAsync(d_start, start, 7 * nm * sizeof(double), hipMemcpyHostToDevice, s);
-    hipMemsetAsync(d_used, 1, np, s);                                  // every point starts as used
-    hipEventRecord(e0, s);
-    hipLaunchKernelGGL(simil_models_kernel, dim3(n_models), dim3(SIMIL_LANES), 0, s, d_begin, d_src, d_dst, d_qs, d_qd, d_start,
-                       (int)max_iterations, reject_threshold * reject_threshold, (int)min_points, d_out, d_outcome, d_used, d_q);
-    if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
-    hipEventRecord(e1, s);
-    hipMemcpyAsync(out, d_out, JAICOV_SIMIL_OUT_PER_MODEL * nm * sizeof(double), hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(h_outcome.data(), d_outcome, 3 * nm * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (pt_used && n_pts > 0) hipMemcpyAsync(pt_used, d_used, (size_t)n_pts, hipMemcpyDeviceToHost, s);
-    if (pt_q && n_pts > 0) hipMemcpyAsync(pt_q, d_q, (size_t)n_pts * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
-    for (size_t g = 0; g < nm; g++) {
-        status[g] = h_outcome[3 * g];
-        if (iterations) iterations[g] = h_outcome[3 * g + 1];
-        if (start_kind) start_kind[g] = h_outcome[3 * g + 2];
-    }
-    if (ms_out) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms; }
-    return JAICOV_OK;
+    BatchCall call;
+    const size_t nm = (size_t)n_models, np = (size_t)n_pts;
+    const int32_t *d_begin = call.in(pt_begin, nm + 1);
+    const double *d_src = call.in(src, 3 * np), *d_dst = call.in(dst, 3 * np), *d_qs = call.in(cof_src, 6 * np), *d_qd = call.in(cof_dst, 6 * np),
+                 *d_start = call.in(start, 7 * nm);
+    double *d_out = call.alloc<double>(JAICOV_SIMIL_OUT_PER_MODEL * nm), *d_q = pt_q ? call.alloc<double>(np) : nullptr;
+    int32_t *d_outcome = call.alloc<int32_t>(3 * nm);
+    uint8_t *d_used = call.filled<uint8_t>(np, 1);                     // every point starts as used
+    call.run([&](hipStream_t s) {
+        hipLaunchKernelGGL(simil_models_kernel, dim3(n_models), dim3(SIMIL_LANES), 0, s, d_begin, d_src, d_dst, d_qs, d_qd, d_start,
+                           (int)max_iterations, reject_threshold * reject_threshold, (int)min_points, d_out, d_outcome, d_used, d_q);
+    });
+    call.out(out, d_out, JAICOV_SIMIL_OUT_PER_MODEL * nm);
+    call.outcomes(d_outcome, nm, 3, status, iterations, start_kind);
+    call.out(pt_used, d_used, np);
+    call.out(pt_q, d_q, np);
+    return call.finish(ms_out);
 }
 
 extern "C" int jaicov_simil_apply(int32_t n_models, const double *par, const int32_t *pt_begin, const double *xyz, const double *cof,
@@ -604,38 +557,23 @@ extern "C" int jaicov_simil_apply(int32_t n_models, const double *par, const int
     if (!device_is_gfx950()) return JAICOV_ERR_NO_DEVICE;
     if (n_pts + n_img == 0) return JAICOV_OK;
 
-    DevStream stream;
-    if (stream.create() != hipSuccess) return JAICOV_ERR_DEVICE;
-    const hipStream_t s = stream.get();
-    const std::vector<int32_t> h_pm = models_of(n_models, pt_begin), h_im = models_of(n_models, img_begin);
-    int32_t *d_pm = nullptr, *d_im = nullptr;
-    double *d_par = nullptr, *d_xyz = nullptr, *d_cof = nullptr, *d_eo = nullptr;
-    DevBag bag;
+    BatchCall call(false);             // this call reports no device time
     const size_t np = (size_t)n_pts, ni = (size_t)n_img;
-    if (bag.alloc(&d_par, 7 * (size_t)n_models) != hipSuccess || bag.alloc(&d_pm, np) != hipSuccess || bag.alloc(&d_im, ni) != hipSuccess ||
-        bag.alloc(&d_xyz, 3 * np) != hipSuccess || (cof && bag.alloc(&d_cof, 6 * np) != hipSuccess) || bag.alloc(&d_eo, 6 * ni) != hipSuccess)
-        return JAICOV_ERR_OUT_OF_MEMORY;
-    hipMemcpyAsync(d_par, par, 7 * (size_t)n_models * sizeof(double), hipMemcpyHostToDevice, s);
-    if (np) {
-        hipMemcpyAsync(d_pm, h_pm.data(), np * sizeof(int32_t), hipMemcpyHostToDevice, s);
-        hipMemcpyAsync(d_xyz, xyz, 3 * np * sizeof(double), hipMemcpyHostToDevice, s);
-        if (cof) hipMemcpyAsync(d_cof, cof, 6 * np * sizeof(double), hipMemcpyHostToDevice, s);
-    }
-    if (ni) {
-        hipMemcpyAsync(d_im, h_im.data(), ni * sizeof(int32_t), hipMemcpyHostToDevice, s);
-        hipMemcpyAsync(d_eo, eo, 6 * ni * sizeof(double), hipMemcpyHostToDevice, s);
-    }
+    const std::vector<int32_t> h_pm = models_of(n_models, pt_begin), h_im = models_of(n_models, img_begin);   // alive until finish()
+    const double *d_par = call.in(par, 7 * (size_t)n_models);
+    const int32_t *d_pm = call.in(h_pm);
+    double *d_xyz = call.in(xyz, 3 * np), *d_cof = call.in(cof, 6 * np);
+    const int32_t *d_im = call.in(h_im);
+    double *d_eo = call.in(eo, 6 * ni);
     // every item is read and written by its own thread, in place
     const long n = n_pts + n_img;
     const int threads = SIMIL_APPLY_THREADS, blocks = (int)((n + threads - 1) / threads < 65536 ? (n + threads - 1) / threads : 65536);
-    hipLaunchKernelGGL(simil_apply_kernel, dim3(blocks), dim3(threads), 0, s, n_pts, n_img, d_par, d_pm, d_im, d_xyz, np && cof ? d_cof : nullptr,
-                       d_eo, d_xyz, np && cof ? d_cof : nullptr, d_eo);
-    if (hipGetLastError() != hipSuccess) return JAICOV_ERR_DEVICE;
-    if (np) {
-        hipMemcpyAsync(xyz_out, d_xyz, 3 * np * sizeof(double), hipMemcpyDeviceToHost, s);
-        if (cof) hipMemcpyAsync(cof_out, d_cof, 6 * np * sizeof(double), hipMemcpyDeviceToHost, s);
-    }
-    if (ni) hipMemcpyAsync(eo_out, d_eo, 6 * ni * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return JAICOV_ERR_DEVICE;
-    return JAICOV_OK;
+    call.run([&](hipStream_t s) {
+        hipLaunchKernelGGL(simil_apply_kernel, dim3(blocks), dim3(threads), 0, s, n_pts, n_img, d_par, d_pm, d_im, d_xyz, np ? d_cof : nullptr,
+                           d_eo, d_xyz, np ? d_cof : nullptr, d_eo);
+    });
+    call.out(xyz_out, d_xyz, 3 * np);
+    call.out(cof_out, d_cof, 6 * np);
+    call.out(eo_out, d_eo, 6 * ni);
+    return call.finish();
 }

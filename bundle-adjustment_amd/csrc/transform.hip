@@ -23,6 +23,7 @@
 
 #include "../../include/jaicov_transform.h"
 #include "qview.h"
+#include "rotation.h"
 #include "status.h"
 #include "transform.h"
 
@@ -40,9 +41,7 @@ __device__ __forceinline__ void xf_rotation(const double *eo, double R[9], doubl
     sincos(eo[3], &so, &co);
     sincos(eo[4], &sp, &cp);
     sincos(eo[5], &sk, &ck);
-    R[0] = cp * ck;                R[1] = -cp * sk;               R[2] = sp;
-    R[3] = co * sk + so * sp * ck; R[4] = co * ck - so * sp * sk; R[5] = -so * cp;
-    R[6] = so * sk - co * sp * ck; R[7] = so * ck + co * sp * sk; R[8] = co * cp;
+    rotation_opk(so, co, sk, ck, sp, cp, R);
     // d/domega: the first row does not depend on omega; row 2' = -row 3, row 3' = row 2
     dR[0][0] = 0.0;   dR[0][1] = 0.0;   dR[0][2] = 0.0;
     dR[0][3] = -R[6]; dR[0][4] = -R[7]; dR[0][5] = -R[8];

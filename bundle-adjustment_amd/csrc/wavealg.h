@@ -11,12 +11,17 @@
 // the order of the restatements in tests/resection_reference.py (solve, rotate, eigen).
 // The intersection's isect_solve3 is not here: it is a hand-unrolled solve of order 3 with another summation order and a restatement
 // of its own (tests/intersect_reference.py: solve3).
+// Also here, once for all four kernels: R(omega, phi, kappa) (rotation.h), the lane idioms around it (wave_sincos3, wave_angles) and
+// what a failed item leaves behind (wave_fail_item).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <math.h>
+#include <stdint.h>
 
 #pragma clang fp contract(off)
+
+#include "rotation.h"      // below the pragma: R(omega, phi, kappa) with every product and sum rounded on its own
 
 namespace jaicov {
 
@@ -218,6 +223,45 @@ __device__ inline void wave_argmax_combine(double &qmax, int &qidx, int off) {
     const double oq = __shfl_xor(qmax, off);
     const int oi = __shfl_xor(qidx, off);
     if (oq > qmax || (oq == qmax && oi < qidx)) { qmax = oq; qidx = oi; }
+}
+
+// sines and cosines of three wave-uniform angles: lanes 0, 1, 2 take one angle each and hand its pair to the wave, so that a kernel
+// holds one copy of sincos and of its constants, not three.  (resect.hip keeps lines of its own for this: see rs_rotation there.)
+__device__ inline void wave_sincos3(int lane, double a0, double a1, double a2, double &s0, double &c0, double &s1, double &c1, double &s2,
+                                    double &c2) {
+    const double angle = lane == 0 ? a0 : lane == 1 ? a1 : a2;
+    double sn, cs;
+    sincos(angle, &sn, &cs);
+    s0 = __shfl(sn, 0); c0 = __shfl(cs, 0); s1 = __shfl(sn, 1); c1 = __shfl(cs, 1); s2 = __shfl(sn, 2); c2 = __shfl(cs, 2);
+}
+
+// omega, phi, kappa of R(omega, phi, kappa) from its entries r23, r33, r12, r11, r13 (rotation.h) into ang[0 .. 2]: omega by lane 0,
+// kappa by lane 1 (one copy of atan2), phi with r13 held to [-1, 1]
+__device__ inline void wave_angles(int lane, double r23, double r33, double r12, double r11, double r13, double *ang) {
+    const double a = atan2(lane == 0 ? -r23 : -r12, lane == 0 ? r33 : r11);
+    ang[0] = __shfl(a, 0);
+    ang[1] = asin(fmin(1.0, fmax(-1.0, r13)));
+    ang[2] = __shfl(a, 1);
+}
+
+// Item g has failed, taken by the whole wave: NaN in its n_values values and in q (may be NULL) of its m observations from k0 on,
+// none of them used; its record among the outcome records of WIDTH words gets the status, the solves so far and, where WIDTH is
+// 3, start kind 0.  It takes the records and g, not the item's record, the width at compile time, and g and the solve count (which
+// two kernels keep in LDS) by reference: the index is formed and the count is read inside the lane-0 branch, not before the call.
+// What must hold after a change here: the four kernels' entries of kernel_resources.json are what they were before it.
+template <int WIDTH>
+__device__ inline void wave_fail_item(int lane, double *values, int n_values, int32_t *outcome, const int &g, int st, const int &iters,
+                                      long k0, int m, uint8_t *used, double *q) {
+    static_assert(WIDTH == 2 || WIDTH == 3, "status and solves, or these and the start kind");
+    if (lane < n_values) values[lane] = NAN;
+    if (lane == 0) {
+        outcome[(long)WIDTH * g] = st; outcome[(long)WIDTH * g + 1] = iters;
+        if (WIDTH == 3) outcome[(long)WIDTH * g + 2] = 0;
+    }
+    for (int t = lane; t < m; t += 64) {
+        used[k0 + t] = 0;
+        if (q) q[k0 + t] = NAN;
+    }
 }
 
 }  // namespace jaicov

@@ -62,6 +62,38 @@ def test_status_macros_exist_once():
         assert where == ["status.h"], (macro, where)
 
 
+ONE_SHOT = ("dlt.hip", "intersect.hip", "resect.hip", "relorient.hip", "simil.hip", "lens.hip")
+SHELL = [r"hipMemcpy\w*\s*\(", r"hipMemset\w*\s*\(", r"hipEventRecord\s*\(", r"hipEventElapsedTime\s*\(", r"hipStreamSynchronize\s*\(",
+         r"\bDevStream\b", r"\bDevEvent\b", r"\bDevBag\b"]
+
+
+def test_the_one_shot_calls_have_one_checked_shell():
+    """copies, fills, event records, the elapsed time, the synchronise and their owners: in BatchCall (csrc/batchcall.h), whose every
+    step is checked, and in none of the six files that use it"""
+    src = sources()
+    for name in ONE_SHOT:
+        for pat in SHELL:
+            hits = [m.group(0) for m in re.finditer(pat, code(src[name]))]
+            assert not hits, (name, hits)
+    own = code(src["batchcall.h"])
+    for pat in SHELL:                                  # the patterns do find what they look for
+        assert re.search(pat, own), pat
+
+
+def test_the_rotation_and_the_failed_item_are_written_once():
+    src = sources()
+    assert [n for n, t in src.items() if "co * sk + so * sp * ck" in code(t)] == ["rotation.h"]
+    for name in ("intersect.hip", "resect.hip", "relorient.hip", "simil.hip"):
+        assert "auto fail" not in code(src[name]), name
+    assert len(re.findall(r"\bvoid\s+wave_fail_item\s*\(", code(src["wavealg.h"]))) == 1
+    # rotation_opk takes omega's, KAPPA's and then phi's pair (csrc/rotation.h says why): every call names its arguments that way
+    calls = [(n, m.group(1)) for n, t in src.items() for m in re.finditer(r"\brotation_opk\s*\(([^;{]*?)\)\s*;", code(t))]
+    assert len(calls) >= 7 and {n for n, _ in calls} == {"intersect.hip", "resect.hip", "relorient.hip", "simil.hip", "transform.hip"}
+    for name, args in calls:
+        names = [a.strip() for a in args.split(",")]
+        assert len(names) == 7 and all(re.fullmatch(p + r"\w*", a) for p, a in zip(("so", "co", "sk", "ck", "sp", "cp"), names)), (name, args)
+
+
 def test_the_cofactor_matrix_has_one_view_and_the_shard_rule_one_place():
     src = sources()
     for name, text in src.items():
