@@ -20,6 +20,7 @@
 #include "datum.h"
 #include "dense.h"
 #include "devbuf.h"
+#include "forms.h"
 #include "gemm_f64.h"
 #include "parameters.h"
 #include "precision.h"

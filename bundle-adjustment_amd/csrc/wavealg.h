@@ -158,6 +158,85 @@ __device__ inline WaveStatus wave_solve_lds(int n, double *U, double *b, double 
     return WAVE_OK;
 }
 
+// ---- Lane-parallel routines on a packed upper triangle of order n <= 64 in LDS, for one wave per workgroup (forms.hip).  Where
+// wave_solve_lds has every lane repeat the whole serial solve, these give lane i the entries of index i; the sum of every entry
+// still runs over r in one fixed order, so the bits do not depend on which lane forms it.  A barrier stands between the stores of
+// one column and the loads of the next: with one wave it costs nothing and tells the compiler what the hardware does anyway.
+
+// index of (i, j >= i) in an upper triangle of order n packed row by row
+__device__ inline int tri_ix_n(int n, int i, int j) { return i * n - i * (i - 1) / 2 + (j - i); }
+
+// U'U = A in place (A packed upper, already scaled to a unit diagonal).  At column j every lane forms the pivot, lane i > j the
+// entry U_ji: p = U_jj - sum_{r<j} U_rj U_rj; U_ji = (U_ji - sum_{r<j} U_ri U_rj) / sqrt(p), r ascending.
+__device__ inline WaveStatus wave_chol_lds(int n, double *U, int lane) {
+    const double SQRT_EPS = sqrt(ldexp(1.0, -53));
+    for (int j = 0; j < n; j++) {
+        const bool mine = lane > j && lane < n;
+        const int li = mine ? lane : j;                // a lane without an entry follows the pivot's loads
+        double sp = 0.0, si = 0.0;
+        for (int r = 0; r < j; r++) {
+            const double a = U[tri_ix_n(n, r, j)];
+            sp += a * a;
+            si += U[tri_ix_n(n, r, li)] * a;
+        }
+        const double p = U[tri_ix_n(n, j, j)] - sp;
+        if (wave_uniform(!(p > SQRT_EPS))) return WAVE_SINGULAR;
+        const double d = sqrt(p);
+        const double uji = U[tri_ix_n(n, j, li)];
+        __syncthreads();
+        if (mine) U[tri_ix_n(n, j, lane)] = (uji - si) / d;
+        if (lane == j) U[tri_ix_n(n, j, j)] = d;
+        __syncthreads();
+    }
+    return WAVE_OK;
+}
+
+// U' Z = B for NR right-hand sides at once, reusing the factor: lane i holds row i of B in z and leaves row i of Z there.
+// z_i = (b_i - sum_{r<i} U_ri z_r) / U_ii, r ascending.  Lanes >= n keep what they had.
+template <int NR>
+__device__ inline void wave_forward_lds(int n, const double *U, double (&z)[NR], int lane) {
+    double acc[NR];
+#pragma unroll
+    for (int c = 0; c < NR; c++) acc[c] = 0.0;
+    for (int r = 0; r < n; r++) {
+        const double urr = U[tri_ix_n(n, r, r)];
+        const double uri = (lane > r && lane < n) ? U[tri_ix_n(n, r, lane)] : 0.0;
+#pragma unroll
+        for (int c = 0; c < NR; c++) {
+            if (lane == r) z[c] = (z[c] - acc[c]) / urr;
+            const double zr = __shfl(z[c], r);
+            acc[c] += uri * zr;
+        }
+    }
+}
+
+// U z = y for one right-hand side: lane i holds y_i and leaves z_i.  z_i = (y_i - sum_{r>i} U_ir z_r) / U_ii, r descending.
+__device__ inline void wave_backward_lds(int n, const double *U, double &y, int lane) {
+    double acc = 0.0;
+    for (int r = n - 1; r >= 0; r--) {
+        const double urr = U[tri_ix_n(n, r, r)];
+        const double uir = lane < r ? U[tri_ix_n(n, lane, r)] : 0.0;
+        if (lane == r) y = (y - acc) / urr;
+        const double yr = __shfl(y, r);
+        acc += uir * yr;
+    }
+}
+
+// Z = the inverse of the factor U (both packed upper, Z apart from U): lane j solves U z = e_j for column j,
+// Z_jj = 1 / U_jj, Z_ij = -(sum_{k=i+1..j} U_ik Z_kj) / U_ii for i = j-1 .. 0, k ascending.  A lane reads no column but its own.
+__device__ inline void wave_trinv_lds(int n, const double *U, double *Z, int lane) {
+    if (lane < n) {
+        const int j = lane;
+        Z[tri_ix_n(n, j, j)] = 1.0 / U[tri_ix_n(n, j, j)];
+        for (int i = j - 1; i >= 0; i--) {
+            double r = 0.0;
+            for (int k = i + 1; k <= j; k++) r += U[tri_ix_n(n, i, k)] * Z[tri_ix_n(n, k, j)];
+            Z[tri_ix_n(n, i, j)] = -r / U[tri_ix_n(n, i, i)];
+        }
+    }
+    __syncthreads();
+}
+
 // the Jacobi rotation that annuls a_pq: t = tan, c = cos, s = sin of its angle
 __device__ inline void jacobi_angle(double app, double aqq, double apq, double &t, double &c, double &s) {
     const double theta = (aqq - app) / (2.0 * apq);

@@ -2,7 +2,7 @@
 ``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_reliability_points.h`` /
 ``include/jaicov_datum.h`` / ``include/jaicov_intersect.h`` / ``include/jaicov_resect.h`` /
 ``include/jaicov_relorient.h`` / ``include/jaicov_simil.h`` / ``include/jaicov_lens.h`` / ``include/jaicov_precision.h`` /
-``include/jaicov_parameters.h`` (``csrc/libjaicov_neq.so``).
+``include/jaicov_parameters.h`` / ``include/jaicov_forms.h`` (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
 library has not been built, and every call fails with ``EngineError`` when no gfx950 device is present.
@@ -63,6 +63,14 @@ PAR_CLASS_POINT, PAR_CLASS_INTERIOR, PAR_CLASS_DISTORTION, PAR_CLASS_EXTERIOR = 
 PAR_CLASS_NAMES = ("point", "interior", "distortion", "exterior")
 PAR_MAX_GROUP, PAR_TEST_COLUMNS = 64, 4
 PAR_ALL_PAIRS = 0xFFFF
+# include/jaicov_forms.h: planes, spheres, lines and circles through adjusted points with the members' whole cofactor block
+FORM_EXPORTS = ["jaicov_form_fit"]
+FORM_PLANE, FORM_SPHERE, FORM_LINE, FORM_CIRCLE = range(4)
+FORM_KINDS = {"plane": FORM_PLANE, "sphere": FORM_SPHERE, "line": FORM_LINE, "circle": FORM_CIRCLE}
+FORM_PARTIAL, FORM_TOO_SMALL, FORM_TOO_LARGE, FORM_DEGENERATE, FORM_SINGULAR, FORM_NOT_FINITE, FORM_NOT_CONVERGED = 1, 2, 4, 8, 16, 32, 64
+FORM_MEMBER_UNTESTED = 1
+FORM_MAX_ROWS, FORM_MAX_PARAMS, FORM_COLUMNS, FORM_QPP_COLUMNS, FORM_MEMBER_COLUMNS = 64, 7, 20, 28, 7
+FORM_REPORTED = (4, 4, 6, 7)      # parameters reported per kind: n d | c r | x0 t | c n r
 # jaicov_dlt_restriction (DirectLinearTransformation.RestrictionType, DT:51-58 order) and the per-image status values
 DLT_IDENTICAL_PRINCIPLE_DISTANCE, DLT_ROTATION_WITHOUT_SHEAR, DLT_FIXED_PRINCIPLE_DISTANCE_X, DLT_FIXED_PRINCIPLE_DISTANCE_Y, \
     DLT_FIXED_PRINCIPAL_POINT_X, DLT_FIXED_PRINCIPAL_POINT_Y = range(6)
@@ -200,6 +208,7 @@ def load_library():
     L.jaicov_par_pairs.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_double, C.c_int64, _pi, _pd, C.POINTER(C.c_int64)]
     L.jaicov_par_block.argtypes = [vp, _pi, C.c_int32, _pi, C.c_int32, _pd]
     L.jaicov_par_tests.argtypes = [vp, C.c_double, _pi, _pi, _pd, C.c_int32, _pd, _pi]
+    L.jaicov_form_fit.argtypes = [vp, C.c_double, C.c_int32, _pi, _pi, _pi, C.c_int32, C.c_double, _pd, _pd, _pd, _pi, _pi, C.POINTER(C.c_float)]
     L.jaicov_dlt_adjust.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pi, C.c_int32, C.c_int32, _pd, _pi, _pi, _pd]
     L.jaicov_isect_points.argtypes = [C.c_int32, _pi, _pi, _pd, _pd, C.c_int32, _pd, _pd, C.c_double, C.c_int32, C.c_double, C.c_int32,
                                       _pd, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
@@ -238,6 +247,11 @@ CorrelatedPairs = namedtuple("CorrelatedPairs", ["cols", "rho", "count"])
 # Engine.parameter_tests: one entry per group; t is NaN unless k == 1
 ParameterTests = namedtuple("ParameterTests", ["q", "T", "k", "t", "status"])
 ColumnName = namedtuple("ColumnName", ["cls", "item", "component"])
+# Engine.fit_forms: one entry per form (include/jaicov_forms.h).  params / sigma (n, 7), NaN behind the kind's parameters; qpp (n, 7, 7)
+# symmetric; begin (n + 1,): the members of form g are rows begin[g] .. begin[g + 1] of v (M, 3), distance, nabla (M, 2), T_member and
+# member_status; kernel_ms: the kernel's time by events
+FormFits = namedtuple("FormFits", ["params", "sigma", "qpp", "omega", "dof", "T", "max_distance", "rms_distance", "iterations", "status",
+                                   "begin", "v", "distance", "nabla", "T_member", "member_status", "kernel_ms"])
 
 
 def _p(a):
@@ -595,6 +609,25 @@ class Engine:
                                           None if xs is None else _p(xs), n, _p(out), status.ctypes.data_as(_pi)))
         return ParameterTests(out[:, 0], out[:, 1], out[:, 2].astype(np.int32), out[:, 3], status)
 
+    # forms through adjusted points (include/jaicov_forms.h) ------------------------------------------------------------------------
+    def fit_forms(self, sigma2, forms, max_iterations=20, tol=0.0):
+        """Fits every form of `forms`, a list of (kind, point_indices) with kind "plane", "sphere", "line", "circle" or FORM_*, to
+        the current coordinates of its points with their whole block of the cofactor matrix (Gauss-Helmert model).  Returns a
+        FormFits: parameters with sigma and Q_pp, Omega, f, T = Omega / (f sigma2), the members' corrections, distances, estimated
+        gross errors and tests.  No quantile is evaluated."""
+        kinds = np.ascontiguousarray([FORM_KINDS.get(k, k) for k, _ in forms], np.int32)
+        members = [np.asarray(pts, np.int32).ravel() for _, pts in forms]
+        begin = np.concatenate([[0], np.cumsum([g.size for g in members])]).astype(np.int32)
+        points = np.ascontiguousarray(np.concatenate(members) if members else np.zeros(0), np.int32)
+        n, M = len(forms), int(points.size)
+        out = np.zeros((n, FORM_COLUMNS)); qpp = np.zeros((n, FORM_QPP_COLUMNS)); mem = np.zeros((max(M, 1), FORM_MEMBER_COLUMNS))
+        status = np.zeros(n, np.int32); mstatus = np.zeros(max(M, 1), np.int32)
+        ms = C.c_float(0.0)
+        self._chk(self.L.jaicov_form_fit(self._h, float(sigma2), n, kinds.ctypes.data_as(_pi), begin.ctypes.data_as(_pi),
+                                         points.ctypes.data_as(_pi), int(max_iterations), float(tol), _p(out), _p(qpp), _p(mem),
+                                         status.ctypes.data_as(_pi), mstatus.ctypes.data_as(_pi), C.byref(ms)))
+        return form_fits(out, qpp, mem[:M], status, mstatus[:M], begin, ms.value)
+
     def get_rows(self, ip_begin, ip_count):
         w = np.zeros((ip_count, 2)); A = np.zeros((ip_count, 2, KROW))
         self._chk(self.L.jaicov_neq_get_rows(self._h, ip_begin, ip_count, _p(w), _p(A)))
@@ -655,6 +688,17 @@ def point_column_range(fp: FlatProblem):
     if cols.size == 0 or cols[-1] - cols[0] + 1 != cols.size:
         raise ValueError("the columns of the image-observed points are not one contiguous range")
     return int(cols[0]), int(cols.size)
+
+
+def form_fits(out, qpp, mem, status, mstatus, begin, kernel_ms=0.0):
+    """The tables of jaicov_form_fit as a FormFits"""
+    n = out.shape[0]
+    full = np.zeros((n, FORM_MAX_PARAMS, FORM_MAX_PARAMS))
+    iu = np.triu_indices(FORM_MAX_PARAMS)
+    full[:, iu[0], iu[1]] = qpp
+    full[:, iu[1], iu[0]] = qpp
+    return FormFits(out[:, 0:7], out[:, 7:14], full, out[:, 14], out[:, 15], out[:, 16], out[:, 17], out[:, 18], out[:, 19], status,
+                    np.asarray(begin), mem[:, 0:3], mem[:, 3], mem[:, 4:6], mem[:, 6], mstatus, kernel_ms)
 
 
 def column_names(fp: FlatProblem):

@@ -203,6 +203,16 @@ PYBIND11_MODULE(_jaicov_host, m) {
                                   py::array_t<int32_t>((py::ssize_t)t.status.size(), t.status.data()));
         }, py::arg("sigma2"), py::arg("groupBegin"), py::arg("groupSlot"), py::arg("x0") = std::vector<double>(),
              "(table (n, 4): q, T, k, t; status (n,)) of the test x_g = x0_g on groups of slots (include/jaicov_parameters.h)")
+        .def("fitForms", [](BundleAdjustment &b, double sigma2, std::vector<int32_t> formType, std::vector<int32_t> formBegin,
+                            std::vector<int32_t> formPoint, int maxIterations, double tol) {
+            auto f = b.fitForms(sigma2, formType, formBegin, formPoint, maxIterations, tol);
+            return py::make_tuple(py::array_t<double>({f.status.size(), (size_t)JAICOV_FORM_COLUMNS}, f.table.data()),
+                                  py::array_t<double>({f.status.size(), (size_t)JAICOV_FORM_QPP_COLUMNS}, f.qpp.data()),
+                                  py::array_t<double>({f.memberStatus.size(), (size_t)JAICOV_FORM_MEMBER_COLUMNS}, f.members.data()),
+                                  py::array_t<int32_t>((py::ssize_t)f.status.size(), f.status.data()),
+                                  py::array_t<int32_t>((py::ssize_t)f.memberStatus.size(), f.memberStatus.data()));
+        }, py::arg("sigma2"), py::arg("formType"), py::arg("formBegin"), py::arg("formPoint"), py::arg("maxIterations") = 20, py::arg("tol") = 0.0,
+             "(table (n, 20), qpp (n, 28), members (M, 7), status (n,), member status (M,)) of the forms through object points (include/jaicov_forms.h)")
         .def("useCentroidedCoordinates", &BundleAdjustment::useCentroidedCoordinates)
         .def("centroidCoordinates", &BundleAdjustment::centroidCoordinates)
         .def("applyAposterioriVarianceOfUnitWeight", &BundleAdjustment::applyAposterioriVarianceOfUnitWeight)

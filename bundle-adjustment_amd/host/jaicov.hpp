@@ -39,6 +39,7 @@
 #include "../../include/jaicov_datum.h"
 #include "../../include/jaicov_precision.h"
 #include "../../include/jaicov_parameters.h"
+#include "../../include/jaicov_forms.h"
 
 namespace jaicov::host {
 
@@ -583,6 +584,17 @@ public:
     };
     ParameterTests testParameters(double sigma2, const std::vector<int32_t> &groupBegin, const std::vector<int32_t> &groupSlot,
                                   const std::vector<double> &x0 = {}) const;
+    // Planes, spheres, lines and circles through adjusted object points, fitted on the device with the members' whole block of the
+    // cofactor matrix (include/jaicov_forms.h).  Form g has the type formType[g] (JAICOV_FORM_*) and the points
+    // formPoint[formBegin[g] .. formBegin[g + 1]) (ObjectCoordinate::index).
+    struct FormFits {
+        std::vector<double> table;               // rows of JAICOV_FORM_COLUMNS: parameters, sigma, Omega, f, T, distances, iterations
+        std::vector<double> qpp;                 // rows of JAICOV_FORM_QPP_COLUMNS: Q_pp, packed upper 7 x 7
+        std::vector<double> members;             // rows of JAICOV_FORM_MEMBER_COLUMNS parallel to formPoint: v, distance, nabla, T_i
+        std::vector<int32_t> status, memberStatus;
+    };
+    FormFits fitForms(double sigma2, const std::vector<int32_t> &formType, const std::vector<int32_t> &formBegin,
+                      const std::vector<int32_t> &formPoint, int maxIterations = 20, double tol = 0.0) const;
     const std::string &lastError() const { return lastError_; }
     jaicov_engine *nativeEngine() const { return engine_; }     // the engine of the last estimateModel (null before)
 

@@ -1,0 +1,93 @@
+"""CPU: the C ABI of include/jaicov_forms.h is exported, declared and bound (Python: engine.FORM_EXPORTS, C++ mirror), the header's
+signature is the ctypes one, its constants are the binding's and the restatement's, and a NULL engine is refused with the outputs
+untouched."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+
+import form_reference as R
+from bundle_adjustment_amd import engine
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "jaicov_forms.h")
+HOST = os.path.join(ROOT, "bundle-adjustment_amd", "host")
+CTYPE = {"jaicov_engine *": C.c_void_p, "double": C.c_double, "int32_t": C.c_int32, "const int32_t *": C.POINTER(C.c_int32),
+         "double *": C.POINTER(C.c_double), "int32_t *": C.POINTER(C.c_int32), "float *": C.POINTER(C.c_float)}
+
+
+def code():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
+def _lib():
+    if not os.path.exists(engine.LIB_PATH):
+        engine.build_library()
+    return engine.load_library()
+
+
+def test_header_declarations_are_exported_and_bound():
+    names = sorted(set(re.findall(r"\b(jaicov_form_[a-z_0-9]+)\s*\(", code())))
+    assert names == sorted(engine.FORM_EXPORTS) == ["jaicov_form_fit"]
+    for other in (engine.EXPORTS, engine.XFORM_EXPORTS, engine.DLT_EXPORTS, engine.REL_EXPORTS, engine.REL_POINT_EXPORTS, engine.DATUM_EXPORTS,
+                  engine.PREC_EXPORTS, engine.PARAM_EXPORTS, engine.ISECT_EXPORTS, engine.RESECT_EXPORTS, engine.RELOR_EXPORTS,
+                  engine.SIMIL_EXPORTS, engine.LENS_EXPORTS):
+        assert not set(names) & set(other)
+    L = _lib()
+    syms = subprocess.run(["nm", "-D", "--defined-only", engine.LIB_PATH], capture_output=True, text=True).stdout
+    assert sorted(re.findall(r"\bT (jaicov_form_\w+)", syms)) == names          # exported, and nothing of the family undeclared
+    assert hasattr(L, "jaicov_form_fit") and callable(engine.Engine.fit_forms) and callable(engine.form_fits)
+
+
+def test_header_signature_is_the_ctypes_one():
+    m = re.search(r"\bint\s+jaicov_form_fit\s*\(([^)]*)\)\s*;", code())
+    assert m
+    args = [re.sub(r"\s+", " ", a.strip()) for a in m.group(1).split(",")]
+    kinds = [re.match(r"(.*?)(\w+)$", a).group(1).strip() for a in args]
+    names = [re.match(r"(.*?)(\w+)$", a).group(2) for a in args]
+    assert names == ["e", "sigma2", "n_forms", "form_type", "form_begin", "form_point", "max_iterations", "tol", "out", "qpp", "member_out",
+                     "status", "member_status", "ms_out"]
+    assert [CTYPE[k] for k in kinds] == list(_lib().jaicov_form_fit.argtypes)
+
+
+def test_constants_match():
+    consts = {k: int(v) for k, v in re.findall(r"#define JAICOV_FORM_(\w+) (\d+)", open(HEADER).read())}
+    assert consts == {
+        "PLANE": engine.FORM_PLANE, "SPHERE": engine.FORM_SPHERE, "LINE": engine.FORM_LINE, "CIRCLE": engine.FORM_CIRCLE,
+        "PARTIAL": engine.FORM_PARTIAL, "TOO_SMALL": engine.FORM_TOO_SMALL, "TOO_LARGE": engine.FORM_TOO_LARGE,
+        "DEGENERATE": engine.FORM_DEGENERATE, "SINGULAR": engine.FORM_SINGULAR, "NOT_FINITE": engine.FORM_NOT_FINITE,
+        "NOT_CONVERGED": engine.FORM_NOT_CONVERGED, "MEMBER_UNTESTED": engine.FORM_MEMBER_UNTESTED, "MAX_ROWS": engine.FORM_MAX_ROWS,
+        "MAX_PARAMS": engine.FORM_MAX_PARAMS, "COLUMNS": engine.FORM_COLUMNS, "QPP_COLUMNS": engine.FORM_QPP_COLUMNS,
+        "MEMBER_COLUMNS": engine.FORM_MEMBER_COLUMNS}
+    assert (R.PLANE, R.SPHERE, R.LINE, R.CIRCLE) == (engine.FORM_PLANE, engine.FORM_SPHERE, engine.FORM_LINE, engine.FORM_CIRCLE)
+    assert R.KINDS == engine.FORM_KINDS and R.REPORTED == engine.FORM_REPORTED
+    assert (R.PARTIAL, R.TOO_SMALL, R.TOO_LARGE, R.DEGENERATE, R.SINGULAR, R.NOT_FINITE, R.NOT_CONVERGED, R.MEMBER_UNTESTED) == (
+        engine.FORM_PARTIAL, engine.FORM_TOO_SMALL, engine.FORM_TOO_LARGE, engine.FORM_DEGENERATE, engine.FORM_SINGULAR, engine.FORM_NOT_FINITE,
+        engine.FORM_NOT_CONVERGED, engine.FORM_MEMBER_UNTESTED)
+    assert (R.MAX_ROWS, R.COLUMNS, R.QPP_COLUMNS, R.MEMBER_COLUMNS, R.MAX_PARAMS) == (
+        engine.FORM_MAX_ROWS, engine.FORM_COLUMNS, engine.FORM_QPP_COLUMNS, engine.FORM_MEMBER_COLUMNS, engine.FORM_MAX_PARAMS)
+    assert engine.FORM_QPP_COLUMNS == engine.FORM_MAX_PARAMS * (engine.FORM_MAX_PARAMS + 1) // 2
+    assert [c * (engine.FORM_MAX_ROWS // c) for c in R.CONDITIONS] == [64, 64, 64, 64]
+
+
+def test_the_cpp_host_mirrors_the_call():
+    hpp = open(os.path.join(HOST, "jaicov.hpp")).read()
+    cpp = open(os.path.join(HOST, "jaicov.cpp")).read()
+    bind = open(os.path.join(HOST, "bindings.cpp")).read()
+    mk = open(os.path.join(HOST, "Makefile")).read()
+    assert '#include "../../include/jaicov_forms.h"' in hpp
+    assert re.search(r"\bfitForms\s*\(", hpp) and re.search(r"BundleAdjustment::fitForms\s*\(", cpp) and re.search(r"\bjaicov_form_fit\s*\(engine_", cpp)
+    assert '.def("fitForms"' in bind and re.search(r"^example_forms:", mk, flags=re.M)
+    from bundle_adjustment_amd import host_api
+    assert hasattr(host_api.BundleAdjustment, "fitForms")
+
+
+def test_null_engine_is_refused_and_outputs_stay():
+    L = _lib()
+    pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    out = np.full(28, 3.0); st = np.full(4, 7, np.int32); idx = np.zeros(4, np.int32); ms = C.c_float(5.0)
+    assert L.jaicov_form_fit(None, 1.0, 1, idx.ctypes.data_as(pi), idx.ctypes.data_as(pi), idx.ctypes.data_as(pi), 10, 0.0, out.ctypes.data_as(pd),
+                             out.ctypes.data_as(pd), out.ctypes.data_as(pd), st.ctypes.data_as(pi), st.ctypes.data_as(pi), C.byref(ms)) == -1
+    assert np.all(out == 3.0) and np.all(st == 7) and ms.value == 5.0
