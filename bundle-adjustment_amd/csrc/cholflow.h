@@ -19,8 +19,8 @@ enum { FACTOR_DEFAULT = 0, FACTOR_STREAMS = 1, FACTOR_TWO_STEP = 2, FACTOR_ONE_K
 
 // Every environment hook of the solver, parsed by flow_hooks() and nowhere else.  WHEN a hook takes effect is up to who calls flow_hooks():
 // a solver keeps the hooks it was initialised under (form, min_blocks, split, trace_on, chain_trace: the tests switch them between engines of
-// one process) and asks again at every factorisation / substitution for timeout_ms, chain8_min_nb and verbose (the tests set those around
-// single calls).
+// one process) and asks again at every factorisation for timeout_ms and verbose, at every substitution for chain8_min_nb (chains.h,
+// chain_decide): the tests set those around single calls.
 constexpr int HOOK_UNSET = INT_MIN;
 struct FlowHooks {
     int form = FACTOR_DEFAULT;     // JAICOV_FACTOR_FORM
@@ -43,7 +43,6 @@ struct FlowDecision {
 };
 // nb block columns to factorise; `kernels_overlap`: two kernels of this process can run at the same time (does not bear on use_flow)
 FlowDecision flow_decide(int nb, bool kernels_overlap, const FlowHooks &h);
-int chain8_min_blocks(const FlowHooks &h);     // the polling-wave chains of the substitution: from this many block columns on
 
 // ---- flag words -----------------------------------------------------------------------------------------------------------------------
 // control words

@@ -1095,10 +1095,6 @@ FlowHooks flow_hooks() {
     return h;
 }
 
-// The polling-wave chains pay two batched GEMM launches per factorisation (~0.1 ms) for ~1.2 us per link and chain: from this many
-// block columns on (config 2, 6 block columns: 0.085 -> 0.14 ms per pass with them; config 3, 29: 0.28 -> 0.27)
-int chain8_min_blocks(const FlowHooks &h) { return h.chain8_min_nb != HOOK_UNSET ? h.chain8_min_nb : 24; }
-
 // Which factorisation a solver of nb block columns uses, and in which form.
 FlowDecision flow_decide(int nb, bool kernels_overlap, const FlowHooks &h) {
     FlowDecision dec{};

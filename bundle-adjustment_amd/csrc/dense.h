@@ -10,6 +10,7 @@
 #include <map>
 #include <vector>
 
+#include "chains.h"
 #include "cholflow.h"
 #include "devbuf.h"
 
@@ -67,18 +68,11 @@ struct DenseSolver {     // not copyable: it holds owners
     const int2 *trtri_tile_order(int tm, int tn, int kind);
     double *L = nullptr;       // n x ld : input SPD matrix (lower) -> Cholesky factor (lower)
     double *invd = nullptr;    // (n/128) x 128 x 128 : inverses of the diagonal blocks of L
-    double *pm = nullptr;      // 2 x 5 x (n/128) x 128 x 128 : the chains' pre-multiplied blocks P_1 .. P_5, Ft_1 .. Ft_5 (premultiply(), dense.hip CH_PM)
-    double *xch = nullptr;     // n : the two workgroups of a block column pass their halves of v through this (backsolve_chain8_kernel<2>)
-    hipError_t launch_chain8(const double *Zrow, double *X, const int *abort_word, long long *trace);
-    bool chain8_split() const;  // two workgroups per block column / row in the one-right-hand-side chains (the grid must be resident at once)
-    bool pm_ready = false;     // pm belongs to the factor at hand (potrf() clears it)
-    DevEvent pm_e0, pm_done;   // the Ft half of premultiply() runs on pstream
-    bool pm_wait = false;      // ... and `stream` has not waited for it yet
-    hipError_t premultiply();
     double *W = nullptr;       // n x ld : L^-1 (lower), only for the inverse
     double *Q = nullptr;       // n x ld : (L L')^-1 (lower tiles valid; symmetrize() fills the rest); workspace of trtri()
     int *d_info = nullptr;     // first failing pivot (1-based), 0 = ok
-    struct Store { DevBuf<double> L, invd, pm, xch, W, Q; DevBuf<int> info; } store;   // the owners of the buffers above
+    struct Store { DevBuf<double> L, invd, W, Q; DevBuf<int> info; } store;   // the owners of the buffers above
+    SolveChains chains;        // the substitution chains (chains.hip) and what they own beyond the factor
     FlowHooks hooks;           // the environment's test hooks as they were at init()
     // optional per-launch profiling of the trailing update (HIP events on `stream`)
     bool profile = false;

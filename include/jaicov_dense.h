@@ -20,8 +20,8 @@ extern "C" {
  * nrhs < 0, nrhs > 8, n <= 0, ap == NULL or b == NULL with nrhs > 0 return JAICOV_ERR_BAD_ARGUMENT before any device is touched.
  * Every right-hand side is solved on its own.  With nrhs = 2 .. 8 the bits of a solution do not depend on how many vectors ride
  * beside it, and nrhs = 1 gives those bits too as long as the matrix has fewer than 24 block columns of 128 (n <= 2944).  From
- * there on a single right-hand side takes another form of the backward substitution (pre-multiplied blocks, csrc/dense.hip,
- * DenseSolver::backsolve_aug): the same solution to rounding, not the same bits.
+ * there on a single right-hand side takes another form of the backward substitution (pre-multiplied blocks, csrc/chains.hip,
+ * chain_decide): the same solution to rounding, not the same bits.
  * Returns jaicov_status: JAICOV_ERR_SINGULAR (1) when N is not positive definite (MatrixNotSPDException, MX:250-251).
  * ms_out (optional) receives the device time of factorisation (+ substitutions, + inverse) in milliseconds. */
 int jaicov_dense_spd_solve_packed(int32_t n, double *ap, double *b, int32_t nrhs, int32_t invert, double *ms_out);

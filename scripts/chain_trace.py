@@ -1,4 +1,4 @@
-"""Link times of the substitution chains (JAICOV_CHAIN_TRACE, dense.hip): one refined solve at a config, the trace goes to stderr.
+"""Link times of the substitution chains (JAICOV_CHAIN_TRACE, chains.hip: SolveChains::dump_trace): one refined solve at a config, the trace goes to stderr.
     JAICOV_CHAIN_TRACE=1 python scripts/chain_trace.py [config]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -3,7 +3,7 @@ grid every shape must be given) and tests/test_gpu_gemm_family.py (the products 
 
 A case is a dict: the launcher's arguments, the expected plan (TM, TN, tag, grid x) and how the buffers are laid out.
   pad        extra doubles on lda, ldb, ldc (even; 0 = leading dimension equals the extent)
-  bcast_b2   strideB2 = 0 (one B for all of the second batch dimension, as DenseSolver::premultiply passes W_k)
+  bcast_b2   strideB2 = 0 (one B for all of the second batch dimension, as SolveChains::premultiply passes W_k)
   same_ab    B is A: one buffer, one pointer (the trailing updates)
   map        None or a function (tile rows, tile cols, lower_only, rng) -> (n, 2) int32 tile map
 """

@@ -266,3 +266,50 @@ def test_the_hooks_reach_the_decision(monkeypatch):
     monkeypatch.setenv("JAICOV_FLOW_SPLIT", "0")         # fewer than one piece: one
     lib.jaicov_debug_flow_decision(6, 1, out)
     assert tuple(out) == (1, 0, 1, 2, 1, 0)
+
+
+# (block columns, right-hand sides, compute units) -> (polling-wave form, workgroups per block column, right-hand sides the kernel carries)
+CHAIN_DECISIONS = [
+    (None, (23, 1, 256), (0, 1, 1)),         # below 24 block columns: backsolve_chain_kernel<1>
+    (None, (24, 1, 256), (1, 2, 1)),         # the polling-wave form, two workgroups per block column while the grid is resident at once
+    (None, (128, 1, 256), (1, 2, 1)),
+    (None, (129, 1, 256), (1, 1, 1)),        # 2 nb > compute units: one workgroup per block column
+    (None, (24, 1, 0), (1, 1, 1)),           # the compute units could not be asked
+    (None, (24, 2, 256), (0, 1, 2)),         # more than one right-hand side: backsolve_chain_kernel<2 / 4 / 8>
+    (None, (24, 3, 256), (0, 1, 4)),
+    (None, (24, 4, 256), (0, 1, 4)),
+    (None, (24, 5, 256), (0, 1, 8)),
+    (None, (24, 8, 256), (0, 1, 8)),
+    ("1", (1, 1, 256), (1, 1, 1)),           # JAICOV_CHAIN8_MIN_NB=1: the split form still only from 8 block columns on
+    ("1", (7, 1, 256), (1, 1, 1)),
+    ("1", (8, 1, 256), (1, 2, 1)),
+    ("1", (8, 2, 256), (0, 1, 2)),
+]
+
+
+def chain_decision(nb, nrhs, cus):
+    lib = engine.load_library()
+    out = (C.c_int * 3)()
+    lib.jaicov_debug_chain_decision(nb, nrhs, cus, out)
+    return tuple(out)
+
+
+@pytest.mark.parametrize("min_nb,case,want", CHAIN_DECISIONS)
+def test_the_form_of_the_substitution_chains_is_decided_in_one_place(monkeypatch, min_nb, case, want):
+    """Which chain kernels a substitution launches (chains.h, chain_decide): what the solver did when the rule was written out in
+    DenseSolver::backsolve_aug, solve_rhs and chain8_split (pre-multiplied blocks and exchange vector present; an MI355X reports 256
+    compute units)."""
+    for h in HOOKS:
+        monkeypatch.delenv(h, raising=False)
+    if min_nb is not None:
+        monkeypatch.setenv("JAICOV_CHAIN8_MIN_NB", min_nb)
+    assert chain_decision(*case) == want
+
+
+def test_the_chain_hook_is_read_at_every_call(monkeypatch):
+    for h in HOOKS:
+        monkeypatch.delenv(h, raising=False)
+    monkeypatch.setenv("JAICOV_CHAIN8_MIN_NB", "1")
+    assert chain_decision(8, 1, 256) == (1, 2, 1)
+    monkeypatch.delenv("JAICOV_CHAIN8_MIN_NB")
+    assert chain_decision(8, 1, 256) == (0, 1, 1)

@@ -59,7 +59,7 @@ def test_dense_spd_solve_and_inverse(n):
 
 @pytest.mark.parametrize("n", [100, 200, 384, 500, 640, 1100, 2100, 4200])
 def test_dense_spd_solve_one_right_hand_side(n, monkeypatch):
-    """ONE right-hand side takes the polling-wave form of the backward chain (backsolve_chain8_kernel, dense.hip; by default from 24
+    """ONE right-hand side takes the polling-wave form of the backward chain (backsolve_chain8_kernel, chains.hip; by default from 24
     block columns on, here from one): 1, 2, 3, 4, 5, 9, 17 and 33 block columns -- no predecessor, fewer predecessors than
     pre-multiplied blocks, streams of odd and even length, one and two workgroups per block column, and streams longer than the ring
     between the polling wave and the streaming waves (8 slots)."""
@@ -82,7 +82,7 @@ def test_dense_spd_solve_at_every_count_of_right_hand_sides(n, monkeypatch):
     a right-hand side is one more row of the factorisation's update and one more column of the chain's sums, each formed in the
     same order whatever rides beside it, so nothing may leak from one vector, or from the padding of a ragged nrhs, into another.
     That holds among the backsolve_chain_kernel instances.  A single right-hand side from 24 block columns on takes the polling-wave
-    form, whose sums differ on purpose (see below and the comment at DenseSolver::backsolve_aug): 1e-13 relative there, no bit-equality.
+    form, whose sums differ on purpose (see below and the comment at chain_decide, csrc/chains.hip): 1e-13 relative there, no bit-equality.
     nrhs = 0 with `invert` is accepted and nrhs = 9 refused with JAICOV_ERR_BAD_ARGUMENT (include/jaicov_dense.h): an argument check
     in front of the device."""
     from test_gpu_refinement import exact_solution
@@ -105,7 +105,7 @@ def test_dense_spd_solve_at_every_count_of_right_hand_sides(n, monkeypatch):
         for q in range(nrhs):
             assert x[q].tobytes() == alone[q].tobytes(), (nrhs, q, float(np.abs(x[q] - alone[q]).max()))
     print(f"n = {n}: nrhs 1 .. 8 worst {worst:.2e} of max|x| from the exact solution; every vector bit-equal to its solve alone")
-    # The one exception, on purpose (dense.hip, DenseSolver::backsolve_aug): ONE right-hand side in the polling-wave form (by default
+    # The one exception, on purpose (chains.hip, chain_decide): ONE right-hand side in the polling-wave form (by default
     # from 24 block columns on, here from one) multiplies by pre-multiplied blocks, other sums than the chain kernel's.  Bit-equality
     # is replaced by 1e-13 of max|x| against the chain kernel's vector, and the exact solution holds it as it holds the others.
     monkeypatch.setenv("JAICOV_CHAIN8_MIN_NB", "1")

@@ -1,4 +1,4 @@
-"""Iterative refinement of the step (csrc/refine.hip, forward substitution in csrc/dense.hip) against the EXACT solution of the
+"""Iterative refinement of the step (csrc/refine.hip, forward substitution in csrc/chains.hip) against the EXACT solution of the
 system the device assembled.
 
 "Exact" = numpy's LU solution of the device's own N, n (bordered with the datum rows the oracle builds for the same
@@ -49,7 +49,7 @@ def rel(a, b):
 @pytest.mark.parametrize("chains", ["default", "polling_wave_from_one_block_column"])
 @pytest.mark.parametrize("name", ["tiny", "tiny_block", "tiny_free", "mid_block", "cfg3"])
 def test_refined_step_is_the_exact_solution_of_the_assembled_system(oracle_mod, name, chains, monkeypatch):
-    if chains != "default":         # dense.hip: the one-right-hand-side chains in their polling-wave form, by default from 24 block columns on
+    if chains != "default":         # chains.hip: the one-right-hand-side chains in their polling-wave form, by default from 24 block columns on
         monkeypatch.setenv("JAICOV_CHAIN8_MIN_NB", "1")
     fp = (scene.make_scene(12, 150, 90, dist=scene.DIST_FULL, weights="block", n_control=5, control_dense=True)
           if name == "mid_block" else scene.config(name))

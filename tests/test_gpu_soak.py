@@ -3,7 +3,7 @@
 The dataflow Cholesky's waits are bounded; a wait that runs out makes `solve` repeat the factorisation (engine.hip) and counts in
 jaicov_neq_kernel_stats()[6].  Round 2 saw one such stall per 300-3 600 factorisations until the last workgroups on the chain
 workgroups' XCDs were taken out (cholflow.hip, "keep"); 16 000 clean factorisations since.  150 passes here by default (5 s);
-JAICOV_SOAK_PASSES=4000 for a real soak (2 min).  Every pass also runs the substitution chains (dense.hip: a lost link
+JAICOV_SOAK_PASSES=4000 for a real soak (2 min).  Every pass also runs the substitution chains (chains.hip: a lost link
 would show as NaNs in the step): 14 000 passes = 28 000 launches of the polling-wave backward chain at the end of round 3, and 6 000
 more with two workgroups per block column, clean."""
 import os
@@ -46,7 +46,7 @@ def test_no_factorisation_is_abandoned_over_many_passes(cfg4_scene):
     for i in range(n):
         eng.build(s2, 0.0)
         dx = eng.solve(False)
-        assert np.isfinite(dx).all(), i      # a lost link of a substitution chain shows up as NaNs (dense.hip)
+        assert np.isfinite(dx).all(), i      # a lost link of a substitution chain shows up as NaNs (chains.hip)
         if i % 1000 == 999:
             print(f"soak: {i + 1} passes", flush=True)     # (a long run must not look hung to the GPU pool's watchdog)
         if ref is None:
