@@ -21,6 +21,7 @@
 #include "dense.h"
 #include "devbuf.h"
 #include "forms.h"
+#include "predict.h"
 #include "gemm_f64.h"
 #include "parameters.h"
 #include "precision.h"

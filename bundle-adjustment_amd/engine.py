@@ -2,7 +2,7 @@
 ``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_reliability_points.h`` /
 ``include/jaicov_datum.h`` / ``include/jaicov_intersect.h`` / ``include/jaicov_resect.h`` /
 ``include/jaicov_relorient.h`` / ``include/jaicov_simil.h`` / ``include/jaicov_lens.h`` / ``include/jaicov_precision.h`` /
-``include/jaicov_parameters.h`` / ``include/jaicov_forms.h`` (``csrc/libjaicov_neq.so``).
+``include/jaicov_parameters.h`` / ``include/jaicov_forms.h`` / ``include/jaicov_predict.h`` (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
 library has not been built, and every call fails with ``EngineError`` when no gfx950 device is present.
@@ -71,6 +71,10 @@ FORM_PARTIAL, FORM_TOO_SMALL, FORM_TOO_LARGE, FORM_DEGENERATE, FORM_SINGULAR, FO
 FORM_MEMBER_UNTESTED = 1
 FORM_MAX_ROWS, FORM_MAX_PARAMS, FORM_COLUMNS, FORM_QPP_COLUMNS, FORM_MEMBER_COLUMNS = 64, 7, 20, 28, 7
 FORM_REPORTED = (4, 4, 6, 7)      # parameters reported per kind: n d | c r | x0 t | c n r
+# include/jaicov_predict.h: predicted image points with their ellipses and the test of check measurements, read from the cofactor matrix
+PRED_EXPORTS = ["jaicov_pred_points", "jaicov_pred_check"]
+PRED_PARTIAL, PRED_NEGATIVE, PRED_NOT_FINITE, PRED_OBSERVED, PRED_SINGULAR = 1, 2, 4, 8, 16     # status bits of a pair or a group
+PRED_POINT_COLUMNS, PRED_CHECK_COLUMNS, PRED_GROUP_COLUMNS, PRED_MAX_GROUP = 10, 8, 4, 32
 # jaicov_dlt_restriction (DirectLinearTransformation.RestrictionType, DT:51-58 order) and the per-image status values
 DLT_IDENTICAL_PRINCIPLE_DISTANCE, DLT_ROTATION_WITHOUT_SHEAR, DLT_FIXED_PRINCIPLE_DISTANCE_X, DLT_FIXED_PRINCIPLE_DISTANCE_Y, \
     DLT_FIXED_PRINCIPAL_POINT_X, DLT_FIXED_PRINCIPAL_POINT_Y = range(6)
@@ -209,6 +213,8 @@ def load_library():
     L.jaicov_par_block.argtypes = [vp, _pi, C.c_int32, _pi, C.c_int32, _pd]
     L.jaicov_par_tests.argtypes = [vp, C.c_double, _pi, _pi, _pd, C.c_int32, _pd, _pi]
     L.jaicov_form_fit.argtypes = [vp, C.c_double, C.c_int32, _pi, _pi, _pi, C.c_int32, C.c_double, _pd, _pd, _pd, _pi, _pi, C.POINTER(C.c_float)]
+    L.jaicov_pred_points.argtypes = [vp, C.c_double, C.c_double, _pi, _pi, C.c_int32, _pd, _pi]
+    L.jaicov_pred_check.argtypes = [vp, C.c_double, _pi, _pi, _pd, _pd, C.c_int32, _pi, C.c_int32, _pd, _pi, _pd, _pi]
     L.jaicov_dlt_adjust.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pi, C.c_int32, C.c_int32, _pd, _pi, _pi, _pd]
     L.jaicov_isect_points.argtypes = [C.c_int32, _pi, _pi, _pd, _pd, C.c_int32, _pd, _pd, C.c_double, C.c_int32, C.c_double, C.c_int32,
                                       _pd, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
@@ -252,6 +258,11 @@ ColumnName = namedtuple("ColumnName", ["cls", "item", "component"])
 # member_status; kernel_ms: the kernel's time by events
 FormFits = namedtuple("FormFits", ["params", "sigma", "qpp", "omega", "dof", "T", "max_distance", "rms_distance", "iterations", "status",
                                    "begin", "v", "distance", "nabla", "T_member", "member_status", "kernel_ms"])
+# Engine.predict_image_points: one entry per pair (include/jaicov_predict.h); cof (n, 3): q_xx, q_xy, q_yy of J Qxx J'; ellipse (n, 2): A >= B
+ImagePrediction = namedtuple("ImagePrediction", ["xy", "cof", "sigma", "ellipse", "direction", "status"])
+# Engine.check_image_points: one entry per pair (d (n, 2), M (n, 3): m_xx, m_xy, m_yy) and one per group (dof = 2 m)
+ImageCheck = namedtuple("ImageCheck", ["d", "M", "q", "T_prio", "T_post", "status"])
+GroupCheck = namedtuple("GroupCheck", ["q", "T_prio", "T_post", "dof", "status"])
 
 
 def _p(a):
@@ -627,6 +638,53 @@ class Engine:
                                          points.ctypes.data_as(_pi), int(max_iterations), float(tol), _p(out), _p(qpp), _p(mem),
                                          status.ctypes.data_as(_pi), mstatus.ctypes.data_as(_pi), C.byref(ms)))
         return form_fits(out, qpp, mem[:M], status, mstatus[:M], begin, ms.value)
+
+    # image space (include/jaicov_predict.h) ------------------------------------------------------------------------------------------
+    def predict_image_points(self, sigma2, images, points, k2=1.0):
+        """Where the adjusted object point points[i] appears in image images[i] (any pair of the problem, observed or not): the model's
+        image coordinates at the current parameters, the 2 x 2 cofactor block J Qxx J', sigma_x and sigma_y, and the confidence
+        ellipse with the expansion factor k2.  Needs INVERT_FULL or INVERT_FULL_EXPANDED.  Returns an ImagePrediction."""
+        im = np.ascontiguousarray(images, np.int32).ravel(); pt = np.ascontiguousarray(points, np.int32).ravel()
+        if im.size != pt.size:
+            raise ValueError("images and points must run parallel")
+        n = im.size
+        out = np.zeros((n, PRED_POINT_COLUMNS)); status = np.zeros(n, np.int32)
+        self._chk(self.L.jaicov_pred_points(self._h, float(sigma2), float(k2), im.ctypes.data_as(_pi), pt.ctypes.data_as(_pi), n, _p(out),
+                                            status.ctypes.data_as(_pi)))
+        return ImagePrediction(out[:, 0:2], out[:, 2:5], out[:, 5:7], out[:, 7:9], out[:, 9], status)
+
+    def check_image_points(self, images, points, xy, var_x, var_y, rho=None, sigma2_post=None, groups=None):
+        """Tests measurements xy (n, 2) that were withheld from the adjustment: d = l - f(x), M = Q_ll + J Qxx J', q = d' inv(M) d,
+        T_prio = q / (2 s0) and T_post = q / (2 sigma2_post) per pair (sigma2_post None: the a-priori factor), and the joint test
+        of every group of `groups` (lists of 1 .. 32 pair indices that together run 0 .. n - 1 in order, or a CSR array).  No
+        quantile is evaluated.  Returns (ImageCheck, GroupCheck or None)."""
+        im = np.ascontiguousarray(images, np.int32).ravel(); pt = np.ascontiguousarray(points, np.int32).ravel()
+        n = im.size
+        l = np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2))
+        disp = np.empty((n, 3))
+        disp[:, 0] = var_x; disp[:, 1] = var_y; disp[:, 2] = 0.0 if rho is None else rho
+        if pt.size != n or l.shape[0] != n:
+            raise ValueError("images, points and xy must run parallel")
+        if sigma2_post is None:
+            sigma2_post = getattr(self, "_sigma2_build", self.fp.sigma2apriori)
+        begin = None
+        if groups is not None:
+            if len(groups) and np.ndim(groups[0]) > 0:
+                if [int(i) for g in groups for i in g] != list(range(n)):
+                    raise ValueError("the groups must hold the pairs 0 .. n - 1 in order")
+                begin = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int32)
+            else:
+                begin = np.ascontiguousarray(groups, np.int32).ravel()
+        G = 0 if begin is None else begin.size - 1
+        out = np.zeros((n, PRED_CHECK_COLUMNS)); status = np.zeros(n, np.int32)
+        gout = np.zeros((max(G, 1), PRED_GROUP_COLUMNS)); gstatus = np.zeros(max(G, 1), np.int32)
+        self._chk(self.L.jaicov_pred_check(self._h, float(sigma2_post), im.ctypes.data_as(_pi), pt.ctypes.data_as(_pi), _p(l), _p(disp), n,
+                                           None if begin is None else begin.ctypes.data_as(_pi), G, _p(out), status.ctypes.data_as(_pi),
+                                           _p(gout), gstatus.ctypes.data_as(_pi)))
+        pairs = ImageCheck(out[:, 0:2], out[:, 2:5], out[:, 5], out[:, 6], out[:, 7], status)
+        if begin is None:
+            return pairs, None
+        return pairs, GroupCheck(gout[:G, 0], gout[:G, 1], gout[:G, 2], gout[:G, 3].astype(np.int32), gstatus[:G])
 
     def get_rows(self, ip_begin, ip_count):
         w = np.zeros((ip_count, 2)); A = np.zeros((ip_count, 2, KROW))

@@ -213,6 +213,21 @@ PYBIND11_MODULE(_jaicov_host, m) {
                                   py::array_t<int32_t>((py::ssize_t)f.memberStatus.size(), f.memberStatus.data()));
         }, py::arg("sigma2"), py::arg("formType"), py::arg("formBegin"), py::arg("formPoint"), py::arg("maxIterations") = 20, py::arg("tol") = 0.0,
              "(table (n, 20), qpp (n, 28), members (M, 7), status (n,), member status (M,)) of the forms through object points (include/jaicov_forms.h)")
+        .def("predictImagePoints", [](BundleAdjustment &b, double sigma2, std::vector<int32_t> images, std::vector<int32_t> points, double k2) {
+            auto t = b.predictImagePoints(sigma2, images, points, k2);
+            return py::make_tuple(py::array_t<double>({t.status.size(), (size_t)t.columns}, t.table.data()),
+                                  py::array_t<int32_t>((py::ssize_t)t.status.size(), t.status.data()));
+        }, py::arg("sigma2"), py::arg("images"), py::arg("points"), py::arg("k2") = 1.0,
+             "(table (n, 10), status (n,)) of the predicted image points of the pairs (image, point) (include/jaicov_predict.h)")
+        .def("checkImagePoints", [](BundleAdjustment &b, std::vector<int32_t> images, std::vector<int32_t> points, std::vector<double> xy,
+                                    std::vector<double> disp, double sigma2Post, std::vector<int32_t> groupBegin) {
+            auto c = b.checkImagePoints(images, points, xy, disp, sigma2Post, groupBegin);
+            return py::make_tuple(py::array_t<double>({c.status.size(), (size_t)JAICOV_PRED_CHECK_COLUMNS}, c.table.data()),
+                                  py::array_t<int32_t>((py::ssize_t)c.status.size(), c.status.data()),
+                                  py::array_t<double>({c.groupStatus.size(), (size_t)JAICOV_PRED_GROUP_COLUMNS}, c.groups.data()),
+                                  py::array_t<int32_t>((py::ssize_t)c.groupStatus.size(), c.groupStatus.data()));
+        }, py::arg("images"), py::arg("points"), py::arg("xy"), py::arg("disp"), py::arg("sigma2Post") = 0.0, py::arg("groupBegin") = std::vector<int32_t>(),
+             "(table (n, 8), status (n,), groups (G, 4), group status (G,)) of the test of check measurements (include/jaicov_predict.h)")
         .def("useCentroidedCoordinates", &BundleAdjustment::useCentroidedCoordinates)
         .def("centroidCoordinates", &BundleAdjustment::centroidCoordinates)
         .def("applyAposterioriVarianceOfUnitWeight", &BundleAdjustment::applyAposterioriVarianceOfUnitWeight)

@@ -640,6 +640,40 @@ BundleAdjustment::FormFits BundleAdjustment::fitForms(double sigma2, const std::
     return f;
 }
 
+// include/jaicov_predict.h on the engine of the last estimateModel
+BundleAdjustment::ImageTable BundleAdjustment::predictImagePoints(double sigma2, const std::vector<int32_t> &images, const std::vector<int32_t> &points,
+                                                                  double k2) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    if (images.size() != points.size()) throw std::runtime_error("predictImagePoints: images and points must run parallel");
+    ImageTable t;
+    t.columns = JAICOV_PRED_POINT_COLUMNS;
+    const size_t n = images.size();
+    t.table.resize(n * t.columns);
+    t.status.resize(n);
+    const int rc = jaicov_pred_points(engine_, sigma2, k2, images.data(), points.data(), (int32_t)n, t.table.data(), t.status.data());
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_pred_points: ") + jaicov_neq_last_error(engine_));
+    return t;
+}
+
+BundleAdjustment::ImageCheck BundleAdjustment::checkImagePoints(const std::vector<int32_t> &images, const std::vector<int32_t> &points,
+                                                                const std::vector<double> &xy, const std::vector<double> &disp, double sigma2Post,
+                                                                const std::vector<int32_t> &groupBegin) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    const size_t n = images.size(), G = groupBegin.empty() ? 0 : groupBegin.size() - 1;
+    if (points.size() != n || xy.size() != 2 * n || disp.size() != 3 * n)
+        throw std::runtime_error("checkImagePoints: points, xy (2 per pair) and disp (3 per pair) must run parallel to images");
+    ImageCheck c;
+    c.table.resize(n * JAICOV_PRED_CHECK_COLUMNS);
+    c.status.resize(n);
+    c.groups.resize(G * JAICOV_PRED_GROUP_COLUMNS);
+    c.groupStatus.resize(G);
+    const int rc = jaicov_pred_check(engine_, sigma2Post > 0.0 ? sigma2Post : sigma2apriori_, images.data(), points.data(), xy.data(), disp.data(),
+                                     (int32_t)n, G ? groupBegin.data() : nullptr, (int32_t)G, c.table.data(), c.status.data(), c.groups.data(),
+                                     c.groupStatus.data());
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_pred_check: ") + jaicov_neq_last_error(engine_));
+    return c;
+}
+
 // CTEO:49-121: rows, coordinates and sigma2 J Qxx J' on the device (jaicov_xform_run), the results copied back
 void CoordinateTransformationExteriorOrientation::transform(const std::vector<ObjectCoordinate *> &objectCoordinatesToTransform,
                                                             const std::vector<std::pair<Image *, std::vector<Image *>>> &imagesToAlign,

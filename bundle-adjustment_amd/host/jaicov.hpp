@@ -40,6 +40,7 @@
 #include "../../include/jaicov_precision.h"
 #include "../../include/jaicov_parameters.h"
 #include "../../include/jaicov_forms.h"
+#include "../../include/jaicov_predict.h"
 
 namespace jaicov::host {
 
@@ -595,6 +596,25 @@ public:
     };
     FormFits fitForms(double sigma2, const std::vector<int32_t> &formType, const std::vector<int32_t> &formBegin,
                       const std::vector<int32_t> &formPoint, int maxIterations = 20, double tol = 0.0) const;
+    // Image space (include/jaicov_predict.h), read on the device from the cofactor matrix of the last estimateModel; needs
+    // MatrixInversion.FULL.  A pair is (image, point): the images in the order of flat.eo_col, ObjectCoordinate::index.
+    // predictImagePoints: where the adjusted point appears in the image, with J Qxx J', sigmas and the ellipse (rows of JAICOV_PRED_POINT_COLUMNS).
+    struct ImageTable {
+        int columns = 0;
+        std::vector<double> table;
+        std::vector<int32_t> status;             // JAICOV_PRED_* bits of every pair
+    };
+    ImageTable predictImagePoints(double sigma2, const std::vector<int32_t> &images, const std::vector<int32_t> &points, double k2 = 1.0) const;
+    // checkImagePoints: the test of measurements xy (two per pair) that were withheld from the adjustment, with their dispersions
+    // disp (var_x, var_y, rho per pair); sigma2Post <= 0: the a-priori factor.  groupBegin empty: no groups; otherwise a CSR over the pairs.
+    struct ImageCheck {
+        std::vector<double> table;               // rows of JAICOV_PRED_CHECK_COLUMNS: d, M, q, T_prio, T_post
+        std::vector<int32_t> status;
+        std::vector<double> groups;              // rows of JAICOV_PRED_GROUP_COLUMNS: q_G, T_prio, T_post, 2 m
+        std::vector<int32_t> groupStatus;
+    };
+    ImageCheck checkImagePoints(const std::vector<int32_t> &images, const std::vector<int32_t> &points, const std::vector<double> &xy,
+                                const std::vector<double> &disp, double sigma2Post = 0.0, const std::vector<int32_t> &groupBegin = {}) const;
     const std::string &lastError() const { return lastError_; }
     jaicov_engine *nativeEngine() const { return engine_; }     // the engine of the last estimateModel (null before)
 
