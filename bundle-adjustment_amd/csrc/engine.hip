@@ -22,6 +22,7 @@
 #include "devbuf.h"
 #include "forms.h"
 #include "predict.h"
+#include "newpoints.h"
 #include "gemm_f64.h"
 #include "parameters.h"
 #include "precision.h"

@@ -1,5 +1,5 @@
 // The one interface between engine.hip (owner of jaicov_engine) and whatever reads the cofactor matrix an inverting solve leaves on
-// the device: transform.hip, reliability.hip, datum.hip (the one writer), precision.hip, parameters.hip, forms.hip and predict.hip.  A consumer adds a state struct of its own,
+// the device: transform.hip, reliability.hip, datum.hip (the one writer), precision.hip, parameters.hip, forms.hip, predict.hip and newpoints.hip.  A consumer adds a state struct of its own,
 // a slot for it in QSlots and its guards; the facts the guards test come from here.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,6 +23,7 @@ struct PrecisionState;   // precision.h
 struct ParamState;       // parameters.h
 struct FormState;        // forms.h
 struct PredictState;     // predict.h
+struct NewPointState;    // newpoints.h
 
 // The engine's slots for what its consumers keep.  A result (xform, rel) stays until the next run of its family or its release, a
 // later inverting solve included; an inverting solve withdraws the S of the datum state alone (datum_state_invalidate).
@@ -34,6 +35,7 @@ struct QSlots {
     std::unique_ptr<ParamState> par;         // work buffers of the jaicov_par_* calls
     std::unique_ptr<FormState> form;         // work buffers of jaicov_form_fit
     std::unique_ptr<PredictState> pred;      // work buffers of the jaicov_pred_* calls
+    std::unique_ptr<NewPointState> newpt;    // work buffers of jaicov_newpt_intersect
 };
 
 // What a consumer sees of an engine.  Pointers stay owned by the engine.

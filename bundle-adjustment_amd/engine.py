@@ -2,7 +2,8 @@
 ``include/jaicov_dlt.h`` / ``include/jaicov_reliability.h`` / ``include/jaicov_reliability_points.h`` /
 ``include/jaicov_datum.h`` / ``include/jaicov_intersect.h`` / ``include/jaicov_resect.h`` /
 ``include/jaicov_relorient.h`` / ``include/jaicov_simil.h`` / ``include/jaicov_lens.h`` / ``include/jaicov_precision.h`` /
-``include/jaicov_parameters.h`` / ``include/jaicov_forms.h`` / ``include/jaicov_predict.h`` (``csrc/libjaicov_neq.so``).
+``include/jaicov_parameters.h`` / ``include/jaicov_forms.h`` / ``include/jaicov_predict.h`` /
+``include/jaicov_newpoints.h`` (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
 library has not been built, and every call fails with ``EngineError`` when no gfx950 device is present.
@@ -75,6 +76,12 @@ FORM_REPORTED = (4, 4, 6, 7)      # parameters reported per kind: n d | c r | x0
 PRED_EXPORTS = ["jaicov_pred_points", "jaicov_pred_check"]
 PRED_PARTIAL, PRED_NEGATIVE, PRED_NOT_FINITE, PRED_OBSERVED, PRED_SINGULAR = 1, 2, 4, 8, 16     # status bits of a pair or a group
 PRED_POINT_COLUMNS, PRED_CHECK_COLUMNS, PRED_GROUP_COLUMNS, PRED_MAX_GROUP = 10, 8, 4, 32
+# include/jaicov_newpoints.h: object points that were not part of the adjustment, intersected in the adjusted block with its full Qxx
+NEWPT_EXPORTS = ["jaicov_newpt_intersect"]
+NEWPT_PARTIAL, NEWPT_NOT_CONVERGED, NEWPT_TOO_FEW_RAYS, NEWPT_TOO_MANY, NEWPT_SINGULAR, NEWPT_NOT_FINITE = 1, 2, 4, 8, 16, 32   # bits of a point
+NEWPT_FAILED = NEWPT_TOO_FEW_RAYS | NEWPT_TOO_MANY | NEWPT_SINGULAR | NEWPT_NOT_FINITE
+NEWPT_PAIR_PARTIAL, NEWPT_PAIR_NEGATIVE, NEWPT_PAIR_NOT_FINITE, NEWPT_PAIR_DEGENERATE = 1, 2, 4, 8                             # bits of a pair
+NEWPT_COLUMNS, NEWPT_PAIR_COLUMNS, NEWPT_MAX_RAYS, NEWPT_MAX_COLS = 20, 7, 64, 448
 # jaicov_dlt_restriction (DirectLinearTransformation.RestrictionType, DT:51-58 order) and the per-image status values
 DLT_IDENTICAL_PRINCIPLE_DISTANCE, DLT_ROTATION_WITHOUT_SHEAR, DLT_FIXED_PRINCIPLE_DISTANCE_X, DLT_FIXED_PRINCIPLE_DISTANCE_Y, \
     DLT_FIXED_PRINCIPAL_POINT_X, DLT_FIXED_PRINCIPAL_POINT_Y = range(6)
@@ -215,6 +222,7 @@ def load_library():
     L.jaicov_form_fit.argtypes = [vp, C.c_double, C.c_int32, _pi, _pi, _pi, C.c_int32, C.c_double, _pd, _pd, _pd, _pi, _pi, C.POINTER(C.c_float)]
     L.jaicov_pred_points.argtypes = [vp, C.c_double, C.c_double, _pi, _pi, C.c_int32, _pd, _pi]
     L.jaicov_pred_check.argtypes = [vp, C.c_double, _pi, _pi, _pd, _pd, C.c_int32, _pi, C.c_int32, _pd, _pi, _pd, _pi]
+    L.jaicov_newpt_intersect.argtypes = [vp, C.c_double, C.c_int32, _pi, _pi, _pd, _pd, _pd, C.c_int32, _pi, C.c_int32, _pd, _pi, _pi, _pd, _pd, _pi]
     L.jaicov_dlt_adjust.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pi, C.c_int32, C.c_int32, _pd, _pi, _pi, _pd]
     L.jaicov_isect_points.argtypes = [C.c_int32, _pi, _pi, _pd, _pd, C.c_int32, _pd, _pd, C.c_double, C.c_int32, C.c_double, C.c_int32,
                                       _pd, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
@@ -263,6 +271,10 @@ ImagePrediction = namedtuple("ImagePrediction", ["xy", "cof", "sigma", "ellipse"
 # Engine.check_image_points: one entry per pair (d (n, 2), M (n, 3): m_xx, m_xy, m_yy) and one per group (dof = 2 m)
 ImageCheck = namedtuple("ImageCheck", ["d", "M", "q", "T_prio", "T_post", "status"])
 GroupCheck = namedtuple("GroupCheck", ["q", "T_prio", "T_post", "dof", "status"])
+# Engine.intersect_new_points: one entry per new point (cof_meas, cof (n, 6): xx xy xz yy yz zz of Q_meas and of Q_XX = Q_meas + Q_sys;
+# ray_w (n_rays, 2)) and one per pair (lengths (n_pairs, 7): L, sigma_L, sigma of D_X, D_Y, D_Z, q_L, q_L without the cross block)
+NewPoints = namedtuple("NewPoints", ["xyz", "cof_meas", "cof", "sigma", "omega", "dof", "status", "iterations", "ray_w", "lengths",
+                                     "length_status"])
 
 
 def _p(a):
@@ -685,6 +697,52 @@ class Engine:
         if begin is None:
             return pairs, None
         return pairs, GroupCheck(gout[:G, 0], gout[:G, 1], gout[:G, 2], gout[:G, 3].astype(np.int32), gstatus[:G])
+
+    # object space (include/jaicov_newpoints.h) -------------------------------------------------------------------------------------
+    def new_point_start_values(self, ray_begin, ray_image, xy, disp):
+        """Start values (n, 3) of new points for intersect_new_points: the measurements reduced to the distortion-free camera
+        (lens_correct, the distance-dependent coefficients left out) and intersected with the current orientations
+        (intersect_points).  NaN where that intersection fails."""
+        fp = self.fp
+        rb = np.ascontiguousarray(ray_begin, np.int32).ravel(); ri = np.ascontiguousarray(ray_image, np.int32).ravel()
+        if rb.size < 2 or ri.size == 0:
+            return np.full((max(rb.size - 1, 0), 3), np.nan)
+        v = self.get_parameters()
+        io = v[fp.slot_io(0):fp.slot_io(0) + 3 * fp.n_cameras].reshape(-1, 3)
+        tables = lens_tables_without_distance(fp.cam_dist_begin, fp.dist_kind, fp.dist_order, v[fp.slot_dist(0):fp.slot_dist(0) + fp.n_dist])
+        cam = np.asarray(fp.image_camera)[ri]
+        l = np.asarray(xy, np.float64).reshape(-1, 2); dv = np.asarray(disp, np.float64).reshape(-1, 3)
+        cxy, cvar, lst = lens_correct(l, cam, io, fp.cam_r0, *tables, var=dv)[:3]
+        ok = lst <= LENS_NOT_CONVERGED
+        cxy = np.where(ok[:, None], cxy, l); cvar = np.where(ok[:, None], cvar, dv)
+        out, st = intersect_points(rb, ri, cxy, cvar, io[np.asarray(fp.image_camera)], v[fp.slot_eo(0):].reshape(-1, 6),
+                                   sigma2apriori=getattr(self, "_sigma2_build", fp.sigma2apriori), min_rays=2)[:2]
+        return np.where((st <= ISECT_NOT_CONVERGED)[:, None], out[:, :3], np.nan)
+
+    def intersect_new_points(self, sigma2, ray_begin, ray_image, xy, disp, start=None, pairs=None, max_iterations=20):
+        """Object points that were not part of the adjustment, from measurements xy (n_rays, 2) with the dispersions disp (n_rays, 3:
+        var_x, var_y, rho) in the images ray_image of the adjusted block; ray_begin (n + 1,) is the CSR of the points' rays.  The model
+        is the adjustment's own rows; the cofactors carry the share of the cameras and stations from Qxx (cof), beside the
+        measurement noise alone (cof_meas).  start None: new_point_start_values.  pairs (n_pairs, 2): lengths between two new points
+        (members >= 0) or a new point and object point P of the block (member -1 - P), with their correlations.  Needs INVERT_FULL or
+        INVERT_FULL_EXPANDED.  Returns a NewPoints."""
+        rb = np.ascontiguousarray(ray_begin, np.int32).ravel(); ri = np.ascontiguousarray(ray_image, np.int32).ravel()
+        n = max(rb.size - 1, 0); R = ri.size
+        l = np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2)); dv = np.ascontiguousarray(np.asarray(disp, np.float64).reshape(-1, 3))
+        if l.shape[0] != R or dv.shape[0] != R or (rb.size and rb[-1] != R):
+            raise ValueError("ray_image, xy and disp must run parallel, and ray_begin must end at their number")
+        x0 = self.new_point_start_values(rb, ri, l, dv) if start is None else np.asarray(start, np.float64).reshape(-1, 3)
+        x0 = np.ascontiguousarray(x0)
+        if x0.shape[0] != n:
+            raise ValueError("one start value per point")
+        pr = np.zeros((0, 2), np.int32) if pairs is None else np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        G = pr.shape[0]
+        out = np.zeros((n, NEWPT_COLUMNS)); status = np.zeros(n, np.int32); iters = np.zeros(n, np.int32); rw = np.zeros((R, 2))
+        pout = np.zeros((max(G, 1), NEWPT_PAIR_COLUMNS)); pst = np.zeros(max(G, 1), np.int32)
+        self._chk(self.L.jaicov_newpt_intersect(self._h, float(sigma2), n, rb.ctypes.data_as(_pi), ri.ctypes.data_as(_pi), _p(l), _p(dv), _p(x0),
+                                                int(max_iterations), pr.ctypes.data_as(_pi), G, _p(out), status.ctypes.data_as(_pi),
+                                                iters.ctypes.data_as(_pi), _p(rw), _p(pout), pst.ctypes.data_as(_pi)))
+        return NewPoints(out[:, 0:3], out[:, 3:9], out[:, 9:15], out[:, 17:20], out[:, 15], out[:, 16], status, iters, rw, pout[:G], pst[:G])
 
     def get_rows(self, ip_begin, ip_count):
         w = np.zeros((ip_count, 2)); A = np.zeros((ip_count, 2, KROW))

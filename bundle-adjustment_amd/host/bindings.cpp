@@ -228,6 +228,19 @@ PYBIND11_MODULE(_jaicov_host, m) {
                                   py::array_t<int32_t>((py::ssize_t)c.groupStatus.size(), c.groupStatus.data()));
         }, py::arg("images"), py::arg("points"), py::arg("xy"), py::arg("disp"), py::arg("sigma2Post") = 0.0, py::arg("groupBegin") = std::vector<int32_t>(),
              "(table (n, 8), status (n,), groups (G, 4), group status (G,)) of the test of check measurements (include/jaicov_predict.h)")
+        .def("intersectNewPoints", [](BundleAdjustment &b, double sigma2, std::vector<int32_t> rayBegin, std::vector<int32_t> rayImage,
+                                      std::vector<double> xy, std::vector<double> disp, std::vector<double> start, std::vector<int32_t> pairs,
+                                      int maxIterations) {
+            auto r = b.intersectNewPoints(sigma2, rayBegin, rayImage, xy, disp, start, pairs, maxIterations);
+            return py::make_tuple(py::array_t<double>({r.status.size(), (size_t)JAICOV_NEWPT_COLUMNS}, r.table.data()),
+                                  py::array_t<int32_t>((py::ssize_t)r.status.size(), r.status.data()),
+                                  py::array_t<int32_t>((py::ssize_t)r.iterations.size(), r.iterations.data()),
+                                  py::array_t<double>({r.rayW.size() / 2, (size_t)2}, r.rayW.data()),
+                                  py::array_t<double>({r.lengthStatus.size(), (size_t)JAICOV_NEWPT_PAIR_COLUMNS}, r.lengths.data()),
+                                  py::array_t<int32_t>((py::ssize_t)r.lengthStatus.size(), r.lengthStatus.data()));
+        }, py::arg("sigma2"), py::arg("rayBegin"), py::arg("rayImage"), py::arg("xy"), py::arg("disp"), py::arg("start"),
+             py::arg("pairs") = std::vector<int32_t>(), py::arg("maxIterations") = 20,
+             "(table (n, 20), status (n,), iterations (n,), ray_w (R, 2), lengths (G, 7), length status (G,)) of new object points (include/jaicov_newpoints.h)")
         .def("useCentroidedCoordinates", &BundleAdjustment::useCentroidedCoordinates)
         .def("centroidCoordinates", &BundleAdjustment::centroidCoordinates)
         .def("applyAposterioriVarianceOfUnitWeight", &BundleAdjustment::applyAposterioriVarianceOfUnitWeight)

@@ -674,6 +674,30 @@ BundleAdjustment::ImageCheck BundleAdjustment::checkImagePoints(const std::vecto
     return c;
 }
 
+// include/jaicov_newpoints.h on the engine of the last estimateModel
+BundleAdjustment::NewPoints BundleAdjustment::intersectNewPoints(double sigma2, const std::vector<int32_t> &rayBegin, const std::vector<int32_t> &rayImage,
+                                                                 const std::vector<double> &xy, const std::vector<double> &disp,
+                                                                 const std::vector<double> &start, const std::vector<int32_t> &pairs,
+                                                                 int maxIterations) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    const size_t n = rayBegin.empty() ? 0 : rayBegin.size() - 1, R = rayImage.size(), G = pairs.size() / 2;
+    if (xy.size() != 2 * R || disp.size() != 3 * R || start.size() != 3 * n || pairs.size() % 2 || (n > 0 && (size_t)rayBegin.back() != R) ||
+        (n == 0 && R > 0))
+        throw std::runtime_error("intersectNewPoints: xy (2 per ray), disp (3 per ray) and start (3 per point) must fit rayBegin and rayImage");
+    NewPoints r;
+    r.table.resize(n * JAICOV_NEWPT_COLUMNS);
+    r.status.resize(n);
+    r.iterations.resize(n);
+    r.rayW.resize(2 * R);
+    r.lengths.resize(G * JAICOV_NEWPT_PAIR_COLUMNS);
+    r.lengthStatus.resize(G);
+    const int rc = jaicov_newpt_intersect(engine_, sigma2, (int32_t)n, rayBegin.data(), rayImage.data(), xy.data(), disp.data(), start.data(),
+                                          maxIterations, G ? pairs.data() : nullptr, (int32_t)G, r.table.data(), r.status.data(),
+                                          r.iterations.data(), r.rayW.data(), r.lengths.data(), r.lengthStatus.data());
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_newpt_intersect: ") + jaicov_neq_last_error(engine_));
+    return r;
+}
+
 // CTEO:49-121: rows, coordinates and sigma2 J Qxx J' on the device (jaicov_xform_run), the results copied back
 void CoordinateTransformationExteriorOrientation::transform(const std::vector<ObjectCoordinate *> &objectCoordinatesToTransform,
                                                             const std::vector<std::pair<Image *, std::vector<Image *>>> &imagesToAlign,

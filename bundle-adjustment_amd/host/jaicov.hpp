@@ -41,6 +41,7 @@
 #include "../../include/jaicov_parameters.h"
 #include "../../include/jaicov_forms.h"
 #include "../../include/jaicov_predict.h"
+#include "../../include/jaicov_newpoints.h"
 
 namespace jaicov::host {
 
@@ -615,6 +616,21 @@ public:
     };
     ImageCheck checkImagePoints(const std::vector<int32_t> &images, const std::vector<int32_t> &points, const std::vector<double> &xy,
                                 const std::vector<double> &disp, double sigma2Post = 0.0, const std::vector<int32_t> &groupBegin = {}) const;
+    // Object space (include/jaicov_newpoints.h): object points that were not part of the adjustment, intersected from measurements
+    // xy (two per ray) with the dispersions disp (var_x, var_y, rho per ray) in the images rayImage (the order of flat.eo_col) of the
+    // adjusted block, read on the device from the cofactor matrix of the last estimateModel; needs MatrixInversion.FULL.  rayBegin is
+    // the CSR of the points' rays, start holds X, Y, Z of every point.  pairs (two members per pair; >= 0: a new point of the call,
+    // -1 - P: object point P of the block) asks for lengths with their correlations.
+    struct NewPoints {
+        std::vector<double> table;               // rows of JAICOV_NEWPT_COLUMNS: X Y Z, Q_meas, Q_XX, Omega, 2m - 3, sigmas
+        std::vector<int32_t> status, iterations; // JAICOV_NEWPT_* bits and the Gauss-Newton steps of every point
+        std::vector<double> rayW;                // the final misclosures, two per ray
+        std::vector<double> lengths;             // rows of JAICOV_NEWPT_PAIR_COLUMNS: L, sigma_L, sigma of D, q_L, q_L without the cross block
+        std::vector<int32_t> lengthStatus;       // JAICOV_NEWPT_PAIR_* bits
+    };
+    NewPoints intersectNewPoints(double sigma2, const std::vector<int32_t> &rayBegin, const std::vector<int32_t> &rayImage,
+                                 const std::vector<double> &xy, const std::vector<double> &disp, const std::vector<double> &start,
+                                 const std::vector<int32_t> &pairs = {}, int maxIterations = 20) const;
     const std::string &lastError() const { return lastError_; }
     jaicov_engine *nativeEngine() const { return engine_; }     // the engine of the last estimateModel (null before)
 
