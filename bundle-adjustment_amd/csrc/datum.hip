@@ -133,8 +133,7 @@ extern "C" int jaicov_datum_transform(jaicov_engine *e, const uint8_t *point_dat
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
     if (v.d == 0) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "datum transformation: the network has no datum defect (d = 0)");
-    if (v.sharded) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "datum transformation on a sharded engine");
-    if (!v.have_q) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
+    TRY(q_guard(v, "datum transformation on a sharded engine"));
     if (!point_datum || n_points != v.n_points) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "point_datum must hold one flag per object point");
     const int n = v.order, d = v.d, nbk = (n + 127) / 128, np = nbk * 128;
     std::vector<double> B;
@@ -163,8 +162,7 @@ extern "C" int jaicov_datum_transform(jaicov_engine *e, const uint8_t *point_dat
             Z[(size_t)i * d + a] = s;
         }
     // work buffers, kept with the engine
-    if (!v.slot->datum) v.slot->datum.reset(new DatumState());
-    DatumState *st = v.slot->datum.get();
+    DatumState *st = q_state(v.slot->datum);
     HIPE(*v.err, st->work.reserve((size_t)d * np * 4 + (size_t)nbk * nbk * 128 * d));
     double *dB = st->work.get(), *dY = dB + (size_t)d * np, *dZY = dY + (size_t)d * np, *dP = dZY + (size_t)2 * d * np;
     HIPE(*v.err, hipMemcpyAsync(dB, B.data(), (size_t)d * np * sizeof(double), hipMemcpyHostToDevice, v.stream));

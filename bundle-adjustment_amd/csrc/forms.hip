@@ -31,12 +31,6 @@ constexpr int FORM_TRI = FORM_R * (FORM_R + 1) / 2;
 constexpr int FORM_SWEEPS = 10;
 static_assert(FORM_R == 64, "one row per lane of one wave");
 
-// entry (i, j) of the symmetric matrix from its lower part; a fixed coordinate (column < 0) is a zero row and column
-__device__ __forceinline__ double form_q(const double *__restrict__ Q, long ld, int ci, int cj) {
-    if (ci < 0 || cj < 0) return 0.0;
-    return ci >= cj ? Q[(long)ci * ld + cj] : Q[(long)cj * ld + ci];
-}
-
 // e1 = (e_k x n) / |e_k x n| with k the index of the smallest |n_k| (the first among equals), e2 = n x e1
 __device__ inline void form_basis(double n0, double n1, double n2, double *e1, double *e2) {
     int k = 0;
@@ -89,7 +83,6 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
     __shared__ double X[3][FORM_R], Vv[3][FORM_R], Bt[3][FORM_R], Bl[3][FORM_R], At[7][FORM_R], Sc[FORM_R], Sv[FORM_R], Lm[FORM_R];
     __shared__ double Nl[28], Jm[7][6];
     __shared__ int col[3][FORM_R];
-    const double EPS = ldexp(1.0, -53);
     const int g = blockIdx.x, lane = threadIdx.x;
     const int type = wave_uniform(ftype[g]);
     const int m0 = wave_uniform(fbegin[g]), k = wave_uniform(fbegin[g + 1]) - m0;
@@ -247,7 +240,7 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
 #pragma unroll
                 for (int a = 0; a < 3; a++)
 #pragma unroll
-                    for (int b = 0; b < 3; b++) q[a][b] = form_q(Q, ld, col[a][i], col[b][j]);
+                    for (int b = 0; b < 3; b++) q[a][b] = q_at(Q, ld, col[a][i], col[b][j]);
                 for (int qa = 0; qa < c; qa++)
                     for (int qb = 0; qb < c; qb++) {
                         const int r = c * i + qa, s = c * j + qb;
@@ -261,34 +254,11 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
             }
         }
         __syncthreads();
-        // powers of two bring the diagonal into [1, 4), then the Jacobi scaling; NaN in z unless every value is finite
+        // NaN in z unless every value is finite
         double z = w * 0.0;
 #pragma unroll
         for (int a = 0; a < 6; a++) z += Ar[a] * 0.0;
-        if (lane < m) {
-            const double qd = U[ix(lane, lane)];
-            Sc[lane] = (qd > 0.0 && isfinite(qd)) ? ldexp(1.0, -(ilogb(qd) >> 1)) : 1.0;
-        }
-        __syncthreads();
-        for (int i = 0; i < m; i++) {
-            const int j = i + lane;
-            if (j < m) {
-                const double a = U[ix(i, j)];
-                z += a * 0.0;
-                U[ix(i, j)] = a * (Sc[i] * Sc[j]);
-            }
-        }
-        __syncthreads();
-        if (lane < m) {
-            const double a = U[ix(lane, lane)];
-            Sv[lane] = a > EPS ? 1.0 / sqrt(a) : 1.0;
-        }
-        __syncthreads();
-        for (int i = 0; i < m; i++) {
-            const int j = i + lane;
-            if (j < m) U[ix(i, j)] = U[ix(i, j)] * (Sv[i] * Sv[j]);
-        }
-        __syncthreads();
+        wave_equilibrate_lds(m, U, Sc, Sv, z, lane);
         if (wave_uniform(__any(!(z == 0.0)) != 0)) { fail(JAICOV_FORM_NOT_FINITE); return; }
         if (SERIAL) {
             if (lane < m) { Bl[0][lane] = 0.0; Bl[1][lane] = 0.0; }
@@ -360,9 +330,9 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
             for (int j = 0; j < k; j++) {
                 const int j0 = col[0][j], j1 = col[1][j], j2 = col[2][j];
                 const double b0 = Bl[0][j], b1 = Bl[1][j], b2 = Bl[2][j];
-                v0 += (form_q(Q, ld, ca, j0) * b0 + form_q(Q, ld, ca, j1) * b1) + form_q(Q, ld, ca, j2) * b2;
-                v1 += (form_q(Q, ld, cb, j0) * b0 + form_q(Q, ld, cb, j1) * b1) + form_q(Q, ld, cb, j2) * b2;
-                v2 += (form_q(Q, ld, cc, j0) * b0 + form_q(Q, ld, cc, j1) * b1) + form_q(Q, ld, cc, j2) * b2;
+                v0 += (q_at(Q, ld, ca, j0) * b0 + q_at(Q, ld, ca, j1) * b1) + q_at(Q, ld, ca, j2) * b2;
+                v1 += (q_at(Q, ld, cb, j0) * b0 + q_at(Q, ld, cb, j1) * b1) + q_at(Q, ld, cb, j2) * b2;
+                v2 += (q_at(Q, ld, cc, j0) * b0 + q_at(Q, ld, cc, j1) * b1) + q_at(Q, ld, cc, j2) * b2;
             }
             Vv[0][lane] = v0; Vv[1][lane] = v1; Vv[2][lane] = v2;
         }
@@ -552,17 +522,6 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
     }
 }
 
-static int form_common(const QView &v) {
-    if (v.sharded) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "forms on a sharded engine");
-    if (!v.have_q) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
-    return JAICOV_OK;
-}
-
-static FormState *form_state(const QView &v) {
-    if (!v.slot->form) v.slot->form.reset(new FormState());
-    return v.slot->form.get();
-}
-
 }  // namespace jaicov
 
 using namespace jaicov;
@@ -572,13 +531,11 @@ static int form_run(jaicov_engine *e, bool serial, double sigma2, int32_t n_form
                     int32_t *status, int32_t *member_status, float *ms_out) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
-    TRY(form_common(v));
+    TRY(q_guard(v, "forms on a sharded engine"));
     if (!form_type || !form_begin || !out || !status || n_forms < 0) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: NULL argument or a negative count");
     for (int g = 0; g < n_forms; g++)
         if (form_type[g] < JAICOV_FORM_PLANE || form_type[g] > JAICOV_FORM_CIRCLE) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: unknown form type");
-    if (form_begin[0] != 0) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: form_begin must ascend from 0");
-    for (int g = 0; g < n_forms; g++)
-        if (form_begin[g + 1] < form_begin[g]) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: form_begin must ascend from 0");
+    if (!ranges_ok(n_forms, form_begin)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: form_begin must ascend from 0");
     const int n = n_forms, M = form_begin[n_forms];
     if (M > 0 && !form_point) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: NULL form_point");
     for (int i = 0; i < M; i++)
@@ -602,10 +559,10 @@ static int form_run(jaicov_engine *e, bool serial, double sigma2, int32_t n_form
         for (int i = form_begin[g]; i < form_begin[g + 1]; i++) {
             tab[o_point + i] = form_point[i];
             for (int a = 0; a < 3; a++) {
-                const int c = (*v.slot_col)[3 * (size_t)form_point[i] + a];
-                if (c >= v.order) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "forms: a member's columns are not in the reduced cofactor matrix");
+                int c;
+                TRY(q_column(v, 3 * (size_t)form_point[i] + a, "forms: a member's columns are not in the reduced cofactor matrix", &c));
                 if (c < 0) tab[o_host + g] |= JAICOV_FORM_PARTIAL;
-                tab[o_cols + 3 * (size_t)i + a] = c < 0 ? -1 : c;
+                tab[o_cols + 3 * (size_t)i + a] = c;
             }
         }
     }
@@ -613,18 +570,15 @@ static int form_run(jaicov_engine *e, bool serial, double sigma2, int32_t n_form
     if (ms_out) *ms_out = 0.f;
     if (n == 0) return JAICOV_OK;
     HIPE(*v.err, hipSetDevice(v.device));
-    FormState *st = form_state(v);
+    FormState *st = q_state(v.slot->form);
     HIPE(*v.err, st->tab.reserve(n_tab + n + Mx));
     HIPE(*v.err, st->out.reserve((size_t)(JAICOV_FORM_COLUMNS + JAICOV_FORM_QPP_COLUMNS) * n + JAICOV_FORM_MEMBER_COLUMNS * Mx));
     int32_t *d_tab = st->tab.get(), *d_status = d_tab + n_tab, *d_mstatus = d_status + n;
     double *d_out = st->out.get(), *d_qpp = d_out + (size_t)JAICOV_FORM_COLUMNS * n, *d_mem = d_qpp + (size_t)JAICOV_FORM_QPP_COLUMNS * n;
-    DevEvent ea, eb;
-    if (ms_out) {
-        HIPE(*v.err, ea.create());
-        HIPE(*v.err, eb.create());
-    }
+    QTimer<2> timer(v.stream);
+    HIPE(*v.err, timer.arm(ms_out != nullptr));
     HIPE(*v.err, hipMemcpyAsync(d_tab, tab.data(), n_tab * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-    if (ms_out) HIPE(*v.err, hipEventRecord(ea.get(), v.stream));
+    HIPE(*v.err, timer.mark(0));
     if (serial)
         hipLaunchKernelGGL(form_fit_kernel<true>, dim3(n), dim3(64), 0, v.stream, v.Q, v.ld, v.d_vals, d_tab, d_tab + o_begin, d_tab + o_host,
                            d_tab + o_point, d_tab + o_cols, sigma2, max_iterations, tol, d_out, d_qpp, d_mem, d_status, d_mstatus);
@@ -632,13 +586,13 @@ static int form_run(jaicov_engine *e, bool serial, double sigma2, int32_t n_form
         hipLaunchKernelGGL(form_fit_kernel<false>, dim3(n), dim3(64), 0, v.stream, v.Q, v.ld, v.d_vals, d_tab, d_tab + o_begin, d_tab + o_host,
                            d_tab + o_point, d_tab + o_cols, sigma2, max_iterations, tol, d_out, d_qpp, d_mem, d_status, d_mstatus);
     HIPE(*v.err, hipGetLastError());
-    if (ms_out) HIPE(*v.err, hipEventRecord(eb.get(), v.stream));
+    HIPE(*v.err, timer.mark(1));
     TRY(q_download(v, {{out, d_out, (size_t)JAICOV_FORM_COLUMNS * n * sizeof(double)},
                        {qpp, d_qpp, (size_t)JAICOV_FORM_QPP_COLUMNS * n * sizeof(double)},
                        {member_out, d_mem, (size_t)JAICOV_FORM_MEMBER_COLUMNS * M * sizeof(double)},
                        {status, d_status, (size_t)n * sizeof(int32_t)},
                        {member_status, d_mstatus, (size_t)M * sizeof(int32_t)}}));
-    if (ms_out) HIPE(*v.err, hipEventElapsedTime(ms_out, ea.get(), eb.get()));
+    HIPE(*v.err, timer.read(ms_out));
     return JAICOV_OK;
 }
 

@@ -13,7 +13,7 @@ namespace jaicov {
 struct NewPointState {
     DevBuf<int32_t> tab;       // ray image [R] | ray point [R] | ray_begin [n + 1] | col_begin [n + 1] | flag [n] | cols [C] |
                                // ray local -> position [KC_MAX R] | pairs [2 G] | state [n] | iterations [n] | status [n] | pair status [G] | moving [1]
-    DevBuf<double> rows;       // J [2 KROW][R] | w [2][R] | x [R] | y [R] | disp [3 R]
+    DevBuf<double> rows;       // the PairRows block (pairrows.h) of the R rays
     DevBuf<double> vals;       // the private slot vector: X, Y, Z of the new points [3 n] | the engine's slots behind its object points
     DevBuf<double> out;        // out [20 n] | F [3 C] (per point [3][M]) | pout [7 G] | ray_w [2 R]
     std::vector<int32_t> image_camera, cam_dist_begin;     // read from the device tables once per engine

@@ -2,10 +2,10 @@
 // adjustment, intersected from measurements in the adjusted images with the adjustment's own rows, their cofactors with the share
 // of the cameras and stations gathered from Qxx, and lengths between them with the correlations this sharing causes.
 //
-//   rows               J and w of every ray come from launch_rows (rows.hip) on a copy of the engine's DevProblem whose image-point
-//                      tables are the call's rays and whose object points are the new points; it reads a private slot vector
+//   rows               J and w of every ray come from the adjustment's own rows (pairrows.h) on a problem whose image points are the
+//                      call's rays and whose object points are the new points; it reads a private slot vector
 //                      [X, Y, Z of the new points | the engine's slots behind its object points], so slot_io, slot_dist and slot_eo
-//                      hold as they are.  The formulas are written once; predict.hip shows the way.
+//                      hold as they are.  The formulas are written once.
 //   newpt_step_kernel  one Gauss-Newton step, one wave per point, lane k owns ray k: the nine sums of N and n meet in an xor butterfly
 //                      (fixed order, the same bits in every lane), every lane solves the 3 x 3 system (wave_solve of wavealg.h), lane 0
 //                      moves the point in the private slot vector.  A converged or failed point leaves at once.  The host enqueues
@@ -29,13 +29,12 @@
 #include "../../include/jaicov_newpoints.h"
 #include "ba_kernels.h"
 #include "newpoints.h"
+#include "pairrows.h"
 #include "qview.h"
 #include "status.h"
 #include "wavealg.h"
 
 namespace jaicov {
-
-hipError_t launch_rows(hipStream_t, const DevProblem &, const double *, int, int, double *, double *);      // rows.hip
 
 constexpr int NP_S = KC_MAX;                                 // shared local columns of one ray: io (3), eo (6), dist (<= 20)
 constexpr int NP_C = JAICOV_NEWPT_MAX_COLS;
@@ -44,12 +43,6 @@ constexpr int NP_CHECK_EVERY = 4;                            // steps between tw
 static_assert(JAICOV_NEWPT_MAX_RAYS == 64, "one lane per ray");
 static_assert(NP_S <= 64, "one lane per shared local column of a ray");
 static_assert(NP_C >= 64 * 6 + 2 * (3 + MAXD), "64 distinct images and two cameras of the largest size");
-
-// entry (i, j) of the symmetric matrix from its lower part; a fixed parameter (column < 0) is a zero row and column
-__device__ __forceinline__ double np_q(const double *__restrict__ Q, long ld, int ci, int cj) {
-    if (ci < 0 || cj < 0) return 0.0;
-    return ci >= cj ? Q[(long)ci * ld + cj] : Q[(long)cj * ld + ci];
-}
 
 // Ray k of the sorted call: A (2 x 3), w, the weights, and its terms of N (6), n (3) and Omega.  n: rays of the call.
 struct NpRay {
@@ -279,8 +272,8 @@ __global__ __launch_bounds__(64) void newpt_pair_kernel(const double *__restrict
 #pragma unroll
                 for (int a = 0; a < 3; a++) Fm[h][a][lane] = a == lane ? 1.0 : 0.0;
             }
-            QX[h][0] = np_q(Q, ld, pc[0], pc[0]); QX[h][1] = np_q(Q, ld, pc[0], pc[1]); QX[h][2] = np_q(Q, ld, pc[0], pc[2]);
-            QX[h][3] = np_q(Q, ld, pc[1], pc[1]); QX[h][4] = np_q(Q, ld, pc[1], pc[2]); QX[h][5] = np_q(Q, ld, pc[2], pc[2]);
+            QX[h][0] = q_at(Q, ld, pc[0], pc[0]); QX[h][1] = q_at(Q, ld, pc[0], pc[1]); QX[h][2] = q_at(Q, ld, pc[0], pc[2]);
+            QX[h][3] = q_at(Q, ld, pc[1], pc[1]); QX[h][4] = q_at(Q, ld, pc[1], pc[2]); QX[h][5] = q_at(Q, ld, pc[2], pc[2]);
         }
     }
     __syncthreads();
@@ -295,7 +288,7 @@ __global__ __launch_bounds__(64) void newpt_pair_kernel(const double *__restrict
     const int MB = Mm[1], cnt = Mm[0] * MB;
     for (int e = lane; e < cnt; e += 64) {
         const int a = e / MB, b = e - a * MB;
-        const double qv = np_q(Q, ld, cm[0][a], cm[1][b]);
+        const double qv = q_at(Q, ld, cm[0][a], cm[1][b]);
 #pragma unroll
         for (int s = 0; s < 3; s++) {
             const double qf = qv * Fm[1][s][b];
@@ -360,11 +353,6 @@ __global__ __launch_bounds__(64) void newpt_pair_kernel(const double *__restrict
     }
 }
 
-static NewPointState *newpt_state(const QView &v) {
-    if (!v.slot->newpt) v.slot->newpt.reset(new NewPointState());
-    return v.slot->newpt.get();
-}
-
 // the two tables of the problem the host needs for the column lists, read from the device once per engine
 static int newpt_tables(const QView &v, NewPointState *st) {
     if (st->have_tables) return JAICOV_OK;
@@ -386,8 +374,7 @@ extern "C" int jaicov_newpt_intersect(jaicov_engine *e, double sigma2, int32_t n
                                       int32_t *pstatus) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
-    if (v.sharded) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "new points on a sharded engine");
-    if (!v.full_q) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "new points need all of Qxx on the device: solve with invert FULL or FULL_EXPANDED first");
+    TRY(q_guard(v, "new points on a sharded engine", "new points need all of Qxx on the device: solve with invert FULL or FULL_EXPANDED first"));
     const DevProblem &p = *v.p;
     const char *what = "new points: NULL argument, a negative count, sigma2 negative or max_iterations < 1";
     if (n_points < 0 || n_pairs < 0 || !(sigma2 >= 0.0) || max_iterations < 1) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, what);
@@ -395,17 +382,13 @@ extern "C" int jaicov_newpt_intersect(jaicov_engine *e, double sigma2, int32_t n
     if (n_pairs > 0 && (!pairs || !pout || !pstatus)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, what);
     long n_rays = 0;
     if (n_points > 0) {
-        if (ray_begin[0] != 0) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "new points: ray_begin must ascend from 0");
-        for (int i = 0; i < n_points; i++)
-            if (ray_begin[i + 1] < ray_begin[i]) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "new points: ray_begin must ascend from 0");
+        if (!ranges_ok(n_points, ray_begin)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "new points: ray_begin must ascend from 0");
         n_rays = ray_begin[n_points];
     }
     if (n_rays > 0 && (!ray_image || !xy || !disp)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, what);
-    for (long k = 0; k < n_rays; k++) {
+    for (long k = 0; k < n_rays; k++)
         if (ray_image[k] < 0 || ray_image[k] >= p.n_images) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "new points: image index out of range");
-        const double vx = disp[3 * k], vy = disp[3 * k + 1], rho = disp[3 * k + 2];
-        if (!(vx > 0.0) || !(vy > 0.0) || !(fabs(rho) < 1.0)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "new points: var must be positive and |rho| below 1");
-    }
+    if (!dispersions_ok(disp, n_rays)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "new points: var must be positive and |rho| below 1");
     for (int j = 0; j < n_pairs; j++) {
         const long a = pairs[2 * (size_t)j], b = pairs[2 * (size_t)j + 1];
         if (a >= n_points || b >= n_points || -1 - a >= p.n_points || -1 - b >= p.n_points)
@@ -415,7 +398,7 @@ extern "C" int jaicov_newpt_intersect(jaicov_engine *e, double sigma2, int32_t n
     }
     if (n_points == 0) return JAICOV_OK;
     HIPE(*v.err, hipSetDevice(v.device));
-    NewPointState *st = newpt_state(v);
+    NewPointState *st = q_state(v.slot->newpt);
     TRY(newpt_tables(v, st));
 
     // the host's part: every point's sorted columns, every ray's map into them, and what is known before the first step
@@ -482,43 +465,36 @@ extern "C" int jaicov_newpt_intersect(jaicov_engine *e, double sigma2, int32_t n
     std::copy(rpos.begin(), rpos.end(), tab.begin() + o_pos);
     if (G) std::copy(pairs, pairs + 2 * G, tab.begin() + o_pairs);
     for (size_t i = 0; i < N; i++) tab[o_state + i] = flag[i] & JAICOV_NEWPT_FAILED;         // NP_MOVING without a failure
-    // rows: J | w | x | y | disp;  out: out | F | pout | ray_w
-    const size_t o_w = (size_t)2 * KROW * R, o_x = o_w + 2 * R, o_y = o_x + R, o_disp = o_y + R, n_rows = o_disp + 3 * R;
+    // out: out | F | pout | ray_w
+    PairRows pr(R);
     const size_t o_F = JAICOV_NEWPT_COLUMNS * N, o_pout = o_F + 3 * Cn, o_rw = o_pout + JAICOV_NEWPT_PAIR_COLUMNS * G, n_out = o_rw + 2 * R;
     const size_t n_shared = (size_t)p.n_slots - s_io, n_vals = 3 * N + n_shared;
     HIPE(*v.err, st->tab.reserve(n_tab));
-    HIPE(*v.err, st->rows.reserve(std::max<size_t>(n_rows, 1)));
+    HIPE(*v.err, st->rows.reserve(std::max<size_t>(pr.size, 1)));
     HIPE(*v.err, st->vals.reserve(n_vals));
     HIPE(*v.err, st->out.reserve(n_out));
     int32_t *d_tab = st->tab.get();
-    double *d_rows = st->rows.get(), *d_vals = st->vals.get(), *d_out = st->out.get();
+    double *d_vals = st->vals.get(), *d_out = st->out.get();
+    pr.bind(st->rows.get());
     HIPE(*v.err, hipMemcpyAsync(d_tab, tab.data(), n_up * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
     HIPE(*v.err, hipMemsetAsync(d_tab + o_iter, 0, N * sizeof(int32_t), v.stream));
-    std::vector<double> meas(5 * R);
-    for (size_t k = 0; k < R; k++) {
-        meas[k] = xy[2 * k]; meas[R + k] = xy[2 * k + 1];
-        for (int c = 0; c < 3; c++) meas[2 * R + 3 * k + c] = disp[3 * k + c];
-    }
-    if (R > 0) HIPE(*v.err, hipMemcpyAsync(d_rows + o_x, meas.data(), 5 * R * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    HIPE(*v.err, pr.stage(v.stream, xy, disp, nullptr));
     HIPE(*v.err, hipMemcpyAsync(d_vals, start, 3 * N * sizeof(double), hipMemcpyHostToDevice, v.stream));
     if (n_shared > 0)
         HIPE(*v.err, hipMemcpyAsync(d_vals + 3 * N, v.d_vals + s_io, n_shared * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
-    DevProblem q = p;
-    q.n_points = n_points; q.n_slots = (int)n_vals; q.n_ip = (int)R;
-    q.ip_image = d_tab; q.ip_point = d_tab + o_pt; q.ip_x = d_rows + o_x; q.ip_y = d_rows + o_y;
-    DevEvent ev[4];
-    if (st->timing)
-        for (DevEvent &x : ev) HIPE(*v.err, x.create());
-    auto mark = [&](int k) { return st->timing ? hipEventRecord(ev[k].get(), v.stream) : hipSuccess; };
+    DevProblem q = pr.problem(p, d_tab, d_tab + o_pt);
+    q.n_points = n_points; q.n_slots = (int)n_vals;
+    QTimer<4> timer(v.stream);
+    HIPE(*v.err, timer.arm(st->timing));
     const double s0 = v.sigma2;
-    HIPE(*v.err, mark(0));
+    HIPE(*v.err, timer.mark(0));
     st->steps = 0;
     for (int it = 0; it < max_iterations; it++) {
         const bool look = it % NP_CHECK_EVERY == NP_CHECK_EVERY - 1 && it + 1 < max_iterations;
-        HIPE(*v.err, launch_rows(v.stream, q, d_vals, 0, (int)R, d_rows, d_rows + o_w));
+        HIPE(*v.err, pr.rows(v.stream, q, d_vals));
         if (look) HIPE(*v.err, hipMemsetAsync(d_tab + o_moving, 0, sizeof(int32_t), v.stream));
-        hipLaunchKernelGGL(newpt_step_kernel, dim3((unsigned)N), dim3(64), 0, v.stream, q, d_vals, d_tab + o_rb, d_rows, d_rows + o_w,
-                           d_rows + o_disp, s0, d_tab + o_state, d_tab + o_iter, look ? d_tab + o_moving : nullptr);
+        hipLaunchKernelGGL(newpt_step_kernel, dim3((unsigned)N), dim3(64), 0, v.stream, q, d_vals, d_tab + o_rb, pr.J, pr.w,
+                           pr.disp, s0, d_tab + o_state, d_tab + o_iter, look ? d_tab + o_moving : nullptr);
         HIPE(*v.err, hipGetLastError());
         st->steps++;
         if (look) {
@@ -527,27 +503,26 @@ extern "C" int jaicov_newpt_intersect(jaicov_engine *e, double sigma2, int32_t n
             if (moving == 0) break;
         }
     }
-    HIPE(*v.err, launch_rows(v.stream, q, d_vals, 0, (int)R, d_rows, d_rows + o_w));
-    HIPE(*v.err, mark(1));
+    HIPE(*v.err, pr.rows(v.stream, q, d_vals));
+    HIPE(*v.err, timer.mark(1));
     hipLaunchKernelGGL(newpt_gain_kernel, dim3((unsigned)N), dim3(64), 0, v.stream, v.Q, v.ld, q, d_vals, d_tab + o_rb, d_tab + o_cb, d_tab + o_flag,
-                       d_tab + o_cols, d_tab + o_pos, d_rows, d_rows + o_w, d_rows + o_disp, s0, sigma2, d_tab + o_state, d_out, d_out + o_F,
+                       d_tab + o_cols, d_tab + o_pos, pr.J, pr.w, pr.disp, s0, sigma2, d_tab + o_state, d_out, d_out + o_F,
                        d_out + o_rw, d_tab + o_status);
     HIPE(*v.err, hipGetLastError());
-    HIPE(*v.err, mark(2));
+    HIPE(*v.err, timer.mark(2));
     if (G > 0) {
         hipLaunchKernelGGL(newpt_pair_kernel, dim3((unsigned)G), dim3(64), 0, v.stream, v.Q, v.ld, p, v.d_vals, d_tab + o_pairs, d_tab + o_cb,
                            d_tab + o_cols, d_out, d_out + o_F, d_tab + o_status, sigma2, d_out + o_pout, d_tab + o_pstatus);
         HIPE(*v.err, hipGetLastError());
     }
-    HIPE(*v.err, mark(3));
+    HIPE(*v.err, timer.mark(3));
     TRY(q_download(v, {{out, d_out, JAICOV_NEWPT_COLUMNS * N * sizeof(double)},
                        {status, d_tab + o_status, N * sizeof(int32_t)},
                        {iterations, d_tab + o_iter, N * sizeof(int32_t)},
                        {ray_w, d_out + o_rw, 2 * R * sizeof(double)},
                        {pout, d_out + o_pout, JAICOV_NEWPT_PAIR_COLUMNS * G * sizeof(double)},
                        {pstatus, d_tab + o_pstatus, G * sizeof(int32_t)}}));
-    if (st->timing)
-        for (int k = 0; k < 3; k++) HIPE(*v.err, hipEventElapsedTime(&st->ms[k], ev[k].get(), ev[k + 1].get()));
+    HIPE(*v.err, timer.read(st->ms));
     return JAICOV_OK;
 }
 
@@ -557,7 +532,7 @@ extern "C" int jaicov_newpt_intersect(jaicov_engine *e, double sigma2, int32_t n
 extern "C" int jaicov_debug_newpt_timing(jaicov_engine *e, int on, float *ms, int32_t *steps) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
-    NewPointState *st = on ? newpt_state(v) : v.slot->newpt.get();       // asking an engine that never ran the call allocates nothing
+    NewPointState *st = on ? q_state(v.slot->newpt) : v.slot->newpt.get();       // asking an engine that never ran the call allocates nothing
     if (st) st->timing = on != 0;
     if (ms)
         for (int k = 0; k < 3; k++) ms[k] = st ? st->ms[k] : 0.f;

@@ -308,7 +308,7 @@ __global__ __launch_bounds__(64) void par_tests_kernel(const double *__restrict_
             const int ci = mcol[m0 + i], j = i + lane;
             if (j < k) {
                 const int cj = mcol[m0 + j];
-                U[ix(i, j)] = ci >= cj ? Q[(long)ci * ld + cj] : Q[(long)cj * ld + ci];
+                U[ix(i, j)] = q_sym(Q, ld, ci, cj);
             }
         }
         if (lane < k) b[lane] = dl[lane] = vals[mslot[m0 + lane]] - mx0[m0 + lane];
@@ -347,17 +347,7 @@ __global__ __launch_bounds__(64) void par_tests_kernel(const double *__restrict_
     }
 }
 
-// the refusals common to all calls, in the header's order (the arguments follow in the callers)
-static int par_common(const QView &v) {
-    if (v.sharded) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "parameter correlations and tests on a sharded engine");
-    if (!v.have_q) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
-    return JAICOV_OK;
-}
-
-static ParamState *par_state(const QView &v) {
-    if (!v.slot->par) v.slot->par.reset(new ParamState());
-    return v.slot->par.get();
-}
+static const char PAR_SHARDED[] = "parameter correlations and tests on a sharded engine";
 
 static bool par_selection_ok(uint32_t mask, uint32_t flags) {
     return !(mask >> 16) && !(flags & ~(uint32_t)(JAICOV_PAR_SKIP_SAME_POINT | JAICOV_PAR_SKIP_SAME_IMAGE));
@@ -402,13 +392,13 @@ using namespace jaicov;
 extern "C" int jaicov_par_maxima(jaicov_engine *e, uint32_t pair_mask, uint32_t flags, double *rho, int32_t *partner, int32_t *status, int32_t n) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
-    TRY(par_common(v));
+    TRY(q_guard(v, PAR_SHARDED));
     if (!rho || !partner || !status || n != v.order) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "correlation maxima: NULL output, or n is not the order of the cofactor matrix");
     if (!par_selection_ok(pair_mask, flags)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "correlation maxima: unknown bits in pair_mask or flags");
     if (n == 0) return JAICOV_OK;
     const int nbk = (v.order + 127) / 128, np = nbk * 128;
     HIPE(*v.err, hipSetDevice(v.device));
-    ParamState *st = par_state(v);
+    ParamState *st = q_state(v.slot->par);
     HIPE(*v.err, st->cand.reserve((size_t)nbk * nbk * 128));
     HIPE(*v.err, st->out_d.reserve((size_t)np));
     HIPE(*v.err, st->out_i.reserve((size_t)2 * np));
@@ -428,7 +418,7 @@ extern "C" int jaicov_par_pairs(jaicov_engine *e, uint32_t pair_mask, uint32_t f
                                 int64_t *count) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
-    TRY(par_common(v));
+    TRY(q_guard(v, PAR_SHARDED));
     if (!count || capacity < 0 || (capacity > 0 && (!cols || !rho))) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "correlated pairs: NULL output or a negative capacity");
     if (!(threshold > 0.0 && threshold <= 1.0)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "correlated pairs: the threshold must lie in (0, 1]");
     if (!par_selection_ok(pair_mask, flags)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "correlated pairs: unknown bits in pair_mask or flags");
@@ -436,7 +426,7 @@ extern "C" int jaicov_par_pairs(jaicov_engine *e, uint32_t pair_mask, uint32_t f
     if (v.order == 0) return JAICOV_OK;
     const int nbk = (v.order + 127) / 128, np = nbk * 128, nt = nbk * (nbk + 1) / 2;
     HIPE(*v.err, hipSetDevice(v.device));
-    ParamState *st = par_state(v);
+    ParamState *st = q_state(v.slot->par);
     HIPE(*v.err, st->count.reserve((size_t)2 * nt + 1));
     TRY(par_prepare(v, st, flags, np));
     const int32_t *cls = st->tab.get(), *item = cls + np;
@@ -476,7 +466,7 @@ extern "C" int jaicov_par_pairs(jaicov_engine *e, uint32_t pair_mask, uint32_t f
 extern "C" int jaicov_par_block(jaicov_engine *e, const int32_t *row_cols, int32_t n_r, const int32_t *col_cols, int32_t n_c, double *out) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
-    TRY(par_common(v));
+    TRY(q_guard(v, PAR_SHARDED));
     if (!row_cols || !col_cols || !out || n_r < 1 || n_c < 1) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "correlation block: NULL argument or an empty list");
     for (int i = 0; i < n_r + n_c; i++) {
         const int c = i < n_r ? row_cols[i] : col_cols[i - n_r];
@@ -484,7 +474,7 @@ extern "C" int jaicov_par_block(jaicov_engine *e, const int32_t *row_cols, int32
     }
     const size_t cells = (size_t)n_r * n_c;
     HIPE(*v.err, hipSetDevice(v.device));
-    ParamState *st = par_state(v);
+    ParamState *st = q_state(v.slot->par);
     HIPE(*v.err, st->out_i.reserve((size_t)n_r + n_c));
     HIPE(*v.err, st->out_d.reserve(cells));
     int32_t *d_rows = st->out_i.get(), *d_cols = d_rows + n_r;
@@ -500,12 +490,10 @@ extern "C" int jaicov_par_tests(jaicov_engine *e, double sigma2, const int32_t *
                                 int32_t n_groups, double *out, int32_t *status) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
-    TRY(par_common(v));
+    TRY(q_guard(v, PAR_SHARDED));
     if (!group_begin || !out || !status || n_groups < 0) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "parameter tests: NULL argument or a negative count");
     if (!(sigma2 > 0.0)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "parameter tests: sigma2 must be positive");
-    if (group_begin[0] != 0) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "parameter tests: group_begin must ascend from 0");
-    for (int g = 0; g < n_groups; g++)
-        if (group_begin[g + 1] < group_begin[g]) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "parameter tests: group_begin must ascend from 0");
+    if (!ranges_ok(n_groups, group_begin)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "parameter tests: group_begin must ascend from 0");
     const int n_members = group_begin[n_groups], n_slots = (int)v.slot_col->size();
     if (n_members > 0 && !group_slot) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "parameter tests: NULL group_slot");
     for (int m = 0; m < n_members; m++)
@@ -518,8 +506,8 @@ extern "C" int jaicov_par_tests(jaicov_engine *e, double sigma2, const int32_t *
     for (int g = 0; g < n; g++) {
         tab[g] = M;
         for (int m = group_begin[g]; m < group_begin[g + 1]; m++) {
-            const int c = (*v.slot_col)[group_slot[m]];
-            if (c >= v.order) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "parameter tests: a member's column is not in the reduced cofactor matrix");
+            int c;
+            TRY(q_column(v, group_slot[m], "parameter tests: a member's column is not in the reduced cofactor matrix", &c));
             if (c < 0) { tab[(size_t)n + 1 + g] |= JAICOV_PAR_PARTIAL; continue; }
             hx0[M] = x0 ? x0[m] : 0.0;
             ++M;
@@ -539,7 +527,7 @@ extern "C" int jaicov_par_tests(jaicov_engine *e, double sigma2, const int32_t *
         }
     const size_t n_tab = o_slot + std::max(M, 1);
     HIPE(*v.err, hipSetDevice(v.device));
-    ParamState *st = par_state(v);
+    ParamState *st = q_state(v.slot->par);
     HIPE(*v.err, st->out_i.reserve(n_tab + n));
     HIPE(*v.err, st->out_d.reserve((size_t)JAICOV_PAR_TEST_COLUMNS * n + std::max(M, 1)));
     int32_t *d_tab = st->out_i.get(), *d_status = d_tab + n_tab;
@@ -558,11 +546,11 @@ extern "C" int jaicov_par_tests(jaicov_engine *e, double sigma2, const int32_t *
 extern "C" int jaicov_debug_par_kernel_ms(jaicov_engine *e, uint32_t pair_mask, double threshold, int32_t repeats, double *ms) {
     if (!e || !ms || repeats < 1) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
-    TRY(par_common(v));
+    TRY(q_guard(v, PAR_SHARDED));
     if (v.order == 0 || !par_selection_ok(pair_mask, 0)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "parameter bench: no columns or a bad mask");
     const int nbk = (v.order + 127) / 128, np = nbk * 128, nt = nbk * (nbk + 1) / 2;
     HIPE(*v.err, hipSetDevice(v.device));
-    ParamState *st = par_state(v);
+    ParamState *st = q_state(v.slot->par);
     HIPE(*v.err, st->cand.reserve((size_t)nbk * nbk * 128));
     HIPE(*v.err, st->count.reserve((size_t)2 * nt + 1));
     HIPE(*v.err, st->out_d.reserve((size_t)np));

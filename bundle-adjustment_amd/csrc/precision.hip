@@ -28,12 +28,6 @@ constexpr double PREC_EPS = 2.220446049250313e-16;     // 2^-52
 constexpr int PREC_SWEEPS = 30;
 constexpr int PREC_TAB = 8;                            // int32 per item of the column table
 
-// entry (i, j) of the symmetric matrix from its lower part; a fixed coordinate (column < 0) is a zero row and column
-__device__ __forceinline__ double prec_q(const double *__restrict__ Q, long ld, int ci, int cj) {
-    if (ci < 0 || cj < 0) return 0.0;
-    return ci >= cj ? Q[(long)ci * ld + cj] : Q[(long)cj * ld + ci];
-}
-
 // one Jacobi rotation (P, Q) of the symmetric a with third index R; false: skipped
 template <int P, int Q_, int R>
 __device__ __forceinline__ bool prec_rot(double (&a)[3][3], double (&v)[3][3]) {
@@ -75,14 +69,14 @@ __global__ __launch_bounds__(256) void prec_block_kernel(const double *__restric
     const int32_t *tb = tab + (size_t)PREC_TAB * i;
     const int c0 = tb[0], c1 = tb[1], c2 = tb[2];
     double C[3][3];
-    C[0][0] = prec_q(Q, ld, c0, c0); C[1][1] = prec_q(Q, ld, c1, c1); C[2][2] = prec_q(Q, ld, c2, c2);
-    C[0][1] = C[1][0] = prec_q(Q, ld, c0, c1);
-    C[0][2] = C[2][0] = prec_q(Q, ld, c0, c2);
-    C[1][2] = C[2][1] = prec_q(Q, ld, c1, c2);
+    C[0][0] = q_at(Q, ld, c0, c0); C[1][1] = q_at(Q, ld, c1, c1); C[2][2] = q_at(Q, ld, c2, c2);
+    C[0][1] = C[1][0] = q_at(Q, ld, c0, c1);
+    C[0][2] = C[2][0] = q_at(Q, ld, c0, c2);
+    C[1][2] = C[2][1] = q_at(Q, ld, c1, c2);
     double ang[3] = {0.0, 0.0, 0.0};
     if (ncol > JAICOV_PREC_POINT_COLUMNS)
 #pragma unroll
-        for (int k = 0; k < 3; k++) ang[k] = prec_q(Q, ld, tb[3 + k], tb[3 + k]);
+        for (int k = 0; k < 3; k++) ang[k] = q_at(Q, ld, tb[3 + k], tb[3 + k]);
     int st = (c0 < 0 || c1 < 0 || c2 < 0) ? JAICOV_PREC_PARTIAL : 0;
     double *o = out + (size_t)ncol * i;
     const double sum = ((C[0][0] + C[1][1]) + C[2][2]) + (C[0][1] + C[0][2] + C[1][2]) + (ang[0] + ang[1] + ang[2]) + sigma2 + k3 + k2;
@@ -174,7 +168,7 @@ __global__ __launch_bounds__(256) void prec_length_kernel(const double *__restri
         double s = 0.0;
 #pragma unroll
         for (int c = 0; c < 6; c++) {
-            const double q = prec_q(Q, ld, col[r], col[c]);
+            const double q = q_at(Q, ld, col[r], col[c]);
             chk += q;
             s += q * g[c];
         }
@@ -197,7 +191,7 @@ __global__ __launch_bounds__(256) void prec_length_kernel(const double *__restri
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        const double dv = (prec_q(Q, ld, col[k], col[k]) + prec_q(Q, ld, col[3 + k], col[3 + k])) - 2.0 * prec_q(Q, ld, col[3 + k], col[k]);
+        const double dv = (q_at(Q, ld, col[k], col[k]) + q_at(Q, ld, col[3 + k], col[3 + k])) - 2.0 * q_at(Q, ld, col[3 + k], col[k]);
         if (dv < 0.0) st |= JAICOV_PREC_NEGATIVE;
         o[2 + k] = sqrt(sigma2 * fmax(dv, 0.0));
     }
@@ -361,24 +355,14 @@ static inline uint64_t prec_splitmix(uint64_t c) {
     return z ^ (z >> 31);
 }
 
-// the refusals common to all calls, in the header's order (the arguments follow in the callers)
-static int prec_common(const QView &v) {
-    if (v.sharded) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "precision figures on a sharded engine");
-    if (!v.have_q) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "no cofactor matrix: solve with invert != 0 first");
-    return JAICOV_OK;
-}
-
-static PrecisionState *prec_state(const QView &v) {
-    if (!v.slot->prec) v.slot->prec.reset(new PrecisionState());
-    return v.slot->prec.get();
-}
+static const char PREC_SHARDED[] = "precision figures on a sharded engine";
 
 // points (station == false) or projection centres: the column table, the launch, the download
 static int prec_blocks(jaicov_engine *e, bool station, double sigma2, double k3, double k2, const int32_t *items, int32_t n, double *out,
                        int32_t *status) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
-    TRY(prec_common(v));
+    TRY(q_guard(v, PREC_SHARDED));
     const DevProblem &p = *v.p;
     if (station && v.reduced) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "station precision needs the exterior orientations' columns: invert FULL or FULL_EXPANDED");
     const int total = station ? p.n_images : p.n_points;
@@ -391,15 +375,13 @@ static int prec_blocks(jaicov_engine *e, bool station, double sigma2, double k3,
         if (it < 0 || it >= total) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "precision: index out of range");
         const int slot = station ? eo0 + 6 * it : 3 * it;
         for (int k = 0; k < (station ? 6 : 3); k++) {
-            const int c = (*v.slot_col)[slot + k];
-            if (c >= v.order) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "precision: the item's columns are not in the reduced cofactor matrix");
-            tab[(size_t)PREC_TAB * i + k] = c < 0 ? -1 : c;
+            TRY(q_column(v, slot + k, "precision: the item's columns are not in the reduced cofactor matrix", &tab[(size_t)PREC_TAB * i + k]));
         }
     }
     if (n == 0) return JAICOV_OK;
     const int ncol = station ? JAICOV_PREC_STATION_COLUMNS : JAICOV_PREC_POINT_COLUMNS;
     HIPE(*v.err, hipSetDevice(v.device));
-    PrecisionState *st = prec_state(v);
+    PrecisionState *st = q_state(v.slot->prec);
     HIPE(*v.err, st->tab.reserve((size_t)(PREC_TAB + 1) * n));
     HIPE(*v.err, st->out.reserve((size_t)ncol * n));
     int32_t *d_tab = st->tab.get(), *d_status = d_tab + (size_t)PREC_TAB * n;
@@ -427,7 +409,7 @@ extern "C" int jaicov_prec_stations(jaicov_engine *e, double sigma2, double k3, 
 extern "C" int jaicov_prec_lengths(jaicov_engine *e, double sigma2, const int32_t *pairs, int32_t n, double *out, int32_t *status) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
-    TRY(prec_common(v));
+    TRY(q_guard(v, PREC_SHARDED));
     const DevProblem &p = *v.p;
     if (!pairs || !out || !status || n < 0) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "length precision: NULL argument or a negative count");
     if (!(sigma2 >= 0.0)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "length precision: sigma2 must not be negative");
@@ -437,16 +419,15 @@ extern "C" int jaicov_prec_lengths(jaicov_engine *e, double sigma2, const int32_
         if (a < 0 || a >= p.n_points || b < 0 || b >= p.n_points) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "length precision: point index out of range");
         if (a == b) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "length precision: a pair names the same point twice");
         for (int k = 0; k < 6; k++) {
-            const int c = (*v.slot_col)[3 * (k < 3 ? a : b) + k % 3];
-            if (c >= v.order) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "length precision: a point's columns are not in the reduced cofactor matrix");
-            tab[(size_t)PREC_TAB * i + k] = c < 0 ? -1 : c;
+            TRY(q_column(v, 3 * (k < 3 ? a : b) + k % 3, "length precision: a point's columns are not in the reduced cofactor matrix",
+                         &tab[(size_t)PREC_TAB * i + k]));
         }
         tab[(size_t)PREC_TAB * i + 6] = 3 * a;
         tab[(size_t)PREC_TAB * i + 7] = 3 * b;
     }
     if (n == 0) return JAICOV_OK;
     HIPE(*v.err, hipSetDevice(v.device));
-    PrecisionState *st = prec_state(v);
+    PrecisionState *st = q_state(v.slot->prec);
     HIPE(*v.err, st->tab.reserve((size_t)(PREC_TAB + 1) * n));
     HIPE(*v.err, st->out.reserve((size_t)JAICOV_PREC_LENGTH_COLUMNS * n));
     int32_t *d_tab = st->tab.get(), *d_status = d_tab + (size_t)PREC_TAB * n;
@@ -462,7 +443,7 @@ extern "C" int jaicov_prec_components(jaicov_engine *e, int32_t first_col, int32
                                       double *values, double *vectors, double *trace, double *residuals, int32_t *iterations) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
-    TRY(prec_common(v));
+    TRY(q_guard(v, PREC_SHARDED));
     if (!values || !vectors || !trace || !residuals || !iterations) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "principal components: NULL output");
     if (k < 1 || k > 4) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "principal components: k must be 1 .. 4");
     if (n_cols < 8 || first_col < v.d || first_col > v.order || n_cols > v.order - first_col)
@@ -473,7 +454,7 @@ extern "C" int jaicov_prec_components(jaicov_engine *e, int32_t first_col, int32
     const int nbk = (hi + 127) / 128, np = nbk * 128, nblk = (np + 255) / 256;
     const size_t n8 = (size_t)np * 8;
     HIPE(*v.err, hipSetDevice(v.device));
-    PrecisionState *st = prec_state(v);
+    PrecisionState *st = q_state(v.slot->prec);
     HIPE(*v.err, st->work.reserve(4 * n8 + 256 + (size_t)nblk * 64 + (size_t)nbk * nbk * 128 * 8));
     double *dXt = st->work.get(), *dXr = dXt + n8, *dY = dXr + n8, *dW = dY + n8, *dM = dW + n8, *dG = dM + 128, *dPart = dM + 256,
            *dP = dPart + (size_t)nblk * 64;

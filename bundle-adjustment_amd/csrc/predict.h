@@ -13,7 +13,7 @@ namespace jaicov {
 struct PredictState {
     DevBuf<int32_t> tab;       // image [n] | point [n] | first pair [W] | pairs [W] of the W workgroups | status [n] | group_begin [G + 1] |
                                // member -> sorted position [n] | group status [G]
-    DevBuf<double> rows;       // J [2 KROW][n] | w [2][n] | x [n] | y [n] | disp [3 n], the pairs sorted by image
+    DevBuf<double> rows;       // the PairRows block (pairrows.h) of the pairs sorted by image
     DevBuf<double> out;        // out [10 n] or [8 n] | gout [4 G]
     std::vector<uint64_t> observed;   // (image << 32 | point) of every image point of the problem, ascending: read from the device once
     bool have_observed = false;

@@ -1,16 +1,15 @@
 // Image-space readers of the cofactor matrix on the device (include/jaicov_predict.h): predicted image points with their
 // confidence ellipses, and the test of check measurements pair by pair and in groups.
 //
-//   rows               J and w of every pair come from launch_rows (rows.hip) on a copy of the engine's DevProblem whose image-point
-//                      tables are the call's pairs: the collinearity and distortion formulas are written once, and a check
-//                      measurement meets the arithmetic of the adjustment's own rows.  The row buffers are the state's own.
+//   rows               J and w of every pair come from the adjustment's own rows (pairrows.h): the collinearity and distortion formulas
+//                      are written once.  The row buffers are the state's own.
 //   pred_cov_kernel    C = J Qxx J' of every pair.  The host sorts the pairs by image (stable); a workgroup of one wave takes up to 64
 //                      pairs of ONE image, stages Q[S, S] of that image's camera and EO columns S (<= 29) once in LDS, and lane i
 //                      gathers for pair i only the 3 x |S| strip and the 3 x 3 block of its point.  J lies in LDS, one column of 64
 //                      words per lane, so the sums over S index it at run time without a register array.
 //   pred_group_kernel  one wave per group of m <= 32 pairs: M_G (2m x 2m, packed upper in LDS) block by block, every block gathered by
-//                      the 64 lanes and reduced by an xor butterfly, then the scaling of forms.hip and the lane-parallel Cholesky
-//                      factor and forward substitution of wavealg.h.
+//                      the 64 lanes and reduced by an xor butterfly, then the scaling, the lane-parallel Cholesky factor and the
+//                      forward substitution of wavealg.h.
 // Nothing here writes to the cofactor matrix or to any other state of the engine but the buffers of PredictState.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -22,14 +21,13 @@
 
 #include "../../include/jaicov_predict.h"
 #include "ba_kernels.h"
+#include "pairrows.h"
 #include "predict.h"
 #include "qview.h"
 #include "status.h"
 #include "wavealg.h"
 
 namespace jaicov {
-
-hipError_t launch_rows(hipStream_t, const DevProblem &, const double *, int, int, double *, double *);      // rows.hip
 
 constexpr int PRED_S = KC_MAX;                               // camera and EO columns of one image: io (3), eo (6), dist (<= 20)
 constexpr int PRED_WG = 64;                                  // pairs of one workgroup of pred_cov_kernel, one lane each
@@ -38,12 +36,6 @@ constexpr int PRED_R = 2 * JAICOV_PRED_MAX_GROUP;            // largest order of
 constexpr int PRED_TRI = PRED_R * (PRED_R + 1) / 2;
 static_assert(PRED_S == KROW - 3, "the local columns behind X, Y, Z are the image's shared columns");
 static_assert(PRED_R == 64, "one lane per row of M_G");
-
-// entry (i, j) of the symmetric matrix from its lower part; a fixed parameter (column < 0) is a zero row and column
-__device__ __forceinline__ double pred_q(const double *__restrict__ Q, long ld, int ci, int cj) {
-    if (ci < 0 || cj < 0) return 0.0;
-    return ci >= cj ? Q[(long)ci * ld + cj] : Q[(long)cj * ld + ci];
-}
 
 // Workgroup w: the pairs first[w] .. first[w] + count[w] (<= 64, sorted order) of one image.  rowsA [2 KROW][n], rowsW [2][n] and
 // disp [3][n] run over the sorted pairs.  CHECK: sa = s0, sb = sigma2_post, out rows of 8; otherwise sa = sigma2, sb = k2, rows of 10.
@@ -76,18 +68,18 @@ __global__ __launch_bounds__(PRED_WG) void pred_cov_kernel(const double *__restr
 #pragma unroll
     for (int t = 0; t < PRED_STAGE; t++) {
         const int e = lane + PRED_WG * t, a = e / ns, b = e - a * ns;
-        stq[t] = e < ns * ns ? pred_q(Q, ld, scol[a], scol[b]) : 0.0;
+        stq[t] = e < ns * ns ? q_at(Q, ld, scol[a], scol[b]) : 0.0;
     }
     double qpp[3][3], q3[3][PRED_S];
 #pragma unroll
     for (int a = 0; a < 3; a++)
 #pragma unroll
-        for (int b = 0; b <= a; b++) qpp[a][b] = qpp[b][a] = pred_q(Q, ld, pc[a], pc[b]);
+        for (int b = 0; b <= a; b++) qpp[a][b] = qpp[b][a] = q_at(Q, ld, pc[a], pc[b]);
 #pragma unroll
     for (int b = 0; b < PRED_S; b++) {
         const int cb = scol[b];                    // -1 behind the camera's coefficients
 #pragma unroll
-        for (int a = 0; a < 3; a++) q3[a][b] = pred_q(Q, ld, pc[a], cb);
+        for (int a = 0; a < 3; a++) q3[a][b] = q_at(Q, ld, pc[a], cb);
     }
 #pragma unroll
     for (int l = 0; l < 2 * KROW; l++) {
@@ -187,7 +179,6 @@ __global__ __launch_bounds__(64) void pred_group_kernel(const double *__restrict
     __shared__ double dv[PRED_R], Sc[PRED_R], Sv[PRED_R];
     __shared__ int col[JAICOV_PRED_MAX_GROUP][KROW];
     __shared__ int kk[JAICOV_PRED_MAX_GROUP], pos[JAICOV_PRED_MAX_GROUP];
-    const double EPS = ldexp(1.0, -53);
     const int g = blockIdx.x, lane = threadIdx.x;
     const int m0 = wave_uniform(gbegin[g]), m = wave_uniform(gbegin[g + 1]) - m0, n2 = 2 * m;
     auto ix = [n2](int i, int j) { return tri_ix_n(n2, i, j); };
@@ -224,7 +215,7 @@ __global__ __launch_bounds__(64) void pred_group_kernel(const double *__restrict
             double xx = 0.0, xy = 0.0, yx = 0.0, yy = 0.0;
             for (int e = lane; e < cnt; e += 64) {
                 const int a = e / kj, b = e - a * kj;
-                const double q = pred_q(Q, ld, col[i][a], col[j][b]);
+                const double q = q_at(Q, ld, col[i][a], col[j][b]);
                 const double qx = q * Jg[j][0][b], qy = q * Jg[j][1][b];
                 xx += Jg[i][0][a] * qx; xy += Jg[i][0][a] * qy; yx += Jg[i][1][a] * qx; yy += Jg[i][1][a] * qy;
             }
@@ -250,33 +241,10 @@ __global__ __launch_bounds__(64) void pred_group_kernel(const double *__restrict
         if (lane == 3) gout[(size_t)JAICOV_PRED_GROUP_COLUMNS * g + 3] = (double)n2;
         if (lane == 0) gstatus[g] = st | bit;
     };
-    // powers of two bring the diagonal into [1, 4), then the Jacobi scaling (forms.hip); NaN in z unless every value is finite
+    // NaN in z unless every value is finite
     double z = (s0 + s2post) * 0.0;
-    if (lane < n2) {
-        const double qd = U[ix(lane, lane)];
-        Sc[lane] = (qd > 0.0 && isfinite(qd)) ? ldexp(1.0, -(ilogb(qd) >> 1)) : 1.0;
-        z += dv[lane] * 0.0;
-    }
-    __syncthreads();
-    for (int i = 0; i < n2; i++) {
-        const int j = i + lane;
-        if (j < n2) {
-            const double a = U[ix(i, j)];
-            z += a * 0.0;
-            U[ix(i, j)] = a * (Sc[i] * Sc[j]);
-        }
-    }
-    __syncthreads();
-    if (lane < n2) {
-        const double a = U[ix(lane, lane)];
-        Sv[lane] = a > EPS ? 1.0 / sqrt(a) : 1.0;
-    }
-    __syncthreads();
-    for (int i = 0; i < n2; i++) {
-        const int j = i + lane;
-        if (j < n2) U[ix(i, j)] = U[ix(i, j)] * (Sv[i] * Sv[j]);
-    }
-    __syncthreads();
+    if (lane < n2) z += dv[lane] * 0.0;
+    wave_equilibrate_lds(n2, U, Sc, Sv, z, lane);
     if (wave_uniform(__any(!(z == 0.0)) != 0)) { fail(JAICOV_PRED_NOT_FINITE); return; }
     if (wave_chol_lds(n2, U, lane) != WAVE_OK) { fail(JAICOV_PRED_SINGULAR); return; }
     // q_G = |U^-T (S d)|^2, the squares added in row order
@@ -292,18 +260,6 @@ __global__ __launch_bounds__(64) void pred_group_kernel(const double *__restrict
         o[0] = q; o[1] = q / ((double)n2 * s0); o[2] = q / ((double)n2 * s2post); o[3] = (double)n2;
         gstatus[g] = st;
     }
-}
-
-// the refusals common to both calls, in the header's order (the arguments follow in the caller)
-static int pred_common(const QView &v) {
-    if (v.sharded) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "image predictions on a sharded engine");
-    if (!v.full_q) FAIL(*v.err, JAICOV_ERR_BAD_STATE, "image predictions need all of Qxx on the device: solve with invert FULL or FULL_EXPANDED first");
-    return JAICOV_OK;
-}
-
-static PredictState *pred_state(const QView &v) {
-    if (!v.slot->pred) v.slot->pred.reset(new PredictState());
-    return v.slot->pred.get();
 }
 
 // the image points of the problem as sorted keys, read from the device tables once per engine
@@ -324,7 +280,8 @@ static int pred_run(jaicov_engine *e, bool check, double sa, double sb, const in
                     int32_t *gstatus) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
-    TRY(pred_common(v));
+    TRY(q_guard(v, "image predictions on a sharded engine",
+                "image predictions need all of Qxx on the device: solve with invert FULL or FULL_EXPANDED first"));
     const DevProblem &p = *v.p;
     const char *what = check ? "check measurements: NULL argument, a negative count or a malformed group table"
                              : "image predictions: NULL argument or a negative count";
@@ -336,14 +293,10 @@ static int pred_run(jaicov_engine *e, bool check, double sa, double sb, const in
     } else if (!(sa >= 0.0) || !(sb >= 0.0)) {
         FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "image predictions: sigma2 and k2 must not be negative");
     }
-    for (int i = 0; i < n; i++) {
+    for (int i = 0; i < n; i++)
         if (images[i] < 0 || images[i] >= p.n_images || points[i] < 0 || points[i] >= p.n_points)
             FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "image predictions: image or point index out of range");
-        if (check) {
-            const double vx = disp[3 * (size_t)i], vy = disp[3 * (size_t)i + 1], rho = disp[3 * (size_t)i + 2];
-            if (!(vx > 0.0) || !(vy > 0.0) || !(fabs(rho) < 1.0)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "check measurements: var must be positive and |rho| below 1");
-        }
-    }
+    if (check && !dispersions_ok(disp, n)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "check measurements: var must be positive and |rho| below 1");
     if (n_groups > 0) {
         if (group_begin[0] != 0 || group_begin[n_groups] != n) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "check measurements: group_begin must run from 0 to n");
         for (int g = 0; g < n_groups; g++) {
@@ -353,7 +306,7 @@ static int pred_run(jaicov_engine *e, bool check, double sa, double sb, const in
     }
     if (n == 0) return JAICOV_OK;
     HIPE(*v.err, hipSetDevice(v.device));
-    PredictState *st = pred_state(v);
+    PredictState *st = q_state(v.slot->pred);
     TRY(pred_observed(v, st));
 
     // a stable counting sort by image: order[s] = the caller's index of sorted position s, inv its inverse
@@ -382,56 +335,43 @@ static int pred_run(jaicov_engine *e, bool check, double sa, double sb, const in
     for (size_t g = 0; g <= G; g++) tab[o_gbegin + g] = G ? group_begin[g] : 0;
     for (int i = 0; i < n; i++) tab[o_gpos + i] = inv[i];
     const int NC = check ? JAICOV_PRED_CHECK_COLUMNS : JAICOV_PRED_POINT_COLUMNS;
-    const size_t o_w = (size_t)2 * KROW * N, o_x = o_w + 2 * N, o_y = o_x + N, o_disp = o_y + N, n_rows = o_disp + 3 * N;
+    PairRows pr(N);
     HIPE(*v.err, st->tab.reserve(n_tab));
-    HIPE(*v.err, st->rows.reserve(n_rows));
+    HIPE(*v.err, st->rows.reserve(pr.size));
     HIPE(*v.err, st->out.reserve((size_t)NC * N + JAICOV_PRED_GROUP_COLUMNS * G));
     int32_t *d_tab = st->tab.get();
-    double *d_rows = st->rows.get(), *d_out = st->out.get(), *d_gout = d_out + (size_t)NC * N;
+    double *d_out = st->out.get(), *d_gout = d_out + (size_t)NC * N;
+    pr.bind(st->rows.get());
     HIPE(*v.err, hipMemcpyAsync(d_tab, tab.data(), n_up * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
     // the rows are zeroed first: rows_kernel writes no column behind the camera's coefficients; x = y = 0 for a prediction
-    HIPE(*v.err, hipMemsetAsync(d_rows, 0, o_disp * sizeof(double), v.stream));
-    std::vector<double> meas;
-    if (check) {
-        meas.resize(5 * N);
-        for (size_t s = 0; s < N; s++) {
-            const size_t i = (size_t)order[s];
-            meas[s] = xy[2 * i]; meas[N + s] = xy[2 * i + 1];
-            for (int k = 0; k < 3; k++) meas[2 * N + 3 * s + k] = disp[3 * i + k];
-        }
-        HIPE(*v.err, hipMemcpyAsync(d_rows + o_x, meas.data(), 5 * N * sizeof(double), hipMemcpyHostToDevice, v.stream));
-    }
-    DevEvent ev[4];
-    if (st->timing)
-        for (DevEvent &x : ev) HIPE(*v.err, x.create());
-    auto mark = [&](int k) { return st->timing ? hipEventRecord(ev[k].get(), v.stream) : hipSuccess; };
-    DevProblem q = p;
-    q.n_ip = n; q.ip_image = d_tab; q.ip_point = d_tab + o_pt; q.ip_x = d_rows + o_x; q.ip_y = d_rows + o_y;
-    HIPE(*v.err, mark(0));
-    HIPE(*v.err, launch_rows(v.stream, q, v.d_vals, 0, n, d_rows, d_rows + o_w));
-    HIPE(*v.err, mark(1));
+    HIPE(*v.err, hipMemsetAsync(pr.J, 0, pr.o_disp * sizeof(double), v.stream));
+    HIPE(*v.err, pr.stage(v.stream, xy, disp, order.data()));
+    QTimer<4> timer(v.stream);
+    HIPE(*v.err, timer.arm(st->timing));
+    HIPE(*v.err, timer.mark(0));
+    HIPE(*v.err, pr.rows(v.stream, pr.problem(p, d_tab, d_tab + o_pt), v.d_vals));
+    HIPE(*v.err, timer.mark(1));
     if (check)
         hipLaunchKernelGGL(pred_cov_kernel<true>, dim3((unsigned)W), dim3(PRED_WG), 0, v.stream, v.Q, v.ld, p, d_tab, d_tab + o_pt, d_tab + o_first,
-                           d_tab + o_count, n, d_rows, d_rows + o_w, d_rows + o_disp, sa, sb, d_out, d_tab + o_status);
+                           d_tab + o_count, n, pr.J, pr.w, pr.disp, sa, sb, d_out, d_tab + o_status);
     else
         hipLaunchKernelGGL(pred_cov_kernel<false>, dim3((unsigned)W), dim3(PRED_WG), 0, v.stream, v.Q, v.ld, p, d_tab, d_tab + o_pt, d_tab + o_first,
-                           d_tab + o_count, n, d_rows, d_rows + o_w, d_rows + o_disp, sa, sb, d_out, d_tab + o_status);
+                           d_tab + o_count, n, pr.J, pr.w, pr.disp, sa, sb, d_out, d_tab + o_status);
     HIPE(*v.err, hipGetLastError());
-    HIPE(*v.err, mark(2));
+    HIPE(*v.err, timer.mark(2));
     if (G > 0) {
-        hipLaunchKernelGGL(pred_group_kernel, dim3((unsigned)G), dim3(64), 0, v.stream, v.Q, v.ld, p, d_tab, d_tab + o_pt, n, d_rows, d_rows + o_w,
-                           d_rows + o_disp, d_tab + o_gbegin, d_tab + o_gpos, sa, sb, d_gout, d_tab + o_gstatus);
+        hipLaunchKernelGGL(pred_group_kernel, dim3((unsigned)G), dim3(64), 0, v.stream, v.Q, v.ld, p, d_tab, d_tab + o_pt, n, pr.J, pr.w,
+                           pr.disp, d_tab + o_gbegin, d_tab + o_gpos, sa, sb, d_gout, d_tab + o_gstatus);
         HIPE(*v.err, hipGetLastError());
     }
-    HIPE(*v.err, mark(3));
+    HIPE(*v.err, timer.mark(3));
     std::vector<double> h_out((size_t)NC * N), h_gout(JAICOV_PRED_GROUP_COLUMNS * G);
     std::vector<int32_t> h_status(N), h_gstatus(G);
     TRY(q_download(v, {{h_out.data(), d_out, h_out.size() * sizeof(double)},
                        {h_status.data(), d_tab + o_status, N * sizeof(int32_t)},
                        {h_gout.data(), d_gout, h_gout.size() * sizeof(double)},
                        {h_gstatus.data(), d_tab + o_gstatus, G * sizeof(int32_t)}}));
-    if (st->timing)
-        for (int k = 0; k < 3; k++) HIPE(*v.err, hipEventElapsedTime(&st->ms[k], ev[k].get(), ev[k + 1].get()));
+    HIPE(*v.err, timer.read(st->ms));
     // back into the caller's order, with the one bit the host knows
     for (int i = 0; i < n; i++) {
         const size_t s = (size_t)inv[i];
@@ -464,7 +404,7 @@ extern "C" int jaicov_pred_check(jaicov_engine *e, double sigma2_post, const int
 // ms[0 .. 2]: what the rows, pred_cov_kernel and pred_group_kernel of the last call took.
 extern "C" int jaicov_debug_pred_timing(jaicov_engine *e, int on, float *ms) {
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
-    PredictState *st = pred_state(q_view(e));
+    PredictState *st = q_state(q_view(e).slot->pred);
     st->timing = on != 0;
     if (ms)
         for (int k = 0; k < 3; k++) ms[k] = st->ms[k];

@@ -1,6 +1,12 @@
 // The one interface between engine.hip (owner of jaicov_engine) and whatever reads the cofactor matrix an inverting solve leaves on
-// the device: transform.hip, reliability.hip, datum.hip (the one writer), precision.hip, parameters.hip, forms.hip, predict.hip and newpoints.hip.  A consumer adds a state struct of its own,
-// a slot for it in QSlots and its guards; the facts the guards test come from here.
+// the device: transform.hip, reliability.hip, datum.hip (the one writer), precision.hip, parameters.hip, forms.hip, predict.hip and
+// newpoints.hip.  Here are the view of the engine (QView), the shell of a call and the device's reads of the matrix.  A consumer adds
+// a state struct of its own and a slot for it in QSlots; a call of it is, in the order of refusals that the headers under include/
+// promise (engine, shard, state, arguments):
+//   q_view, q_guard with the call's own texts, the argument checks (argcheck.h; q_column for a slot's column), q_state for the work
+//   buffers, the launches on v.stream (QTimer around them where a bench hook times them), q_download.
+// Its kernels read the matrix through q_sym or q_at.  Calls that bring image measurements of their own build their rows with
+// pairrows.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,7 +17,9 @@
 #include <vector>
 
 #include "../../include/jaicov_neq.h"
+#include "argcheck.h"
 #include "ba_kernels.h"
+#include "devbuf.h"
 #include "status.h"
 
 namespace jaicov {
@@ -78,6 +86,50 @@ inline QView q_view(jaicov_engine *e) {
     return v;
 }
 
+// The refusals a reader begins with: a sharded engine (UNSUPPORTED), then the matrix (BAD_STATE).  full_text null: any cofactor
+// matrix will do; otherwise all of Qxx is needed, and this is what its absence is called.
+inline int q_guard(const QView &v, const char *sharded_text, const char *full_text = nullptr) {
+    if (v.sharded) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, sharded_text);
+    if (full_text ? !v.full_q : !v.have_q) FAIL(*v.err, JAICOV_ERR_BAD_STATE, full_text ? full_text : "no cofactor matrix: solve with invert != 0 first");
+    return JAICOV_OK;
+}
+
+// the state of a slot, created on first use
+template <typename S>
+inline S *q_state(std::unique_ptr<S> &slot) {
+    if (!slot) slot.reset(new S());
+    return slot.get();
+}
+
+// *c = the matrix column of a slot, -1 for a fixed parameter; a column outside the reduced matrix is refused with `what`
+inline int q_column(const QView &v, size_t slot_index, const char *what, int *c) {
+    const int col = (*v.slot_col)[slot_index];
+    if (col >= v.order) FAIL(*v.err, JAICOV_ERR_BAD_STATE, what);
+    *c = col < 0 ? -1 : col;
+    return JAICOV_OK;
+}
+
+// N marks on the engine's stream behind a bench hook's switch; not armed, it creates no event and does nothing
+template <int N>
+class QTimer {
+    DevEvent ev_[N];
+    hipStream_t stream_;
+    bool on_ = false;
+  public:
+    explicit QTimer(hipStream_t stream) : stream_(stream) {}
+    hipError_t arm(bool on) {
+        on_ = on;
+        for (int k = 0; on_ && k < N; k++) HIPCHK(ev_[k].create());
+        return hipSuccess;
+    }
+    hipError_t mark(int k) { return on_ ? hipEventRecord(ev_[k].get(), stream_) : hipSuccess; }
+    // ms[k]: from mark k to mark k + 1, once the stream has been synchronised
+    hipError_t read(float *ms) {
+        for (int k = 0; on_ && k + 1 < N; k++) HIPCHK(hipEventElapsedTime(&ms[k], ev_[k].get(), ev_[k + 1].get()));
+        return hipSuccess;
+    }
+};
+
 // the state a slot holds, or null with `none` as the error text
 template <typename S>
 inline S *q_result(const QView &v, const std::unique_ptr<S> &slot, const char *none) {
@@ -102,6 +154,19 @@ inline int q_download(const QView &v, std::initializer_list<QCopy> copies) {
         if (c.dst && c.bytes) HIPE(*v.err, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, v.stream));
     HIPE(*v.err, hipStreamSynchronize(v.stream));
     return JAICOV_OK;
+}
+
+// ---- the device's reads of the matrix
+
+// entry (i, j) of the symmetric matrix from its lower part
+__device__ __forceinline__ double q_sym(const double *__restrict__ Q, long ld, int i, int j) {
+    return i >= j ? Q[(long)i * ld + j] : Q[(long)j * ld + i];
+}
+
+// the same by columns of parameters: a fixed parameter (column < 0) is a zero row and column
+__device__ __forceinline__ double q_at(const double *__restrict__ Q, long ld, int ci, int cj) {
+    if (ci < 0 || cj < 0) return 0.0;
+    return q_sym(Q, ld, ci, cj);
 }
 
 }  // namespace jaicov

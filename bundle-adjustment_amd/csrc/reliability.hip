@@ -54,9 +54,6 @@ constexpr int RL_K = 64;                  // inner dimension of the shared-colum
 constexpr double RL_UNCONTROLLED = 1e-10; // (P Q_vv P)_ii <= this * P_ii: the observation is not controlled, t = NaN
 static_assert(2 * KC_MAX <= RL_K && RL_K % GEMM_BK == 0, "[Y | A_s] must fit the inner dimension of the shared-column GEMM");
 
-__device__ __forceinline__ double rl_q(const double *__restrict__ Q, long ld, int i, int j) {
-    return i >= j ? Q[(long)i * ld + j] : Q[(long)j * ld + i];
-}
 // shared local column c (0..kc) -> local row of the compact rows, and its global column (assemble.hip's shared_local / shared_col)
 __device__ __forceinline__ int rl_local(int c) { return c < 3 ? 3 + c : (c < 9 ? 6 + (c - 3) : 12 + (c - 9)); }
 __device__ __forceinline__ int rl_col(const DevProblem &p, int img, int cam, int jb, int c) {
@@ -114,7 +111,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_points_kernel(DevProblem p, const 
     for (int i = tid; i < kc * kc; i += RL_PTS) {
         const int a = i / kc, b = i - a * kc;
         const int qa = scol[a], qb = scol[b];
-        sQ[a * KC_MAX + b] = (qa < 0 || qb < 0) ? 0.0 : rl_q(Q, ld, qa, qb);
+        sQ[a * KC_MAX + b] = (qa < 0 || qb < 0) ? 0.0 : q_sym(Q, ld, qa, qb);
     }
     __syncthreads();
     if (tid >= ch.y) return;
@@ -139,7 +136,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_points_kernel(DevProblem p, const 
 #pragma unroll
         for (int b = 0; b < 3; b++) {
             if (pc[a] < 0 || pc[b] < 0) continue;
-            const double q = rl_q(Q, ld, pc[a], pc[b]);
+            const double q = q_sym(Q, ld, pc[a], pc[b]);
             h00 = fma(ap[0][a], q * ap[0][b], h00);
             h01 = fma(ap[0][a], q * ap[1][b], h01);
             h11 = fma(ap[1][a], q * ap[1][b], h11);
@@ -151,7 +148,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_points_kernel(DevProblem p, const 
 #pragma unroll
         for (int a = 0; a < 3; a++) {
             if (pc[a] < 0) continue;
-            const double q = rl_q(Q, ld, qc, pc[a]);
+            const double q = q_sym(Q, ld, qc, pc[a]);
             y0 = fma(q, ap[0][a], y0);
             y1 = fma(q, ap[1][a], y1);
         }
@@ -203,7 +200,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_prep_kernel(DevProblem p, const in
     for (int i = tid; i < kc * kc; i += RL_PTS) {
         const int a = i / kc, b = i - a * kc;
         const int qa = scol[a], qb = scol[b];
-        sQ[a * KC_MAX + b] = (qa < 0 || qb < 0) ? 0.0 : rl_q(Q, ld, qa, qb);
+        sQ[a * KC_MAX + b] = (qa < 0 || qb < 0) ? 0.0 : q_sym(Q, ld, qa, qb);
     }
     __syncthreads();
     const int i = blockIdx.x * RL_PTS + tid;
@@ -228,7 +225,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_prep_kernel(DevProblem p, const in
         if (c < kc && scol[c] >= 0) {
 #pragma unroll
             for (int a = 0; a < 3; a++)
-                if (pc[a] >= 0) y = fma(rl_q(Q, ld, scol[c], pc[a]), ap[a], y);
+                if (pc[a] >= 0) y = fma(q_sym(Q, ld, scol[c], pc[a]), ap[a], y);
             double z = 0.0;
             for (int b = 0; b < kc; b++) z = fma(sQ[c * KC_MAX + b], my[b * RL_PTS], z);
             u = y + z;
@@ -395,7 +392,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_points_loo_kernel(DevProblem p, co
     for (int i = tid; i < kc * kc; i += RL_PTS) {
         const int a = i / kc, b = i - a * kc;
         const int qa = scol[a], qb = scol[b];
-        sQ[a * KC_MAX + b] = (qa < 0 || qb < 0) ? 0.0 : rl_q(Q, ld, qa, qb);
+        sQ[a * KC_MAX + b] = (qa < 0 || qb < 0) ? 0.0 : q_sym(Q, ld, qa, qb);
     }
     __syncthreads();
     if (tid >= ch.y) return;
@@ -420,7 +417,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_points_loo_kernel(DevProblem p, co
 #pragma unroll
         for (int b = 0; b < 3; b++) {
             if (pc[a] < 0 || pc[b] < 0) continue;
-            const double q = rl_q(Q, ld, pc[a], pc[b]);
+            const double q = q_sym(Q, ld, pc[a], pc[b]);
             h00 = fma(ap[0][a], q * ap[0][b], h00);
             h01 = fma(ap[0][a], q * ap[1][b], h01);
             h11 = fma(ap[1][a], q * ap[1][b], h11);
@@ -432,7 +429,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_points_loo_kernel(DevProblem p, co
 #pragma unroll
         for (int a = 0; a < 3; a++) {
             if (pc[a] < 0) continue;
-            const double q = rl_q(Q, ld, qc, pc[a]);
+            const double q = q_sym(Q, ld, qc, pc[a]);
             y0 = fma(q, ap[0][a], y0);
             y1 = fma(q, ap[1][a], y1);
         }
@@ -472,7 +469,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_points_loo_kernel(DevProblem p, co
         const double bp = ap[0][b] * c0 + ap[1][b] * c1;
 #pragma unroll
         for (int a = 0; a < 3; a++)
-            if (pc[a] >= 0) sh[a] = fma(rl_q(Q, ld, pc[a], pc[b]), bp, sh[a]);
+            if (pc[a] >= 0) sh[a] = fma(q_sym(Q, ld, pc[a], pc[b]), bp, sh[a]);
     }
     for (int c = 0; c < kc; c++) {
         const int qc = scol[c];
@@ -480,7 +477,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_points_loo_kernel(DevProblem p, co
         const double bs = my0[c * RL_PTS] * c0 + my1[c * RL_PTS] * c1;
 #pragma unroll
         for (int a = 0; a < 3; a++)
-            if (pc[a] >= 0) sh[a] = fma(rl_q(Q, ld, pc[a], qc), bs, sh[a]);
+            if (pc[a] >= 0) sh[a] = fma(q_sym(Q, ld, pc[a], qc), bs, sh[a]);
     }
     const bool ok = !isnan(nab.x);
 #pragma unroll
@@ -555,7 +552,7 @@ __global__ __launch_bounds__(256) void rel_shift_pp_kernel(DevProblem p, const i
     for (int i = tid; i < RL_PC * RL_PC; i += 256) {
         const int r = i / RL_PC, c = i - r * RL_PC;
         const int qr = colA[r], qc = colB[c];
-        sQ[r * (RL_PC + 1) + c] = (qr < 0 || qc < 0) ? 0.0 : rl_q(Q, ld, qr, qc);
+        sQ[r * (RL_PC + 1) + c] = (qr < 0 || qc < 0) ? 0.0 : q_sym(Q, ld, qr, qc);
     }
     __syncthreads();
     const double *Pb = P + (long)blockIdx.y * mpad * mpad, *nb_ = nab + (long)blockIdx.y * mpad;
@@ -635,7 +632,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_shift_kernel(DevProblem p, const i
         if (qc < 0) continue;
 #pragma unroll
         for (int a = 0; a < 3; a++)
-            if (pc[a] >= 0) sh[a] = fma(rl_q(Q, ld, pc[a], qc), acc[c], sh[a]);
+            if (pc[a] >= 0) sh[a] = fma(q_sym(Q, ld, pc[a], qc), acc[c], sh[a]);
     }
     const long n = p.n_ip, o = new2old ? new2old[ipb + q] : ipb + q;
     const bool ok = !isnan(nx);
@@ -662,7 +659,7 @@ __global__ __launch_bounds__(64) void rel_scalebar_kernel(DevProblem p, const do
         v = fma(ev[k], dx[col[k]], v);
         double z = 0.0;
         for (int l = 0; l < 6; l++)
-            if (col[l] >= 0) z = fma(rl_q(Q, ld, col[k], col[l]), ev[l], z);
+            if (col[l] >= 0) z = fma(q_sym(Q, ld, col[k], col[l]), ev[l], z);
         h = fma(ev[k], z, h);
     }
     const double P = s0 / p.sb_var[s];
@@ -686,7 +683,7 @@ __global__ __launch_bounds__(256) void rel_direct_kernel(DevProblem p, const dou
     };
     auto h_of = [&](int k, int l) {
         const int ck = col_of(k), cl = col_of(l);
-        return (ck < 0 || cl < 0) ? 0.0 : rl_q(Q, ld, ck, cl);
+        return (ck < 0 || cl < 0) ? 0.0 : q_sym(Q, ld, ck, cl);
     };
     for (int i = threadIdx.x; i < m; i += 256) {
         const double hii = h_of(i, i), vi = v_of(i);

@@ -166,6 +166,37 @@ __device__ inline WaveStatus wave_solve_lds(int n, double *U, double *b, double 
 // index of (i, j >= i) in an upper triangle of order n packed row by row
 __device__ inline int tri_ix_n(int n, int i, int j) { return i * n - i * (i - 1) / 2 + (j - i); }
 
+// The scaling in front of wave_chol_lds, A (packed upper) in place: powers of two bring the diagonal into [1, 4) without rounding,
+// whatever its magnitude (Sc), then the Jacobi scaling to a unit diagonal (Sv); row i of the system takes Sc[i] Sv[i].  z, to which
+// the caller has added 0 x its own values, comes back NaN in some lane unless every entry of A is finite too.
+__device__ inline void wave_equilibrate_lds(int n, double *U, double *Sc, double *Sv, double &z, int lane) {
+    const double EPS = ldexp(1.0, -53);
+    if (lane < n) {
+        const double qd = U[tri_ix_n(n, lane, lane)];
+        Sc[lane] = (qd > 0.0 && isfinite(qd)) ? ldexp(1.0, -(ilogb(qd) >> 1)) : 1.0;
+    }
+    __syncthreads();
+    for (int i = 0; i < n; i++) {
+        const int j = i + lane;
+        if (j < n) {
+            const double a = U[tri_ix_n(n, i, j)];
+            z += a * 0.0;
+            U[tri_ix_n(n, i, j)] = a * (Sc[i] * Sc[j]);
+        }
+    }
+    __syncthreads();
+    if (lane < n) {
+        const double a = U[tri_ix_n(n, lane, lane)];
+        Sv[lane] = a > EPS ? 1.0 / sqrt(a) : 1.0;
+    }
+    __syncthreads();
+    for (int i = 0; i < n; i++) {
+        const int j = i + lane;
+        if (j < n) U[tri_ix_n(n, i, j)] = U[tri_ix_n(n, i, j)] * (Sv[i] * Sv[j]);
+    }
+    __syncthreads();
+}
+
 // U'U = A in place (A packed upper, already scaled to a unit diagonal).  At column j every lane forms the pivot, lane i > j the
 // entry U_ji: p = U_jj - sum_{r<j} U_rj U_rj; U_ji = (U_ji - sum_{r<j} U_ri U_rj) / sqrt(p), r ascending.
 __device__ inline WaveStatus wave_chol_lds(int n, double *U, int lane) {

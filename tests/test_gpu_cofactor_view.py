@@ -1,6 +1,6 @@
 """Every consumer of the cofactor matrix in every state of the engine that decides what it may read: a table of state x call.
 
-The consumers (transform, reliability, datum, precision, the getters of the engine) each test the same few facts about the matrix an
+The consumers (transform, reliability, datum, precision, parameters, forms, predict, new points, the getters of the engine) each test the same few facts about the matrix an
 inverting solve leaves: is there one, is it the reduced one, is the engine a shard.  The table below is their status code and, for a
 refusal, the whole text of jaicov_neq_last_error, written out from the consumers' sources and the order of refusals that the headers
 under include/ state.  One engine walks through
@@ -27,6 +27,12 @@ NO_S = (-2, "no datum transformation since the last inverting solve")
 SHARD_REL = (-3, "reliability needs an engine that holds every observation (not a shard)")
 SHARD_DATUM = (-3, "datum transformation on a sharded engine")
 SHARD_PREC = (-3, "precision figures on a sharded engine")
+SHARD_PAR = (-3, "parameter correlations and tests on a sharded engine")
+SHARD_FORM = (-3, "forms on a sharded engine")
+SHARD_PRED = (-3, "image predictions on a sharded engine")
+SHARD_NEWPT = (-3, "new points on a sharded engine")
+NO_ALL_PRED = (-2, "image predictions need all of Qxx on the device: solve with invert FULL or FULL_EXPANDED first")
+NO_ALL_NEWPT = (-2, "new points need all of Qxx on the device: solve with invert FULL or FULL_EXPANDED first")
 NO_DEFECT = (-3, "datum transformation: the network has no datum defect (d = 0)")
 BAD_S2T = (-1, "sigma2_test must be positive and finite")
 BAD_L0 = (-1, "lambda0 must be positive and finite")
@@ -35,6 +41,11 @@ BAD_MASK = (-1, "point_datum must hold one flag per object point")
 BAD_ITEM = (-1, "precision: index out of range")
 BAD_PAIR = (-1, "length precision: point index out of range")
 BAD_K = (-1, "principal components: k must be 1 .. 4")
+BAD_BITS = (-1, "correlation maxima: unknown bits in pair_mask or flags")
+BAD_SLOT = (-1, "parameter tests: slot out of range")
+BAD_MEMBER = (-1, "forms: point index out of range")
+BAD_PRED = (-1, "image predictions: image or point index out of range")
+BAD_RAY = (-1, "new points: image index out of range")
 BAD_LEN = (-1, "cofactor buffer length must be order(order+1)/2 with order = jaicov_neq_cofactor_order()")
 BAD_IDX = (-1, None)                # jaicov_neq_get_cofactor_sub names no reason for an index out of range
 
@@ -48,6 +59,12 @@ TABLE = {
         "precision_stations": (NO_Q, NO_Q),
         "precision_lengths": (NO_Q, NO_Q),
         "principal_components": (NO_Q, NO_Q),
+        "correlation_maxima": (NO_Q, NO_Q),
+        "parameter_tests": (NO_Q, NO_Q),
+        "fit_forms": (NO_Q, NO_Q),
+        "predict_image_points": (NO_ALL_PRED, NO_ALL_PRED),
+        "check_image_points": (NO_ALL_PRED, NO_ALL_PRED),
+        "intersect_new_points": (NO_ALL_NEWPT, NO_ALL_NEWPT),
         "get_cofactor": (NO_Q_GET, NO_Q_GET),
         "get_cofactor_sub": (NO_Q, NO_Q),
         "datum_transform": (NO_Q, NO_Q),
@@ -60,6 +77,12 @@ TABLE = {
         "precision_stations": (NO_STATIONS, NO_STATIONS),
         "precision_lengths": (OK, BAD_PAIR),
         "principal_components": (OK, BAD_K),
+        "correlation_maxima": (OK, BAD_BITS),
+        "parameter_tests": (OK, BAD_SLOT),
+        "fit_forms": (OK, BAD_MEMBER),
+        "predict_image_points": (NO_ALL_PRED, NO_ALL_PRED),
+        "check_image_points": (NO_ALL_PRED, NO_ALL_PRED),
+        "intersect_new_points": (NO_ALL_NEWPT, NO_ALL_NEWPT),
         "get_cofactor": (OK, BAD_LEN),
         "get_cofactor_sub": (OK, BAD_IDX),
         "datum_transform": (OK, BAD_MASK),
@@ -72,6 +95,12 @@ TABLE = {
         "precision_stations": (OK, BAD_ITEM),
         "precision_lengths": (OK, BAD_PAIR),
         "principal_components": (OK, BAD_K),
+        "correlation_maxima": (OK, BAD_BITS),
+        "parameter_tests": (OK, BAD_SLOT),
+        "fit_forms": (OK, BAD_MEMBER),
+        "predict_image_points": (OK, BAD_PRED),
+        "check_image_points": (OK, BAD_PRED),
+        "intersect_new_points": (OK, BAD_RAY),
         "get_cofactor": (OK, BAD_LEN),
         "get_cofactor_sub": (OK, BAD_IDX),
         "datum_transform": (OK, BAD_MASK),
@@ -84,6 +113,12 @@ TABLE = {
         "precision_stations": (SHARD_PREC, SHARD_PREC),
         "precision_lengths": (SHARD_PREC, SHARD_PREC),
         "principal_components": (SHARD_PREC, SHARD_PREC),
+        "correlation_maxima": (SHARD_PAR, SHARD_PAR),
+        "parameter_tests": (SHARD_PAR, SHARD_PAR),
+        "fit_forms": (SHARD_FORM, SHARD_FORM),
+        "predict_image_points": (SHARD_PRED, SHARD_PRED),
+        "check_image_points": (SHARD_PRED, SHARD_PRED),
+        "intersect_new_points": (SHARD_NEWPT, SHARD_NEWPT),
         "get_cofactor": (NO_Q_GET, NO_Q_GET),
         "get_cofactor_sub": (NO_Q, NO_Q),
         "datum_transform": (SHARD_DATUM, SHARD_DATUM),
@@ -98,6 +133,14 @@ def get_cofactor(eng, n):
     return Q
 
 
+def correlation_maxima(eng, n, pair_mask):
+    """jaicov_par_maxima itself (Engine.correlation_maxima answers a missing matrix on its own)."""
+    rho = np.zeros(n); partner = np.zeros(n, np.int32); status = np.zeros(n, np.int32)
+    pi = C.POINTER(C.c_int32)
+    eng._chk(eng.L.jaicov_par_maxima(eng._h, pair_mask, 0, rho.ctypes.data_as(C.POINTER(C.c_double)), partner.ctypes.data_as(pi),
+                                     status.ctypes.data_as(pi), n))
+
+
 def calls(eng, fp):
     """call -> (with valid arguments, with one invalid argument)"""
     P, I, U = fp.n_points, fp.n_images, fp.n_unknowns
@@ -105,6 +148,8 @@ def calls(eng, fp):
     n = order * (order + 1) // 2
     first, cols = eng.point_column_range()
     rel = dict(omega=1.0, dof=fp.degree_of_freedom)
+    var = [1e-6]
+    rays = dict(ray_begin=[0, 2], xy=np.zeros((2, 2)), disp=[[1e-6, 1e-6, 0.0]] * 2, start=fp.values[0:3])
     return {
         "transform": (lambda: eng.transform([0, 1, 2], [(0, 1)], S2), lambda: eng.transform([0, P], [(0, 1)], S2)),
         "reliability": (lambda: eng.reliability(S2), lambda: eng.reliability(-1.0)),
@@ -114,6 +159,15 @@ def calls(eng, fp):
         "precision_lengths": (lambda: eng.precision_lengths(S2, [(0, 1)]), lambda: eng.precision_lengths(S2, [(0, P)])),
         "principal_components": (lambda: eng.principal_components(3, first, cols, max_iterations=4),
                                  lambda: eng.principal_components(5, first, cols, max_iterations=4)),
+        "correlation_maxima": (lambda: correlation_maxima(eng, order, engine.PAR_ALL_PAIRS),
+                               lambda: correlation_maxima(eng, order, 1 << 16)),
+        "parameter_tests": (lambda: eng.parameter_tests(S2, [[0, 1, 2]]), lambda: eng.parameter_tests(S2, [[0, fp.n_slots]])),
+        "fit_forms": (lambda: eng.fit_forms(S2, [("plane", [0, 1, 2, 3])]), lambda: eng.fit_forms(S2, [("plane", [0, 1, 2, P])])),
+        "predict_image_points": (lambda: eng.predict_image_points(S2, [0], [0]), lambda: eng.predict_image_points(S2, [0], [P])),
+        "check_image_points": (lambda: eng.check_image_points([0], [0], np.zeros((1, 2)), var, var),
+                               lambda: eng.check_image_points([0], [P], np.zeros((1, 2)), var, var)),
+        "intersect_new_points": (lambda: eng.intersect_new_points(S2, ray_image=[0, 1], **rays),
+                                 lambda: eng.intersect_new_points(S2, ray_image=[0, I], **rays)),
         "get_cofactor": (lambda: get_cofactor(eng, n), lambda: get_cofactor(eng, n + 1)),
         "get_cofactor_sub": (lambda: eng.get_cofactor_sub([0, order - 1]), lambda: eng.get_cofactor_sub([0, U + 7])),
         "datum_transform": (lambda: eng.datum_transform(np.ones(P)), lambda: eng.datum_transform(np.ones(P + 1))),
