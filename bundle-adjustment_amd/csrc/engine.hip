@@ -23,6 +23,7 @@
 #include "forms.h"
 #include "predict.h"
 #include "newpoints.h"
+#include "vce.h"
 #include "gemm_f64.h"
 #include "parameters.h"
 #include "precision.h"
@@ -1587,6 +1588,7 @@ void jaicov::engine_q_view(jaicov_engine *e, QView *v) {
     v->ip_old2new = &e->ip_old2new;
     v->blk_ip_begin = &e->h_blk_ip_begin;
     v->blk_w_off = &e->h_blk_w_off;
+    v->caller_block = &e->h_caller_block;
     v->slot = &e->slot;
     v->err = &e->err;
 }

@@ -32,6 +32,7 @@ struct ParamState;       // parameters.h
 struct FormState;        // forms.h
 struct PredictState;     // predict.h
 struct NewPointState;    // newpoints.h
+struct VceState;         // vce.h
 
 // The engine's slots for what its consumers keep.  A result (xform, rel) stays until the next run of its family or its release, a
 // later inverting solve included; an inverting solve withdraws the S of the datum state alone (datum_state_invalidate).
@@ -44,6 +45,7 @@ struct QSlots {
     std::unique_ptr<FormState> form;         // work buffers of jaicov_form_fit
     std::unique_ptr<PredictState> pred;      // work buffers of the jaicov_pred_* calls
     std::unique_ptr<NewPointState> newpt;    // work buffers of jaicov_newpt_intersect
+    std::unique_ptr<VceState> vce;           // result of jaicov_vce_run
 };
 
 // What a consumer sees of an engine.  Pointers stay owned by the engine.
@@ -72,6 +74,7 @@ struct QView {
     const std::vector<int32_t> *ip_old2new = nullptr;   // empty, or the engine position of the caller's image point
     const std::vector<int32_t> *blk_ip_begin = nullptr; // engine image blocks (ordinary images served as blocks included)
     const std::vector<int64_t> *blk_w_off = nullptr;    // their weight offsets in p->blk_w (< 0: 2 x 2 weights)
+    const std::vector<int32_t> *caller_block = nullptr; // empty, or the caller's index of an engine image block (-1: an ordinary image)
     QSlots *slot = nullptr;            // the engine's slots
     std::string *err = nullptr;        // jaicov_neq_last_error text
 };

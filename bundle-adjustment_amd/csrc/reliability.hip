@@ -906,6 +906,27 @@ static int rel_run_impl(const QView &v, RelState *s, double s2t, const double *d
     return JAICOV_OK;
 }
 
+// The run once state and arguments are accepted: from here on the previous result goes.
+static int rel_run_accepted(jaicov_engine *e, const QView &v, double sigma2_test, const double *dx, const RelPointArgs *pa, long rows) {
+    HIPE(*v.err, hipSetDevice(v.device));
+    int rc = engine_ensure_rows(e);    // the compact rows of the current parameter values
+    if (rc != JAICOV_OK) return rc;
+    v.slot->rel.reset();
+    std::unique_ptr<RelState> s(new RelState());
+    s->n_rows = rows;
+    rc = rel_run_impl(v, s.get(), sigma2_test, dx, pa);
+    if (rc != JAICOV_OK) {
+        hipStreamSynchronize(v.stream);
+        return rc;
+    }
+    v.slot->rel = std::move(s);
+    return JAICOV_OK;
+}
+
+int jaicov::rel_run_plain(jaicov_engine *e, const QView &v, double sigma2_test, const double *dx, long rows) {
+    return rel_run_accepted(e, v, sigma2_test, dx, nullptr, rows);
+}
+
 // jaicov_rel_run (pa == nullptr) and jaicov_rel_run_points
 static int rel_run_checked(jaicov_engine *e, double sigma2_test, const double *dx, const RelPointArgs *pa, int32_t *n_rows,
                            int32_t *n_image_points) {
@@ -919,19 +940,7 @@ static int rel_run_checked(jaicov_engine *e, double sigma2_test, const double *d
     const DevProblem &p0 = *v.p;
     const long rows = 2 * (long)p0.n_ip + p0.n_sb + p0.n_dg_rows;
     if (rows > INT32_MAX) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "more than 2^31 - 1 observation rows");
-    HIPE(*v.err, hipSetDevice(v.device));
-    int rc = engine_ensure_rows(e);    // the compact rows of the current parameter values
-    if (rc != JAICOV_OK) return rc;
-    // the arguments are accepted: the previous result goes
-    v.slot->rel.reset();
-    std::unique_ptr<RelState> s(new RelState());
-    s->n_rows = rows;
-    rc = rel_run_impl(v, s.get(), sigma2_test, dx, pa);
-    if (rc != JAICOV_OK) {
-        hipStreamSynchronize(v.stream);
-        return rc;
-    }
-    v.slot->rel = std::move(s);
+    TRY(rel_run_accepted(e, v, sigma2_test, dx, pa, rows));
     if (n_rows) *n_rows = (int32_t)rows;
     if (n_image_points) *n_image_points = (int32_t)p0.n_ip;
     return JAICOV_OK;

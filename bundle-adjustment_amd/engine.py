@@ -3,7 +3,7 @@
 ``include/jaicov_datum.h`` / ``include/jaicov_intersect.h`` / ``include/jaicov_resect.h`` /
 ``include/jaicov_relorient.h`` / ``include/jaicov_simil.h`` / ``include/jaicov_lens.h`` / ``include/jaicov_precision.h`` /
 ``include/jaicov_parameters.h`` / ``include/jaicov_forms.h`` / ``include/jaicov_predict.h`` /
-``include/jaicov_newpoints.h`` (``csrc/libjaicov_neq.so``).
+``include/jaicov_newpoints.h`` / ``include/jaicov_vce.h`` (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
 library has not been built, and every call fails with ``EngineError`` when no gfx950 device is present.
@@ -82,6 +82,10 @@ NEWPT_PARTIAL, NEWPT_NOT_CONVERGED, NEWPT_TOO_FEW_RAYS, NEWPT_TOO_MANY, NEWPT_SI
 NEWPT_FAILED = NEWPT_TOO_FEW_RAYS | NEWPT_TOO_MANY | NEWPT_SINGULAR | NEWPT_NOT_FINITE
 NEWPT_PAIR_PARTIAL, NEWPT_PAIR_NEGATIVE, NEWPT_PAIR_NOT_FINITE, NEWPT_PAIR_DEGENERATE = 1, 2, 4, 8                             # bits of a pair
 NEWPT_COLUMNS, NEWPT_PAIR_COLUMNS, NEWPT_MAX_RAYS, NEWPT_MAX_COLS = 20, 7, 64, 448
+# include/jaicov_vce.h: variance components of observation groups from the residuals, redundancy numbers and weights on the device
+VCE_EXPORTS = ["jaicov_vce_run", "jaicov_vce_get", "jaicov_vce_summary", "jaicov_vce_release"]
+VCE_EMPTY, VCE_UNCONTROLLED, VCE_NOT_FINITE = 1, 2, 4                                                  # status bits of a group
+VCE_COLUMNS = 6
 # jaicov_dlt_restriction (DirectLinearTransformation.RestrictionType, DT:51-58 order) and the per-image status values
 DLT_IDENTICAL_PRINCIPLE_DISTANCE, DLT_ROTATION_WITHOUT_SHEAR, DLT_FIXED_PRINCIPLE_DISTANCE_X, DLT_FIXED_PRINCIPLE_DISTANCE_Y, \
     DLT_FIXED_PRINCIPAL_POINT_X, DLT_FIXED_PRINCIPAL_POINT_Y = range(6)
@@ -223,6 +227,11 @@ def load_library():
     L.jaicov_pred_points.argtypes = [vp, C.c_double, C.c_double, _pi, _pi, C.c_int32, _pd, _pi]
     L.jaicov_pred_check.argtypes = [vp, C.c_double, _pi, _pi, _pd, _pd, C.c_int32, _pi, C.c_int32, _pd, _pi, _pd, _pi]
     L.jaicov_newpt_intersect.argtypes = [vp, C.c_double, C.c_int32, _pi, _pi, _pd, _pd, _pd, C.c_int32, _pi, C.c_int32, _pd, _pi, _pi, _pd, _pd, _pi]
+    L.jaicov_vce_run.argtypes = [vp, C.c_double, _pd, _pi, _pi, _pi, C.c_int32, _pi]
+    L.jaicov_vce_get.argtypes = [vp, _pd, _pi, C.c_int32]
+    L.jaicov_vce_summary.argtypes = [vp, _pd, C.c_int32]
+    L.jaicov_vce_release.argtypes = [vp]
+    L.jaicov_debug_vce_timing.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
     L.jaicov_dlt_adjust.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pi, C.c_int32, C.c_int32, _pd, _pi, _pi, _pd]
     L.jaicov_isect_points.argtypes = [C.c_int32, _pi, _pi, _pd, _pd, C.c_int32, _pd, _pd, C.c_double, C.c_int32, C.c_double, C.c_int32,
                                       _pd, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
@@ -275,6 +284,32 @@ GroupCheck = namedtuple("GroupCheck", ["q", "T_prio", "T_post", "dof", "status"]
 # ray_w (n_rays, 2)) and one per pair (lengths (n_pairs, 7): L, sigma_L, sigma of D_X, D_Y, D_Z, q_L, q_L without the cross block)
 NewPoints = namedtuple("NewPoints", ["xyz", "cof_meas", "cof", "sigma", "omega", "dof", "status", "iterations", "ray_w", "lengths",
                                      "length_status"])
+
+
+# Groups of weight blocks for Engine.variance_components (vce_groups builds them): ip / sb / dg hold the group of every image point,
+# scale bar and directly observed group (-1: in none; None: none of that kind is in a group); names: one label per group
+VceGroups = namedtuple("VceGroups", ["ip", "sb", "dg", "n_groups", "names"])
+# the totals of Engine.variance_components over all rows, grouped or not
+VceSummary = namedtuple("VceSummary", ["omega", "sum_r", "rows_grouped", "rows_ungrouped", "damping"])
+# estimate_variance_components: factors (n_groups,) accumulated over the iterations, tables (one VarianceComponents per iteration),
+# engine (the last one, open), problem (the FlatProblem that engine was built from), converged
+VceEstimate = namedtuple("VceEstimate", ["factors", "tables", "engine", "problem", "converged"])
+
+
+class VarianceComponents:
+    """Engine.variance_components: one entry per group (include/jaicov_vce.h).  n rows, omega = sum v_b' P_b v_b, r = sum r_i,
+    s2 = omega / r, k = s2 / sigma0^2 (the factor for the group's dispersions), sd = k sqrt(2 / r); s2, k, sd are NaN where status
+    has VCE_EMPTY, VCE_UNCONTROLLED or VCE_NOT_FINITE.  table is the (VCE_COLUMNS, n_groups) array of them, summary a VceSummary."""
+
+    def __init__(self, table, status, summary, names=None):
+        self.table, self.status, self.summary, self.names = table, status, summary, names
+        self.n, self.omega, self.r, self.s2, self.k, self.sd = table
+
+    def __repr__(self):
+        names = self.names if self.names is not None else [str(g) for g in range(self.status.size)]
+        rows = [f"  {nm}: n={int(n)} omega={om:.6g} r={r:.6g} k={k:.4g} +- {sd:.2g} status={st}"
+                for nm, n, om, r, k, sd, st in zip(names, self.n, self.omega, self.r, self.k, self.sd, self.status)]
+        return "VarianceComponents(\n" + "\n".join(rows) + f"\n  {self.summary})"
 
 
 def _p(a):
@@ -518,6 +553,45 @@ class Engine:
 
     def reliability_release(self):
         self._chk(self.L.jaicov_rel_release(self._h))
+
+    # variance components (include/jaicov_vce.h) -------------------------------------------------------------------------------
+    def variance_components(self, groups, sigma2_test=None, dx=None):
+        """Variance components of groups of observations (a VceGroups, see vce_groups): for every group the factor k by which its
+        a-priori dispersions should be multiplied, from Omega_g = sum v' P v and r_g = sum r_i of its weight blocks.  Runs
+        reliability(sigma2_test, dx) first, through the same routine, so that call's result is fresh afterwards.  sigma2_test None =
+        the variance factor of the last build; it enters the test values of the reliability result only.  Needs all of Qxx."""
+        d = None if dx is None else np.ascontiguousarray(dx, np.float64)
+        if d is not None and d.size != self.fp.n_unknowns:
+            raise ValueError("dx must have U entries")
+        fp = self.fp
+
+        def ids(a, n, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.int32).ravel()
+            if a.size != n:
+                raise ValueError(f"groups.{what} must have {n} entries")
+            return a
+        ip = ids(groups.ip, fp.n_image_points, "ip"); sb = ids(groups.sb, fp.n_scale_bars, "sb"); dg = ids(groups.dg, fp.n_direct_groups, "dg")
+        if sigma2_test is None:
+            sigma2_test = getattr(self, "_sigma2_build", fp.sigma2apriori)
+        G = int(groups.n_groups)
+        as_pi = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(_pi)
+        self._chk(self.L.jaicov_vce_run(self._h, float(sigma2_test), None if d is None else _p(d), as_pi(ip), as_pi(sb), as_pi(dg), G, None))
+        table = np.zeros((VCE_COLUMNS, G)); status = np.zeros(G, np.int32); summ = np.zeros(5)
+        self._chk(self.L.jaicov_vce_get(self._h, _p(table), status.ctypes.data_as(_pi), G))
+        self._chk(self.L.jaicov_vce_summary(self._h, _p(summ), 5))
+        return VarianceComponents(table, status, VceSummary(*summ), groups.names)
+
+    def variance_components_reliability(self, n_rows=None):
+        """The Reliability (v, qvv, r, t) that the last variance_components left on the device."""
+        n = self.fp.n_observations if n_rows is None else int(n_rows)
+        out = [np.zeros(n) for _ in range(4)]
+        self._chk(self.L.jaicov_rel_get(self._h, *[_p(a) for a in out], n))
+        return Reliability(*out)
+
+    def variance_components_release(self):
+        self._chk(self.L.jaicov_vce_release(self._h))
 
     # datum transformation (include/jaicov_datum.h) --------------------------------------------------------------------------------
     def datum_transform(self, mask):
@@ -793,6 +867,53 @@ class Engine:
         res = EstimateResult()
         self._chk(self.L.jaicov_neq_estimate(self._h, C.byref(o), C.byref(res)))
         return self.get_parameters(), res
+
+
+def vce_groups(fp: FlatProblem, by="kind") -> VceGroups:
+    """Groups for Engine.variance_components.  by = "kind": image points / scale bars / directly observed rows (three groups, some
+    perhaps empty); "camera": the image points of every camera; "image": the image points of every image; "direct_group": every
+    directly observed group on its own."""
+    n_ip, n_sb, n_dg = fp.n_image_points, fp.n_scale_bars, fp.n_direct_groups
+    if by == "kind":
+        return VceGroups(np.zeros(n_ip, np.int32), np.full(n_sb, 1, np.int32), np.full(n_dg, 2, np.int32), 3,
+                         ["image points", "scale bars", "direct rows"])
+    if by == "camera":
+        return VceGroups(fp.image_camera[fp.ip_image].astype(np.int32), None, None, fp.n_cameras, [f"camera {c}" for c in range(fp.n_cameras)])
+    if by == "image":
+        return VceGroups(fp.ip_image.astype(np.int32), None, None, fp.n_images, [f"image {i}" for i in range(fp.n_images)])
+    if by == "direct_group":
+        if n_dg == 0:
+            raise ValueError("the problem has no directly observed groups")
+        return VceGroups(None, None, np.arange(n_dg, dtype=np.int32), n_dg, [f"direct group {g}" for g in range(n_dg)])
+    raise ValueError(f"by must be 'kind', 'camera', 'image' or 'direct_group', not {by!r}")
+
+
+def estimate_variance_components(fp: FlatProblem, groups, tol=0.05, max_iter=10, values=None, lam0=0.0, max_estimate_iter=5000,
+                                 **engine_kw) -> VceEstimate:
+    """Iterated variance component estimation.  Per iteration: a FRESH engine from the problem (the weights are cached when an
+    engine is created, so scaled dispersions need a new one), estimate() from the last parameter values with the full inverse,
+    variance_components(groups), and the dispersions of every group multiplied by its k (problem.scale_dispersions).  Stops when
+    max |k_g - 1| <= tol over the groups with a finite k, or after max_iter iterations.  A group whose k is NaN (empty, not
+    controlled) keeps its factor.  Returns a VceEstimate; its engine is the last one and stays open."""
+    from .problem import scale_dispersions
+    factors = np.ones(int(groups.n_groups))
+    tables = []
+    vals = fp.values if values is None else values
+    eng, converged, k = None, False, None
+    for _ in range(max_iter):
+        if eng is not None:
+            eng.close()
+            fp = scale_dispersions(fp, groups, k)
+        eng = Engine(fp, **engine_kw)
+        vals, _res = eng.estimate(values=vals, lam0=lam0, max_iter=max_estimate_iter, invert=INVERT_FULL)
+        vc = eng.variance_components(groups)
+        tables.append(vc)
+        k = np.where(np.isfinite(vc.k), vc.k, 1.0)
+        factors = factors * k
+        if np.max(np.abs(k - 1.0)) <= tol:
+            converged = True
+            break
+    return VceEstimate(factors, tables, eng, fp, converged)
 
 
 def point_column_range(fp: FlatProblem):

@@ -241,6 +241,17 @@ PYBIND11_MODULE(_jaicov_host, m) {
         }, py::arg("sigma2"), py::arg("rayBegin"), py::arg("rayImage"), py::arg("xy"), py::arg("disp"), py::arg("start"),
              py::arg("pairs") = std::vector<int32_t>(), py::arg("maxIterations") = 20,
              "(table (n, 20), status (n,), iterations (n,), ray_w (R, 2), lengths (G, 7), length status (G,)) of new object points (include/jaicov_newpoints.h)")
+        .def("varianceComponents", [](BundleAdjustment &b, std::vector<int32_t> ip, std::vector<int32_t> sb, std::vector<int32_t> dg, int nGroups,
+                                      double sigma2Test) {
+            BundleAdjustment::VarianceGroups g;
+            g.ip = std::move(ip); g.sb = std::move(sb); g.dg = std::move(dg); g.nGroups = nGroups;
+            auto r = b.varianceComponents(g, sigma2Test);
+            const double summary[5] = {r.omega, r.sumR, r.rowsGrouped, r.rowsUngrouped, r.damping};
+            return py::make_tuple(py::array_t<double>({(size_t)JAICOV_VCE_COLUMNS, r.status.size()}, r.table.data()),
+                                  py::array_t<int32_t>((py::ssize_t)r.status.size(), r.status.data()), py::array_t<double>(5, summary));
+        }, py::arg("ip") = std::vector<int32_t>(), py::arg("sb") = std::vector<int32_t>(), py::arg("dg") = std::vector<int32_t>(),
+             py::arg("nGroups") = 0, py::arg("sigma2Test") = 0.0,
+             "(table (6, G), status (G,), summary (5,)) of the variance components of groups of observations (include/jaicov_vce.h)")
         .def("useCentroidedCoordinates", &BundleAdjustment::useCentroidedCoordinates)
         .def("centroidCoordinates", &BundleAdjustment::centroidCoordinates)
         .def("applyAposterioriVarianceOfUnitWeight", &BundleAdjustment::applyAposterioriVarianceOfUnitWeight)

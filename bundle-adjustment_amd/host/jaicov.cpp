@@ -698,6 +698,45 @@ BundleAdjustment::NewPoints BundleAdjustment::intersectNewPoints(double sigma2, 
     return r;
 }
 
+// include/jaicov_vce.h on the engine of the last estimateModel
+BundleAdjustment::VarianceComponents BundleAdjustment::varianceComponents(const VarianceGroups &g, double sigma2Test) const {
+    if (!engine_ || inversion_ != MatrixInversion::FULL)
+        throw std::runtime_error("no full cofactor matrix: run estimateModel with MatrixInversion.FULL first");
+    const size_t nIp = flat.ip_image.size(), nSb = flat.sb_a.size(), nDg = flat.dg_row_begin.size() - 1;
+    if ((!g.ip.empty() && g.ip.size() != nIp) || (!g.sb.empty() && g.sb.size() != nSb) || (!g.dg.empty() && g.dg.size() != nDg))
+        throw std::runtime_error("varianceComponents: ip, sb and dg hold one group per image point, scale bar and directly observed group, or are empty");
+    const int G = g.nGroups;
+    int rc = jaicov_vce_run(engine_, sigma2Test > 0 ? sigma2Test : sigma2apriori_, nullptr, g.ip.empty() ? nullptr : g.ip.data(),
+                            g.sb.empty() ? nullptr : g.sb.data(), g.dg.empty() ? nullptr : g.dg.data(), G, nullptr);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_vce_run: ") + jaicov_neq_last_error(engine_));
+    VarianceComponents r;
+    r.table.resize((size_t)JAICOV_VCE_COLUMNS * G);
+    r.status.resize(G);
+    rc = jaicov_vce_get(engine_, r.table.data(), r.status.data(), G);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_vce_get: ") + jaicov_neq_last_error(engine_));
+    double s[5];
+    rc = jaicov_vce_summary(engine_, s, 5);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_vce_summary: ") + jaicov_neq_last_error(engine_));
+    r.omega = s[0]; r.sumR = s[1]; r.rowsGrouped = s[2]; r.rowsUngrouped = s[3]; r.damping = s[4];
+    return r;
+}
+
+BundleAdjustment::VarianceGroups BundleAdjustment::varianceGroupsByKind() const {
+    VarianceGroups g;
+    g.ip.assign(flat.ip_image.size(), 0);
+    g.sb.assign(flat.sb_a.size(), 1);
+    g.dg.assign(flat.dg_row_begin.size() - 1, 2);
+    g.nGroups = 3;
+    return g;
+}
+
+BundleAdjustment::VarianceGroups BundleAdjustment::varianceGroupsByImage() const {
+    VarianceGroups g;
+    g.ip = flat.ip_image;
+    g.nGroups = (int)flat.image_camera.size();
+    return g;
+}
+
 // CTEO:49-121: rows, coordinates and sigma2 J Qxx J' on the device (jaicov_xform_run), the results copied back
 void CoordinateTransformationExteriorOrientation::transform(const std::vector<ObjectCoordinate *> &objectCoordinatesToTransform,
                                                             const std::vector<std::pair<Image *, std::vector<Image *>>> &imagesToAlign,

@@ -42,6 +42,7 @@
 #include "../../include/jaicov_forms.h"
 #include "../../include/jaicov_predict.h"
 #include "../../include/jaicov_newpoints.h"
+#include "../../include/jaicov_vce.h"
 
 namespace jaicov::host {
 
@@ -631,6 +632,24 @@ public:
     NewPoints intersectNewPoints(double sigma2, const std::vector<int32_t> &rayBegin, const std::vector<int32_t> &rayImage,
                                  const std::vector<double> &xy, const std::vector<double> &disp, const std::vector<double> &start,
                                  const std::vector<int32_t> &pairs = {}, int maxIterations = 20) const;
+    // Variance components of groups of observations (include/jaicov_vce.h) on the engine of the last estimateModel, at the adjusted
+    // values (a zero step); needs MatrixInversion.FULL.  A group is a union of weight blocks: ip names the group of every image
+    // point (in the order of the rows, one entry per pair), sb of every scale bar, dg of every directly observed group; -1: in no
+    // group; an empty vector: none of that kind.  The image points of an image with a joint dispersion must share one group.
+    struct VarianceGroups {
+        std::vector<int32_t> ip, sb, dg;
+        int nGroups = 0;
+    };
+    struct VarianceComponents {
+        std::vector<double> table;               // JAICOV_VCE_COLUMNS rows of nGroups entries: n_g, Omega_g, r_g, s2_g, k_g, sd(k_g)
+        std::vector<int32_t> status;             // JAICOV_VCE_* bits of every group
+        double omega = 0, sumR = 0, rowsGrouped = 0, rowsUngrouped = 0, damping = 0;   // the totals over all rows
+        double k(int g) const { return table[4 * status.size() + g]; }
+    };
+    VarianceComponents varianceComponents(const VarianceGroups &groups, double sigma2Test = 0.0) const;   // sigma2Test <= 0: the a-priori factor
+    // the groups "by kind" (image points, scale bars, directly observed rows) and "by image" of the flattened problem
+    VarianceGroups varianceGroupsByKind() const;
+    VarianceGroups varianceGroupsByImage() const;
     const std::string &lastError() const { return lastError_; }
     jaicov_engine *nativeEngine() const { return engine_; }     // the engine of the last estimateModel (null before)
 

@@ -188,3 +188,53 @@ def packed_to_full(ap: np.ndarray, n: int) -> np.ndarray:
 def full_to_packed(full: np.ndarray) -> np.ndarray:
     n = full.shape[0]
     return np.ascontiguousarray(full[np.tril_indices(n)])
+
+
+def block_groups(fp: FlatProblem, ip_group) -> np.ndarray:
+    """The group of every dense image block from the groups of the image points; a block whose points differ is an error."""
+    ip_group = np.asarray(ip_group)
+    out = np.full(fp.n_image_blocks, -1, np.int32)
+    for b in range(fp.n_image_blocks):
+        lo, hi = int(fp.blk_ip_begin[b]), int(fp.blk_ip_begin[b + 1])
+        if hi <= lo:
+            continue
+        if np.any(ip_group[lo:hi] != ip_group[lo]):
+            raise ValueError(f"the image points of dense image block {b} name more than one group")
+        out[b] = ip_group[lo]
+    return out
+
+
+def scale_dispersions(fp: FlatProblem, groups, factors) -> FlatProblem:
+    """A new FlatProblem whose a-priori dispersions are multiplied, group by group, by `factors` (one per group; NaN leaves the
+    group as it is): ``ip_var_x``, ``ip_var_y``, ``blk_disp``, ``sb_var``, ``dg_var`` and ``dg_disp``.  `groups` has the fields
+    ``ip``, ``sb``, ``dg`` (group of every image point, scale bar and directly observed group, -1: none; None: none of the kind), as
+    ``engine.vce_groups`` returns them.  ``ip_rho`` stays as it is (a correlation coefficient has no scale), and so does
+    ``sigma2apriori``: the factors are relative to the variance factor the weights were built with, and changing it as well would
+    apply them twice."""
+    import dataclasses
+    f = np.asarray(factors, np.float64).copy()
+    f[~np.isfinite(f)] = 1.0
+
+    def of(ids, n):
+        ids = np.full(n, -1, np.int64) if ids is None else np.asarray(ids, np.int64)
+        return np.where(ids >= 0, f[np.maximum(ids, 0)], 1.0)
+
+    fi = of(groups.ip, fp.n_image_points)
+    blk_disp = fp.blk_disp.copy()
+    if fp.n_image_blocks:
+        bg = block_groups(fp, np.full(fp.n_image_points, -1) if groups.ip is None else groups.ip)
+        for b in range(fp.n_image_blocks):
+            m = 2 * int(fp.blk_ip_begin[b + 1] - fp.blk_ip_begin[b])
+            if bg[b] >= 0 and m:
+                off = int(fp.blk_disp_offset[b])
+                blk_disp[off:off + m * m] *= f[bg[b]]
+    fg = of(groups.dg, fp.n_direct_groups)
+    dg_var = fp.dg_var.copy(); dg_disp = fp.dg_disp.copy()
+    for g in range(fp.n_direct_groups):
+        lo, hi = int(fp.dg_row_begin[g]), int(fp.dg_row_begin[g + 1])
+        dg_var[lo:hi] *= fg[g]
+        off = int(fp.dg_disp_offset[g]) if fp.dg_disp_offset.size > g else -1
+        if off >= 0:
+            dg_disp[off:off + (hi - lo) ** 2] *= fg[g]
+    return dataclasses.replace(fp, ip_var_x=fp.ip_var_x * fi, ip_var_y=fp.ip_var_y * fi, blk_disp=blk_disp,
+                               sb_var=fp.sb_var * of(groups.sb, fp.n_scale_bars), dg_var=dg_var, dg_disp=dg_disp)
