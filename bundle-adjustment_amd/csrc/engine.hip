@@ -24,6 +24,7 @@
 #include "predict.h"
 #include "newpoints.h"
 #include "vce.h"
+#include "calibration.h"
 #include "gemm_f64.h"
 #include "parameters.h"
 #include "precision.h"

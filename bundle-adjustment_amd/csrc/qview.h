@@ -1,6 +1,6 @@
 // The one interface between engine.hip (owner of jaicov_engine) and whatever reads the cofactor matrix an inverting solve leaves on
-// the device: transform.hip, reliability.hip, datum.hip (the one writer), precision.hip, parameters.hip, forms.hip, predict.hip and
-// newpoints.hip.  Here are the view of the engine (QView), the shell of a call and the device's reads of the matrix.  A consumer adds
+// the device: transform.hip, reliability.hip, datum.hip (the one writer), precision.hip, parameters.hip, forms.hip, predict.hip,
+// newpoints.hip, vce.hip and calibration.hip.  Here are the view of the engine (QView), the shell of a call and the device's reads of the matrix.  A consumer adds
 // a state struct of its own and a slot for it in QSlots; a call of it is, in the order of refusals that the headers under include/
 // promise (engine, shard, state, arguments):
 //   q_view, q_guard with the call's own texts, the argument checks (argcheck.h; q_column for a slot's column), q_state for the work
@@ -33,6 +33,7 @@ struct FormState;        // forms.h
 struct PredictState;     // predict.h
 struct NewPointState;    // newpoints.h
 struct VceState;         // vce.h
+struct CalibState;       // calibration.h
 
 // The engine's slots for what its consumers keep.  A result (xform, rel) stays until the next run of its family or its release, a
 // later inverting solve included; an inverting solve withdraws the S of the datum state alone (datum_state_invalidate).
@@ -46,6 +47,7 @@ struct QSlots {
     std::unique_ptr<PredictState> pred;      // work buffers of the jaicov_pred_* calls
     std::unique_ptr<NewPointState> newpt;    // work buffers of jaicov_newpt_intersect
     std::unique_ptr<VceState> vce;           // result of jaicov_vce_run
+    std::unique_ptr<CalibState> calib;       // work buffers of the jaicov_calib_* calls
 };
 
 // What a consumer sees of an engine.  Pointers stay owned by the engine.

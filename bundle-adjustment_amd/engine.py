@@ -3,7 +3,7 @@
 ``include/jaicov_datum.h`` / ``include/jaicov_intersect.h`` / ``include/jaicov_resect.h`` /
 ``include/jaicov_relorient.h`` / ``include/jaicov_simil.h`` / ``include/jaicov_lens.h`` / ``include/jaicov_precision.h`` /
 ``include/jaicov_parameters.h`` / ``include/jaicov_forms.h`` / ``include/jaicov_predict.h`` /
-``include/jaicov_newpoints.h`` / ``include/jaicov_vce.h`` (``csrc/libjaicov_neq.so``).
+``include/jaicov_newpoints.h`` / ``include/jaicov_vce.h`` / ``include/jaicov_calibration.h`` (``csrc/libjaicov_neq.so``).
 
 This is the Python image of the stub a JNI shim would hold.  There is no CPU path: loading fails loudly when the HIP
 library has not been built, and every call fails with ``EngineError`` when no gfx950 device is present.
@@ -86,6 +86,12 @@ NEWPT_COLUMNS, NEWPT_PAIR_COLUMNS, NEWPT_MAX_RAYS, NEWPT_MAX_COLS = 20, 7, 64, 4
 VCE_EXPORTS = ["jaicov_vce_run", "jaicov_vce_get", "jaicov_vce_summary", "jaicov_vce_release"]
 VCE_EMPTY, VCE_UNCONTROLLED, VCE_NOT_FINITE = 1, 2, 4                                                  # status bits of a group
 VCE_COLUMNS = 6
+# include/jaicov_calibration.h: the distortion field of a camera with its covariance, and the comparison of two calibrations
+CALIB_EXPORTS = ["jaicov_calib_field", "jaicov_calib_compare", "jaicov_calib_release"]
+CALIB_PARTIAL, CALIB_NEGATIVE, CALIB_NOT_FINITE, CALIB_SINGULAR = 1, 2, 4, 16                         # status bits of a node
+CALIB_FIELD_COLUMNS, CALIB_COMPARE_COLUMNS, CALIB_SUMMARY_COLUMNS, CALIB_MAX_COLUMNS = 14, 8, 8, 23
+CALIB_PRINCIPAL_POINT, CALIB_PRINCIPAL_DISTANCE, CALIB_KIND_SHIFT, CALIB_ALL = 1, 2, 2, 4095          # `columns` of calibration_field
+CALIB_RELATIVE = 1                                                                                      # `flags` of calibration_compare
 # jaicov_dlt_restriction (DirectLinearTransformation.RestrictionType, DT:51-58 order) and the per-image status values
 DLT_IDENTICAL_PRINCIPLE_DISTANCE, DLT_ROTATION_WITHOUT_SHEAR, DLT_FIXED_PRINCIPLE_DISTANCE_X, DLT_FIXED_PRINCIPLE_DISTANCE_Y, \
     DLT_FIXED_PRINCIPAL_POINT_X, DLT_FIXED_PRINCIPAL_POINT_Y = range(6)
@@ -232,6 +238,10 @@ def load_library():
     L.jaicov_vce_summary.argtypes = [vp, _pd, C.c_int32]
     L.jaicov_vce_release.argtypes = [vp]
     L.jaicov_debug_vce_timing.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
+    L.jaicov_calib_field.argtypes = [vp, C.c_double, C.c_double, C.c_uint32, _pi, _pd, _pd, C.c_int32, _pd, _pd, _pi]
+    L.jaicov_calib_compare.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, _pd, _pd, C.c_uint32, _pd, _pd, C.c_int32, _pd, _pi, _pd]
+    L.jaicov_calib_release.argtypes = [vp]
+    L.jaicov_debug_calib_timing.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
     L.jaicov_dlt_adjust.argtypes = [C.c_int32, _pi, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pi, C.c_int32, C.c_int32, _pd, _pi, _pi, _pd]
     L.jaicov_isect_points.argtypes = [C.c_int32, _pi, _pi, _pd, _pd, C.c_int32, _pd, _pd, C.c_double, C.c_int32, C.c_double, C.c_int32,
                                       _pd, _pi, _pi, C.POINTER(C.c_uint8), _pd, _pd]
@@ -280,6 +290,13 @@ ImagePrediction = namedtuple("ImagePrediction", ["xy", "cof", "sigma", "ellipse"
 # Engine.check_image_points: one entry per pair (d (n, 2), M (n, 3): m_xx, m_xy, m_yy) and one per group (dof = 2 m)
 ImageCheck = namedtuple("ImageCheck", ["d", "M", "q", "T_prio", "T_post", "status"])
 GroupCheck = namedtuple("GroupCheck", ["q", "T_prio", "T_post", "dof", "status"])
+# Engine.calibration_field: one entry per node (include/jaicov_calibration.h); delta (n, 2): the image correction; cof (n, 3): q_xx, q_xy,
+# q_yy of J Q J' over the selected columns; radial (n, 2): dr, dt and sigma_radial (n, 2) their sigmas; jac (n, 2, 23) or None
+CalibrationField = namedtuple("CalibrationField", ["delta", "cof", "sigma", "ellipse", "direction", "radial", "sigma_radial", "status", "jac"])
+# Engine.calibration_compare: one entry per node (d (n, 2), M (n, 3): m_xx, m_xy, m_yy of C_d; all None with nodes=False) and the summary
+CalibrationCompare = namedtuple("CalibrationCompare", ["d", "M", "q", "T_prio", "T_post", "status", "summary"])
+CalibrationSummary = namedtuple("CalibrationSummary", ["n_finite", "rms", "rms_expected", "max_d", "max_d_node", "max_T_prio", "max_T_node",
+                                                       "n_singular"])
 # Engine.intersect_new_points: one entry per new point (cof_meas, cof (n, 6): xx xy xz yy yz zz of Q_meas and of Q_XX = Q_meas + Q_sys;
 # ray_w (n_rays, 2)) and one per pair (lengths (n_pairs, 7): L, sigma_L, sigma of D_X, D_Y, D_Z, q_L, q_L without the cross block)
 NewPoints = namedtuple("NewPoints", ["xyz", "cof_meas", "cof", "sigma", "omega", "dof", "status", "iterations", "ray_w", "lengths",
@@ -772,6 +789,63 @@ class Engine:
             return pairs, None
         return pairs, GroupCheck(gout[:G, 0], gout[:G, 1], gout[:G, 2], gout[:G, 3].astype(np.int32), gstatus[:G])
 
+    # the camera in image space (include/jaicov_calibration.h) ---------------------------------------------------------------------------
+    def calibration_field(self, sigma2, cameras, xy, depth=None, k2=1.0, columns=CALIB_ALL, jacobian=False):
+        """The image correction of camera cameras[i] (a scalar: one camera for all) at the node xy[i] = (xs, ys), ideal coordinates
+        relative to the principal point at the current c, with its 2 x 2 cofactor block over the camera's selected columns (`columns`:
+        CALIB_PRINCIPAL_POINT, CALIB_PRINCIPAL_DISTANCE, 1 << (CALIB_KIND_SHIFT + kind), CALIB_ALL), sigmas, the confidence ellipse and
+        the radial and tangential components.  The ray is held fixed.  depth None: N = -c (refused for a camera with D_i terms).  Any
+        cofactor matrix serves, that of INVERT_REDUCED included.  Returns a CalibrationField."""
+        l = np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2))
+        n = l.shape[0]
+        cam = np.ascontiguousarray(cameras, np.int32).ravel()
+        if cam.size == 1:
+            cam = np.full(n, cam[0], np.int32)
+        dep = None if depth is None else np.ascontiguousarray(np.broadcast_to(np.asarray(depth, np.float64), (n,)))
+        if cam.size != n or (dep is not None and dep.size != n):
+            raise ValueError("cameras, xy and depth must run parallel")
+        out = np.zeros((n, CALIB_FIELD_COLUMNS)); status = np.zeros(n, np.int32)
+        jac = np.zeros((n, 2, CALIB_MAX_COLUMNS)) if jacobian else None
+        self._chk(self.L.jaicov_calib_field(self._h, float(sigma2), float(k2), int(columns), cam.ctypes.data_as(_pi), _p(l),
+                                            None if dep is None else _p(dep), n, _p(out), None if jac is None else _p(jac),
+                                            status.ctypes.data_as(_pi)))
+        return CalibrationField(out[:, 0:2], out[:, 2:5], out[:, 5:7], out[:, 7:9], out[:, 9], out[:, 10:12], out[:, 12:14], status, jac)
+
+    def calibration_compare(self, cam_a, cam_b, xy, depth=None, ref_values=None, ref_cov=None, sigma2_post=None, relative=False, nodes=True):
+        """The difference field d = g_a - g_b of two calibrations at the nodes xy (ideal coordinates at camera cam_a's current c, the
+        same ray for both sides) with its cofactor block C_d, q = d' inv(C_d) d, T_prio and T_post.  Side B is camera cam_b of this
+        engine, or with ref_values (x0, y0, c, then the coefficients of cam_b's table) a certificate or an earlier epoch, ref_cov its
+        covariance.  relative: positions relative to each side's own principal point.  The summary (CalibrationSummary) is formed on
+        the device; nodes=False returns it alone.  sigma2_post None: the a-priori factor.  Returns a CalibrationCompare."""
+        l = np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2))
+        n = l.shape[0]
+        dep = None if depth is None else np.ascontiguousarray(np.broadcast_to(np.asarray(depth, np.float64), (n,)))
+        if dep is not None and dep.size != n:
+            raise ValueError("xy and depth must run parallel")
+        ref = None if ref_values is None else np.ascontiguousarray(ref_values, np.float64).ravel()
+        cov = None if ref_cov is None else np.ascontiguousarray(ref_cov, np.float64)
+        if ref is not None:
+            K = 3 + int(self.fp.cam_dist_begin[cam_b + 1] - self.fp.cam_dist_begin[cam_b]) if 0 <= cam_b < self.fp.n_cameras else ref.size
+            if ref.size != K or (cov is not None and cov.shape != (K, K)):
+                raise ValueError("ref_values holds x0, y0, c and the coefficients of camera cam_b, ref_cov their covariance")
+        if sigma2_post is None:
+            sigma2_post = getattr(self, "_sigma2_build", self.fp.sigma2apriori)
+        out = np.zeros((n, CALIB_COMPARE_COLUMNS)) if nodes else None
+        status = np.zeros(n, np.int32) if nodes else None
+        summ = np.zeros(CALIB_SUMMARY_COLUMNS)
+        self._chk(self.L.jaicov_calib_compare(self._h, float(sigma2_post), int(cam_a), int(cam_b), None if ref is None else _p(ref),
+                                              None if cov is None else _p(cov), CALIB_RELATIVE if relative else 0, _p(l),
+                                              None if dep is None else _p(dep), n, None if out is None else _p(out),
+                                              None if status is None else status.ctypes.data_as(_pi), _p(summ)))
+        summary = CalibrationSummary(int(summ[0]), summ[1], summ[2], summ[3], int(summ[4]), summ[5], int(summ[6]), int(summ[7]))
+        if not nodes:
+            return CalibrationCompare(None, None, None, None, None, None, summary)
+        return CalibrationCompare(out[:, 0:2], out[:, 2:5], out[:, 5], out[:, 6], out[:, 7], status, summary)
+
+    def calibration_release(self):
+        """Frees the work buffers of the calibration calls."""
+        self._chk(self.L.jaicov_calib_release(self._h))
+
     # object space (include/jaicov_newpoints.h) -------------------------------------------------------------------------------------
     def new_point_start_values(self, ray_begin, ray_image, xy, disp):
         """Start values (n, 3) of new points for intersect_new_points: the measurements reduced to the distortion-free camera
@@ -867,6 +941,19 @@ class Engine:
         res = EstimateResult()
         self._chk(self.L.jaicov_neq_estimate(self._h, C.byref(o), C.byref(res)))
         return self.get_parameters(), res
+
+
+def sensor_grid(width, height, nx, ny):
+    """nx x ny nodes (nx ny, 2) over a sensor of width x height about the principal point, row by row from (-width / 2, -height / 2):
+    the nodes of Engine.calibration_field and calibration_compare"""
+    gx, gy = np.meshgrid(np.linspace(-0.5 * width, 0.5 * width, int(nx)), np.linspace(-0.5 * height, 0.5 * height, int(ny)))
+    return np.column_stack([gx.ravel(), gy.ravel()])
+
+
+def radial_profile(rmax, n, azimuth=0.0):
+    """n nodes (n, 2) at the radii rmax / n, 2 rmax / n, .., rmax along the direction `azimuth` (radians from +x towards +y)"""
+    r = rmax * np.arange(1, int(n) + 1) / int(n)
+    return np.column_stack([r * np.cos(azimuth), r * np.sin(azimuth)])
 
 
 def vce_groups(fp: FlatProblem, by="kind") -> VceGroups:

@@ -252,6 +252,27 @@ PYBIND11_MODULE(_jaicov_host, m) {
         }, py::arg("ip") = std::vector<int32_t>(), py::arg("sb") = std::vector<int32_t>(), py::arg("dg") = std::vector<int32_t>(),
              py::arg("nGroups") = 0, py::arg("sigma2Test") = 0.0,
              "(table (6, G), status (G,), summary (5,)) of the variance components of groups of observations (include/jaicov_vce.h)")
+        .def("calibrationField", [](BundleAdjustment &b, double sigma2, std::vector<int32_t> cameras, std::vector<double> xy, std::vector<double> depth,
+                                    double k2, uint32_t columns, bool withJacobian) {
+            auto f = b.calibrationField(sigma2, cameras, xy, depth, k2, columns, withJacobian);
+            const size_t n = f.status.size();
+            return py::make_tuple(py::array_t<double>({n, (size_t)JAICOV_CALIB_FIELD_COLUMNS}, f.table.data()),
+                                  py::array_t<int32_t>((py::ssize_t)n, f.status.data()),
+                                  py::array_t<double>({withJacobian ? n : (size_t)0, (size_t)2, (size_t)JAICOV_CALIB_MAX_COLUMNS}, f.jacobian.data()));
+        }, py::arg("sigma2"), py::arg("cameras"), py::arg("xy"), py::arg("depth") = std::vector<double>(), py::arg("k2") = 1.0,
+             py::arg("columns") = (uint32_t)JAICOV_CALIB_ALL, py::arg("withJacobian") = false,
+             "(table (n, 14), status (n,), jacobian (n, 2, 23) or (0, 2, 23)) of the distortion field at the nodes (include/jaicov_calibration.h)")
+        .def("compareCalibration", [](BundleAdjustment &b, int camA, int camB, std::vector<double> xy, std::vector<double> depth,
+                                      std::vector<double> refValues, std::vector<double> refCov, double sigma2Post, bool relative) {
+            auto c = b.compareCalibration(camA, camB, xy, depth, refValues, refCov, sigma2Post, relative);
+            const size_t n = c.status.size();
+            return py::make_tuple(py::array_t<double>({n, (size_t)JAICOV_CALIB_COMPARE_COLUMNS}, c.table.data()),
+                                  py::array_t<int32_t>((py::ssize_t)n, c.status.data()),
+                                  py::array_t<double>((py::ssize_t)JAICOV_CALIB_SUMMARY_COLUMNS, c.summary));
+        }, py::arg("camA"), py::arg("camB"), py::arg("xy"), py::arg("depth") = std::vector<double>(), py::arg("refValues") = std::vector<double>(),
+             py::arg("refCov") = std::vector<double>(), py::arg("sigma2Post") = 0.0, py::arg("relative") = false,
+             "(table (n, 8), status (n,), summary (8,)) of the difference field of two calibrations (include/jaicov_calibration.h)")
+        .def("cameraValues", &BundleAdjustment::cameraValues, "x0, y0, c and the coefficients of a camera at the engine's current values")
         .def("useCentroidedCoordinates", &BundleAdjustment::useCentroidedCoordinates)
         .def("centroidCoordinates", &BundleAdjustment::centroidCoordinates)
         .def("applyAposterioriVarianceOfUnitWeight", &BundleAdjustment::applyAposterioriVarianceOfUnitWeight)

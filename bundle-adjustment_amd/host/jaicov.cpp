@@ -721,6 +721,56 @@ BundleAdjustment::VarianceComponents BundleAdjustment::varianceComponents(const 
     return r;
 }
 
+// include/jaicov_calibration.h on the engine of the last estimateModel
+BundleAdjustment::CalibrationField BundleAdjustment::calibrationField(double sigma2, const std::vector<int32_t> &cameras, const std::vector<double> &xy,
+                                                                      const std::vector<double> &depth, double k2, uint32_t columns,
+                                                                      bool withJacobian) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    const size_t n = cameras.size();
+    if (xy.size() != 2 * n || (!depth.empty() && depth.size() != n))
+        throw std::runtime_error("calibrationField: xy (2 per node) and depth (1 per node, or empty) must run parallel to cameras");
+    CalibrationField f;
+    f.table.resize(n * JAICOV_CALIB_FIELD_COLUMNS);
+    f.status.resize(n);
+    if (withJacobian) f.jacobian.resize(n * 2 * JAICOV_CALIB_MAX_COLUMNS);
+    const int rc = jaicov_calib_field(engine_, sigma2, k2, columns, cameras.data(), xy.data(), depth.empty() ? nullptr : depth.data(), (int32_t)n,
+                                      f.table.data(), withJacobian ? f.jacobian.data() : nullptr, f.status.data());
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_calib_field: ") + jaicov_neq_last_error(engine_));
+    return f;
+}
+
+BundleAdjustment::CalibrationCompare BundleAdjustment::compareCalibration(int camA, int camB, const std::vector<double> &xy,
+                                                                          const std::vector<double> &depth, const std::vector<double> &refValues,
+                                                                          const std::vector<double> &refCov, double sigma2Post, bool relative) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    const size_t n = xy.size() / 2, K = refValues.size();
+    const size_t nCam = flat.io_col.size() / 3;
+    if (xy.size() % 2 || (!depth.empty() && depth.size() != n)) throw std::runtime_error("compareCalibration: xy holds 2 per node, depth 1 per node or nothing");
+    if (K > 0 && camB >= 0 && (size_t)camB < nCam && K != 3 + (size_t)(flat.cam_dist_begin[camB + 1] - flat.cam_dist_begin[camB]))
+        throw std::runtime_error("compareCalibration: refValues holds x0, y0, c and the coefficients of camera camB");
+    if (!refCov.empty() && refCov.size() != K * K) throw std::runtime_error("compareCalibration: refCov is the K x K covariance of refValues");
+    CalibrationCompare c;
+    c.table.resize(n * JAICOV_CALIB_COMPARE_COLUMNS);
+    c.status.resize(n);
+    const int rc = jaicov_calib_compare(engine_, sigma2Post > 0.0 ? sigma2Post : sigma2apriori_, camA, camB, K ? refValues.data() : nullptr,
+                                        refCov.empty() ? nullptr : refCov.data(), relative ? JAICOV_CALIB_RELATIVE : 0, xy.data(),
+                                        depth.empty() ? nullptr : depth.data(), (int32_t)n, c.table.data(), c.status.data(), c.summary);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_calib_compare: ") + jaicov_neq_last_error(engine_));
+    return c;
+}
+
+std::vector<double> BundleAdjustment::cameraValues(int cam) const {
+    const size_t nCam = flat.io_col.size() / 3, nPoints = flat.point_col.size() / 3;
+    if (!engine_ || cam < 0 || (size_t)cam >= nCam) throw std::runtime_error("cameraValues: no engine, or a camera out of range");
+    std::vector<double> all(jaicov_neq_num_slots(engine_));
+    const int rc = jaicov_neq_get_parameters(engine_, all.data(), all.size());
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_neq_get_parameters: ") + jaicov_neq_last_error(engine_));
+    const size_t io = 3 * nPoints + 3 * (size_t)cam, dist = 3 * nPoints + 3 * nCam;
+    std::vector<double> v(all.begin() + io, all.begin() + io + 3);
+    v.insert(v.end(), all.begin() + dist + flat.cam_dist_begin[cam], all.begin() + dist + flat.cam_dist_begin[cam + 1]);
+    return v;
+}
+
 BundleAdjustment::VarianceGroups BundleAdjustment::varianceGroupsByKind() const {
     VarianceGroups g;
     g.ip.assign(flat.ip_image.size(), 0);

@@ -43,6 +43,7 @@
 #include "../../include/jaicov_predict.h"
 #include "../../include/jaicov_newpoints.h"
 #include "../../include/jaicov_vce.h"
+#include "../../include/jaicov_calibration.h"
 
 namespace jaicov::host {
 
@@ -650,6 +651,32 @@ public:
     // the groups "by kind" (image points, scale bars, directly observed rows) and "by image" of the flattened problem
     VarianceGroups varianceGroupsByKind() const;
     VarianceGroups varianceGroupsByImage() const;
+    // The camera in image space (include/jaicov_calibration.h), read on the device from the cofactor matrix of the last
+    // estimateModel; MatrixInversion.REDUCED serves as well as FULL.  A node is (xs, ys): ideal coordinates relative to the principal
+    // point at the camera's current c (two per node in xy); cameras in the order of flat.io_col.  depth empty: N = -c.
+    // calibrationField: the image correction at every node with J Q J' over the camera's selected columns, sigmas, the ellipse and
+    // the radial and tangential components (rows of JAICOV_CALIB_FIELD_COLUMNS); withJacobian: the camera part of every row as well.
+    struct CalibrationField {
+        std::vector<double> table;               // rows of JAICOV_CALIB_FIELD_COLUMNS
+        std::vector<double> jacobian;            // 2 x JAICOV_CALIB_MAX_COLUMNS per node, or empty
+        std::vector<int32_t> status;             // JAICOV_CALIB_* bits of every node
+    };
+    CalibrationField calibrationField(double sigma2, const std::vector<int32_t> &cameras, const std::vector<double> &xy,
+                                      const std::vector<double> &depth = {}, double k2 = 1.0, uint32_t columns = JAICOV_CALIB_ALL,
+                                      bool withJacobian = false) const;
+    // compareCalibration: the difference field of camera camA and either camera camB of the same adjustment (refValues empty) or the
+    // values refValues (x0, y0, c, then the coefficients of camB's table) with the covariance refCov (empty: none); sigma2Post <= 0:
+    // the a-priori factor.  The summary is formed on the device.
+    struct CalibrationCompare {
+        std::vector<double> table;               // rows of JAICOV_CALIB_COMPARE_COLUMNS: d, C_d, q, T_prio, T_post
+        std::vector<int32_t> status;
+        double summary[JAICOV_CALIB_SUMMARY_COLUMNS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    };
+    CalibrationCompare compareCalibration(int camA, int camB, const std::vector<double> &xy, const std::vector<double> &depth = {},
+                                          const std::vector<double> &refValues = {}, const std::vector<double> &refCov = {},
+                                          double sigma2Post = 0.0, bool relative = false) const;
+    // x0, y0, c and the coefficients of camera `cam` at the engine's current values: a reference set for compareCalibration
+    std::vector<double> cameraValues(int cam) const;
     const std::string &lastError() const { return lastError_; }
     jaicov_engine *nativeEngine() const { return engine_; }     // the engine of the last estimateModel (null before)
 
