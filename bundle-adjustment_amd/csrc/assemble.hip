@@ -7,6 +7,7 @@
 
 #include "ba_kernels.h"
 #include "gemm_f64.h"
+#include "launchers.h"
 
 namespace jaicov {
 
@@ -1076,12 +1077,6 @@ hipError_t launch_assemble_small(hipStream_t s, const DevProblem &p, const int32
                        N, n);
     return hipGetLastError();
 }
-
-hipError_t launch_schur_eliminate(hipStream_t, const DevProblem &, const int32_t *, int, int, const int32_t *, int,
-                                  const double *, const double *, double *, double, double, double *, double *, double *,
-                                  double *, int *, double *, double *, const PPGather *, double *);
-
-hipError_t launch_schur_tfix(hipStream_t, const DevProblem &, const int32_t *, int, const double *, const double *, double, double *);
 
 // JAICOV_ASSEMBLY_FORM = t_vector | no_fork | materialise: the alternative forms of the dense-block assembly kept as second paths
 // for parity (the vector form of T = Dinv [A_c | w]; the camera-side kernels in front of the gather instead of beside it; P' written

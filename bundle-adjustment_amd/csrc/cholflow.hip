@@ -27,7 +27,7 @@
 // dispatch order (tests/test_flow_schedule.py replays every form's list against a model of the companion).  The companion
 // runs on its own CU-masked stream and the host launches the tile kernel only once it is resident.
 // Every wait is bounded (wall clock): a stall sets the abort word, every waiter leaves, the host repeats the factorisation
-// or reports an error (engine.hip, solve).
+// or reports an error (engine_solve.hip).
 //
 // Visibility (MI355X_MICROARCH.md, inter-workgroup visibility; the per-XCD L2s are not coherent, a CU's L1 is never
 // refreshed by other CUs' stores).  Producer: every byte that another workgroup will read is stored write-through
@@ -87,7 +87,7 @@ struct FlowArgs {
     int *alive;              // host-visible words: workgroup b of the diagonal / chain kernel stores `seq` into alive[b] when it starts (FlowFactor::factor's handshake)
     int seq;
     // optional: the matrix is not in L yet but is M = V N V + Bh' Bh (identity on the d border rows and on the padding) of a
-    // source square N (NES.applyPrecondition, NES:82-91, fused into the first load of every tile; engine.hip scale_copy_kernel)
+    // source square N (NES.applyPrecondition, NES:82-91, fused into the first load of every tile; engine_solve.hip scale_copy_kernel)
     const double *src;       // N, row-major lower, leading dimension src_ld; null = the tiles are in L
     long src_ld;
     const double *V;         // [>= 128 nb]

@@ -1,6 +1,6 @@
 // Engine creation, first stage: everything jaicov_neq_create decides and tabulates on the host, before anything exists on
 // the device.  The plan is a pure function of (description, options, assembly form): no device call, no launch, no
-// knowledge of the engine.  engine.hip uploads what the plan holds (create_impl); jaicov_debug_create_plan exposes the
+// knowledge of the engine.  engine_create.hip uploads what the plan holds (engine_create_impl); jaicov_debug_create_plan exposes the
 // decisions and tests/test_create_plan.py holds the tables to their invariants on any machine.
 #pragma once
 #include <stdint.h>
@@ -422,6 +422,14 @@ inline bool build_create_plan(CreatePlan &pl, const jaicov_problem_desc &desc, c
     if (!gather_tables(pl)) return false;
     decide_elimination(pl, o);
     return true;
+}
+
+// the options of a caller that passes none
+inline jaicov_engine_options default_options() {
+    jaicov_engine_options o{};
+    o.image_begin = o.image_end = -1;
+    o.apply_shared = 1;
+    return o;
 }
 
 }  // namespace jaicov

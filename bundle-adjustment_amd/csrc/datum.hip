@@ -19,6 +19,7 @@
 #include "../../include/jaicov_datum.h"
 #include "datum.h"
 #include "qview.h"
+#include "small_inverse.h"
 #include "status.h"
 #include "symtile.h"
 
@@ -91,38 +92,6 @@ static hipError_t launch_update_d(int D, hipStream_t st, double *Q, long ld, int
     case 6: return launch_update<6>(st, Q, ld, n, D, ZY);
     default: return launch_update<7>(st, Q, ld, n, D, ZY);
     }
-}
-
-// inverse of a d x d matrix (d <= 7) by Gauss-Jordan with partial pivoting; false when a pivot falls to 1e-12 of the largest
-// entry (the datum rows do not fix the frame: collinear or coincident datum points)
-static bool datum_small_inverse(int d, const double *M, double *Minv) {
-    double a[7][14], mx = 0.0;
-    for (int i = 0; i < d; i++)
-        for (int j = 0; j < d; j++) {
-            a[i][j] = M[i * d + j];
-            a[i][d + j] = i == j ? 1.0 : 0.0;
-            mx = std::max(mx, fabs(M[i * d + j]));
-        }
-    if (!(mx > 0.0) || !std::isfinite(mx)) return false;
-    for (int c = 0; c < d; c++) {
-        int piv = c;
-        for (int r = c + 1; r < d; r++)
-            if (fabs(a[r][c]) > fabs(a[piv][c])) piv = r;
-        if (!(fabs(a[piv][c]) > 1e-12 * mx)) return false;
-        if (piv != c)
-            for (int j = 0; j < 2 * d; j++) std::swap(a[c][j], a[piv][j]);
-        const double inv = 1.0 / a[c][c];
-        for (int j = 0; j < 2 * d; j++) a[c][j] *= inv;
-        for (int r = 0; r < d; r++) {
-            if (r == c) continue;
-            const double f = a[r][c];
-            if (f != 0.0)
-                for (int j = 0; j < 2 * d; j++) a[r][j] -= f * a[c][j];
-        }
-    }
-    for (int i = 0; i < d; i++)
-        for (int j = 0; j < d; j++) Minv[i * d + j] = a[i][d + j];
-    return true;
 }
 
 }  // namespace jaicov

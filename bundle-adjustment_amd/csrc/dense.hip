@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "gemm_f64.h"
+#include "launchers.h"
 #include "potrf_diag.h"
 #include "status.h"
 

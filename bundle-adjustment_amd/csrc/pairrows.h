@@ -10,10 +10,9 @@
 #include <vector>
 
 #include "ba_kernels.h"
+#include "launchers.h"
 
 namespace jaicov {
-
-hipError_t launch_rows(hipStream_t, const DevProblem &, const double *, int, int, double *, double *);      // rows.hip
 
 struct PairRows {
     const size_t n, o_w, o_x, o_disp, size;      // pairs, offsets of w, x and disp, doubles in all

@@ -1,4 +1,4 @@
-// The one interface between engine.hip (owner of jaicov_engine) and whatever reads the cofactor matrix an inverting solve leaves on
+// The one interface between the engine (engine.hip; jaicov_engine itself is engine_state.h, not for readers) and whatever reads the cofactor matrix an inverting solve leaves on
 // the device: transform.hip, reliability.hip, datum.hip (the one writer), precision.hip, parameters.hip, forms.hip, predict.hip,
 // newpoints.hip, vce.hip and calibration.hip.  Here are the view of the engine (QView), the shell of a call and the device's reads of the matrix.  A consumer adds
 // a state struct of its own and a slot for it in QSlots; a call of it is, in the order of refusals that the headers under include/

@@ -16,14 +16,11 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "launchers.h"      // RefineBorder: the datum border of the system, by value into the residual kernel
+
 namespace jaicov {
 
 typedef double d4r_t __attribute__((ext_vector_type(4)));
-
-struct RefineBorder {       // datum border of the system, d <= 7 (by value: 7 * 2 doubles)
-    double kappa[7];        // unscaled multipliers (dx[0..d))
-    double rk[7];           // scaled border residual  r_k = -R (B dx)
-};
 
 // (hi, lo) += a * x, error-free product, TwoSum; lo collects the rounding errors
 __device__ __forceinline__ void dd_fma(double a, double x, double &hi, double &lo) {

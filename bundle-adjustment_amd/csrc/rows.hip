@@ -2,6 +2,7 @@
 // Restates CollinearityEquationFactory (PDF:94-190), the base fill of getPartialDerivativeImageCoordinate
 // (PDF:321-414) and the distortion factories (ASF:37-81, TDF:39-134, RSF:39-90, RDF:39-161 via DMF:33-101).
 #include "ba_kernels.h"
+#include "launchers.h"
 
 namespace jaicov {
 

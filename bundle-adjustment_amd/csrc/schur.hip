@@ -12,6 +12,7 @@
 // recovers the EO step afterwards.  Levenberg-Marquardt damping enters through E_kk (1 + lambda) (BA:814-822).
 #include "ba_kernels.h"
 #include "gemm_f64.h"
+#include "launchers.h"
 
 namespace jaicov {
 

@@ -25,3 +25,14 @@
         hipError_t _e = (x);                       \
         if (_e != hipSuccess) return _e;           \
     } while (0)
+
+// what every entry point that may be the process's first asks before it touches the device
+inline int check_device(std::string &err) {
+    int count = 0;
+    hipError_t r = hipGetDeviceCount(&count);
+    if (r != hipSuccess || count <= 0) {
+        err = "no HIP device available (this engine has no CPU fallback)";
+        return JAICOV_ERR_NO_DEVICE;
+    }
+    return JAICOV_OK;
+}

@@ -1435,7 +1435,7 @@ def dense_gemm(alay, blay, A, B, C_in, M, N, K, alpha=1.0, beta=0.0, lower_only=
 
 
 class DebugGemmArgs(C.Structure):
-    """jaicov_debug_gemm_args (csrc/engine.hip)"""
+    """jaicov_debug_gemm_args (csrc/debug.hip)"""
     _fields_ = [("struct_size", C.c_uint32), ("alay", C.c_int32), ("blay", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
                 ("alpha", C.c_double), ("beta", C.c_double), ("A", C.c_void_p), ("n_A", C.c_int64), ("B", C.c_void_p), ("n_B", C.c_int64),
                 ("C", C.c_void_p), ("n_C", C.c_int64), ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64),

@@ -63,5 +63,6 @@ def test_engine_frees_none_of_its_members_by_hand():
     """The engine's growable device buffers have one owner each (DevBuf in csrc/engine.hip) that frees them in its destructor;
     jaicov_neq_destroy frees the create-time allocations in its loop.  A hand-written free of a member is how the
     Newton-Schulz workspace came to be freed under a live pointer."""
-    txt = open(os.path.join(ROOT, "bundle-adjustment_amd", "csrc", "engine.hip")).read()
-    assert "hipFree(e->" not in txt
+    for unit in ("engine.hip", "engine_create.hip", "engine_solve.hip", "engine_state.h"):
+        txt = open(os.path.join(ROOT, "bundle-adjustment_amd", "csrc", unit)).read()
+        assert "hipFree(e->" not in txt, unit

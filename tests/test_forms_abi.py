@@ -79,7 +79,8 @@ def test_the_cpp_host_mirrors_the_call():
     mk = open(os.path.join(HOST, "Makefile")).read()
     assert '#include "../../include/jaicov_forms.h"' in hpp
     assert re.search(r"\bfitForms\s*\(", hpp) and re.search(r"BundleAdjustment::fitForms\s*\(", cpp) and re.search(r"\bjaicov_form_fit\s*\(engine_", cpp)
-    assert '.def("fitForms"' in bind and re.search(r"^example_forms:", mk, flags=re.M)
+    # one pattern rule builds every program named in EXAMPLES
+    assert '.def("fitForms"' in bind and re.search(r"^EXAMPLES\s*:=.*\bexample_forms\b", mk, flags=re.M) and re.search(r"^example_%:", mk, flags=re.M)
     from bundle_adjustment_amd import host_api
     assert hasattr(host_api.BundleAdjustment, "fitForms")
 

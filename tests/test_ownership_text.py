@@ -100,4 +100,34 @@ def test_the_cofactor_matrix_has_one_view_and_the_shard_rule_one_place():
         for gone in VIEWS_GONE:
             assert not re.search(r"\b%s\b" % gone, text), (name, gone)
     assert [n for n, t in src.items() if re.search(r"\bstruct\s+QView\s*\{", t)] == ["qview.h"]
-    assert src["engine.hip"].count("ip_count != e->p.n_ip") == 1
+    assert sum(t.count("ip_count != e->p.n_ip") for t in src.values()) == 1
+
+
+ENGINE_UNITS = ["engine.hip", "engine_create.hip", "engine_solve.hip"]
+LAUNCHERS = ["launch_rows", "launch_assemble_small", "launch_assemble_blocks", "launch_schur_eliminate", "launch_schur_tfix",
+             "launch_schur_backsub", "launch_schur_expand_f", "launch_shared_groups", "launch_omega", "launch_residual_dd"]
+LAUNCHER_DECL = r"hipError_t\s+(launch_\w+)\s*\([^{;]*\)\s*;"
+
+
+def test_the_engine_struct_is_private_to_the_engine_units():
+    src = sources()
+    assert [n for n, t in src.items() if "struct jaicov_engine {" in t] == ["engine_state.h"]
+    assert sorted(n for n, t in src.items() if re.search(r'#\s*include\s*"engine_state\.h"', t)) == ENGINE_UNITS
+
+
+def test_launchers_and_the_structs_they_pass_are_declared_once():
+    src = sources()
+    assert [n for n, t in src.items() if re.search(r"\bstruct\s+RefineBorder\s*\{", code(t))] == ["launchers.h"]
+    for name, text in src.items():                     # no hand copy of a prototype where it is called (chains.h has members of that name)
+        if name.endswith(".hip") or name == "pairrows.h":
+            hits = re.findall(LAUNCHER_DECL, code(text))
+            assert not hits, (name, hits)
+    declared = re.findall(LAUNCHER_DECL, code(src["launchers.h"]))
+    for fn in LAUNCHERS:
+        assert declared.count(fn) == 1, (fn, declared)
+
+
+def test_the_dead_glue_kernels_stay_gone():
+    for name, text in sources().items():
+        for gone in ("store_inv_kernel", "load_disp_kernel"):
+            assert gone not in text, (name, gone)
