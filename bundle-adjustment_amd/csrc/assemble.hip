@@ -8,29 +8,9 @@
 #include "ba_kernels.h"
 #include "gemm_f64.h"
 #include "launchers.h"
+#include "obsmodel.h"
 
 namespace jaicov {
-
-// shared local column c (0..kc) -> local row id l in the rows buffer, and its global column
-//   c: 0..2 = x0,y0,c ; 3..8 = X0,Y0,Z0,omega,phi,kappa ; 9.. = distortion coefficients
-__device__ __forceinline__ int shared_local(int c) { return c < 3 ? 3 + c : (c < 9 ? 6 + (c - 3) : 12 + (c - 9)); }
-__device__ __forceinline__ int shared_col(const DevProblem &p, int img, int cam, int jb, int c) {
-    return c < 3 ? p.io_col[3 * cam + c] : (c < 9 ? p.eo_col[6 * img + (c - 3)] : p.dist_col[jb + (c - 9)]);
-}
-
-// 2x2 weight of an ordinary image point (PDF:296-319): returns p00, p01, p11
-__device__ __forceinline__ void weight2x2(const DevProblem &p, int ip, double sigma2, double &p00, double &p01,
-                                          double &p11) {
-    const double vx = p.ip_var_x[ip], vy = p.ip_var_y[ip], rho = p.ip_rho[ip];
-    if (rho == 0) {
-        p00 = sigma2 / vx; p11 = sigma2 / vy; p01 = 0.0;
-    } else {
-        const double invDet = sigma2 / ((1.0 - rho * rho) * vx * vy);
-        p00 = invDet * vy;
-        p11 = invDet * vx;
-        p01 = -invDet * rho * sqrt(vx * vy);
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // ordinary (2x2 / diagonal) image points: one workgroup per segment of <= 256 points of one image
@@ -49,17 +29,17 @@ __global__ __launch_bounds__(256) void assemble_small_kernel(DevProblem p, const
     const int img = p.ip_image[b], cam = p.image_camera[img];
     const int jb = p.cam_dist_begin[cam], nd = p.cam_dist_begin[cam + 1] - jb;
     const int kc = 9 + nd;
-    if (tid < kc) cols[tid] = shared_col(p, img, cam, jb, tid);
+    if (tid < kc) cols[tid] = obs_shared_col(p, img, cam, jb, tid);
     // stage the shared sub-rows
     for (int idx = tid; idx < 2 * cnt * (kc + 1); idx += 256) {
         const int c = idx / (2 * cnt), k = idx - c * (2 * cnt);      // k = 2*o + r ... coalesce over o below
         const int r = k / cnt, o = k - r * cnt;
-        const double v = (c < kc) ? rowsA[(long)(2 * shared_local(c) + r) * S + b + o] : rowsW[(long)r * S + b + o];
+        const double v = (c < kc) ? rowsA[(long)(2 * obs_shared_row(c) + r) * S + b + o] : rowsW[(long)r * S + b + o];
         As[(2 * o + r) * KC_LD + c] = v;
     }
     if (tid < cnt) {
         double p00, p01, p11;
-        weight2x2(p, b + tid, sigma2, p00, p01, p11);
+        obs_weight(p, b + tid, sigma2, p00, p01, p11);
         Ps[3 * tid] = p00; Ps[3 * tid + 1] = p01; Ps[3 * tid + 2] = p11;
     }
     __syncthreads();
@@ -139,7 +119,7 @@ __global__ __launch_bounds__(T_NT) void blk_T_kernel(DevProblem p, const int32_t
     if ((int)blockIdx.x * (T_NT * T_TR) >= m || p.blk_w_offset[g] < 0) return;      // (block-diagonal weights: blk_T_diag_kernel)
     const long S = p.n_ip;
     const int img = p.ip_image[ipb], cam = p.image_camera[img];
-    const int kc = 9 + p.cam_dist_begin[cam + 1] - p.cam_dist_begin[cam];
+    const int kc = obs_kc(p, cam);
     const double *P = p.blk_w + p.blk_w_offset[g];
     double acc[T_TR][KC_LD];
     int rr_[T_TR];
@@ -159,7 +139,7 @@ __global__ __launch_bounds__(T_NT) void blk_T_kernel(DevProblem p, const int32_t
             const int c = idx / kn, kk = idx - c * kn;
             const int k = k0 + kk, o = k >> 1, rr = k & 1;
             double v = 0.0;
-            if (c < kc) v = rowsA[(long)(2 * shared_local(c) + rr) * S + ipb + o];
+            if (c < kc) v = rowsA[(long)(2 * obs_shared_row(c) + rr) * S + ipb + o];
             else if (c == kc) v = rowsW[(long)rr * S + ipb + o];
             Ac[kk * KC_LD + c] = v;
         }
@@ -223,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void blk_T_mfma_kernel(DevProblem p, const 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
     const long S = p.n_ip;
     const int img = p.ip_image[ipb], cam = p.image_camera[img];
-    const int kc = 9 + p.cam_dist_begin[cam + 1] - p.cam_dist_begin[cam];
+    const int kc = obs_kc(p, cam);
     const double *P = p.blk_w + p.blk_w_offset[g];
     const int i0 = blockIdx.x * 256 + 64 * wave;
     d4_t acc[4][2];
@@ -253,7 +233,7 @@ __global__ __launch_bounds__(256, 2) void blk_T_mfma_kernel(DevProblem p, const 
             const int k = kb + kk, o = k >> 1, rr = k & 1;
             double v = 0.0;
             if (k < m) {
-                if (c < kc) v = rowsA[(long)(2 * shared_local(c) + rr) * S + ipb + o];
+                if (c < kc) v = rowsA[(long)(2 * obs_shared_row(c) + rr) * S + ipb + o];
                 else if (c == kc) v = rowsW[(long)rr * S + ipb + o];
             }
             sv[j] = v;
@@ -313,9 +293,9 @@ __global__ __launch_bounds__(256) void blk_T_diag_kernel(DevProblem p, const int
     if (o >= mp || c >= KC_LD) return;
     const long S = p.n_ip;
     const int img = p.ip_image[ipb], cam = p.image_camera[img];
-    const int kc = 9 + p.cam_dist_begin[cam + 1] - p.cam_dist_begin[cam];
+    const int kc = obs_kc(p, cam);
     double x0 = 0.0, x1 = 0.0;
-    if (c < kc) { x0 = rowsA[(long)(2 * shared_local(c)) * S + ipb + o]; x1 = rowsA[(long)(2 * shared_local(c) + 1) * S + ipb + o]; }
+    if (c < kc) { x0 = rowsA[(long)(2 * obs_shared_row(c)) * S + ipb + o]; x1 = rowsA[(long)(2 * obs_shared_row(c) + 1) * S + ipb + o]; }
     else if (c == kc) { x0 = rowsW[ipb + o]; x1 = rowsW[S + ipb + o]; }
     const double *w = p.ip_w3 + 3 * (long)(ipb + o);
     double *out = T + ((long)2 * (ipb + o)) * KC_LD + c;
@@ -336,7 +316,7 @@ __global__ __launch_bounds__(256) void blk_cc_kernel(DevProblem p, const int32_t
     const int ipb = p.blk_ip_begin[g], m = 2 * (p.blk_ip_begin[g + 1] - ipb);
     const long S = p.n_ip;
     const int img = p.ip_image[ipb], cam = p.image_camera[img];
-    const int kc = 9 + p.cam_dist_begin[cam + 1] - p.cam_dist_begin[cam];
+    const int kc = obs_kc(p, cam);
     const int nent = kc * (kc + 1);   // a in [0,kc), b in [0,kc] (b == kc -> n)
     double *out = partial + ((long)blockIdx.x * gridDim.y + blockIdx.y) * CC_ENT;
     for (int ent = threadIdx.x; ent < nent; ent += 256) {
@@ -345,7 +325,7 @@ __global__ __launch_bounds__(256) void blk_cc_kernel(DevProblem p, const int32_t
         const bool skip = (bb < kc && bb > a) || (schur && ((a >= 3 && a < 9) || (bb >= 3 && bb < 9)));
         double s = 0.0;
         if (!skip) {
-            const double *ra = rowsA + (long)(2 * shared_local(a)) * S + ipb;
+            const double *ra = rowsA + (long)(2 * obs_shared_row(a)) * S + ipb;
             const double *tb = T + (long)2 * ipb * KC_LD + bb;
             const int o0 = (int)((long)(m / 2) * blockIdx.y / gridDim.y), o1 = (int)((long)(m / 2) * (blockIdx.y + 1) / gridDim.y);
             for (int o = o0; o < o1; o++)
@@ -378,7 +358,7 @@ __global__ __launch_bounds__(256) void blk_cc_reduce_kernel(DevProblem p, const 
         double s = 0.0;
         for (int q = 0; q < parts; q++) s += partial[((long)t * parts + q) * CC_ENT + ent];
         if (eo) {
-            const int ga = shared_col(p, img, cam, jb, a), gb = bb < kc ? shared_col(p, img, cam, jb, bb) : 0;
+            const int ga = obs_shared_col(p, img, cam, jb, a), gb = bb < kc ? obs_shared_col(p, img, cam, jb, bb) : 0;
             if (ga >= 0 && gb >= 0) {
                 if (bb == kc) n[ga] += s;
                 else N[(long)max(ga, gb) * p.ld + min(ga, gb)] += s;
@@ -394,7 +374,7 @@ __global__ __launch_bounds__(256) void blk_cc_reduce_kernel(DevProblem p, const 
         __syncthreads();
     }
     if (tid == 0) {
-        const int ga = shared_col(p, 0, cam, jb, a), gb = bb < kc ? shared_col(p, 0, cam, jb, bb) : 0;   // no EO column: the image is irrelevant
+        const int ga = obs_shared_col(p, 0, cam, jb, a), gb = bb < kc ? obs_shared_col(p, 0, cam, jb, bb) : 0;   // no EO column: the image is irrelevant
         if (ga >= 0 && gb >= 0) {
             if (bb == kc) n[ga] += red[0];
             else N[(long)max(ga, gb) * p.ld + min(ga, gb)] += red[0];
@@ -417,7 +397,7 @@ __global__ __launch_bounds__(256) void blk_pc_kernel(DevProblem p, const int32_t
     const int img = p.ip_image[ip], cam = p.image_camera[img], pt = p.ip_point[ip];
     const int jb = p.cam_dist_begin[cam], kc = 9 + p.cam_dist_begin[cam + 1] - jb;
     if (c > kc) return;
-    const int gc = c < kc ? shared_col(p, img, cam, jb, c) : 0;
+    const int gc = c < kc ? obs_shared_col(p, img, cam, jb, c) : 0;
     if (gc < 0) return;
     const double t0 = T[((long)2 * ip) * KC_LD + c], t1 = T[((long)2 * ip + 1) * KC_LD + c];
 #pragma unroll
@@ -467,7 +447,7 @@ __global__ __launch_bounds__(256) void blk_pc_gather_kernel(DevProblem p, PPGath
         int tgt;
         if (c > kc) tgt = -1;
         else if (c == kc) tgt = -3;
-        else { tgt = shared_col(p, img, cam, jb, c); if (tgt < 0) tgt = -1; }
+        else { tgt = obs_shared_col(p, img, cam, jb, c); if (tgt < 0) tgt = -1; }
         if (tgt != cur) { flush(); cur = tgt; }
         if (tgt == -1) continue;
         const double t0 = T[((long)2 * ip) * KC_LD + c], t1 = T[((long)2 * ip + 1) * KC_LD + c];
@@ -905,15 +885,11 @@ __global__ void scalebar_kernel(DevProblem p, const double *__restrict__ vals, d
                                 const double *dx, double *omega) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= p.n_sb) return;
-    const int pa = p.sb_a[s], pb = p.sb_b[s];
-    const double *a = vals + 3 * pa, *b = vals + 3 * pb;
-    const double dX = b[0] - a[0], dY = b[1] - a[1], dZ = b[2] - a[2];
-    const double len = sqrt(dX * dX + dY * dY + dZ * dZ);
-    const double ev[6] = {-dX / len, -dY / len, -dZ / len, dX / len, dY / len, dZ / len};
+    int col[6];
+    double ev[6], len;
+    obs_scalebar_row(p, vals, s, col, ev, len);
     const double P = sigma2 / p.sb_var[s];
     const double w = p.sb_len[s] - len;
-    int col[6];
-    for (int t = 0; t < 6; t++) col[t] = t < 3 ? p.point_col[3 * pa + t] : p.point_col[3 * pb + t - 3];
     if (dx) {   // omega mode (BA:480-488)
         double v = w;
         for (int t = 0; t < 6; t++)
@@ -946,12 +922,8 @@ __global__ __launch_bounds__(256) void direct_kernel(DevProblem p, const double 
     __shared__ double red[256];
     __shared__ double s_v[DIRECT_STAGE];
     __shared__ int s_col[DIRECT_STAGE];
-    auto row_col = [&](int c) { return p.slot_col[p.dg_slot[b + c]]; };
-    auto row_v = [&](int c, int cc) {
-        double vc = p.dg_obs[b + c] - vals[p.dg_slot[b + c]];
-        if (dx && cc >= 0) vc -= dx[cc];
-        return vc;
-    };
+    auto row_col = [&](int c) { return obs_direct_col(p, b + c); };
+    auto row_v = [&](int c, int cc) { return obs_direct_w(p, vals, dx, b + c, cc); };
     for (int c = threadIdx.x; c < m && c < DIRECT_STAGE; c += 256) {
         const int cc = row_col(c);
         s_col[c] = cc;
@@ -985,13 +957,8 @@ __global__ __launch_bounds__(256) void direct_kernel(DevProblem p, const double 
         }
     }
     if (dx) {
-        red[threadIdx.x] = om;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) unsafeAtomicAdd(omega, red[0]);
+        const double sum = block_sum_256(red, om);
+        if (threadIdx.x == 0) unsafeAtomicAdd(omega, sum);
     }
 }
 
@@ -1013,8 +980,7 @@ __global__ __launch_bounds__(256) void omega_points_kernel(DevProblem p, const u
         const int jb = p.cam_dist_begin[cam], nd = p.cam_dist_begin[cam + 1] - jb;
         double v0 = rowsW[ip], v1 = rowsW[S + ip];
         for (int l = 0; l < 12 + nd; l++) {
-            const int col = l < 3 ? p.point_col[3 * pt + l]
-                                  : (l < 6 ? p.io_col[3 * cam + l - 3] : (l < 12 ? p.eo_col[6 * img + l - 6] : p.dist_col[jb + l - 12]));
+            const int col = obs_row_col(p, pt, img, cam, jb, l);
             if (col < 0) continue;
             const double d = dx[col];
             v0 -= rowsA[(long)(2 * l) * S + ip] * d;
@@ -1025,17 +991,12 @@ __global__ __launch_bounds__(256) void omega_points_kernel(DevProblem p, const u
             vbuf[2 * (long)ip + 1] = v1;
         } else {
             double p00, p01, p11;
-            weight2x2(p, ip, sigma2, p00, p01, p11);
+            obs_weight(p, ip, sigma2, p00, p01, p11);
             om = v0 * (p00 * v0 + p01 * v1) + v1 * (p01 * v0 + p11 * v1);
         }
     }
-    red[threadIdx.x] = om;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && red[0] != 0.0) unsafeAtomicAdd(omega, red[0]);
+    const double sum = block_sum_256(red, om);
+    if (threadIdx.x == 0 && sum != 0.0) unsafeAtomicAdd(omega, sum);
 }
 
 // omega of an image block: sigma2 * v' Dinv v ; grid (ceil(m/256), n_list)
@@ -1057,13 +1018,8 @@ __global__ __launch_bounds__(256) void omega_block_kernel(DevProblem p, const in
         const double pr0 = (r & 1) ? w[1] : w[0], pr1 = (r & 1) ? w[2] : w[1];
         s = (pr0 * v[r & ~1] + pr1 * v[r | 1]) * v[r] * sigma2;
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int t = 128; t > 0; t >>= 1) {
-        if (threadIdx.x < t) red[threadIdx.x] += red[threadIdx.x + t];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) unsafeAtomicAdd(omega, red[0]);
+    const double sum = block_sum_256(red, s);
+    if (threadIdx.x == 0) unsafeAtomicAdd(omega, sum);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

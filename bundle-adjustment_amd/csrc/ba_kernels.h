@@ -12,8 +12,8 @@
 namespace jaicov {
 
 constexpr int MAXD = JAICOV_MAX_DIST_PER_CAMERA;   // 20
-constexpr int KROW = 12 + MAXD;                    // local row layout: X,Y,Z,x0,y0,c,X0,Y0,Z0,omega,phi,kappa,dist..
-constexpr int KC_MAX = 9 + MAXD;                   // shared (camera + EO) local columns: io(3), eo(6), dist
+constexpr int KROW = 12 + MAXD;                    // local rows of the compact rows      (both layouts: obsmodel.h)
+constexpr int KC_MAX = 9 + MAXD;                   // shared (camera + EO) local columns
 constexpr int KC_LD = KC_MAX + 1;                  // + the misclosure column in T = P [A_c | w]
 constexpr int SEG = 256;                           // image points per assembly segment
 constexpr int SCHUR_GLD = 24;                      // row length of G = U' [A_io, A_dist | w] (schur.hip)

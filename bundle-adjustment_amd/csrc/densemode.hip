@@ -14,14 +14,10 @@
 #include "ba_kernels.h"
 #include "gemm_f32.h"
 #include "gemm_f64.h"
+#include "obsmodel.h"
 #include "status.h"
 
 namespace jaicov {
-
-__device__ __forceinline__ int dm_shared_local(int c) { return c < 3 ? 3 + c : (c < 9 ? 6 + (c - 3) : 12 + (c - 9)); }
-__device__ __forceinline__ int dm_shared_col(const DevProblem &p, int img, int cam, int jb, int c) {
-    return c < 3 ? p.io_col[3 * cam + c] : (c < 9 ? p.eo_col[6 * img + (c - 3)] : p.dist_col[jb + (c - 9)]);
-}
 
 // P_g (m x m) -> Ppad (mpad x mpad, zero padded).  grid (mpad/256, mpad, batch).  T = double, or float for the
 // fp32-accumulate variant of BASELINE config 5 (assembly_mode = 2): operands rounded to fp32, fp32 MFMA accumulation.
@@ -51,7 +47,7 @@ __global__ __launch_bounds__(256) void dm_pack_rows_kernel(DevProblem p, const i
     const int ipb = p.blk_ip_begin[g], mp = p.blk_ip_begin[g + 1] - ipb, m = 2 * mp;
     const long S = p.n_ip;
     const int img = p.ip_image[ipb], cam = p.image_camera[img];
-    const int jb = p.cam_dist_begin[cam], kc = 9 + p.cam_dist_begin[cam + 1] - jb;
+    const int jb = p.cam_dist_begin[cam], kc = obs_kc(p, cam);
     const int k = 3 * mp + kc;
     const int row = blockIdx.x * 256 + threadIdx.x;
     int32_t *cm = cmap + (long)b * kpad;
@@ -59,7 +55,7 @@ __global__ __launch_bounds__(256) void dm_pack_rows_kernel(DevProblem p, const i
         for (int c = threadIdx.x; c < kpad; c += 256) {
             int col = -1;
             if (c < 3 * mp) col = p.point_col[3 * p.ip_point[ipb + c / 3] + c % 3];
-            else if (c < k) col = dm_shared_col(p, img, cam, jb, c - 3 * mp);
+            else if (c < k) col = obs_shared_col(p, img, cam, jb, c - 3 * mp);
             else if (c == k) col = -2;
             cm[c] = col;
         }
@@ -69,7 +65,7 @@ __global__ __launch_bounds__(256) void dm_pack_rows_kernel(DevProblem p, const i
     T *out = Apad + (long)b * mpad * kpad + (long)row * kpad;
 #pragma unroll
     for (int a = 0; a < 3; a++) out[3 * q + a] = (T)rowsA[(long)(2 * a + r) * S + ipb + q];
-    for (int c = 0; c < kc; c++) out[3 * mp + c] = (T)rowsA[(long)(2 * dm_shared_local(c) + r) * S + ipb + q];
+    for (int c = 0; c < kc; c++) out[3 * mp + c] = (T)rowsA[(long)(2 * obs_shared_row(c) + r) * S + ipb + q];
     out[k] = (T)rowsW[(long)r * S + ipb + q];
 }
 

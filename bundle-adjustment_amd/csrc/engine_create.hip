@@ -7,6 +7,7 @@
 #include "batchinv.h"
 #include "create_plan.h"
 #include "engine_state.h"
+#include "obsmodel.h"
 
 // ---- dense dispersions -> weights, all groups of one padded order together (batchinv.hip) ------------------------------------
 struct DispItem { const double *host; double *dst; const int32_t *perm; int m; };   // dst, perm: device pointers
@@ -42,13 +43,8 @@ __global__ void fill_ip_w3_kernel(const double *__restrict__ vx, const double *_
                                   double *__restrict__ out) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n_ip) return;
-    const double x = vx[q], y = vy[q], c = rho[q];
     double w00, w01, w11;
-    if (c == 0.0) { w00 = 1.0 / x; w01 = 0.0; w11 = 1.0 / y; }
-    else {
-        const double inv_det = 1.0 / ((1.0 - c * c) * x * y);
-        w00 = inv_det * y; w01 = -inv_det * c * sqrt(x * y); w11 = inv_det * x;
-    }
+    jaicov::obs_weight(vx[q], vy[q], rho[q], 1.0, w00, w01, w11);
     out[3 * (long)q] = w00; out[3 * (long)q + 1] = w01; out[3 * (long)q + 2] = w11;
 }
 
@@ -57,14 +53,9 @@ __global__ void fill_ip_w3_kernel(const double *__restrict__ vx, const double *_
 __global__ void fill_diag_weight_kernel(const double *__restrict__ vx, const double *__restrict__ vy, const double *__restrict__ rho, int ipb, int m,
                                         double *__restrict__ out) {
     const int i = blockIdx.x, q = i >> 1, r = i & 1;
-    const double x = vx[ipb + q], y = vy[ipb + q], c = rho[ipb + q];
-    double w0, w1;   // entries (i, 2q), (i, 2q + 1)
-    if (c == 0.0) { w0 = r == 0 ? 1.0 / x : 0.0; w1 = r == 0 ? 0.0 : 1.0 / y; }
-    else {
-        const double inv_det = 1.0 / ((1.0 - c * c) * x * y), off = -inv_det * c * sqrt(x * y);
-        w0 = r == 0 ? inv_det * y : off;
-        w1 = r == 0 ? off : inv_det * x;
-    }
+    double w00, w01, w11;
+    jaicov::obs_weight(vx[ipb + q], vy[ipb + q], rho[ipb + q], 1.0, w00, w01, w11);
+    const double w0 = r == 0 ? w00 : w01, w1 = r == 0 ? w01 : w11;   // entries (i, 2q), (i, 2q + 1)
     double *o = out + (long)i * m;
     for (int j = threadIdx.x; j < m; j += blockDim.x) o[j] = j == 2 * q ? w0 : (j == 2 * q + 1 ? w1 : 0.0);
 }

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <initializer_list>
 #include <memory>
 #include <string>
@@ -159,6 +160,33 @@ inline int q_download(const QView &v, std::initializer_list<QCopy> copies) {
         if (c.dst && c.bytes) HIPE(*v.err, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, v.stream));
     HIPE(*v.err, hipStreamSynchronize(v.stream));
     return JAICOV_OK;
+}
+
+// What reliability.hip and vce.hip need to know of the engine's image blocks before they launch
+struct QImageBlocks {
+    std::vector<int32_t> new2old;   // engine position -> the caller's image point; empty: the two orders are one
+    std::vector<uint8_t> dense;     // [n_ip] 1: in a block with a dense weight matrix; 0: 2 x 2 weights (compact-weight blocks included)
+    std::vector<int32_t> blocks;    // the engine image blocks with a dense weight matrix and at least one point, ascending
+    int max_m = 0;                  // rows of the largest of them
+    int caller(long q) const { return new2old.empty() ? (int)q : new2old[q]; }
+};
+inline QImageBlocks q_image_blocks(const QView &v) {
+    QImageBlocks ib;
+    const long n_ip = v.p->n_ip;
+    if (!v.ip_old2new->empty()) {
+        ib.new2old.resize(n_ip);
+        for (long o = 0; o < n_ip; o++) ib.new2old[(*v.ip_old2new)[o]] = (int32_t)o;
+    }
+    ib.dense.assign(n_ip, 0);
+    const std::vector<int32_t> &bb = *v.blk_ip_begin;
+    const std::vector<int64_t> &bw = *v.blk_w_off;
+    for (size_t g = 0; g + 1 < bb.size(); g++) {
+        if (bw[g] < 0 || bb[g + 1] <= bb[g]) continue;
+        ib.blocks.push_back((int32_t)g);
+        ib.max_m = std::max(ib.max_m, 2 * (bb[g + 1] - bb[g]));
+        for (int q = bb[g]; q < bb[g + 1]; q++) ib.dense[q] = 1;
+    }
+    return ib;
 }
 
 // ---- the device's reads of the matrix

@@ -14,14 +14,18 @@
 //
 // Leave-one-out table of every image point (include/jaicov_reliability_points.h), launched by jaicov_rel_run_points only, after
 // the kernels above, which it runs unchanged:
-//   rel_points_loo_kernel     image points with 2 x 2 weights: H, P as in rel_points_kernel, then M = P - P H P, nabla^ = -inv(M) g
+//   rel_points_loo_kernel     image points with 2 x 2 weights: H from the same rl_point, then M = P - P H P, nabla^ = -inv(M) g
 //                             and the shift -Q[P(q), cols(q)] A_q' P nabla^ over the point's own 3 + kc columns, all per lane
 //   rel_block_points_kernel   dense blocks, one thread per image point, after G = H P: g, M = P_S - (P G)_SS (sums over
 //                             j = 0 .. m-1 in order), the closed-form columns; nabla^ goes to a work buffer
 //   rel_shift_pp_kernel       dense blocks: sum_j Q[P(q), P(j)] a_p(j) c_q[j], c_q = P[:, S_q] nabla^_q, one workgroup per pair of
-//                             16-point chunks (rel_pp_kernel's staging of Q), one partial sum per (point, chunk)
+//                             16-point chunks (the same rl_stage_pair as rel_pp_kernel), one partial sum per (point, chunk)
 //   rel_shift_kernel          dense blocks, one thread per image point: A_s' c_q (kc sums over j in order), Q[P(q), S] of it, the
 //                             partial sums added in chunk order; the sum order does not depend on the images per batch
+//
+// Shared parts.  Layout, 2 x 2 weight, scale-bar and directly observed row: obsmodel.h.  Here: rl_stage_shared (scol and Q[S, S] of an
+// image), rl_point (a_s and H of an image point), rl_stage_pair (chunk pair, a_p and Q[cols(a), cols(b)]).  Host: rel_run_impl hands one
+// RelRun to rel_run_points2x2, rel_run_dense and rel_run_rest; which blocks are dense is q_image_blocks (qview.h), as for vce.hip.
 //
 // H of a dense block.  A row of image point q has its 3 point columns P(q) and the kc <= 29 shared columns S of the image (IO,
 // distortion, EO).  With a_p, a_s the two parts of a row:
@@ -40,6 +44,7 @@
 #include "../../include/jaicov_reliability.h"
 #include "../../include/jaicov_reliability_points.h"
 #include "gemm_f64.h"
+#include "obsmodel.h"
 #include "qview.h"
 #include "reliability.h"
 #include "status.h"
@@ -54,11 +59,6 @@ constexpr int RL_K = 64;                  // inner dimension of the shared-colum
 constexpr double RL_UNCONTROLLED = 1e-10; // (P Q_vv P)_ii <= this * P_ii: the observation is not controlled, t = NaN
 static_assert(2 * KC_MAX <= RL_K && RL_K % GEMM_BK == 0, "[Y | A_s] must fit the inner dimension of the shared-column GEMM");
 
-// shared local column c (0..kc) -> local row of the compact rows, and its global column (assemble.hip's shared_local / shared_col)
-__device__ __forceinline__ int rl_local(int c) { return c < 3 ? 3 + c : (c < 9 ? 6 + (c - 3) : 12 + (c - 9)); }
-__device__ __forceinline__ int rl_col(const DevProblem &p, int img, int cam, int jb, int c) {
-    return c < 3 ? p.io_col[3 * cam + c] : (c < 9 ? p.eo_col[6 * img + (c - 3)] : p.dist_col[jb + (c - 9)]);
-}
 __device__ __forceinline__ long rl_row(const int32_t *__restrict__ new2old, int ip, int c) {
     return 2 * (long)(new2old ? new2old[ip] : ip) + c;
 }
@@ -82,8 +82,7 @@ __global__ __launch_bounds__(256) void rel_v_kernel(DevProblem p, const double *
     const int jb = p.cam_dist_begin[cam], nd = p.cam_dist_begin[cam + 1] - jb;
     double v0 = -rowsW[ip], v1 = -rowsW[S + ip];
     for (int l = 0; l < 12 + nd; l++) {
-        const int col = l < 3 ? p.point_col[3 * pt + l]
-                              : (l < 6 ? p.io_col[3 * cam + l - 3] : (l < 12 ? p.eo_col[6 * img + l - 6] : p.dist_col[jb + l - 12]));
+        const int col = obs_row_col(p, pt, img, cam, jb, l);
         if (col < 0) continue;
         const double d = dx[col];
         v0 = fma(rowsA[(long)(2 * l) * S + ip], d, v0);
@@ -91,6 +90,81 @@ __global__ __launch_bounds__(256) void rel_v_kernel(DevProblem p, const double *
     }
     v[2 * (long)ip] = v0;
     v[2 * (long)ip + 1] = v1;
+}
+
+// A workgroup of RL_PTS threads stages what it needs of the shared columns S of image img: scol[c] = the global column of shared local
+// column c, sQ = Q[S, S] (row length KC_MAX, zero in the fixed columns).  Returns kc; the last barrier is behind it.
+__device__ __forceinline__ int rl_stage_shared(const DevProblem &p, int img, const double *Q, long ld, int *scol, double *sQ) {
+    const int tid = threadIdx.x;
+    const int cam = p.image_camera[img], jb = p.cam_dist_begin[cam], kc = obs_kc(p, cam);
+    if (tid < kc) scol[tid] = obs_shared_col(p, img, cam, jb, tid);
+    __syncthreads();
+    for (int i = tid; i < kc * kc; i += RL_PTS) {
+        const int a = i / kc, b = i - a * kc;
+        const int qa = scol[a], qb = scol[b];
+        sQ[a * KC_MAX + b] = (qa < 0 || qb < 0) ? 0.0 : q_sym(Q, ld, qa, qb);
+    }
+    __syncthreads();
+    return kc;
+}
+
+// An image point with 2 x 2 weights: its point columns pc, their coefficients ap (zero where fixed) and the 2 x 2 H = A Q A' of its rows
+struct RelPoint {
+    int pc[3];
+    double ap[2][3];
+    double h00, h01, h11;
+};
+
+// Fills o for engine image point ip and leaves the shared part a_s of its two rows in LDS: column c of row 0 / 1 at my0 / my1[c * RL_PTS]
+// (zero where fixed).  scol, sQ: rl_stage_shared's.  No barrier: a lane reads its own a_s only.
+__device__ __forceinline__ void rl_point(const DevProblem &p, int ip, int kc, const int *scol, const double *sQ, double *my0, double *my1,
+                                         const double *Q, long ld, const double *rowsA, RelPoint &o) {
+    const long S = p.n_ip;
+    const int pt = p.ip_point[ip];
+    for (int c = 0; c < kc; c++) {
+        const bool f = scol[c] >= 0;
+        my0[c * RL_PTS] = f ? rowsA[(long)(2 * obs_shared_row(c)) * S + ip] : 0.0;
+        my1[c * RL_PTS] = f ? rowsA[(long)(2 * obs_shared_row(c) + 1) * S + ip] : 0.0;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        o.pc[a] = p.point_col[3 * pt + a];
+        o.ap[0][a] = o.pc[a] >= 0 ? rowsA[(long)(2 * a) * S + ip] : 0.0;
+        o.ap[1][a] = o.pc[a] >= 0 ? rowsA[(long)(2 * a + 1) * S + ip] : 0.0;
+    }
+    double h00 = 0.0, h01 = 0.0, h11 = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            if (o.pc[a] < 0 || o.pc[b] < 0) continue;
+            const double q = q_sym(Q, ld, o.pc[a], o.pc[b]);
+            h00 = fma(o.ap[0][a], q * o.ap[0][b], h00);
+            h01 = fma(o.ap[0][a], q * o.ap[1][b], h01);
+            h11 = fma(o.ap[1][a], q * o.ap[1][b], h11);
+        }
+    for (int c = 0; c < kc; c++) {
+        const int qc = scol[c];
+        if (qc < 0) continue;
+        double y0 = 0.0, y1 = 0.0, z0 = 0.0, z1 = 0.0;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            if (o.pc[a] < 0) continue;
+            const double q = q_sym(Q, ld, qc, o.pc[a]);
+            y0 = fma(q, o.ap[0][a], y0);
+            y1 = fma(q, o.ap[1][a], y1);
+        }
+        for (int b = 0; b < kc; b++) {
+            const double q = sQ[c * KC_MAX + b];
+            z0 = fma(q, my0[b * RL_PTS], z0);
+            z1 = fma(q, my1[b * RL_PTS], z1);
+        }
+        const double a0 = my0[c * RL_PTS], a1 = my1[c * RL_PTS];
+        h00 += a0 * (2.0 * y0 + z0);
+        h11 += a1 * (2.0 * y1 + z1);
+        h01 += y0 * a1 + a0 * (y1 + z1);
+    }
+    o.h00 = h00; o.h01 = h01; o.h11 = h11;
 }
 
 // chunks[i] = (first engine image point, count <= RL_PTS), all of one image, all with 2 x 2 weights
@@ -103,83 +177,21 @@ __global__ __launch_bounds__(RL_PTS) void rel_points_kernel(DevProblem p, const 
     __shared__ int scol[KC_MAX];
     const int tid = threadIdx.x;
     const int2 ch = chunks[blockIdx.x];
-    const int img = p.ip_image[ch.x], cam = p.image_camera[img], jb = p.cam_dist_begin[cam];
-    const int kc = 9 + p.cam_dist_begin[cam + 1] - jb;
-    const long S = p.n_ip;
-    if (tid < kc) scol[tid] = rl_col(p, img, cam, jb, tid);
-    __syncthreads();
-    for (int i = tid; i < kc * kc; i += RL_PTS) {
-        const int a = i / kc, b = i - a * kc;
-        const int qa = scol[a], qb = scol[b];
-        sQ[a * KC_MAX + b] = (qa < 0 || qb < 0) ? 0.0 : q_sym(Q, ld, qa, qb);
-    }
-    __syncthreads();
+    const int kc = rl_stage_shared(p, p.ip_image[ch.x], Q, ld, scol, sQ);
     if (tid >= ch.y) return;
-    const int ip = ch.x + tid, pt = p.ip_point[ip];
-    double *my0 = sA + tid, *my1 = sA + KC_MAX * RL_PTS + tid;   // column c of row 0 / 1 at [c * RL_PTS]
-    for (int c = 0; c < kc; c++) {
-        const bool f = scol[c] >= 0;
-        my0[c * RL_PTS] = f ? rowsA[(long)(2 * rl_local(c)) * S + ip] : 0.0;
-        my1[c * RL_PTS] = f ? rowsA[(long)(2 * rl_local(c) + 1) * S + ip] : 0.0;
-    }
-    int pc[3];
-    double ap[2][3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        pc[a] = p.point_col[3 * pt + a];
-        ap[0][a] = pc[a] >= 0 ? rowsA[(long)(2 * a) * S + ip] : 0.0;
-        ap[1][a] = pc[a] >= 0 ? rowsA[(long)(2 * a + 1) * S + ip] : 0.0;
-    }
-    double h00 = 0.0, h01 = 0.0, h11 = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) {
-            if (pc[a] < 0 || pc[b] < 0) continue;
-            const double q = q_sym(Q, ld, pc[a], pc[b]);
-            h00 = fma(ap[0][a], q * ap[0][b], h00);
-            h01 = fma(ap[0][a], q * ap[1][b], h01);
-            h11 = fma(ap[1][a], q * ap[1][b], h11);
-        }
-    for (int c = 0; c < kc; c++) {
-        const int qc = scol[c];
-        if (qc < 0) continue;
-        double y0 = 0.0, y1 = 0.0, z0 = 0.0, z1 = 0.0;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            if (pc[a] < 0) continue;
-            const double q = q_sym(Q, ld, qc, pc[a]);
-            y0 = fma(q, ap[0][a], y0);
-            y1 = fma(q, ap[1][a], y1);
-        }
-        for (int b = 0; b < kc; b++) {
-            const double q = sQ[c * KC_MAX + b];
-            z0 = fma(q, my0[b * RL_PTS], z0);
-            z1 = fma(q, my1[b * RL_PTS], z1);
-        }
-        const double a0 = my0[c * RL_PTS], a1 = my1[c * RL_PTS];
-        h00 += a0 * (2.0 * y0 + z0);
-        h11 += a1 * (2.0 * y1 + z1);
-        h01 += y0 * a1 + a0 * (y1 + z1);
-    }
-    // P = sigma0^2 inv(D) of the point (PDF:296-319)
+    const int ip = ch.x + tid;
+    RelPoint k;
+    rl_point(p, ip, kc, scol, sQ, sA + tid, sA + KC_MAX * RL_PTS + tid, Q, ld, rowsA, k);
     double p00, p01, p11;
-    {
-        const double vx = p.ip_var_x[ip], vy = p.ip_var_y[ip], rho = p.ip_rho[ip];
-        if (rho == 0) {
-            p00 = s0 / vx; p11 = s0 / vy; p01 = 0.0;
-        } else {
-            const double invDet = s0 / ((1.0 - rho * rho) * vx * vy);
-            p00 = invDet * vy; p11 = invDet * vx; p01 = -invDet * rho * sqrt(vx * vy);
-        }
-    }
-    const double g00 = h00 * p00 + h01 * p01, g01 = h00 * p01 + h01 * p11;
-    const double g10 = h01 * p00 + h11 * p01, g11 = h01 * p01 + h11 * p11;
+    obs_weight(p, ip, s0, p00, p01, p11);
+    // g01 as an fma: which of its two products is fused must not hang on the order in which obs_weight defines its results
+    const double g00 = k.h00 * p00 + k.h01 * p01, g01 = fma(k.h00, p01, k.h01 * p11);
+    const double g10 = k.h01 * p00 + k.h11 * p01, g11 = k.h01 * p01 + k.h11 * p11;
     const double ppp0 = p00 - (p00 * g00 + p01 * g10), ppp1 = p11 - (p01 * g01 + p11 * g11);
     const double v0 = v[2 * (long)ip], v1 = v[2 * (long)ip + 1];
     const double pv0 = p00 * v0 + p01 * v1, pv1 = p01 * v0 + p11 * v1;
-    rl_store(out, n_rows, rl_row(new2old, ip, 0), v0, lld[2 * (long)ip] / s0 - h00, 1.0 - g00, rl_t(pv0, ppp0, p00, s2t));
-    rl_store(out, n_rows, rl_row(new2old, ip, 1), v1, lld[2 * (long)ip + 1] / s0 - h11, 1.0 - g11, rl_t(pv1, ppp1, p11, s2t));
+    rl_store(out, n_rows, rl_row(new2old, ip, 0), v0, lld[2 * (long)ip] / s0 - k.h00, 1.0 - g00, rl_t(pv0, ppp0, p00, s2t));
+    rl_store(out, n_rows, rl_row(new2old, ip, 1), v1, lld[2 * (long)ip + 1] / s0 - k.h11, 1.0 - g11, rl_t(pv1, ppp1, p11, s2t));
 }
 
 // Dense blocks, per row i < m of block bl[blockIdx.y]: L[i] = [y(i) | a_s(i)], R[i] = [a_s(i) | u(i)] (KC_MAX each, zero beyond kc and
@@ -192,17 +204,8 @@ __global__ __launch_bounds__(RL_PTS) void rel_prep_kernel(DevProblem p, const in
     const int tid = threadIdx.x;
     const int g = bl[blockIdx.y];
     const int ipb = p.blk_ip_begin[g], m = 2 * (p.blk_ip_begin[g + 1] - ipb);
-    const int img = p.ip_image[ipb], cam = p.image_camera[img], jb = p.cam_dist_begin[cam];
-    const int kc = 9 + p.cam_dist_begin[cam + 1] - jb;
+    const int kc = rl_stage_shared(p, p.ip_image[ipb], Q, ld, scol, sQ);
     const long S = p.n_ip;
-    if (tid < kc) scol[tid] = rl_col(p, img, cam, jb, tid);
-    __syncthreads();
-    for (int i = tid; i < kc * kc; i += RL_PTS) {
-        const int a = i / kc, b = i - a * kc;
-        const int qa = scol[a], qb = scol[b];
-        sQ[a * KC_MAX + b] = (qa < 0 || qb < 0) ? 0.0 : q_sym(Q, ld, qa, qb);
-    }
-    __syncthreads();
     const int i = blockIdx.x * RL_PTS + tid;
     if (i >= mpad) return;
     double *Lr = L + ((long)blockIdx.y * mpad + i) * RL_K, *Rr = R + ((long)blockIdx.y * mpad + i) * RL_K;
@@ -212,7 +215,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_prep_kernel(DevProblem p, const in
     }
     const int ip = ipb + (i >> 1), r = i & 1, pt = p.ip_point[ip];
     double *my = sA + tid;
-    for (int c = 0; c < kc; c++) my[c * RL_PTS] = scol[c] >= 0 ? rowsA[(long)(2 * rl_local(c) + r) * S + ip] : 0.0;
+    for (int c = 0; c < kc; c++) my[c * RL_PTS] = scol[c] >= 0 ? rowsA[(long)(2 * obs_shared_row(c) + r) * S + ip] : 0.0;
     int pc[3];
     double ap[3];
 #pragma unroll
@@ -237,18 +240,21 @@ __global__ __launch_bounds__(RL_PTS) void rel_prep_kernel(DevProblem p, const in
     for (int k = 2 * KC_MAX; k < RL_K; k++) { Lr[k] = 0.0; Rr[k] = 0.0; }
 }
 
-// Dense blocks: H[bi][rows of chunk a][rows of chunk b] = a_p Q[P, P] a_p' (and its mirror), one workgroup per chunk pair b <= a.
-// grid (most chunk pairs of a block of the batch, blocks of the batch)
-__global__ __launch_bounds__(256) void rel_pp_kernel(DevProblem p, const int32_t *__restrict__ bl, int mpad, const double *__restrict__ Q, long ld,
-                                                     const double *__restrict__ rowsA, double *__restrict__ H) {
-    __shared__ double sQ[RL_PC * (RL_PC + 1)];
-    __shared__ double sAa[RL_RC * 3], sAb[RL_RC * 3];
-    __shared__ int colA[RL_PC], colB[RL_PC];
+// The chunk pair b <= a of workgroup blockIdx.x of block bl[blockIdx.y]: false where the block has fewer pairs (the whole workgroup
+// leaves).  Otherwise colA / colB = the point columns of the chunks' points (-1: none), sAa / sAb = a_p of their 32 rows each,
+// sQ = Q[cols(a), cols(b)] (row length RL_PC + 1, zero where a column is none); the last barrier is behind it.
+struct RelPair {
+    long a, b;                 // chunks
+    int pa0, pb0, na, nb;      // first point and points of either chunk
+};
+__device__ __forceinline__ bool rl_stage_pair(const DevProblem &p, const int32_t *bl, const double *Q, long ld,
+                                              const double *rowsA, double *sQ, double *sAa, double *sAb, int *colA, int *colB,
+                                              RelPair &o) {
     const int tid = threadIdx.x;
     const int g = bl[blockIdx.y];
     const int ipb = p.blk_ip_begin[g], mp = p.blk_ip_begin[g + 1] - ipb;
     const long nch = (mp + RL_TP - 1) / RL_TP, tiles = nch * (nch + 1) / 2, t = blockIdx.x;
-    if (t >= tiles) return;
+    if (t >= tiles) return false;
     long a = (long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
     while (a * (a + 1) / 2 > t) a--;
     while ((a + 1) * (a + 2) / 2 <= t) a++;
@@ -282,6 +288,22 @@ __global__ __launch_bounds__(256) void rel_pp_kernel(DevProblem p, const int32_t
         if (qr >= 0 && qc >= 0 && qr < qc) sQ[r * (RL_PC + 1) + c] = Q[(long)qc * ld + qr];
     }
     __syncthreads();
+    o.a = a; o.b = b; o.pa0 = pa0; o.pb0 = pb0; o.na = na; o.nb = nb;
+    return true;
+}
+
+// Dense blocks: H[bi][rows of chunk a][rows of chunk b] = a_p Q[P, P] a_p' (and its mirror), one workgroup per chunk pair b <= a.
+// grid (most chunk pairs of a block of the batch, blocks of the batch)
+__global__ __launch_bounds__(256) void rel_pp_kernel(DevProblem p, const int32_t *__restrict__ bl, int mpad, const double *__restrict__ Q, long ld,
+                                                     const double *__restrict__ rowsA, double *__restrict__ H) {
+    __shared__ double sQ[RL_PC * (RL_PC + 1)];
+    __shared__ double sAa[RL_RC * 3], sAb[RL_RC * 3];
+    __shared__ int colA[RL_PC], colB[RL_PC];
+    const int tid = threadIdx.x;
+    RelPair t;
+    if (!rl_stage_pair(p, bl, Q, ld, rowsA, sQ, sAa, sAb, colA, colB, t)) return;
+    const long a = t.a, b = t.b;
+    const int pa0 = t.pa0, pb0 = t.pb0, na = t.na, nb = t.nb;
     double *Hb = H + (long)blockIdx.y * mpad * mpad;
     const int ra = 2 * pa0, rb = 2 * pb0;
     for (int i = tid; i < RL_RC * RL_RC; i += 256) {
@@ -374,7 +396,7 @@ __device__ __forceinline__ double2 rl_point_columns(double g0, double g1, double
     return make_double2(nx, ny);
 }
 
-// The image points of rel_points_kernel's chunks once more: H and P as there, then the point's columns and its shift.
+// The image points of rel_points_kernel's chunks once more: the same rl_point, then the point's columns and its shift.
 __global__ __launch_bounds__(RL_PTS) void rel_points_loo_kernel(DevProblem p, const int2 *__restrict__ chunks, const double *__restrict__ Q, long ld,
                                                                 const double *__restrict__ rowsA, const double *__restrict__ v,
                                                                 const int32_t *__restrict__ new2old, double s0, double s2t, RelPointArgs pa,
@@ -384,65 +406,14 @@ __global__ __launch_bounds__(RL_PTS) void rel_points_loo_kernel(DevProblem p, co
     __shared__ int scol[KC_MAX];
     const int tid = threadIdx.x;
     const int2 ch = chunks[blockIdx.x];
-    const int img = p.ip_image[ch.x], cam = p.image_camera[img], jb = p.cam_dist_begin[cam];
-    const int kc = 9 + p.cam_dist_begin[cam + 1] - jb;
-    const long S = p.n_ip;
-    if (tid < kc) scol[tid] = rl_col(p, img, cam, jb, tid);
-    __syncthreads();
-    for (int i = tid; i < kc * kc; i += RL_PTS) {
-        const int a = i / kc, b = i - a * kc;
-        const int qa = scol[a], qb = scol[b];
-        sQ[a * KC_MAX + b] = (qa < 0 || qb < 0) ? 0.0 : q_sym(Q, ld, qa, qb);
-    }
-    __syncthreads();
+    const int kc = rl_stage_shared(p, p.ip_image[ch.x], Q, ld, scol, sQ);
     if (tid >= ch.y) return;
-    const int ip = ch.x + tid, pnt = p.ip_point[ip];
-    double *my0 = sA + tid, *my1 = sA + KC_MAX * RL_PTS + tid;   // column c of row 0 / 1 at [c * RL_PTS]
-    for (int c = 0; c < kc; c++) {
-        const bool f = scol[c] >= 0;
-        my0[c * RL_PTS] = f ? rowsA[(long)(2 * rl_local(c)) * S + ip] : 0.0;
-        my1[c * RL_PTS] = f ? rowsA[(long)(2 * rl_local(c) + 1) * S + ip] : 0.0;
-    }
-    int pc[3];
-    double ap[2][3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        pc[a] = p.point_col[3 * pnt + a];
-        ap[0][a] = pc[a] >= 0 ? rowsA[(long)(2 * a) * S + ip] : 0.0;
-        ap[1][a] = pc[a] >= 0 ? rowsA[(long)(2 * a + 1) * S + ip] : 0.0;
-    }
-    double h00 = 0.0, h01 = 0.0, h11 = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) {
-            if (pc[a] < 0 || pc[b] < 0) continue;
-            const double q = q_sym(Q, ld, pc[a], pc[b]);
-            h00 = fma(ap[0][a], q * ap[0][b], h00);
-            h01 = fma(ap[0][a], q * ap[1][b], h01);
-            h11 = fma(ap[1][a], q * ap[1][b], h11);
-        }
-    for (int c = 0; c < kc; c++) {
-        const int qc = scol[c];
-        if (qc < 0) continue;
-        double y0 = 0.0, y1 = 0.0, z0 = 0.0, z1 = 0.0;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            if (pc[a] < 0) continue;
-            const double q = q_sym(Q, ld, qc, pc[a]);
-            y0 = fma(q, ap[0][a], y0);
-            y1 = fma(q, ap[1][a], y1);
-        }
-        for (int b = 0; b < kc; b++) {
-            const double q = sQ[c * KC_MAX + b];
-            z0 = fma(q, my0[b * RL_PTS], z0);
-            z1 = fma(q, my1[b * RL_PTS], z1);
-        }
-        const double a0 = my0[c * RL_PTS], a1 = my1[c * RL_PTS];
-        h00 += a0 * (2.0 * y0 + z0);
-        h11 += a1 * (2.0 * y1 + z1);
-        h01 += y0 * a1 + a0 * (y1 + z1);
-    }
+    const int ip = ch.x + tid;
+    double *my0 = sA + tid, *my1 = sA + KC_MAX * RL_PTS + tid;
+    RelPoint k;
+    rl_point(p, ip, kc, scol, sQ, my0, my1, Q, ld, rowsA, k);
+    // P written out, not obs_weight: rl_point_columns fuses the products of q and tr by the rank of P's entries, and the table's bits
+    // are those of this order of definition (the dense blocks' kernel, which loads P, has its own)
     double p00, p01, p11;
     {
         const double vx = p.ip_var_x[ip], vy = p.ip_var_y[ip], rho = p.ip_rho[ip];
@@ -454,8 +425,8 @@ __global__ __launch_bounds__(RL_PTS) void rel_points_loo_kernel(DevProblem p, co
         }
     }
     // N = P H P (H has no entries outside the point's own two rows: P is 2 x 2)
-    const double g00 = h00 * p00 + h01 * p01, g01 = h00 * p01 + h01 * p11;
-    const double g10 = h01 * p00 + h11 * p01, g11 = h01 * p01 + h11 * p11;
+    const double g00 = k.h00 * p00 + k.h01 * p01, g01 = k.h00 * p01 + k.h01 * p11;
+    const double g10 = k.h01 * p00 + k.h11 * p01, g11 = k.h01 * p01 + k.h11 * p11;
     const double nxx = p00 * g00 + p01 * g10, nxy = p00 * g01 + p01 * g11, nyy = p01 * g01 + p11 * g11;
     const double v0 = v[2 * (long)ip], v1 = v[2 * (long)ip + 1];
     const long n = p.n_ip, o = new2old ? new2old[ip] : ip;
@@ -465,11 +436,11 @@ __global__ __launch_bounds__(RL_PTS) void rel_points_loo_kernel(DevProblem p, co
     double sh[3] = {0.0, 0.0, 0.0};
 #pragma unroll
     for (int b = 0; b < 3; b++) {
-        if (pc[b] < 0) continue;
-        const double bp = ap[0][b] * c0 + ap[1][b] * c1;
+        if (k.pc[b] < 0) continue;
+        const double bp = k.ap[0][b] * c0 + k.ap[1][b] * c1;
 #pragma unroll
         for (int a = 0; a < 3; a++)
-            if (pc[a] >= 0) sh[a] = fma(q_sym(Q, ld, pc[a], pc[b]), bp, sh[a]);
+            if (k.pc[a] >= 0) sh[a] = fma(q_sym(Q, ld, k.pc[a], k.pc[b]), bp, sh[a]);
     }
     for (int c = 0; c < kc; c++) {
         const int qc = scol[c];
@@ -477,11 +448,11 @@ __global__ __launch_bounds__(RL_PTS) void rel_points_loo_kernel(DevProblem p, co
         const double bs = my0[c * RL_PTS] * c0 + my1[c * RL_PTS] * c1;
 #pragma unroll
         for (int a = 0; a < 3; a++)
-            if (pc[a] >= 0) sh[a] = fma(q_sym(Q, ld, pc[a], qc), bs, sh[a]);
+            if (k.pc[a] >= 0) sh[a] = fma(q_sym(Q, ld, k.pc[a], qc), bs, sh[a]);
     }
     const bool ok = !isnan(nab.x);
 #pragma unroll
-    for (int a = 0; a < 3; a++) pt[(11 + a) * n + o] = ok ? (pc[a] >= 0 ? -sh[a] : 0.0) : (double)NAN;
+    for (int a = 0; a < 3; a++) pt[(11 + a) * n + o] = ok ? (k.pc[a] >= 0 ? -sh[a] : 0.0) : (double)NAN;
 }
 
 // Dense blocks, image point q of block bl[blockIdx.y]: grid (ceil(mpad / 2 / 256), batch).  nab: [batch][mpad / 2][2]
@@ -525,36 +496,10 @@ __global__ __launch_bounds__(256) void rel_shift_pp_kernel(DevProblem p, const i
     __shared__ double sT[2][RL_TP * RL_TP * 3];
     __shared__ int colA[RL_PC], colB[RL_PC];
     const int tid = threadIdx.x;
-    const int g = bl[blockIdx.y];
-    const int ipb = p.blk_ip_begin[g], mp = p.blk_ip_begin[g + 1] - ipb;
-    const long nch = (mp + RL_TP - 1) / RL_TP, tiles = nch * (nch + 1) / 2, t = blockIdx.x;
-    if (t >= tiles) return;
-    long a = (long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (a * (a + 1) / 2 > t) a--;
-    while ((a + 1) * (a + 2) / 2 <= t) a++;
-    const long b = t - a * (a + 1) / 2;
-    const int pa0 = (int)a * RL_TP, pb0 = (int)b * RL_TP;
-    const int na = min(RL_TP, mp - pa0), nb = min(RL_TP, mp - pb0);
-    const long S = p.n_ip;
-    if (tid < RL_PC) {
-        const int k = tid / 3, c = tid - 3 * k;
-        colA[tid] = k < na ? p.point_col[3 * p.ip_point[ipb + pa0 + k] + c] : -1;
-        colB[tid] = k < nb ? p.point_col[3 * p.ip_point[ipb + pb0 + k] + c] : -1;
-    }
-    __syncthreads();
-    if (tid < 2 * RL_RC) {   // a_p of the 32 rows of chunk a (threads 0-31) and of chunk b (32-63)
-        const int side = tid / RL_RC, k = tid - side * RL_RC, q = k >> 1, r = k & 1;
-        const int n = side ? nb : na, p0 = side ? pb0 : pa0;
-        const int *cl = side ? colB : colA;
-        double *dst = (side ? sAb : sAa) + 3 * k;
-        for (int c = 0; c < 3; c++) dst[c] = (q < n && cl[3 * q + c] >= 0) ? rowsA[(long)(2 * c + r) * S + ipb + p0 + q] : 0.0;
-    }
-    for (int i = tid; i < RL_PC * RL_PC; i += 256) {
-        const int r = i / RL_PC, c = i - r * RL_PC;
-        const int qr = colA[r], qc = colB[c];
-        sQ[r * (RL_PC + 1) + c] = (qr < 0 || qc < 0) ? 0.0 : q_sym(Q, ld, qr, qc);
-    }
-    __syncthreads();
+    RelPair t;
+    if (!rl_stage_pair(p, bl, Q, ld, rowsA, sQ, sAa, sAb, colA, colB, t)) return;
+    const long a = t.a, b = t.b;
+    const int pa0 = t.pa0, pb0 = t.pb0, na = t.na, nb = t.nb;
     const double *Pb = P + (long)blockIdx.y * mpad * mpad, *nb_ = nab + (long)blockIdx.y * mpad;
     const int qi = tid / RL_TP, ki = tid - qi * RL_TP;
     const int dirs = a != b ? 2 : 1;
@@ -603,8 +548,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_shift_kernel(DevProblem p, const i
     const int g = bl[blockIdx.y];
     const int ipb = p.blk_ip_begin[g], mp = p.blk_ip_begin[g + 1] - ipb, m = 2 * mp;
     if (q >= mp) return;
-    const int img = p.ip_image[ipb], cam = p.image_camera[img], jb = p.cam_dist_begin[cam];
-    const int kc = 9 + p.cam_dist_begin[cam + 1] - jb;
+    const int img = p.ip_image[ipb], cam = p.image_camera[img], jb = p.cam_dist_begin[cam], kc = obs_kc(p, cam);
     const double *Pb = P + (long)blockIdx.y * mpad * mpad + 2 * q, *Rb = R + (long)blockIdx.y * mpad * RL_K;
     const double nx = nab[(long)blockIdx.y * mpad + 2 * q], ny = nab[(long)blockIdx.y * mpad + 2 * q + 1];
     double acc[KC_MAX];
@@ -628,7 +572,7 @@ __global__ __launch_bounds__(RL_PTS) void rel_shift_kernel(DevProblem p, const i
         for (int a = 0; a < 3; a++) sh[a] += pq[3 * c + a];
 #pragma unroll
     for (int c = 0; c < KC_MAX; c++) {
-        const int qc = c < kc ? rl_col(p, img, cam, jb, c) : -1;
+        const int qc = c < kc ? obs_shared_col(p, img, cam, jb, c) : -1;
         if (qc < 0) continue;
 #pragma unroll
         for (int a = 0; a < 3; a++)
@@ -646,13 +590,9 @@ __global__ __launch_bounds__(64) void rel_scalebar_kernel(DevProblem p, const do
                                                           double *__restrict__ out) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= p.n_sb) return;
-    const int pa = p.sb_a[s], pb = p.sb_b[s];
-    const double *a = vals + 3 * pa, *b = vals + 3 * pb;
-    const double dX = b[0] - a[0], dY = b[1] - a[1], dZ = b[2] - a[2];
-    const double len = sqrt(dX * dX + dY * dY + dZ * dZ);
-    const double ev[6] = {-dX / len, -dY / len, -dZ / len, dX / len, dY / len, dZ / len};
     int col[6];
-    for (int k = 0; k < 6; k++) col[k] = k < 3 ? p.point_col[3 * pa + k] : p.point_col[3 * pb + k - 3];
+    double ev[6], len;
+    obs_scalebar_row(p, vals, s, col, ev, len);
     double v = len - p.sb_len[s], h = 0.0;     // v = A dx - w, w = observed - computed
     for (int k = 0; k < 6; k++) {
         if (col[k] < 0) continue;
@@ -676,11 +616,9 @@ __global__ __launch_bounds__(256) void rel_direct_kernel(DevProblem p, const dou
     const int b = p.dg_row_begin[g], m = p.dg_row_begin[g + 1] - b;
     const long woff = p.dg_w_offset[g];
     const double *W = woff >= 0 ? p.dg_w + woff : nullptr;
-    auto col_of = [&](int k) { return p.slot_col[p.dg_slot[b + k]]; };
-    auto v_of = [&](int k) {                   // v = A dx - w, w = observed - value
-        const int c = col_of(k);
-        return vals[p.dg_slot[b + k]] - p.dg_obs[b + k] + (c >= 0 ? dx[c] : 0.0);
-    };
+    auto col_of = [&](int k) { return obs_direct_col(p, b + k); };
+    // v = A dx - w = 0 - (w - A dx): the exact negative, and 0 - x leaves a zero its positive sign as (value - observed) + dx does
+    auto v_of = [&](int k) { return 0.0 - obs_direct_w(p, vals, dx, b + k, col_of(k)); };
     auto h_of = [&](int k, int l) {
         const int ck = col_of(k), cl = col_of(l);
         return (ck < 0 || cl < 0) ? 0.0 : q_sym(Q, ld, ck, cl);
@@ -755,155 +693,177 @@ namespace {
 constexpr size_t RL_BATCH_BYTES = (size_t)1 << 30;   // work buffers of the dense blocks per batch
 }  // namespace
 
+// What the three parts of a run share (w frees the run's device buffers on every exit).  pa != nullptr: the table of the image points
+// as well (jaicov_rel_run_points); everything it adds is launched after the plain run's kernels of the same group
+struct RelRun {
+    const QView &v;
+    DevBag &w;
+    double s2t;
+    const RelPointArgs *pa;
+    long n_rows;
+    double *d_res, *d_pt, *d_dx, *d_v;   // the result [4][n_rows], the table of the image points, the step, the residuals
+    int32_t *d_new2old;
+};
 
-// pa != nullptr: the table of the image points as well (jaicov_rel_run_points); everything it adds is launched after the plain run's
-// kernels of the same group, which stay what they are
-static int rel_run_impl(const QView &v, RelState *s, double s2t, const double *dx, const RelPointArgs *pa) {
+// the image points with 2 x 2 weights, in chunks of one image
+static int rel_run_points2x2(const RelRun &r, const QImageBlocks &ib) {
+    const QView &v = r.v;
+    const DevProblem &p = *v.p;
+    const long n_ip = p.n_ip;
+    const hipStream_t st = v.stream;
+    std::vector<int32_t> ip_image(n_ip);
+    HIPE(*v.err, hipMemcpyAsync(ip_image.data(), p.ip_image, (size_t)n_ip * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPE(*v.err, hipStreamSynchronize(st));
+    std::vector<int2> chunks;
+    for (long q = 0; q < n_ip;) {
+        if (ib.dense[q]) { q++; continue; }
+        long en = q;
+        while (en < n_ip && !ib.dense[en] && ip_image[en] == ip_image[q] && en - q < RL_PTS) en++;
+        chunks.push_back(make_int2((int)q, (int)(en - q)));
+        q = en;
+    }
+    if (chunks.empty()) return JAICOV_OK;
+    int2 *d_chunks = nullptr;
+    HIPE(*v.err, r.w.alloc(&d_chunks, chunks.size()));
+    HIPE(*v.err, hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(rel_points_kernel, dim3((unsigned)chunks.size()), dim3(RL_PTS), 0, st, p, d_chunks, v.Q, v.ld, v.rowsA, r.d_v,
+                       v.ll_diag, r.d_new2old, v.sigma2, r.s2t, r.n_rows, r.d_res);
+    HIPE(*v.err, hipGetLastError());
+    if (r.pa) {
+        hipLaunchKernelGGL(rel_points_loo_kernel, dim3((unsigned)chunks.size()), dim3(RL_PTS), 0, st, p, d_chunks, v.Q, v.ld, v.rowsA,
+                           r.d_v, r.d_new2old, v.sigma2, r.s2t, *r.pa, r.d_pt);
+        HIPE(*v.err, hipGetLastError());
+    }
+    return JAICOV_OK;
+}
+
+// the dense image blocks, as many at a time as the work buffers hold
+static int rel_run_dense(const RelRun &r, const QImageBlocks &ib) {
+    if (ib.blocks.empty()) return JAICOV_OK;
+    const QView &v = r.v;
+    const DevProblem &p = *v.p;
+    const RelPointArgs *pa = r.pa;
+    const double s0 = v.sigma2;
+    const hipStream_t st = v.stream;
+    DevBag &w = r.w;
+    const std::vector<int32_t> &bb = *v.blk_ip_begin;
+    const int nd = (int)ib.blocks.size();
+    const int mpad = (ib.max_m + 127) / 128 * 128;
+    const size_t sq = (size_t)mpad * mpad;
+    const size_t n_nab = (size_t)mpad, n_part = (size_t)(mpad / 2) * (mpad / RL_RC) * 3;   // per block, table run only
+    const size_t per = (3 * sq + 2 * (size_t)mpad * RL_K + (pa ? n_nab + n_part : 0)) * sizeof(double);
+    size_t cap = RL_BATCH_BYTES / per;
+    if (const char *hook = getenv("JAICOV_REL_BATCH")) cap = std::min<size_t>(cap, (size_t)std::max(1, atoi(hook)));   // test hook
+    const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)nd, cap));
+    int32_t *d_bl = nullptr;
+    double *d_H = nullptr, *d_P = nullptr, *d_G = nullptr, *d_L = nullptr, *d_R = nullptr;
+    HIPE(*v.err, w.alloc(&d_bl, (size_t)nd));
+    HIPE(*v.err, w.alloc(&d_H, nb * sq));
+    HIPE(*v.err, w.alloc(&d_P, nb * sq));
+    HIPE(*v.err, w.alloc(&d_G, nb * sq));
+    HIPE(*v.err, w.alloc(&d_L, (size_t)nb * mpad * RL_K));
+    HIPE(*v.err, w.alloc(&d_R, (size_t)nb * mpad * RL_K));
+    double *d_nab = nullptr, *d_part = nullptr;
+    if (pa) {
+        HIPE(*v.err, w.alloc(&d_nab, nb * n_nab));
+        HIPE(*v.err, w.alloc(&d_part, nb * n_part));
+    }
+    HIPE(*v.err, hipMemcpyAsync(d_bl, ib.blocks.data(), (size_t)nd * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    for (int b0 = 0; b0 < nd; b0 += nb) {
+        const int n = std::min(nb, nd - b0);
+        const int32_t *bl = d_bl + b0;
+        long tmax = 0;
+        for (int k = b0; k < b0 + n; k++) {
+            const long mp = bb[ib.blocks[k] + 1] - bb[ib.blocks[k]], nch = (mp + RL_TP - 1) / RL_TP;
+            tmax = std::max(tmax, nch * (nch + 1) / 2);
+        }
+        HIPE(*v.err, hipMemsetAsync(d_H, 0, n * sq * sizeof(double), st));
+        hipLaunchKernelGGL(rel_prep_kernel, dim3(mpad / RL_PTS, n), dim3(RL_PTS), 0, st, p, bl, mpad, v.Q, v.ld, v.rowsA, d_L, d_R);
+        hipLaunchKernelGGL(rel_pp_kernel, dim3((unsigned)tmax, n), dim3(256), 0, st, p, bl, mpad, v.Q, v.ld, v.rowsA, d_H);
+        hipLaunchKernelGGL(rel_pad_kernel, dim3(mpad / 256 + (mpad % 256 ? 1 : 0), mpad, n), dim3(256), 0, st, p, bl, mpad, s0, d_P);
+        HIPE(*v.err, hipGetLastError());
+        GemmArgs g1{};   // H += [Y | A_s] [A_s | U]'
+        g1.A = d_L; g1.lda = RL_K; g1.B = d_R; g1.ldb = RL_K; g1.C = d_H; g1.ldc = mpad;
+        g1.M = mpad; g1.N = mpad; g1.K = RL_K; g1.alpha = 1.0; g1.beta = 1.0; g1.kmode = KMODE_FULL;
+        g1.strideA = (long)mpad * RL_K; g1.strideB = (long)mpad * RL_K; g1.strideC = (long)sq;
+        HIPE(*v.err, gemm_f64(st, LAY_KC, LAY_KC, g1, n));
+        GemmArgs g2{};   // G = H P  (P symmetric: P(k, j) = P[j][k])
+        g2.A = d_H; g2.lda = mpad; g2.B = d_P; g2.ldb = mpad; g2.C = d_G; g2.ldc = mpad;
+        g2.M = mpad; g2.N = mpad; g2.K = mpad; g2.alpha = 1.0; g2.beta = 0.0; g2.kmode = KMODE_FULL;
+        g2.strideA = (long)sq; g2.strideB = (long)sq; g2.strideC = (long)sq;
+        HIPE(*v.err, gemm_f64(st, LAY_KC, LAY_KC, g2, n));
+        hipLaunchKernelGGL(rel_block_kernel, dim3(mpad / 256 + (mpad % 256 ? 1 : 0), n), dim3(256), 0, st, p, bl, mpad, d_H, d_P, d_G,
+                           r.d_v, v.ll_diag, r.d_new2old, s0, r.s2t, r.n_rows, r.d_res);
+        HIPE(*v.err, hipGetLastError());
+        if (pa) {
+            const int mp_pad = mpad / 2;
+            hipLaunchKernelGGL(rel_block_points_kernel, dim3((mp_pad + 255) / 256, n), dim3(256), 0, st, p, bl, mpad, d_P, d_G, r.d_v,
+                               r.d_new2old, r.s2t, *pa, d_nab, r.d_pt);
+            hipLaunchKernelGGL(rel_shift_pp_kernel, dim3((unsigned)tmax, n), dim3(256), 0, st, p, bl, mpad, v.Q, v.ld, v.rowsA, d_P,
+                               d_nab, d_part);
+            hipLaunchKernelGGL(rel_shift_kernel, dim3((mp_pad + RL_PTS - 1) / RL_PTS, n), dim3(RL_PTS), 0, st, p, bl, mpad, v.Q, v.ld,
+                               d_P, d_R, d_nab, d_part, r.d_new2old, r.d_pt);
+            HIPE(*v.err, hipGetLastError());
+        }
+    }
+    return JAICOV_OK;
+}
+
+// scale bars and directly observed groups, then the summary over all rows
+static int rel_run_rest(const RelRun &r, RelState *s) {
+    const QView &v = r.v;
     const DevProblem &p = *v.p;
     const double s0 = v.sigma2;
-    const long n_ip = p.n_ip, n_rows = s->n_rows;
+    const long n_ip = p.n_ip;
     const hipStream_t st = v.stream;
-    DevBag w;                                           // device buffers of this run, freed on every exit
-    s->summary[5] = v.lambda;
-    HIPE(*v.err, s->out.reserve(std::max<size_t>(4 * (size_t)n_rows, 1)));   // the result belongs to the state
-    double *const d_res = s->out.get();
-    if (pa) {
-        HIPE(*v.err, s->points.reserve(std::max<size_t>(JAICOV_REL_POINT_COLUMNS * (size_t)n_ip, 1)));
-        s->n_points = n_ip;
-    }
-    double *const d_pt = s->points.get();
-    if (n_rows == 0) return JAICOV_OK;
-    double *d_dx = nullptr, *d_v = nullptr, *d_sum = nullptr;
-    HIPE(*v.err, w.alloc(&d_dx, (size_t)v.U));
-    HIPE(*v.err, w.alloc(&d_v, 2 * (size_t)n_ip));
-    HIPE(*v.err, w.alloc(&d_sum, 5));
-    if (dx) HIPE(*v.err, hipMemcpyAsync(d_dx, dx, (size_t)v.U * sizeof(double), hipMemcpyHostToDevice, st));
-    else HIPE(*v.err, hipMemsetAsync(d_dx, 0, (size_t)v.U * sizeof(double), st));
-    // engine position -> the caller's image point
-    int32_t *d_new2old = nullptr;
-    if (!v.ip_old2new->empty() && n_ip > 0) {
-        std::vector<int32_t> new2old(n_ip);
-        for (long o = 0; o < n_ip; o++) new2old[(*v.ip_old2new)[o]] = (int32_t)o;
-        HIPE(*v.err, w.alloc(&d_new2old, (size_t)n_ip));
-        HIPE(*v.err, hipMemcpyAsync(d_new2old, new2old.data(), (size_t)n_ip * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        HIPE(*v.err, hipStreamSynchronize(st));        // new2old is a host temporary
-    }
-    if (n_ip > 0) {
-        hipLaunchKernelGGL(rel_v_kernel, dim3((unsigned)((n_ip + 255) / 256)), dim3(256), 0, st, p, v.rowsA, v.rowsW, d_dx, d_v);
-        HIPE(*v.err, hipGetLastError());
-        // which image points have 2 x 2 weights (ordinary groups, or ordinary images served as blocks with compact weights)
-        const std::vector<int32_t> &bb = *v.blk_ip_begin;
-        const std::vector<int64_t> &bw = *v.blk_w_off;
-        std::vector<uint8_t> dense(n_ip, 0);
-        std::vector<int32_t> dense_blocks;
-        int max_m = 0;
-        for (size_t g = 0; g + 1 < bb.size(); g++) {
-            if (bw[g] < 0 || bb[g + 1] <= bb[g]) continue;
-            dense_blocks.push_back((int32_t)g);
-            max_m = std::max(max_m, 2 * (bb[g + 1] - bb[g]));
-            for (int q = bb[g]; q < bb[g + 1]; q++) dense[q] = 1;
-        }
-        std::vector<int32_t> ip_image(n_ip);
-        HIPE(*v.err, hipMemcpyAsync(ip_image.data(), p.ip_image, (size_t)n_ip * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPE(*v.err, hipStreamSynchronize(st));
-        std::vector<int2> chunks;
-        for (long q = 0; q < n_ip;) {
-            if (dense[q]) { q++; continue; }
-            long en = q;
-            while (en < n_ip && !dense[en] && ip_image[en] == ip_image[q] && en - q < RL_PTS) en++;
-            chunks.push_back(make_int2((int)q, (int)(en - q)));
-            q = en;
-        }
-        if (!chunks.empty()) {
-            int2 *d_chunks = nullptr;
-            HIPE(*v.err, w.alloc(&d_chunks, chunks.size()));
-            HIPE(*v.err, hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(rel_points_kernel, dim3((unsigned)chunks.size()), dim3(RL_PTS), 0, st, p, d_chunks, v.Q, v.ld, v.rowsA, d_v,
-                               v.ll_diag, d_new2old, s0, s2t, n_rows, d_res);
-            HIPE(*v.err, hipGetLastError());
-            if (pa) {
-                hipLaunchKernelGGL(rel_points_loo_kernel, dim3((unsigned)chunks.size()), dim3(RL_PTS), 0, st, p, d_chunks, v.Q, v.ld, v.rowsA,
-                                   d_v, d_new2old, s0, s2t, *pa, d_pt);
-                HIPE(*v.err, hipGetLastError());
-            }
-        }
-        if (!dense_blocks.empty()) {
-            const int nd = (int)dense_blocks.size();
-            const int mpad = (max_m + 127) / 128 * 128;
-            const size_t sq = (size_t)mpad * mpad;
-            const size_t n_nab = (size_t)mpad, n_part = (size_t)(mpad / 2) * (mpad / RL_RC) * 3;   // per block, table run only
-            const size_t per = (3 * sq + 2 * (size_t)mpad * RL_K + (pa ? n_nab + n_part : 0)) * sizeof(double);
-            size_t cap = RL_BATCH_BYTES / per;
-            if (const char *hook = getenv("JAICOV_REL_BATCH")) cap = std::min<size_t>(cap, (size_t)std::max(1, atoi(hook)));   // test hook
-            const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)nd, cap));
-            int32_t *d_bl = nullptr;
-            double *d_H = nullptr, *d_P = nullptr, *d_G = nullptr, *d_L = nullptr, *d_R = nullptr;
-            HIPE(*v.err, w.alloc(&d_bl, (size_t)nd));
-            HIPE(*v.err, w.alloc(&d_H, nb * sq));
-            HIPE(*v.err, w.alloc(&d_P, nb * sq));
-            HIPE(*v.err, w.alloc(&d_G, nb * sq));
-            HIPE(*v.err, w.alloc(&d_L, (size_t)nb * mpad * RL_K));
-            HIPE(*v.err, w.alloc(&d_R, (size_t)nb * mpad * RL_K));
-            double *d_nab = nullptr, *d_part = nullptr;
-            if (pa) {
-                HIPE(*v.err, w.alloc(&d_nab, nb * n_nab));
-                HIPE(*v.err, w.alloc(&d_part, nb * n_part));
-            }
-            HIPE(*v.err, hipMemcpyAsync(d_bl, dense_blocks.data(), (size_t)nd * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            for (int b0 = 0; b0 < nd; b0 += nb) {
-                const int n = std::min(nb, nd - b0);
-                const int32_t *bl = d_bl + b0;
-                long tmax = 0;
-                for (int k = b0; k < b0 + n; k++) {
-                    const long mp = bb[dense_blocks[k] + 1] - bb[dense_blocks[k]], nch = (mp + RL_TP - 1) / RL_TP;
-                    tmax = std::max(tmax, nch * (nch + 1) / 2);
-                }
-                HIPE(*v.err, hipMemsetAsync(d_H, 0, n * sq * sizeof(double), st));
-                hipLaunchKernelGGL(rel_prep_kernel, dim3(mpad / RL_PTS, n), dim3(RL_PTS), 0, st, p, bl, mpad, v.Q, v.ld, v.rowsA, d_L, d_R);
-                hipLaunchKernelGGL(rel_pp_kernel, dim3((unsigned)tmax, n), dim3(256), 0, st, p, bl, mpad, v.Q, v.ld, v.rowsA, d_H);
-                hipLaunchKernelGGL(rel_pad_kernel, dim3(mpad / 256 + (mpad % 256 ? 1 : 0), mpad, n), dim3(256), 0, st, p, bl, mpad, s0, d_P);
-                HIPE(*v.err, hipGetLastError());
-                GemmArgs g1{};   // H += [Y | A_s] [A_s | U]'
-                g1.A = d_L; g1.lda = RL_K; g1.B = d_R; g1.ldb = RL_K; g1.C = d_H; g1.ldc = mpad;
-                g1.M = mpad; g1.N = mpad; g1.K = RL_K; g1.alpha = 1.0; g1.beta = 1.0; g1.kmode = KMODE_FULL;
-                g1.strideA = (long)mpad * RL_K; g1.strideB = (long)mpad * RL_K; g1.strideC = (long)sq;
-                HIPE(*v.err, gemm_f64(st, LAY_KC, LAY_KC, g1, n));
-                GemmArgs g2{};   // G = H P  (P symmetric: P(k, j) = P[j][k])
-                g2.A = d_H; g2.lda = mpad; g2.B = d_P; g2.ldb = mpad; g2.C = d_G; g2.ldc = mpad;
-                g2.M = mpad; g2.N = mpad; g2.K = mpad; g2.alpha = 1.0; g2.beta = 0.0; g2.kmode = KMODE_FULL;
-                g2.strideA = (long)sq; g2.strideB = (long)sq; g2.strideC = (long)sq;
-                HIPE(*v.err, gemm_f64(st, LAY_KC, LAY_KC, g2, n));
-                hipLaunchKernelGGL(rel_block_kernel, dim3(mpad / 256 + (mpad % 256 ? 1 : 0), n), dim3(256), 0, st, p, bl, mpad, d_H, d_P, d_G,
-                                   d_v, v.ll_diag, d_new2old, s0, s2t, n_rows, d_res);
-                HIPE(*v.err, hipGetLastError());
-                if (pa) {
-                    const int mp_pad = mpad / 2;
-                    hipLaunchKernelGGL(rel_block_points_kernel, dim3((mp_pad + 255) / 256, n), dim3(256), 0, st, p, bl, mpad, d_P, d_G, d_v,
-                                       d_new2old, s2t, *pa, d_nab, d_pt);
-                    hipLaunchKernelGGL(rel_shift_pp_kernel, dim3((unsigned)tmax, n), dim3(256), 0, st, p, bl, mpad, v.Q, v.ld, v.rowsA, d_P,
-                                       d_nab, d_part);
-                    hipLaunchKernelGGL(rel_shift_kernel, dim3((mp_pad + RL_PTS - 1) / RL_PTS, n), dim3(RL_PTS), 0, st, p, bl, mpad, v.Q, v.ld,
-                                       d_P, d_R, d_nab, d_part, d_new2old, d_pt);
-                    HIPE(*v.err, hipGetLastError());
-                }
-            }
-        }
-    }
+    double *d_sum = nullptr;
+    HIPE(*v.err, r.w.alloc(&d_sum, 5));
     if (p.n_sb > 0) {
-        hipLaunchKernelGGL(rel_scalebar_kernel, dim3((p.n_sb + 63) / 64), dim3(64), 0, st, p, v.d_vals, v.Q, v.ld, d_dx, s0, s2t, 2 * n_ip,
-                           n_rows, d_res);
+        hipLaunchKernelGGL(rel_scalebar_kernel, dim3((p.n_sb + 63) / 64), dim3(64), 0, st, p, v.d_vals, v.Q, v.ld, r.d_dx, s0, r.s2t, 2 * n_ip,
+                           r.n_rows, r.d_res);
         HIPE(*v.err, hipGetLastError());
     }
     if (p.n_dg > 0) {
-        hipLaunchKernelGGL(rel_direct_kernel, dim3(p.n_dg), dim3(256), 0, st, p, v.d_vals, v.Q, v.ld, d_dx, v.ll_diag + 2 * n_ip, s0, s2t,
-                           2 * n_ip + p.n_sb, n_rows, d_res);
+        hipLaunchKernelGGL(rel_direct_kernel, dim3(p.n_dg), dim3(256), 0, st, p, v.d_vals, v.Q, v.ld, r.d_dx, v.ll_diag + 2 * n_ip, s0, r.s2t,
+                           2 * n_ip + p.n_sb, r.n_rows, r.d_res);
         HIPE(*v.err, hipGetLastError());
     }
-    hipLaunchKernelGGL(rel_summary_kernel, dim3(1), dim3(256), 0, st, d_res, n_rows, d_sum);
+    hipLaunchKernelGGL(rel_summary_kernel, dim3(1), dim3(256), 0, st, r.d_res, r.n_rows, d_sum);
     HIPE(*v.err, hipGetLastError());
     HIPE(*v.err, hipMemcpyAsync(s->summary, d_sum, 5 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPE(*v.err, hipStreamSynchronize(st));
     return JAICOV_OK;
+}
+
+static int rel_run_impl(const QView &v, RelState *s, double s2t, const double *dx, const RelPointArgs *pa) {
+    const long n_ip = v.p->n_ip, n_rows = s->n_rows;
+    const hipStream_t st = v.stream;
+    DevBag w;
+    s->summary[5] = v.lambda;
+    HIPE(*v.err, s->out.reserve(std::max<size_t>(4 * (size_t)n_rows, 1)));   // the result belongs to the state
+    if (pa) {
+        HIPE(*v.err, s->points.reserve(std::max<size_t>(JAICOV_REL_POINT_COLUMNS * (size_t)n_ip, 1)));
+        s->n_points = n_ip;
+    }
+    if (n_rows == 0) return JAICOV_OK;
+    RelRun r{v, w, s2t, pa, n_rows, s->out.get(), s->points.get(), nullptr, nullptr, nullptr};
+    HIPE(*v.err, w.alloc(&r.d_dx, (size_t)v.U));
+    HIPE(*v.err, w.alloc(&r.d_v, 2 * (size_t)n_ip));
+    if (dx) HIPE(*v.err, hipMemcpyAsync(r.d_dx, dx, (size_t)v.U * sizeof(double), hipMemcpyHostToDevice, st));
+    else HIPE(*v.err, hipMemsetAsync(r.d_dx, 0, (size_t)v.U * sizeof(double), st));
+    if (n_ip > 0) {
+        const QImageBlocks ib = q_image_blocks(v);
+        if (!ib.new2old.empty()) {
+            HIPE(*v.err, w.alloc(&r.d_new2old, (size_t)n_ip));
+            HIPE(*v.err, hipMemcpyAsync(r.d_new2old, ib.new2old.data(), (size_t)n_ip * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIPE(*v.err, hipStreamSynchronize(st));        // ib is a host temporary
+        }
+        hipLaunchKernelGGL(rel_v_kernel, dim3((unsigned)((n_ip + 255) / 256)), dim3(256), 0, st, *v.p, v.rowsA, v.rowsW, r.d_dx, r.d_v);
+        HIPE(*v.err, hipGetLastError());
+        TRY(rel_run_points2x2(r, ib));
+        TRY(rel_run_dense(r, ib));
+    }
+    return rel_run_rest(r, s);
 }
 
 // The run once state and arguments are accepted: from here on the previous result goes.

@@ -13,10 +13,9 @@
 #include "ba_kernels.h"
 #include "gemm_f64.h"
 #include "launchers.h"
+#include "obsmodel.h"
 
 namespace jaicov {
-
-__device__ __forceinline__ int schur_shared_local(int c) { return c < 3 ? 3 + c : (c < 9 ? 6 + (c - 3) : 12 + (c - 9)); }
 
 // one workgroup per image block: E, n_E, L_E^-1, U, and G = U' [A_r,shared | w]
 __global__ __launch_bounds__(256) void blk_elim_kernel(DevProblem p, const int32_t *__restrict__ blk_list,
@@ -35,7 +34,7 @@ __global__ __launch_bounds__(256) void blk_elim_kernel(DevProblem p, const int32
     const int ipb = p.blk_ip_begin[g], mp = p.blk_ip_begin[g + 1] - ipb, m = 2 * mp;
     const long S = p.n_ip;
     const int img = p.ip_image[ipb], cam = p.image_camera[img];
-    const int kc = 9 + p.cam_dist_begin[cam + 1] - p.cam_dist_begin[cam];
+    const int kc = obs_kc(p, cam);
     if (tid < 42) red[tid] = 0.0;
     __syncthreads();
     {
@@ -130,7 +129,7 @@ __global__ __launch_bounds__(256) void blk_elim_kernel(DevProblem p, const int32
         const int c = tid & 31, rs = tid >> 5;
         if (c <= ncr) {
             const int cs = c < 3 ? c : c + 6;     // shared column index of reduced column c
-            const double *acol = c < ncr ? rowsA + (long)(2 * schur_shared_local(cs)) * S + ipb : rowsW + ipb;
+            const double *acol = c < ncr ? rowsA + (long)(2 * obs_shared_row(cs)) * S + ipb : rowsW + ipb;
             double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
             for (int row = rs; row < m; row += 8) {
                 const double a = acol[(long)(row & 1) * S + (row >> 1)];
@@ -209,7 +208,7 @@ __global__ __launch_bounds__(256) void blk_tfix_kernel(DevProblem p, const int32
     if (li >= n_list) return;
     const int ip = ip_list[li];
     const int img = p.ip_image[ip], cam = p.image_camera[img];
-    const int kc = 9 + p.cam_dist_begin[cam + 1] - p.cam_dist_begin[cam];
+    const int kc = obs_kc(p, cam);
     const int ncr = kc - 6;
     const double *u = Ubuf + ((long)2 * ip + r) * 8;
     const double *Gi = G + (long)img * 6 * SCHUR_GLD;

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/jaicov_vce.h"
+#include "obsmodel.h"
 #include "qview.h"
 #include "reliability.h"
 #include "status.h"
@@ -148,14 +149,8 @@ __global__ __launch_bounds__(256) void vce_small_kernel(DevProblem p, const uint
         if (p.ip_w3) {
             const double *w = p.ip_w3 + 3 * t;
             p00 = s0 * w[0]; p01 = s0 * w[1]; p11 = s0 * w[2];
-        } else {                                           // P = sigma0^2 inv(D) of the point as rel_points_kernel forms it
-            const double vx = p.ip_var_x[t], vy = p.ip_var_y[t], rh = p.ip_rho[t];
-            if (rh == 0) {
-                p00 = s0 / vx; p11 = s0 / vy; p01 = 0.0;
-            } else {
-                const double invDet = s0 / ((1.0 - rh * rh) * vx * vy);
-                p00 = invDet * vy; p11 = invDet * vx; p01 = -invDet * rh * sqrt(vx * vy);
-            }
+        } else {
+            obs_weight(p, (int)t, s0, p00, p01, p11);
         }
         const double v0 = v[2 * o], v1 = v[2 * o + 1];
         omega[o] = fma(p00 * v0, v0, fma(2.0 * p01 * v0, v1, p11 * v1 * v1));
@@ -352,37 +347,27 @@ extern "C" int jaicov_vce_run(jaicov_engine *e, double sigma2_test, const double
         FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "a group id must be -1 or 0 .. n_groups - 1");
     const long n_ip = p.n_ip, rows = 2 * n_ip + p.n_sb + p.n_dg_rows;
     if (rows > INT32_MAX) FAIL(*v.err, JAICOV_ERR_UNSUPPORTED, "more than 2^31 - 1 observation rows");
-    // engine position -> the caller's image point; the dense image blocks, each in one group
-    std::vector<int32_t> new2old;
-    if (!v.ip_old2new->empty()) {
-        new2old.resize(n_ip);
-        for (long o = 0; o < n_ip; o++) new2old[(*v.ip_old2new)[o]] = (int32_t)o;
-    }
-    std::vector<uint8_t> dense(n_ip, 0);
+    // the dense image blocks, each in one group
+    const QImageBlocks ib = q_image_blocks(v);
     std::vector<VceBlock> blocks;
     const std::vector<int32_t> &bb = *v.blk_ip_begin;
-    const std::vector<int64_t> &bw = *v.blk_w_off;
-    for (size_t g = 0; g + 1 < bb.size(); g++) {
-        if (bw[g] < 0 || bb[g + 1] <= bb[g]) continue;
+    for (const int32_t g : ib.blocks) {
         int32_t first = INT32_MAX;
-        for (int q = bb[g]; q < bb[g + 1]; q++) {
-            dense[q] = 1;
-            first = std::min(first, new2old.empty() ? q : new2old[q]);
-        }
+        for (int q = bb[g]; q < bb[g + 1]; q++) first = std::min(first, ib.caller(q));
         if (ip_group)
             for (int q = bb[g]; q < bb[g + 1]; q++)
-                if (ip_group[new2old.empty() ? q : new2old[q]] != ip_group[first]) {
+                if (ip_group[ib.caller(q)] != ip_group[first]) {
                     const long cb = v.caller_block->empty() ? (long)g : (long)(*v.caller_block)[g];
                     FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT,
                          "the image points of dense image block " + std::to_string(cb) + " name more than one group: a group is a union of weight blocks");
                 }
-        blocks.push_back(VceBlock{bw[g], 0, bb[g], 2 * (bb[g + 1] - bb[g]), first});
+        blocks.push_back(VceBlock{(*v.blk_w_off)[g], 0, bb[g], 2 * (bb[g + 1] - bb[g]), first});
     }
     // accepted: the reliability run, then the sums
     VceState *st = q_state(v.slot->vce);
     st->have = false;
     TRY(rel_run_plain(e, v, sigma2_test, dx, rows));
-    const int rc = vce_run_impl(v, st, ip_group, sb_group, dg_group, n_groups, new2old, dense, blocks);
+    const int rc = vce_run_impl(v, st, ip_group, sb_group, dg_group, n_groups, ib.new2old, ib.dense, blocks);
     if (rc != JAICOV_OK) {
         hipStreamSynchronize(v.stream);
         return rc;

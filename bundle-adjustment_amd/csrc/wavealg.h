@@ -19,9 +19,14 @@
 #include <math.h>
 #include <stdint.h>
 
+#ifdef JAICOV_OBSMODEL_H
+#error "wavealg.h after obsmodel.h: obs_weight would keep the engine's contraction in the start-value algebra"
+#endif
+#define JAICOV_WAVEALG_H
 #pragma clang fp contract(off)
 
-#include "rotation.h"      // below the pragma: R(omega, phi, kappa) with every product and sum rounded on its own
+#include "obsweight.h"     // below the pragma: obs_weight and
+#include "rotation.h"      // R(omega, phi, kappa) with every product and sum rounded on its own
 
 namespace jaicov {
 
@@ -315,17 +320,6 @@ __device__ inline void wave_eigen3(const double *S, double *lam, double *E) {
     lam[0] = a00; lam[1] = a11; lam[2] = a22;
 #pragma unroll
     for (int k = 0; k < 9; k++) E[k] = W[k];
-}
-
-// the weights of one observation (PDF:308-319) from its dispersions vx, vy, rho.  It takes the three values, not the array and an
-// index: the loads stay with the caller's other loads of the same index, and resect.hip's kernel keeps its register allocation.
-__device__ inline void obs_weight(double vx, double vy, double rho, double s0, double &p11, double &p12, double &p22) {
-    if (rho == 0.0) {
-        p11 = s0 / vx; p12 = 0.0; p22 = s0 / vy;
-    } else {
-        const double inv = s0 / ((1.0 - rho * rho) * vx * vy);
-        p11 = inv * vy; p22 = inv * vx; p12 = -inv * rho * sqrt(vx * vy);
-    }
 }
 
 // one step of the xor butterfly over (largest q, lowest index among equal values)
