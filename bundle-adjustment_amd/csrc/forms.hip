@@ -7,6 +7,8 @@
 //                     the end of a step.  The factorisation and the substitutions are the lane-parallel routines of wavealg.h
 //                     (wave_chol_lds, wave_forward_lds, wave_backward_lds, wave_trinv_lds); the system of the u <= 6 free
 //                     parameters is solved by every lane with wave_solve<6>.
+// Cylinders, cones and start values from the caller (include/jaicov_surfaces.h) are a second entry to the same kernel and the same host
+// shell: form_fit_kernel<.., SURF>, with the start search of the two surfaces in surfstart.h (surf_start_kernel) in front of it.
 // Nothing here writes to the cofactor matrix or to any other state of the engine but the work buffers of FormState.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -17,9 +19,11 @@
 #include <vector>
 
 #include "../../include/jaicov_forms.h"
+#include "../../include/jaicov_surfaces.h"
 #include "forms.h"
 #include "qview.h"
 #include "status.h"
+#include "surfstart.h"
 #include "wavealg.h"
 
 #pragma clang fp contract(off)
@@ -72,13 +76,17 @@ __device__ inline void form_untri(int n, int e, int &a, int &b) {
 // bits the host found.  One wave per workgroup: the precondition of the LDS routines of wavealg.h.
 // SERIAL (the hook of scripts/forms_bench.py): M is factorised by wave_solve_lds, where every lane repeats the whole serial solve, in
 // the place of wave_chol_lds; everything else is the same.
-template <bool SERIAL>
+// SURF (jaicov_surf_fit, include/jaicov_surfaces.h): the cylinder and the cone beside the four forms, and start [n][7], whose row g
+// holds the start values of form g in the reported order and the engine's frame unless its first entry is NaN.  Without SURF none
+// of that is compiled in and start is not read.
+template <bool SERIAL, bool SURF>
 __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__ Q, long ld, const double *__restrict__ vals,
                                                       const int32_t *__restrict__ ftype, const int32_t *__restrict__ fbegin,
                                                       const int32_t *__restrict__ fhost, const int32_t *__restrict__ fpoint,
-                                                      const int32_t *__restrict__ fcols, double sigma2, int max_it, double tol,
-                                                      double *__restrict__ out, double *__restrict__ qpp, double *__restrict__ mem_out,
-                                                      int32_t *__restrict__ status, int32_t *__restrict__ mem_status) {
+                                                      const int32_t *__restrict__ fcols, const double *__restrict__ start, double sigma2,
+                                                      int max_it, double tol, double *__restrict__ out, double *__restrict__ qpp,
+                                                      double *__restrict__ mem_out, int32_t *__restrict__ status,
+                                                      int32_t *__restrict__ mem_status) {
     __shared__ double U[FORM_TRI], Z[FORM_TRI];
     __shared__ double X[3][FORM_R], Vv[3][FORM_R], Bt[3][FORM_R], Bl[3][FORM_R], At[7][FORM_R], Sc[FORM_R], Sv[FORM_R], Lm[FORM_R];
     __shared__ double Nl[28], Jm[7][6];
@@ -87,10 +95,11 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
     const int type = wave_uniform(ftype[g]);
     const int m0 = wave_uniform(fbegin[g]), k = wave_uniform(fbegin[g + 1]) - m0;
     int st = wave_uniform(fhost[g]);
-    const int c = type >= JAICOV_FORM_LINE ? 2 : 1;
-    const int u = type == JAICOV_FORM_PLANE ? 3 : type == JAICOV_FORM_CIRCLE ? 6 : 4;
-    const int npar = type == JAICOV_FORM_LINE ? 6 : type == JAICOV_FORM_CIRCLE ? 7 : 4;
-    const int least = type == JAICOV_FORM_PLANE ? 3 : type == JAICOV_FORM_SPHERE ? 4 : type == JAICOV_FORM_LINE ? 2 : 3;
+    const bool cyl = SURF && type == JAICOV_SURF_CYLINDER, cone = SURF && type == JAICOV_SURF_CONE, surf = cyl || cone;
+    const int c = surf ? 1 : type >= JAICOV_FORM_LINE ? 2 : 1;
+    const int u = cyl ? 5 : cone ? 6 : type == JAICOV_FORM_PLANE ? 3 : type == JAICOV_FORM_CIRCLE ? 6 : 4;
+    const int npar = surf ? 7 : type == JAICOV_FORM_LINE ? 6 : type == JAICOV_FORM_CIRCLE ? 7 : 4;
+    const int least = surf ? u : type == JAICOV_FORM_PLANE ? 3 : type == JAICOV_FORM_SPHERE ? 4 : type == JAICOV_FORM_LINE ? 2 : 3;
     const int m = c * k;
     int iters = 0;
     auto ix = [m](int i, int j) { return tri_ix_n(m, i, j); };
@@ -134,7 +143,40 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
     // ---- start values
     double n[3] = {0.0, 0.0, 0.0}, pc[3] = {0.0, 0.0, 0.0}, pr = 0.0;       // n or t | c or x0 | r or d_c
     double e1[3] = {0.0, 0.0, 0.0}, e2[3] = {0.0, 0.0, 0.0};
-    {
+    bool given = false;
+    if (SURF) {
+        // a start row (the caller's, or the search's for a cylinder or a cone) is brought into working form
+        double sv[JAICOV_FORM_MAX_PARAMS];
+#pragma unroll
+        for (int a = 0; a < JAICOV_FORM_MAX_PARAMS; a++) sv[a] = start[(size_t)JAICOV_FORM_MAX_PARAMS * g + a];
+        given = wave_uniform(sv[0] == sv[0]);
+        if (!given && surf) { fail(JAICOV_FORM_DEGENERATE); return; }          // the search was left without a candidate
+        if (given) {
+            bool bad = false;
+            if (type == JAICOV_FORM_PLANE) {
+                n[0] = sv[0]; n[1] = sv[1]; n[2] = sv[2]; pr = sv[3];
+            } else {
+                pc[0] = sv[0] - G[0]; pc[1] = sv[1] - G[1]; pc[2] = sv[2] - G[2];
+                if (type == JAICOV_FORM_SPHERE) pr = sv[3];
+                else { n[0] = sv[3]; n[1] = sv[4]; n[2] = sv[5]; }
+                if (type == JAICOV_FORM_CIRCLE || surf) pr = sv[6];
+            }
+            if (type != JAICOV_FORM_SPHERE) {
+                const double l = sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+                bad = !(l > 0.0);
+                n[0] = n[0] / l; n[1] = n[1] / l; n[2] = n[2] / l;
+            }
+            if (type == JAICOV_FORM_PLANE) pr = pr - ((n[0] * G[0] + n[1] * G[1]) + n[2] * G[2]);
+            if (type == JAICOV_FORM_LINE || cyl) {
+                const double s = (n[0] * pc[0] + n[1] * pc[1]) + n[2] * pc[2];
+                pc[0] = pc[0] - s * n[0]; pc[1] = pc[1] - s * n[1]; pc[2] = pc[2] - s * n[2];
+            }
+            if (type == JAICOV_FORM_SPHERE || type == JAICOV_FORM_CIRCLE || cyl) bad = bad || !(pr > 0.0);
+            if (cone) bad = bad || !(pr > 0.0 && pr < M_PI);
+            if (wave_uniform(bad)) { fail(JAICOV_FORM_DEGENERATE); return; }
+        }
+    }
+    if (!given) {
         double lam[3], E[9];
         wave_eigen3<FORM_SWEEPS>(S, lam, E);
         if (type == JAICOV_FORM_PLANE || type == JAICOV_FORM_CIRCLE) {
@@ -145,7 +187,7 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
             n[0] = E[0]; n[1] = E[1]; n[2] = E[2];
         }
     }
-    if (type == JAICOV_FORM_SPHERE || type == JAICOV_FORM_CIRCLE) {
+    if (!given && (type == JAICOV_FORM_SPHERE || type == JAICOV_FORM_CIRCLE)) {
         // |q|^2 - 2 c.q + t = 0 in (c, t): rows [-2 q, 1], right-hand side -|q|^2; the circle has q = (e1.x, e2.x, 0) and N_22 = 1
         const bool circle = type == JAICOV_FORM_CIRCLE;
         if (circle) form_basis(n[0], n[1], n[2], e1, e2);
@@ -188,6 +230,8 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
         if (type != JAICOV_FORM_SPHERE) form_basis(n[0], n[1], n[2], e1, e2);
         x0l[0] = pc[0]; x0l[1] = pc[1]; x0l[2] = pc[2];
         double Br[3] = {0.0, 0.0, 0.0}, Ar[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, w = 0.0;
+        double ca = 0.0, sa = 0.0;                           // of the cone's alpha, held in pr
+        if (cone) { ca = cos(pr); sa = sin(pr); }
         if (lane < m) {
             const double v0 = Vv[0][mi], v1 = Vv[1][mi], v2 = Vv[2][mi];
             const double xh0 = X[0][mi] + v0, xh1 = X[1][mi] + v1, xh2 = X[2][mi] + v2;
@@ -214,6 +258,22 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
                     Ar[1] = -1.0; Ar[3] = -s;
                 }
                 f = (Br[0] * d0 + Br[1] * d1) + Br[2] * d2;
+            } else if (surf) {
+                const double s = (n[0] * d0 + n[1] * d1) + n[2] * d2;
+                const double p0 = d0 - s * n[0], p1 = d1 - s * n[1], p2 = d2 - s * n[2];
+                const double rho = sqrt((p0 * p0 + p1 * p1) + p2 * p2);
+                const double g0 = p0 / rho, g1 = p1 / rho, g2 = p2 / rho;
+                const double ge1 = (g0 * e1[0] + g1 * e1[1]) + g2 * e1[2], ge2 = (g0 * e2[0] + g1 * e2[1]) + g2 * e2[2];
+                if (cyl) {
+                    Br[0] = g0; Br[1] = g1; Br[2] = g2;
+                    Ar[0] = -ge1; Ar[1] = -ge2; Ar[2] = -(s * ge1); Ar[3] = -(s * ge2); Ar[4] = -1.0;
+                    f = rho - pr;
+                } else {
+                    const double q = s * ca + rho * sa;
+                    Br[0] = g0 * ca - n[0] * sa; Br[1] = g1 * ca - n[1] * sa; Br[2] = g2 * ca - n[2] * sa;
+                    Ar[0] = -Br[0]; Ar[1] = -Br[1]; Ar[2] = -Br[2]; Ar[3] = -(q * ge1); Ar[4] = -(q * ge2); Ar[5] = -q;
+                    f = rho * ca - s * sa;
+                }
             } else {
                 if (cq == 0) {
                     Br[0] = n[0]; Br[1] = n[1]; Br[2] = n[2];
@@ -355,6 +415,22 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
                 n[a] = (n[a] + dx[2] * e1[a]) + dx[3] * e2[a];
             }
             big = fmax(fmax(fabs(dx[0]) / ext, fabs(dx[1]) / ext), fmax(fabs(dx[2]), fabs(dx[3])));
+        } else if (cyl) {
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                pc[a] = (pc[a] + dx[0] * e1[a]) + dx[1] * e2[a];
+                n[a] = (n[a] + dx[2] * e1[a]) + dx[3] * e2[a];
+            }
+            pr = pr + dx[4];
+            big = fmax(fmax(fmax(fabs(dx[0]), fabs(dx[1])), fabs(dx[4])) / ext, fmax(fabs(dx[2]), fabs(dx[3])));
+        } else if (cone) {
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                pc[a] = pc[a] + dx[a];
+                n[a] = (n[a] + dx[3] * e1[a]) + dx[4] * e2[a];
+            }
+            pr = pr + dx[5];
+            big = fmax(fmax(fmax(fabs(dx[0]), fabs(dx[1])), fabs(dx[2])) / ext, fmax(fmax(fabs(dx[3]), fabs(dx[4])), fabs(dx[5])));
         } else {
 #pragma unroll
             for (int a = 0; a < 3; a++) {
@@ -368,12 +444,13 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
             const double l = sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
             n[0] = n[0] / l; n[1] = n[1] / l; n[2] = n[2] / l;
         }
-        if (type == JAICOV_FORM_LINE) {
+        if (type == JAICOV_FORM_LINE || cyl) {
             const double s = (n[0] * pc[0] + n[1] * pc[1]) + n[2] * pc[2];
             pc[0] = pc[0] - s * n[0]; pc[1] = pc[1] - s * n[1]; pc[2] = pc[2] - s * n[2];
         }
         const double chk = ((((big + omega) + pr) + ((n[0] + n[1]) + n[2])) + ((pc[0] + pc[1]) + pc[2])) * 0.0;
         if (wave_uniform(!(chk == 0.0))) { fail(JAICOV_FORM_NOT_FINITE); return; }
+        if (surf && wave_uniform(cyl ? !(pr > 0.0) : !(pr > 0.0 && pr < M_PI))) { fail(JAICOV_FORM_DEGENERATE); return; }
         if (wave_uniform(big <= tol)) { conv = true; break; }
         if (iters >= max_it) break;
     }
@@ -381,7 +458,8 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
 
     // ---- the sign rule, Q_pp = J N^-1 J' and the form's figures
     double sg = 1.0;
-    if (type != JAICOV_FORM_SPHERE) {
+    if (cone && pr > 0.5 * M_PI) sg = -1.0;                  // the cone's t turns with alpha, not by its largest component
+    if (type != JAICOV_FORM_SPHERE && !cone) {
         double bigc = n[0];
         if (fabs(n[1]) > fabs(bigc)) bigc = n[1];
         if (fabs(n[2]) > fabs(bigc)) bigc = n[2];
@@ -397,20 +475,22 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
             Jm[3][2] = sg;
         } else if (type == JAICOV_FORM_SPHERE) {
             for (int a = 0; a < 4; a++) Jm[a][a] = 1.0;
-        } else if (type == JAICOV_FORM_LINE) {
+        } else if (type == JAICOV_FORM_LINE || cyl) {
             const double s1 = (e1[0] * x0l[0] + e1[1] * x0l[1]) + e1[2] * x0l[2], s2 = (e2[0] * x0l[0] + e2[1] * x0l[1]) + e2[2] * x0l[2];
             for (int a = 0; a < 3; a++) {
                 Jm[a][0] = e1[a]; Jm[a][1] = e2[a]; Jm[a][2] = -s1 * n[a]; Jm[a][3] = -s2 * n[a];
                 Jm[3 + a][2] = sg * e1[a]; Jm[3 + a][3] = sg * e2[a];
             }
+            if (cyl) Jm[6][4] = 1.0;
         } else {
             for (int a = 0; a < 3; a++) { Jm[a][a] = 1.0; Jm[3 + a][3] = sg * e1[a]; Jm[3 + a][4] = sg * e2[a]; }
-            Jm[6][5] = 1.0;
+            Jm[6][5] = cone ? sg : 1.0;
         }
     }
     __syncthreads();
     n[0] = sg * n[0]; n[1] = sg * n[1]; n[2] = sg * n[2];
     if (type == JAICOV_FORM_PLANE) pr = sg * pr;
+    if (cone && sg < 0.0) pr = M_PI - pr;
     double *o = out + (size_t)JAICOV_FORM_COLUMNS * g;
     if (lane < JAICOV_FORM_QPP_COLUMNS) {
         int i, j;
@@ -439,7 +519,9 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
                 const double s = (n[0] * d0 + n[1] * d1) + n[2] * d2;
                 const double p0 = d0 - s * n[0], p1 = d1 - s * n[1], p2 = d2 - s * n[2];
                 const double perp = sqrt((p0 * p0 + p1 * p1) + p2 * p2);
-                dist = type == JAICOV_FORM_LINE ? perp : sqrt(s * s + (perp - pr) * (perp - pr));
+                if (cyl) dist = perp - pr;
+                else if (cone) dist = perp * cos(pr) - s * sin(pr);
+                else dist = type == JAICOV_FORM_LINE ? perp : sqrt(s * s + (perp - pr) * (perp - pr));
             }
         }
         Bl[0][lane] = dist;
@@ -459,7 +541,7 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
                 o[3] = pr;
             } else {
                 o[3] = n[0]; o[4] = n[1]; o[5] = n[2];
-                if (type == JAICOV_FORM_CIRCLE) o[6] = pr;
+                if (type == JAICOV_FORM_CIRCLE || surf) o[6] = pr;
             }
         }
         o[14] = omega;
@@ -512,7 +594,7 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
             Ti = (lam_r * a + l2 * b) / (2.0 * sigma2);
         }
     }
-    if (type != JAICOV_FORM_SPHERE) nab0 = sg * nab0;
+    if (type != JAICOV_FORM_SPHERE && !cyl) nab0 = sg * nab0;
     if (lane < m && cq == 0) {
         double *mo = mem_out + (size_t)JAICOV_FORM_MEMBER_COLUMNS * (m0 + mi);
         mo[0] = Vv[0][mi]; mo[1] = Vv[1][mi]; mo[2] = Vv[2][mi];
@@ -526,15 +608,20 @@ __global__ __launch_bounds__(64) void form_fit_kernel(const double *__restrict__
 
 using namespace jaicov;
 
-static int form_run(jaicov_engine *e, bool serial, double sigma2, int32_t n_forms, const int32_t *form_type, const int32_t *form_begin,
-                    const int32_t *form_point, int32_t max_iterations, double tol, double *out, double *qpp, double *member_out,
-                    int32_t *status, int32_t *member_status, float *ms_out) {
+// the three entries to the fit: jaicov_form_fit, its serial variant for the benchmark, and jaicov_surf_fit with `start` (may be NULL)
+enum FormEntry { FORM_ENTRY_FIT, FORM_ENTRY_SERIAL, FORM_ENTRY_SURF };
+
+static int form_run(jaicov_engine *e, FormEntry entry, double sigma2, int32_t n_forms, const int32_t *form_type, const int32_t *form_begin,
+                    const int32_t *form_point, const double *start, int32_t max_iterations, double tol, double *out, double *qpp,
+                    double *member_out, int32_t *status, int32_t *member_status, float *ms_out) {
+    const bool surf = entry == FORM_ENTRY_SURF;
+    const int last_type = surf ? JAICOV_SURF_CONE : JAICOV_FORM_CIRCLE;
     if (!e) return JAICOV_ERR_BAD_ARGUMENT;
     const QView v = q_view(e);
     TRY(q_guard(v, "forms on a sharded engine"));
     if (!form_type || !form_begin || !out || !status || n_forms < 0) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: NULL argument or a negative count");
     for (int g = 0; g < n_forms; g++)
-        if (form_type[g] < JAICOV_FORM_PLANE || form_type[g] > JAICOV_FORM_CIRCLE) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: unknown form type");
+        if (form_type[g] < JAICOV_FORM_PLANE || form_type[g] > last_type) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: unknown form type");
     if (!ranges_ok(n_forms, form_begin)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: form_begin must ascend from 0");
     const int n = n_forms, M = form_begin[n_forms];
     if (M > 0 && !form_point) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: NULL form_point");
@@ -549,6 +636,24 @@ static int form_run(jaicov_engine *e, bool serial, double sigma2, int32_t n_form
     if (!(sigma2 > 0.0)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: sigma2 must be positive");
     if (!(tol >= 0.0)) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: tol must not be negative");
     if (max_iterations < 1) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "forms: max_iterations must be at least 1");
+    // the start rows as the kernels read them: NaN in front where the form finds its own; does any cylinder or cone have to search?
+    static const int reported[] = {4, 4, 6, 7, 7, 7};
+    std::vector<double> rows;
+    bool search = false;
+    if (surf) {
+        rows.assign((size_t)JAICOV_FORM_MAX_PARAMS * std::max(n, 1), NAN);
+        for (int g = 0; g < n; g++) {
+            const double *row = start ? start + (size_t)JAICOV_FORM_MAX_PARAMS * g : nullptr;
+            if (!row || std::isnan(row[0])) {
+                search = search || form_type[g] >= JAICOV_SURF_CYLINDER;
+                continue;
+            }
+            for (int a = 0; a < reported[form_type[g]]; a++) {
+                if (!std::isfinite(row[a])) FAIL(*v.err, JAICOV_ERR_BAD_ARGUMENT, "surfaces: a start row holds a non-finite value behind its first entry");
+                rows[(size_t)JAICOV_FORM_MAX_PARAMS * g + a] = row[a];
+            }
+        }
+    }
     // type [n] | begin [n + 1] | status bits of the host [n] | point [M] | columns [3 M]
     const size_t Mx = (size_t)std::max(M, 1), o_begin = (size_t)n, o_host = o_begin + n + 1, o_point = o_host + n, o_cols = o_point + Mx,
                  n_tab = o_cols + 3 * Mx;
@@ -572,19 +677,25 @@ static int form_run(jaicov_engine *e, bool serial, double sigma2, int32_t n_form
     HIPE(*v.err, hipSetDevice(v.device));
     FormState *st = q_state(v.slot->form);
     HIPE(*v.err, st->tab.reserve(n_tab + n + Mx));
-    HIPE(*v.err, st->out.reserve((size_t)(JAICOV_FORM_COLUMNS + JAICOV_FORM_QPP_COLUMNS) * n + JAICOV_FORM_MEMBER_COLUMNS * Mx));
+    HIPE(*v.err, st->out.reserve((size_t)(JAICOV_FORM_COLUMNS + JAICOV_FORM_QPP_COLUMNS + JAICOV_FORM_MAX_PARAMS) * n + JAICOV_FORM_MEMBER_COLUMNS * Mx));
     int32_t *d_tab = st->tab.get(), *d_status = d_tab + n_tab, *d_mstatus = d_status + n;
-    double *d_out = st->out.get(), *d_qpp = d_out + (size_t)JAICOV_FORM_COLUMNS * n, *d_mem = d_qpp + (size_t)JAICOV_FORM_QPP_COLUMNS * n;
+    double *d_out = st->out.get(), *d_qpp = d_out + (size_t)JAICOV_FORM_COLUMNS * n, *d_mem = d_qpp + (size_t)JAICOV_FORM_QPP_COLUMNS * n,
+           *d_start = d_mem + JAICOV_FORM_MEMBER_COLUMNS * Mx;
     QTimer<2> timer(v.stream);
     HIPE(*v.err, timer.arm(ms_out != nullptr));
     HIPE(*v.err, hipMemcpyAsync(d_tab, tab.data(), n_tab * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+    if (surf) HIPE(*v.err, hipMemcpyAsync(d_start, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, v.stream));
     HIPE(*v.err, timer.mark(0));
-    if (serial)
-        hipLaunchKernelGGL(form_fit_kernel<true>, dim3(n), dim3(64), 0, v.stream, v.Q, v.ld, v.d_vals, d_tab, d_tab + o_begin, d_tab + o_host,
-                           d_tab + o_point, d_tab + o_cols, sigma2, max_iterations, tol, d_out, d_qpp, d_mem, d_status, d_mstatus);
+    if (surf) {
+        if (search) hipLaunchKernelGGL(surf_start_kernel, dim3(n), dim3(64), 0, v.stream, v.d_vals, d_tab, d_tab + o_begin, d_tab + o_point, d_start);
+        hipLaunchKernelGGL((form_fit_kernel<false, true>), dim3(n), dim3(64), 0, v.stream, v.Q, v.ld, v.d_vals, d_tab, d_tab + o_begin, d_tab + o_host,
+                           d_tab + o_point, d_tab + o_cols, d_start, sigma2, max_iterations, tol, d_out, d_qpp, d_mem, d_status, d_mstatus);
+    } else if (entry == FORM_ENTRY_SERIAL)
+        hipLaunchKernelGGL((form_fit_kernel<true, false>), dim3(n), dim3(64), 0, v.stream, v.Q, v.ld, v.d_vals, d_tab, d_tab + o_begin, d_tab + o_host,
+                           d_tab + o_point, d_tab + o_cols, (const double *)nullptr, sigma2, max_iterations, tol, d_out, d_qpp, d_mem, d_status, d_mstatus);
     else
-        hipLaunchKernelGGL(form_fit_kernel<false>, dim3(n), dim3(64), 0, v.stream, v.Q, v.ld, v.d_vals, d_tab, d_tab + o_begin, d_tab + o_host,
-                           d_tab + o_point, d_tab + o_cols, sigma2, max_iterations, tol, d_out, d_qpp, d_mem, d_status, d_mstatus);
+        hipLaunchKernelGGL((form_fit_kernel<false, false>), dim3(n), dim3(64), 0, v.stream, v.Q, v.ld, v.d_vals, d_tab, d_tab + o_begin, d_tab + o_host,
+                           d_tab + o_point, d_tab + o_cols, (const double *)nullptr, sigma2, max_iterations, tol, d_out, d_qpp, d_mem, d_status, d_mstatus);
     HIPE(*v.err, hipGetLastError());
     HIPE(*v.err, timer.mark(1));
     TRY(q_download(v, {{out, d_out, (size_t)JAICOV_FORM_COLUMNS * n * sizeof(double)},
@@ -599,12 +710,20 @@ static int form_run(jaicov_engine *e, bool serial, double sigma2, int32_t n_form
 extern "C" int jaicov_form_fit(jaicov_engine *e, double sigma2, int32_t n_forms, const int32_t *form_type, const int32_t *form_begin,
                                const int32_t *form_point, int32_t max_iterations, double tol, double *out, double *qpp, double *member_out,
                                int32_t *status, int32_t *member_status, float *ms_out) {
-    return form_run(e, false, sigma2, n_forms, form_type, form_begin, form_point, max_iterations, tol, out, qpp, member_out, status, member_status,
-                    ms_out);
+    return form_run(e, FORM_ENTRY_FIT, sigma2, n_forms, form_type, form_begin, form_point, nullptr, max_iterations, tol, out, qpp, member_out, status,
+                    member_status, ms_out);
+}
+
+extern "C" int jaicov_surf_fit(jaicov_engine *e, double sigma2, int32_t n_forms, const int32_t *form_type, const int32_t *form_begin,
+                               const int32_t *form_point, const double *start, int32_t max_iterations, double tol, double *out, double *qpp,
+                               double *member_out, int32_t *status, int32_t *member_status, float *ms_out) {
+    return form_run(e, FORM_ENTRY_SURF, sigma2, n_forms, form_type, form_begin, form_point, start, max_iterations, tol, out, qpp, member_out, status,
+                    member_status, ms_out);
 }
 
 // The hook of scripts/forms_bench.py: the same call with M factorised by wave_solve_lds in the place of wave_chol_lds.
 extern "C" int jaicov_debug_form_fit_serial(jaicov_engine *e, double sigma2, int32_t n_forms, const int32_t *form_type, const int32_t *form_begin,
                                             const int32_t *form_point, int32_t max_iterations, double tol, double *out, int32_t *status, float *ms_out) {
-    return form_run(e, true, sigma2, n_forms, form_type, form_begin, form_point, max_iterations, tol, out, nullptr, nullptr, status, nullptr, ms_out);
+    return form_run(e, FORM_ENTRY_SERIAL, sigma2, n_forms, form_type, form_begin, form_point, nullptr, max_iterations, tol, out, nullptr, nullptr, status,
+                    nullptr, ms_out);
 }

@@ -72,6 +72,11 @@ FORM_PARTIAL, FORM_TOO_SMALL, FORM_TOO_LARGE, FORM_DEGENERATE, FORM_SINGULAR, FO
 FORM_MEMBER_UNTESTED = 1
 FORM_MAX_ROWS, FORM_MAX_PARAMS, FORM_COLUMNS, FORM_QPP_COLUMNS, FORM_MEMBER_COLUMNS = 64, 7, 20, 28, 7
 FORM_REPORTED = (4, 4, 6, 7)      # parameters reported per kind: n d | c r | x0 t | c n r
+# include/jaicov_surfaces.h: cylinders and cones beside them, and start values from the caller for all six
+SURF_EXPORTS = ["jaicov_surf_fit"]
+SURF_CYLINDER, SURF_CONE = 4, 5
+SURF_KINDS = dict(FORM_KINDS, cylinder=SURF_CYLINDER, cone=SURF_CONE)
+SURF_REPORTED = FORM_REPORTED + (7, 7)      # x0 t r | apex t alpha
 # include/jaicov_predict.h: predicted image points with their ellipses and the test of check measurements, read from the cofactor matrix
 PRED_EXPORTS = ["jaicov_pred_points", "jaicov_pred_check"]
 PRED_PARTIAL, PRED_NEGATIVE, PRED_NOT_FINITE, PRED_OBSERVED, PRED_SINGULAR = 1, 2, 4, 8, 16     # status bits of a pair or a group
@@ -230,6 +235,7 @@ def load_library():
     L.jaicov_par_block.argtypes = [vp, _pi, C.c_int32, _pi, C.c_int32, _pd]
     L.jaicov_par_tests.argtypes = [vp, C.c_double, _pi, _pi, _pd, C.c_int32, _pd, _pi]
     L.jaicov_form_fit.argtypes = [vp, C.c_double, C.c_int32, _pi, _pi, _pi, C.c_int32, C.c_double, _pd, _pd, _pd, _pi, _pi, C.POINTER(C.c_float)]
+    L.jaicov_surf_fit.argtypes = [vp, C.c_double, C.c_int32, _pi, _pi, _pi, _pd, C.c_int32, C.c_double, _pd, _pd, _pd, _pi, _pi, C.POINTER(C.c_float)]
     L.jaicov_pred_points.argtypes = [vp, C.c_double, C.c_double, _pi, _pi, C.c_int32, _pd, _pi]
     L.jaicov_pred_check.argtypes = [vp, C.c_double, _pi, _pi, _pd, _pd, C.c_int32, _pi, C.c_int32, _pd, _pi, _pd, _pi]
     L.jaicov_newpt_intersect.argtypes = [vp, C.c_double, C.c_int32, _pi, _pi, _pd, _pd, _pd, C.c_int32, _pi, C.c_int32, _pd, _pi, _pi, _pd, _pd, _pi]
@@ -740,6 +746,34 @@ class Engine:
         self._chk(self.L.jaicov_form_fit(self._h, float(sigma2), n, kinds.ctypes.data_as(_pi), begin.ctypes.data_as(_pi),
                                          points.ctypes.data_as(_pi), int(max_iterations), float(tol), _p(out), _p(qpp), _p(mem),
                                          status.ctypes.data_as(_pi), mstatus.ctypes.data_as(_pi), C.byref(ms)))
+        return form_fits(out, qpp, mem[:M], status, mstatus[:M], begin, ms.value)
+
+    # cylinders, cones and start values from the caller (include/jaicov_surfaces.h) -------------------------------------------------
+    def fit_surfaces(self, sigma2, forms, start=None, max_iterations=20, tol=0.0):
+        """fit_forms with the kinds "cylinder" and "cone" (SURF_*) beside the four forms, and with start values: `start` is None or
+        one row per form (seven values, the reported parameters in the reported order and the engine's frame, whatever behind
+        them); None in the place of a row, or a row that begins with NaN, lets that form find its own.  Returns a FormFits; a cone's
+        seventh parameter is its half angle alpha."""
+        kinds = np.ascontiguousarray([SURF_KINDS.get(k, k) for k, _ in forms], np.int32)
+        members = [np.asarray(pts, np.int32).ravel() for _, pts in forms]
+        begin = np.concatenate([[0], np.cumsum([g.size for g in members])]).astype(np.int32)
+        points = np.ascontiguousarray(np.concatenate(members) if members else np.zeros(0), np.int32)
+        n, M = len(forms), int(points.size)
+        rows = None
+        if start is not None:
+            if len(start) != n:
+                raise ValueError("start must have one row per form")
+            rows = np.full((max(n, 1), FORM_MAX_PARAMS), np.nan)
+            for g, row in enumerate(start):
+                if row is not None:
+                    row = np.asarray(row, np.float64).ravel()
+                    rows[g, :min(row.size, FORM_MAX_PARAMS)] = row[:FORM_MAX_PARAMS]
+        out = np.zeros((n, FORM_COLUMNS)); qpp = np.zeros((n, FORM_QPP_COLUMNS)); mem = np.zeros((max(M, 1), FORM_MEMBER_COLUMNS))
+        status = np.zeros(n, np.int32); mstatus = np.zeros(max(M, 1), np.int32)
+        ms = C.c_float(0.0)
+        self._chk(self.L.jaicov_surf_fit(self._h, float(sigma2), n, kinds.ctypes.data_as(_pi), begin.ctypes.data_as(_pi),
+                                         points.ctypes.data_as(_pi), None if rows is None else _p(rows), int(max_iterations), float(tol),
+                                         _p(out), _p(qpp), _p(mem), status.ctypes.data_as(_pi), mstatus.ctypes.data_as(_pi), C.byref(ms)))
         return form_fits(out, qpp, mem[:M], status, mstatus[:M], begin, ms.value)
 
     # image space (include/jaicov_predict.h) ------------------------------------------------------------------------------------------

@@ -213,6 +213,17 @@ PYBIND11_MODULE(_jaicov_host, m) {
                                   py::array_t<int32_t>((py::ssize_t)f.memberStatus.size(), f.memberStatus.data()));
         }, py::arg("sigma2"), py::arg("formType"), py::arg("formBegin"), py::arg("formPoint"), py::arg("maxIterations") = 20, py::arg("tol") = 0.0,
              "(table (n, 20), qpp (n, 28), members (M, 7), status (n,), member status (M,)) of the forms through object points (include/jaicov_forms.h)")
+        .def("fitSurfaces", [](BundleAdjustment &b, double sigma2, std::vector<int32_t> formType, std::vector<int32_t> formBegin,
+                               std::vector<int32_t> formPoint, std::vector<double> start, int maxIterations, double tol) {
+            auto f = b.fitSurfaces(sigma2, formType, formBegin, formPoint, start, maxIterations, tol);
+            return py::make_tuple(py::array_t<double>({f.status.size(), (size_t)JAICOV_FORM_COLUMNS}, f.table.data()),
+                                  py::array_t<double>({f.status.size(), (size_t)JAICOV_FORM_QPP_COLUMNS}, f.qpp.data()),
+                                  py::array_t<double>({f.memberStatus.size(), (size_t)JAICOV_FORM_MEMBER_COLUMNS}, f.members.data()),
+                                  py::array_t<int32_t>((py::ssize_t)f.status.size(), f.status.data()),
+                                  py::array_t<int32_t>((py::ssize_t)f.memberStatus.size(), f.memberStatus.data()));
+        }, py::arg("sigma2"), py::arg("formType"), py::arg("formBegin"), py::arg("formPoint"), py::arg("start") = std::vector<double>(),
+             py::arg("maxIterations") = 20, py::arg("tol") = 0.0,
+             "the tuple of fitForms for the types 0 .. 5 (cylinders and cones), with start values (n x 7, flat) or none (include/jaicov_surfaces.h)")
         .def("predictImagePoints", [](BundleAdjustment &b, double sigma2, std::vector<int32_t> images, std::vector<int32_t> points, double k2) {
             auto t = b.predictImagePoints(sigma2, images, points, k2);
             return py::make_tuple(py::array_t<double>({t.status.size(), (size_t)t.columns}, t.table.data()),

@@ -640,6 +640,32 @@ BundleAdjustment::FormFits BundleAdjustment::fitForms(double sigma2, const std::
     return f;
 }
 
+// include/jaicov_surfaces.h on the engine of the last estimateModel
+BundleAdjustment::FormFits BundleAdjustment::fitSurfaces(double sigma2, const std::vector<int32_t> &formType, const std::vector<int32_t> &formBegin,
+                                                         const std::vector<int32_t> &formPoint, const std::vector<double> &start, int maxIterations,
+                                                         double tol) const {
+    requireCofactorOnEngine(engine_, hasCofactorMatrix());
+    if (formBegin.size() != formType.size() + 1 || formBegin.back() != (int32_t)formPoint.size())
+        throw std::runtime_error("fitSurfaces: formBegin must have one entry more than formType and end at formPoint.size()");
+    if (!start.empty() && start.size() != formType.size() * JAICOV_FORM_MAX_PARAMS)
+        throw std::runtime_error("fitSurfaces: start must be empty or hold seven values per form");
+    FormFits f;
+    const size_t n = formType.size(), M = formPoint.size();
+    f.table.resize(std::max<size_t>(n, 1) * JAICOV_FORM_COLUMNS);
+    f.qpp.resize(std::max<size_t>(n, 1) * JAICOV_FORM_QPP_COLUMNS);
+    f.members.resize(std::max<size_t>(M, 1) * JAICOV_FORM_MEMBER_COLUMNS);
+    f.status.resize(std::max<size_t>(n, 1));
+    f.memberStatus.resize(std::max<size_t>(M, 1));
+    int32_t none = 0;
+    const int rc = jaicov_surf_fit(engine_, sigma2, (int32_t)n, formType.empty() ? &none : formType.data(), formBegin.data(),
+                                   formPoint.empty() ? &none : formPoint.data(), start.empty() ? nullptr : start.data(), maxIterations, tol,
+                                   f.table.data(), f.qpp.data(), f.members.data(), f.status.data(), f.memberStatus.data(), nullptr);
+    if (rc != JAICOV_OK) throw std::runtime_error(std::string("jaicov_surf_fit: ") + jaicov_neq_last_error(engine_));
+    f.table.resize(n * JAICOV_FORM_COLUMNS); f.qpp.resize(n * JAICOV_FORM_QPP_COLUMNS); f.members.resize(M * JAICOV_FORM_MEMBER_COLUMNS);
+    f.status.resize(n); f.memberStatus.resize(M);
+    return f;
+}
+
 // include/jaicov_predict.h on the engine of the last estimateModel
 BundleAdjustment::ImageTable BundleAdjustment::predictImagePoints(double sigma2, const std::vector<int32_t> &images, const std::vector<int32_t> &points,
                                                                   double k2) const {

@@ -40,6 +40,7 @@
 #include "../../include/jaicov_precision.h"
 #include "../../include/jaicov_parameters.h"
 #include "../../include/jaicov_forms.h"
+#include "../../include/jaicov_surfaces.h"
 #include "../../include/jaicov_predict.h"
 #include "../../include/jaicov_newpoints.h"
 #include "../../include/jaicov_vce.h"
@@ -599,6 +600,11 @@ public:
     };
     FormFits fitForms(double sigma2, const std::vector<int32_t> &formType, const std::vector<int32_t> &formBegin,
                       const std::vector<int32_t> &formPoint, int maxIterations = 20, double tol = 0.0) const;
+    // The same with cylinders and cones (JAICOV_SURF_*) and with start values (include/jaicov_surfaces.h): start is empty or holds
+    // seven values per form, the reported parameters in the engine's frame; a row that begins with NaN lets the form find its own.
+    FormFits fitSurfaces(double sigma2, const std::vector<int32_t> &formType, const std::vector<int32_t> &formBegin,
+                         const std::vector<int32_t> &formPoint, const std::vector<double> &start = {}, int maxIterations = 20,
+                         double tol = 0.0) const;
     // Image space (include/jaicov_predict.h), read on the device from the cofactor matrix of the last estimateModel; needs
     // MatrixInversion.FULL.  A pair is (image, point): the images in the order of flat.eo_col, ObjectCoordinate::index.
     // predictImagePoints: where the adjusted point appears in the image, with J Qxx J', sigmas and the ellipse (rows of JAICOV_PRED_POINT_COLUMNS).
